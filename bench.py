@@ -27,7 +27,8 @@ all-reduce of the per-shard lnL per step (E: of the partitionCount per-partition
 csrc/sharded.cpp: one engine instance per GPU on its own host thread, ncclAllReduce of the root sums); with the default
 `--route ranks` rank 0 appends a shorter run of that route to the line as "library_route" (configs A-D).
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  `--dump-outputs DIR`: after the timed steps, what the last of them computed goes to DIR/<name>.npy
+(dump_outputs), so that two builds given the same arguments — the same seeded inputs — can be compared output for output.
 """
 import argparse
 import hashlib
@@ -40,6 +41,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 TIMER_EVERY = 4            # the engine's HIP-event kernel timer brackets every 4th evaluation of a timed region (bench_single)
+DUMP_LIMIT_BYTES = 64 << 20      # --dump-outputs: at most this many bytes of arrays in all
 HBM_PEAK_GBS = 8000.0      # MI355X HBM3E spec peak (MI355X_MICROARCH.md: 8.0 TB/s; ~6.3 TB/s achievable with a copy kernel)
 KERNEL_SOURCES = ("kernels_walk4.hip", "walk4_fast_loop.inc", "kernels_mfma.hip", "kernels.hip", "planner.cpp", "engine_walk.cpp", "engine_levels.cpp", "engine_instance.cpp")
 
@@ -51,6 +53,88 @@ def kernel_source_hash():
         with open(os.path.join(ROOT, "beast-mcmc_amd", "csrc", f), "rb") as fh:
             h.update(fh.read())
     return h.hexdigest()[:16]
+
+
+def default_cache_dir():
+    """The generated workloads' directory: one per user under the temporary directory (a machine's /tmp is shared, and a
+    directory another user made is not writable by this one)."""
+    import tempfile
+    return os.path.join(tempfile.gettempdir(), "beagle_mi355_cache-%d" % os.getuid())
+
+
+def workload_cache_file(cache_dir, config, scale, tree):
+    """The pickle of one generated workload, named after the sources that generate it (beast-mcmc_amd/inputs/): a file written
+    by another version of the generator is never read back as this version's inputs.  None = no cache (--cache '', or a
+    directory that cannot be made)."""
+    if not cache_dir:
+        return None
+    try:
+        os.makedirs(cache_dir, exist_ok=True)
+    except OSError:
+        return None
+    h = hashlib.sha256()
+    src = os.path.join(ROOT, "beast-mcmc_amd", "inputs")
+    for f in sorted(os.listdir(src)):
+        if f.endswith(".py"):
+            with open(os.path.join(src, f), "rb") as fh:
+                h.update(f.encode() + b"\0" + fh.read())
+    return os.path.join(cache_dir, "wl_%s_%g_%s_%s.pkl" % (config, scale, tree, h.hexdigest()[:12]))
+
+
+def load_workload(cache, maker):
+    """The workload from its cache file, or ``maker()`` (seeded: the same inputs every time) written to it.  A cache file that
+    cannot be read or written costs only the cache; a write that fails leaves no partial file behind."""
+    import pickle
+    if cache:
+        try:
+            with open(cache, "rb") as fh:
+                return pickle.load(fh)
+        except (OSError, EOFError, pickle.UnpicklingError):
+            pass
+    wl = maker()
+    if cache:
+        tmp = "%s.%d.tmp" % (cache, os.getpid())
+        try:
+            with open(tmp, "wb") as fh:
+                pickle.dump(wl, fh, protocol=4)
+            os.replace(tmp, cache)
+        except OSError:
+            try:
+                os.remove(tmp)
+            except OSError:
+                pass
+    return wl
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: what the timed path computed in its last step, one ``path/<name>.npy`` per array, float64.  DUMP_LIMIT_BYTES
+    in all: an array larger than its share is replaced by a fixed, seeded sample of its entries (the same indices every run, in
+    increasing order).  -> {name: entries written}"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = (DUMP_LIMIT_BYTES - 4096 * len(arrays)) // max(1, len(arrays))
+    written = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(np.atleast_1d(np.asarray(a, dtype=np.float64)).ravel())
+        keep = share // a.itemsize
+        if a.size > keep:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+        written[name] = int(a.size)
+    return written
+
+
+def gather_ranks(dist, a, part_counts=None):
+    """One rank's per-pattern array -> the whole alignment's, in the alignment's pattern order whatever the rank count.  A rank
+    holds one contiguous block of the patterns, or (config E, `part_counts` = this rank's patterns per partition) one block of
+    every partition's patterns, partition after partition: the blocks are put back partition by partition."""
+    import numpy as np
+    if dist is None:
+        return a
+    rows = [None] * dist.get_world_size()
+    dist.all_gather_object(rows, (np.asarray(a), list(part_counts or [len(a)])))
+    pieces = [np.split(r, np.cumsum(c)[:-1]) for r, c in rows]        # per rank: one piece per partition
+    return np.concatenate([p[k] for k in range(len(pieces[0])) for p in pieces])
 
 
 def prune_bytes_per_eval(wl):
@@ -115,7 +199,7 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--patterns", type=int, default=0, help="development: keep only the first N patterns (size of one shard of an N-GPU job)")
     ap.add_argument("--force-sharded", action="store_true", help="development: take the multi-GPU code path (process group, device-side sum, all-reduce) even with one rank")
-    ap.add_argument("--cache", default="/tmp/beagle_mi355_cache", help="directory for the generated workload ('' = off)")
+    ap.add_argument("--cache", default=default_cache_dir(), help="directory for the generated workload ('' = off)")
     ap.add_argument("--cpu-sample", type=int, default=0, help="patterns in the CPU-baseline sample (0 = sized for ~10-20 s of CPU work)")
     ap.add_argument("--rescaling", default="dynamic", choices=["dynamic", "always", "none"],
                     help="dynamic (default, the metric's protocol): steady state = read mode, every 100th evaluation recomputes the factors; "
@@ -135,9 +219,14 @@ def main():
                     help="do not append the other BASELINE configs (B, C, D on the reference's benchmark1 alignment, E) to the default line")
     ap.add_argument("--selftest-launcher", action="store_true",
                     help="CPU check of the N-rank bring-up only (gloo, no engine, no GPU): tests/test_host_and_abi.py")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float64, 64 MB at most in all): "
+                         "lnL, site_lnL (per pattern), and for config E partition_lnL")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.route == "ranks" and args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(args.gpus))          # started plainly: bring up the N ranks ourselves
     if args.selftest_launcher:
@@ -186,15 +275,13 @@ def main():
               "C": lambda: bm.synth.config_c(scale=args.scale),
               "D": lambda: bm.synth.config_d(categories=1),
               "E": lambda: bm.synth.config_e(scale=args.scale)}
-    if args.cache:
-        os.makedirs(args.cache, exist_ok=True)
-    cache = os.path.join(args.cache, "wl_%s_%g_%s.pkl" % (args.config, args.scale, args.tree)) if args.cache else None
+    cache = workload_cache_file(args.cache, args.config, args.scale, args.tree)
     if cache and world > 1 and rank != 0:
         dist.barrier()                                  # rank 0 generates, the others read its file
     if args.real:
         args.config, cache = "D", None
         makers["D"] = lambda: bm.synth.from_pattern_fixture(os.path.join(ROOT, "tests", "golden", args.real + "_patterns.npz"))
-    wl = bm.synth.cached(cache, makers[args.config])
+    wl = load_workload(cache, makers[args.config])
     if cache and world > 1 and rank == 0:
         dist.barrier()
     t_gen = time.time() - t_gen
@@ -571,6 +658,13 @@ def bench_single(args, bm, wl, rank, world, dist, device, res, t_gen, sharded, S
         timed_calls = timed_calls_cached if dist is not None else max(1, raw.kernelTimerCalls())
     evals_per_s = args.steps / elapsed
     counters = local.counters()
+    dumped = None
+    if args.dump_outputs:
+        # the last timed step's values, read back after the clock stopped: its lnL and its per-pattern log-likelihoods (what
+        # getSiteLogLikelihoods returns after that evaluation — every step of `--caller btl`)
+        site = gather_ranks(dist, local.getSiteLogLikelihoods())
+        if rank == 0:
+            dumped = {"dir": args.dump_outputs, "arrays": dump_outputs(args.dump_outputs, {"lnL": [lnl], "site_lnL": site})}
 
     out = None
     if rank == 0:
@@ -664,6 +758,8 @@ def bench_single(args, bm, wl, rank, world, dist, device, res, t_gen, sharded, S
             "evaluations_total": int(local.counters()["evaluations"]),
             "kernel_source_hash": kernel_source_hash(), "workload_generation_s": round(t_gen, 1),
         }
+        if dumped:
+            out["dumped_outputs"] = dumped
     tl.close()
     return out
 
@@ -892,10 +988,12 @@ def bench_partitioned(args, bm, pw, rank, world, dist, device, res, t_gen):
     k = len(pw.parts)
     buf = torch.zeros(k, dtype=torch.float64, device=device)
     rates0 = np.ones(pw.tree.node_count)
+    last = [None]                                       # the last step's per-partition values (--dump-outputs)
 
     def step(i):
         tl.set_branch_rates(rates0 * (1.0 + 1e-6 * (i & 1)))       # a clock-rate move: every matrix of every partition changes
         by_part, total = tl.calculate()
+        last[0] = by_part
         if dist is not None:
             buf.copy_(torch.from_numpy(by_part))
             dist.all_reduce(buf, op=dist.ReduceOp.SUM)
@@ -920,6 +1018,15 @@ def bench_partitioned(args, bm, pw, rank, world, dist, device, res, t_gen):
     stats["fused_cherries"] = tl.b.walkLaunchInfo()["fused_cherries"]
     kernel_ms, _ = tl.b.kernelTimer(False)
     timed_calls = max(1, tl.b.kernelTimerCalls())
+    dumped = None
+    if args.dump_outputs:
+        # the last timed step's values: the total, the per-partition values (all-reduced over the ranks, as the step summed
+        # them) and the per-pattern log-likelihoods of that evaluation (in the alignment's pattern order: gather_ranks)
+        parts = buf.cpu().numpy() if dist is not None else last[0]
+        site = gather_ranks(dist, tl.getSiteLogLikelihoods(), local_pw.pattern_counts)
+        if rank == 0:
+            dumped = {"dir": args.dump_outputs,
+                      "arrays": dump_outputs(args.dump_outputs, {"lnL": [lnl], "partition_lnL": parts, "site_lnL": site})}
     out = None
     if rank == 0:
         p_, c_ = local_pw.pattern_count, tl.C
@@ -961,6 +1068,8 @@ def bench_partitioned(args, bm, pw, rank, world, dist, device, res, t_gen):
             "cpu_baseline": cpu, "partial_update": partial, "lnL": lnl, "lnL_first_eval": lnl0, "kernel_source_hash": kernel_source_hash(),
             "evaluations_total": tl.evaluations, "workload_generation_s": round(t_gen, 1),
         }
+        if dumped:
+            out["dumped_outputs"] = dumped
     tl.close()
     return out
 
