@@ -123,7 +123,7 @@ ABI_SYMBOLS = ["beagleGetVersion", "beagleGetCitation", "beagleGetResourceList",
                "beagleGetPartitionApiTable"] + \
               ["beagle" + k for k in _PROTOS] + \
               ["beagleMi355SetStream", "beagleMi355CalculateRootLogLikelihoodsDevice", "beagleMi355Synchronize",
-               "beagleMi355KernelTimer", "beagleMi355DeviceBytes", "beagleMi355WalkStats", "beagleMi355GradientStats", "beagleMi355GetPartialsBatch",
+               "beagleMi355KernelTimer", "beagleMi355DeviceBytes", "beagleMi355WalkStats", "beagleMi355GradientStats", "beagleMi355GetPartialsBatch", "beagleMi355SampleAncestralStates",
                "beagleMi355GetPartialsPinned", "beagleMi355GetSiteLogLikelihoodsPinned",
                "beagleMi355KernelTimerCalls", "beagleMi355WalkHealth", "beagleMi355WalkLaunchInfo", "beagleMi355RootFusedCount", "beagleMi355SitePrefetchCount", "beagleMi355KernelTimerRestart", "beagleMi355GetDimensions", "beagleMi355GetCommUniqueId", "beagleMi355CommInit", "beagleMi355CommInfo", "beagleMi355CalculateRootLogLikelihoodsAllReduce"]
 
@@ -513,6 +513,20 @@ class Beagle:
         f = self._ext("beagleMi355GetPartialsBatch", [C.c_int, _IP, _IP, C.c_int, _DP])
         self._check("getPartialsBatch", f(self.instance, _ip(b), _ip(sc), len(b), _dp(out)))
         return out.reshape(len(b), self.categoryCount, self.patternCount, self.stateCount)
+
+    def sampleAncestralStates(self, nodes, categoryWeightsIndex, stateFrequenciesIndex, seed, map=False):
+        """One draw of every listed node's state per pattern on the device (include/beagle_mi355.h beagleMi355SampleAncestralStates).
+        ``nodes``: [nodeCount][3] rows {bufferIndex, matrixIndex, parentRow}, the root first.  -> (states uint8 [nodeCount, P],
+        categories int32 [P]).  A draw whose total weight was not finite and > 0 raises BeagleException with code -8
+        (FLOATING_POINT_ERROR)."""
+        rows = _i(nodes).reshape(-1, 3)
+        states = np.empty((rows.shape[0], self.patternCount), dtype=np.uint8)
+        cats = np.zeros(self.patternCount, dtype=np.int32)
+        f = self._ext("beagleMi355SampleAncestralStates", [C.c_int, _IP, C.c_int, C.c_int, C.c_int, C.c_ulonglong, C.c_int,
+                                                           C.c_void_p, _IP])
+        self._check("sampleAncestralStates", f(self.instance, _ip(rows), rows.shape[0], categoryWeightsIndex, stateFrequenciesIndex,
+                                               int(seed) & 0xFFFFFFFFFFFFFFFF, 1 if map else 0, states.ctypes.data, _ip(cats)))
+        return states, cats
 
     def walkStats(self):
         """Counters of the 4-state pattern walk since the last kernelTimer call (include/beagle_mi355.h)."""

@@ -812,6 +812,91 @@ int beagleMi355GetPartialsBatch(int instance, const int* bufferIndices, const in
     return exportPartials(in, bufferIndices, scaleIndices, count, outPartials);
 }
 
+// One draw of every listed node's state per pattern (include/beagle_mi355.h beagleMi355SampleAncestralStates; what
+// AncestralStateBeagleTreeLikelihood.traverseSample computes from a getPartials per internal node and a getTransitionMatrix per
+// branch, AncestralStateBeagleTreeLikelihood.java:414-625).  Virtual buffers are materialised by one walk, as for a read-back; the
+// draw itself is ONE launch (kernels_ancestral.hip), then the states and categories come back in two copies.  The instance's
+// patterns are patterns pOffset .. pOffset + P - 1 of an alignment of globalP (the sharded handle): the random numbers are keyed
+// on the global pattern, and row r's states land at outStates + r * globalP + pOffset.
+static int sampleAncestral(Instance* in, const int* nodes, int nodeCount, int wIdx, int fIdx, unsigned long long seed, int flags,
+                           int globalP, int pOffset, unsigned char* outStates, int* outCategories) {
+    if (in->partitionCount > 1) return BEAGLE_ERROR_NO_IMPLEMENTATION;
+    if (badIndex(wIdx, in->eigenCount) || badIndex(fIdx, in->eigenCount)) return BEAGLE_ERROR_OUT_OF_RANGE;
+    std::vector<int> need;
+    for (int r = 0; r < nodeCount; r++) {
+        const int b = nodes[3 * r], m = nodes[3 * r + 1], parent = nodes[3 * r + 2];
+        if (badIndex(b, in->partialsCount)) return BEAGLE_ERROR_OUT_OF_RANGE;
+        if (r == 0 && isCompactTip(in, b)) return BEAGLE_ERROR_OUT_OF_RANGE;
+        if (r > 0 && (badIndex(m, in->matrixCount) || parent < 0 || parent >= r)) return BEAGLE_ERROR_OUT_OF_RANGE;
+        if (isVirt(in, b)) in->planner.keysOf(b, need);
+    }
+    if (!need.empty()) { int rc = materializeList(in, need); if (rc) return rc; }
+    const size_t n = (size_t)in->C * in->S * in->S;
+    std::vector<mi355::AncestralRow> rows(nodeCount);
+    for (int r = 0; r < nodeCount; r++) {
+        const int b = nodes[3 * r];
+        mi355::AncestralRow& row = rows[r];
+        row.partials = nullptr; row.states = nullptr; row.pad = 0;
+        if (isCompactTip(in, b)) row.states = in->tipStates[b];
+        else if (in->partials[b]) row.partials = in->partials[b];
+        else return BEAGLE_ERROR_OUT_OF_RANGE;                 // a buffer nothing was ever written to
+        row.matrix = r == 0 ? nullptr : in->matrices + n * nodes[3 * r + 1];
+        row.parent = r == 0 ? -1 : nodes[3 * r + 2];
+    }
+    const size_t stateBytes = ((size_t)nodeCount * in->P + 255) & ~(size_t)255;
+    const size_t tailBytes = (size_t)in->P * sizeof(int) + sizeof(unsigned);
+    if (in->ancestralBytes < stateBytes + tailBytes) {
+        if (in->ancestralDev) {
+            HIP_TRY(hipStreamSynchronize(live(in)));
+            in->allocations.erase(std::find(in->allocations.begin(), in->allocations.end(), (void*)in->ancestralDev));
+            in->deviceBytes -= in->ancestralBytes;
+            hipFree(in->ancestralDev);
+            in->ancestralDev = nullptr; in->ancestralBytes = 0;
+        }
+        int rc = devAlloc(in, (void**)&in->ancestralDev, stateBytes + tailBytes); if (rc) return rc;
+        in->ancestralBytes = stateBytes + tailBytes;
+    }
+    uint8_t* dStates = (uint8_t*)in->ancestralDev;
+    int* dCats = (int*)(in->ancestralDev + stateBytes);
+    unsigned* dError = (unsigned*)(dCats + in->P);
+    void* dRows = nullptr;
+    int rc = uploadTransient(in, rows.data(), rows.size() * sizeof(mi355::AncestralRow), &dRows); if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(dError, 0, sizeof(unsigned), live(in)));
+    mi355::launchSampleAncestral(live(in), (const mi355::AncestralRow*)dRows, nodeCount, in->weights + (size_t)wIdx * in->C,
+                                 in->freqs + (size_t)fIdx * in->S, in->P, in->S, in->C, in->tiled, globalP, pOffset, seed,
+                                 (flags & BEAGLE_MI355_ANCESTRAL_MAP) != 0, dStates, dCats, dError);
+    HIP_TRY(hipGetLastError());
+    if (globalP == in->P)
+        HIP_TRY(hipMemcpyAsync(outStates, dStates, (size_t)nodeCount * in->P, hipMemcpyDeviceToHost, live(in)));
+    else
+        HIP_TRY(hipMemcpy2DAsync(outStates + pOffset, (size_t)globalP, dStates, (size_t)in->P, (size_t)in->P, (size_t)nodeCount,
+                                 hipMemcpyDeviceToHost, live(in)));
+    std::vector<int> tail(in->P + 1);
+    rc = download(in, tail.data(), dCats, tailBytes); if (rc) return rc;
+    if (outCategories) memcpy(outCategories + pOffset, tail.data(), (size_t)in->P * sizeof(int));
+    unsigned err; memcpy(&err, &tail[in->P], sizeof(unsigned));
+    return err ? BEAGLE_ERROR_FLOATING_POINT : BEAGLE_SUCCESS;
+}
+
+int beagleMi355SampleAncestralStates(int instance, const int* nodes, int nodeCount, int categoryWeightsIndex, int stateFrequenciesIndex,
+                                     unsigned long long seed, int flags, unsigned char* outStates, int* outRateCategories) {
+    if (!nodes || nodeCount < 1 || !outStates) return BEAGLE_ERROR_OUT_OF_RANGE;
+    if (mi355::isShardedHandle(instance)) {
+        // every shard draws its own pattern range into its columns of the caller's arrays
+        const int globalP = mi355::shardedPatternCount(instance);
+        return mi355::shardedBroadcast(instance, [&](int h) {
+            int pStart = 0, pEnd = 0;
+            mi355::shardedBoundsOfHandle(instance, h, &pStart, &pEnd);
+            GET_INSTANCE(h);
+            return sampleAncestral(in, nodes, nodeCount, categoryWeightsIndex, stateFrequenciesIndex, seed, flags, globalP, pStart,
+                                   outStates, outRateCategories);
+        });
+    }
+    GET_INSTANCE(instance);
+    return sampleAncestral(in, nodes, nodeCount, categoryWeightsIndex, stateFrequenciesIndex, seed, flags, in->P, 0, outStates,
+                           outRateCategories);
+}
+
 // MI355X extensions for the JNI shim: the result stays in the engine's pinned bounce buffer (valid until the next call on the
 // instance) and goes from there into the Java array with ONE copy.  Not for the sharded instance (NO_IMPLEMENTATION: the
 // shim then takes the ordinary entry point).

@@ -187,6 +187,8 @@ struct Instance {
     // read-back (getPartials): API-layout export buffers on the device and a pinned bounce buffer on the host
     double* exportDev[2] = {nullptr, nullptr}; double* exportHost[2] = {nullptr, nullptr}; size_t exportBytes = 0;   // two chunks in flight
     hipEvent_t exportEvent[2] = {nullptr, nullptr};
+    // ancestral-state draws (beagleMi355SampleAncestralStates): states [rows][P] | categories [P] | error word, grown on demand
+    char* ancestralDev = nullptr; size_t ancestralBytes = 0;
     long statMicroOps = 0, statStored = 0, statMemReads = 0, statTipReads = 0, statScaleReads = 0, statWalks = 0, statScaleWrites = 0;   // since the last timer reset
     hipStream_t stream = nullptr, ownStream = nullptr;
     int tipCount = 0, partialsCount = 0, compactCount = 0, S = 0, P = 0, eigenCount = 0, matrixCount = 0, C = 0, scaleCount = 0;

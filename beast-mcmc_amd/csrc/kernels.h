@@ -470,6 +470,22 @@ int  rootSiteTiledBlocks(int patterns);      // entries launchRootSiteTiled writ
 void launchRootSiteTiled(hipStream_t stream, const double* root, const double* catWeights, const double* freqs,
                          const double* cum, int cumIsRaw, const double* patternWeights, double* siteLogL,
                          double* blockSums, int P, int S, int C, int pStart, int pEnd);
+// ---- ancestral states (kernels_ancestral.hip; beagleMi355SampleAncestralStates) -----------------------------------------
+// One row of the pre-order node list, resolved on the host: the node's partials (plain [C][P][S] or T32) OR its compact tip states
+// (uint8 [P], value >= S = unknown), its branch matrix [C][S][S] (nullptr at the root) and the row of its parent (-1 at the root).
+struct AncestralRow {
+    const double*  partials;
+    const uint8_t* states;
+    const double*  matrix;
+    int            parent;
+    int            pad;
+};
+// states[row][p] (uint8) and cats[p] (may be nullptr) for the instance's P patterns, ONE launch; the random numbers are keyed on
+// the global pattern pOffset + p of an alignment of globalP patterns (a shard of the sharded handle draws what one instance would).
+// *fpError |= 1 when some draw's total weight was not finite and > 0 (the state is then 0).
+void launchSampleAncestral(hipStream_t stream, const AncestralRow* dRows, int nRows, const double* catWeights, const double* freqs,
+                           int P, int S, int C, bool tiled, int globalP, int pOffset, unsigned long long seed, bool map,
+                           uint8_t* states, int* cats, unsigned* fpError);
 // out[0] = sum of n block sums in a fixed order
 void launchRootFinal(hipStream_t stream, const double* blockSums, int n, double* out, unsigned long long* flag = nullptr,
                      unsigned long long seq = 0);

@@ -55,6 +55,7 @@ def host_library():
         lib.btlLastError.argtypes = [C.c_void_p]
         lib.btlRootBufferIndex.argtypes = [C.c_void_p]
         lib.btlNodeBufferIndex.argtypes = [C.c_void_p, C.c_int]
+        lib.btlNodeMatrixIndex.argtypes = [C.c_void_p, C.c_int]
         lib.btlNodeScaleIndex.argtypes = [C.c_void_p, C.c_int]
         lib.btlCumulativeScaleIndex.argtypes = [C.c_void_p]
         lib.btlCounters.argtypes = [C.c_void_p, C.POINTER(C.c_long)]
@@ -218,6 +219,10 @@ class BeagleTreeLikelihood:
 
     def node_buffer_index(self, node):
         return self.h.btlNodeBufferIndex(self.ptr, node)
+
+    def node_matrix_index(self, node):
+        """The matrix buffer that holds node's branch matrix now (the caller's double buffering: BufferIndexHelper)."""
+        return self.h.btlNodeMatrixIndex(self.ptr, node)
 
     def node_scale_index(self, node):
         return self.h.btlNodeScaleIndex(self.ptr, node)

@@ -330,6 +330,26 @@ int beagleMi355CommInfo(int instance, int* outRanks);
  * layout conversion, pinned copies, one synchronisation per 256 MiB — for hosts that read many nodes per sample
  * (AncestralStateBeagleTreeLikelihood.java:414-542); the per-buffer beagleGetPartials takes the same path with count 1. */
 int beagleMi355GetPartialsBatch(int instance, const int* bufferIndices, const int* scaleIndices, int count, double* outPartials);
+/* Ancestral states: ONE draw of every listed node's state per pattern, on the device — what AncestralStateBeagleTreeLikelihood
+ * .traverseSample computes from a getPartials per internal node and a getTransitionMatrix per branch
+ * (AncestralStateBeagleTreeLikelihood.java:414-625; linear-space conditionals, marginal mode).
+ *   nodes: nodeCount triples {bufferIndex, matrixIndex, parentRow} in pre-order — row 0 is the root {rootBuffer, ignored, -1},
+ *          every other row names its branch matrix and a parentRow smaller than its own.  A buffer may hold partials (internal
+ *          node, or a tip set with setTipPartials) or compact tip states (not at the root); a compact state >= stateCount is
+ *          drawn from the matrix row alone.
+ *   outStates: [nodeCount][patternCount] bytes, row r = nodes[r];  outRateCategories: [patternCount] or NULL.
+ *   flags: BEAGLE_MI355_ANCESTRAL_MAP = argmax instead of a draw (useMAP).
+ * Rate category (C > 1) drawn from (sum_k rootPartial[c][p][k]) * categoryWeight[c]; root state from rootPartial[c*][p][i] * freq[i];
+ * other rows from partial[c*][p][i] * M[c*][parentState][i].  Every draw is randomChoicePDF (MathUtils.java:82-104) with
+ * u = SplitMix64 output number ctr + 1 from state `seed`, ctr = (row * patternCount + p) * 2 + kind (kind 1: the root's rate
+ * category), u = (z >> 11) * 2^-53 — stateless, so a host can restate every draw; the sharded handle (resource G+1) keys it on the
+ * global pattern and returns a single instance's states byte for byte.  Stored partials are read as they are (rescaling does not
+ * change any draw).  BEAGLE_ERROR_OUT_OF_RANGE for a bad index, parent row or root, nodeCount < 1 or outStates == NULL;
+ * BEAGLE_ERROR_NO_IMPLEMENTATION on an instance with more than one pattern partition; BEAGLE_ERROR_FLOATING_POINT when some
+ * draw's total weight was not finite and > 0 — that state is 0 and every other draw is still made. */
+#define BEAGLE_MI355_ANCESTRAL_MAP 1
+int beagleMi355SampleAncestralStates(int instance, const int* nodes, int nodeCount, int categoryWeightsIndex, int stateFrequenciesIndex,
+                                     unsigned long long seed, int flags, unsigned char* outStates, int* outRateCategories);
 /* For the JNI shim: getPartials / getSiteLogLikelihoods whose result STAYS in the engine's pinned host buffer — *outPinned,
  * *outCount doubles, valid until the next call on the instance — so that it reaches the Java array with one copy
  * (Set<Type>ArrayRegion) instead of two.  BEAGLE_ERROR_NO_IMPLEMENTATION on the sharded instance: use the ordinary call. */

@@ -509,6 +509,7 @@ int btlGetSiteLogLikelihoods(void* h, double* out) {
 int btlLastError(void* h) { return ((TreeLikelihood*)h)->lastError; }
 int btlRootBufferIndex(void* h) { TreeLikelihood* t = (TreeLikelihood*)h; return t->partialBufferHelper.getOffsetIndex(t->root); }
 int btlNodeBufferIndex(void* h, int node) { return ((TreeLikelihood*)h)->partialBufferHelper.getOffsetIndex(node); }
+int btlNodeMatrixIndex(void* h, int node) { return ((TreeLikelihood*)h)->matrixBufferHelper.getOffsetIndex(node); }
 int btlNodeScaleIndex(void* h, int node) { TreeLikelihood* t = (TreeLikelihood*)h; return t->scaleBufferIndices[node - t->tipCount]; }
 int btlCumulativeScaleIndex(void* h) {
     TreeLikelihood* t = (TreeLikelihood*)h;
