@@ -10,8 +10,10 @@ using namespace mi355::eng;
 
 namespace {
 
+// part < 0: the whole pattern range (every partition's)
 int accumulate(Instance* in, const int* idx, int count, int cum, double sign, int part) {
-    if (badIndex(cum, in->scaleCount) || badIndex(part, in->partitionCount)) return BEAGLE_ERROR_OUT_OF_RANGE;
+    if (badIndex(cum, in->scaleCount) || (part >= 0 && badIndex(part, in->partitionCount))) return BEAGLE_ERROR_OUT_OF_RANGE;
+    const int pStart = part < 0 ? 0 : in->partStart[part], pEnd = part < 0 ? in->P : in->partEnd[part];
     int rc = materializeScaleUsers(in, cum); if (rc) return rc;
     rc = ensureScale(in, cum); if (rc) return rc;
     if (in->scaleIsRaw[cum]) return BEAGLE_ERROR_OUT_OF_RANGE;
@@ -30,7 +32,7 @@ int accumulate(Instance* in, const int* idx, int count, int cum, double sign, in
             void* dRows = nullptr;
             rc = uploadTransient(in, in->lastSums.rows.data(), in->lastSums.rows.size() * sizeof(int), &dRows); if (rc) return rc;
             mi355::launchAccumulateSlices(live(in), in->scale[cum], in->sliceMant, in->sliceExp, (const int*)dRows, (int)in->lastSums.rows.size(), in->pairLen,
-                                          in->dPairPos, sign, in->partStart[part], in->partEnd[part]);
+                                          in->dPairPos, sign, pStart, pEnd);
             in->statSliceAccum++;
             HIP_TRY(hipGetLastError());
             return 0;
@@ -49,8 +51,7 @@ int accumulate(Instance* in, const int* idx, int count, int cum, double sign, in
         void *dSrc = nullptr, *dRaw = nullptr;
         rc = uploadTransient(in, &srcs[b], (size_t)n * sizeof(double*), &dSrc); if (rc) return rc;
         rc = uploadTransient(in, &raw[b], (size_t)n * sizeof(int), &dRaw); if (rc) return rc;
-        mi355::launchAccumulateScale(live(in), in->scale[cum], (const double* const*)dSrc, (const int*)dRaw, n, sign,
-                                     in->partStart[part], in->partEnd[part]);
+        mi355::launchAccumulateScale(live(in), in->scale[cum], (const double* const*)dSrc, (const int*)dRaw, n, sign, pStart, pEnd);
     }
     HIP_TRY(hipGetLastError());
     return 0;
@@ -122,6 +123,12 @@ int rootEnqueue(Instance* in, int rootIdx, int wIdx, int fIdx, int cumIdx, int p
         const Instance::PendingWalk& pw = in->pendingWalk;
         int seg = -1;
         for (size_t i = 0; i < pw.finalStore.size(); i++) if (pw.finalStore[i] == rootIdx) seg = (int)i;
+        // (a partitioned instance's walk — held for the by-partition root call — finishes this whole-range root only if the slice's
+        // partition IS the whole range: otherwise live() launches the walk as it is and the plain root kernel below covers [0, P))
+        if (seg >= 0 && in->partitionCount > 1) {
+            const int k = pw.finalPart[(size_t)seg];
+            if (in->partStart[k] != 0 || in->partEnd[k] != in->P) seg = -1;
+        }
         if (seg >= 0) {
             mi355::RootFused rf;
             memset(&rf, 0, sizeof(rf));
@@ -1212,6 +1219,21 @@ int beagleUpdatePartials(int instance, const int* operations, int operationCount
             in->scaleOfPartial[op[0]] = (sIdx != BEAGLE_OP_NONE && !badIndex(sIdx, in->scaleCount)) ? sIdx : -1;
             in->scaleVersionAtWrite[op[0]] = in->scaleOfPartial[op[0]] >= 0 ? in->scaleVersion[sIdx] : 0u;
         }
+    if (operations && operationCount > 0 && in->partitionCount > 1) {
+        // a partitioned instance: a 7-int list covers every pattern — it runs as the same list of 9-int tuples, each operation once per
+        // (non-empty) partition in a row, the cumulative index on every tuple (include/beagle_mi355.h)
+        std::vector<int> ops9;
+        ops9.reserve((size_t)operationCount * in->partitionCount * BEAGLE_PARTITION_OP_COUNT);
+        for (int k = 0; k < operationCount; k++) {
+            const int* op = operations + (size_t)k * BEAGLE_OP_COUNT;
+            for (int part = 0; part < in->partitionCount; part++) {
+                if (in->partEnd[part] <= in->partStart[part]) continue;
+                ops9.insert(ops9.end(), op, op + BEAGLE_OP_COUNT);
+                ops9.push_back(part); ops9.push_back(cumulativeScaleIndex);
+            }
+        }
+        return runOperations(in, ops9.data(), (int)(ops9.size() / BEAGLE_PARTITION_OP_COUNT), BEAGLE_PARTITION_OP_COUNT, BEAGLE_OP_NONE);
+    }
     return runOperations(in, operations, operationCount, BEAGLE_OP_COUNT, cumulativeScaleIndex);
 }
 
@@ -1249,7 +1271,7 @@ int beagleAccumulateScaleFactors(int instance, const int* scaleIndices, int coun
     if (mi355::isShardedHandle(instance)) { std::vector<int> v(scaleIndices, scaleIndices + std::max(0, count)); return mi355::shardedPost(instance, [=](int h) { return beagleAccumulateScaleFactors(h, v.data(), count, cumulativeScaleIndex); }); }
     GET_INSTANCE_KEEP_PENDING(instance);          // (scale buffers only: nothing a held-back pre-order list reads or writes)
     if (!badIndex(cumulativeScaleIndex, in->scaleCount)) in->scaleVersion[cumulativeScaleIndex]++;
-    return accumulate(in, scaleIndices, count, cumulativeScaleIndex, 1.0, 0);
+    return accumulate(in, scaleIndices, count, cumulativeScaleIndex, 1.0, -1);
 }
 int beagleAccumulateScaleFactorsByPartition(int instance, const int* scaleIndices, int count, int cumulativeScaleIndex, int partitionIndex) {
     if (mi355::isShardedHandle(instance)) { std::vector<int> v(scaleIndices, scaleIndices + std::max(0, count)); return mi355::shardedPost(instance, [=](int h) { return beagleAccumulateScaleFactorsByPartition(h, v.data(), count, cumulativeScaleIndex, partitionIndex); }); }
@@ -1261,7 +1283,7 @@ int beagleRemoveScaleFactors(int instance, const int* scaleIndices, int count, i
     if (mi355::isShardedHandle(instance)) { std::vector<int> v(scaleIndices, scaleIndices + std::max(0, count)); return mi355::shardedPost(instance, [=](int h) { return beagleRemoveScaleFactors(h, v.data(), count, cumulativeScaleIndex); }); }
     GET_INSTANCE_KEEP_PENDING(instance);          // (scale buffers only: nothing a held-back pre-order list reads or writes)
     if (!badIndex(cumulativeScaleIndex, in->scaleCount)) in->scaleVersion[cumulativeScaleIndex]++;
-    return accumulate(in, scaleIndices, count, cumulativeScaleIndex, -1.0, 0);
+    return accumulate(in, scaleIndices, count, cumulativeScaleIndex, -1.0, -1);
 }
 int beagleRemoveScaleFactorsByPartition(int instance, const int* scaleIndices, int count, int cumulativeScaleIndex, int partitionIndex) {
     if (mi355::isShardedHandle(instance)) { std::vector<int> v(scaleIndices, scaleIndices + std::max(0, count)); return mi355::shardedPost(instance, [=](int h) { return beagleRemoveScaleFactorsByPartition(h, v.data(), count, cumulativeScaleIndex, partitionIndex); }); }

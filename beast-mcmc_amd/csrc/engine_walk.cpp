@@ -138,7 +138,10 @@ int runPlan(Instance* in, const mi355::Plan& plan, long planTag, hipEvent_t reco
     const bool fused = in->fuseWaves && in->fastWalk && !in->walkT && plan.launchOrder.size() == plan.segs.size();
     const bool asmLoop = in->fastWalk && !in->walkT;          // k_walk4_fast runs this program (otherwise k_walk4 / k_walkT32)
     // ... on tickets when its slices form a forest: the slices without dependencies first (they are the launch's grid), in launch order
-    const bool ticket = fused && in->useTickets && plan.leaves > 0;
+    bool ticket = fused && in->useTickets && plan.leaves > 0;
+    // (a slice without micro-operations leaves the kernel before it counts itself in at its next slice, which would then never run and
+    // whose ticket words would stay non-zero for the next launch: such a program runs on flags)
+    for (size_t i = 0; i < plan.segs.size() && ticket; i++) if (plan.segs[i].progCount <= 0) ticket = false;
     std::vector<int> order;
     if (fused) {
         order = plan.launchOrder;

@@ -211,7 +211,10 @@ int beagleUpdateTransitionMatricesWithMultipleModels(int instance, const int* ei
 /* updatePartials (I[III)I — BeagleTreeLikelihood.java:1003, BeagleDataLikelihoodDelegate.java:904.
  * operations = int[7*count]: {dest, writeScale, readScale, child1, matrix1, child2, matrix2}
  * (tuple built at BeagleTreeLikelihood.java:1266-1299).  The list must be dependency ordered;
- * it need not be level ordered (the engine levelises it). */
+ * it need not be level ordered (the engine levelises it).  On an instance with several pattern partitions
+ * the list covers every pattern: it runs as the 9-int list that names each operation once per non-empty
+ * partition, in a row, with cumulativeScaleIndex as every tuple's cumulative index.  Whole-range
+ * accumulate/remove/resetScaleFactors and calculateRootLogLikelihoods likewise cover all P patterns. */
 int beagleUpdatePartials(int instance, const int* operations, int operationCount, int cumulativeScaleIndex);
 /* updatePartialsByPartition (I[II)I — int[9*count]:
  * {dest, writeScale, readScale, child1, matrix1, child2, matrix2, partition, cumulativeScale} */

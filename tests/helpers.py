@@ -6,7 +6,8 @@ import numpy as np
 
 import beast_mcmc_amd as bm
 import reference_quantile
-from beast_mcmc_amd.inputs import patterns, siterates, substmodel, trees
+from beast_mcmc_amd.inputs import patterns, siterates, substmodel, synth, trees
+from beast_mcmc_amd.inputs.siterates import GammaSiteRateModel
 from beast_mcmc_amd.inputs.synth import Workload
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -134,3 +135,28 @@ def walk_stats(tl):
     raw = bm.beagle.Beagle.__new__(bm.beagle.Beagle)
     raw.lib, raw._f, raw.instance = tl.engine, tl.engine.fn, tl.instance
     return raw.walkStats()
+
+
+def two_partitions(S, T, sizes, seed):
+    """One tree and len(sizes) partitions of it, partition k with its own model (gamma shape 0.4 + 0.5 k) and sizes[k] unique
+    patterns simulated on the tree, 3 % of the tip states unknown."""
+    rng = np.random.default_rng(seed)
+    wls = []
+    tree = None
+    for k, n in enumerate(sizes):
+        if S == 4:
+            pi = rng.dirichlet(np.full(4, 8.0))
+            eig = substmodel.gtr(rng.gamma(2.0, 1.0, size=6) + 0.1, pi)
+        else:
+            eig, pi = substmodel.random_reversible(S, rng)
+        if tree is None:
+            wl = synth.make_workload("part0", T, n, eig, pi, alpha=0.4 + 0.5 * k, categories=4, seed=seed)
+            tree = wl.tree
+        else:
+            rates, props = GammaSiteRateModel(alpha=0.4 + 0.5 * k, gamma_categories=4).category_rates_and_proportions()
+            tips = synth.simulate_unique_patterns(tree, eig, np.asarray(pi), rates, props, n, rng).astype(np.int32)
+            tips[rng.random(tips.shape) < 0.03] = S
+            wl = Workload("part%d" % k, tree, eig, pi, rates, props, np.ascontiguousarray(tips),
+                          rng.integers(1, 9, size=n).astype(np.float64), S)
+        wls.append(wl)
+    return tree, wls

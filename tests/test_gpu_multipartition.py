@@ -9,42 +9,18 @@ import pytest
 
 import beast_mcmc_amd as bm
 import helpers
-from beast_mcmc_amd.inputs import substmodel, synth
-from beast_mcmc_amd.inputs.siterates import GammaSiteRateModel
+from beast_mcmc_amd.inputs import substmodel
 from beast_mcmc_amd.treelikelihood import BeagleTreeLikelihood, RESCALE_ALWAYS, RESCALE_NONE
 
 pytestmark = pytest.mark.gpu
 NONE = bm.beagle.NONE
 
 
-def two_partitions(S, T, sizes, seed):
-    rng = np.random.default_rng(seed)
-    wls = []
-    tree = None
-    for k, n in enumerate(sizes):
-        if S == 4:
-            pi = rng.dirichlet(np.full(4, 8.0))
-            eig = substmodel.gtr(rng.gamma(2.0, 1.0, size=6) + 0.1, pi)
-        else:
-            eig, pi = substmodel.random_reversible(S, rng)
-        if tree is None:
-            wl = synth.make_workload("part0", T, n, eig, pi, alpha=0.4 + 0.5 * k, categories=4, seed=seed)
-            tree = wl.tree
-        else:
-            rates, props = GammaSiteRateModel(alpha=0.4 + 0.5 * k, gamma_categories=4).category_rates_and_proportions()
-            tips = synth.simulate_unique_patterns(tree, eig, np.asarray(pi), rates, props, n, rng).astype(np.int32)
-            tips[rng.random(tips.shape) < 0.03] = S
-            wl = synth.Workload("part%d" % k, tree, eig, pi, rates, props, np.ascontiguousarray(tips),
-                                rng.integers(1, 9, size=n).astype(np.float64), S)
-        wls.append(wl)
-    return tree, wls
-
-
 @pytest.mark.parametrize("S", [4, 20, 61])
 @pytest.mark.parametrize("scaling", [False, True])
 def test_multi_partition_protocol(S, scaling, oracle_lib):
     T = 9
-    tree, wls = two_partitions(S, T, [150, 77], seed=40 + S)
+    tree, wls = helpers.two_partitions(S, T, [150, 77], seed=40 + S)
     K = len(wls)
     P = sum(w.pattern_count for w in wls)
     nodes = 2 * T - 1
@@ -115,7 +91,7 @@ def test_partitioned_instance_partial_updates_with_per_partition_flips(S, oracle
     (300, 77 and 140 patterns) do not end at tile boundaries — a tile of 32 patterns that straddles two partitions is walked
     once per partition (kernels_mfma.hip k_walkT32)."""
     T, C = 24, 4
-    tree, wls = two_partitions(S, T, [300, 77, 140], seed=77)
+    tree, wls = helpers.two_partitions(S, T, [300, 77, 140], seed=77)
     K = len(wls)
     P = sum(w.pattern_count for w in wls)
     nodes = 2 * T - 1

@@ -44,3 +44,48 @@ def test_moves_and_rejections_on_one_partition(oracle_lib):
     _, again = tl.calculate()
     assert helpers.rel_err(again, fresh(pw.parts[0], oracle_lib)) <= 1e-13
     tl.close()
+
+
+def test_per_partition_references_add_up_to_the_unpartitioned_one(oracle_lib):
+    """The reference of tests/test_gpu_partition_sequences.py: with one model shared by every partition, the per-partition oracle
+    instances' log-likelihoods add up to — and their site values in a row are — those of one unpartitioned instance over all
+    patterns, with and without write-mode rescaling.  (A wrong reference must not pass a wrong engine.)"""
+    import beast_mcmc_amd as bm
+    from beast_mcmc_amd.inputs.synth import Workload
+    NONE = bm.beagle.NONE
+    for S, sizes in ((4, [37, 5, 130, 64, 1, 77, 33, 129, 20]), (20, [150, 77])):
+        tree, wls = helpers.two_partitions(S, 10, sizes, seed=5 + S)
+        m = wls[0]
+        wls = [Workload(w.name, w.tree, m.eig, m.freqs, m.cat_rates, m.cat_weights, w.tip_states, w.weights, S) for w in wls]
+        T, nodes = 10, 19
+        internal = [n for n in tree.postorder() if n >= T]
+        branches = [n for n in range(nodes) if n != tree.root]
+        for scaling in (False, True):
+            def evaluate(tips, weights):
+                b = bm.beagle.Beagle(T, nodes, T, S, len(weights), 1, nodes, 4, T, library=oracle_lib)
+                try:
+                    for t in range(T):
+                        b.setTipStates(t, tips[t])
+                    b.setPatternWeights(weights)
+                    b.setEigenDecomposition(0, m.eig.evec, m.eig.ievc, m.eig.evals)
+                    b.setCategoryRates(m.cat_rates)
+                    b.setCategoryWeights(0, m.cat_weights)
+                    b.setStateFrequencies(0, m.freqs)
+                    b.updateTransitionMatrices(0, branches, None, None, [tree.branch_length(n) for n in branches], len(branches))
+                    ops = []
+                    for n in internal:
+                        l, r = int(tree.left[n]), int(tree.right[n])
+                        ops += [n, n - T if scaling else NONE, NONE, l, l, r, r]
+                    if scaling:
+                        b.resetScaleFactors(T - 1)
+                    b.updatePartials(ops, len(internal), T - 1 if scaling else NONE)
+                    v = [0.0]
+                    b.calculateRootLogLikelihoods([tree.root], [0], [0], [T - 1 if scaling else NONE], 1, v)
+                    return v[0], b.getSiteLogLikelihoods()
+                finally:
+                    b.finalize()
+            parts = [evaluate(w.tip_states, w.weights) for w in wls]
+            whole = evaluate(np.concatenate([w.tip_states for w in wls], axis=1), np.concatenate([w.weights for w in wls]))
+            assert helpers.rel_err(sum(v for v, _ in parts), whole[0]) <= 1e-12, (S, scaling)
+            site = np.concatenate([s for _, s in parts])
+            assert np.max(np.abs(site - whole[1]) / np.abs(whole[1])) <= 1e-12, (S, scaling)
