@@ -123,7 +123,7 @@ ABI_SYMBOLS = ["beagleGetVersion", "beagleGetCitation", "beagleGetResourceList",
                "beagleGetPartitionApiTable"] + \
               ["beagle" + k for k in _PROTOS] + \
               ["beagleMi355SetStream", "beagleMi355CalculateRootLogLikelihoodsDevice", "beagleMi355Synchronize",
-               "beagleMi355KernelTimer", "beagleMi355DeviceBytes", "beagleMi355WalkStats", "beagleMi355GradientStats", "beagleMi355GetPartialsBatch", "beagleMi355SampleAncestralStates",
+               "beagleMi355KernelTimer", "beagleMi355DeviceBytes", "beagleMi355WalkStats", "beagleMi355GradientStats", "beagleMi355GetPartialsBatch", "beagleMi355SampleAncestralStates", "beagleMi355SampleMarkovJumps",
                "beagleMi355GetPartialsPinned", "beagleMi355GetSiteLogLikelihoodsPinned",
                "beagleMi355KernelTimerCalls", "beagleMi355WalkHealth", "beagleMi355WalkLaunchInfo", "beagleMi355RootFusedCount", "beagleMi355SitePrefetchCount", "beagleMi355KernelTimerRestart", "beagleMi355GetDimensions", "beagleMi355GetCommUniqueId", "beagleMi355CommInit", "beagleMi355CommInfo", "beagleMi355CalculateRootLogLikelihoodsAllReduce"]
 
@@ -527,6 +527,47 @@ class Beagle:
         self._check("sampleAncestralStates", f(self.instance, _ip(rows), rows.shape[0], categoryWeightsIndex, stateFrequenciesIndex,
                                                int(seed) & 0xFFFFFFFFFFFFFFFF, 1 if map else 0, states.ctypes.data, _ip(cats)))
         return states, cats
+
+    def sampleMarkovJumps(self, nodes, branchTimes, branchRates, eigenIndex, categoryRatesIndex, categoryWeightsIndex,
+                          stateFrequenciesIndex, registers, registerFlags, seed, map=False, states=False, jumps=False,
+                          pattern_totals=True, row_totals=True):
+        """One ancestral draw plus the expected Markov-jump counts / rewards of every register on every row and pattern
+        (include/beagle_mi355.h beagleMi355SampleMarkovJumps).  ``nodes``: as for sampleAncestralStates; ``branchTimes`` [nodeCount]
+        (parent height - child height), ``branchRates`` [nodeCount] or None (all 1); ``registers`` [K][S][S]; ``registerFlags`` [K]
+        (JUMPS_REWARDS | JUMPS_SCALE_BY_TIME).  -> dict of what was asked for: "states" uint8 [nodeCount, P] and "categories"
+        int32 [P] (states=True), "jumps" [K, nodeCount, P], "pattern_totals" [K, P], "row_totals" [K, nodeCount].  A failed draw
+        or a value that is not finite raises BeagleException with code -8."""
+        rows = _i(nodes).reshape(-1, 3)
+        n, P = rows.shape[0], self.patternCount
+        regs = _d(registers).reshape(-1, self.stateCount, self.stateCount)
+        K = regs.shape[0]
+        flags = _i(registerFlags).reshape(-1)
+        times = _d(branchTimes).reshape(-1)
+        rates = None if branchRates is None else _d(branchRates).reshape(-1)
+        if times.shape[0] != n or (rates is not None and rates.shape[0] != n) or flags.shape[0] != K:
+            raise ValueError("branchTimes, branchRates and registerFlags must have one entry per row / register")
+        out = {}
+        if states:
+            out["states"] = np.empty((n, P), dtype=np.uint8)
+            out["categories"] = np.zeros(P, dtype=np.int32)
+        if jumps:
+            out["jumps"] = np.empty((K, n, P))
+        if pattern_totals:
+            out["pattern_totals"] = np.empty((K, P))
+        if row_totals:
+            out["row_totals"] = np.empty((K, n))
+
+        def ptr(key):
+            return out[key].ctypes.data if key in out else None
+
+        f = self._ext("beagleMi355SampleMarkovJumps", [C.c_int, _IP, C.c_int, _DP, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                       _DP, _IP, C.c_int, C.c_ulonglong, C.c_int, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p, C.c_void_p, C.c_void_p])
+        self._check("sampleMarkovJumps", f(self.instance, _ip(rows), n, _dp(times), None if rates is None else rates.ctypes.data,
+                                           eigenIndex, categoryRatesIndex, categoryWeightsIndex, stateFrequenciesIndex, _dp(regs),
+                                           _ip(flags), K, int(seed) & 0xFFFFFFFFFFFFFFFF, 1 if map else 0, ptr("states"),
+                                           ptr("categories"), ptr("jumps"), ptr("pattern_totals"), ptr("row_totals")))
+        return out
 
     def walkStats(self):
         """Counters of the 4-state pattern walk since the last kernelTimer call (include/beagle_mi355.h)."""

@@ -819,14 +819,27 @@ int beagleMi355GetPartialsBatch(int instance, const int* bufferIndices, const in
     return exportPartials(in, bufferIndices, scaleIndices, count, outPartials);
 }
 
-// One draw of every listed node's state per pattern (include/beagle_mi355.h beagleMi355SampleAncestralStates; what
-// AncestralStateBeagleTreeLikelihood.traverseSample computes from a getPartials per internal node and a getTransitionMatrix per
-// branch, AncestralStateBeagleTreeLikelihood.java:414-625).  Virtual buffers are materialised by one walk, as for a read-back; the
-// draw itself is ONE launch (kernels_ancestral.hip), then the states and categories come back in two copies.  The instance's
-// patterns are patterns pOffset .. pOffset + P - 1 of an alignment of globalP (the sharded handle): the random numbers are keyed
-// on the global pattern, and row r's states land at outStates + r * globalP + pOffset.
-static int sampleAncestral(Instance* in, const int* nodes, int nodeCount, int wIdx, int fIdx, unsigned long long seed, int flags,
-                           int globalP, int pOffset, unsigned char* outStates, int* outCategories) {
+// Grow-only device scratch of an instance (ancestral draws, Markov jumps): at least `need` bytes, counted in deviceBytes.
+static int growScratch(Instance* in, char*& buf, size_t& bytes, size_t need) {
+    if (bytes >= need) return 0;
+    if (buf) {
+        HIP_TRY(hipStreamSynchronize(live(in)));
+        in->allocations.erase(std::find(in->allocations.begin(), in->allocations.end(), (void*)buf));
+        in->deviceBytes -= bytes;
+        hipFree(buf);
+        buf = nullptr; bytes = 0;
+    }
+    int rc = devAlloc(in, (void**)&buf, need); if (rc) return rc;
+    bytes = need;
+    return 0;
+}
+
+// Where a device-side draw left its results (in->ancestralDev): states [rows][P] | categories [P] | error word.
+struct AncestralDraw { uint8_t* states; int* cats; unsigned* error; };
+
+// The draw itself, left on the device: validation, materialising virtual buffers, ONE launch (kernels_ancestral.hip).
+static int drawAncestral(Instance* in, const int* nodes, int nodeCount, int wIdx, int fIdx, unsigned long long seed, int flags,
+                         int globalP, int pOffset, AncestralDraw* d) {
     if (in->partitionCount > 1) return BEAGLE_ERROR_NO_IMPLEMENTATION;
     if (badIndex(wIdx, in->eigenCount) || badIndex(fIdx, in->eigenCount)) return BEAGLE_ERROR_OUT_OF_RANGE;
     std::vector<int> need;
@@ -852,36 +865,49 @@ static int sampleAncestral(Instance* in, const int* nodes, int nodeCount, int wI
     }
     const size_t stateBytes = ((size_t)nodeCount * in->P + 255) & ~(size_t)255;
     const size_t tailBytes = (size_t)in->P * sizeof(int) + sizeof(unsigned);
-    if (in->ancestralBytes < stateBytes + tailBytes) {
-        if (in->ancestralDev) {
-            HIP_TRY(hipStreamSynchronize(live(in)));
-            in->allocations.erase(std::find(in->allocations.begin(), in->allocations.end(), (void*)in->ancestralDev));
-            in->deviceBytes -= in->ancestralBytes;
-            hipFree(in->ancestralDev);
-            in->ancestralDev = nullptr; in->ancestralBytes = 0;
-        }
-        int rc = devAlloc(in, (void**)&in->ancestralDev, stateBytes + tailBytes); if (rc) return rc;
-        in->ancestralBytes = stateBytes + tailBytes;
-    }
-    uint8_t* dStates = (uint8_t*)in->ancestralDev;
-    int* dCats = (int*)(in->ancestralDev + stateBytes);
-    unsigned* dError = (unsigned*)(dCats + in->P);
+    int rc = growScratch(in, in->ancestralDev, in->ancestralBytes, stateBytes + tailBytes); if (rc) return rc;
+    d->states = (uint8_t*)in->ancestralDev;
+    d->cats = (int*)(in->ancestralDev + stateBytes);
+    d->error = (unsigned*)(d->cats + in->P);
     void* dRows = nullptr;
-    int rc = uploadTransient(in, rows.data(), rows.size() * sizeof(mi355::AncestralRow), &dRows); if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(dError, 0, sizeof(unsigned), live(in)));
+    rc = uploadTransient(in, rows.data(), rows.size() * sizeof(mi355::AncestralRow), &dRows); if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(d->error, 0, sizeof(unsigned), live(in)));
     mi355::launchSampleAncestral(live(in), (const mi355::AncestralRow*)dRows, nodeCount, in->weights + (size_t)wIdx * in->C,
                                  in->freqs + (size_t)fIdx * in->S, in->P, in->S, in->C, in->tiled, globalP, pOffset, seed,
-                                 (flags & BEAGLE_MI355_ANCESTRAL_MAP) != 0, dStates, dCats, dError);
+                                 (flags & BEAGLE_MI355_ANCESTRAL_MAP) != 0, d->states, d->cats, d->error);
     HIP_TRY(hipGetLastError());
-    if (globalP == in->P)
-        HIP_TRY(hipMemcpyAsync(outStates, dStates, (size_t)nodeCount * in->P, hipMemcpyDeviceToHost, live(in)));
-    else
-        HIP_TRY(hipMemcpy2DAsync(outStates + pOffset, (size_t)globalP, dStates, (size_t)in->P, (size_t)in->P, (size_t)nodeCount,
-                                 hipMemcpyDeviceToHost, live(in)));
+    return 0;
+}
+
+// Copy-out of a draw: the states (queued; NULL: none), then the categories and the error word in one synchronising copy.
+static int copyAncestral(Instance* in, const AncestralDraw& d, int nodeCount, int globalP, int pOffset, unsigned char* outStates,
+                         int* outCategories, unsigned* error) {
+    if (outStates) {
+        if (globalP == in->P)
+            HIP_TRY(hipMemcpyAsync(outStates, d.states, (size_t)nodeCount * in->P, hipMemcpyDeviceToHost, live(in)));
+        else
+            HIP_TRY(hipMemcpy2DAsync(outStates + pOffset, (size_t)globalP, d.states, (size_t)in->P, (size_t)in->P, (size_t)nodeCount,
+                                     hipMemcpyDeviceToHost, live(in)));
+    }
     std::vector<int> tail(in->P + 1);
-    rc = download(in, tail.data(), dCats, tailBytes); if (rc) return rc;
+    int rc = download(in, tail.data(), d.cats, (size_t)in->P * sizeof(int) + sizeof(unsigned)); if (rc) return rc;
     if (outCategories) memcpy(outCategories + pOffset, tail.data(), (size_t)in->P * sizeof(int));
-    unsigned err; memcpy(&err, &tail[in->P], sizeof(unsigned));
+    memcpy(error, &tail[in->P], sizeof(unsigned));
+    return 0;
+}
+
+// One draw of every listed node's state per pattern (include/beagle_mi355.h beagleMi355SampleAncestralStates; what
+// AncestralStateBeagleTreeLikelihood.traverseSample computes from a getPartials per internal node and a getTransitionMatrix per
+// branch, AncestralStateBeagleTreeLikelihood.java:414-625).  Virtual buffers are materialised by one walk, as for a read-back; the
+// draw itself is ONE launch (kernels_ancestral.hip), then the states and categories come back in two copies.  The instance's
+// patterns are patterns pOffset .. pOffset + P - 1 of an alignment of globalP (the sharded handle): the random numbers are keyed
+// on the global pattern, and row r's states land at outStates + r * globalP + pOffset.
+static int sampleAncestral(Instance* in, const int* nodes, int nodeCount, int wIdx, int fIdx, unsigned long long seed, int flags,
+                           int globalP, int pOffset, unsigned char* outStates, int* outCategories) {
+    AncestralDraw d;
+    int rc = drawAncestral(in, nodes, nodeCount, wIdx, fIdx, seed, flags, globalP, pOffset, &d); if (rc) return rc;
+    unsigned err = 0;
+    rc = copyAncestral(in, d, nodeCount, globalP, pOffset, outStates, outCategories, &err); if (rc) return rc;
     return err ? BEAGLE_ERROR_FLOATING_POINT : BEAGLE_SUCCESS;
 }
 
@@ -902,6 +928,130 @@ int beagleMi355SampleAncestralStates(int instance, const int* nodes, int nodeCou
     GET_INSTANCE(instance);
     return sampleAncestral(in, nodes, nodeCount, categoryWeightsIndex, stateFrequenciesIndex, seed, flags, in->P, 0, outStates,
                            outRateCategories);
+}
+
+// Expected Markov-jump counts and rewards per branch and pattern (include/beagle_mi355.h beagleMi355SampleMarkovJumps; what
+// MarkovJumpsBeagleTreeLikelihood.hookCalculation computes inside traverseSample, MarkovJumpsBeagleTreeLikelihood.java:429-567).
+// The draw is drawAncestral's, left on the device; then four launches (kernels_markovjumps.hip): the registers' M_k, the
+// conditional tables of every (register, row, category), the per-pattern gather (in row chunks of at most 256 MiB of outJumps when
+// it is asked for), the per-row totals.  As for the draw, the instance's patterns are pOffset .. pOffset + P - 1 of globalP;
+// outRowTotals gets THIS instance's sums ([K][nodeCount]).
+static int sampleJumps(Instance* in, const int* nodes, int nodeCount, const double* branchTimes, const double* branchRates,
+                       int eigenIndex, int ratesIndex, int wIdx, int fIdx, const double* registers, const int* registerFlags, int K,
+                       unsigned long long seed, int flags, int globalP, int pOffset, unsigned char* outStates, int* outCategories,
+                       double* outJumps, double* outPatternTotals, double* outRowTotals) {
+    if (in->partitionCount > 1 || in->eigenComplex) return BEAGLE_ERROR_NO_IMPLEMENTATION;
+    if (badIndex(eigenIndex, in->eigenCount) || badIndex(ratesIndex, in->eigenCount)) return BEAGLE_ERROR_OUT_OF_RANGE;
+    AncestralDraw d;
+    int rc = drawAncestral(in, nodes, nodeCount, wIdx, fIdx, seed, flags, globalP, pOffset, &d); if (rc) return rc;
+    const int S = in->S, C = in->C, P = in->P;
+    const size_t SS = (size_t)S * S, R = (size_t)nodeCount, blocks = (size_t)mi355::jumpSiteBlocks(P);
+    const size_t stageRows = outJumps ? std::max<size_t>(1, std::min<size_t>(R, (256ull << 20) / ((size_t)K * P * sizeof(double)))) : 0;
+    // jumpDev (doubles): registers [K][S][S] | rateReg, tmp, M [3][K][S][S] | cond [K][R][C][S][S] | blockPartials [blocks][K][R]
+    //                    | rowTotals [K][R] | patternTotals [K][P] | outJumps stage [K][stageRows][P] | register flags int [K]
+    const size_t nReg = (size_t)K * SS, nCond = (size_t)K * R * C * SS, nPart = blocks * K * R, nRow = (size_t)K * R,
+                 nPat = (size_t)K * P, nStage = (size_t)K * stageRows * P;
+    const size_t doubles = 4 * nReg + nCond + nPart + nRow + nPat + nStage;
+    rc = growScratch(in, in->jumpDev, in->jumpBytes, doubles * sizeof(double) + mi355::MAX_JUMP_REGISTERS * sizeof(int)); if (rc) return rc;
+    double* dReg = (double*)in->jumpDev;
+    double* dRateReg = dReg + nReg;
+    double* dTmp = dRateReg + nReg;
+    double* dM = dTmp + nReg;
+    double* dCond = dM + nReg;
+    double* dPart = dCond + nCond;
+    double* dRow = dPart + nPart;
+    double* dPat = dRow + nRow;
+    double* dStage = dPat + nPat;
+    int* dFlags = (int*)(dStage + nStage);
+    std::vector<int> fl(K, 0);
+    if (registerFlags) for (int k = 0; k < K; k++) fl[k] = registerFlags[k];
+    rc = upload(in, dReg, registers, nReg * sizeof(double)); if (rc) return rc;
+    rc = upload(in, dFlags, fl.data(), K * sizeof(int)); if (rc) return rc;
+    std::vector<mi355::JumpRow> rows(nodeCount);
+    for (int r = 0; r < nodeCount; r++) {
+        mi355::JumpRow& row = rows[r];
+        row.time = branchTimes[r];
+        row.rate = branchRates ? branchRates[r] : 1.0;
+        row.matrix = r == 0 ? nullptr : in->matrices + (size_t)C * SS * nodes[3 * r + 1];
+        row.parent = r == 0 ? -1 : nodes[3 * r + 2];
+        row.pad = 0;
+    }
+    void* dRowsV = nullptr;
+    rc = uploadTransient(in, rows.data(), rows.size() * sizeof(mi355::JumpRow), &dRowsV); if (rc) return rc;
+    const mi355::JumpRow* dRows = (const mi355::JumpRow*)dRowsV;
+    const double* eig = in->eigen + (2 * SS + S) * (size_t)eigenIndex;
+    const double* rates = in->rates + (size_t)ratesIndex * C;
+    mi355::launchJumpRegisters(live(in), eig, dReg, dFlags, K, S, dRateReg, dTmp, dM);
+    mi355::launchJumpMatrices(live(in), dRows, nodeCount, eig, rates, dM, dFlags, K, S, C, dCond);
+    HIP_TRY(hipGetLastError());
+    const size_t chunk = outJumps ? stageRows : R;
+    for (size_t r0 = 0; r0 < R; r0 += chunk) {
+        const size_t r1 = std::min(R, r0 + chunk);
+        mi355::launchJumpSites(live(in), dRows, nodeCount, (int)r0, (int)r1, d.states, d.cats, dCond, K, S, C, P,
+                               outJumps ? dStage : nullptr, dPat, dPart, d.error);
+        HIP_TRY(hipGetLastError());
+        if (!outJumps) continue;
+        for (int k = 0; k < K; k++)
+            HIP_TRY(hipMemcpy2DAsync(outJumps + ((size_t)k * R + r0) * globalP + pOffset, (size_t)globalP * sizeof(double),
+                                     dStage + (size_t)k * (r1 - r0) * P, (size_t)P * sizeof(double), (size_t)P * sizeof(double), r1 - r0,
+                                     hipMemcpyDeviceToHost, live(in)));
+        HIP_TRY(hipStreamSynchronize(live(in)));           // (the next chunk overwrites the stage)
+    }
+    mi355::launchJumpRowTotals(live(in), dPart, (int)blocks, K, nodeCount, dRow);
+    HIP_TRY(hipGetLastError());
+    if (outPatternTotals)
+        HIP_TRY(hipMemcpy2DAsync(outPatternTotals + pOffset, (size_t)globalP * sizeof(double), dPat, (size_t)P * sizeof(double),
+                                 (size_t)P * sizeof(double), (size_t)K, hipMemcpyDeviceToHost, live(in)));
+    if (outRowTotals) HIP_TRY(hipMemcpyAsync(outRowTotals, dRow, nRow * sizeof(double), hipMemcpyDeviceToHost, live(in)));
+    unsigned err = 0;
+    rc = copyAncestral(in, d, nodeCount, globalP, pOffset, outStates, outCategories, &err); if (rc) return rc;
+    return err ? BEAGLE_ERROR_FLOATING_POINT : BEAGLE_SUCCESS;
+}
+
+int beagleMi355SampleMarkovJumps(int instance, const int* nodes, int nodeCount, const double* branchTimes, const double* branchRates,
+                                 int eigenIndex, int categoryRatesIndex, int categoryWeightsIndex, int stateFrequenciesIndex,
+                                 const double* registers, const int* registerFlags, int registerCount, unsigned long long seed, int flags,
+                                 unsigned char* outStates, int* outRateCategories, double* outJumps, double* outPatternTotals,
+                                 double* outRowTotals) {
+    if (!nodes || nodeCount < 1 || !branchTimes || !registers) return BEAGLE_ERROR_OUT_OF_RANGE;
+    if (registerCount < 1 || registerCount > mi355::MAX_JUMP_REGISTERS) return BEAGLE_ERROR_OUT_OF_RANGE;
+    if (!outJumps && !outPatternTotals && !outRowTotals) return BEAGLE_ERROR_OUT_OF_RANGE;
+    if (registerFlags)
+        for (int k = 0; k < registerCount; k++)
+            if (registerFlags[k] & ~(BEAGLE_MI355_JUMPS_REWARDS | BEAGLE_MI355_JUMPS_SCALE_BY_TIME)) return BEAGLE_ERROR_OUT_OF_RANGE;
+    const size_t nRow = (size_t)registerCount * nodeCount;
+    if (mi355::isShardedHandle(instance)) {
+        // every shard fills its own columns; the row totals are the shards' sums, added in shard (= pattern) order
+        const int globalP = mi355::shardedPatternCount(instance);
+        std::mutex mu;
+        std::vector<std::pair<int, std::vector<double>>> partial;
+        const int rc = mi355::shardedBroadcast(instance, [&](int h) {
+            int pStart = 0, pEnd = 0;
+            mi355::shardedBoundsOfHandle(instance, h, &pStart, &pEnd);
+            GET_INSTANCE(h);
+            std::vector<double> rows(outRowTotals ? nRow : 0);
+            const int r = sampleJumps(in, nodes, nodeCount, branchTimes, branchRates, eigenIndex, categoryRatesIndex, categoryWeightsIndex,
+                                      stateFrequenciesIndex, registers, registerFlags, registerCount, seed, flags, globalP, pStart,
+                                      outStates, outRateCategories, outJumps, outPatternTotals, outRowTotals ? rows.data() : nullptr);
+            std::lock_guard<std::mutex> lock(mu);
+            partial.emplace_back(pStart, std::move(rows));
+            return r;
+        });
+        if (outRowTotals && (rc == BEAGLE_SUCCESS || rc == BEAGLE_ERROR_FLOATING_POINT)) {
+            std::sort(partial.begin(), partial.end(), [](const std::pair<int, std::vector<double>>& a,
+                                                         const std::pair<int, std::vector<double>>& b) { return a.first < b.first; });
+            for (size_t i = 0; i < nRow; i++) {
+                double s = partial[0].second[i];
+                for (size_t q = 1; q < partial.size(); q++) s = s + partial[q].second[i];
+                outRowTotals[i] = s;
+            }
+        }
+        return rc;
+    }
+    GET_INSTANCE(instance);
+    return sampleJumps(in, nodes, nodeCount, branchTimes, branchRates, eigenIndex, categoryRatesIndex, categoryWeightsIndex,
+                       stateFrequenciesIndex, registers, registerFlags, registerCount, seed, flags, in->P, 0, outStates, outRateCategories,
+                       outJumps, outPatternTotals, outRowTotals);
 }
 
 // MI355X extensions for the JNI shim: the result stays in the engine's pinned bounce buffer (valid until the next call on the

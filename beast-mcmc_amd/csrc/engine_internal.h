@@ -189,6 +189,8 @@ struct Instance {
     hipEvent_t exportEvent[2] = {nullptr, nullptr};
     // ancestral-state draws (beagleMi355SampleAncestralStates): states [rows][P] | categories [P] | error word, grown on demand
     char* ancestralDev = nullptr; size_t ancestralBytes = 0;
+    // Markov jumps (beagleMi355SampleMarkovJumps): registers, tables, per-block row sums, totals, outJumps stage, grown on demand
+    char* jumpDev = nullptr; size_t jumpBytes = 0;
     long statMicroOps = 0, statStored = 0, statMemReads = 0, statTipReads = 0, statScaleReads = 0, statWalks = 0, statScaleWrites = 0;   // since the last timer reset
     hipStream_t stream = nullptr, ownStream = nullptr;
     int tipCount = 0, partialsCount = 0, compactCount = 0, S = 0, P = 0, eigenCount = 0, matrixCount = 0, C = 0, scaleCount = 0;

@@ -486,6 +486,31 @@ struct AncestralRow {
 void launchSampleAncestral(hipStream_t stream, const AncestralRow* dRows, int nRows, const double* catWeights, const double* freqs,
                            int P, int S, int C, bool tiled, int globalP, int pOffset, unsigned long long seed, bool map,
                            uint8_t* states, int* cats, unsigned* fpError);
+// ---- Markov jumps (kernels_markovjumps.hip; beagleMi355SampleMarkovJumps) ------------------------------------------------
+constexpr int MAX_JUMP_REGISTERS = 8;
+// One row of the node list: the branch's time and rate, its matrices [C][S][S] (nullptr at the root) and its parent row
+struct JumpRow {
+    double         time;
+    double         rate;
+    const double*  matrix;
+    int            parent;
+    int            pad;
+};
+// register flags: bit 0 = reward register (rateReg = diag(R)), bit 1 = divide by branchRate * categoryRate.
+// rr, tmp, M: [K][S][S] scratch; M[k] = U^-1 rateReg_k U from the (real) eigen system at `eigen` (U | U^-1 | lambda).
+void launchJumpRegisters(hipStream_t stream, const double* eigen, const double* registers, const int* regFlags, int K, int S,
+                         double* rr, double* tmp, double* M);
+// cond[k][r][c][S][S] = (U ((A o M_k) U^-1)) / P_r[c] (then / (rate_r * rate_c) for a scaled register) for rows 1 .. nRows-1
+void launchJumpMatrices(hipStream_t stream, const JumpRow* dRows, int nRows, const double* eigen, const double* rates,
+                        const double* M, const int* regFlags, int K, int S, int C, double* cond);
+int  jumpSiteBlocks(int P);                  // workgroups of launchJumpSites (rows of blockPartials)
+// rows [r0, r1) of every pattern: jumps [K][r1-r0][P] (may be nullptr), running pattern totals [K][P] (read unless r0 == 0),
+// blockPartials [jumpSiteBlocks(P)][K][nRows]; *fpError |= 2 when some value is not finite
+void launchJumpSites(hipStream_t stream, const JumpRow* dRows, int nRows, int r0, int r1, const uint8_t* states, const int* cats,
+                     const double* cond, int K, int S, int C, int P, double* jumps, double* patternTotals, double* blockPartials,
+                     unsigned* fpError);
+// out[k][r] = sum of blockPartials[.][k][r] over `blocks` workgroups in ascending order
+void launchJumpRowTotals(hipStream_t stream, const double* blockPartials, int blocks, int K, int nRows, double* out);
 // out[0] = sum of n block sums in a fixed order
 void launchRootFinal(hipStream_t stream, const double* blockSums, int n, double* out, unsigned long long* flag = nullptr,
                      unsigned long long seq = 0);

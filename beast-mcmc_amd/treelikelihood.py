@@ -56,6 +56,8 @@ def host_library():
         lib.btlRootBufferIndex.argtypes = [C.c_void_p]
         lib.btlNodeBufferIndex.argtypes = [C.c_void_p, C.c_int]
         lib.btlNodeMatrixIndex.argtypes = [C.c_void_p, C.c_int]
+        lib.btlNodeBranchTime.argtypes = [C.c_void_p, C.c_int, _DP]
+        lib.btlEigenIndex.argtypes = [C.c_void_p]
         lib.btlNodeScaleIndex.argtypes = [C.c_void_p, C.c_int]
         lib.btlCumulativeScaleIndex.argtypes = [C.c_void_p]
         lib.btlCounters.argtypes = [C.c_void_p, C.POINTER(C.c_long)]
@@ -120,11 +122,13 @@ class BeagleTreeLikelihood:
             raise _b.BeagleException(what, rc)
 
     def set_substitution_model(self, eig, freqs):
+        self.eig, self.freqs = eig, np.asarray(freqs, dtype=np.float64)
         u, ui, lam, f = _d(eig.evec), _d(eig.ievc), _d(eig.evals), _d(freqs)
         self._chk(self.h.btlSetSubstitutionModel(self.ptr, u.ctypes.data_as(_DP), ui.ctypes.data_as(_DP),
                                                  lam.ctypes.data_as(_DP), f.ctypes.data_as(_DP)), "setSubstitutionModel")
 
     def set_site_model(self, rates, weights):
+        self.cat_rates, self.cat_weights = np.asarray(rates, dtype=np.float64), np.asarray(weights, dtype=np.float64)
         r, w = _d(rates), _d(weights)
         self._chk(self.h.btlSetSiteModel(self.ptr, r.ctypes.data_as(_DP), w.ctypes.data_as(_DP)), "setSiteModel")
 
@@ -223,6 +227,17 @@ class BeagleTreeLikelihood:
     def node_matrix_index(self, node):
         """The matrix buffer that holds node's branch matrix now (the caller's double buffering: BufferIndexHelper)."""
         return self.h.btlNodeMatrixIndex(self.ptr, node)
+
+    def node_branch_time(self, node):
+        """(height[parent] - height[node], branchRate[node]) as the host driver holds them now: the two operands whose product is
+        the edge length of node's transition matrix."""
+        out = (C.c_double * 2)()
+        self._chk(self.h.btlNodeBranchTime(self.ptr, node, out), "nodeBranchTime")
+        return out[0], out[1]
+
+    def eigen_index(self):
+        """The eigen buffer that holds the substitution model now (the caller's double buffering)."""
+        return self.h.btlEigenIndex(self.ptr)
 
     def node_scale_index(self, node):
         return self.h.btlNodeScaleIndex(self.ptr, node)

@@ -353,6 +353,45 @@ int beagleMi355GetPartialsBatch(int instance, const int* bufferIndices, const in
 #define BEAGLE_MI355_ANCESTRAL_MAP 1
 int beagleMi355SampleAncestralStates(int instance, const int* nodes, int nodeCount, int categoryWeightsIndex, int stateFrequenciesIndex,
                                      unsigned long long seed, int flags, unsigned char* outStates, int* outRateCategories);
+/* Markov jumps: ONE call that draws the ancestral states as beagleMi355SampleAncestralStates does and, for every register k, row
+ * r >= 1 and pattern p, forms the expected number of registered substitutions (a count register) or the expected reward (a reward
+ * register) on row r's branch, conditioned on the drawn parent and child states — what MarkovJumpsBeagleTreeLikelihood.hookCalculation
+ * computes inside traverseSample with useUniformization = false (MarkovJumpsBeagleTreeLikelihood.java:429-567).
+ *   nodes, nodeCount, categoryWeightsIndex, stateFrequenciesIndex, seed, flags: as for beagleMi355SampleAncestralStates; the states
+ *          and categories are the bytes that call returns.  outStates [nodeCount][patternCount] and outRateCategories [patternCount]
+ *          may be NULL here.
+ *   branchTimes[r]: parent height - child height;  branchRates[r] (NULL: all 1.0).  Row 0 (the root) is ignored.
+ *   eigenIndex, categoryRatesIndex: the eigen system and the category rates rate_c the registers and times are formed from.
+ *   registers: registerCount (1..8) matrices of S x S doubles R_k;  registerFlags[k] (NULL: all 0) = BEAGLE_MI355_JUMPS_REWARDS for a
+ *          reward register, | BEAGLE_MI355_JUMPS_SCALE_BY_TIME to divide by branchRate * categoryRate (scaleByTime).
+ * Count register: rateReg = Q o R with R's diagonal 0 (MarkovJumpsSubstitutionModel.setRegistration / makeRateRegistrationMatrix),
+ * Q = U diag(lambda) U^-1 formed on the device from eigen system eigenIndex — the engine keeps no Q of its own, so Q equals the
+ * reference's getInfinitesimalMatrix up to rounding.  Reward register: rateReg = diag(R[i][i]) (only the diagonal is read).
+ * M_k = U^-1 rateReg_k U (PRECOMPUTE).  With c = category[p], i = state[parent(r)][p], j = state[r][p],
+ * tau = (branchTimes[r] * branchRates[r]) * rate_c (substTime * branchRate * rate, :499/:533 — the bits of the engine's transition
+ * distance when row r's matrix was built from edge length branchRate * time):
+ *   rate_c > 0: A[a][b] = |la - lb| < 1e-7 ? e^(la tau) tau : (e^(la tau) - e^(lb tau)) / (la - lb);  J = U ((A o M_k) U^-1);
+ *               V = J[i][j] / P_r[c][i][j] with P_r the instance's matrix of row r (hookCalculation divides by getMatrix);
+ *               SCALE_BY_TIME: V = V / (branchRates[r] * rate_c)   (MarkovJumpsCore.computeCondStatMarkovJumpsPrecompute)
+ *   rate_c <= 0: V = 0, except a reward register with SCALE_BY_TIME: V = (i == j) ? branchTimes[r] : 0 (:553-559).
+ *   row 0: V = 0.
+ * Outputs (any may be NULL, not all three; all deterministic — two identical calls give identical bits):
+ *   outJumps [K][nodeCount][patternCount] = V (the <tag>_base trait);
+ *   outPatternTotals [K][patternCount] = sum over rows 1 .. nodeCount-1 in row order (the c_<tag>[p] column, :640-654);
+ *   outRowTotals [K][nodeCount] = sum over the instance's patterns, unweighted (TreeTrait.SumAcrossArrayD: the <tag>_sum trait).
+ * The sharded handle (resource G+1) returns one instance's states, categories, outJumps and outPatternTotals byte for byte;
+ * outRowTotals there is the shards' sums added in shard order (equal to one instance's to rounding).
+ * Errors: those of beagleMi355SampleAncestralStates, and BEAGLE_ERROR_OUT_OF_RANGE for registerCount outside 1..8, an unknown
+ * register-flag bit, a bad eigenIndex or categoryRatesIndex, branchTimes or registers NULL, or all three jump outputs NULL;
+ * BEAGLE_ERROR_NO_IMPLEMENTATION on an EIGEN_COMPLEX instance or one with more than one pattern partition;
+ * BEAGLE_ERROR_FLOATING_POINT when a draw failed or some V is not finite — everything else is still written. */
+#define BEAGLE_MI355_JUMPS_REWARDS       1
+#define BEAGLE_MI355_JUMPS_SCALE_BY_TIME 2
+int beagleMi355SampleMarkovJumps(int instance, const int* nodes, int nodeCount, const double* branchTimes, const double* branchRates,
+                                 int eigenIndex, int categoryRatesIndex, int categoryWeightsIndex, int stateFrequenciesIndex,
+                                 const double* registers, const int* registerFlags, int registerCount, unsigned long long seed, int flags,
+                                 unsigned char* outStates, int* outRateCategories, double* outJumps, double* outPatternTotals,
+                                 double* outRowTotals);
 /* For the JNI shim: getPartials / getSiteLogLikelihoods whose result STAYS in the engine's pinned host buffer — *outPinned,
  * *outCount doubles, valid until the next call on the instance — so that it reaches the Java array with one copy
  * (Set<Type>ArrayRegion) instead of two.  BEAGLE_ERROR_NO_IMPLEMENTATION on the sharded instance: use the ordinary call. */

@@ -510,6 +510,15 @@ int btlLastError(void* h) { return ((TreeLikelihood*)h)->lastError; }
 int btlRootBufferIndex(void* h) { TreeLikelihood* t = (TreeLikelihood*)h; return t->partialBufferHelper.getOffsetIndex(t->root); }
 int btlNodeBufferIndex(void* h, int node) { return ((TreeLikelihood*)h)->partialBufferHelper.getOffsetIndex(node); }
 int btlNodeMatrixIndex(void* h, int node) { return ((TreeLikelihood*)h)->matrixBufferHelper.getOffsetIndex(node); }
+// {height[parent] - height[node], branchRate[node]}: the two operands whose product is node's edge length in runTraversal
+int btlNodeBranchTime(void* h, int node, double* out2) {
+    TreeLikelihood* t = (TreeLikelihood*)h;
+    if (node < 0 || node >= t->nodeCount || t->parent[node] < 0) return BEAGLE_ERROR_OUT_OF_RANGE;
+    out2[0] = t->height[t->parent[node]] - t->height[node];
+    out2[1] = t->branchRate[node];
+    return 0;
+}
+int btlEigenIndex(void* h) { return ((TreeLikelihood*)h)->eigenBufferHelper.getOffsetIndex(0); }
 int btlNodeScaleIndex(void* h, int node) { TreeLikelihood* t = (TreeLikelihood*)h; return t->scaleBufferIndices[node - t->tipCount]; }
 int btlCumulativeScaleIndex(void* h) {
     TreeLikelihood* t = (TreeLikelihood*)h;
