@@ -123,7 +123,7 @@ ABI_SYMBOLS = ["beagleGetVersion", "beagleGetCitation", "beagleGetResourceList",
                "beagleGetPartitionApiTable"] + \
               ["beagle" + k for k in _PROTOS] + \
               ["beagleMi355SetStream", "beagleMi355CalculateRootLogLikelihoodsDevice", "beagleMi355Synchronize",
-               "beagleMi355KernelTimer", "beagleMi355DeviceBytes", "beagleMi355WalkStats", "beagleMi355GradientStats", "beagleMi355GetPartialsBatch", "beagleMi355SampleAncestralStates", "beagleMi355SampleMarkovJumps",
+               "beagleMi355KernelTimer", "beagleMi355DeviceBytes", "beagleMi355WalkStats", "beagleMi355GradientStats", "beagleMi355GetPartialsBatch", "beagleMi355SampleAncestralStates", "beagleMi355SampleMarkovJumps", "beagleMi355SampleMarkovJumpsUniformized",
                "beagleMi355GetPartialsPinned", "beagleMi355GetSiteLogLikelihoodsPinned",
                "beagleMi355KernelTimerCalls", "beagleMi355WalkHealth", "beagleMi355WalkLaunchInfo", "beagleMi355RootFusedCount", "beagleMi355SitePrefetchCount", "beagleMi355KernelTimerRestart", "beagleMi355GetDimensions", "beagleMi355GetCommUniqueId", "beagleMi355CommInit", "beagleMi355CommInfo", "beagleMi355CalculateRootLogLikelihoodsAllReduce"]
 
@@ -567,6 +567,76 @@ class Beagle:
                                            eigenIndex, categoryRatesIndex, categoryWeightsIndex, stateFrequenciesIndex, _dp(regs),
                                            _ip(flags), K, int(seed) & 0xFFFFFFFFFFFFFFFF, 1 if map else 0, ptr("states"),
                                            ptr("categories"), ptr("jumps"), ptr("pattern_totals"), ptr("row_totals")))
+        return out
+
+    def sampleMarkovJumpsUniformized(self, nodes, branchTimes, branchRates, nodeHeights, infinitesimalMatrix, categoryRatesIndex,
+                                     categoryWeightsIndex, stateFrequenciesIndex, registers, registerFlags, seed, simulants=1,
+                                     map=False, states=False, jumps=False, pattern_totals=True, row_totals=True, history=False,
+                                     event_capacity=None, retry=True):
+        """One ancestral draw plus SAMPLED Markov-jump counts / rewards by uniformization (include/beagle_mi355.h
+        beagleMi355SampleMarkovJumpsUniformized).  Arguments as for sampleMarkovJumps, and ``nodeHeights`` [nodeCount] (row order;
+        needed with ``history``), ``infinitesimalMatrix`` Q [S][S], ``simulants`` (1..1024).  -> dict as sampleMarkovJumps returns,
+        and "fallbacks" (histories that took the reference's uniform-event fallback); with ``history``: "event_counts" int32
+        [nodeCount, P], "event_heights" [E], "event_states" uint8 [E, 2], "event_total".  The event buffer starts at
+        ``event_capacity`` (default: a guess) and the call is made once more with the exact size when it was too small (``retry``;
+        without it a full buffer returns the other outputs and "rc" = -5 instead of raising)."""
+        rows = _i(nodes).reshape(-1, 3)
+        n, P, S = rows.shape[0], self.patternCount, self.stateCount
+        regs = _d(registers).reshape(-1, S, S)
+        K = regs.shape[0]
+        flags = _i(registerFlags).reshape(-1)
+        times = _d(branchTimes).reshape(-1)
+        rates = None if branchRates is None else _d(branchRates).reshape(-1)
+        heights = None if nodeHeights is None else _d(nodeHeights).reshape(-1)
+        Q = _d(infinitesimalMatrix).reshape(S, S)
+        if times.shape[0] != n or (rates is not None and rates.shape[0] != n) or flags.shape[0] != K or \
+                (heights is not None and heights.shape[0] != n):
+            raise ValueError("branchTimes, branchRates, nodeHeights and registerFlags must have one entry per row / register")
+        capacity = int(event_capacity) if event_capacity is not None else n * P // 4 + 1024
+        f = self._ext("beagleMi355SampleMarkovJumpsUniformized",
+                      [C.c_int, _IP, C.c_int, _DP, C.c_void_p, C.c_void_p, _DP, C.c_int, C.c_int, C.c_int, _DP, _IP, C.c_int,
+                       C.c_int, C.c_ulonglong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                       C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
+        for attempt in range(2):
+            out = {}
+            if states:
+                out["states"] = np.empty((n, P), dtype=np.uint8)
+                out["categories"] = np.zeros(P, dtype=np.int32)
+            if jumps:
+                out["jumps"] = np.empty((K, n, P))
+            if pattern_totals:
+                out["pattern_totals"] = np.empty((K, P))
+            if row_totals:
+                out["row_totals"] = np.empty((K, n))
+            if history:
+                out["event_counts"] = np.empty((n, P), dtype=np.int32)
+                out["event_heights"] = np.empty(capacity)
+                out["event_states"] = np.empty((capacity, 2), dtype=np.uint8)
+            total, fallbacks = C.c_longlong(0), C.c_longlong(0)
+
+            def ptr(key):
+                return out[key].ctypes.data if key in out else None
+
+            rc = f(self.instance, _ip(rows), n, _dp(times), None if rates is None else rates.ctypes.data,
+                   None if heights is None else heights.ctypes.data, _dp(Q), categoryRatesIndex, categoryWeightsIndex,
+                   stateFrequenciesIndex, _dp(regs), _ip(flags), K, int(simulants), int(seed) & 0xFFFFFFFFFFFFFFFF, 1 if map else 0,
+                   ptr("states"), ptr("categories"), ptr("jumps"), ptr("pattern_totals"), ptr("row_totals"), ptr("event_counts"),
+                   capacity if history else 0, ptr("event_heights"), ptr("event_states"), C.byref(total) if history else None,
+                   C.byref(fallbacks))
+            if rc == -5 and history and total.value > capacity:
+                if retry and attempt == 0:
+                    capacity = int(total.value)
+                    continue
+                if not retry:
+                    out["rc"] = rc
+                    rc = 0
+            break
+        self._check("sampleMarkovJumpsUniformized", rc)
+        out["fallbacks"] = int(fallbacks.value)
+        if history:
+            out["event_total"] = int(total.value)
+            out["event_heights"] = out["event_heights"][:total.value]
+            out["event_states"] = out["event_states"][:total.value]
         return out
 
     def walkStats(self):

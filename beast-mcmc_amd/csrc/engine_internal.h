@@ -191,6 +191,10 @@ struct Instance {
     char* ancestralDev = nullptr; size_t ancestralBytes = 0;
     // Markov jumps (beagleMi355SampleMarkovJumps): registers, tables, per-block row sums, totals, outJumps stage, grown on demand
     char* jumpDev = nullptr; size_t jumpBytes = 0;
+    // uniformized Markov jumps (beagleMi355SampleMarkovJumpsUniformized): R^n table, rows, registers, sums, counts, grown on demand;
+    // the event list of the last call that asked for one
+    char* uniformDev = nullptr; size_t uniformBytes = 0;
+    char* eventDev = nullptr; size_t eventBytes = 0;
     long statMicroOps = 0, statStored = 0, statMemReads = 0, statTipReads = 0, statScaleReads = 0, statWalks = 0, statScaleWrites = 0;   // since the last timer reset
     hipStream_t stream = nullptr, ownStream = nullptr;
     int tipCount = 0, partialsCount = 0, compactCount = 0, S = 0, P = 0, eigenCount = 0, matrixCount = 0, C = 0, scaleCount = 0;

@@ -511,6 +511,48 @@ void launchJumpSites(hipStream_t stream, const JumpRow* dRows, int nRows, int r0
                      unsigned* fpError);
 // out[k][r] = sum of blockPartials[.][k][r] over `blocks` workgroups in ascending order
 void launchJumpRowTotals(hipStream_t stream, const double* blockPartials, int blocks, int K, int nRows, double* out);
+// ---- uniformized Markov jumps (kernels_uniformized.hip; beagleMi355SampleMarkovJumpsUniformized) --------------------------
+// One row of the node list: the branch's time and rate, the parent's and the node's heights, its matrices [C][S][S] (nullptr at
+// the root) and its parent row
+struct UniformRow {
+    double         time;
+    double         rate;
+    double         hParent;
+    double         hChild;
+    const double*  matrix;
+    int            parent;
+    int            pad;
+};
+constexpr int UNIFORM_MAX_TRIES = 1000;        // SubordinatedProcess.drawNumberOfChanges' maxTries
+constexpr int UNIFORM_MAX_SIMULANTS = 1024;
+struct UniformSiteArgs {
+    const UniformRow* rows;
+    const uint8_t* states;               // the draw's states [nRows][P] and categories [P]
+    const int* cats;
+    const double* rates;                 // category rates [C]
+    const double* table;                 // R^n [N][S][S] (R^0 = I)
+    const double* registers;             // [K][S][S]
+    const int* regFlags;                 // [K]: bit 0 reward, bit 1 scale by time
+    double* stage;                       // values [K][stageRows][P] of the launched rows
+    double* blockPartials;               // [jumpSiteBlocks(P)][K][nRows]
+    int* eventCounts;                    // [nRows][P] real changes of simulant 0 (nullptr: not counted); offsets when writing
+    const long long* patternOffsets;     // [P] first event of each pattern (writing)
+    double* eventHeights;                // [events] (writing)
+    uint8_t* eventStates;                // [events][2] (writing)
+    unsigned* fpError;                   // |= 2 on a failed draw or a value that is not finite
+    unsigned long long* fallbacks;       // += histories that took the fallback
+    unsigned long long seed;
+    double mu;
+    int nRows, K, S, P, N, simulants, stageRows, globalP, pOffset;
+};
+// table[n] = table[n-1] table[1] for n = 2 .. N-1
+void launchUniformPowers(hipStream_t stream, double* table, int S, int N);
+// rows [r0, r1) of every pattern: values, row sums, counts (write = false), or the events (write = true)
+void launchUniformSites(hipStream_t stream, const UniformSiteArgs& a, int r0, int r1, bool write);
+// patternTotals [K][P] (+)= stage rows [r0, r1) in row order
+void launchUniformPatternTotals(hipStream_t stream, const double* stage, int stageRows, int r0, int r1, int K, int P, double* patternTotals);
+// counts [nRows][P] -> offsets within each pattern (in place); patternOffsets [P + 1]: exclusive scan of the pattern sums, then the total
+void launchEventOffsets(hipStream_t stream, int* counts, int nRows, int P, long long* patternOffsets);
 // out[0] = sum of n block sums in a fixed order
 void launchRootFinal(hipStream_t stream, const double* blockSums, int n, double* out, unsigned long long* flag = nullptr,
                      unsigned long long seq = 0);

@@ -17,43 +17,14 @@
 #pragma clang fp contract(off)
 
 #include "kernels.h"
-#include <float.h>
+#include "ancestral_draw.h"
 
 namespace mi355 {
 
 namespace {
 
-// SplitMix64: the (ctr + 1)-th output from state `seed`, as a double in [0, 1) with 53 random bits
-__device__ __forceinline__ double ancestralUniform(unsigned long long seed, unsigned long long ctr) {
-    unsigned long long z = seed + (ctr + 1ull) * 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return (double)(z >> 11) * 0x1.0p-53;
-}
-
-// drawChoice over n weights w(i): MAP = first index of the strict maximum; otherwise randomChoicePDF with U = u * total, and the
-// largest index of a positive weight when rounding lets the walk fall through.  A total that is not finite and > 0 sets `bad`
-// and gives 0 (the reference's root: AncestralStateBeagleTreeLikelihood.java:473-477).
-template <class W>
-__device__ __forceinline__ int drawChoice(const W& w, int n, double u, bool map, bool& bad) {
-    double total = 0.0, best = 0.0;
-    int lastPositive = 0, choice = 0;
-    for (int i = 0; i < n; i++) {
-        const double v = w(i);
-        total = total + v;
-        if (v > 0.0) lastPositive = i;
-        if (i == 0 || v > best) { best = v; choice = i; }
-    }
-    if (!(total > 0.0) || !(total <= DBL_MAX)) { bad = true; return 0; }
-    if (map) return choice;
-    double U = u * total;
-    for (int i = 0; i < n; i++) {
-        U = U - w(i);
-        if (U < 0.0) return i;
-    }
-    return lastPositive;
-}
+using draw::ancestralUniform;
+using draw::drawChoice;
 
 // SS = 4: the state count as a constant (loops unrolled, the row's partials held in registers); SS = 0: any state count
 template <int SS>

@@ -1,6 +1,6 @@
 """Markov-jump counts and rewards on the device: the caller-side mirror of
 ``dr.evomodel.treelikelihood.MarkovJumpsBeagleTreeLikelihood`` (src/dr/evomodel/treelikelihood/MarkovJumpsBeagleTreeLikelihood.java)
-with ``useUniformization = false``.
+with ``useUniformization = false`` (expectations) and ``true`` (sampled histories, complete histories included).
 
 The reference extends the ancestral sampler: inside ``traverseSample`` its ``hookCalculation`` (:429-567) turns every branch's drawn
 (parent, child) state pair into the expected number of registered substitutions, or the expected reward, on that branch.  Here the
@@ -60,9 +60,21 @@ class MarkovJumpsSampler:
                 times[r], rates[r] = self.tl.node_branch_time(int(n))
         return times, rates
 
+    def node_heights(self, order):
+        """height per row of the node list, read from the host driver (the Python tree's heights go stale)."""
+        return np.array([self.tl.node_height(int(n)) for n in order], dtype=np.float64)
+
+    def infinitesimal_matrix(self):
+        """Q from the driver's eigen system (as marginal_rate forms it)."""
+        eig = self.tl.eig
+        return (eig.evec * eig.evals[None, :]) @ eig.ievc
+
     def sample(self, seed, map=False, per_site=False, states=False, category_weights_index=0, state_frequencies_index=0,
-               category_rates_index=0):
-        """-> dict indexed by tree node number:
+               category_rates_index=0, uniformization=False, simulants=1, history=False, infinitesimal_matrix=None):
+        """With ``uniformization``: sampled histories (include/beagle_mi355.h beagleMi355SampleMarkovJumpsUniformized), the mean
+        over ``simulants``; ``infinitesimal_matrix`` Q (default: from the driver's eigen system); ``history`` (one simulant) adds
+        "event_counts" [nodeCount, P] by node and the event list "events" (rows as tree nodes), read by ``histories``.
+        -> dict indexed by tree node number:
           "branch"  [K, nodeCount]  per-branch totals over patterns (the <tag>_sum trait; the root's row is 0)
           "pattern" [K, P]          per-pattern totals over branches (the c_<tag>[p] columns)
           "tree"    [K]             the sum of "branch" (the register-parameter trait)
@@ -72,9 +84,17 @@ class MarkovJumpsSampler:
             raise ValueError("no register")
         rows, order = self.ancestral.node_list()
         times, rates = self.branch_times(order)
-        res = self.beagle.sampleMarkovJumps(rows, times, rates, self.tl.eigen_index(), category_rates_index, category_weights_index,
-                                            state_frequencies_index, np.stack(self.registers), self.flags(), seed, map=map,
-                                            states=states, jumps=per_site)
+        if uniformization:
+            Q = self.infinitesimal_matrix() if infinitesimal_matrix is None else np.asarray(infinitesimal_matrix, dtype=np.float64)
+            heights = self.node_heights(order) if history else None
+            res = self.beagle.sampleMarkovJumpsUniformized(rows, times, rates, heights, Q, category_rates_index, category_weights_index,
+                                                           state_frequencies_index, np.stack(self.registers), self.flags(), seed,
+                                                           simulants=simulants, map=map, states=states, jumps=per_site,
+                                                           history=history)
+        else:
+            res = self.beagle.sampleMarkovJumps(rows, times, rates, self.tl.eigen_index(), category_rates_index, category_weights_index,
+                                                state_frequencies_index, np.stack(self.registers), self.flags(), seed, map=map,
+                                                states=states, jumps=per_site)
         out = {"pattern": res["pattern_totals"]}
         branch = np.empty_like(res["row_totals"])
         branch[:, order] = res["row_totals"]
@@ -85,6 +105,16 @@ class MarkovJumpsSampler:
             site = np.empty_like(res["jumps"])
             site[:, order] = res["jumps"]
             out["site"] = site
+        if uniformization:
+            out["fallbacks"] = res["fallbacks"]
+        if history:
+            counts = np.empty_like(res["event_counts"])
+            counts[order] = res["event_counts"]
+            out["event_counts"] = counts
+            row_of = np.repeat(np.tile(np.arange(len(order)), res["event_counts"].shape[1]), res["event_counts"].T.ravel())
+            pattern_of = np.repeat(np.arange(res["event_counts"].shape[1]), res["event_counts"].sum(axis=0))
+            out["events"] = {"node": np.asarray(order)[row_of], "pattern": pattern_of, "height": res["event_heights"],
+                             "states": res["event_states"]}
         if states:
             st = np.empty_like(res["states"])
             st[order] = res["states"]
@@ -122,3 +152,33 @@ class MarkovJumpsSampler:
         if cats is None:
             raise ValueError("several rate categories: pass the categories of a sample (sample(..., states=True))")
         return value * self.tl.cat_rates[np.asarray(cats)]
+
+    def histories(self, sample, codes=None, compact=False):
+        """[node][pattern] -> the reference's history string for a ``sample(..., history=True)`` (the history / history_all traits:
+        StateHistory.toStringChanges, addEventToStringBuilder; with ``compact`` the 1-based site leads every event).  ``codes``:
+        the data type's code per state (default "ACGT" for 4 states, else the state numbers)."""
+        S = self.tl.state_count
+        if codes is None:
+            codes = "ACGT" if S == 4 else [str(i) for i in range(S)]
+        ev = sample["events"]
+        counts = sample["event_counts"]
+        out = [["{}"] * counts.shape[1] for _ in range(counts.shape[0])]
+        parts = {}
+        for node, p, h, (a, b) in zip(ev["node"], ev["pattern"], ev["height"], ev["states"]):
+            body = "{" + ("%d," % (p + 1) if compact else "") + java_double(h) + "," + codes[a] + "," + codes[b] + "}"
+            parts.setdefault((int(node), int(p)), []).append(body)
+        for (node, p), v in parts.items():
+            out[node][p] = "{" + ",".join(v) + "}"
+        return out
+
+
+def java_double(x):
+    """Double.toString: the shortest repr, as d.ddd for 1e-3 <= |x| < 1e7 and d.dddE[-]n otherwise."""
+    x = float(x)
+    if x == 0.0 or 1e-3 <= abs(x) < 1e7:
+        r = repr(x)
+        return r if "." in r else r + ".0"
+    mant, exp = np.format_float_scientific(x, unique=True, trim="-").split("e")
+    if "." not in mant:
+        mant += ".0"
+    return "%sE%d" % (mant, int(exp))

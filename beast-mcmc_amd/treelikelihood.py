@@ -57,6 +57,7 @@ def host_library():
         lib.btlNodeBufferIndex.argtypes = [C.c_void_p, C.c_int]
         lib.btlNodeMatrixIndex.argtypes = [C.c_void_p, C.c_int]
         lib.btlNodeBranchTime.argtypes = [C.c_void_p, C.c_int, _DP]
+        lib.btlNodeHeight.argtypes = [C.c_void_p, C.c_int, _DP]
         lib.btlEigenIndex.argtypes = [C.c_void_p]
         lib.btlNodeScaleIndex.argtypes = [C.c_void_p, C.c_int]
         lib.btlCumulativeScaleIndex.argtypes = [C.c_void_p]
@@ -234,6 +235,12 @@ class BeagleTreeLikelihood:
         out = (C.c_double * 2)()
         self._chk(self.h.btlNodeBranchTime(self.ptr, node, out), "nodeBranchTime")
         return out[0], out[1]
+
+    def node_height(self, node):
+        """height[node] as the host driver holds it now (the Python tree's heights go stale after set_node_height)."""
+        out = C.c_double(0.0)
+        self._chk(self.h.btlNodeHeight(self.ptr, node, C.byref(out)), "nodeHeight")
+        return out.value
 
     def eigen_index(self):
         """The eigen buffer that holds the substitution model now (the caller's double buffering)."""

@@ -392,6 +392,61 @@ int beagleMi355SampleMarkovJumps(int instance, const int* nodes, int nodeCount, 
                                  const double* registers, const int* registerFlags, int registerCount, unsigned long long seed, int flags,
                                  unsigned char* outStates, int* outRateCategories, double* outJumps, double* outPatternTotals,
                                  double* outRowTotals);
+/* Markov jumps by uniformization: ONE call that draws the ancestral states as beagleMi355SampleMarkovJumps does (same keys: the same
+ * seed gives the same states) and then, for every simulant s, row r >= 1 and pattern p, SAMPLES an endpoint-conditioned
+ * substitution history on row r's branch — what MarkovJumpsBeagleTreeLikelihood.computeSampledMarkovJumpsForBranch computes with
+ * useUniformization = true (MarkovJumpsBeagleTreeLikelihood.java:473-509; UniformizedSubstitutionModel, SubordinatedProcess,
+ * UniformizedStateHistory.simulateConditionalOnEndingState).  No eigen system is read, so it works on EIGEN_COMPLEX instances.
+ *   nodes, nodeCount, branchTimes, branchRates, categoryRatesIndex, categoryWeightsIndex, stateFrequenciesIndex, registers,
+ *          registerFlags, registerCount, seed, flags, outStates, outRateCategories, outJumps, outPatternTotals, outRowTotals: as for
+ *          beagleMi355SampleMarkovJumps (layouts and summation orders included).
+ *   nodeHeights[r]: row r's node height (only read for histories).
+ *   infinitesimalMatrix: Q, S x S row-major (getInfinitesimalMatrix).  mu = max_i -Q_ii, R = I + Q / mu (entry by entry: Q/mu, then
+ *          +1 on the diagonal); R^n = R^(n-1) R summed over the inner index in ascending order, no FMA (MarkovJumpsCore.matrixMultiply).
+ *   simulantCount: 1..1024; the value is the mean over simulants (summed in simulant order, then / simulantCount).
+ * With i = state[parent(r)][p], j = state[r][p], c = category[p], tau = (branchTimes[r] * branchRates[r]) * rate_c, P_ij = the
+ * instance's matrix of row r [c][i][j], and u_q = the q-th number of the history's stream (below):
+ *   n: the table holds R^0 .. R^(N-1), N = min(1000, ceil(lambda + 20 sqrt(lambda)) + 40), lambda = mu * the largest tau of the call
+ *          (every row >= 1 and category with rate_c > 0).  cdf = 0, scale = 1, eff = mu tau; for n = 0, 1, ...: while u_0 >= cdf:
+ *          n > 0: scale = scale * eff; n > 1: scale = scale / n; cdf = cdf + ((exp(-eff) * scale) * R^n[i][j]) / P_ij
+ *          (SubordinatedProcess.drawNumberOfChanges).  Reaching n = N is the reference's fallback after maxTries
+ *          (RETURN_UNIFORMLY_DISTRIBUTED_EVENT): one change i -> j at f = u_1 when i != j, none otherwise; it is counted into
+ *          *outFallbacks and is not an error.
+ *   n = 0, or n = 1 with i == j: no change.  n = 1 with i != j: one change at f = u_1.
+ *   n >= 2: spacings E_q = -log(1 - u_q), q = 1..n+1, S_m = E_1 + .. + E_m, jump m at f_m = S_m / S_(n+1) (the order statistics of n
+ *          uniforms).  State draw m = 1..n-1 from the current state cur: weights R[cur][k] * R^(n-m)[k][j], drawn with u_(n+1+m) as
+ *          beagleMi355SampleAncestralStates draws (randomChoicePDF); a draw k != cur is a change at f_m.  Then, if cur != j, a change to
+ *          j at f_n.  f is the fraction of tau from the parent.
+ *   Register values per simulant, over the real changes in time order from 0.0, with t = f * tau: a count register adds
+ *          R_k[from][to] (its diagonal is never read); a reward register adds R_k[from][from] * (t - t_previous) per change, then
+ *          R_k[j'][j'] * (tau - t_last) for the final state j' (t_previous starts at 0).  SCALE_BY_TIME divides the mean by
+ *          branchRates[r] * rate_c.  rate_c <= 0: the rule of beagleMi355SampleMarkovJumps, and no change.  Row 0: 0.
+ *   Every register of a simulant reads the SAME history: "all jumps" = "upper" + "lower" in every sample.
+ * Random numbers: the history of (s, r, p) has the stream z = SplitMix64's output for key = (s * nodeCount + r) * globalP + p (p the
+ * pattern of the whole alignment), from the state seed ^ 0x6A09E667F3BCC909, as a 64-bit integer; u_q is SplitMix64's (q + 1)-th
+ * output from the state z, as beagleMi355SampleAncestralStates forms its numbers.
+ * Histories (simulantCount == 1 and nodeHeights non-NULL; asked for when any of outEventCounts, outEventHeights, outEventStates,
+ * outEventTotal is non-NULL):
+ *   outEventCounts [nodeCount][patternCount]: the real changes of each (row, pattern);
+ *   events ordered by pattern, then node-list row, then time from the parent: outEventHeights[e] = h_parent + f * (h_child - h_parent)
+ *          (nodeHeights of row r's parent row and of row r: rescaleTimesOfEvents), outEventStates[2e], [2e + 1] = from, to;
+ *   *outEventTotal: the number of events (always written when non-NULL).  More than eventCapacity: no event is written, everything
+ *          else is, and the call returns BEAGLE_ERROR_OUT_OF_RANGE — the draws are keyed, so a second call with a larger buffer is exact.
+ * The sharded handle (resource G+1) returns one instance's states, categories, outJumps, outPatternTotals, event counts and events
+ * byte for byte (a shard's events follow the earlier shards'); outRowTotals is the shards' sums added in shard order.
+ * Errors: BEAGLE_ERROR_OUT_OF_RANGE for registerCount outside 1..8, an unknown register-flag bit, simulantCount outside 1..1024,
+ * infinitesimalMatrix NULL or not finite or with mu not > 0, histories asked for with simulantCount > 1 or without nodeHeights, all
+ * outputs NULL, a bad categoryRatesIndex, the errors of beagleMi355SampleAncestralStates, and a full event buffer (above);
+ * BEAGLE_ERROR_NO_IMPLEMENTATION with more than one pattern partition; BEAGLE_ERROR_FLOATING_POINT when a draw failed, P_ij of a
+ * drawn pair is not finite and > 0, or some value is not finite — everything else is still written. */
+int beagleMi355SampleMarkovJumpsUniformized(int instance, const int* nodes, int nodeCount, const double* branchTimes,
+                                            const double* branchRates, const double* nodeHeights, const double* infinitesimalMatrix,
+                                            int categoryRatesIndex, int categoryWeightsIndex, int stateFrequenciesIndex,
+                                            const double* registers, const int* registerFlags, int registerCount, int simulantCount,
+                                            unsigned long long seed, int flags, unsigned char* outStates, int* outRateCategories,
+                                            double* outJumps, double* outPatternTotals, double* outRowTotals, int* outEventCounts,
+                                            long long eventCapacity, double* outEventHeights, unsigned char* outEventStates,
+                                            long long* outEventTotal, long long* outFallbacks);
 /* For the JNI shim: getPartials / getSiteLogLikelihoods whose result STAYS in the engine's pinned host buffer — *outPinned,
  * *outCount doubles, valid until the next call on the instance — so that it reaches the Java array with one copy
  * (Set<Type>ArrayRegion) instead of two.  BEAGLE_ERROR_NO_IMPLEMENTATION on the sharded instance: use the ordinary call. */

@@ -518,6 +518,12 @@ int btlNodeBranchTime(void* h, int node, double* out2) {
     out2[1] = t->branchRate[node];
     return 0;
 }
+int btlNodeHeight(void* h, int node, double* out) {
+    TreeLikelihood* t = (TreeLikelihood*)h;
+    if (node < 0 || node >= t->nodeCount) return BEAGLE_ERROR_OUT_OF_RANGE;
+    *out = t->height[node];
+    return 0;
+}
 int btlEigenIndex(void* h) { return ((TreeLikelihood*)h)->eigenBufferHelper.getOffsetIndex(0); }
 int btlNodeScaleIndex(void* h, int node) { TreeLikelihood* t = (TreeLikelihood*)h; return t->scaleBufferIndices[node - t->tipCount]; }
 int btlCumulativeScaleIndex(void* h) {
