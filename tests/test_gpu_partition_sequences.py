@@ -36,9 +36,9 @@ def site_rel(a, b):
 class Case:
     """One engine instance with K partitions (each its own eigen system and category rates) and per-partition buffer sets (BEAST's partialBufferHelper[i]: set j holds internal
     node n at T + j (T - 1) + n - T), one oracle instance per non-empty partition, and — shared_model — one unpartitioned oracle
-    instance over all patterns."""
+    instance over all patterns.  env: BEAGLE_MI355_* switches in force while the engine instance is created (tests/test_gpu_switches.py)."""
 
-    def __init__(self, S, K, oracle_lib, scaling=False, seed=0, shared_model=False, sizes=None, ids=None, resource=(1,), T=10, C=4):
+    def __init__(self, S, K, oracle_lib, scaling=False, seed=0, shared_model=False, sizes=None, ids=None, resource=(1,), T=10, C=4, env=None):
         sizes, ids = (sizes, ids) if sizes is not None else LAYOUTS[K]
         self.tree, wls = helpers.two_partitions(S, T, sizes, seed=seed + 31 * S + K)
         # every partition integrates its root with the same category weights and state frequencies (a whole-range root call names
@@ -58,7 +58,16 @@ class Case:
             self.ranges[k] = (off, off + w.pattern_count)
             off += w.pattern_count
         self.cum = T - 1                                        # scale buffers: 0..T-2 per node, T-1 and T cumulative
-        self.eng = bm.beagle.Beagle(T, T + K * (T - 1), T, S, self.P, K, K * self.nodes, C, T + 1, resourceList=resource)
+        old = {k: os.environ.get(k) for k in (env or {})}
+        os.environ.update(env or {})
+        try:
+            self.eng = bm.beagle.Beagle(T, T + K * (T - 1), T, S, self.P, K, K * self.nodes, C, T + 1, resourceList=resource)
+        finally:
+            for k, v in old.items():
+                if v is None:
+                    os.environ.pop(k, None)
+                else:
+                    os.environ[k] = v
         self.ora = [bm.beagle.Beagle(T, 2 * T - 1, T, S, w.pattern_count, 1, self.nodes, C, T + 1, library=oracle_lib) for w in wls]
         self.whole = bm.beagle.Beagle(T, 2 * T - 1, T, S, self.P, 1, self.nodes, C, T + 1, library=oracle_lib) if shared_model else None
         e = self.eng

@@ -131,3 +131,56 @@ def test_a_list_that_names_other_buffers_takes_the_general_kernel(oracle_lib):
     assert res["0"][1] == (1, 0, 0) and res["1"][1] == (0, 0, 0)
     for a, b in zip(res["0"][0], res["1"][0]):
         assert np.max(np.abs(a - b)) <= 1e-12 * max(1.0, float(np.max(np.abs(b))))
+
+
+def test_reset_of_a_per_node_buffer_the_walk_wrote_takes_the_general_kernel():
+    """Raw calls: the walk writes every internal node's factors; resetScaleFactors then clears ONE of those per-node buffers before the
+    cumulative buffer is reset and all of them are accumulated.  The per-slice products no longer describe the buffers: the general
+    kernel must answer, with what NO_SLICE_SUMS=1 gives."""
+    wl = helpers.random_workload(60, 900, 4, 4, seed=9393, tree_kind="coalescent")
+    res = {}
+    for mode in ("0", "1"):
+        os.environ["BEAGLE_MI355_NO_SLICE_SUMS"] = mode
+        try:
+            tl = BeagleTreeLikelihood(wl, rescaling=RESCALE_ALWAYS, delay_rescaling=False)
+        finally:
+            del os.environ["BEAGLE_MI355_NO_SLICE_SUMS"]
+        raw = bm.beagle.Beagle.attach(tl)
+        tl.getLogLikelihood()
+        idx = [tl.node_scale_index(n) for n in range(wl.tree.tip_count, wl.tree.node_count)]
+        cum = tl.cumulative_scale_index()
+        full = raw.getLogScaleFactors(cum).copy()
+        n0 = raw.walkLaunchInfo()["slice_accumulations"]
+        lost = raw.getLogScaleFactors(idx[7]).copy()
+        raw.resetScaleFactors(idx[7])
+        raw.resetScaleFactors(cum)
+        raw.accumulateScaleFactors(idx, len(idx), cum)
+        res[mode] = (raw.getLogScaleFactors(cum).copy(), full, lost, raw.walkLaunchInfo()["slice_accumulations"] - n0)
+        tl.close()
+    assert res["0"][3] == 0 and res["1"][3] == 0
+    assert np.any(res["1"][2] != 0.0)                                  # (the cleared buffer held factors: the test can tell)
+    for k in range(2):
+        a, b = res["0"][k], res["1"][k]
+        assert np.max(np.abs(a - b)) <= 1e-12 * max(1.0, float(np.max(np.abs(b))))
+    # the general kernel's sum without the cleared buffer's factors
+    want = res["1"][1] - res["1"][2]
+    assert np.max(np.abs(res["0"][0] - want)) <= 1e-12 * max(1.0, float(np.max(np.abs(want))))
+
+
+@pytest.mark.parametrize("T,P,C", [(300, 5000, 4), (64, 129, 1)])
+def test_always_chain_with_every_workgroup_serving_itself(T, P, C, oracle_lib):
+    """BEAGLE_MI355_WALK_SPIN_US=0 (every workgroup computes the slices it reads from itself: the forward-progress path) leaves per-slice
+    products too; the ALWAYS chain against NO_SLICE_SUMS=1 to rounding, as test_always_rescaling_adds_slice_products does."""
+    wl = helpers.random_workload(T, P, 4, C, seed=9500 + T, tree_kind="coalescent")
+    sv, sc, ss, _, sinfo = chain(wl, RESCALE_ALWAYS, {"BEAGLE_MI355_NO_SLICE_SUMS": "0", "BEAGLE_MI355_WALK_SPIN_US": "0"})
+    gv, gc, gs, _, ginfo = chain(wl, RESCALE_ALWAYS, {"BEAGLE_MI355_NO_SLICE_SUMS": "1"})
+    assert sinfo["slice_accumulations"] >= 3 and ginfo["slice_accumulations"] == 0
+    for a, b in zip(sc, gc):
+        assert np.max(np.abs(a - b)) <= 1e-12 * max(1.0, float(np.max(np.abs(b))))
+    for a, b in zip(sv, gv):
+        assert helpers.rel_err(a, b) <= 1e-13
+    assert np.max(np.abs(ss - gs) / np.abs(gs)) <= 1e-12
+    o = BeagleTreeLikelihood(wl, library=oracle_lib, rescaling=RESCALE_ALWAYS, delay_rescaling=False)
+    ref = o.getLogLikelihood()
+    o.close()
+    assert helpers.rel_err(sv[0], ref) <= 1e-10
