@@ -29,6 +29,13 @@ csrc/sharded.cpp: one engine instance per GPU on its own host thread, ncclAllRed
 
 Prints ONE JSON line on rank 0.  `--dump-outputs DIR`: after the timed steps, what the last of them computed goes to DIR/<name>.npy
 (dump_outputs), so that two builds given the same arguments — the same seeded inputs — can be compared output for output.
+
+A plain run does what the headline figure needs and nothing else: it generates the workload, sets up, warms up, times the steps,
+dumps if asked to and prints the line.  `--full` adds everything else the line can carry, each behind its own `--no-*` switch:
+the other caller protocol's figure, the CPU baseline and its cross-check of the site values, the partial-update side record,
+roofline.traffic measured in this run (rocprofv3 re-runs), the in-library route, the 12 500-pattern shard point and the other
+BASELINE configurations (child runs).  The headline's steps are the same either way.  No run reads a workload an earlier run
+wrote unless `--cache DIR` names a directory to keep them in.
 """
 import argparse
 import hashlib
@@ -56,8 +63,9 @@ def kernel_source_hash():
 
 
 def default_cache_dir():
-    """The generated workloads' directory: one per user under the temporary directory (a machine's /tmp is shared, and a
-    directory another user made is not writable by this one)."""
+    """A directory for generated workloads shared by the development tools (tools/*_bench.py; `bench.py --cache` takes it too):
+    one per user under the temporary directory (a machine's /tmp is shared, and a directory another user made is not writable
+    by this one)."""
     import tempfile
     return os.path.join(tempfile.gettempdir(), "beagle_mi355_cache-%d" % os.getuid())
 
@@ -184,7 +192,7 @@ def perturbed_models(bm, wl, config):
     return out
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
@@ -196,10 +204,14 @@ def main():
     ap.add_argument("--tree", default="coalescent", choices=["coalescent", "yule", "caterpillar"])
     ap.add_argument("--real", default="", choices=["", "benchmark1", "benchmark2"],
                     help="config D on a REAL alignment of the reference's examples/Benchmarks (tests/golden/<name>_patterns.npz) instead of the synthetic stand-in")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything besides the headline figure (module docstring); the --no-* switches below leave out parts of it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--patterns", type=int, default=0, help="development: keep only the first N patterns (size of one shard of an N-GPU job)")
     ap.add_argument("--force-sharded", action="store_true", help="development: take the multi-GPU code path (process group, device-side sum, all-reduce) even with one rank")
-    ap.add_argument("--cache", default=default_cache_dir(), help="directory for the generated workload ('' = off)")
+    ap.add_argument("--cache", default=None,
+                    help="directory to keep generated workloads in and read them back from, across runs (development; '' = off).  Default: a plain "
+                         "run keeps none, a --full run one of its own for the child runs it starts, removed when it ends")
     ap.add_argument("--cpu-sample", type=int, default=0, help="patterns in the CPU-baseline sample (0 = sized for ~10-20 s of CPU work)")
     ap.add_argument("--rescaling", default="dynamic", choices=["dynamic", "always", "none"],
                     help="dynamic (default, the metric's protocol): steady state = read mode, every 100th evaluation recomputes the factors; "
@@ -222,11 +234,16 @@ def main():
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
                     help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float64, 64 MB at most in all): "
                          "lnL, site_lnL (per pattern), and for config E partition_lnL")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
     if args.steps < 1 or args.warmup < 0:
         raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+def main():
+    args = parse_args()
     if args.route == "ranks" and args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(args.gpus))          # started plainly: bring up the N ranks ourselves
     if args.selftest_launcher:
@@ -247,6 +264,16 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    if args.cache is None:
+        # no workload file outlives the run: a plain run keeps none; a --full run's child runs (rocprofv3 re-runs, other configs)
+        # read the workloads it generated from a directory of its own
+        args.cache = ""
+        if args.full and world == 1:
+            import atexit
+            import shutil
+            import tempfile
+            args.cache = tempfile.mkdtemp(prefix="bench_workloads_")
+            atexit.register(shutil.rmtree, args.cache, True)
     if args.route == "library":
         if world > 1:
             raise SystemExit("--route library is ONE process driving all GPUs; do not start it under torch.distributed.run")
@@ -301,7 +328,7 @@ def main():
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
-    if rank == 0 and out is not None and args.route == "ranks" and not args.no_library_route and args.config != "E":
+    if rank == 0 and out is not None and args.full and args.route == "ranks" and not args.no_library_route and args.config != "E":
         # the other multi-GPU route on the same workload (a shorter run), after this route's instances and process group are gone
         try:
             if world > 1:
@@ -312,13 +339,13 @@ def main():
                 out["library_route"] = library_route(args, bm, wl, world, torch, device, BeagleTreeLikelihood, RESCALE_DYNAMIC)
         except Exception as e:                                        # noqa: BLE001  (must not cost the main line)
             out["library_route"] = {"error": "%s: %s" % (type(e).__name__, e)}
-    if (rank == 0 and out is not None and world == 1 and args.route == "ranks" and args.config == "A" and args.scale == 1.0
+    if (rank == 0 and out is not None and args.full and world == 1 and args.route == "ranks" and args.config == "A" and args.scale == 1.0
             and not args.patterns and not args.no_side_records):
         try:
             out["shard_point"] = shard_point(args, bm, wl, torch, device, res, ShardedTreeLikelihood, BeagleTreeLikelihood, RESCALE_DYNAMIC)
         except Exception as e:                                        # noqa: BLE001
             out["shard_point"] = {"error": "%s: %s" % (type(e).__name__, e)}
-    if (rank == 0 and out is not None and world == 1 and args.route == "ranks" and args.config == "A" and args.scale == 1.0
+    if (rank == 0 and out is not None and args.full and world == 1 and args.route == "ranks" and args.config == "A" and args.scale == 1.0
             and not args.patterns and not args.no_side_records and not args.no_other_configs):
         try:
             out["other_configs"] = other_configs(args)
@@ -340,7 +367,7 @@ def main():
 def other_configs(args, budget_s=420.0):
     """BASELINE.json's other configurations on the same box, in the same run as the headline: B (20 states), C (61 states), D on
     the reference's own examples/Benchmarks/benchmark1.xml alignment (tests/golden fixture) and E (partitioned), each as a child
-    `bench.py --config X` of >= 50 timed steps with its own kernel timer, in-run rocprofv3 traffic passes and CPU baseline (a
+    `bench.py --full --config X` of >= 50 timed steps with its own kernel timer, in-run rocprofv3 traffic passes and CPU baseline (a
     shorter one: --cpu-seconds 4), cut down to the figures a reader compares.  A child that fails or overruns costs only its own
     entry; the whole record stops starting children once `budget_s` is spent."""
     import subprocess
@@ -351,7 +378,7 @@ def other_configs(args, budget_s=420.0):
         if left < 30.0:
             rec[name] = {"error": "not started: the record's time budget (%.0f s) was spent" % budget_s}
             continue
-        cmd = [sys.executable, os.path.abspath(__file__), "--config", name, "--steps", str(steps), "--warmup", str(warm), "--no-library-route",
+        cmd = [sys.executable, os.path.abspath(__file__), "--full", "--config", name, "--steps", str(steps), "--warmup", str(warm), "--no-library-route",
                "--no-side-records", "--no-other-configs", "--cpu-seconds", "4", "--cache", args.cache] + extra
         t0 = time.time()
         try:
@@ -526,14 +553,15 @@ def live_traffic(args, kernel):
 
 def traffic_for(args, kernel, world, rank):
     """roofline.traffic: live (live_traffic) on a 1-GPU run when rocprofv3 is there, else replayed from the committed profile
-    of the same build (profiled_traffic) and labelled so."""
-    if world == 1 and rank == 0 and not args.no_live_traffic:
+    of the same build (profiled_traffic) and labelled so.  A plain run takes no re-runs: --full measures it."""
+    if world == 1 and rank == 0 and args.full and not args.no_live_traffic:
         rec, note = live_traffic(args, kernel)
         if rec:
             return rec, note
         live_note = note
     else:
-        live_note = "not measured live (%s)" % ("child of a profiled run or --no-live-traffic" if args.no_live_traffic else "multi-GPU run")
+        live_note = "not measured live (%s)" % ("child of a profiled run or --no-live-traffic" if args.no_live_traffic else
+                                                 "a plain run: --full measures it" if not args.full else "multi-GPU run")
     if args.patterns or args.scale != 1.0 or args.real or args.rescaling != "dynamic":
         return None, live_note + "; no replay: not the profiled size / protocol"
     rec, note = profiled_traffic(args.config)
@@ -590,7 +618,9 @@ def bench_single(args, bm, wl, rank, world, dist, device, res, t_gen, sharded, S
 
     # the other caller protocol, for the record (a shorter run of the same loop) — BEFORE the main measurement: whatever
     # bench.py measures first finds a device that has idled through the seconds of workload generation, and the main line
-    # should not be the one that pays for that (step_ms of a cold start: profiles/r04_experiments.txt)
+    # should not be the one that pays for that (step_ms of a cold start: profiles/r04_experiments.txt).  A plain run takes these
+    # steps too and only leaves their figure out: the timed steps start from the state they have always started from (the
+    # clocks, and the evaluation count DYNAMIC rescaling recomputes its factors by)
     other = None
     if world == 1:
         keep = args.caller
@@ -599,7 +629,8 @@ def bench_single(args, bm, wl, rank, world, dist, device, res, t_gen, sharded, S
             step(i)                                   # (its first calls allocate: read-back buffers, numpy arrays)
         n2 = max(30, args.steps // 4)
         e2, _ = timed_loop(torch, device, dist, n2, step)
-        other = {"caller": args.caller, "evals_per_s": round(n2 / e2, 3), "ms_per_step": round(1e3 * e2 / n2, 4), "steps": n2}
+        if args.full:
+            other = {"caller": args.caller, "evals_per_s": round(n2 / e2, 3), "ms_per_step": round(1e3 * e2 / n2, 4), "steps": n2}
         args.caller = keep
 
     for i in range(args.warmup):
@@ -724,10 +755,10 @@ def bench_single(args, bm, wl, rank, world, dist, device, res, t_gen, sharded, S
         collective_name = ("ncclAllReduce inside the engine, on its stream (RCCL over xGMI; torch.distributed only carried the communicator id)"
                            if sharded and getattr(tl, "collective", "") == "engine" else "torch.distributed over RCCL")
         cpu = None
-        if n_gpus == 1 and args.route == "ranks" and not args.no_cpu_baseline:
+        if n_gpus == 1 and args.route == "ranks" and args.full and not args.no_cpu_baseline:
             cpu = cpu_baseline(bm, wl, args.cpu_sample, tl, seconds=args.cpu_seconds)
         partial = None           # (after the CPU cross-check, which reads this instance's site values of the unmoved tree)
-        if world == 1 and args.route == "ranks" and not sharded and args.config in ("A", "D") and not args.no_side_records:
+        if world == 1 and args.route == "ranks" and not sharded and args.config in ("A", "D") and args.full and not args.no_side_records:
             try:
                 partial = partial_update_point(bm, wl, tl, raw, handles=handles)
             except Exception as e:                                        # noqa: BLE001  (must not cost the main line)
@@ -739,7 +770,7 @@ def bench_single(args, bm, wl, rank, world, dist, device, res, t_gen, sharded, S
             "ms_per_step_median": round(1e3 * per_step[len(per_step) // 2], 4) if per_step else None,
             "ms_per_step_max": round(1e3 * per_step[-1], 4) if per_step else None,
             "higher_is_better": True, "scaling": "strong",
-            "vs_baseline": None, "dtype": "f64", "rccl": rccl,
+            "vs_baseline": None, "dtype": "f64", "rccl": rccl, "full": args.full,
             "data": ("real alignment of examples/Benchmarks/%s.xml (tests/golden), seeded coalescent tree" % args.real) if args.real else "synthetic",
             "route": args.route,
             "config": {"workload": "%s: %d taxa x %d unique patterns, %d states, %d rate categories, %s tree (%d dependency levels), "
@@ -1039,7 +1070,7 @@ def bench_partitioned(args, bm, pw, rank, world, dist, device, res, t_gen):
         alg = sum(prune_bytes_per_eval(w) for w in local_pw.parts)
         achieved = moved / kernel_s / 1e9 if kernel_s > 0 else 0.0
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             cpu = cpu_baseline_partitioned(bm, pw, seconds=args.cpu_seconds)
             # ... and its per-partition values beside this instance's for the same (unperturbed) branch rates
             tl.set_branch_rates(rates0)
@@ -1047,7 +1078,7 @@ def bench_partitioned(args, bm, pw, rank, world, dist, device, res, t_gen):
             cpu["gpu_vs_cpu_partition_lnL_max_rel_err"] = float(max(abs(a - b) / abs(b) for a, b in zip(gpu_parts, cpu.pop("partition_lnL"))))
         prof, prof_note = traffic_for(args, "k_walk4", world, rank)
         partial = None
-        if world == 1 and not args.no_side_records:
+        if world == 1 and args.full and not args.no_side_records:
             try:
                 partial = partial_update_point_partitioned(tl, local_pw)
             except Exception as e:                                        # noqa: BLE001  (must not cost the main line)
@@ -1056,7 +1087,7 @@ def bench_partitioned(args, bm, pw, rank, world, dist, device, res, t_gen):
             "metric": "full-tree lnL evals/sec", "value": round(args.steps / elapsed, 3), "unit": "evals/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 4),
             "ms_per_step_median": round(1e3 * per_step[len(per_step) // 2], 4) if per_step else None,
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic", "full": args.full,
             "config": {"workload": "%s: %d taxa, unique patterns per partition %s, 4 states, %d rate categories, one instance, "
                                    "updatePartialsByPartition, new branch rates every step" % (pw.name, pw.tip_count, pw.pattern_counts, c_),
                        "patterns_per_gpu": p_, "parallelism": "pattern-shard x%d of every partition + 1 all-reduce of %d doubles" % (world, k)},

@@ -7,12 +7,12 @@
 #   2. --pmc FETCH_SIZE         HBM/fabric read traffic per dispatch
 #   3. --pmc WRITE_SIZE         HBM/fabric write traffic per dispatch
 #   4. --pmc SQ_*               where the waves' cycles go (parked / issue-stalled / issuing)
-# Raw output lands in gpurun_out/prof_<round><tag>/ (scratch); profiles/summarize.py turns it into the tracked
-# summaries under profiles/.
+# Raw output lands in $PROFILE_RAW/prof_<round><tag>/ (scratch; default: beagle_mi355_profiles under the temporary directory);
+# profiles/summarize.py turns it into the tracked summaries under profiles/.
 R=${1:-r02}; shift
 TAG=${TAG:-}
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
-OUT=$ROOT/gpurun_out/prof_$R$TAG
+OUT=${PROFILE_RAW:-${TMPDIR:-/tmp}/beagle_mi355_profiles}/prof_$R$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 STEPS=${STEPS:-20}

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Turn the raw rocprofv3 output of profiles/collect.sh (gpurun_out/prof_<round><tag>/) into the tracked summaries:
+"""Turn the raw rocprofv3 output of profiles/collect.sh ($PROFILE_RAW/prof_<round><tag>/) into the tracked summaries:
 
   profiles/<round><tag>_kernel_stats.csv   rocprofv3 --kernel-trace --stats summary (verbatim copy)
   profiles/<round><tag>_bench.json         the bench line printed by the profiled command
@@ -35,7 +35,7 @@ def main():
     tag = sys.argv[1] if len(sys.argv) > 1 else "r02"
     config = sys.argv[2] if len(sys.argv) > 2 else "A"
     kernel = sys.argv[3] if len(sys.argv) > 3 else "k_walk4"
-    src = os.path.join(ROOT, "gpurun_out", "prof_" + tag)
+    src = os.path.join(os.environ.get("PROFILE_RAW") or os.path.join(os.environ.get("TMPDIR") or "/tmp", "beagle_mi355_profiles"), "prof_" + tag)
     out = os.path.join(ROOT, "profiles")
     for p in glob.glob(os.path.join(src, "kt", "**", "*kernel_stats.csv"), recursive=True):
         shutil.copy(p, os.path.join(out, tag + "_kernel_stats.csv"))
@@ -60,7 +60,7 @@ def main():
     rec["kernel_us_per_eval_unprofiled"] = bench["roofline"].get("kernel_us_per_eval")
     rec["HBM_GBps_from_counters"] = round(rec["bytes_per_eval"] / (bench["roofline"]["kernel_us_per_eval"] * 1e-6) / 1e9, 1)
     rec["corrections"] = "FETCH_SIZE x2 (gfx950 128-B requests tallied at 64 B), x1024 B per unit; WRITE_SIZE x1024"
-    rec["source"] = "gpurun_out/prof_%s (rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE, separate passes)" % tag
+    rec["source"] = "prof_%s (rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE, separate passes)" % tag
     path = os.path.join(out, "hbm_traffic.json")
     allrec = json.load(open(path)) if os.path.exists(path) else {}
     if "kernel" in allrec:          # round-1 layout (one flat record): start over

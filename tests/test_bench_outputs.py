@@ -1,5 +1,6 @@
-"""bench.py's --dump-outputs files (what the timed path computed, 64 MB at most, a fixed sample of anything larger) and its workload
-cache (one file per version of the generator sources) on the CPU; on the GPU, that the files hold the last timed step's values."""
+"""bench.py's --dump-outputs files (what the timed path computed, 64 MB at most, a fixed sample of anything larger), its workload
+cache (one file per version of the generator sources) and what a plain run leaves to --full, on the CPU; on the GPU, that the files
+hold the last timed step's values and that --full adds its records without changing them."""
 import json
 import os
 import subprocess
@@ -44,6 +45,32 @@ def test_workload_cache_file_follows_the_generator_sources(tmp_path):
     assert f == bench.workload_cache_file(d, "A", 1.0, "coalescent")
     assert f != bench.workload_cache_file(d, "B", 1.0, "coalescent")
     assert bench.workload_cache_file("", "A", 1.0, "coalescent") is None
+
+
+def test_a_plain_run_is_the_default_and_keeps_no_workload_file():
+    plain = bench.parse_args(["--gpus", "1", "--steps", "5", "--warmup", "2"])
+    assert plain.full is False and plain.cache is None
+    assert bench.parse_args(["--full"]).full is True
+
+
+def test_other_configs_are_full_child_runs_sharing_the_cache(monkeypatch):
+    """--full's other configurations: each a child `bench.py --full` (its own CPU baseline and traffic passes) reading and writing
+    the parent run's workload directory."""
+    import types
+    cmds = []
+
+    def fake_run(cmd, **kw):
+        cmds.append(cmd)
+        line = {"value": 1.0, "unit": "evals/s", "steps": int(cmd[cmd.index("--steps") + 1]), "roofline": {}, "cpu_baseline": {"value": 0.5}}
+        return types.SimpleNamespace(returncode=0, stdout="banner\n" + json.dumps(line) + "\n", stderr="")
+    monkeypatch.setattr(subprocess, "run", fake_run)
+    args = bench.parse_args(["--full"])
+    args.cache = "/nonexistent/workloads"
+    rec = bench.other_configs(args)
+    assert [c[c.index("--config") + 1] for c in cmds] == ["B", "C", "D", "E"]
+    for c in cmds:
+        assert "--full" in c and c[c.index("--cache") + 1] == "/nonexistent/workloads"
+    assert all(rec[k]["value"] == 1.0 and rec[k]["cpu_baseline"] == {"value": 0.5} for k in "BCDE")
 
 
 def test_steps_below_one_is_refused():
@@ -102,9 +129,9 @@ def test_cache_that_cannot_be_written_costs_only_the_cache(tmp_path):
 SHORT = ["--no-cpu-baseline", "--no-live-traffic", "--no-library-route", "--no-side-records", "--no-other-configs"]
 
 
-def _bench(out_dir, *args, env=None):
+def _bench(out_dir, *args, env=None, switches=SHORT):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--warmup", "2", "--dump-outputs", str(out_dir)]
-                       + SHORT + list(args), capture_output=True, text=True, timeout=600, env=env)
+                       + switches + list(args), capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     return line, {f[:-4]: np.load(os.path.join(out_dir, f)) for f in os.listdir(out_dir)}
@@ -145,3 +172,20 @@ def test_partitioned_dump_and_its_sharded_code_path(tmp_path):
     _, ds = _bench(tmp_path / "sharded", "--config", "E", "--steps", "3", "--cache", str(tmp_path / "cache"), "--force-sharded", env=env)
     assert np.array_equal(d["partition_lnL"], ds["partition_lnL"]) and np.array_equal(d["site_lnL"], ds["site_lnL"])
     assert abs(float(ds["lnL"][0]) - line["lnL"]) <= 1e-12 * abs(line["lnL"])     # (the sum over partitions taken on the device)
+
+
+@pytest.mark.gpu
+def test_full_adds_its_records_and_leaves_the_headline_steps_alone(tmp_path):
+    """config D on the benchmark1 alignment: a plain run carries none of --full's records and measures no traffic of its own; a
+    --full run carries them, and its timed steps compute the same numbers, to the bit, as the plain run's."""
+    real = ("--config", "D", "--real", "benchmark1", "--steps", "3")
+    plain, dp = _bench(tmp_path / "plain", *real, switches=[])
+    assert plain["full"] is False and plain["steps"] == 3 and plain["ms_per_step"] > 0
+    assert plain["cpu_baseline"] is None and plain["other_caller"] is None and plain["partial_update"] is None
+    assert "measured in this run" not in plain["roofline"]["traffic_source"]
+    full, df = _bench(tmp_path / "full", *real, "--cpu-seconds", "1", switches=["--full", "--no-live-traffic"])
+    assert full["full"] is True
+    assert full["cpu_baseline"]["gpu_vs_cpu_site_lnL_max_rel_err"] <= 1e-10
+    assert full["other_caller"]["caller"] == "btl" and "error" not in full["partial_update"]
+    assert full["lnL"] == plain["lnL"] and full["lnL_first_eval"] == plain["lnL_first_eval"]
+    assert set(df) == set(dp) and all(np.array_equal(df[k], dp[k]) for k in dp)

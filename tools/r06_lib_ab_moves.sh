@@ -4,6 +4,6 @@ pu() { python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitli
 for pass in 1 2; do for L in "$@"; do
   export BEAGLE_MI355_ENGINE_LIB=$R/$L
   echo "pass $pass $L"
-  echo "   D1:      $(timeout 200 python bench.py --real benchmark1 --steps 200 --warmup 10 --no-cpu-baseline --no-live-traffic --no-library-route --no-other-configs 2>/dev/null | pu)"
-  echo "   D synth: $(timeout 200 python bench.py --config D --steps 200 --warmup 10 --no-cpu-baseline --no-live-traffic --no-library-route --no-other-configs 2>/dev/null | pu)"
+  echo "   D1:      $(timeout 200 python bench.py --full --real benchmark1 --steps 200 --warmup 10 --no-cpu-baseline --no-live-traffic --no-library-route --no-other-configs 2>/dev/null | pu)"
+  echo "   D synth: $(timeout 200 python bench.py --full --config D --steps 200 --warmup 10 --no-cpu-baseline --no-live-traffic --no-library-route --no-other-configs 2>/dev/null | pu)"
 done; done

@@ -5,7 +5,7 @@ line() { python -c "import sys,json; d=json.loads(sys.stdin.read().strip().split
 for pass in 1 2; do for t in 0 1; do
   export BEAGLE_MI355_NO_XCD_MAP=$t
   echo "== pass $pass NO_XCD_MAP=$t"
-  echo "E (with traffic passes): $(timeout 300 python bench.py --config E --steps 300 --warmup 20 --no-cpu-baseline --no-side-records 2>/dev/null | line)"
+  echo "E (with traffic passes): $(timeout 300 python bench.py --full --config E --steps 300 --warmup 20 --no-cpu-baseline --no-side-records 2>/dev/null | line)"
   echo "D real1: $(timeout 300 python bench.py --real benchmark1 --steps 300 --warmup 20 $common 2>/dev/null | line)"
   echo "D real2: $(timeout 300 python bench.py --real benchmark2 --steps 300 --warmup 20 $common 2>/dev/null | line)"
   echo "shard 6250: $(timeout 200 python bench.py --patterns 6250 --steps 300 --warmup 12 $common 2>/dev/null | line)"
