@@ -8,10 +8,11 @@ Layout (only what the hot path needs — SURVEY.md §8):
   treelikelihood.py   ctypes handle on the C++ host driver
   ancestral.py        ancestral-state draws on the device (AncestralStateBeagleTreeLikelihood's caller side)
   markovjumps.py      Markov-jump counts and rewards on the device (MarkovJumpsBeagleTreeLikelihood's caller side)
+  basta.py            the BASTA structured-coalescent likelihood on the device (BeagleBastaLikelihoodDelegate's caller side)
   inputs/   what feeds the engine: eigen systems, gamma rate categories, site patterns, trees, synthetic workloads
   sharding.py         pattern-block sharding across GPUs + the single lnL all-reduce
 
 The directory name contains a hyphen, so import it through the root-level shim: ``import beast_mcmc_amd``.
 """
-from . import ancestral, beagle, markovjumps, multipartition, treelikelihood          # noqa: F401
+from . import ancestral, basta, beagle, markovjumps, multipartition, treelikelihood          # noqa: F401
 from .inputs import patterns, siterates, substmodel, synth, trees   # noqa: F401

@@ -125,7 +125,10 @@ ABI_SYMBOLS = ["beagleGetVersion", "beagleGetCitation", "beagleGetResourceList",
               ["beagleMi355SetStream", "beagleMi355CalculateRootLogLikelihoodsDevice", "beagleMi355Synchronize",
                "beagleMi355KernelTimer", "beagleMi355DeviceBytes", "beagleMi355WalkStats", "beagleMi355GradientStats", "beagleMi355GetPartialsBatch", "beagleMi355SampleAncestralStates", "beagleMi355SampleMarkovJumps", "beagleMi355SampleMarkovJumpsUniformized",
                "beagleMi355GetPartialsPinned", "beagleMi355GetSiteLogLikelihoodsPinned",
-               "beagleMi355KernelTimerCalls", "beagleMi355WalkHealth", "beagleMi355WalkLaunchInfo", "beagleMi355RootFusedCount", "beagleMi355SitePrefetchCount", "beagleMi355KernelTimerRestart", "beagleMi355GetDimensions", "beagleMi355GetCommUniqueId", "beagleMi355CommInit", "beagleMi355CommInfo", "beagleMi355CalculateRootLogLikelihoodsAllReduce"]
+               "beagleMi355KernelTimerCalls", "beagleMi355WalkHealth", "beagleMi355WalkLaunchInfo", "beagleMi355RootFusedCount", "beagleMi355SitePrefetchCount", "beagleMi355KernelTimerRestart", "beagleMi355GetDimensions", "beagleMi355GetCommUniqueId", "beagleMi355CommInit", "beagleMi355CommInfo", "beagleMi355CalculateRootLogLikelihoodsAllReduce"] + \
+              ["beagleBasta" + k for k in ("AllocateCoalescentBuffers", "UpdatePartials", "AccumulatePartials", "GetBuffer", "GetBufferLength", "Stats",
+                                           "UpdatePartialsGrad", "UpdateTransitionMatricesGrad", "AccumulatePartialsGrad")]
+BASTA_OPERATION_SIZE = 8
 
 
 class EngineLibrary:
@@ -638,6 +641,42 @@ class Beagle:
             out["event_heights"] = out["event_heights"][:total.value]
             out["event_states"] = out["event_states"][:total.value]
         return out
+
+    # BASTA structured coalescent (beagle.basta.BeagleBasta; include/beagle_mi355.h beagleBasta*)
+    def allocateCoalescentBuffers(self, bufferCount, maxCoalescentIntervalCount, partialsBufferCount, initial, threadCount=-1):
+        f = self._ext("beagleBastaAllocateCoalescentBuffers", [C.c_int] * 6)
+        self._check("allocateCoalescentBuffers",
+                    f(self.instance, bufferCount, maxCoalescentIntervalCount, partialsBufferCount, initial, threadCount))
+
+    def updateBastaPartials(self, operations, operationCount, intervals, intervalCount, populationSizesIndex,
+                            coalescentProbabilityIndex):
+        ops, iv = _i(operations), _i(intervals)
+        f = self._ext("beagleBastaUpdatePartials", [C.c_int, _IP, C.c_int, _IP, C.c_int, C.c_int, C.c_int])
+        self._check("updateBastaPartials", f(self.instance, _ip(ops), operationCount, _ip(iv), intervalCount,
+                                             populationSizesIndex, coalescentProbabilityIndex))
+
+    def accumulateBastaPartials(self, operations, operationCount, intervals, intervalCount, intervalLengths,
+                                populationSizesIndex, coalescentProbabilityIndex, result):
+        """``result`` (a float64 array) is in/out: the log-density is ADDED to result[0]."""
+        ops, iv, ln = _i(operations), _i(intervals), _d(intervalLengths)
+        assert isinstance(result, np.ndarray) and result.dtype == np.float64 and result.flags.c_contiguous
+        f = self._ext("beagleBastaAccumulatePartials", [C.c_int, _IP, C.c_int, _IP, C.c_int, _DP, C.c_int, C.c_int, _DP])
+        self._check("accumulateBastaPartials", f(self.instance, _ip(ops), operationCount, _ip(iv), intervalCount, _dp(ln),
+                                                 populationSizesIndex, coalescentProbabilityIndex, _dp(result)))
+
+    def getBastaBuffer(self, index):
+        n = self._ext("beagleBastaGetBufferLength", [C.c_int, C.c_int])(self.instance, index)
+        if n < 0:
+            raise BeagleException("getBastaBuffer", n)
+        out = np.empty(n)
+        self._check("getBastaBuffer", self._ext("beagleBastaGetBuffer", [C.c_int, C.c_int, _DP])(self.instance, index, _dp(out)))
+        return out
+
+    def bastaStats(self):
+        """(uploads of an operation list, updates run as one launch, updates run interval by interval, partialsBufferCount)"""
+        out = (C.c_long * 4)()
+        self._check("bastaStats", self._ext("beagleBastaStats", [C.c_int, C.POINTER(C.c_long)])(self.instance, out))
+        return tuple(out)
 
     def walkStats(self):
         """Counters of the 4-state pattern walk since the last kernelTimer call (include/beagle_mi355.h)."""

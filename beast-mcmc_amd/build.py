@@ -1,6 +1,8 @@
 """In-tree build of the native pieces (explicit hipcc / g++ command lines, no build system):
 
   lib/libhmsbeagle-jni.so   HIP engine + C ABI + JNI shim, gfx950 only   (csrc/*.hip, csrc/*.cpp)
+  lib/libhmsbeagle-jni-bit.so   the natives of beagle.basta.BastaJNIWrapper: thin wrappers over the engine's beagleBasta* calls,
+                            linked against the engine library next to it   (jni_basta/*.cpp, plain g++)
   lib/libbeast_host.so      the caller stand-in: BeagleTreeLikelihood's call protocol in C++  (tools/host/tree_likelihood.cpp;
                             harness for tests and bench.py — in production the caller is BEAST's Java)
   lib/lab/libhmsbeagle-jni.so   (``--lab`` only) the same engine compiled with -DBEAGLE_MI355_LAB: the tuning knobs and timing
@@ -20,6 +22,7 @@ ROOT = os.path.dirname(HERE)
 LIB = os.path.join(HERE, "lib")
 CSRC = os.path.join(HERE, "csrc")
 HOST = os.path.join(ROOT, "tools", "host")
+JNI_BASTA = os.path.join(HERE, "jni_basta")
 
 
 def _newer(target, sources):
@@ -83,8 +86,22 @@ def build_host(force=False):
     return out
 
 
+def build_basta_jni(force=False):
+    """libhmsbeagle-jni-bit.so (the name BastaJNIWrapper loads): it holds no device code, finds the engine library in its own
+    directory ($ORIGIN) and exports the seven natives only (jni_basta/exports.map)."""
+    os.makedirs(LIB, exist_ok=True)
+    out = os.path.join(LIB, "libhmsbeagle-jni-bit.so")
+    engine = os.path.join(LIB, "libhmsbeagle-jni.so")
+    src = os.path.join(JNI_BASTA, "jni_basta.cpp")
+    exports = os.path.join(JNI_BASTA, "exports.map")
+    if force or _newer(out, [src, exports, engine, os.path.join(CSRC, "jni_min.h"), os.path.join(ROOT, "include", "beagle_mi355.h")]):
+        _run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-fvisibility=hidden", src, "-L" + LIB, "-l:libhmsbeagle-jni.so",
+              "-Wl,-rpath,$ORIGIN", "-Wl,--no-undefined", "-Wl,--version-script=" + exports, "-o", out])
+    return out
+
+
 def build_all(force=False):
-    return [build_engine(force), build_host(force)]
+    return [build_engine(force), build_basta_jni(force), build_host(force)]
 
 
 if __name__ == "__main__":

@@ -701,6 +701,7 @@ int beagleSetTipPartials(int instance, int tipIndex, const double* inPartials) {
 int beagleSetPartials(int instance, int bufferIndex, const double* inPartials) {
     if (mi355::isShardedHandle(instance)) { return mi355::shardedSetPerPatternDoubles(instance, inPartials, shardedStates(instance), shardedCategories(instance), [&](int h, const double* v) { return beagleSetPartials(h, bufferIndex, v); }); }
     GET_INSTANCE_KEEP_PENDING(instance);
+    if (in->basta) return bastaSetPartials(in, bufferIndex, inPartials);      // (a BASTA instance's vectors: engine_basta.cpp)
     if (badIndex(bufferIndex, in->partialsCount)) return BEAGLE_ERROR_OUT_OF_RANGE;
     // (a held-back pre-order list has its own copy of its root's pre-order partial — the buffer the gradient delegates rewrite
     // before every list — and waits unless this is one of the other buffers it reads or writes)
@@ -804,6 +805,7 @@ static int exportPartials(Instance* in, const int* bufferIndices, const int* sca
 int beagleGetPartials(int instance, int bufferIndex, int scaleIndex, double* outPartials) {
     if (mi355::isShardedHandle(instance)) { return mi355::shardedGetPerPatternDoubles(instance, outPartials, shardedStates(instance), shardedCategories(instance), [&](int h, double* v) { return beagleGetPartials(h, bufferIndex, scaleIndex, v); }); }
     GET_INSTANCE(instance);
+    if (in->basta) return bastaGetPartials(in, bufferIndex, outPartials);
     return exportPartials(in, &bufferIndex, &scaleIndex, 1, outPartials);
 }
 

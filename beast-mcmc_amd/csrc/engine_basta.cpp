@@ -1,0 +1,386 @@
+// engine_basta.cpp — the BASTA structured-coalescent calls (include/beagle_mi355.h beagleBasta*): what
+// BeagleBastaLikelihoodDelegate asks of its native library on top of an ordinary instance (one pattern, one category).
+//
+// State: a dense [buffer][S] array of vectors, separate from the pattern-major partials store (setPartials / getPartials of an
+// instance that has it go here), and coalescentBufferCount interval-indexed buffers (coalescent probabilities, e, f, g, h).
+//
+// beagleBastaUpdatePartials runs a whole operation list in a number of launches that does not depend on the interval count.
+// Operations of one interval are independent and an operation reads what earlier intervals wrote, so the list is a dependency
+// graph over buffer indices; the reference's lists give every vector one writer and one reader (a lineage's buffer advances with
+// every interval), which makes the graph a forest of chains that meet at coalescences.  analyse() checks exactly that — every
+// buffer written at most once, every produced input written as a `dest` in an EARLIER interval and read by one operation — and
+// then the list runs as ONE launch (kernels_basta.hip k_bastaUpdate<true>).  A list that is anything else still means what the
+// interval order says, so it runs interval by interval (k_bastaUpdate<false>, a launch each): correct for every list, and never
+// taken by a caller that numbers its buffers as the reference does.
+//
+// The 8-int list is the bulk of the traffic (16 MB at 1000 tips).  It is copied once into a pinned staging buffer and sent from
+// there with one asynchronous copy; beagleBastaAccumulatePartials compares the list it is handed with the staged one — length,
+// then contents (memcmp) — and uploads nothing when they are equal, which is what follows every beagleBastaUpdatePartials.
+#include "engine_internal.h"
+
+namespace mi355 {
+namespace eng {
+
+constexpr int BASTA_OP = 8;
+
+struct Basta {
+    int vectorCount = 0, maxIntervals = 0, bufferCount = 0, coalescentIndex = 0;
+    double* vectors = nullptr;                           // [vectorCount][S]
+    double* buffers = nullptr;                           // [bufferCount][maxIntervals * S]
+    double* intervalLogL = nullptr;                      // [maxIntervals + 1] terms of the last accumulate, [maxIntervals]: their sum
+    // the operation list and its intervals as last sent to the device
+    int* hOps = nullptr; int* dOps = nullptr; size_t opsCap = 0; int opCount = -1;
+    int* hIntervals = nullptr; int* dIntervals = nullptr; size_t intervalsCap = 0; int intervalCount = -1;
+    double* hLengths = nullptr; double* dLengths = nullptr; size_t lengthsCap = 0;
+    int* hLink = nullptr; int* dLink = nullptr; int* dLeaves = nullptr; unsigned* dTickets = nullptr; size_t linkCap = 0;   // (hLink: [2 n link | n leaves])
+    hipEvent_t sent = nullptr;                           // the last copy out of the pinned buffers
+    std::vector<int> writer, writes, intervalOf;         // analyse()'s scratch
+    long statUploads = 0, statChainCalls = 0, statIntervalCalls = 0;
+};
+
+namespace {
+
+int bastaInstance(int instance, Instance** out) {
+    if (mi355::isShardedHandle(instance)) return BEAGLE_ERROR_NO_IMPLEMENTATION;
+    Instance* in = lookup(instance);
+    if (!in) return BEAGLE_ERROR_UNINITIALIZED_INSTANCE;
+    if (hipSetDevice(in->device) != hipSuccess) return BEAGLE_ERROR_GENERAL;
+    if (in->P != 1 || in->C != 1) return BEAGLE_ERROR_NO_IMPLEMENTATION;
+    *out = in;
+    return 0;
+}
+
+void release(Instance* in, void* p, size_t bytes) {
+    if (!p) return;
+    in->allocations.erase(std::find(in->allocations.begin(), in->allocations.end(), p));
+    in->deviceBytes -= bytes;
+    hipFree(p);
+}
+
+// pinned host + device pair of at least `count` elements (grow-only; growing waits for the copies in flight)
+template <class T> int growPair(Instance* in, T*& h, T*& d, size_t& cap, size_t count) {
+    if (cap >= count) return 0;
+    HIP_TRY(hipStreamSynchronize(live(in)));
+    if (h) hipHostFree(h);
+    release(in, d, cap * sizeof(T));
+    h = nullptr; d = nullptr; cap = 0;
+    const size_t n = count + count / 4 + 64;
+    HIP_TRY(hipHostMalloc((void**)&h, n * sizeof(T), hipHostMallocDefault));
+    int rc = devAlloc(in, (void**)&d, n * sizeof(T)); if (rc) return rc;
+    cap = n;
+    return 0;
+}
+
+int checkList(const Instance* in, const Basta* b, const int* ops, int opCount, const int* intervals, int intervalCount,
+              int sizesIndex, int coalescentIndex) {
+    if (opCount < 0 || intervalCount < 1 || (opCount > 0 && !ops) || !intervals) return BEAGLE_ERROR_OUT_OF_RANGE;
+    if (badIndex(sizesIndex, in->eigenCount) || badIndex(coalescentIndex, b->bufferCount)) return BEAGLE_ERROR_OUT_OF_RANGE;
+    // every operation belongs to one interval: offsets start at 0, do not decrease and end at the operation count
+    if (intervals[0] != 0 || intervals[intervalCount - 1] != opCount) return BEAGLE_ERROR_OUT_OF_RANGE;
+    for (int k = 1; k < intervalCount; k++) if (intervals[k] < intervals[k - 1]) return BEAGLE_ERROR_OUT_OF_RANGE;
+    for (int k = 0; k < opCount; k++) {
+        const int* op = ops + (size_t)k * BASTA_OP;
+        if (badIndex(op[0], b->vectorCount) || badIndex(op[1], b->vectorCount) || badIndex(op[2], in->matrixCount) ||
+            badIndex(op[5], b->vectorCount) || badIndex(op[7], b->maxIntervals)) return BEAGLE_ERROR_OUT_OF_RANGE;
+        if (op[3] >= 0 && (badIndex(op[3], b->vectorCount) || badIndex(op[4], in->matrixCount) || badIndex(op[6], b->vectorCount)))
+            return BEAGLE_ERROR_OUT_OF_RANGE;
+    }
+    return 0;
+}
+
+// Is the list a forest of chains (see the head of this file)?  Fills link = [n][2] {reader of the result or -1, inputs of that
+// reader the list produces} and the starting operations.
+bool analyse(Basta* b, const int* ops, int n, const int* intervals, int intervalCount, int* link, int* leaves, int* nLeaves) {
+    b->writer.assign(b->vectorCount, -1); b->writes.assign(b->vectorCount, 0);
+    b->intervalOf.resize(n);
+    for (int t = 0; t + 1 < intervalCount; t++) for (int k = intervals[t]; k < intervals[t + 1]; k++) b->intervalOf[k] = t;
+    for (int k = 0; k < n; k++) {
+        const int* op = ops + (size_t)k * BASTA_OP;
+        b->writer[op[0]] = k;
+        if (++b->writes[op[0]] > 1) return false;
+        if (op[3] >= 0) {
+            if (++b->writes[op[5]] > 1 || ++b->writes[op[6]] > 1) return false;
+            if (op[5] == op[0] || op[6] == op[0]) return false;
+        }
+    }
+    for (int k = 0; k < n; k++) { link[2 * k] = -1; link[2 * k + 1] = 0; }
+    std::vector<char> seen(b->vectorCount, 0);
+    std::vector<int> produced(n, 0);
+    for (int k = 0; k < n; k++) {
+        const int* op = ops + (size_t)k * BASTA_OP;
+        for (int side = 0; side < 2; side++) {
+            const int x = op[side ? 3 : 1];
+            if (x < 0) continue;
+            if (b->writes[x] == 0) continue;                 // not written by this list: what the caller stored
+            const int w = b->writer[x];
+            if (w < 0 || ops[(size_t)w * BASTA_OP] != x) return false;          // an accumulation buffer read back
+            if (b->intervalOf[w] >= b->intervalOf[k]) return false;            // written later, or in the same interval
+            if (seen[x]) return false;                       // a second reader
+            seen[x] = 1;
+            link[2 * w] = k;
+            produced[k]++;
+        }
+    }
+    *nLeaves = 0;
+    for (int k = 0; k < n; k++) {
+        if (link[2 * k] >= 0) link[2 * k + 1] = produced[link[2 * k]];
+        if (produced[k] == 0) leaves[(*nLeaves)++] = k;
+    }
+    return true;
+}
+
+// the list and its intervals on the device: nothing is sent when they are what the device already holds
+int sendList(Instance* in, Basta* b, const int* ops, int n, const int* intervals, int intervalCount, bool* fresh) {
+    const size_t opInts = (size_t)n * BASTA_OP;
+    const bool same = b->opCount == n && b->intervalCount == intervalCount &&
+                      memcmp(b->hIntervals, intervals, (size_t)intervalCount * sizeof(int)) == 0 &&
+                      (opInts == 0 || memcmp(b->hOps, ops, opInts * sizeof(int)) == 0);
+    *fresh = !same;
+    if (same) return 0;
+    HIP_TRY(hipEventSynchronize(b->sent));                   // (the previous list has left the pinned buffers)
+    b->opCount = b->intervalCount = -1;
+    int rc = growPair(in, b->hOps, b->dOps, b->opsCap, opInts + 1); if (rc) return rc;
+    rc = growPair(in, b->hIntervals, b->dIntervals, b->intervalsCap, (size_t)intervalCount); if (rc) return rc;
+    if (opInts) memcpy(b->hOps, ops, opInts * sizeof(int));
+    memcpy(b->hIntervals, intervals, (size_t)intervalCount * sizeof(int));
+    hipStream_t s = live(in);
+    if (opInts) HIP_TRY(hipMemcpyAsync(b->dOps, b->hOps, opInts * sizeof(int), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(b->dIntervals, b->hIntervals, (size_t)intervalCount * sizeof(int), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(b->sent, s));
+    b->opCount = n; b->intervalCount = intervalCount;
+    b->statUploads++;
+    return 0;
+}
+
+}  // namespace
+
+int bastaSetPartials(Instance* in, int bufferIndex, const double* inPartials) {
+    Basta* b = in->basta;
+    if (badIndex(bufferIndex, b->vectorCount) || !inPartials) return BEAGLE_ERROR_OUT_OF_RANGE;
+    return upload(in, b->vectors + (size_t)bufferIndex * in->S, inPartials, (size_t)in->S * sizeof(double));
+}
+
+int bastaGetPartials(Instance* in, int bufferIndex, double* outPartials) {
+    Basta* b = in->basta;
+    if (badIndex(bufferIndex, b->vectorCount) || !outPartials) return BEAGLE_ERROR_OUT_OF_RANGE;
+    return download(in, outPartials, b->vectors + (size_t)bufferIndex * in->S, (size_t)in->S * sizeof(double));
+}
+
+void bastaFree(Instance* in) {
+    Basta* b = in->basta;
+    if (!b) return;
+    if (in->stream) hipStreamSynchronize(in->stream);
+    // (device memory is on the instance's allocation list and goes with it)
+    if (b->hOps) hipHostFree(b->hOps);
+    if (b->hIntervals) hipHostFree(b->hIntervals);
+    if (b->hLengths) hipHostFree(b->hLengths);
+    if (b->hLink) hipHostFree(b->hLink);
+    if (b->sent) hipEventDestroy(b->sent);
+    delete b;
+    in->basta = nullptr;
+}
+
+}  // namespace eng
+}  // namespace mi355
+
+using namespace mi355::eng;
+
+extern "C" {
+
+int beagleBastaAllocateCoalescentBuffers(int instance, int coalescentBufferCount, int maxCoalescentIntervalCount,
+                                         int partialsBufferCount, int initial, int threadCount) {
+    (void)threadCount;
+    Instance* in = nullptr;
+    int rc = bastaInstance(instance, &in); if (rc) return rc;
+    if (coalescentBufferCount < 1 || maxCoalescentIntervalCount < 1 || partialsBufferCount < 1) return BEAGLE_ERROR_OUT_OF_RANGE;
+    if (in->heldPre.held) { rc = executeHeldPre(in); if (rc) return rc; }
+    const size_t S = (size_t)in->S;
+    Basta* old = in->basta;
+    Basta* b = old;
+    if (!b) {
+        b = new Basta();
+        if (hipEventCreateWithFlags(&b->sent, hipEventDisableTiming) != hipSuccess) { delete b; return BEAGLE_ERROR_GENERAL; }
+    }
+    double* vectors = nullptr; double* buffers = nullptr; double* terms = nullptr;
+    const size_t vBytes = (size_t)partialsBufferCount * S * sizeof(double);
+    const size_t bBytes = (size_t)coalescentBufferCount * maxCoalescentIntervalCount * S * sizeof(double);
+    const size_t tBytes = ((size_t)maxCoalescentIntervalCount + 1) * sizeof(double);
+    rc = devAlloc(in, (void**)&vectors, vBytes);
+    if (!rc) rc = devAlloc(in, (void**)&buffers, bBytes);
+    if (!rc) rc = devAlloc(in, (void**)&terms, tBytes);
+    if (rc) { if (!old) { hipEventDestroy(b->sent); delete b; } return rc; }
+    hipStream_t s = live(in);
+    HIP_TRY(hipMemsetAsync(vectors, 0, vBytes, s));
+    HIP_TRY(hipMemsetAsync(buffers, 0, bBytes, s));
+    HIP_TRY(hipMemsetAsync(terms, 0, tBytes, s));
+    if (old && !initial && old->vectors)                     // a growing call keeps what setPartials (and the last update) stored
+        HIP_TRY(hipMemcpyAsync(vectors, old->vectors, std::min(vBytes, (size_t)old->vectorCount * S * sizeof(double)), hipMemcpyDeviceToDevice, s));
+    if (old) {
+        HIP_TRY(hipStreamSynchronize(s));
+        release(in, old->vectors, (size_t)old->vectorCount * S * sizeof(double));
+        release(in, old->buffers, (size_t)old->bufferCount * old->maxIntervals * S * sizeof(double));
+        release(in, old->intervalLogL, ((size_t)old->maxIntervals + 1) * sizeof(double));
+    }
+    b->vectors = vectors; b->buffers = buffers; b->intervalLogL = terms;
+    b->vectorCount = partialsBufferCount; b->maxIntervals = maxCoalescentIntervalCount; b->bufferCount = coalescentBufferCount;
+    b->coalescentIndex = 0;
+    in->basta = b;
+    return BEAGLE_SUCCESS;
+}
+
+int beagleBastaUpdatePartials(int instance, const int* operations, int operationCount, const int* intervals, int intervalCount,
+                              int populationSizesIndex, int coalescentProbabilityIndex) {
+    Instance* in = nullptr;
+    int rc = bastaInstance(instance, &in); if (rc) return rc;
+    Basta* b = in->basta;
+    if (!b) return BEAGLE_ERROR_NO_IMPLEMENTATION;
+    rc = checkList(in, b, operations, operationCount, intervals, intervalCount, populationSizesIndex, coalescentProbabilityIndex);
+    if (rc) return rc;
+    if (in->heldPre.held) { rc = executeHeldPre(in); if (rc) return rc; }
+    const int n = operationCount;
+    bool fresh = false;
+    rc = sendList(in, b, operations, n, intervals, intervalCount, &fresh); if (rc) return rc;
+    // the chains of the list (3 n ints, staged and sent like the list itself)
+    if (b->linkCap < (size_t)3 * n + 1) {
+        HIP_TRY(hipStreamSynchronize(live(in)));
+        if (b->hLink) hipHostFree(b->hLink);
+        release(in, b->dLink, b->linkCap * sizeof(int));
+        release(in, b->dTickets, b->linkCap / 3 * sizeof(unsigned));
+        b->hLink = nullptr; b->dLink = nullptr; b->dTickets = nullptr; b->linkCap = 0;
+        const size_t cap = 3 * ((size_t)n + n / 4 + 64);
+        HIP_TRY(hipHostMalloc((void**)&b->hLink, cap * sizeof(int), hipHostMallocDefault));
+        rc = devAlloc(in, (void**)&b->dLink, cap * sizeof(int)); if (rc) return rc;
+        rc = devAlloc(in, (void**)&b->dTickets, cap / 3 * sizeof(unsigned)); if (rc) return rc;
+        b->linkCap = cap;
+    }
+    HIP_TRY(hipEventSynchronize(b->sent));
+    int nLeaves = 0;
+    const bool forest = n > 0 && analyse(b, operations, n, intervals, intervalCount, b->hLink, b->hLink + (size_t)2 * n, &nLeaves);
+    b->coalescentIndex = coalescentProbabilityIndex;
+    double* coalescent = b->buffers + (size_t)coalescentProbabilityIndex * b->maxIntervals * in->S;
+    const double* sizes = in->freqs + (size_t)populationSizesIndex * in->S;
+    hipStream_t s = live(in);
+    HIP_TRY(hipMemsetAsync(coalescent, 0, (size_t)b->maxIntervals * sizeof(double), s));
+    if (forest) {
+        HIP_TRY(hipMemcpyAsync(b->dLink, b->hLink, (size_t)3 * n * sizeof(int), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipEventRecord(b->sent, s));
+        HIP_TRY(hipMemsetAsync(b->dTickets, 0, (size_t)n * sizeof(unsigned), s));
+    }
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (timeThisCall(in)) {
+        if (in->eventsUsed == in->events.size()) {
+            hipEvent_t x, y;
+            HIP_TRY(hipEventCreate(&x)); HIP_TRY(hipEventCreate(&y));
+            in->events.emplace_back(x, y);
+        }
+        e0 = in->events[in->eventsUsed].first; e1 = in->events[in->eventsUsed].second; in->eventsUsed++;
+        HIP_TRY(hipEventRecord(e0, s));
+    }
+    int launches = 0;
+    if (forest) {
+        mi355::launchBastaChains(s, b->dOps, b->dLink, b->dLink + (size_t)2 * n, nLeaves, b->dTickets, in->matrices, b->vectors, sizes, coalescent, in->S);
+        launches = 1;
+        b->statChainCalls++;
+    } else {
+        for (int t = 0; t + 1 < intervalCount; t++) {
+            const int count = intervals[t + 1] - intervals[t];
+            if (count <= 0) continue;
+            mi355::launchBastaInterval(s, b->dOps, intervals[t], count, in->matrices, b->vectors, sizes, coalescent, in->S);
+            launches++;
+        }
+        if (n > 0) b->statIntervalCalls++;
+    }
+    if (e1 && launches > 0) { HIP_TRY(hipEventRecord(e1, s)); in->pendingLaunches += launches; }
+    else if (e1) { in->eventsUsed--; in->timedCalls--; }
+    HIP_TRY(hipGetLastError());
+    return BEAGLE_SUCCESS;
+}
+
+int beagleBastaAccumulatePartials(int instance, const int* operations, int operationCount, const int* intervals, int intervalCount,
+                                  const double* intervalLengths, int populationSizesIndex, int coalescentProbabilityIndex,
+                                  double* outLogLikelihood) {
+    Instance* in = nullptr;
+    int rc = bastaInstance(instance, &in); if (rc) return rc;
+    Basta* b = in->basta;
+    if (!b) return BEAGLE_ERROR_NO_IMPLEMENTATION;
+    rc = checkList(in, b, operations, operationCount, intervals, intervalCount, populationSizesIndex, coalescentProbabilityIndex);
+    if (rc) return rc;
+    if (!outLogLikelihood || (intervalCount > 1 && !intervalLengths)) return BEAGLE_ERROR_OUT_OF_RANGE;
+    if (b->bufferCount < 5 || intervalCount - 1 > b->maxIntervals) return BEAGLE_ERROR_OUT_OF_RANGE;      // probabilities, e, f, g, h
+    if (in->heldPre.held) { rc = executeHeldPre(in); if (rc) return rc; }
+    bool fresh = false;
+    rc = sendList(in, b, operations, operationCount, intervals, intervalCount, &fresh); if (rc) return rc;
+    const int nIntervals = intervalCount - 1;
+    rc = growPair(in, b->hLengths, b->dLengths, b->lengthsCap, (size_t)nIntervals + 1); if (rc) return rc;
+    HIP_TRY(hipEventSynchronize(b->sent));
+    if (nIntervals) memcpy(b->hLengths, intervalLengths, (size_t)nIntervals * sizeof(double));
+    hipStream_t s = live(in);
+    if (nIntervals) HIP_TRY(hipMemcpyAsync(b->dLengths, b->hLengths, (size_t)nIntervals * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(b->sent, s));
+    // e, f, g, h: the four lowest buffers that do not hold the coalescent probabilities
+    double* efgh[4]; int at = 0;
+    const size_t stride = (size_t)b->maxIntervals * in->S;
+    for (int k = 0; k < b->bufferCount && at < 4; k++) if (k != coalescentProbabilityIndex) efgh[at++] = b->buffers + k * stride;
+    double* total = b->intervalLogL + b->maxIntervals;
+    mi355::launchBastaReduce(s, b->dOps, b->dIntervals, nIntervals, b->dLengths, b->vectors,
+                             in->freqs + (size_t)populationSizesIndex * in->S, b->buffers + coalescentProbabilityIndex * stride,
+                             efgh[0], efgh[1], efgh[2], efgh[3], b->intervalLogL, total, in->S);
+    HIP_TRY(hipGetLastError());
+    double logL = 0.0;
+    rc = download(in, &logL, total, sizeof(double)); if (rc) return rc;
+    if (in->asyncError) { const int e = in->asyncError.exchange(0); if (e) return e; }
+    if (std::isnan(logL)) return BEAGLE_ERROR_FLOATING_POINT;
+    outLogLikelihood[0] += logL;
+    return BEAGLE_SUCCESS;
+}
+
+int beagleBastaGetBuffer(int instance, int index, double* out) {
+    Instance* in = nullptr;
+    int rc = bastaInstance(instance, &in); if (rc) return rc;
+    Basta* b = in->basta;
+    if (!b) return BEAGLE_ERROR_NO_IMPLEMENTATION;
+    if (badIndex(index, b->bufferCount) || !out) return BEAGLE_ERROR_OUT_OF_RANGE;
+    const size_t stride = (size_t)b->maxIntervals * in->S;
+    const size_t count = index == b->coalescentIndex ? (size_t)b->maxIntervals : stride;
+    return download(in, out, b->buffers + index * stride, count * sizeof(double));
+}
+
+int beagleBastaGetBufferLength(int instance, int index) {
+    Instance* in = nullptr;
+    int rc = bastaInstance(instance, &in); if (rc) return rc;
+    Basta* b = in->basta;
+    if (!b) return BEAGLE_ERROR_NO_IMPLEMENTATION;
+    if (badIndex(index, b->bufferCount)) return BEAGLE_ERROR_OUT_OF_RANGE;
+    return index == b->coalescentIndex ? b->maxIntervals : b->maxIntervals * in->S;
+}
+
+int beagleBastaStats(int instance, long* out4) {
+    Instance* in = nullptr;
+    int rc = bastaInstance(instance, &in); if (rc) return rc;
+    Basta* b = in->basta;
+    if (!b) return BEAGLE_ERROR_NO_IMPLEMENTATION;
+    if (!out4) return BEAGLE_ERROR_OUT_OF_RANGE;
+    out4[0] = b->statUploads; out4[1] = b->statChainCalls; out4[2] = b->statIntervalCalls; out4[3] = (long)b->vectorCount;
+    return BEAGLE_SUCCESS;
+}
+
+int beagleBastaUpdatePartialsGrad(int instance, const int* operations, int operationCount, const int* intervals, int intervalCount,
+                                  int populationSizesIndex, int coalescentProbabilityIndex) {
+    (void)instance; (void)operations; (void)operationCount; (void)intervals; (void)intervalCount; (void)populationSizesIndex; (void)coalescentProbabilityIndex;
+    return BEAGLE_ERROR_NO_IMPLEMENTATION;
+}
+
+int beagleBastaUpdateTransitionMatricesGrad(int instance, const int* transitionMatrixIndices, const double* branchLengths, int count) {
+    (void)instance; (void)transitionMatrixIndices; (void)branchLengths; (void)count;
+    return BEAGLE_ERROR_NO_IMPLEMENTATION;
+}
+
+int beagleBastaAccumulatePartialsGrad(int instance, const int* operations, int operationCount, const int* intervals, int intervalCount,
+                                      const double* intervalLengths, int populationSizesIndex, int coalescentProbabilityIndex,
+                                      double* outGradient) {
+    (void)instance; (void)operations; (void)operationCount; (void)intervals; (void)intervalCount; (void)intervalLengths;
+    (void)populationSizesIndex; (void)coalescentProbabilityIndex; (void)outGradient;
+    return BEAGLE_ERROR_NO_IMPLEMENTATION;
+}
+
+}  // extern "C"

@@ -174,6 +174,7 @@ void destroy(Instance* in) {
                 in->hostHits ? in->hostPlanHitUs / in->hostHits : 0.0, in->hostHits ? in->hostRunHitUs / in->hostHits : 0.0);
     in->pendingCopies.clear();
     if (in->ownStream) hipStreamSynchronize(in->ownStream);
+    if (in->basta) bastaFree(in);
     if (in->comm) { if (in->stream) hipStreamSynchronize(in->stream); ncclCommDestroy(in->comm); in->comm = nullptr; }
     if (in->stream && in->stream != in->ownStream) hipStreamSynchronize(in->stream);
     for (void* p : in->allocations) hipFree(p);

@@ -45,6 +45,8 @@ constexpr int PRE_SCRATCH = 32;            // pre-order ops per two-pass chunk o
 constexpr int GRADIENT_VIRT_STEPS = 2;     // longest definition a gradient chain can leave unstored (Instance::gradientVirtual)
 constexpr int GRADIENT_VIRT_DEFAULT = 1;   // ... and what it does leave unstored by default: nodes over two tips (engine_abi.cpp)
 
+struct Basta;                              // engine_basta.cpp
+
 struct Instance {
     int device = 0;
     // 4 states: every operation list runs as ONE launch of the pattern-walk kernel (kernels_walk4.hip), programmed by the
@@ -195,6 +197,8 @@ struct Instance {
     // the event list of the last call that asked for one
     char* uniformDev = nullptr; size_t uniformBytes = 0;
     char* eventDev = nullptr; size_t eventBytes = 0;
+    // BASTA structured coalescent (beagleBastaAllocateCoalescentBuffers, engine_basta.cpp): null on every other instance
+    Basta* basta = nullptr;
     long statMicroOps = 0, statStored = 0, statMemReads = 0, statTipReads = 0, statScaleReads = 0, statWalks = 0, statScaleWrites = 0;   // since the last timer reset
     hipStream_t stream = nullptr, ownStream = nullptr;
     int tipCount = 0, partialsCount = 0, compactCount = 0, S = 0, P = 0, eigenCount = 0, matrixCount = 0, C = 0, scaleCount = 0;
@@ -402,6 +406,11 @@ int executeHeldPre(Instance* in);
 int edgeDifferentials(Instance* in, const int* postIdx, const int* preIdx, const int* dIdx, int wIdx, int count,
                       double* outDerivatives, double* outSum, double* outSumSquared);
 int crossProducts(Instance* in, const int* postIdx, const int* preIdx, int rateIdx, int wIdx, const double* lengths, int count, double* outSum);
+
+// ---- engine_basta.cpp: an instance that has BASTA buffers keeps its S-double vectors there (setPartials / getPartials)
+int bastaSetPartials(Instance* in, int bufferIndex, const double* inPartials);
+int bastaGetPartials(Instance* in, int bufferIndex, double* outPartials);
+void bastaFree(Instance* in);
 
 }  // namespace eng
 }  // namespace mi355

@@ -557,4 +557,18 @@ void launchEventOffsets(hipStream_t stream, int* counts, int nRows, int P, long 
 void launchRootFinal(hipStream_t stream, const double* blockSums, int n, double* out, unsigned long long* flag = nullptr,
                      unsigned long long seq = 0);
 
+// ---- BASTA structured coalescent (kernels_basta.hip): a partial is S doubles, an operation is 8 ints
+// {dest, in1, matrix1, in2, matrix2, acc1, acc2, interval number} (include/beagle_mi355.h)
+// the whole list in ONE launch: a wave per starting operation (leaves), link = per operation {the operation that reads its result
+// or -1, how many inputs of THAT operation the list produces}, tickets = one zeroed word per operation
+void launchBastaChains(hipStream_t stream, const int* ops, const int* link, const int* leaves, int nLeaves, unsigned* tickets,
+                       const double* matrices, double* partials, const double* sizes, double* coalescent, int S);
+// operations [first, first + count) of one interval, each on its own
+void launchBastaInterval(hipStream_t stream, const int* ops, int first, int count, const double* matrices, double* partials,
+                         const double* sizes, double* coalescent, int S);
+// per interval e, f, g, h and its term of the log-density (a wave each, operations in list order), then out[0] = the terms' sum in a fixed order
+void launchBastaReduce(hipStream_t stream, const int* ops, const int* intervals, int nIntervals, const double* lengths,
+                       const double* partials, const double* sizes, const double* coalescent, double* e, double* f, double* g,
+                       double* h, double* intervalLogL, double* out, int S);
+
 }  // namespace mi355

@@ -133,3 +133,41 @@ def caterpillar_tree(tip_count, root_height=1.0):
         height[node] = root_height * i / (n - 1)
         prev = node
     return Tree(left, right, height, 2 * n - 2)
+
+
+def heterochronous_coalescent_tree(tip_count, rng, sampling_span=1.0, population=None, tied=0):
+    """Kingman-coalescent genealogy of tips sampled through time (serially sampled data: what a phylogeographic analysis
+    has).  Tip heights are uniform on [0, sampling_span], the most recent at 0 and, with ``tied`` > 1, rounded to ``tied``
+    distinct values; going back in time a pair of the lineages sampled so far coalesces at rate k(k-1)/(2 population)
+    (default: population = sampling_span, so that lineages coexist).  Internal node T+i is the i-th coalescence; the root is 2T-2."""
+    n = tip_count
+    times = rng.uniform(0.0, sampling_span, size=n)
+    if tied > 1:
+        times = np.floor(times / sampling_span * tied) * (sampling_span / tied)
+    times -= times.min()
+    pop = sampling_span if population is None else population
+    left = [-1] * (2 * n - 1)
+    right = [-1] * (2 * n - 1)
+    height = [0.0] * (2 * n - 1)
+    waiting = sorted(range(n), key=lambda i: (times[i], i))
+    for i in range(n):
+        height[i] = float(times[i])
+    t = float(times[waiting[0]])
+    active = [waiting.pop(0)]
+    nxt = n
+    while len(active) > 1 or waiting:
+        k = len(active)
+        wait = rng.exponential(2.0 * pop / (k * (k - 1))) if k > 1 else np.inf
+        if waiting and t + wait >= times[waiting[0]]:
+            t = float(times[waiting[0]])
+            active.append(waiting.pop(0))
+            continue
+        t += wait
+        i, j = rng.choice(k, size=2, replace=False)
+        a, b = active[i], active[j]
+        left[nxt], right[nxt], height[nxt] = a, b, t
+        for idx in sorted((i, j), reverse=True):
+            active.pop(idx)
+        active.append(nxt)
+        nxt += 1
+    return Tree(left, right, height, 2 * n - 2)

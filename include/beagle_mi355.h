@@ -510,6 +510,55 @@ int beagleMi355GetDimensions(int instance, int* out8);
 /* Bytes of HBM currently allocated by the instance. */
 long beagleMi355DeviceBytes(int instance);
 
+/* ---- BASTA: the structured-coalescent approximation (beagle/basta/BastaJNIWrapper.java; the natives
+ * BeagleBastaLikelihoodDelegate calls on an ordinary instance).  The arithmetic restates the reference's pure-Java twin,
+ * GenericBastaLikelihoodDelegate.peelPartials / reduceWithinInterval / reduceAcrossIntervals.
+ *
+ * A BASTA instance has patternCount 1 and categoryCount 1 (anything else: BEAGLE_ERROR_NO_IMPLEMENTATION from every call below,
+ * as on the sharded handle, and as from every other call below before the first AllocateCoalescentBuffers).  A "partial" is S
+ * doubles.  Once an instance has BASTA buffers, beagleSetPartials / beagleGetPartials (scale index ignored) address THEM: S
+ * doubles in, S doubles out.  Population sizes travel through beagleSetStateFrequencies(populationSizesIndex, sizes) and are
+ * stored as given; matrices through beagleUpdateTransitionMatrices / beagleSetTransitionMatrix as ever.
+ * BEAGLE_ERROR_OUT_OF_RANGE for an index outside the allocation, a negative in1, an interval number >= maxCoalescentIntervalCount,
+ * intervals that do not start at 0, decrease, or do not end at operationCount.
+ *
+ * (Re)size the instance's BASTA state: partialsBufferCount vectors and coalescentBufferCount (5: probabilities, e, f, g, h)
+ * interval-indexed buffers.  initial != 0: everything zero.  initial == 0 (the caller's buffer numbers outgrew the allocation):
+ * the vectors stored so far are kept.  threadCount is ignored. */
+int beagleBastaAllocateCoalescentBuffers(int instance, int coalescentBufferCount, int maxCoalescentIntervalCount,
+                                         int partialsBufferCount, int initial, int threadCount);
+/* operations: operationCount tuples {dest, in1, matrix1, in2, matrix2, acc1, acc2, intervalNumber}; intervals: intervalCount offsets
+ * into the list, the first 0 and the last operationCount (intervalCount - 1 intervals).  Per operation left = M1 p[in1]; with
+ * in2 < 0, p[dest] = left; otherwise right = M2 p[in2], entry_i = left_i right_i / size_i, prob = sum_i entry_i, p[dest] = entry / prob,
+ * p[acc1] = left, p[acc2] = right, probabilities[intervalNumber] = prob.  The probabilities are zeroed first.  Operations of one
+ * interval are independent; an operation may read what an earlier interval wrote.  The number of kernel launches does not depend
+ * on the number of intervals when every vector the list writes is written once and read by one operation of a later interval
+ * (the reference's numbering); any other list runs one launch per interval.  Returns when the work is enqueued. */
+int beagleBastaUpdatePartials(int instance, const int* operations, int operationCount, const int* intervals, int intervalCount,
+                              int populationSizesIndex, int coalescentProbabilityIndex);
+/* Per interval k (its number n = the interval number of its first operation): e, f, g, h [n] = sums over its operations, in list order,
+ * and their one or two children of p[in], p[in]^2, p[acc], p[acc]^2 per state; sum = sum_s (e_s^2 - f_s + g_s^2 - h_s) / size_s;
+ * logL_k = -intervalLengths[k] sum / 4 + (probabilities[n] != 0 ? log probabilities[n] : 0).  outLogLikelihood[0] += sum_k logL_k,
+ * the terms added in a fixed order (two calls give the same bits).  Needs coalescentBufferCount >= 5.  A list equal to the one the
+ * device already holds (the usual case: the list just given to beagleBastaUpdatePartials) is not uploaded again.
+ * BEAGLE_ERROR_FLOATING_POINT when the sum is NaN (outLogLikelihood untouched). */
+int beagleBastaAccumulatePartials(int instance, const int* operations, int operationCount, const int* intervals, int intervalCount,
+                                  const double* intervalLengths, int populationSizesIndex, int coalescentProbabilityIndex,
+                                  double* outLogLikelihood);
+/* Buffer `index` of the coalescent buffers: the one that held the probabilities in the last update (index 0 before any) as
+ * maxCoalescentIntervalCount doubles, any other as [maxCoalescentIntervalCount][S] doubles; beagleBastaGetBufferLength says which. */
+int beagleBastaGetBuffer(int instance, int index, double* out);
+int beagleBastaGetBufferLength(int instance, int index);
+/* out4 = {uploads of an operation list so far, updates run as one launch, updates run interval by interval, partialsBufferCount}. */
+int beagleBastaStats(int instance, long* out4);
+/* The gradient natives of BastaJNIWrapper: not built, BEAGLE_ERROR_NO_IMPLEMENTATION. */
+int beagleBastaUpdatePartialsGrad(int instance, const int* operations, int operationCount, const int* intervals, int intervalCount,
+                                  int populationSizesIndex, int coalescentProbabilityIndex);
+int beagleBastaUpdateTransitionMatricesGrad(int instance, const int* transitionMatrixIndices, const double* branchLengths, int count);
+int beagleBastaAccumulatePartialsGrad(int instance, const int* operations, int operationCount, const int* intervals, int intervalCount,
+                                      const double* intervalLengths, int populationSizesIndex, int coalescentProbabilityIndex,
+                                      double* outGradient);
+
 /* Function table: lets a host driver (host/tree_likelihood.cpp) or a test drive any engine
  * that implements this ABI (the HIP engine, or the CPU oracle under oracle/) through one type. */
 typedef struct BeagleApi {
