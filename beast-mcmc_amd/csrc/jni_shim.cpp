@@ -31,9 +31,10 @@ namespace {
 enum Mode { IN, OUT, INOUT };
 // n < 0: the whole array.  n >= 0: the number of entries the call defines (inputs: reads; outputs: writes) — a Java array
 // shorter than that is an error the wrapper reports (tooShort) instead of letting the library run past the copy.
-// Outputs go back to the Java array only when the call succeeded (commit), and only the n entries it defines.
+// Outputs go back to the Java array only when the call was made and succeeded (commitTo), and only the n entries it defines: a
+// wrapper that returns before the call — another array was too short — leaves every Java array as it was.
 struct IntArr {
-    JNIEnv* env; jintArray arr; std::vector<jint> buf; Mode mode; bool tooShort = false, write = true;
+    JNIEnv* env; jintArray arr; std::vector<jint> buf; Mode mode; bool tooShort = false, write = false; jint none = 0;
     IntArr(JNIEnv* e, jintArray a, long n = -1, Mode m = IN) : env(e), arr(a), mode(m) {
         if (!a) return;
         const long len = (long)jni::GetArrayLength(e, a);
@@ -42,10 +43,10 @@ struct IntArr {
         if (mode != OUT && !buf.empty()) jni::GetIntArrayRegion(e, a, 0, (jsize)buf.size(), buf.data());
     }
     ~IntArr() { if (arr && mode != IN && write && !tooShort && !buf.empty()) jni::SetIntArrayRegion(env, arr, 0, (jsize)buf.size(), buf.data()); }
-    operator int*() { return arr ? buf.data() : nullptr; }
+    operator int*() { return !arr ? nullptr : buf.empty() ? &none : buf.data(); }     // (a non-null array stays non-null at count 0)
 };
 struct DblArr {
-    JNIEnv* env; jdoubleArray arr; std::vector<jdouble> buf; Mode mode; bool tooShort = false, write = true;
+    JNIEnv* env; jdoubleArray arr; std::vector<jdouble> buf; Mode mode; bool tooShort = false, write = false; jdouble none = 0;
     DblArr(JNIEnv* e, jdoubleArray a, long n = -1, Mode m = IN) : env(e), arr(a), mode(m) {
         if (!a) return;
         const long len = (long)jni::GetArrayLength(e, a);
@@ -54,7 +55,7 @@ struct DblArr {
         if (mode != OUT && !buf.empty()) jni::GetDoubleArrayRegion(e, a, 0, (jsize)buf.size(), buf.data());
     }
     ~DblArr() { if (arr && mode != IN && write && !tooShort && !buf.empty()) jni::SetDoubleArrayRegion(env, arr, 0, (jsize)buf.size(), buf.data()); }
-    operator double*() { return arr ? buf.data() : nullptr; }
+    operator double*() { return !arr ? nullptr : buf.empty() ? &none : buf.data(); }
 };
 inline bool anyShort() { return false; }
 template <class A, class... R> inline bool anyShort(const A& a, const R&... r) { return a.tooShort || anyShort(r...); }
@@ -71,6 +72,20 @@ inline Dims dimsOf(int instance) {
     if (beagleMi355GetDimensions(instance, d) == BEAGLE_SUCCESS) { r.S = d[2]; r.P = d[3]; r.C = d[4]; r.ok = true; }
     return r;
 }
+
+// the pinned routes of getPartials / getSiteLogLikelihoods obey the rules of every other output: written on success and on
+// BEAGLE_ERROR_FLOATING_POINT (when the library handed a buffer over), refused when the Java array is shorter than the result
+inline int fromPinned(JNIEnv* env, jdoubleArray out, int rc, const double* pinned, long n) {
+    if ((rc == BEAGLE_SUCCESS || rc == BEAGLE_ERROR_FLOATING_POINT) && pinned && out) {
+        if ((long)jni::GetArrayLength(env, out) < n) return BEAGLE_ERROR_OUT_OF_RANGE;
+        if (n > 0) jni::SetDoubleArrayRegion(env, out, 0, (jsize)n, pinned);
+    }
+    return rc;
+}
+// an input the INSTANCE sizes (pattern weights, tip states, partials, a matrix, ...) is copied whole — its Java array is exactly
+// that long in BEAST — but one shorter than what the library will read is refused like any other short array
+template <class A> inline bool shorterThan(const A& a, long n) { return a.arr && (long)a.buf.size() < n; }
+#define NEEDS(a, expr) do { const Dims d = dimsOf(instance); if (d.ok && shorterThan(a, (expr))) return BEAGLE_ERROR_OUT_OF_RANGE; } while (0)
 
 // a failed class / method lookup leaves a pending NoSuchMethodError / NoClassDefFoundError: clear it, the caller sees null / skips
 bool pendingCleared(JNIEnv* env) {
@@ -171,7 +186,7 @@ JNI_FN(jint, createInstance)(JNIEnv* env, jobject, jint tipCount, jint partialsB
                              jint categoryCount, jint scaleBufferCount, jintArray resourceList, jint resourceCount,
                              jlong preferenceFlags, jlong requirementFlags, jobject outDetails) {
     BeagleInstanceDetails d = {0, nullptr, nullptr, nullptr, 0};
-    IntArr res(env, resourceList, resourceCount);
+    IntArr res(env, resourceList, resourceCount); SHORT_CHECK(res);
     const int h = beagleCreateInstance(tipCount, partialsBufferCount, compactBufferCount, stateCount, patternCount,
                                        eigenBufferCount, matrixBufferCount, categoryCount, scaleBufferCount, res, resourceCount,
                                        (long)preferenceFlags, (long)requirementFlags, &d);
@@ -189,13 +204,13 @@ JNI_FN(jint, finalize)(JNIEnv*, jobject, jint instance) { return beagleFinalizeI
 JNI_FN(jint, setCPUThreadCount)(JNIEnv*, jobject, jint instance, jint n) { return beagleSetCPUThreadCount(instance, n); }
 
 JNI_FN(jint, setPatternWeights)(JNIEnv* env, jobject, jint instance, jdoubleArray w) {
-    DblArr a(env, w); return beagleSetPatternWeights(instance, a);
+    DblArr a(env, w); NEEDS(a, d.P); return beagleSetPatternWeights(instance, a);
 }
 JNI_FN(jint, setPatternPartitions)(JNIEnv* env, jobject, jint instance, jint partitionCount, jintArray parts) {
-    IntArr a(env, parts); return beagleSetPatternPartitions(instance, partitionCount, a);
+    IntArr a(env, parts); NEEDS(a, d.P); return beagleSetPatternPartitions(instance, partitionCount, a);
 }
 JNI_FN(jint, setTipStates)(JNIEnv* env, jobject, jint instance, jint tip, jintArray states) {
-    IntArr a(env, states); return beagleSetTipStates(instance, tip, a);
+    IntArr a(env, states); NEEDS(a, d.P); return beagleSetTipStates(instance, tip, a);
 }
 JNI_FN(jint, getTipStates)(JNIEnv* env, jobject, jint instance, jint tip, jintArray states) {
     const Dims d = dimsOf(instance);
@@ -203,14 +218,14 @@ JNI_FN(jint, getTipStates)(JNIEnv* env, jobject, jint instance, jint tip, jintAr
     const int rc = beagleGetTipStates(instance, tip, a); commitTo(rc, a); return rc;
 }
 JNI_FN(jint, setTipPartials)(JNIEnv* env, jobject, jint instance, jint tip, jdoubleArray partials) {
-    DblArr a(env, partials); return beagleSetTipPartials(instance, tip, a);
+    DblArr a(env, partials); NEEDS(a, d.P * d.S); return beagleSetTipPartials(instance, tip, a);
 }
 JNI_FN(jint, setRootPrePartials)(JNIEnv* env, jobject, jint instance, jintArray bufs, jintArray freqs, jint count) {
     IntArr a(env, bufs, count), b(env, freqs, count); SHORT_CHECK(a, b);
     return beagleSetRootPrePartials(instance, a, b, count);
 }
 JNI_FN(jint, setPartials)(JNIEnv* env, jobject, jint instance, jint buf, jdoubleArray partials) {
-    DblArr a(env, partials); return beagleSetPartials(instance, buf, a);
+    DblArr a(env, partials); NEEDS(a, d.C * d.P * d.S); return beagleSetPartials(instance, buf, a);
 }
 JNI_FN(jint, getPartials)(JNIEnv* env, jobject, jint instance, jint buf, jint scaleIndex, jdoubleArray out) {
     // straight from the engine's pinned bounce buffer into the Java array (no copy in, one copy out)
@@ -221,11 +236,7 @@ JNI_FN(jint, getPartials)(JNIEnv* env, jobject, jint instance, jint buf, jint sc
         DblArr a(env, out, d.ok ? d.C * d.P * d.S : -1, OUT); SHORT_CHECK(a);
         const int rc2 = beagleGetPartials(instance, buf, scaleIndex, a); commitTo(rc2, a); return rc2;
     }
-    if (rc == BEAGLE_SUCCESS && out) {
-        if ((long)jni::GetArrayLength(env, out) < n) return BEAGLE_ERROR_OUT_OF_RANGE;
-        jni::SetDoubleArrayRegion(env, out, 0, (jsize)n, pinned);
-    }
-    return rc;
+    return fromPinned(env, out, rc, pinned, n);
 }
 JNI_FN(jint, getLogScaleFactors)(JNIEnv* env, jobject, jint instance, jint scaleIndex, jdoubleArray out) {
     const Dims d = dimsOf(instance);
@@ -233,25 +244,27 @@ JNI_FN(jint, getLogScaleFactors)(JNIEnv* env, jobject, jint instance, jint scale
     const int rc = beagleGetLogScaleFactors(instance, scaleIndex, a); commitTo(rc, a); return rc;
 }
 JNI_FN(jint, setEigenDecomposition)(JNIEnv* env, jobject, jint instance, jint eigenIndex, jdoubleArray u, jdoubleArray ui, jdoubleArray lam) {
-    DblArr a(env, u), b(env, ui), c(env, lam); return beagleSetEigenDecomposition(instance, eigenIndex, a, b, c);
+    DblArr a(env, u), b(env, ui), c(env, lam);
+    NEEDS(a, d.S * d.S); NEEDS(b, d.S * d.S); NEEDS(c, d.S);
+    return beagleSetEigenDecomposition(instance, eigenIndex, a, b, c);
 }
 JNI_FN(jint, setStateFrequencies)(JNIEnv* env, jobject, jint instance, jint idx, jdoubleArray f) {
-    DblArr a(env, f); return beagleSetStateFrequencies(instance, idx, a);
+    DblArr a(env, f); NEEDS(a, d.S); return beagleSetStateFrequencies(instance, idx, a);
 }
 JNI_FN(jint, setCategoryWeights)(JNIEnv* env, jobject, jint instance, jint idx, jdoubleArray w) {
-    DblArr a(env, w); return beagleSetCategoryWeights(instance, idx, a);
+    DblArr a(env, w); NEEDS(a, d.C); return beagleSetCategoryWeights(instance, idx, a);
 }
 JNI_FN(jint, setCategoryRates)(JNIEnv* env, jobject, jint instance, jdoubleArray r) {
-    DblArr a(env, r); return beagleSetCategoryRates(instance, a);
+    DblArr a(env, r); NEEDS(a, d.C); return beagleSetCategoryRates(instance, a);
 }
 JNI_FN(jint, setCategoryRatesWithIndex)(JNIEnv* env, jobject, jint instance, jint idx, jdoubleArray r) {
-    DblArr a(env, r); return beagleSetCategoryRatesWithIndex(instance, idx, a);
+    DblArr a(env, r); NEEDS(a, d.C); return beagleSetCategoryRatesWithIndex(instance, idx, a);
 }
 JNI_FN(jint, setTransitionMatrix)(JNIEnv* env, jobject, jint instance, jint idx, jdoubleArray m, jdouble padded) {
-    DblArr a(env, m); return beagleSetTransitionMatrix(instance, idx, a, padded);
+    DblArr a(env, m); NEEDS(a, d.C * d.S * d.S); return beagleSetTransitionMatrix(instance, idx, a, padded);
 }
 JNI_FN(jint, setDifferentialMatrix)(JNIEnv* env, jobject, jint instance, jint idx, jdoubleArray m) {
-    DblArr a(env, m); return beagleSetDifferentialMatrix(instance, idx, a);
+    DblArr a(env, m); NEEDS(a, d.C * d.S * d.S); return beagleSetDifferentialMatrix(instance, idx, a);
 }
 JNI_FN(jint, getTransitionMatrix)(JNIEnv* env, jobject, jint instance, jint idx, jdoubleArray out) {
     const Dims d = dimsOf(instance);
@@ -348,11 +361,7 @@ JNI_FN(jint, getSiteLogLikelihoods)(JNIEnv* env, jobject, jint instance, jdouble
         DblArr o(env, out, d.ok ? d.P : -1, OUT); SHORT_CHECK(o);
         const int rc2 = beagleGetSiteLogLikelihoods(instance, o); commitTo(rc2, o); return rc2;
     }
-    if (rc == BEAGLE_SUCCESS && out) {
-        if ((long)jni::GetArrayLength(env, out) < n) return BEAGLE_ERROR_OUT_OF_RANGE;
-        jni::SetDoubleArrayRegion(env, out, 0, (jsize)n, pinned);
-    }
-    return rc;
+    return fromPinned(env, out, rc, pinned, n);
 }
 
 // gradient entry points.  BEAST passes null for outDerivatives and, on the second-derivative call, for
@@ -364,6 +373,7 @@ JNI_FN(jint, calculateEdgeDifferentials)(JNIEnv* env, jobject, jint instance, ji
     const Dims dm = dimsOf(instance);
     DblArr o0(env, outDeriv, dm.ok ? (long)count * dm.P : -1, OUT), o1(env, outSum, count, OUT), o2(env, outSumSquared, count, OUT);
     SHORT_CHECK(a, b, c, o0, o1, o2);
+    if (count > 0 && shorterThan(w, 1)) return BEAGLE_ERROR_OUT_OF_RANGE;
     const int rc = beagleCalculateEdgeDifferentials(instance, a, b, c, w, count, o0, o1, o2); commitTo(rc, o0, o1, o2); return rc;
 }
 JNI_FN(jint, calculateCrossProductDifferentials)(JNIEnv* env, jobject, jint instance, jintArray post, jintArray pre, jintArray rates,
@@ -372,6 +382,8 @@ JNI_FN(jint, calculateCrossProductDifferentials)(JNIEnv* env, jobject, jint inst
     IntArr a(env, post, count), b(env, pre, count), r(env, rates), w(env, weights);
     DblArr t(env, lengths, count), o1(env, outSum, -1, INOUT), o2(env, outSumSquared, -1, INOUT);      // the sums are ADDED to what the arrays hold
     SHORT_CHECK(a, b, t);
+    if (count > 0 && (shorterThan(r, 1) || shorterThan(w, 1))) return BEAGLE_ERROR_OUT_OF_RANGE;
+    NEEDS(o1, d.S * d.S); NEEDS(o2, d.S * d.S);
     const int rc = beagleCalculateCrossProductDifferentials(instance, a, b, r, w, t, count, o1, o2); commitTo(rc, o1, o2); return rc;
 }
 JNI_FN(jint, calculateEdgeDerivative)(JNIEnv*, jobject, jint, jintArray, jintArray, jint, jintArray, jintArray, jint, jint, jint,
