@@ -9,10 +9,11 @@ Layout (only what the hot path needs — SURVEY.md §8):
   ancestral.py        ancestral-state draws on the device (AncestralStateBeagleTreeLikelihood's caller side)
   markovjumps.py      Markov-jump counts and rewards on the device (MarkovJumpsBeagleTreeLikelihood's caller side)
   basta.py            the BASTA structured-coalescent likelihood on the device (BeagleBastaLikelihoodDelegate's caller side)
+  mds.py              multidimensional scaling on the device (MultiDimensionalScalingLikelihood's caller side, libmds2_jni.so)
   inputs/   what feeds the engine: eigen systems, gamma rate categories, site patterns, trees, synthetic workloads
   sharding.py         pattern-block sharding across GPUs + the single lnL all-reduce
 
 The directory name contains a hyphen, so import it through the root-level shim: ``import beast_mcmc_amd``.
 """
-from . import ancestral, basta, beagle, markovjumps, multipartition, treelikelihood          # noqa: F401
+from . import ancestral, basta, beagle, markovjumps, mds, multipartition, treelikelihood     # noqa: F401
 from .inputs import patterns, siterates, substmodel, synth, trees   # noqa: F401

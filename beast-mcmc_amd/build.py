@@ -3,6 +3,9 @@
   lib/libhmsbeagle-jni.so   HIP engine + C ABI + JNI shim, gfx950 only   (csrc/*.hip, csrc/*.cpp)
   lib/libhmsbeagle-jni-bit.so   the natives of beagle.basta.BastaJNIWrapper: thin wrappers over the engine's beagleBasta* calls,
                             linked against the engine library next to it   (jni_basta/*.cpp, plain g++)
+  lib/libmds2_jni.so        multidimensional scaling: HIP kernels + C ABI (include/mds_mi355.h) + the 14 natives of
+                            dr.inference.multidimensionalscaling.NativeMDSSingleton, gfx950 only; it stands alone (no engine
+                            library next to it)   (csrc/kernels_mds.hip, csrc/engine_mds.cpp, jni_mds/jni_mds.cpp)
   lib/libbeast_host.so      the caller stand-in: BeagleTreeLikelihood's call protocol in C++  (tools/host/tree_likelihood.cpp;
                             harness for tests and bench.py — in production the caller is BEAST's Java)
   lib/lab/libhmsbeagle-jni.so   (``--lab`` only) the same engine compiled with -DBEAGLE_MI355_LAB: the tuning knobs and timing
@@ -23,6 +26,9 @@ LIB = os.path.join(HERE, "lib")
 CSRC = os.path.join(HERE, "csrc")
 HOST = os.path.join(ROOT, "tools", "host")
 JNI_BASTA = os.path.join(HERE, "jni_basta")
+JNI_MDS = os.path.join(HERE, "jni_mds")
+MDS_SOURCES = ("kernels_mds.hip", "engine_mds.cpp")      # csrc files of libmds2_jni.so: not part of the engine library
+MDS_HEADERS = ("kernels_mds.h",)
 
 
 def _newer(target, sources):
@@ -53,8 +59,8 @@ def build_engine(force=False, lab=False):
     obj_dir = os.path.join(lib_dir, "obj")
     os.makedirs(obj_dir, exist_ok=True)
     out = os.path.join(lib_dir, "libhmsbeagle-jni.so")
-    srcs = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith((".hip", ".cpp"))]
-    headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))] + \
+    srcs = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith((".hip", ".cpp")) and f not in MDS_SOURCES]
+    headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc")) and f not in MDS_HEADERS] + \
         [os.path.join(ROOT, "include", "beagle_mi355.h")]
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-DBEAGLE_MI355_BUILD", "-Wall",
              "-Wno-unused-result", "-Wno-unused-value", "-Wno-cuda-compat", "-fvisibility=hidden"] + (["-DBEAGLE_MI355_LAB"] if lab else [])
@@ -100,8 +106,53 @@ def build_basta_jni(force=False):
     return out
 
 
+def build_mds(force=False):
+    """libmds2_jni.so (the name NativeMDSSingleton loads): kernels, C ABI and natives in one library of its own.  The kernel
+    file's resource report (-Rpass-analysis=kernel-resource-usage) is kept next to the library as mds_kernel_resources.txt,
+    and a kernel that spills to scratch fails the build."""
+    os.makedirs(LIB, exist_ok=True)
+    obj_dir = os.path.join(LIB, "obj")
+    os.makedirs(obj_dir, exist_ok=True)
+    out = os.path.join(LIB, "libmds2_jni.so")
+    exports = os.path.join(JNI_MDS, "exports.map")
+    srcs = [os.path.join(CSRC, f) for f in MDS_SOURCES] + [os.path.join(JNI_MDS, "jni_mds.cpp")]
+    headers = [os.path.join(CSRC, f) for f in MDS_HEADERS + ("jni_min.h",)] + [os.path.join(ROOT, "include", "mds_mi355.h")]
+    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-DMDS_MI355_BUILD", "-Wall", "-Wno-unused-result",
+             "-Wno-cuda-compat", "-fvisibility=hidden"]
+    objs, built = [], False
+    for s in srcs:
+        o = os.path.join(obj_dir, "mds_" + os.path.basename(s) + ".o")
+        objs.append(o)
+        if not (force or _newer(o, [s] + headers)):
+            continue
+        built = True
+        if s.endswith(".hip"):
+            cmd = [hipcc()] + flags + ["-Rpass-analysis=kernel-resource-usage", "-c", "-x", "hip", s, "-o", o]
+            print("+ " + " ".join(cmd), flush=True)
+            done = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+            report = [line for line in done.stdout.splitlines() if "remark:" in line]
+            other = [line for line in done.stdout.splitlines() if "remark:" not in line and line.strip()]
+            if other:
+                print("\n".join(other), flush=True)
+            if done.returncode:
+                raise subprocess.CalledProcessError(done.returncode, cmd)
+            report = [line.split("remark: ", 1)[1].replace(" [-Rpass-analysis=kernel-resource-usage]", "").rstrip() for line in report]
+            with open(os.path.join(LIB, "mds_kernel_resources.txt"), "w") as fh:
+                fh.write("\n".join(report) + "\n")
+            spills = [line for line in report if "ScratchSize [bytes/lane]:" in line and not line.endswith(": 0")]
+            if spills:
+                os.remove(o)
+                raise RuntimeError("an MDS kernel uses scratch memory:\n" + "\n".join(spills))
+        else:
+            _run([hipcc()] + flags + ["-c", "-x", "hip", s, "-o", o])
+    if built or force or _newer(out, objs + [exports]):
+        _run([hipcc(), "--offload-arch=gfx950", "-fPIC", "-shared"] + objs + ["-L/opt/rocm/lib", "-Wl,-rpath,/opt/rocm/lib",
+             "-Wl,--no-undefined", "-Wl,--version-script=" + exports, "-o", out])
+    return out
+
+
 def build_all(force=False):
-    return [build_engine(force), build_basta_jni(force), build_host(force)]
+    return [build_engine(force), build_basta_jni(force), build_mds(force), build_host(force)]
 
 
 if __name__ == "__main__":

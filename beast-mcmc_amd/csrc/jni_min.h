@@ -34,6 +34,7 @@ typedef JNIFunctionTable JNIEnv;                // C view of JNIEnv: `JNIEnv* en
 enum JniSlot {
     JNI_GetVersion = 4,
     JNI_FindClass = 6,
+    JNI_ThrowNew = 14,              // recalled from the specification's table (Throw 13, ThrowNew 14), not read from a <jni.h>
     JNI_ExceptionClear = 17,
     JNI_DeleteLocalRef = 23,
     JNI_NewObject = 28,
@@ -44,6 +45,7 @@ enum JniSlot {
     JNI_GetArrayLength = 171,
     JNI_NewObjectArray = 172,
     JNI_SetObjectArrayElement = 174,
+    JNI_NewDoubleArray = 182,       // recalled likewise: New<Boolean..Double>Array are 175..182
     JNI_GetIntArrayElements = 187,
     JNI_GetDoubleArrayElements = 190,
     JNI_ReleaseIntArrayElements = 195,
@@ -95,6 +97,10 @@ inline void SetIntArrayRegion(JNIEnv* e, jintArray a, jsize start, jsize len, co
 inline void SetDoubleArrayRegion(JNIEnv* e, jdoubleArray a, jsize start, jsize len, const jdouble* buf) {
     fn<void (*)(JNIEnv*, jdoubleArray, jsize, jsize, const jdouble*)>(e, JNI_SetDoubleArrayRegion)(e, a, start, len, buf);
 }
+inline jint ThrowNew(JNIEnv* e, jclass c, const char* message) {
+    return fn<jint (*)(JNIEnv*, jclass, const char*)>(e, JNI_ThrowNew)(e, c, message);
+}
+inline jdoubleArray NewDoubleArray(JNIEnv* e, jsize n) { return fn<jdoubleArray (*)(JNIEnv*, jsize)>(e, JNI_NewDoubleArray)(e, n); }
 inline jboolean ExceptionCheck(JNIEnv* e) { return fn<jboolean (*)(JNIEnv*)>(e, JNI_ExceptionCheck)(e); }
 inline void ExceptionClear(JNIEnv* e) { fn<void (*)(JNIEnv*)>(e, JNI_ExceptionClear)(e); }
 inline void DeleteLocalRef(JNIEnv* e, jobject o) { fn<void (*)(JNIEnv*, jobject)>(e, JNI_DeleteLocalRef)(e, o); }
