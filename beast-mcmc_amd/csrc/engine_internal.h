@@ -1,6 +1,14 @@
 // engine_internal.h — what the engine's translation units share: the instance record and its staging / allocation helpers
 // (engine_instance.cpp), the 4-state walk runner (engine_walk.cpp), the level scheduler for every other state count
-// (engine_levels.cpp), the pre-order / gradient paths (engine_preorder.cpp); the C ABI itself is engine_abi.cpp.
+// (engine_levels.cpp), the pre-order / gradient paths (engine_preorder.cpp).  The C ABI of include/beagle_mi355.h is spread over
+//   engine_create.cpp    instance creation, the -beagle_auto self-benchmark
+//   engine_abi.cpp       everything a caller SETS or ENQUEUES: patterns, tips, partials, model arrays, transition matrices,
+//                        updatePartials, scale factors, the pre-order entry points; the two Beagle*Api tables
+//   engine_root.cpp      the calls that observe a likelihood: root sums, the polled result page, site log-likelihoods
+//   engine_readback.cpp  partials and scale factors back to the host
+//   engine_sampling.cpp  the device samplers (ancestral draws, Markov jumps, uniformized histories)
+//   engine_stats.cpp     stream, synchronisation, kernel timer, counters
+// each of them argument checks, buffer bookkeeping and one call into the files above.
 // All arithmetic is in the .hip files; these files validate indices, resolve buffer indices to device pointers and enqueue
 // kernels on the instance's HIP stream.  Results are only observed at calculateRootLogLikelihoods / get*, so every other
 // call returns as soon as its work is enqueued (SURVEY 8b "Threading").
@@ -43,7 +51,7 @@ constexpr size_t RING_BYTES = 16u << 20;   // pinned host staging ring + its dev
 constexpr int SLAB_BUFFERS = 32;           // partials buffers per hipMalloc
 constexpr int PRE_SCRATCH = 32;            // pre-order ops per two-pass chunk on the T32 layout
 constexpr int GRADIENT_VIRT_STEPS = 2;     // longest definition a gradient chain can leave unstored (Instance::gradientVirtual)
-constexpr int GRADIENT_VIRT_DEFAULT = 1;   // ... and what it does leave unstored by default: nodes over two tips (engine_abi.cpp)
+constexpr int GRADIENT_VIRT_DEFAULT = 1;   // ... and what it does leave unstored by default: nodes over two tips (engine_create.cpp)
 
 struct Basta;                              // engine_basta.cpp
 
@@ -131,7 +139,7 @@ struct Instance {
                                                          // definitions the pre-order walk re-evaluates from the tips itself
     // 4 states: a gradient chain's post-order passes keep definitions of up to GRADIENT_VIRT_STEPS steps (tip-tip nodes, and those
     // under one more tip — half the nodes of a coalescent tree) instead of storing every node, and k_preWalk4 re-evaluates them where
-    // it needs them (engine_preorder.cpp walkableDefinition).  BEAGLE_MI355_GRADIENT_VIRTUAL at creation (engine_abi.cpp): 0 = every
+    // it needs them (engine_preorder.cpp walkableDefinition).  BEAGLE_MI355_GRADIENT_VIRTUAL at creation (engine_create.cpp): 0 = every
     // node stored, as in round 4; 1 = THE DEFAULT (GRADIENT_VIRT_DEFAULT): nodes over two tips stay unstored and are evaluated inside
     // their parents' descriptors (a third of the bytes of both passes: 6.1 -> 5.3-5.5 ms per gradient at 1e5 patterns); 2 = also such a
     // node under one more tip, by descriptors of their own (half the bytes, slower: a descriptor costs a stage whatever it computes).
@@ -336,6 +344,15 @@ inline hipStream_t live(Instance* in) {
 }
 // queue `bytes` already staged at ring offset `off` for device address dst (or copy them now: kernelUploads off)
 int queueCopy(Instance* in, void* dst, size_t off, size_t bytes);
+// the stream is idle, or a result behind everything staged so far has been seen: with nothing queued the ring starts over
+inline void ringIdle(Instance* in) { if (in->pendingCopies.empty() && !in->pendingWalk.valid) in->ringHead = 0; }
+// while one of these lives, an upload leaves a held walk launch held: what is uploaded is the root's input or the held walk's own,
+// nothing the walk's kernels before it read (Instance::copyKeepsWalk, queueCopy)
+struct KeepWalkHeld {
+    Instance* in;
+    explicit KeepWalkHeld(Instance* i) : in(i) { in->copyKeepsWalk = true; }
+    ~KeepWalkHeld() { in->copyKeepsWalk = false; }
+};
 
 // (a held-back pre-order list — Instance::heldPre — runs before anything else touches the instance; the few calls that cannot
 // interact with it use GET_INSTANCE_KEEP_PENDING)
@@ -406,6 +423,10 @@ int executeHeldPre(Instance* in);
 int edgeDifferentials(Instance* in, const int* postIdx, const int* preIdx, const int* dIdx, int wIdx, int count,
                       double* outDerivatives, double* outSum, double* outSumSquared);
 int crossProducts(Instance* in, const int* postIdx, const int* preIdx, int rateIdx, int wIdx, const double* lengths, int count, double* outSum);
+
+// ---- engine_create.cpp
+size_t matrixSlotLayout(Instance* in);
+int uploadIdentityMatrix(Instance* in);
 
 // ---- engine_basta.cpp: an instance that has BASTA buffers keeps its S-double vectors there (setPartials / getPartials)
 int bastaSetPartials(Instance* in, int bufferIndex, const double* inPartials);

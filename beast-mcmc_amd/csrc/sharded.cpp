@@ -301,7 +301,7 @@ int shardedRootReduce(int handle, int count, const std::function<int(int shardHa
         }
         if (ncclGroupEnd() != ncclSuccess) return BEAGLE_ERROR_GENERAL;
         // the result reaches the host from shard 0: one small kernel behind its all-reduce writes the values and a sequence word
-        // into mapped host memory, which this thread polls (engine_abi.cpp publishAndWait) — a device-to-host copy, a stream
+        // into mapped host memory, which this thread polls (engine_root.cpp publishAndWait) — a device-to-host copy, a stream
         // synchronisation and a synchronisation of every other shard cost more than a small shard's kernels.  The other shards
         // are not waited for: their rank of the all-reduce has contributed when shard 0's completes, and what follows on their
         // streams is ordered behind it by the streams themselves (their staging rings drain when they wrap).
@@ -317,7 +317,7 @@ int shardedRootReduce(int handle, int count, const std::function<int(int shardHa
     } else {
         // no communicator (one GPU, or BEAGLE_MI355_SHARDS on one): every shard's sums reach the host the way a single instance's do — a
         // small kernel behind the shard's root kernels writes them and a sequence word into mapped host memory, which this thread polls
-        // (engine_abi.cpp publishAndWait; it resets the shard's staging ring) — and are added in shard order.  A device-to-host copy and a
+        // (engine_root.cpp publishAndWait; it resets the shard's staging ring) — and are added in shard order.  A device-to-host copy and a
         // stream synchronisation per shard cost 20-50 us of an evaluation (round 6: the reference's benchmark1 alignment through this
         // handle on one GPU 7 080 -> see profiles/r06_experiments.txt 25).
         std::vector<double> acc(count, 0.0), part(count);

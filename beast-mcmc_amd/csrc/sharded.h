@@ -1,6 +1,7 @@
 // sharded.h — the multi-GPU (pattern-sharded) instance behind one handle; see sharded.cpp.
 #pragma once
 #include <functional>
+#include <mutex>
 
 #include "../../include/beagle_mi355.h"
 
@@ -8,7 +9,7 @@ namespace mi355 {
 
 constexpr int SHARD_HANDLE_BASE = 1 << 20;      // handles >= this are sharded instances
 // While the library creates the shards of a sharded instance: the pattern count of the WHOLE alignment.  The size-dependent choices an
-// instance makes for itself (how long a virtual definition may be: engine_abi.cpp) are then made as the single-GPU instance of the same
+// instance makes for itself (how long a virtual definition may be: engine_create.cpp) are then made as the single-GPU instance of the same
 // alignment would make them — same programs per pattern, hence the same site values bit for bit (tests/test_gpu_sharded_instance.py).
 extern thread_local int tlsWholePatternCount;
 inline bool isShardedHandle(int h) { return h >= SHARD_HANDLE_BASE; }
@@ -29,6 +30,17 @@ void shardedBoundsOfHandle(int handle, int shardHandle, int* pStart, int* pEnd);
 
 // the same call on every shard (each on its own host thread); first error wins
 int shardedBroadcast(int handle, const std::function<int(int shardHandle)>& call);
+// the same call, answered by ONE shard — whichever arrives first; the others return 0 — for what every shard would answer alike (a
+// matrix, the counters of programs every shard runs the same way)
+template <class Call>
+int shardedFirst(int handle, Call call) {
+    bool first = true;
+    std::mutex mu;
+    return shardedBroadcast(handle, [&](int h) {
+        { std::lock_guard<std::mutex> l(mu); if (!first) return 0; first = false; }
+        return call(h);
+    });
+}
 // the same, WITHOUT waiting (calls that return nothing to the caller): `call` must own everything it reads — the caller's
 // arrays may be reused as soon as this returns; errors surface at the next waiting call
 int shardedPost(int handle, std::function<int(int shardHandle)> call);
@@ -43,7 +55,7 @@ int shardedRootReduce(int handle, int count, const std::function<int(int shardHa
 int shardedSumDoubles(int handle, int len, const std::function<int(int shardHandle, double* out)>& call, double* outSum);
 
 
-// engine_abi.cpp, for the reduction above: `count` doubles at device address dValues of (single-GPU) instance `instance` go to
+// engine_root.cpp, for the reduction above: `count` doubles at device address dValues of (single-GPU) instance `instance` go to
 // the host through the instance's mapped result words — one small kernel behind whatever is on the instance's stream, then a
 // poll — instead of a device-to-host copy and a stream synchronisation.  count <= 480.
 int publishAndWait(int instance, const double* dValues, int count, double* out);

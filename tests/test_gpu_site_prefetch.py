@@ -1,4 +1,4 @@
-"""Site log-likelihoods sent to the host before the caller asks (engine_abi.cpp sitePrefetchAfterRoot / sitePrefetchTake).
+"""Site log-likelihoods sent to the host before the caller asks (engine_root.cpp sitePrefetchAfterRoot / sitePrefetchTake).
 
 BeagleTreeLikelihood reads the site values back after EVERY evaluation (BeagleTreeLikelihood.java:1050).  After two such reads in a
 row the engine copies the next root sum's site values into a pinned host buffer right behind the root's kernel; the getter then

@@ -331,7 +331,8 @@ def test_product_library_knows_only_the_documented_switches():
     csrc = os.path.join(ROOT, "beast-mcmc_amd", "csrc")
     for f in os.listdir(csrc):
         src += open(os.path.join(csrc, f), errors="replace").read()
-    read = set(re.findall(r'(?:getenv|labEnv)\("(BEAGLE_MI355_[A-Z0-9_]+)"\)', src))
+    # (switchOn: engine_create.cpp's reader of the on/off switches)
+    read = set(re.findall(r'(?:getenv|labEnv|switchOn)\("(BEAGLE_MI355_[A-Z0-9_]+)"\)', src))
     assert read <= documented | lab_names, read - (documented | lab_names)
     assert {n for n in re.findall(r'labEnv\("(BEAGLE_MI355_[A-Z0-9_]+)"\)', src)} <= lab_names
 

@@ -27,7 +27,7 @@ from beast_mcmc_amd.treelikelihood import BeagleTreeLikelihood, RESCALE_DYNAMIC 
 
 def sampler_source_hash():
     h = hashlib.sha256()
-    for f in ("kernels_ancestral.hip", "engine_abi.cpp"):
+    for f in ("kernels_ancestral.hip", "engine_sampling.cpp"):
         with open(os.path.join(ROOT, "beast-mcmc_amd", "csrc", f), "rb") as fh:
             h.update(fh.read())
     return h.hexdigest()[:16]

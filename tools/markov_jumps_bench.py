@@ -28,7 +28,7 @@ from beast_mcmc_amd.treelikelihood import BeagleTreeLikelihood, RESCALE_DYNAMIC 
 
 def source_hash():
     h = hashlib.sha256()
-    for f in ("kernels_markovjumps.hip", "kernels_ancestral.hip", "engine_abi.cpp"):
+    for f in ("kernels_markovjumps.hip", "kernels_ancestral.hip", "engine_sampling.cpp"):
         with open(os.path.join(ROOT, "beast-mcmc_amd", "csrc", f), "rb") as fh:
             h.update(fh.read())
     return h.hexdigest()[:16]

@@ -31,7 +31,7 @@ HOST_PATTERNS = 200
 
 def source_hash():
     h = hashlib.sha256()
-    for f in ("kernels_uniformized.hip", "kernels_ancestral.hip", "ancestral_draw.h", "engine_abi.cpp"):
+    for f in ("kernels_uniformized.hip", "kernels_ancestral.hip", "ancestral_draw.h", "engine_sampling.cpp"):
         with open(os.path.join(ROOT, "beast-mcmc_amd", "csrc", f), "rb") as fh:
             h.update(fh.read())
     return h.hexdigest()[:16]
