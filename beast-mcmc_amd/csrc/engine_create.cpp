@@ -213,6 +213,18 @@ int beagleCreateInstance(int tipCount, int partialsBufferCount, int compactBuffe
     in->walkTWrite = in->walkT && stateCount <= 20 && categoryCount <= mi355::WALK_T32_WRITE_MAX_CATEGORIES && in->holdSlots <= mi355::WALK_T32_WRITE_MAX_HOLD &&
                      !switchOn("BEAGLE_MI355_NO_T32_WRITE_WALK");
     in->planner.init(partialsBufferCount, tipCount, matrixBufferCount, scaleBufferCount, maxVirtSteps, virtualOn, in->holdSlots);
+    // Memory definitions (planner.h memStepCap): a node over ONE stored internal node and a tip or a small clade is defined over that
+    // stored node instead of being stored itself — over half of config A's stored nodes are of that kind.  The 4-state walk
+    // with hold slots, where a store is what an evaluation waits for (buffers of 2 MiB and more: the definition cap of 24); one
+    // partition (the planner's users list of a stored operand is per buffer); not the gradient chain (planner.h stepLimit).  The T32 /
+    // T64 walks (16..64 states) keep every such node stored.  BEAGLE_MI355_NO_MEM_DEFS=1: off;  BEAGLE_MI355_MEM_DEF_STEPS=n: the
+    // cap, on any 4-state walk instance (0: off).
+    {
+        int memSteps = maxVirtSteps == 24 ? MEM_DEF_STEPS : 0;
+        if (getenv("BEAGLE_MI355_MEM_DEF_STEPS")) memSteps = std::max(0, std::min(maxVirtSteps, atoi(getenv("BEAGLE_MI355_MEM_DEF_STEPS"))));
+        if (switchOn("BEAGLE_MI355_NO_MEM_DEFS") || !in->walk || in->walkT || !virtualOn || in->holdSlots < 2) memSteps = 0;
+        in->planner.memStepCap = memSteps;
+    }
     in->planner.cacheEnabled = !switchOn("BEAGLE_MI355_NO_PLAN_CACHE");
     in->fastWalk = !switchOn("BEAGLE_MI355_NO_FAST_WALK");
     in->strictWaits = !(getenv("BEAGLE_MI355_STRICT_WAITS") && atoi(getenv("BEAGLE_MI355_STRICT_WAITS")) == 0);

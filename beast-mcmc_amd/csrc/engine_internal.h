@@ -51,6 +51,7 @@ constexpr size_t RING_BYTES = 16u << 20;   // pinned host staging ring + its dev
 constexpr int SLAB_BUFFERS = 32;           // partials buffers per hipMalloc
 constexpr int PRE_SCRATCH = 32;            // pre-order ops per two-pass chunk on the T32 layout
 constexpr int GRADIENT_VIRT_STEPS = 2;     // longest definition a gradient chain can leave unstored (Instance::gradientVirtual)
+constexpr int MEM_DEF_STEPS = 8;           // longest definition over a stored internal node (planner.h memStepCap; engine_create.cpp)
 constexpr int GRADIENT_VIRT_DEFAULT = 1;   // ... and what it does leave unstored by default: nodes over two tips (engine_create.cpp)
 
 struct Basta;                              // engine_basta.cpp

@@ -8,7 +8,7 @@ namespace mi355 {
 
 namespace {
 constexpr int OP_NONE = -1;                 // BEAGLE_OP_NONE
-enum { CL_TIPS = 0, CL_MEM = 1, CL_VIRT = 2, CL_REAL = 3 };
+enum { CL_TIPS = 0, CL_MEM = 1, CL_VIRT = 2, CL_REAL = 3, CL_PATH = 4 };      // (CL_PATH: planner.h memStepCap, emitReal)
 inline int popcount2(unsigned m) { return (int)(m & 1u) + (int)((m >> 1) & 1u) + (int)((m >> 2) & 1u); }      // free hold slots (up to 3)
 inline int lowestSlot(unsigned m) { return (m & 1u) ? 0 : (m & 2u) ? 1 : 2; }
 }  // namespace
@@ -67,8 +67,11 @@ void WalkPlanner::registerVirtual(int X) {
 // Try to define buffer X = node(child1 over matrix m1, child2 over matrix m2, scale).  Children are compact tips or
 // virtual buffers.  Appends (source, destination) matrix-copy pairs.  false: too many steps, or its evaluation would need
 // more hold slots than a definition may take.
-bool WalkPlanner::buildVirtual(int X, int c1, bool tip1, bool mem1, int m1, int c2, bool tip2, bool mem2, int m2, int scaleIdx, std::vector<int>& snapPairs) {
-    // (tip1 / tip2: the child is a LEAF — compact states, or with mem1 / mem2 uploaded tip partials)
+bool WalkPlanner::buildVirtual(int X, int c1, bool tip1, bool mem1, int m1, int c2, bool tip2, bool mem2, int m2, int scaleIdx, std::vector<int>& snapPairs,
+                               bool stored1, bool stored2) {
+    // (tip1 / tip2: the child is a LEAF — compact states, or with mem1 / mem2 uploaded tip partials, or with stored1 / stored2 as well
+    // a stored internal node: a memory definition, planner.h memStepCap — at most one such leaf in the whole definition)
+    if (stored1 && stored2) return false;
     VirtDef nv;
     nv.on = true; nv.stamp = stamp_; nv.nSteps = 0; nv.chainOnly = true;
     std::vector<int>& pairs = pairScratch_;
@@ -79,6 +82,10 @@ bool WalkPlanner::buildVirtual(int X, int c1, bool tip1, bool mem1, int m1, int 
     auto append = [&](int srcBuf) -> int {
         const VirtDef& src = virt_[srcBuf];
         const int base = nv.nSteps;
+        if (src.memKey >= 0) {
+            if (nv.memKey >= 0) return -1;
+            nv.memKey = src.memKey; nv.memStep = base + src.memStep;
+        }
         for (int s = 0; s < src.nSteps; s++) {
             if (nv.nSteps >= cap) return -1;
             VirtStep h = src.steps[s];
@@ -98,6 +105,7 @@ bool WalkPlanner::buildVirtual(int X, int c1, bool tip1, bool mem1, int m1, int 
     last.scaleIdx = scaleIdx; last.tipA = -1; last.tipB = -1; last.subA = -1; last.subB = -1; last.need = 0; last.memA = last.memB = false;
     if (tip1 && tip2) {
         last.type = VT_CHERRY; last.tipA = c1; last.tipB = c2; last.originA = m1; last.originB = m2; last.memA = mem1; last.memB = mem2;
+        if (stored1 || stored2) { nv.memKey = stored1 ? c1 : c2; nv.memStep = 0; }
     } else if (tip1 != tip2) {
         const int vb = tip1 ? c2 : c1, t = tip1 ? c1 : c2, mv = tip1 ? m2 : m1, mt = tip1 ? m1 : m2;
         if (!virt_[vb].on) return false;
@@ -105,6 +113,10 @@ bool WalkPlanner::buildVirtual(int X, int c1, bool tip1, bool mem1, int m1, int 
         if (r < 0) return false;
         last.type = VT_EXTEND; last.subA = r; last.tipB = t; last.originA = mv; last.originB = mt; last.memB = tip1 ? mem1 : mem2;
         last.need = nv.steps[r].need;
+        if (tip1 ? stored1 : stored2) {
+            if (nv.memKey >= 0) return false;
+            nv.memKey = t; nv.memStep = nv.nSteps;
+        }
     } else {
         if (!virt_[c1].on || !virt_[c2].on) return false;
         const int ra = append(c1);
@@ -116,7 +128,7 @@ bool WalkPlanner::buildVirtual(int X, int c1, bool tip1, bool mem1, int m1, int 
         last.need = std::min(std::max(na, 1 + nb), std::max(nb, 1 + na));
         if (last.need > maxNeed) return false;
     }
-    if (nv.nSteps >= cap) return false;
+    if (nv.nSteps >= (nv.memKey >= 0 ? std::min(cap, memStepCap) : cap)) return false;
     pairs.push_back(last.originA); pairs.push_back(snapSlot(X, nv.nSteps, 0));
     pairs.push_back(last.originB); pairs.push_back(snapSlot(X, nv.nSteps, 1));
     nv.steps[nv.nSteps++] = last;
@@ -175,11 +187,72 @@ void WalkPlanner::mustMaterializeBefore(const int* ops, int count, int tuple, st
         for (int u : scaleUsers_[wS])
             if (wStamp_[u] != stamp_) out.push_back(u);          // a destination of this list is redefined anyway
     }
+    // memory definitions (planner.h memStepCap): a buffer keeps the value its operation gave it, so whatever reads a destination of
+    // this list as its stored operand — and is not a destination itself — is evaluated from the OLD data first
+    if (memStepCap > 0 && keyParts_ == 1)
+        for (int k = 0; k < count; k++)
+            for (int u : tipUsers_[ops[(size_t)k * tuple]])
+                if (wStamp_[u] != stamp_) out.push_back(u);
+}
+
+// ---- memory definitions (planner.h memStepCap) ---------------------------------------------------------------------
+int WalkPlanner::operandOp(int vkey) const {
+    const VirtDef& v = virt_[vkey];
+    if (!v.on || v.memKey < 0 || wStamp_[v.memKey] != stamp_) return -1;
+    const int a = wOp_[v.memKey];
+    return info_[a].virtDest ? -1 : a;
+}
+
+bool WalkPlanner::onPath(const VirtDef& v, int idx) const {
+    int p = v.memStep;
+    for (int t = p + 1; t <= idx && p != idx; t++)
+        if (v.steps[t].subA == p || v.steps[t].subB == p) p = t;
+    return p == idx;
+}
+
+// Steps memStep .. upTo of a memory definition evaluated where the program has just produced the stored operand (needA: the hold
+// slots the operand's own evaluation takes): at every step of the path the costlier side first, parked while the other is evaluated.
+int WalkPlanner::pathNeed(const VirtDef& v, int upTo, int needA) const {
+    auto both = [](int a, int b) { return std::min(std::max(a, 1 + b), std::max(b, 1 + a)); };
+    int p = v.memStep, n = needA;
+    if (v.steps[p].type == VT_EXTEND) n = both(needA, v.steps[v.steps[p].subA].need);
+    for (int t = p + 1; t <= upTo && p != upTo; t++) {
+        const VirtStep& s = v.steps[t];
+        if (s.subA != p && s.subB != p) continue;
+        if (s.type == VT_JOIN) n = both(n, v.steps[s.subA == p ? s.subB : s.subA].need);
+        p = t;
+    }
+    return n;
+}
+
+// hold slots the evaluation of the real op k needs, and its size — children come earlier in the list
+void WalkPlanner::realInfo(int k) {
+    OpInfo& o = info_[k];
+    int need[2] = {0, 0}, size[2] = {0, 0}; bool eval[2] = {false, false}, real[2] = {false, false};
+    for (int w = 0; w < 2; w++) {
+        const bool tip = w ? o.tip2 : o.tip1;
+        const int c = w ? o.c2 : o.c1, prod = w ? prod2_[k] : prod1_[k];
+        if (tip) continue;
+        if (prod >= 0 && !info_[prod].virtDest) { eval[w] = real[w] = true; need[w] = info_[prod].need; size[w] = info_[prod].size; }
+        else if (virt_[key(c, o.part)].on) {
+            const VirtDef& v = virt_[key(c, o.part)];
+            const int a = operandOp(key(c, o.part));
+            eval[w] = true;
+            if (a >= 0) { need[w] = pathNeed(v, v.nSteps - 1, info_[a].need); size[w] = info_[a].size; }
+            else need[w] = virtNeed(key(c, o.part));
+        }
+    }
+    o.size = 1 + size[0] + size[1];
+    if (eval[0] && eval[1]) {
+        auto cost = [&](int a, int b) { return real[a] ? std::max(need[a], need[b]) : std::max(need[a], 1 + need[b]); };
+        o.need = std::min(cost(0, 1), cost(1, 0));
+    } else o.need = eval[0] ? need[0] : eval[1] ? need[1] : 0;
+    if (allSlots_ == 0u) o.need = 0;            // no hold slots: the first of two evaluated children goes through memory
 }
 
 // ---- emission ----------------------------------------------------------------------------------------------------
 namespace {
-struct Child { int cls, buf, mat, prod, need, size, vkey; };      // vkey: definition key of (buf, the op's partition)
+struct Child { int cls, buf, mat, prod, need, size, vkey, vstep; };      // vkey: definition key of (buf, the op's partition), vstep: the step of it to evaluate
 inline MicroOp blankOp() {
     MicroOp m; m.storeBuf = PLAN_NONE; m.k1 = PK_MEM; m.a1 = 0; m.k2 = PK_MEM; m.a2 = 0; m.mat1 = 0; m.mat2 = 0;
     m.scaleIdx = PLAN_NONE; m.smode = PS_NONE; m.hold = 0;
@@ -240,29 +313,62 @@ void WalkPlanner::emitVirtual(int buf, unsigned freeMask, bool writeMode, Plan& 
 // heap): the dependency depth of an operation list is unbounded — a 5000-tip ladder tree is 4999 frames deep — and under
 // BEAST this runs on a JVM thread whose native stack is 1 MiB or less (-Xss).
 void WalkPlanner::emitReal(int root, unsigned rootMask, Plan& out) {
-    struct Frame { int j; unsigned freeMask; int phase; Child ch[2]; int first; bool hold; MicroOp m; };
+    // A frame is a real op of the list (j >= 0), or — a memory definition evaluated behind its operand's own program, planner.h memStepCap —
+    // step pidx of definition pkey on the path from the stored operand to the definition's last step (j < 0): a node like any other,
+    // whose children are the path below it (at step memStep: the operand's real op) and a tip or a plain part of the definition, whose
+    // matrices are the definition's snapshots and whose result is not stored.
+    struct Frame { int j, pkey, pidx; unsigned freeMask; int phase; Child ch[2]; int first; bool hold; MicroOp m; };
     std::vector<Frame> st;
-    auto push = [&](int j, unsigned fm) { Frame f; f.j = j; f.freeMask = fm; f.phase = 0; f.first = 0; f.hold = false; f.m = blankOp(); st.push_back(f); };
-    push(root, rootMask);
+    auto push = [&](int j, int pkey, int pidx, unsigned fm) { Frame f; f.j = j; f.pkey = pkey; f.pidx = pidx; f.freeMask = fm; f.phase = 0; f.first = 0; f.hold = false; f.m = blankOp(); st.push_back(f); };
+    auto pushChild = [&](const Child& c, unsigned fm) { if (c.cls == CL_REAL) push(c.prod, -1, -1, fm); else push(-1, c.vkey, c.vstep, fm); };
+    push(root, -1, -1, rootMask);
     while (!st.empty()) {
         const size_t top = st.size() - 1;                 // (a push invalidates references: every path that pushes `continue`s)
-        OpInfo& o = info_[st[top].j];
         if (st[top].phase == 0) {
             Frame& f = st[top];
-            for (int w = 0; w < 2; w++) {
-                Child& c = f.ch[w];
-                c.buf = w ? o.c2 : o.c1; c.mat = w ? o.m2 : o.m1;
-                const bool tip = w ? o.tip2 : o.tip1;
-                c.prod = -1; c.need = 0; c.size = 0; c.vkey = key(c.buf, o.part);
-                if (tip) { c.cls = CL_TIPS; continue; }
-                const int prod = w ? prod2_[f.j] : prod1_[f.j];
-                if (prod >= 0) {
-                    const OpInfo& p = info_[prod];
-                    if (p.virtDest) { c.cls = CL_VIRT; c.need = virtNeed(c.vkey); c.size = 0; }
-                    else if (p.emitted) c.cls = CL_MEM;
-                    else { c.cls = CL_REAL; c.prod = prod; c.need = p.need; c.size = p.size; }
-                } else if (virt_[c.vkey].on) { c.cls = CL_VIRT; c.need = virtNeed(c.vkey); }
-                else c.cls = CL_MEM;
+            if (f.j >= 0) {
+                const OpInfo& o = info_[f.j];
+                for (int w = 0; w < 2; w++) {
+                    Child& c = f.ch[w];
+                    c.buf = w ? o.c2 : o.c1; c.mat = w ? o.m2 : o.m1;
+                    const bool tip = w ? o.tip2 : o.tip1;
+                    c.prod = -1; c.need = 0; c.size = 0; c.vkey = key(c.buf, o.part); c.vstep = -1;
+                    if (tip) { c.cls = CL_TIPS; continue; }
+                    const int prod = w ? prod2_[f.j] : prod1_[f.j];
+                    bool virt = false;
+                    if (prod >= 0) {
+                        const OpInfo& p = info_[prod];
+                        if (p.virtDest) virt = true;
+                        else if (p.emitted) c.cls = CL_MEM;
+                        else { c.cls = CL_REAL; c.prod = prod; c.need = p.need; c.size = p.size; }
+                    } else if (virt_[c.vkey].on) virt = true;
+                    else c.cls = CL_MEM;
+                    if (virt) {
+                        const VirtDef& v = virt_[c.vkey];
+                        c.cls = CL_VIRT; c.need = virtNeed(c.vkey); c.vstep = v.nSteps - 1;
+                        const int a = v.memKey >= 0 ? operandOp(c.vkey) : -1;
+                        if (a >= 0 && !info_[a].emitted) { c.cls = CL_PATH; c.prod = a; c.need = pathNeed(v, c.vstep, info_[a].need); c.size = info_[a].size; }
+                    }
+                }
+            } else {
+                const VirtDef& v = virt_[f.pkey];
+                const VirtStep& s = v.steps[f.pidx];
+                const int a = operandOp(f.pkey);
+                auto leaf = [&](Child& c, int buf, bool mem, int which) { c.cls = mem ? CL_MEM : CL_TIPS; c.buf = buf; c.mat = snapSlot(f.pkey, f.pidx, which); c.prod = -1; c.need = 0; c.size = 0; c.vkey = -1; c.vstep = -1; };
+                auto operand = [&](Child& c, int which) { c.cls = CL_REAL; c.buf = v.memKey; c.mat = snapSlot(f.pkey, f.pidx, which); c.prod = a; c.need = info_[a].need; c.size = info_[a].size; c.vkey = -1; c.vstep = -1; };
+                auto sub = [&](Child& c, int step, int which) {
+                    c.buf = -1; c.mat = snapSlot(f.pkey, f.pidx, which); c.prod = -1; c.size = 0; c.vkey = f.pkey; c.vstep = step;
+                    if (onPath(v, step)) { c.cls = CL_PATH; c.need = pathNeed(v, step, info_[a].need); c.size = info_[a].size; }
+                    else { c.cls = CL_VIRT; c.need = v.steps[step].need; }
+                };
+                if (s.type == VT_CHERRY) {                // (the path's first step: the stored operand over a tip)
+                    const bool opA = s.memA && s.tipA == v.memKey;
+                    if (opA) { operand(f.ch[0], 0); leaf(f.ch[1], s.tipB, s.memB, 1); }
+                    else { leaf(f.ch[0], s.tipA, s.memA, 0); operand(f.ch[1], 1); }
+                } else if (s.type == VT_EXTEND) {
+                    sub(f.ch[0], s.subA, 0);
+                    if (f.pidx == v.memStep) operand(f.ch[1], 1); else leaf(f.ch[1], s.tipB, s.memB, 1);
+                } else { sub(f.ch[0], s.subA, 0); sub(f.ch[1], s.subB, 1); }
             }
             const bool e0 = f.ch[0].cls >= CL_VIRT, e1 = f.ch[1].cls >= CL_VIRT;
             if (!e0 && !e1) {
@@ -278,12 +384,12 @@ void WalkPlanner::emitReal(int root, unsigned rootMask, Plan& out) {
                 if (l.cls == CL_MEM) lastMemReads++;
                 f.m.k2 = PK_ACC; f.m.mat2 = e.mat;
                 f.phase = 9;
-                if (e.cls == CL_VIRT) emitVirtual(e.vkey, f.freeMask, true, out);
-                else { push(e.prod, f.freeMask); continue; }
+                if (e.cls == CL_VIRT) emitVirtualStep(e.vkey, e.vstep, f.freeMask, true, out);
+                else { const unsigned fm = f.freeMask; pushChild(e, fm); continue; }
             } else {
                 const int F = popcount2(f.freeMask);
                 auto holdOK = [&](const Child& a, const Child& b) { return a.need <= F && 1 + b.need <= F; };
-                auto plainOK = [&](const Child& a, const Child& b) { return a.cls == CL_REAL && a.need <= F && b.need <= F; };
+                auto plainOK = [&](const Child& a, const Child& b) { return a.cls == CL_REAL && f.j >= 0 && a.need <= F && b.need <= F; };
                 const Child* ch = f.ch;
                 const bool h01 = holdOK(ch[0], ch[1]), h10 = holdOK(ch[1], ch[0]);
                 if (h01 || h10) {
@@ -300,11 +406,8 @@ void WalkPlanner::emitReal(int root, unsigned rootMask, Plan& out) {
                 }
                 f.phase = 1;
                 const Child a = ch[f.first];
-                if (a.cls == CL_VIRT) {
-                    emitVirtual(a.vkey, f.freeMask, true, out);
-                    if (!f.hold) { out.prog.back().storeBuf = a.buf; lastStored++; }      // (read back as PK_MEM below)
-                }
-                else { push(a.prod, f.freeMask); continue; }
+                if (a.cls == CL_VIRT) emitVirtualStep(a.vkey, a.vstep, f.freeMask, true, out);
+                else { const unsigned fm = f.freeMask; pushChild(a, fm); continue; }
             }
         }
         if (st[top].phase == 1) {                         // the first of two evaluated children is done
@@ -318,23 +421,36 @@ void WalkPlanner::emitReal(int root, unsigned rootMask, Plan& out) {
                 mask2 = f.freeMask & ~(1u << h);
                 f.m.k1 = PK_H0 + h; f.m.mat1 = a.mat;
             } else {
+                if (a.cls != CL_REAL) { out.prog.back().storeBuf = a.buf; lastStored++; }      // (a definition, stored for once)
                 f.m.k1 = PK_MEM; f.m.a1 = a.buf; f.m.mat1 = a.mat;
                 lastMemReads++;
             }
             f.m.k2 = PK_ACC; f.m.mat2 = b.mat;
             f.phase = 9;
-            if (b.cls == CL_VIRT) emitVirtual(b.vkey, mask2, true, out);
-            else { push(b.prod, mask2); continue; }
+            if (b.cls == CL_VIRT) emitVirtualStep(b.vkey, b.vstep, mask2, true, out);
+            else { pushChild(b, mask2); continue; }
         }
         {                                                 // phase 9: the node itself
             Frame& f = st[top];
             MicroOp& m = f.m;
-            m.storeBuf = o.dest;
-            if (o.wS != OP_NONE) { m.scaleIdx = o.wS; m.smode = PS_WRITE; sDone_[(size_t)o.wS * parts_ + o.part] = stamp_; }
-            else if (o.rS != OP_NONE) { m.scaleIdx = o.rS; m.smode = PS_READ; }
+            if (f.j >= 0) {
+                OpInfo& o = info_[f.j];
+                m.storeBuf = o.dest;
+                if (o.wS != OP_NONE) { m.scaleIdx = o.wS; m.smode = PS_WRITE; sDone_[(size_t)o.wS * parts_ + o.part] = stamp_; }
+                else if (o.rS != OP_NONE) { m.scaleIdx = o.rS; m.smode = PS_READ; }
+                o.emitted = true;
+                lastStored++;
+            } else {
+                const VirtStep& s = virt_[f.pkey].steps[f.pidx];
+                if (s.scaleIdx >= 0) {                    // (as emitVirtualStep)
+                    m.scaleIdx = s.scaleIdx;
+                    const size_t sk = (size_t)s.scaleIdx * parts_ + partitionOf(f.pkey);
+                    const bool w = sWStamp_[sk] == stamp_;
+                    m.smode = w ? PS_WRITE : PS_READ;
+                    if (w) sDone_[sk] = stamp_;
+                }
+            }
             out.prog.push_back(m);
-            o.emitted = true;
-            lastStored++;
             st.pop_back();
         }
     }
@@ -377,13 +493,15 @@ int WalkPlanner::plan(const int* ops, int count, int tuple, int parts, bool allo
             fill = &cache_[cacheNext_];
             cacheNext_ = (cacheNext_ + 1) % CACHE_WAYS;
             fill->valid = false; fill->cleanAtEpoch = -1; fill->tag = ++cacheTagNext_; fill->count = count; fill->tuple = tuple; fill->parts = parts; fill->chunkOps = chunkOps;
-            fill->allowVirtual = allowVirtual; fill->stepLimit = allowVirtual ? stepLimit : 0; fill->tipEpoch = compactEpoch; fill->simple = simple;
+            fill->allowVirtual = allowVirtual; fill->stepLimit = allowVirtual ? stepLimit : 0; fill->memStepCap = allowVirtual ? memStepCap : 0; fill->tipEpoch = compactEpoch; fill->simple = simple;
             fill->ops.assign(ops, ops + (size_t)count * tuple);
         }
     }
     info_.assign(count, OpInfo());
     prod1_.assign(count, -1); prod2_.assign(count, -1);
     std::vector<char> consumed(count, 0);
+    const bool memDefs = allowVirtual && memDefsOn(parts);
+    bool anyMem = false;
 
     // ---- pass 1, list order: virtual definitions, producers, hold needs
     for (int k = 0; k < count; k++) {
@@ -407,7 +525,9 @@ int WalkPlanner::plan(const int* ops, int count, int tuple, int parts, bool allo
         const bool v1 = !o.leaf1 && virt_[kc1].on, v2 = !o.leaf2 && virt_[kc2].on;
         const int ownScale = o.wS != OP_NONE ? o.wS : o.rS;
         bool makeVirtual = false;
-        if (allowVirtual && (o.leaf1 || v1) && (o.leaf2 || v2) && o.c1 != o.dest && o.c2 != o.dest) {
+        // (memory definitions: ONE child may be a stored internal node, or a definition that reads one — planner.h memStepCap)
+        const bool st1 = memDefs && !o.leaf1 && !v1, st2 = memDefs && !o.leaf2 && !v2;
+        if (allowVirtual && (o.leaf1 || v1 || st1) && (o.leaf2 || v2 || st2) && !(st1 && st2) && o.c1 != o.dest && o.c2 != o.dest) {
             VirtDef& ev = virt_[kd];
             // Steady state: the same op on the same buffers as when `dest` was last defined, its virtual children unchanged
             // (same definition version) and re-confirmed in this list exactly as they were fresh then -> the definition
@@ -418,7 +538,7 @@ int WalkPlanner::plan(const int* ops, int count, int tuple, int parts, bool allo
                 const VirtDef& cv = virt_[c];
                 return fresh && cv.stamp == stamp_ && cv.version == ver;
             };
-            if (ev.on && ev.nSteps <= stepCap() && ev.sigC1 == o.c1 && ev.sigM1 == o.m1 && ev.sigC2 == o.c2 && ev.sigM2 == o.m2 && ev.sigScale == ownScale &&
+            if (ev.on && ev.memKey < 0 && !st1 && !st2 && ev.nSteps <= stepCap() && ev.sigC1 == o.c1 && ev.sigM1 == o.m1 && ev.sigC2 == o.c2 && ev.sigM2 == o.m2 && ev.sigScale == ownScale &&
                 ev.sigMem1 == (o.leaf1 && !o.tip1) && ev.sigMem2 == (o.leaf2 && !o.tip2) &&
                 childSame(kc1, o.leaf1, ev.sigTip1, ev.childVer1, ev.fresh1) && childSame(kc2, o.leaf2, ev.sigTip2, ev.childVer2, ev.fresh2)) {
                 for (int st = 0; st < ev.nSteps; st++) {
@@ -430,16 +550,16 @@ int WalkPlanner::plan(const int* ops, int count, int tuple, int parts, bool allo
             } else {
                 VirtDef saved = ev;
                 if (saved.on) clearVirtualKey((int)kd);
-                makeVirtual = buildVirtual((int)kd, o.leaf1 ? o.c1 : (int)kc1, o.leaf1, o.leaf1 && !o.tip1, o.m1,
-                                           o.leaf2 ? o.c2 : (int)kc2, o.leaf2, o.leaf2 && !o.tip2, o.m2, ownScale, out.snapPairs);
+                makeVirtual = buildVirtual((int)kd, o.leaf1 || st1 ? o.c1 : (int)kc1, o.leaf1 || st1, (o.leaf1 && !o.tip1) || st1, o.m1,
+                                           o.leaf2 || st2 ? o.c2 : (int)kc2, o.leaf2 || st2, (o.leaf2 && !o.tip2) || st2, o.m2, ownScale, out.snapPairs, st1, st2);
                 if (!makeVirtual && saved.on) { virt_[kd] = saved; tagOf_[kd] = saved.cacheTag; tagEpoch_++; registerVirtual((int)kd); }
                 if (makeVirtual) {
                     VirtDef& nv = virt_[kd];
                     nv.version = ++virtVersion_;
                     nv.sigC1 = o.c1; nv.sigM1 = o.m1; nv.sigC2 = o.c2; nv.sigM2 = o.m2; nv.sigScale = ownScale;
-                    nv.sigTip1 = o.leaf1; nv.sigTip2 = o.leaf2; nv.sigMem1 = o.leaf1 && !o.tip1; nv.sigMem2 = o.leaf2 && !o.tip2;
-                    nv.fresh1 = !o.leaf1 && virt_[kc1].stamp == stamp_; nv.fresh2 = !o.leaf2 && virt_[kc2].stamp == stamp_;
-                    nv.childVer1 = o.leaf1 ? -1 : virt_[kc1].version; nv.childVer2 = o.leaf2 ? -1 : virt_[kc2].version;
+                    nv.sigTip1 = o.leaf1 || st1; nv.sigTip2 = o.leaf2 || st2; nv.sigMem1 = (o.leaf1 && !o.tip1) || st1; nv.sigMem2 = (o.leaf2 && !o.tip2) || st2;
+                    nv.fresh1 = !nv.sigTip1 && virt_[kc1].stamp == stamp_; nv.fresh2 = !nv.sigTip2 && virt_[kc2].stamp == stamp_;
+                    nv.childVer1 = nv.sigTip1 ? -1 : virt_[kc1].version; nv.childVer2 = nv.sigTip2 ? -1 : virt_[kc2].version;
                 }
             }
         }
@@ -447,22 +567,47 @@ int WalkPlanner::plan(const int* ops, int count, int tuple, int parts, bool allo
         o.virtDest = makeVirtual;
         wStamp_[kd] = stamp_; wOp_[kd] = k;
 
-        // hold slots the evaluation of this (real) node needs, and its size — children come earlier in the list
+        if (makeVirtual && virt_[kd].memKey >= 0) anyMem = true;
         if (!makeVirtual) {
-            int need[2] = {0, 0}, size[2] = {0, 0}; bool eval[2] = {false, false}, real[2] = {false, false};
-            for (int w = 0; w < 2; w++) {
-                const bool tip = w ? o.tip2 : o.tip1;
-                const int c = w ? o.c2 : o.c1, prod = w ? prod2_[k] : prod1_[k];
-                if (tip) continue;
-                if (prod >= 0 && !info_[prod].virtDest) { eval[w] = real[w] = true; need[w] = info_[prod].need; size[w] = info_[prod].size; }
-                else if (virt_[key(c, o.part)].on) { eval[w] = true; need[w] = virtNeed(key(c, o.part)); }
+            realInfo(k);
+            // two memory definitions, each behind its own operand's program, can take a hold slot more than the walk has: store them
+            if (memDefs && o.need > popcount2(allSlots_)) {
+                for (int w = 0; w < 2; w++) {
+                    const int ck = key(w ? o.c2 : o.c1, o.part);
+                    if ((w ? o.tip2 : o.tip1) || operandOp(ck) < 0 || wStamp_[ck] != stamp_) continue;
+                    const int x = wOp_[ck];
+                    clearVirtualKey(ck);
+                    info_[x].virtDest = false;
+                    realInfo(x);
+                }
+                realInfo(k);
             }
-            o.size = 1 + size[0] + size[1];
-            if (eval[0] && eval[1]) {
-                auto cost = [&](int a, int b) { return real[a] ? std::max(need[a], need[b]) : std::max(need[a], 1 + need[b]); };
-                o.need = std::min(cost(0, 1), cost(1, 0));
-            } else o.need = eval[0] ? need[0] : eval[1] ? need[1] : 0;
-            if (allSlots_ == 0u) o.need = 0;            // no hold slots: the first of two evaluated children goes through memory
+        }
+    }
+    // Memory definitions: who consumes whom is settled backwards — a definition nothing in this list evaluates is stored after all (the
+    // root of a tree: whoever reads it would otherwise evaluate it from memory in a launch of its own), and a stored operand is
+    // consumed by a definition only where that definition is evaluated
+    if (anyMem) {
+        std::fill(consumed.begin(), consumed.end(), 0);
+        std::vector<char> live(count, 0), absorbed(count, 0);      // evaluated by a real op of the list; its steps stand in a longer definition
+        for (int k = count - 1; k >= 0; k--) {
+            OpInfo& o = info_[k];
+            const int kd = key(o.dest, o.part);
+            if (o.virtDest && virt_[kd].memKey >= 0 && !live[k] && !absorbed[k]) { clearVirtualKey(kd); o.virtDest = false; realInfo(k); }
+            if (o.virtDest) {
+                const int a = live[k] ? operandOp(kd) : -1;
+                if (a >= 0) consumed[a] = 1;
+                for (int w = 0; w < 2; w++) {
+                    const int prod = w ? prod2_[k] : prod1_[k];
+                    if (prod >= 0 && info_[prod].virtDest) absorbed[prod] = 1;
+                }
+                continue;
+            }
+            for (int w = 0; w < 2; w++) {
+                const int prod = w ? prod2_[k] : prod1_[k];
+                if (prod < 0) continue;
+                if (info_[prod].virtDest) live[prod] = 1; else consumed[prod] = 1;
+            }
         }
     }
 
@@ -494,7 +639,11 @@ int WalkPlanner::plan(const int* ops, int count, int tuple, int parts, bool allo
                         const int buf = c ? o.c2 : o.c1, prod = c ? prod2_[k] : prod1_[k];
                         if (tip) continue;
                         if (prod >= 0 && !info_[prod].virtDest) { if (!info_[prod].emitted) w += weight[prod]; }
-                        else if (virt_[key(buf, o.part)].on) w += virt_[key(buf, o.part)].nSteps;
+                        else if (virt_[key(buf, o.part)].on) {
+                            w += virt_[key(buf, o.part)].nSteps;
+                            const int a = anyMem ? operandOp(key(buf, o.part)) : -1;      // (a memory definition: its operand's program comes with it)
+                            if (a >= 0 && !info_[a].emitted) w += weight[a];
+                        }
                     }
                     weight[k] = w;
                     if (!consumed[k]) total += w;
@@ -510,7 +659,8 @@ int WalkPlanner::plan(const int* ops, int count, int tuple, int parts, bool allo
                         if (weight[k] <= chunk) { chunkRoots.push_back(k); continue; }
                         bool descended = false;
                         for (int c = 1; c >= 0; c--) {
-                            const int prod = c ? prod2_[k] : prod1_[k];
+                            int prod = c ? prod2_[k] : prod1_[k];
+                            if (anyMem && !(c ? info_[k].tip2 : info_[k].tip1) && (prod < 0 || info_[prod].virtDest)) prod = operandOp(key(c ? info_[k].c2 : info_[k].c1, part));
                             if (prod >= 0 && !info_[prod].virtDest && !info_[prod].emitted) { stack.push_back(prod); descended = true; }
                         }
                         if (!descended) chunkRoots.push_back(k);      // heavier than a chunk but nothing below is left to peel
@@ -681,7 +831,7 @@ void WalkPlanner::linkSlices(Plan& out) {
 WalkPlanner::CacheEntry* WalkPlanner::findCached(const int* ops, int count, int tuple, int parts, bool allowVirtual, int chunkOps) {
     for (CacheEntry& e : cache_)
         if (e.valid && e.count == count && e.tuple == tuple && e.parts == parts && e.chunkOps == chunkOps && e.allowVirtual == allowVirtual &&
-            e.stepLimit == (allowVirtual ? stepLimit : 0) &&
+            e.stepLimit == (allowVirtual ? stepLimit : 0) && e.memStepCap == (allowVirtual ? memStepCap : 0) &&
             e.tipEpoch == compactEpoch && memcmp(e.ops.data(), ops, (size_t)count * tuple * sizeof(int)) == 0)
             return &e;
     return nullptr;
@@ -692,6 +842,13 @@ bool WalkPlanner::replayCached(const int* ops, int count, int tuple, int parts, 
     allowVirtual = allowVirtual && enabled_;
     CacheEntry* e = findCached(ops, count, tuple, parts, allowVirtual, chunkOps);
     if (!e || (simple && !e->simple)) return false;    // (asked for a simple list only: nothing has been touched)
+    // memory definitions: a simple list skips mustMaterializeBefore, so nothing but this entry's own definitions may read what the list
+    // overwrites (a branch move in between leaves such readers behind: that evaluation takes the long way) — looked at only when a
+    // definition has changed hands since this entry's last replay
+    if (simple && memStepCap > 0 && parts == 1 && e->cleanAtEpoch != tagEpoch_)
+        for (int k = 0; k < count; k++)
+            for (int u : tipUsers_[ops[(size_t)k * tuple]])
+                if (tagOf_[u] != e->tag) return false;
     parts_ = parts;
     stamp_ += 2;                                       // a list of its own, as in plan()
     replay(*e, ops);

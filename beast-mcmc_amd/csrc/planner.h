@@ -100,6 +100,9 @@ struct VirtDef {
     bool sigTip1 = false, sigTip2 = false, sigMem1 = false, sigMem2 = false, fresh1 = false, fresh2 = false;   // sigTip: the child is a leaf
     int childVer1 = -1, childVer2 = -1;
     long cacheTag = 0;      // plan-cache entry that last wrote or confirmed this definition (0: none) — see WalkPlanner::replay
+    // a MEMORY definition (WalkPlanner::memStepCap): one leaf of it is a stored INTERNAL node — memKey, read as partials in step memStep
+    // (tipA with memA of a VT_CHERRY, tipB with memB of a VT_EXTEND) — instead of a tip; -1: every leaf is a tip
+    int memKey = -1, memStep = -1;
     VirtStep steps[PLAN_MAX_STEPS];      // (copies take steps[0 .. nSteps) only)
     VirtDef() {}
     VirtDef(const VirtDef& o) { copyFrom(o); }
@@ -112,7 +115,7 @@ inline void VirtDef::copyFrom(const VirtDef& o) {
     on = o.on; chainOnly = o.chainOnly; nSteps = o.nSteps; stamp = o.stamp; version = o.version;
     sigC1 = o.sigC1; sigM1 = o.sigM1; sigC2 = o.sigC2; sigM2 = o.sigM2; sigScale = o.sigScale;
     sigTip1 = o.sigTip1; sigTip2 = o.sigTip2; sigMem1 = o.sigMem1; sigMem2 = o.sigMem2; fresh1 = o.fresh1; fresh2 = o.fresh2;
-    childVer1 = o.childVer1; childVer2 = o.childVer2; cacheTag = o.cacheTag;
+    childVer1 = o.childVer1; childVer2 = o.childVer2; cacheTag = o.cacheTag; memKey = o.memKey; memStep = o.memStep;
     for (int s = 0; s < o.nSteps; s++) steps[s] = o.steps[s];
 }
 
@@ -196,6 +199,16 @@ public:
     // under one more tip, nothing longer); part of a cached plan's identity.  The snapshot slots keep the instance's own spacing.
     int stepLimit = 0;
     int stepCap() const { return stepLimit > 0 && stepLimit < maxSteps_ ? stepLimit : maxSteps_; }
+    // memStepCap > 0: MEMORY definitions.  A node over ONE stored internal node A and a tip or a plain definition — or over a memory
+    // definition and a tip or a plain definition: the chain goes on upwards — is defined, not stored, while the definition has at most
+    // this many steps (<= stepCap()) and its evaluation fits the hold slots.  A stands in the definition as a leaf read from memory
+    // (VirtStep::memA / memB, VirtDef::memKey), so tipUsers(A) lists the definitions that read it and whoever overwrites A — an
+    // operation list (mustMaterializeBefore), an upload — gives them real data first.  A program that produces A itself evaluates the
+    // definition BEHIND A, taking A from ACC or a hold slot as a stored parent would (emitReal: path frames); only a program that does
+    // not produce A — a branch move passing the node as a sibling, a materialisation, a slice above the one that stored A — reads A.
+    // One partition, no step limit, a walk with hold slots; a definition that nothing in its list consumes is stored after all (a root).
+    // Part of a cached plan's identity.  0 (the default): off.
+    int memStepCap = 0;
     long cacheHits = 0;                  // plans served from the cache below
     long replayInPlace = 0;              // definitions a replay took over from another entry with their leaves unchanged (user lists edited in place)
     bool cacheEnabled = true;
@@ -212,12 +225,18 @@ private:
         int size;           // real micro-ops below (ordering heuristic)
         bool emitted;
     };
-    bool buildVirtual(int X, int c1, bool leaf1, bool mem1, int m1, int c2, bool leaf2, bool mem2, int m2, int scaleIdx, std::vector<int>& snapPairs);   // X, and a non-leaf child: KEYS
+    bool buildVirtual(int X, int c1, bool leaf1, bool mem1, int m1, int c2, bool leaf2, bool mem2, int m2, int scaleIdx, std::vector<int>& snapPairs,
+                      bool stored1 = false, bool stored2 = false);   // X, and a non-leaf child: KEYS;  stored: the leaf is a stored internal node (memStepCap)
     void registerVirtual(int X);
     // emission
     void emitReal(int root, unsigned freeMask, Plan& out);
     void emitVirtualStep(int buf, int idx, unsigned freeMask, bool writeMode, Plan& out);
     void emitVirtual(int buf, unsigned freeMask, bool writeMode, Plan& out);
+    bool memDefsOn(int parts) const { return memStepCap > 0 && parts == 1 && stepLimit == 0 && allSlots_ != 0u; }
+    int operandOp(int vkey) const;       // the real op of the list being planned that produces the definition's stored operand, or -1
+    int pathNeed(const VirtDef& v, int upTo, int needA) const;       // hold slots of steps memStep .. upTo evaluated behind the operand's own program
+    bool onPath(const VirtDef& v, int idx) const;                    // is step memStep in the subtree of step idx
+    void realInfo(int k);                // OpInfo::need / size of the (real) op k
     int virtNeed(int buf) const { return virt_[buf].nSteps ? virt_[buf].steps[virt_[buf].nSteps - 1].need : 0; }
     void linkSlices(Plan& out);          // PlanSeg::dep*, tail and Plan::launchOrder
     std::vector<int> storedBy_, storedStamp_;          // per (buffer, partition): the slice of the current plan that stores it
@@ -250,7 +269,7 @@ private:
     struct CacheEntry {
         bool valid = false;
         long tag = 0;
-        int count = 0, tuple = 0, parts = 0, chunkOps = 0, stepLimit = 0;
+        int count = 0, tuple = 0, parts = 0, chunkOps = 0, stepLimit = 0, memStepCap = 0;
         bool allowVirtual = false;
         std::vector<int> ops;
         long tipEpoch = -1;                            // compactEpoch the plan was made under
