@@ -125,7 +125,7 @@ ABI_SYMBOLS = ["beagleGetVersion", "beagleGetCitation", "beagleGetResourceList",
               ["beagleMi355SetStream", "beagleMi355CalculateRootLogLikelihoodsDevice", "beagleMi355Synchronize",
                "beagleMi355KernelTimer", "beagleMi355DeviceBytes", "beagleMi355WalkStats", "beagleMi355GradientStats", "beagleMi355GetPartialsBatch", "beagleMi355SampleAncestralStates", "beagleMi355SampleMarkovJumps", "beagleMi355SampleMarkovJumpsUniformized",
                "beagleMi355GetPartialsPinned", "beagleMi355GetSiteLogLikelihoodsPinned",
-               "beagleMi355KernelTimerCalls", "beagleMi355WalkHealth", "beagleMi355WalkLaunchInfo", "beagleMi355RootFusedCount", "beagleMi355SitePrefetchCount", "beagleMi355KernelTimerRestart", "beagleMi355GetDimensions", "beagleMi355GetCommUniqueId", "beagleMi355CommInit", "beagleMi355CommInfo", "beagleMi355CalculateRootLogLikelihoodsAllReduce"] + \
+               "beagleMi355KernelTimerCalls", "beagleMi355WalkHealth", "beagleMi355RepeatStats", "beagleMi355WalkLaunchInfo", "beagleMi355RootFusedCount", "beagleMi355SitePrefetchCount", "beagleMi355KernelTimerRestart", "beagleMi355GetDimensions", "beagleMi355GetCommUniqueId", "beagleMi355CommInit", "beagleMi355CommInfo", "beagleMi355CalculateRootLogLikelihoodsAllReduce"] + \
               ["beagleBasta" + k for k in ("AllocateCoalescentBuffers", "UpdatePartials", "AccumulatePartials", "GetBuffer", "GetBufferLength", "Stats",
                                            "UpdatePartialsGrad", "UpdateTransitionMatricesGrad", "AccumulatePartialsGrad")]
 BASTA_OPERATION_SIZE = 8
@@ -683,6 +683,17 @@ class Beagle:
         out = (C.c_long * 8)()
         self._check("walkStats", self._ext("beagleMi355WalkStats", [C.c_int, C.POINTER(C.c_long)])(self.instance, out))
         keys = ("micro_ops", "stored", "mem_reads", "tip_reads", "scale_reads", "walks", "scale_writes", "fast_walks")
+        stats = {k: int(out[i]) for i, k in enumerate(keys)}
+        rep = self.repeatStats()      # clades evaluated once per distinct sub-pattern: the counters above stay those of full-width vectors
+        stats.update({k: rep[k] for k in ("table_rows", "table_reads", "repeat_clades")})
+        return stats
+
+    def repeatStats(self):
+        """Repeated sub-patterns (include/beagle_mi355.h beagleMi355RepeatStats): the first three since the last kernelTimer call."""
+        out = (C.c_long * 10)()
+        self._check("repeatStats", self._ext("beagleMi355RepeatStats", [C.c_int, C.POINTER(C.c_long)])(self.instance, out))
+        keys = ("table_rows", "table_reads", "repeat_clades", "table_bytes", "clades_indexed", "index_host_us", "two_table_nodes",
+                "tables_under_definitions", "index_host_bytes", "index_resets")
         return {k: int(out[i]) for i, k in enumerate(keys)}
 
     def walkHealth(self):

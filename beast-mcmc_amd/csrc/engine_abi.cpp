@@ -238,6 +238,11 @@ int beagleSetTipStates(int instance, int tipIndex, const int* inStates) {
         const uint8_t v = (inStates[p] >= 0 && inStates[p] < in->S) ? (uint8_t)inStates[p] : (uint8_t)in->S;
         s[p] = v; s[in->statePairOff + in->pairPos[p]] = v;
     }
+    if (in->repeatsOn) {                               // the class indices are built from the states (engine_walk.cpp prepareRepeats)
+        repeatsForget(in);
+        in->hostTips[(size_t)tipIndex].assign(s.begin(), s.begin() + in->P);
+        in->repeatIndex.setTip(tipIndex, in->hostTips[(size_t)tipIndex].data());
+    }
     return upload(in, in->tipStates[tipIndex], s.data(), s.size());
 }
 

@@ -225,6 +225,25 @@ int beagleCreateInstance(int tipCount, int partialsBufferCount, int compactBuffe
         if (switchOn("BEAGLE_MI355_NO_MEM_DEFS") || !in->walk || in->walkT || !virtualOn || in->holdSlots < 2) memSteps = 0;
         in->planner.memStepCap = memSteps;
     }
+    // Repeated sub-patterns (engine_internal.h repeatsOn): where a node's vector is long enough for the arithmetic to be what an
+    // evaluation costs — the gate of the memory definitions —; BEAGLE_MI355_REPEATS_ANY_SIZE=1: on any 4-state walk instance;
+    // BEAGLE_MI355_NO_REPEATS=1: off;  BEAGLE_MI355_REPEAT_MAX_FRAC=1/n (or a decimal fraction): most classes a clade may have, of the pattern count
+    {
+        double frac = 1.0 / 8.0;
+        if (const char* f = getenv("BEAGLE_MI355_REPEAT_MAX_FRAC")) {
+            const char* slash = strchr(f, '/');
+            const double num = atof(f), den = slash ? atof(slash + 1) : 1.0;
+            if (num > 0.0 && den > 0.0) frac = num > 1.0 && !slash ? 1.0 / num : num / den;
+        }
+        frac = std::min(frac, 0.5);
+        in->repeatsOn = in->walk && !in->walkT && virtualOn && stateCount == 4 && in->holdSlots >= 2 && !switchOn("BEAGLE_MI355_NO_REPEATS") &&
+                        (bufferBytes >= ((size_t)2 << 20) || switchOn("BEAGLE_MI355_REPEATS_ANY_SIZE"));
+        in->repeatMaxClasses = std::max(1, (int)((double)patternCount * frac));
+        if (in->repeatsOn) { in->repeatIndex.init(tipCount, patternCount, in->repeatMaxClasses); in->hostTips.assign((size_t)tipCount, std::vector<uint8_t>()); }
+        // BEAGLE_MI355_REPEAT_CAPACITY=n: the clades the index keeps before everything is dropped (planner.h RepeatIndex::capacity;
+        // default 8 per tip + 1024) — small values make a short chain cross the reset a long one reaches (tests)
+        if (in->repeatsOn && getenv("BEAGLE_MI355_REPEAT_CAPACITY")) in->repeatIndex.setCapacity((size_t)std::max(1, atoi(getenv("BEAGLE_MI355_REPEAT_CAPACITY"))));
+    }
     in->planner.cacheEnabled = !switchOn("BEAGLE_MI355_NO_PLAN_CACHE");
     in->fastWalk = !switchOn("BEAGLE_MI355_NO_FAST_WALK");
     in->strictWaits = !(getenv("BEAGLE_MI355_STRICT_WAITS") && atoi(getenv("BEAGLE_MI355_STRICT_WAITS")) == 0);

@@ -183,6 +183,8 @@ void destroy(Instance* in) {
     if (in->walkFlags) hipFree(in->walkFlags);
     if (in->sliceMant) hipFree(in->sliceMant);
     if (in->sliceExp) hipFree(in->sliceExp);
+    for (auto& b : in->repeatPool) if (b.dev) hipFree(b.dev);
+    if (in->repeatStage) hipHostFree(in->repeatStage);
     for (auto& r : in->resolved) if (r.dProg) hipFree(r.dProg);
     for (int k = 0; k < 2; k++) {
         if (in->exportDev[k]) hipFree(in->exportDev[k]);

@@ -28,6 +28,7 @@
 #include <vector>
 #include <chrono>
 #include <atomic>
+#include <unordered_map>
 #include "../../include/beagle_mi355.h"
 #include "kernels.h"
 #include "planner.h"
@@ -88,6 +89,11 @@ struct Instance {
         std::vector<int> folds;                          // folded reciprocal vectors the program reads (Instance::folds)
         long foldEpoch = -1;                             // scaleWriteEpoch those vectors were last checked against
         long noFoldTag = 0;                              // the plan whose folds left the safe range: resolved with per-node factors
+        // repeated sub-patterns (below): the program was made from `repeats.plan` instead of the planner's own; its last `lower` slices are
+        // the class-table programs, launched in front of the others
+        bool compressed = false; mi355::RepeatPlan repeats; int lowerRange = 0;
+        long tableRows = 0, tableReads = 0, repeatClades = 0, twoTables = 0, unstoredConsumers = 0;
+        bool repeatsMissing = false;                     // a clade of it had no index yet: resolved again once the index is there
     } resolved[8];                                       // (as many as the planner's cache has ways: planner.h CACHE_WAYS)
     // Read mode, 4 states: a node that is not stored is seen by nobody but its parent, and a partial is linear in each child — so
     // the reciprocal scale factors of the unstored nodes below a stored one are applied ONCE, at that node, as one vector: the
@@ -106,6 +112,32 @@ struct Instance {
     bool foldScales = true;
     unsigned long long* foldWorst = nullptr; size_t foldWorstCount = 0;      // device: k_foldReciprocals' range check
     long resolveEpoch = 0;                               // bumped when pattern ranges change
+    // Repeated sub-patterns (planner.h RepeatIndex): in a cached read-mode full evaluation, a clade of compact tips that the
+    // plan evaluates inside its consumer's program (a plain definition) and whose patterns fall into at most repeatMaxClasses classes is
+    // evaluated ONCE PER CLASS — by an ordinary slice of the walk over the class representatives' tip states, stored as rows of a table
+    // arena, in a launch of its own in front of the walk — and its consumer reads the pattern's row (kernels.h WK_TAB).  Every pattern
+    // still goes through the arithmetic it went through, on the same matrices and the same folded reciprocals: bit for bit the
+    // uncompressed program.  One partition, buffers of 2 MiB and more (BEAGLE_MI355_REPEATS_ANY_SIZE=1: any size), BEAGLE_MI355_NO_REPEATS=1: off,
+    // BEAGLE_MI355_REPEAT_MAX_FRAC=<1/n>: the class limit as a fraction of the pattern count.
+    bool repeatsOn = false; int repeatMaxClasses = 0;
+    mi355::RepeatIndex repeatIndex;
+    std::vector<std::vector<uint8_t>> hostTips;          // per tip: the state codes as uploaded (what the index is built from)
+    long tipDataEpoch = 0, repeatEpoch = -1, repeatCompactEpoch = -1;     // setTipStates calls; what the index and the tables were made under
+    struct RepeatTable { int D = 0, arena = 0, row = 0; char* dev = nullptr; size_t bytes = 0, tipStride = 0; std::vector<int> tips; };   // dev: [row vector | tip rows]
+    std::unordered_map<int, RepeatTable> repeatTables;   // by clade
+    // where the tables' row vectors and tip rows live: a few large device blocks handed out front to back (all of it is given up at
+    // once, dropRepeatTables), filled by stream-ordered copies out of a pinned staging buffer — no allocation and no blocking copy per table
+    struct RepeatBlock { char* dev = nullptr; size_t size = 0, used = 0; };
+    std::vector<RepeatBlock> repeatPool;
+    char* repeatStage = nullptr; size_t repeatStageSize = 0, repeatStageUsed = 0;
+    double* repeatArena = nullptr; int repeatArenas = 0; mi355::RepeatRows repeatRows;      // [arenas][C][P][4]; who has which rows
+    std::vector<int> repeatQueue;                        // clades waiting for their index (built where the host waits for a result)
+    long statTableRows = 0, statTableReads = 0, statRepeatClades = 0, statTwoTables = 0, statUnstoredConsumers = 0;      // since the last timer reset
+    size_t repeatTableCap = 0;                           // most tables kept (three times what the last compressed plan took): past it, as when the arena is full
+    bool lastPlanCached = false;                         // the last runPlan ran a cached full-evaluation plan (the result wait behind it is long enough for index work)
+    long statRepeatResets = 0;                           // times the indices were dropped at their capacity, since creation
+    long statRepeatBuildUs = 0;                          // host time spent building indices and tables, since creation
+    bool lowerLaunched = false;                          // the last runPlan launched class-table programs (a launch more for the kernel timer)
     bool fastWalk = true;                                // BEAGLE_MI355_NO_FAST_WALK=1 at creation: k_walk4 only (A/B runs, tests)
     // 4 states: a pre-order operation list is HELD BACK (engine_preorder.cpp): the chain that evaluates gradients wants the
     // edge-derivative sums that follow it, not the pre-order partials, and those sums can be had without writing a single
@@ -394,7 +426,12 @@ inline void clearVirtual(Instance* in, int X) { if (in->virt) in->planner.clearV
 inline bool isCompactTip(const Instance* in, int X) { return in->tipStates[X] && X < in->tipCount; }
 // what buffer X holds changed: compact tip states (on), or something else — in which case it is no uploaded-partials leaf
 // either until setLeaf says so (planner.h leafPartials)
-inline void setCompact(Instance* in, int X, bool on) { in->planner.setCompactTip(X, on); in->planner.setLeafPartials(X, false); }
+void repeatsForget(Instance* in);     // (engine_walk.cpp: the class indices and tables are of the tip states they were built from)
+void repeatsIdle(Instance* in);
+inline void setCompact(Instance* in, int X, bool on) {
+    in->planner.setCompactTip(X, on); in->planner.setLeafPartials(X, false);
+    if (in->repeatsOn && !on && X < in->tipCount && !in->hostTips[(size_t)X].empty()) { in->repeatIndex.setTip(X, nullptr); in->hostTips[(size_t)X].clear(); repeatsForget(in); }
+}
 inline void setLeaf(Instance* in, int X) { if (X < in->tipCount) in->planner.setLeafPartials(X, true); }
 
 // ---- engine_walk.cpp

@@ -118,6 +118,9 @@ int rootEnqueue(Instance* in, int rootIdx, int wIdx, int fIdx, int cumIdx, int p
 // is the last thing in the (in-order) stream, so seeing the number means everything before it has completed.  Polled — a stream
 // synchronisation costs a wake-up per evaluation — for 20 ms, then blocking (a long evaluation, another rank's, or an error).
 int waitResult(Instance* in, unsigned long long seq) {
+    // (class indices a topology move left to build: a step of that work while the device computes — behind a full evaluation, which takes
+    // longer than a pass over the patterns; a partial update's result is not kept waiting)
+    if (!in->repeatQueue.empty() && in->lastPlanCached) repeatsIdle(in);
     volatile unsigned long long* flag = (volatile unsigned long long*)(in->hResult + 8);
     const auto t0 = std::chrono::steady_clock::now();
     unsigned spins = 0;

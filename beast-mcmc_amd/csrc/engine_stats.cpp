@@ -10,6 +10,7 @@ using namespace mi355::eng;
 static void resetWalkCounters(Instance* in) {
     in->statMicroOps = in->statStored = in->statMemReads = in->statTipReads = in->statScaleReads = in->statWalks = in->statScaleWrites = 0;
     in->statFastWalks = in->statFused = 0;
+    in->statTableRows = in->statTableReads = in->statRepeatClades = in->statTwoTables = in->statUnstoredConsumers = 0;
 }
 
 extern "C" {
@@ -140,6 +141,22 @@ int beagleMi355WalkHealth(int instance, long* out4) {
     unsigned served = 0;
     if (in->walkSelfServed) { int rc = download(in, &served, in->walkSelfServed, sizeof(served)); if (rc) return rc; }
     out4[0] = (long)served; out4[1] = (long)(in->walkSpinLimit / 100ull); out4[2] = in->statFoldedVectors; out4[3] = in->statFoldBuilds;
+    return BEAGLE_SUCCESS;
+}
+
+int beagleMi355RepeatStats(int instance, long* out10) {
+    long* out6 = out10;
+    if (mi355::isShardedHandle(instance)) {             // shard 0's
+        return mi355::shardedFirst(instance, [&](int h) { return beagleMi355RepeatStats(h, out10); });
+    }
+    Instance* in = lookup(instance);
+    if (!in || !out6) return BEAGLE_ERROR_UNINITIALIZED_INSTANCE;
+    out10[6] = in->statTwoTables; out10[7] = in->statUnstoredConsumers;
+    out10[8] = (long)in->repeatIndex.bytes(); out10[9] = in->statRepeatResets;
+    size_t bytes = in->repeatArena ? (size_t)in->repeatArenas * in->C * in->P * 32 : 0;
+    for (const auto& b : in->repeatPool) bytes += b.size;
+    out6[0] = in->statTableRows; out6[1] = in->statTableReads; out6[2] = in->statRepeatClades;
+    out6[3] = (long)bytes; out6[4] = in->repeatIndex.builds; out6[5] = in->statRepeatBuildUs;
     return BEAGLE_SUCCESS;
 }
 

@@ -98,6 +98,155 @@ static int refreshFolds(Instance* in, const std::vector<int>& ids, bool* anyBad)
     return 0;
 }
 
+// ---- repeated sub-patterns (Instance::repeatIndex; planner.h RepeatIndex) -------------------------------------------------
+// drop every class table (and, `index`, every class index): tip states changed, or the arena is full of clades no list names any more.
+// Every kept program may point at a table: all are resolved again.
+static void dropRepeatTables(Instance* in, bool index) {
+    // (the pool's blocks are kept and handed out again: whatever overwrites them is a copy on the instance's stream, behind every launch
+    // that reads the old contents.  Kept programs and slots that wait for an index name clades by their old ids: all are resolved again)
+    if (!in->repeatTables.empty() || (index && in->repeatIndex.size())) {
+        in->repeatTables.clear();
+        in->resolveEpoch++;
+        for (Instance::Resolved& r : in->resolved) r.repeatsMissing = false;
+    }
+    for (Instance::RepeatBlock& b : in->repeatPool) b.used = 0;
+    in->repeatRows.reset();
+    if (index) { in->repeatIndex.clear(); in->repeatQueue.clear(); }
+}
+void repeatsForget(Instance* in) { if (in->repeatsOn && (in->repeatIndex.size() || !in->repeatTables.empty())) dropRepeatTables(in, true); }
+
+// the class table of `clade` (its index is built): rows of the arena, the row vector and the representatives' tip states on the device.
+// nullptr: no room (*full), or out of memory
+static Instance::RepeatTable* repeatTableFor(Instance* in, int clade, bool* full) {
+    auto it = in->repeatTables.find(clade);
+    if (it != in->repeatTables.end()) return &it->second;
+    const mi355::RepeatIndex::Clade& c = in->repeatIndex.clade(clade);
+    const int P = in->P, Dpad = (c.D + 127) & ~127;
+    if (Dpad > P || !in->repeatArena) return nullptr;
+    if (in->repeatTableCap && in->repeatTables.size() >= in->repeatTableCap) { *full = true; return nullptr; }
+    Instance::RepeatTable t;
+    const mi355::RepeatRows before = in->repeatRows;
+    if (!in->repeatRows.place(c.D, t.arena, t.row)) { *full = true; return nullptr; }
+    t.D = c.D; t.tips = c.tips; t.tipStride = (size_t)Dpad;
+    const size_t rowBytes = (in->pairLen * sizeof(unsigned) + 255) & ~(size_t)255;
+    t.bytes = rowBytes + t.tips.size() * t.tipStride + 256;
+    t.bytes = (t.bytes + 255) & ~(size_t)255;
+    // device room from the pool, host room in the pinned staging buffer (wrapping it waits for the copies still reading it: the first
+    // evaluation of a large instance at most)
+    const size_t expect = std::max<size_t>(8, in->repeatTableCap / 3);
+    Instance::RepeatBlock* blk = nullptr;
+    for (Instance::RepeatBlock& b : in->repeatPool) if (b.size - b.used >= t.bytes) { blk = &b; break; }
+    if (!blk) {
+        Instance::RepeatBlock b;
+        b.size = std::max(t.bytes, std::min<size_t>((size_t)16 << 20, expect * t.bytes));
+        if (hipMalloc((void**)&b.dev, b.size) != hipSuccess) { in->repeatRows = before; return nullptr; }
+        in->deviceBytes += b.size;
+        in->repeatPool.push_back(b);
+        blk = &in->repeatPool.back();
+    }
+    if (in->repeatStageSize < t.bytes) {
+        (void)hipStreamSynchronize(live(in));
+        if (in->repeatStage) hipHostFree(in->repeatStage);
+        in->repeatStage = nullptr; in->repeatStageSize = 0; in->repeatStageUsed = 0;
+        const size_t want = std::max(t.bytes, std::min<size_t>((size_t)32 << 20, (expect + expect / 4) * t.bytes));
+        if (hipHostMalloc((void**)&in->repeatStage, want, hipHostMallocDefault) != hipSuccess) { in->repeatStage = nullptr; in->repeatRows = before; return nullptr; }
+        in->repeatStageSize = want;
+    }
+    if (in->repeatStageSize - in->repeatStageUsed < t.bytes) { (void)hipStreamSynchronize(live(in)); in->repeatStageUsed = 0; }
+    unsigned char* const h = reinterpret_cast<unsigned char*>(in->repeatStage + in->repeatStageUsed);
+    memset(h, 4, t.bytes);                            // (padding of the tip rows: "missing")
+    unsigned* rows = reinterpret_cast<unsigned*>(h);
+    const size_t base = (size_t)t.arena * in->C * P + (size_t)t.row;
+    for (size_t q = 0; q < in->pairLen; q++) rows[q] = (unsigned)(base * 32);
+    for (int p = 0; p < P; p++) rows[in->pairPos[(size_t)p]] = (unsigned)((base + c.cls[(size_t)p]) * 32);
+    for (size_t k = 0; k < t.tips.size(); k++) {
+        const std::vector<uint8_t>& st = in->hostTips[(size_t)t.tips[k]];
+        unsigned char* dst = h + rowBytes + k * t.tipStride;
+        for (int d = 0; d < c.D; d++) dst[mi355::walkPairIndex((size_t)d)] = st[(size_t)c.rep[(size_t)d]];
+    }
+    t.dev = blk->dev + blk->used;
+    if (hipMemcpyAsync(t.dev, h, t.bytes, hipMemcpyHostToDevice, live(in)) != hipSuccess) { in->repeatRows = before; return nullptr; }
+    blk->used += t.bytes; in->repeatStageUsed += t.bytes;
+    return &in->repeatTables.emplace(clade, std::move(t)).first->second;
+}
+static inline const uint8_t* repeatTipRows(const Instance* in, const Instance::RepeatTable& t, int tip) {
+    const size_t rowBytes = (in->pairLen * sizeof(unsigned) + 255) & ~(size_t)255;
+    for (size_t k = 0; k < t.tips.size(); k++) if (t.tips[k] == tip) return (const uint8_t*)t.dev + rowBytes + k * t.tipStride;
+    return nullptr;
+}
+
+// Which definitions of a cached read-mode plan are evaluated once per class (slot->repeats; slot->compressed says whether any).  The
+// first plan of an instance builds its indices here — the first read-mode evaluation pays for them once —; later a clade the index
+// does not know (a topology move made it) is evaluated as before and queued: repeatsIdle builds it where the host waits for a result.
+static int prepareRepeats(Instance* in, const mi355::Plan& plan, const mi355::FoldMap* fold, Instance::Resolved* slot) {
+    struct Spent { Instance* in; std::chrono::steady_clock::time_point t0;
+                   ~Spent() { in->statRepeatBuildUs += (long)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(); } } spent{in, std::chrono::steady_clock::now()};
+    slot->compressed = false; slot->repeatsMissing = false; slot->tableRows = slot->tableReads = slot->repeatClades = 0; slot->lowerRange = 0;
+    slot->twoTables = slot->unstoredConsumers = 0;
+    // the index forgets nothing clade by clade: at its capacity everything goes (tables and kept programs with it) and this list's clades
+    // are indexed afresh, here — once in thousands of topology moves
+    if (in->repeatIndex.overCapacity()) { dropRepeatTables(in, true); in->statRepeatResets++; }
+    std::vector<mi355::RepeatRun> cand, take;
+    std::vector<int> missing;
+    const bool buildNow = in->repeatTables.empty() && in->repeatQueue.empty();
+    mi355::findRepeatRuns(plan, fold, in->repeatIndex, buildNow, cand, &missing);
+    if (!missing.empty()) {
+        slot->repeatsMissing = true;
+        for (int c : missing) if (std::find(in->repeatQueue.begin(), in->repeatQueue.end(), c) == in->repeatQueue.end()) in->repeatQueue.push_back(c);
+    }
+    if (cand.empty()) return 0;
+    in->repeatTableCap = std::max<size_t>(64, 3 * cand.size());
+    if (!in->repeatArena) {
+        // (row offsets are 32-bit: the arenas together stay below 4 GiB)
+        // twice the rows this plan's tables take (the lists of a chain share their clades; a topology move adds a few), two arenas at least
+        const size_t one = (size_t)in->C * in->P * 32;
+        size_t need = 0;
+        for (const mi355::RepeatRun& r : cand) need += (size_t)((in->repeatIndex.clade(r.clade).D + 127) & ~127);
+        const size_t perArena = std::max<size_t>(128, (size_t)in->P & ~(size_t)127);
+        int arenas = (int)std::min<size_t>(64, std::max<size_t>(2, (2 * need + perArena - 1) / perArena));
+        while (arenas > 1 && (size_t)arenas * one >= ((size_t)1 << 32)) arenas--;
+        if (one >= ((size_t)1 << 32)) return 0;
+        int rc = devAlloc(in, (void**)&in->repeatArena, (size_t)arenas * one + 512); if (rc) return rc;
+        in->repeatArenas = arenas; in->repeatRows.init(arenas, in->P);
+    }
+    for (int attempt = 0; attempt < 2; attempt++) {
+        bool full = false;
+        take.clear();
+        for (const mi355::RepeatRun& r : cand) {
+            if (!repeatTableFor(in, r.clade, &full)) { if (full) break; continue; }
+            take.push_back(r);
+        }
+        if (!full) break;
+        // clades of lists long gone fill the arena: start over, the live ones come back as they are asked for (a plan that does not fit
+        // even then keeps the tables that do)
+        if (attempt == 0) dropRepeatTables(in, false);
+    }
+    if (take.empty()) return 0;
+    mi355::emitRepeatPlan(plan, take, slot->repeats);
+    slot->compressed = true;
+    slot->tableReads = slot->repeats.tableReads; slot->repeatClades = (long)slot->repeats.lower.size();
+    slot->twoTables = slot->repeats.twoTables; slot->unstoredConsumers = slot->repeats.unstoredConsumers;
+    for (const mi355::PlanSeg& sg : slot->repeats.lower) {
+        const Instance::RepeatTable& t = in->repeatTables[sg.partition];
+        slot->tableRows += (long)t.D * sg.progCount;
+        slot->lowerRange = std::max(slot->lowerRange, t.D);
+    }
+    return 0;
+}
+
+// the host is about to wait for a result: a step of the queued index work (one clade node: a pass over the patterns)
+void repeatsIdle(Instance* in) {
+    if (in->repeatQueue.empty()) return;
+    const auto t0 = std::chrono::steady_clock::now();
+    int budget = 1;
+    const int c = in->repeatQueue.back();
+    in->repeatIndex.build(c, &budget);
+    if (in->repeatIndex.clade(c).built) in->repeatQueue.pop_back();
+    if (in->repeatQueue.empty())
+        for (Instance::Resolved& r : in->resolved) if (r.repeatsMissing) { r.tag = 0; r.dProgValid = false; r.repeatsMissing = false; }
+    in->statRepeatBuildUs += (long)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+}
+
 // did this run of a plan write per-node scale buffers?  (folds built from them are stale then)
 static inline bool anyScaleWriteIn(const Instance* in, const Instance::Resolved* slot, bool reuse, long writesAtEntry) {
     return reuse ? slot->scaleWrites > 0 : in->statScaleWrites != writesAtEntry;
@@ -125,6 +274,7 @@ int runPlan(Instance* in, const mi355::Plan& plan, long planTag, hipEvent_t reco
     Instance::Resolved* slot = planTag && !ablate ? &in->resolved[planTag & 7] : nullptr;
     const bool reuse = slot && slot->tag == planTag && slot->epoch == in->resolveEpoch;
     in->lastResolveMiss = !reuse;
+    in->lastPlanCached = planTag != 0;
     std::vector<mi355::WalkOp>& w = slot ? slot->w : in->walkOps;
     std::vector<mi355::WalkSeg> segsLocal;
     std::vector<mi355::WalkSeg>& segs = slot ? slot->segs : segsLocal;
@@ -148,8 +298,12 @@ int runPlan(Instance* in, const mi355::Plan& plan, long planTag, hipEvent_t reco
         if (ticket) std::stable_partition(order.begin(), order.end(), [&](int s) { return plan.segs[(size_t)s].depCount == 0; });
     }
     int maxRange = 0;
+    // the plan the device program is made from: the planner's, or the one with its repeated clades taken from class tables (prepareRepeats)
+    const mi355::Plan* use = &plan;
     if (reuse) {
         maxRange = slot->maxRange;
+        if (slot->compressed) use = &slot->repeats.plan;
+        in->statTableRows += slot->tableRows; in->statTableReads += slot->tableReads; in->statRepeatClades += slot->repeatClades; in->statTwoTables += slot->twoTables; in->statUnstoredConsumers += slot->unstoredConsumers;
         in->statMemReads += slot->memReads; in->statTipReads += slot->tipReads; in->statScaleReads += slot->scaleReads;
         in->statScaleWrites += slot->scaleWrites; in->statStored += slot->stored; in->statFused += slot->fused;
     } else {
@@ -166,6 +320,19 @@ int runPlan(Instance* in, const mi355::Plan& plan, long planTag, hipEvent_t reco
     bool anyWrite = false;
     for (const mi355::MicroOp& q : plan.prog) if (q.smode == mi355::PS_WRITE) { anyWrite = true; break; }
     const bool noWrites = asmLoop && in->walk && !anyWrite;
+    if (slot) slot->compressed = false;
+    if (slot && in->repeatsOn && in->walk && !in->walkT && in->partitionCount == 1 && !anyWrite && in->planner.stepLimit == 0 && !plan.runs.empty() &&
+        (in->fastWalk || in->C <= 8)) {                // (k_walk4's table variant: up to eight categories, kernels_walk4.hip)
+        int rcr = prepareRepeats(in, plan, fold ? &foldMap : nullptr, slot); if (rcr) return rcr;
+        if (slot->compressed) {
+            use = &slot->repeats.plan;
+            in->statTableRows += slot->tableRows; in->statTableReads += slot->tableReads; in->statRepeatClades += slot->repeatClades; in->statTwoTables += slot->twoTables; in->statUnstoredConsumers += slot->unstoredConsumers;
+        }
+    }
+    const mi355::Plan& U = *use;
+    const bool compressed = slot && slot->compressed;
+    const size_t nUp = U.segs.size(), nLow = compressed ? slot->repeats.lower.size() : 0;
+    auto org = [&](int i) { return compressed ? slot->repeats.origin[(size_t)i] : i; };      // the planner's micro-operation (foldMap's index)
     // write-mode programs: every slice leaves the product of its factors behind (Instance::lastSums); the vectors are named by the last no-op
     // behind the slice's program.  They are the instance's, so growing them invalidates what other kept programs point at.
     const bool sums = anyWrite && in->walk && !in->walkT && in->sliceSums && in->partitionCount == 1;
@@ -191,10 +358,10 @@ int runPlan(Instance* in, const mi355::Plan& plan, long planTag, hipEvent_t reco
     const unsigned skipLoads = noWrites && in->skipTipLoads ? (mi355::WF_NOLOAD1 | mi355::WF_NOLOAD2) : 0u;
     struct FusedAt { size_t at; int matA, matB; };
     std::vector<FusedAt> fusedAt;
-    auto paysFactors = [&](int j) { return fold ? foldMap.payStart[(size_t)j + 1] > foldMap.payStart[(size_t)j] : plan.prog[(size_t)j].smode == mi355::PS_READ; };
+    auto paysFactors = [&](int j) { return fold ? foldMap.payStart[(size_t)org(j) + 1] > foldMap.payStart[(size_t)org(j)] : U.prog[(size_t)j].smode == mi355::PS_READ; };
     w.clear();
-    w.reserve(n + 6 * plan.segs.size());
-    segs.assign(plan.segs.size(), mi355::WalkSeg());
+    w.reserve(U.prog.size() + 6 * (nUp + nLow));
+    segs.assign(nUp + nLow, mi355::WalkSeg());
     devDeps.clear();
     std::vector<int> posOf(plan.segs.size(), -1);
     const size_t matStride = (size_t)in->C * in->S * in->S;
@@ -214,12 +381,16 @@ int runPlan(Instance* in, const mi355::Plan& plan, long planTag, hipEvent_t reco
     nop.m1 = in->matrices; nop.m2 = in->matrices;
     nop.src1 = in->dummyTips; nop.src2 = in->dummyTips; nop.scale = in->onesScale;
     nop.flags = (unsigned)((mi355::WK_TIPS << 5) | (mi355::WK_TIPS << 8)) | skipLoads;         // loads nothing, stores nothing
-    for (size_t oi = 0; oi < plan.segs.size(); oi++) {
+    for (size_t oi = 0; oi < nUp + nLow; oi++) {
         const size_t si = oi;                                   // position in the device program
-        const mi355::PlanSeg& ps = plan.segs[fused ? (size_t)order[oi] : oi];
-        posOf[fused ? (size_t)order[oi] : oi] = (int)oi;
+        const bool low = oi >= nUp;                             // a class-table program (behind the slices of the walk proper)
+        const mi355::PlanSeg& ps = low ? slot->repeats.lower[oi - nUp] : U.segs[fused ? (size_t)order[oi] : oi];
+        const Instance::RepeatTable* tab = low ? &in->repeatTables.find(ps.partition)->second : nullptr;      // (PlanSeg::partition of a lower slice: its clade)
+        if (!low) posOf[fused ? (size_t)order[oi] : oi] = (int)oi;
+        // where a compact tip's states are read: the instance's array, or for a class-table program the representatives' rows
+        auto tipSrc = [&](int buf) -> const uint8_t* { return low ? repeatTipRows(in, *tab, buf) : in->tipStates[buf] ? in->tipStates[buf] + tipOff : nullptr; };
         segs[si].depStart = (int)devDeps.size();
-        if (fused) for (int d = ps.depStart; d < ps.depStart + ps.depCount; d++) {
+        if (fused && !low) for (int d = ps.depStart; d < ps.depStart + ps.depCount; d++) {
             if (posOf[plan.deps[d]] < 0) return BEAGLE_ERROR_GENERAL;      // (a slice behind one that waits for it: the planner's order forbids it)
             devDeps.push_back(posOf[plan.deps[d]]);
         }
@@ -227,7 +398,7 @@ int runPlan(Instance* in, const mi355::Plan& plan, long planTag, hipEvent_t reco
         segs[si].progStart = (int)w.size();
         int lastStore = -1, lastHold = 0, cherry = -1;    // what the micro-operation emitted last stores / parks (1 + slot); a cherry waiting to be fused into the next one
         for (int i = ps.progStart; i < ps.progStart + ps.progCount; i++) {
-            mi355::MicroOp m = plan.prog[i];
+            mi355::MicroOp m = U.prog[i];
             // A cherry that is consumed at once is fused into its consumer (kernels.h WK_CHERRY): tip x tip, not stored, not parked, pays no
             // factors; the next micro-operation of the slice takes it as its second operand (ACC), multiplies by no reciprocals itself (the
             // descriptor's scale field carries the cherry's second tip) and would not come to sit right behind the micro-operation that
@@ -235,9 +406,9 @@ int runPlan(Instance* in, const mi355::Plan& plan, long planTag, hipEvent_t reco
             // stage before — in front of that stage's store and hold-slot write: with the cherry's own stage between them that was safe).
             if (fuseOk && i + 1 < ps.progStart + ps.progCount && m.k1 == mi355::PK_TIPS && m.k2 == mi355::PK_TIPS && m.storeBuf < 0 && m.hold == 0 &&
                 !paysFactors(i) && in->tipStates[m.a1] && in->tipStates[m.a2]) {
-                const mi355::MicroOp& nx = plan.prog[(size_t)i + 1];
+                const mi355::MicroOp& nx = U.prog[(size_t)i + 1];
                 if (nx.k2 == mi355::PK_ACC && !paysFactors(i + 1) && !(nx.k1 == mi355::PK_MEM && lastStore == nx.a1) &&
-                    !(nx.k1 >= mi355::PK_H0 && lastHold == nx.k1 - mi355::PK_H0 + 1)) { cherry = i; continue; }
+                    !(mi355::isHoldKind(nx.k1) && lastHold == nx.k1 - mi355::PK_H0 + 1)) { cherry = i; continue; }
             }
             // The kernels request a first child's partials one stage early — before the previous micro-operation's store
             // is issued (kernels_walk4.hip WALK_STAGE).  The planner never emits that sequence (tests/native/plan_check.cpp
@@ -246,13 +417,26 @@ int runPlan(Instance* in, const mi355::Plan& plan, long planTag, hipEvent_t reco
                 if (m.k2 == mi355::PK_ACC) { m.k2 = mi355::PK_MEM; m.a2 = m.a1; }      // the no-op overwrites ACC; the value is in memory as well
                 w.push_back(nop);
             }
+            // (k_walk4 reads a first child from a class table one stage early, like a hold slot: not in front of a program's first stage)
+            if (!asmLoop && (int)w.size() == segs[si].progStart && m.k1 == mi355::PK_TAB) w.push_back(nop);
             mi355::WalkOp d;
             memset(&d, 0, sizeof(d));
             d.src1 = in->dummyTips; d.src2 = in->dummyTips; d.scale = in->onesScale;     // unused operands stay readable (kernels.h launchWalk4Fast)
+            // (the counters are of full-width vectors: a class-table program's reads and stores are statTableRows)
             if (m.k1 == mi355::PK_MEM) { d.src1 = in->partials[m.a1]; if (!d.src1 || isCompactTip(in, m.a1)) return BEAGLE_ERROR_OUT_OF_RANGE; in->statMemReads++; }
-            else if (m.k1 == mi355::PK_TIPS) { if (!in->tipStates[m.a1]) return BEAGLE_ERROR_OUT_OF_RANGE; d.src1 = in->tipStates[m.a1] + tipOff; in->statTipReads++; }
+            else if (m.k1 == mi355::PK_TIPS) { d.src1 = tipSrc(m.a1); if (!d.src1) return BEAGLE_ERROR_OUT_OF_RANGE; if (!low) in->statTipReads++; }
             if (m.k2 == mi355::PK_MEM) { d.src2 = in->partials[m.a2]; if (!d.src2 || isCompactTip(in, m.a2)) return BEAGLE_ERROR_OUT_OF_RANGE; in->statMemReads++; }
-            else if (m.k2 == mi355::PK_TIPS) { if (!in->tipStates[m.a2]) return BEAGLE_ERROR_OUT_OF_RANGE; d.src2 = in->tipStates[m.a2] + tipOff; in->statTipReads++; }
+            else if (m.k2 == mi355::PK_TIPS) { d.src2 = tipSrc(m.a2); if (!d.src2) return BEAGLE_ERROR_OUT_OF_RANGE; if (!low) in->statTipReads++; }
+            // a child from a class table (kernels.h WK_TAB): its row vector, and the arena where a write-mode operation has its scale buffer
+            if (m.k1 == mi355::PK_TAB || m.k2 == mi355::PK_TAB) {
+                for (int which = 0; which < 2; which++) {
+                    if ((which ? m.k2 : m.k1) != mi355::PK_TAB) continue;
+                    const auto t = in->repeatTables.find(which ? m.a2 : m.a1);
+                    if (t == in->repeatTables.end()) return BEAGLE_ERROR_GENERAL;
+                    (which ? d.src2 : d.src1) = t->second.dev;
+                }
+                d.scaleW = in->repeatArena;
+            }
             if (m.smode != mi355::PS_NONE) {
                 int rc = ensureScale(in, m.scaleIdx); if (rc) return rc;
                 if (m.smode == mi355::PS_WRITE) { if (in->walkT && !in->walkTWrite) return BEAGLE_ERROR_GENERAL; in->scaleIsRaw[m.scaleIdx] = 1; in->statScaleWrites++; d.scaleW = in->scale[m.scaleIdx];
@@ -267,7 +451,7 @@ int runPlan(Instance* in, const mi355::Plan& plan, long planTag, hipEvent_t reco
             }
             int smodeNow = m.smode;
             if (fold) {                            // multiply by what the planner says this result pays for — nothing, one buffer's reciprocals, a fold
-                const int b0 = foldMap.payStart[(size_t)i], b1 = foldMap.payStart[(size_t)i + 1];
+                const int b0 = foldMap.payStart[(size_t)org(i)], b1 = foldMap.payStart[(size_t)org(i) + 1];
                 smodeNow = b1 > b0 ? mi355::PS_READ : mi355::PS_NONE;
                 if (b1 - b0 == 1) d.scale = in->scale[foldMap.members[(size_t)b0]] + (in->walkT ? 0 : in->scaleStride);
                 else if (b1 > b0) {
@@ -284,17 +468,22 @@ int runPlan(Instance* in, const mi355::Plan& plan, long planTag, hipEvent_t reco
                 d.store = in->partials[m.storeBuf];
                 in->statStored++;
             }
+            const bool tableStore = low && i == ps.progStart + ps.progCount - 1;      // a class-table program's result: rows of the arena
+            if (tableStore) d.store = in->repeatArena + (size_t)tab->arena * in->C * in->P * 4;
             d.m1 = in->matrices + (size_t)gatherFrom(m.mat1) * matStride; d.m2 = in->matrices + (size_t)gatherFrom(m.mat2) * matStride;
             int k2 = m.k2;
             if (cherry >= 0) {
-                const mi355::MicroOp& c = plan.prog[(size_t)cherry];
-                d.src2 = in->tipStates[c.a1] + tipOff; d.scale = (const double*)(in->tipStates[c.a2] + tipOff);
+                const mi355::MicroOp& c = U.prog[(size_t)cherry];
+                d.src2 = tipSrc(c.a1); d.scale = (const double*)tipSrc(c.a2);
+                if (!d.src2 || !d.scale) return BEAGLE_ERROR_OUT_OF_RANGE;
                 k2 = mi355::WK_CHERRY;
                 fusedAt.push_back(FusedAt{w.size(), gatherFrom(c.mat1), gatherFrom(c.mat2)});
-                in->statTipReads += 2;
+                if (!low) in->statTipReads += 2;
                 cherry = -1;
             }
-            d.flags = mi355::walkFlags(m.k1, k2, m.hold, smodeNow, m.storeBuf >= 0);
+            d.flags = mi355::walkFlags(m.k1, k2, m.hold, smodeNow, m.storeBuf >= 0 || tableStore);
+            if (asmLoop && m.k1 == mi355::PK_TAB) d.flags |= mi355::WF_X | mi355::WF_TAB1;
+            if (asmLoop && k2 == mi355::PK_TAB) d.flags |= mi355::WF_MEM2 | mi355::WF_TAB2;
             if (m.k1 != mi355::PK_TIPS) d.flags |= skipLoads & mi355::WF_NOLOAD1;
             if (k2 != mi355::PK_TIPS) d.flags |= skipLoads & mi355::WF_NOLOAD2;
             if (ablate) {       // TIMING EXPERIMENTS ONLY (wrong results): 1 no stores, 2 no partials loads, 4 no scale traffic, 8 no tip traffic
@@ -362,11 +551,12 @@ int runPlan(Instance* in, const mi355::Plan& plan, long planTag, hipEvent_t reco
             const int nWait = (w[i].flags & mi355::WF_X) ? fetchLoads(i + 2) : fetchLoads(i + 1) + fetchLoads(i + 2) + x1;
             w[i].flags |= mi355::walkWaitCode(nWait);
         }
+        if (low) { segs[si].pStart = tab->row; segs[si].pEnd = tab->row + tab->D; segs[si].tStart = 0; segs[si].next = -1; continue; }
         segs[si].pStart = in->partStart[ps.partition]; segs[si].pEnd = in->partEnd[ps.partition]; segs[si].tStart = in->padStart[ps.partition];
         maxRange = std::max(maxRange, segs[si].pEnd - segs[si].pStart);
     }
-    for (size_t oi = 0; oi < plan.segs.size(); oi++) {          // (kernels.h WalkSeg::next: rows of THIS array)
-        const mi355::PlanSeg& ps = plan.segs[fused ? (size_t)order[oi] : oi];
+    for (size_t oi = 0; oi < nUp; oi++) {          // (kernels.h WalkSeg::next: rows of THIS array)
+        const mi355::PlanSeg& ps = U.segs[fused ? (size_t)order[oi] : oi];
         segs[oi].next = ticket && ps.next >= 0 ? posOf[(size_t)ps.next] : -1;
     }
     if (slot) slot->leaves = ticket ? plan.leaves : 0;
@@ -408,7 +598,10 @@ int runPlan(Instance* in, const mi355::Plan& plan, long planTag, hipEvent_t reco
         }
         in->statFoldedVectors = (long)slot->folds.size();
     }
-    in->statMicroOps += (long)n;
+    // (from here on: UP = the plan the device program was made from; its slices come first in `segs`, the class-table programs behind them)
+    const mi355::Plan& UP = *use;
+    const size_t upN = UP.segs.size(), lowN = slot && slot->compressed ? slot->repeats.lower.size() : 0;
+    { long upperOps = 0; for (const mi355::PlanSeg& sg : UP.segs) upperOps += sg.progCount; in->statMicroOps += upperOps; }
     ph1 = PhaseClock::now();
     // pack: [micro-ops (64 B each) | segments (32 B each) | dependency lists | snapshot pairs] — ONE host-to-device copy
     const size_t opBytes = w.size() * sizeof(mi355::WalkOp), segBytes = segs.size() * sizeof(mi355::WalkSeg) + ((devDeps.size() * sizeof(int) + 31) & ~(size_t)31);
@@ -515,9 +708,9 @@ int runPlan(Instance* in, const mi355::Plan& plan, long planTag, hipEvent_t reco
     else mi355::launchGatherMatrices(live(in), (const mi355::WalkOp*)dBase, (int)w.size(), in->C, in->matStream,
                                      cmBytes ? (const double* const*)(dBase + cmOff) : nullptr);
     if (labEnv("BEAGLE_MI355_DUMP_PLAN")) {           // development (LAB builds): the slices of this program, wave by wave
-        fprintf(stderr, "[mi355] plan: %zu micro-ops in %zu slices:", n, segs.size());
-        for (size_t i = 0; i < segs.size(); i++) {
-            const mi355::PlanSeg& ps = plan.segs[fused ? (size_t)order[i] : i];
+        fprintf(stderr, "[mi355] plan: %zu micro-ops in %zu slices (+ %zu class-table programs):", n, upN, lowN);
+        for (size_t i = 0; i < upN; i++) {
+            const mi355::PlanSeg& ps = UP.segs[fused ? (size_t)order[i] : i];
             fprintf(stderr, " w%d:%d", ps.wave, segs[i].progCount);
             if (fused) fprintf(stderr, "(t%d d%d)", ps.tail, ps.depCount);
         }
@@ -540,11 +733,23 @@ int runPlan(Instance* in, const mi355::Plan& plan, long planTag, hipEvent_t reco
         fprintf(stderr, "[mi355] program of %zu micro-operations resolved: descriptors and waits %.1f us, upload %.1f us, stream + gather launch %.1f us\n", n, us(ph0, ph1), us(ph1, ph2), us(ph2, ph3));
     }
     if (recordBeforeWalk) HIP_TRY(hipEventRecord(recordBeforeWalk, live(in)));
+    // the class tables of this evaluation: every class-table program in ONE launch in front of the walk — they wait for nothing, and
+    // stream order is all the walk needs to find their rows written
+    in->lowerLaunched = false;
+    if (lowN) {
+        const mi355::WalkSeg* dLow = (const mi355::WalkSeg*)(dBase + opBytes) + upN;
+        if (in->fastWalk)
+            mi355::launchWalk4Fast(live(in), (const mi355::WalkOp*)dBase, dLow, (int)lowN, slot->lowerRange, in->matStream, in->P, in->C, (long)in->scaleStride,
+                                   nullptr, nullptr, 0, 0, nullptr, 0, nullptr, nullptr, 0, false, cmBytes ? (unsigned)(w.size() * (size_t)in->C * 40 * sizeof(double)) : 0u);
+        else
+            mi355::launchWalk4(live(in), (const mi355::WalkOp*)dBase, dLow, (int)lowN, slot->lowerRange, in->matStream, in->P, in->C, (long)in->scaleStride);
+        in->lowerLaunched = true;
+    }
     if (fused) {
         // ONE launch: slice y of the device program is dispatched before slice y + 1 (x fastest), every slice behind the ones it
         // waits for; a workgroup signals flags[y][x] = epoch when its stores are out, its dependants poll for exactly that value
         int range = 0;
-        for (size_t i = 0; i < segs.size(); i++) range = std::max(range, segs[i].pEnd - segs[i].pStart);
+        for (size_t i = 0; i < upN; i++) range = std::max(range, segs[i].pEnd - segs[i].pStart);
         const int flagStride = (in->P + 127) / 128 + 1;
         const size_t flagBytes = segs.size() * (size_t)flagStride * sizeof(unsigned);
         if (in->walkFlagBytes < flagBytes) {
@@ -561,7 +766,7 @@ int runPlan(Instance* in, const mi355::Plan& plan, long planTag, hipEvent_t reco
         Instance::PendingWalk& pw = in->pendingWalk;
         if (pw.valid) { int rcf = flushWalk(in); if (rcf) return rcf; }            // (cannot happen: every path here went through live())
         pw.prog = (const mi355::WalkOp*)dBase; pw.segs = (const mi355::WalkSeg*)(dBase + opBytes); pw.deps = (const int*)(dBase + depOff);
-        pw.nSegs = (int)segs.size(); pw.range = range; pw.flagStride = flagStride; pw.epoch = in->walkEpoch;
+        pw.nSegs = (int)upN; pw.range = range; pw.flagStride = flagStride; pw.epoch = in->walkEpoch;
         pw.leaves = slot && reuse ? slot->leaves : (ticket ? plan.leaves : 0);
         pw.cherryOff = cmBytes ? (unsigned)(w.size() * (size_t)in->C * 40 * sizeof(double)) : 0u;
         in->statFastWalks++; in->statWalks++;
@@ -573,7 +778,7 @@ int runPlan(Instance* in, const mi355::Plan& plan, long planTag, hipEvent_t reco
         if (!(slot && reuse)) {
             std::vector<char> feeds(segs.size(), 0);
             for (int d : devDeps) feeds[(size_t)d] = 1;
-            for (size_t i = 0; i < segs.size(); i++) if (!feeds[i] && segs[i].progCount > 0) sinks++;
+            for (size_t i = 0; i < upN; i++) if (!feeds[i] && segs[i].progCount > 0) sinks++;
             if (slot) slot->sinks = sinks;
         }
         // (a partitioned instance, round 6: up to eight partitions in the list, every one ending in ONE slice — the by-partition root call
@@ -581,14 +786,14 @@ int runPlan(Instance* in, const mi355::Plan& plan, long planTag, hipEvent_t reco
         const bool holdParts = in->partitionCount > 1 && sinks >= 1 && sinks <= mi355::ROOT_MAX_PARTS && in->fuseRootParts;
         const bool hold = in->deferWalk && in->fuseLaunches && !recordBeforeWalk && ((in->partitionCount == 1 && range == in->P && sinks == 1) || holdParts);
         if (hold) {
-            pw.finalStore.assign(segs.size(), -1);
-            pw.finalPart.assign(segs.size(), 0);
+            pw.finalStore.assign(upN, -1);
+            pw.finalPart.assign(upN, 0);
             pw.sinkRows.clear();
             std::vector<char> feeds(segs.size(), 0);
             for (int d : devDeps) feeds[(size_t)d] = 1;         // (the slot's own list: what it held when the program was resolved)
-            for (size_t i = 0; i < segs.size(); i++) {
-                const mi355::PlanSeg& ps = plan.segs[(size_t)order[i]];
-                if (ps.progCount > 0) pw.finalStore[i] = plan.prog[(size_t)ps.progStart + ps.progCount - 1].storeBuf;
+            for (size_t i = 0; i < upN; i++) {
+                const mi355::PlanSeg& ps = UP.segs[(size_t)order[i]];
+                if (ps.progCount > 0) pw.finalStore[i] = UP.prog[(size_t)ps.progStart + ps.progCount - 1].storeBuf;
                 pw.finalPart[i] = ps.partition;
                 if (!feeds[i] && ps.progCount > 0) pw.sinkRows.push_back((int)i);
             }
@@ -600,9 +805,9 @@ int runPlan(Instance* in, const mi355::Plan& plan, long planTag, hipEvent_t reco
         return flushWalk(in);
     }
     // one launch per wave of independent slices (a single one unless the planner cut the forest for a small shard)
-    for (size_t b = 0; b < segs.size();) {
+    for (size_t b = 0; b < upN;) {
         size_t e = b + 1;
-        while (e < segs.size() && plan.segs[e].wave == plan.segs[b].wave) e++;
+        while (e < upN && UP.segs[e].wave == UP.segs[b].wave) e++;
         int range = 0;
         const bool fast = in->fastWalk;                 // the assembly loop (BEAGLE_MI355_NO_FAST_WALK=1: the C++ reference kernel)
         for (size_t i = b; i < e; i++) range = std::max(range, segs[i].pEnd - segs[i].pStart);
@@ -616,7 +821,7 @@ int runPlan(Instance* in, const mi355::Plan& plan, long planTag, hipEvent_t reco
             in->statFastWalks++;
         } else
             mi355::launchWalk4(live(in), (const mi355::WalkOp*)dBase, (const mi355::WalkSeg*)(dBase + opBytes) + b, (int)(e - b), range,
-                               in->matStream, in->P, in->C, (long)in->scaleStride);
+                               in->matStream, in->P, in->C, (long)in->scaleStride, lowN > 0);
         in->statWalks++;
         b = e;
     }
@@ -773,7 +978,7 @@ int runOperationsWalk(Instance* in, const int* ops, int count, int tuple, int gl
                 a = in->events[in->eventsUsed].first; b = in->events[in->eventsUsed].second; in->eventsUsed++;
             }
             int rc = runPlan(in, *in->planner.planned, in->planner.plannedTag, a); if (rc) return rc;
-            if (b) { HIP_TRY(hipEventRecord(b, live(in))); in->pendingLaunches++; }
+            if (b) { HIP_TRY(hipEventRecord(b, live(in))); in->pendingLaunches += in->lowerLaunched ? 2 : 1; }
             const double usRun = usSince(t1);
             in->hostRunUs += usRun; in->hostRunHitUs += usRun;
             if (in->hostTrace && usPlan + usRun > 40.0)
@@ -827,7 +1032,7 @@ int runOperationsWalk(Instance* in, const int* ops, int count, int tuple, int gl
         // snapshot copies are outside: the events time the pruning kernel, which is what the roofline is about)
         if (!in->planner.planned->prog.empty()) {
             rc = runPlan(in, *in->planner.planned, in->planner.plannedTag, launches == 0 ? e0 : nullptr); if (rc) return rc;
-            launches++;
+            launches += in->lowerLaunched ? 2 : 1;
         } else { rc = runPlan(in, *in->planner.planned, in->planner.plannedTag); if (rc) return rc; }
         { const double us = usSince(t1); in->hostRunUs += us; if (hit) in->hostRunHitUs += us;
           if (in->hostTrace && usPlanThis + us > 40.0)

@@ -64,7 +64,14 @@ bool grantDynamicLds(const void* kernel, size_t bytes);
 // the previous micro-operation's result (WK_ACC, second operand only) or one of two hold slots (WK_H0/WK_H1, first
 // operand only; `hold` = 1 + slot: the result of THIS micro-operation is also parked there).  The product commutes
 // bitwise, so the planner is free to order the two children that way; a child in memory comes first.
-enum { WK_MEM = 0, WK_TIPS = 1, WK_ACC = 2, WK_H0 = 3, WK_H1 = 4, WK_H2 = 5, WK_CHERRY = 6 };
+enum { WK_MEM = 0, WK_TIPS = 1, WK_ACC = 2, WK_H0 = 3, WK_H1 = 4, WK_H2 = 5, WK_CHERRY = 6, WK_TAB = 7 };
+// WK_TAB (first or second operand; 4 states): the child is a clade whose value an earlier launch evaluated once per distinct sub-pattern
+// (planner.h RepeatIndex, engine_walk.cpp).  src1 / src2 = the clade's ROW VECTOR: per pattern, pair-interleaved like the tip states, the
+// byte offset (uint32) of the pattern's class row from the start of the table arena — laid out [C][P][4] like a partials buffer, or
+// several of them back to back —, whose address the descriptor carries in scaleW (such a micro-operation never rescales in write mode).
+// The lane's two rows are read at arena + offset + c P 32: an index load, a wait, the row loads.  k_walk4 does that where it consumes
+// the operand; for the assembly loop the engine adds WF_X | WF_TAB1 (the row loads then count as a first child from memory in the
+// stage waits) or WF_MEM2 | WF_TAB2 (the blocking second-child path).
 // WK_CHERRY (second operand only, k_walk4_fast only; round 6): the child is a node over two compact tips whose own micro-operation the
 // engine has FUSED into this one (engine_walk.cpp runPlan): src2 = the states of its first tip, scale = those of its second (the
 // micro-operation multiplies by no reciprocals: WF_INV and WK_CHERRY exclude each other), the same entry of the matrix stream's cherry
@@ -85,7 +92,7 @@ enum { WF_X = 1, WF_T1 = 2, WF_T2 = 4, WF_INV = 8, WF_STORE = 16, WF_CHERRY2 = 1
 // k_walk4 keeps its wait-table jump there (walkWaitJump) — "the fetch skips the first / second tip-state load" (WF_NOLOAD1 / 2: the
 // child is no compact tip; set in programs that do not rescale in write mode) and the stage's wait as a 4-bit code (walkWaitCode)
 enum : unsigned { WF_HREAD = 1u << 24, WF_HREAD1 = 1u << 25, WF_MEM2 = 1u << 26, WF_HWRITE = 1u << 27, WF_NOLOAD1 = 1u << 16, WF_NOLOAD2 = 1u << 17,
-                  WF_WAIT_SHIFT = 18, WF_HREAD2 = 1u << 31 };
+                  WF_WAIT_SHIFT = 18, WF_HREAD2 = 1u << 31, WF_TAB1 = 1u << 28, WF_TAB2 = 1u << 29 };
 // k_walk4_fast's pipeline is three micro-operations deep: the wait of stage k is "at most N vector-memory instructions outstanding",
 // N = what was issued behind the small loads of k and may stay in flight (engine_walk.cpp runPlan).  A fetch is three loads, four
 // for a micro-operation that multiplies by reciprocal scale factors (WF_INV), six with a fused cherry (WF_CHERRY2: its table half and
@@ -127,7 +134,7 @@ inline unsigned walkFlags(int k1, int k2, int hold, int smode, bool store) {
     if (k2 == WK_TIPS) f |= WF_T2;
     if (smode == WS_READ) f |= WF_INV;
     if (store) f |= WF_STORE;
-    if (k1 >= WK_H0) f |= WF_HREAD | (k1 == WK_H1 ? WF_HREAD1 : 0u) | (k1 == WK_H2 ? WF_HREAD2 : 0u);
+    if (k1 >= WK_H0 && k1 <= WK_H2) f |= WF_HREAD | (k1 == WK_H1 ? WF_HREAD1 : 0u) | (k1 == WK_H2 ? WF_HREAD2 : 0u);
     if (k2 == WK_MEM) f |= WF_MEM2;
     if (k2 == WK_CHERRY) f |= WF_CHERRY2;
     if (hold) f |= WF_HWRITE;
@@ -154,8 +161,9 @@ struct WalkSeg { int progStart, progCount, pStart, pEnd, tStart, depStart, depCo
 // one launch: every 128-pattern group of every segment walks its program; maxRange = max (pEnd - pStart).  A lane owns two
 // patterns, 64 apart; its tip states and reciprocal scale factors are stored pair-interleaved (walkPairIndex).
 // dStream = the matrix stream of the WHOLE device program (launchGatherMatrices), nOps * C * 16 {M1, M2} pairs.
+// tables: the program has class-table operands (kernels.h WK_TAB): the kernel k_walk4Tab, up to eight categories
 void launchWalk4(hipStream_t stream, const WalkOp* dProg, const WalkSeg* dSegs, int nSegs, int maxRange, const void* dStream,
-                 int P, int C, long recipOff);
+                 int P, int C, long recipOff, bool tables = false);
 // cherryMats != nullptr (programs of k_walk4_fast with fused cherries): behind the stream's nOps * C entries a CHERRY region of as many, the
 // tables of cherryMats[2 k], [2 k + 1] (a fused cherry's branch matrices, category 0) at entry k where they are not null
 void launchGatherMatrices(hipStream_t stream, const WalkOp* dProg, int nOps, int C, void* dStream, const double* const* cherryMats = nullptr);

@@ -202,10 +202,30 @@ __device__ __forceinline__ v4d tipColumn(const char* tbl, unsigned s) {
     return v4d{lo.x, lo.y, hi.x, hi.y};
 }
 
+// A WK_TAB operand (kernels.h): the class rows of the lane's two patterns — the offsets from the clade's row vector (uint32 per pattern at
+// the pattern's pair position), then 32 bytes per pattern at arena + offset + c P 32.  Blocking: per pattern index load, wait, row loads;
+// every load issued before has landed by then, so the exact stage waits around it only wait for less.  Branched around inside the
+// block where the operand kind is another (`kind`: the 3-bit field), like the groups of fetchIssue: the registers keep their contents.
+__device__ __forceinline__ void tableRowsIf(unsigned kind, v2d& a0, v2d& a1, v2d& b0, v2d& b1, const LaneOffsets& o, u64 rows, u64 arena, int c, int P) {
+    const u64 base = arena + (u64)((unsigned)c * (unsigned)P * 32u);
+    unsigned i;                                       // (one pattern after the other: one index register)
+    asm volatile("s_cmp_eq_u32 %[kind], 7\n\t"
+                 "s_cbranch_scc0 .Ltr%=\n\t"
+                 "v_lshlrev_b32 %[i], 2, %[tA]\n\tglobal_load_dword %[i], %[i], %[rows]\n\ts_waitcnt vmcnt(0)\n\t"
+                 "global_load_dwordx4 %[a0], %[i], %[base]\n\tglobal_load_dwordx4 %[a1], %[i], %[base] offset:16\n\t"
+                 "v_lshlrev_b32 %[i], 2, %[tB]\n\tglobal_load_dword %[i], %[i], %[rows]\n\ts_waitcnt vmcnt(0)\n\t"
+                 "global_load_dwordx4 %[b0], %[i], %[base]\n\tglobal_load_dwordx4 %[b1], %[i], %[base] offset:16\n\ts_waitcnt vmcnt(0)\n"
+                 ".Ltr%=:"
+                 : [a0] "+v"(a0), [a1] "+v"(a1), [b0] "+v"(b0), [b1] "+v"(b1), [i] "=&v"(i)
+                 : [kind] "s"(kind), [tA] "v"(o.tipA), [tB] "v"(o.tipB), [rows] "s"(rows), [base] "s"(base) : "memory", "scc");
+}
+
 // MAXT = 64 * C threads; MINW = waves per SIMD the register allocation must allow (see the file header)
-template <int MAXT, int MINW>
-__global__ __launch_bounds__(MAXT, MINW) void k_walk4(const unsigned MI355_CONST* __restrict__ prog, const WalkSeg MI355_CONST* __restrict__ segs,
-                                                      const v2d MI355_CONST* __restrict__ matStream, int P, int C, long recipOff) {
+// TAB: the program may read operands from class tables (kernels.h WK_TAB) — the kernel k_walk4Tab below: the loop of k_walk4 sits at
+// exactly the 128 registers that four waves per SIMD leave it, and the table loads need a few more
+template <int MAXT, bool TAB>
+__device__ __forceinline__ void walk4Body(const unsigned MI355_CONST* __restrict__ prog, const WalkSeg MI355_CONST* __restrict__ segs,
+                                          const v2d MI355_CONST* __restrict__ matStream, int P, int C, long recipOff) {
     extern __shared__ v2d lds[];                      // hold[walkHoldSlots(C)][C][4][64] (v2d), exch[C][128] (double), table[2][MAXT / 64][320 B]
     const WalkSeg MI355_CONST& sg = segs[blockIdx.y];
     const int progStart = sg.progStart, progCount = sg.progCount, pStart = sg.pStart, pEnd = sg.pEnd, tStart = sg.tStart;
@@ -252,7 +272,11 @@ __global__ __launch_bounds__(MAXT, MINW) void k_walk4(const unsigned MI355_CONST
         const unsigned fl = DCUR.flags;                                                                                   \
         const u64 dStore = DCUR.store, dScale = DCUR.scaleW, dSrc2 = DCUR.src2;                                            \
         const int k1n = (DNXT.flags >> 5) & 7;         /* a hold-slot operand of the NEXT micro-operation is read now */  \
-        if (k1n >= WK_H0) {                                                                                               \
+        /* ... and operands from a class table (kernels.h WK_TAB; scaleW = the arena): the next one's first child where a hold-slot  \
+           operand would go (a program's FIRST micro-operation has no stage before it: the host puts a no-op in front of one that   \
+           reads a table first, engine_walk.cpp runPlan) */                                                                       \
+        if constexpr (TAB) tableRowsIf((unsigned)k1n, NXT.xa0, NXT.xa1, NXT.xb0, NXT.xb1, o, DNXT.src1, DNXT.scaleW, c, P);     \
+        if (k1n >= WK_H0 && k1n <= WK_H2) {                                                                               \
             const v2d* h = holdBase + (size_t)(k1n - WK_H0) * C * 256;                                                    \
             NXT.xa0 = h[0]; NXT.xa1 = h[64]; NXT.xb0 = h[128]; NXT.xb1 = h[192];                                          \
         }                                                                                                                 \
@@ -268,7 +292,12 @@ __global__ __launch_bounds__(MAXT, MINW) void k_walk4(const unsigned MI355_CONST
                         v4d{CUR.xb0.x, CUR.xb0.y, CUR.xb1.x, CUR.xb1.y}, fa, fb);                                         \
         if (k2 == WK_TIPS) { ga = tipColumn(tb + WALK_TABLE_M2, t2a); gb = tipColumn(tb + WALK_TABLE_M2, t2b); }          \
         else if (k2 == WK_ACC) matvecDpp2(*reinterpret_cast<const double*>(tb + WALK_TABLE_M2 + spOff), ACCa, ACCb, ga, gb);   \
-        else {                                         /* both children in memory (rare): the second one is not prefetched */ \
+        else if (TAB && k2 == WK_TAB) {                /* the second child from a class table: like a second child in memory, below */ \
+            v2d y0 = v2d{1.0, 1.0}, y1 = y0, y2 = y0, y3 = y0;                                                            \
+            tableRowsIf(7u, y0, y1, y2, y3, o, dSrc2, dScale, c, P);                                                      \
+            matvecDpp2(*reinterpret_cast<const double*>(tb + WALK_TABLE_M2 + spOff), v4d{y0.x, y0.y, y1.x, y1.y},         \
+                       v4d{y2.x, y2.y, y3.x, y3.y}, ga, gb);                                                              \
+        } else {                                         /* both children in memory (rare): the second one is not prefetched */ \
             v2d y0, y1, y2, y3;                                                                                           \
             asm volatile("global_load_dwordx4 %0, %4, %6\n\tglobal_load_dwordx4 %1, %4, %6 offset:16\n\t"                \
                          "global_load_dwordx4 %2, %5, %6\n\tglobal_load_dwordx4 %3, %5, %6 offset:16\n\ts_waitcnt vmcnt(0)"   \
@@ -333,6 +362,19 @@ __global__ __launch_bounds__(MAXT, MINW) void k_walk4(const unsigned MI355_CONST
         int MI355_GLOBAL* x = (int MI355_GLOBAL*)expTo;
         m[o.tipA] = pmA; m[o.tipB] = pmB; x[o.tipA] = peA; x[o.tipB] = peB;
     }
+}
+
+template <int MAXT, int MINW>
+__global__ __launch_bounds__(MAXT, MINW) void k_walk4(const unsigned MI355_CONST* __restrict__ prog, const WalkSeg MI355_CONST* __restrict__ segs,
+                                                      const v2d MI355_CONST* __restrict__ matStream, int P, int C, long recipOff) {
+    walk4Body<MAXT, false>(prog, segs, matStream, P, C, recipOff);
+}
+// ... and with class-table operands: two waves per SIMD's worth of registers (up to eight categories: a workgroup of sixteen waves
+// has four per SIMD whatever it asks for, and programs with table operands are not made for it — engine_walk.cpp runPlan)
+template <int MAXT>
+__global__ __launch_bounds__(MAXT, 2) void k_walk4Tab(const unsigned MI355_CONST* __restrict__ prog, const WalkSeg MI355_CONST* __restrict__ segs,
+                                                      const v2d MI355_CONST* __restrict__ matStream, int P, int C, long recipOff) {
+    walk4Body<MAXT, true>(prog, segs, matStream, P, C, recipOff);
 }
 
 // stream[k][c] = the matrix table of micro-operation k, category c (see tipColumn): 2 x 5 columns x 4 doubles, in
@@ -681,8 +723,9 @@ void launchWalk4Fast(hipStream_t stream, const WalkOp* dProg, const WalkSeg* dSe
            hipLaunchKernelGGL((k_walk4_fast<16>), grid, block, lds, stream, prog, segs, ms, P, C, recipOffBytes, deps, flags, epoch, flagStride, spinLimit, selfServed, ra, tickets, xcdGroups, nSegs, cherryOff); }
 }
 
-void launchWalk4(hipStream_t stream, const WalkOp* dProg, const WalkSeg* dSegs, int nSegs, int maxRange, const void* dStream, int P, int C, long recipOff) {
+void launchWalk4(hipStream_t stream, const WalkOp* dProg, const WalkSeg* dSegs, int nSegs, int maxRange, const void* dStream, int P, int C, long recipOff, bool tables) {
     if (nSegs <= 0 || maxRange <= 0) return;
+    if (tables && C > 8) return;                      // (never asked for: see k_walk4Tab)
     const dim3 grid((maxRange + 127) / 128, nSegs), block(64 * C);
     const int maxC = C <= 4 ? 4 : C <= 8 ? 8 : 16;
     const int slots = walkHoldSlots(C);
@@ -690,6 +733,12 @@ void launchWalk4(hipStream_t stream, const WalkOp* dProg, const WalkSeg* dSegs, 
     const unsigned MI355_CONST* prog = (const unsigned MI355_CONST*)dProg;
     const WalkSeg MI355_CONST* segs = (const WalkSeg MI355_CONST*)dSegs;
     const v2d MI355_CONST* ms = (const v2d MI355_CONST*)dStream;
+    if (tables) {
+        if (C <= 4) hipLaunchKernelGGL((k_walk4Tab<256>), grid, block, lds, stream, prog, segs, ms, P, C, recipOff);
+        else { if (!grantDynamicLds(reinterpret_cast<const void*>(k_walk4Tab<512>), lds)) return;
+               hipLaunchKernelGGL((k_walk4Tab<512>), grid, block, lds, stream, prog, segs, ms, P, C, recipOff); }
+        return;
+    }
     if (C <= 4) hipLaunchKernelGGL((k_walk4<256, 4>), grid, block, lds, stream, prog, segs, ms, P, C, recipOff);
     else if (C <= 8) { if (!grantDynamicLds(reinterpret_cast<const void*>(k_walk4<512, 4>), lds)) return;     // > 64 KiB of LDS: opt in per device
                        hipLaunchKernelGGL((k_walk4<512, 4>), grid, block, lds, stream, prog, segs, ms, P, C, recipOff); }

@@ -321,6 +321,12 @@ void WalkPlanner::emitReal(int root, unsigned rootMask, Plan& out) {
     std::vector<Frame> st;
     auto push = [&](int j, int pkey, int pidx, unsigned fm) { Frame f; f.j = j; f.pkey = pkey; f.pidx = pidx; f.freeMask = fm; f.phase = 0; f.first = 0; f.hold = false; f.m = blankOp(); st.push_back(f); };
     auto pushChild = [&](const Child& c, unsigned fm) { if (c.cls == CL_REAL) push(c.prod, -1, -1, fm); else push(-1, c.vkey, c.vstep, fm); };
+    // (a definition evaluated inside this program: Plan::runs)
+    auto emitRun = [&](const Child& c, unsigned fm) {
+        const int s0 = (int)out.prog.size();
+        emitVirtualStep(c.vkey, c.vstep, fm, true, out);
+        out.runs.push_back(PlanRun{s0, (int)out.prog.size() - s0});
+    };
     push(root, -1, -1, rootMask);
     while (!st.empty()) {
         const size_t top = st.size() - 1;                 // (a push invalidates references: every path that pushes `continue`s)
@@ -384,7 +390,7 @@ void WalkPlanner::emitReal(int root, unsigned rootMask, Plan& out) {
                 if (l.cls == CL_MEM) lastMemReads++;
                 f.m.k2 = PK_ACC; f.m.mat2 = e.mat;
                 f.phase = 9;
-                if (e.cls == CL_VIRT) emitVirtualStep(e.vkey, e.vstep, f.freeMask, true, out);
+                if (e.cls == CL_VIRT) emitRun(e, f.freeMask);
                 else { const unsigned fm = f.freeMask; pushChild(e, fm); continue; }
             } else {
                 const int F = popcount2(f.freeMask);
@@ -406,7 +412,7 @@ void WalkPlanner::emitReal(int root, unsigned rootMask, Plan& out) {
                 }
                 f.phase = 1;
                 const Child a = ch[f.first];
-                if (a.cls == CL_VIRT) emitVirtualStep(a.vkey, a.vstep, f.freeMask, true, out);
+                if (a.cls == CL_VIRT) emitRun(a, f.freeMask);
                 else { const unsigned fm = f.freeMask; pushChild(a, fm); continue; }
             }
         }
@@ -427,7 +433,7 @@ void WalkPlanner::emitReal(int root, unsigned rootMask, Plan& out) {
             }
             f.m.k2 = PK_ACC; f.m.mat2 = b.mat;
             f.phase = 9;
-            if (b.cls == CL_VIRT) emitVirtualStep(b.vkey, b.vstep, mask2, true, out);
+            if (b.cls == CL_VIRT) emitRun(b, mask2);
             else { pushChild(b, mask2); continue; }
         }
         {                                                 // phase 9: the node itself
@@ -709,7 +715,7 @@ int WalkPlanner::plan(const int* ops, int count, int tuple, int parts, bool allo
         // a hit; the definitions of unstored destinations are copied, steps in use only, over whatever the way held before)
         fill->plan.clear();
         fill->plan.prog.swap(out.prog); fill->plan.segs.swap(out.segs); fill->plan.deps.swap(out.deps);
-        fill->plan.launchOrder.swap(out.launchOrder); fill->plan.snapPairs.swap(out.snapPairs); fill->plan.leaves = out.leaves;
+        fill->plan.launchOrder.swap(out.launchOrder); fill->plan.snapPairs.swap(out.snapPairs); fill->plan.runs.swap(out.runs); fill->plan.leaves = out.leaves;
         planned = &fill->plan;
         if ((int)fill->defs.size() < count) fill->defs.resize(count);
         fill->defOn.assign(count, 0);
@@ -946,7 +952,7 @@ bool foldScaleFactors(const Plan& plan, int maxMembers, FoldMap& out) {
         for (int i = sg.progStart; i < sg.progStart + sg.progCount; i++) {
             const MicroOp& m = plan.prog[(size_t)i];
             cur.clear();
-            if (m.k1 >= PK_H0) { const std::vector<int>& h = hold[m.k1 - PK_H0]; cur.insert(cur.end(), h.begin(), h.end()); }
+            if (isHoldKind(m.k1)) { const std::vector<int>& h = hold[m.k1 - PK_H0]; cur.insert(cur.end(), h.begin(), h.end()); }
             if (m.k2 == PK_ACC) cur.insert(cur.end(), acc.begin(), acc.end());
             if (m.smode == PS_READ) cur.push_back(m.scaleIdx);
             if (m.storeBuf >= 0 || i == sg.progStart + sg.progCount - 1 || (int)cur.size() >= maxMembers) { pays[(size_t)i] = cur; cur.clear(); }
@@ -960,6 +966,186 @@ bool foldScaleFactors(const Plan& plan, int maxMembers, FoldMap& out) {
     }
     out.payStart[n] = (int)out.members.size();
     return true;
+}
+
+// ---- repeated sub-patterns (planner.h RepeatIndex) ---------------------------------------------------------------------
+void RepeatIndex::init(int tipCount, int patterns, int maxClasses) {
+    tipCount_ = tipCount; P_ = patterns; maxClasses_ = std::max(1, std::min(maxClasses, 65535));      // (classes are kept as 16-bit numbers)
+    tip_.assign((size_t)tipCount, nullptr);
+    capacity_ = (size_t)8 * (size_t)std::max(0, tipCount) + 1024;
+    clear();
+}
+
+void RepeatIndex::clear() { clades_.clear(); memo_.clear(); }
+
+std::size_t RepeatIndex::bytes() const {
+    size_t b = clades_.capacity() * sizeof(Clade) + memo_.size() * 32;
+    for (const Clade& c : clades_) b += c.cls.capacity() * sizeof(std::uint16_t) + (c.rep.capacity() + c.tips.capacity()) * sizeof(int);
+    return b;
+}
+
+int RepeatIndex::find(int a, int b) const {
+    if (a > b) std::swap(a, b);
+    const auto it = memo_.find(((std::uint64_t)(unsigned)a << 32) | (unsigned)b);
+    return it == memo_.end() ? -1 : it->second;
+}
+
+int RepeatIndex::intern(int a, int b) {
+    if (a > b) std::swap(a, b);
+    const std::uint64_t k = ((std::uint64_t)(unsigned)a << 32) | (unsigned)b;
+    const auto it = memo_.find(k);
+    if (it != memo_.end()) return it->second;
+    Clade c; c.a = a; c.b = b;
+    clades_.push_back(c);
+    const int id = tipCount_ + (int)clades_.size() - 1;
+    memo_.emplace(k, id);
+    return id;
+}
+
+bool RepeatIndex::build(int id, int* budget) {
+    if (isTip(id)) return tip_[(size_t)id] != nullptr;
+    // children first, without recursion (a ladder clade is as deep as it has tips)
+    std::vector<int> todo(1, id);
+    while (!todo.empty()) {
+        const int x = todo.back();
+        Clade& c = clades_[(size_t)(x - tipCount_)];
+        if (c.built) { todo.pop_back(); continue; }
+        bool wait = false, none = false;
+        for (int ch : {c.a, c.b}) {
+            if (isTip(ch)) { if (!tip_[(size_t)ch]) none = true; continue; }
+            const Clade& k = clades_[(size_t)(ch - tipCount_)];
+            if (!k.built) { todo.push_back(ch); wait = true; } else if (k.over) none = true;
+        }
+        if (wait) continue;
+        if (budget && (*budget)-- <= 0) return false;
+        todo.pop_back();
+        c.built = true; c.over = none; c.D = 0; c.cls.clear(); c.rep.clear(); c.tips.clear();
+        builds++;
+        if (none) continue;
+        const std::uint8_t* ta = isTip(c.a) ? tip_[(size_t)c.a] : nullptr;
+        const std::uint8_t* tb = isTip(c.b) ? tip_[(size_t)c.b] : nullptr;
+        const Clade* ka = ta ? nullptr : &clades_[(size_t)(c.a - tipCount_)];
+        const Clade* kb = tb ? nullptr : &clades_[(size_t)(c.b - tipCount_)];
+        const std::uint32_t Db = tb ? 5u : (std::uint32_t)kb->D, Da = ta ? 5u : (std::uint32_t)ka->D;
+        const std::uint64_t space = (std::uint64_t)Da * Db;                // (< 2^32: both counts are at most 65 535)
+        c.cls.resize((size_t)P_);
+        const bool direct = space <= ((std::uint64_t)1 << 16);     // (a table of 256 KB at most to clear per clade)
+        std::unordered_map<std::uint32_t, int> sparse;
+        if (direct) table_.assign((size_t)space, -1);
+        bool over = false;
+        for (int p = 0; p < P_; p++) {
+            const std::uint32_t ca = ta ? (ta[p] < 4 ? ta[p] : 4u) : ka->cls[(size_t)p], cb = tb ? (tb[p] < 4 ? tb[p] : 4u) : kb->cls[(size_t)p];
+            const std::uint32_t key = ca * Db + cb;
+            int d;
+            if (direct) { int& slot = table_[key]; if (slot < 0) { slot = c.D++; c.rep.push_back(p); } d = slot; }
+            else { const auto ins = sparse.emplace(key, c.D); if (ins.second) { c.D++; c.rep.push_back(p); } d = ins.first->second; }
+            if (c.D > maxClasses_) { over = true; break; }
+            c.cls[(size_t)p] = (std::uint16_t)d;
+        }
+        if (over) { c.over = true; c.D = 0; std::vector<std::uint16_t>().swap(c.cls); std::vector<int>().swap(c.rep); continue; }
+        for (int ch : {c.a, c.b}) {
+            if (isTip(ch)) c.tips.push_back(ch);
+            else { const Clade& k = clades_[(size_t)(ch - tipCount_)]; c.tips.insert(c.tips.end(), k.tips.begin(), k.tips.end()); }
+        }
+    }
+    const Clade& c = clades_[(size_t)(id - tipCount_)];
+    return c.built && !c.over;
+}
+
+void findRepeatRuns(const Plan& plan, const FoldMap* fold, RepeatIndex& idx, bool build, std::vector<RepeatRun>& out, std::vector<int>* missing) {
+    out.clear();
+    if (plan.runs.empty()) return;
+    for (const MicroOp& m : plan.prog) if (m.smode == PS_WRITE) return;
+    auto pays = [&](int i) { return fold ? fold->payStart[(size_t)i + 1] > fold->payStart[(size_t)i] : plan.prog[(size_t)i].smode == PS_READ; };
+    // the slice of every run (runs are in program order, slices tile the program in any order)
+    auto sliceEnd = [&](int at) { for (const PlanSeg& sg : plan.segs) if (at >= sg.progStart && at < sg.progStart + sg.progCount) return sg.progStart + sg.progCount; return -1; };
+    for (size_t r = 0; r < plan.runs.size(); r++) {
+        const PlanRun& run = plan.runs[r];
+        const int last = run.start + run.count - 1, end = sliceEnd(run.start);
+        if (run.count <= 0 || end < 0 || last >= end) continue;
+        bool ok = true;
+        int acc = -1, hold[3] = {-1, -1, -1};
+        for (int i = run.start; i <= last && ok; i++) {
+            const MicroOp& m = plan.prog[(size_t)i];
+            if (m.storeBuf >= 0 || pays(i)) ok = false;
+            int a, b;
+            if (m.k1 == PK_TIPS) a = m.a1; else if (isHoldKind(m.k1)) a = hold[m.k1 - PK_H0]; else a = -1;
+            if (m.k2 == PK_TIPS) b = m.a2; else if (m.k2 == PK_ACC) b = acc; else b = -1;
+            if (a < 0 || b < 0 || (m.k1 == PK_TIPS && a >= idx.tipCount()) || (m.k2 == PK_TIPS && b >= idx.tipCount())) { ok = false; break; }
+            acc = idx.intern(a, b);
+            if (m.hold && i < last) hold[m.hold - 1] = acc;
+        }
+        if (!ok) continue;
+        RepeatRun rr; rr.run = (int)r; rr.clade = acc; rr.viaHold = plan.prog[(size_t)last].hold != 0; rr.consumer = -1;
+        if (rr.viaHold) {
+            const int k = PK_H0 + plan.prog[(size_t)last].hold - 1;
+            for (int j = last + 1; j < end; j++) if (plan.prog[(size_t)j].k1 == k) { rr.consumer = j; break; }
+        } else if (last + 1 < end && plan.prog[(size_t)last + 1].k2 == PK_ACC) rr.consumer = last + 1;
+        if (rr.consumer < 0) continue;
+        const RepeatIndex::Clade& c = idx.clade(rr.clade);
+        if (!c.built) {
+            if (build) idx.build(rr.clade);
+            else { if (missing) missing->push_back(rr.clade); continue; }
+        }
+        if (idx.clade(rr.clade).over) continue;
+        out.push_back(rr);
+    }
+}
+
+void emitRepeatPlan(const Plan& plan, const std::vector<RepeatRun>& take, RepeatPlan& out) {
+    out.plan.clear(); out.lower.clear(); out.origin.clear(); out.tableReads = 0; out.twoTables = 0; out.unstoredConsumers = 0;
+    const size_t n = plan.prog.size();
+    std::vector<MicroOp> mod(plan.prog);
+    std::vector<char> gone(n, 0);
+    auto sliceStart = [&](int at) { for (const PlanSeg& sg : plan.segs) if (at >= sg.progStart && at < sg.progStart + sg.progCount) return sg.progStart; return 0; };
+    for (const RepeatRun& rr : take) {                   // (in program order: a consumer's first operand is settled before its second)
+        const PlanRun& run = plan.runs[(size_t)rr.run];
+        for (int i = run.start; i < run.start + run.count; i++) gone[(size_t)i] = 1;
+        MicroOp& c = mod[(size_t)rr.consumer];
+        out.tableReads++;
+        if (rr.viaHold) { c.k1 = PK_TAB; c.a1 = rr.clade; continue; }
+        const int prev = run.start - 1;
+        if (c.k1 == PK_TIPS || c.k1 == PK_MEM) {          // the other child is a leaf: the table goes first (the kernels prefetch a first child)
+            const int k = c.k1, a = c.a1, mt = c.mat1;
+            c.k1 = PK_TAB; c.a1 = rr.clade; c.mat1 = c.mat2;
+            c.k2 = k; c.a2 = a; c.mat2 = mt;
+        } else if (isHoldKind(c.k1) && prev >= sliceStart(run.start) && !gone[(size_t)prev] && mod[(size_t)prev].hold == c.k1 - PK_H0 + 1) {
+            // the other child was parked while the run was evaluated; with the run gone it is still in ACC: nothing is parked
+            mod[(size_t)prev].hold = 0;
+            const int mt = c.mat1;
+            c.k1 = PK_TAB; c.a1 = rr.clade; c.mat1 = c.mat2;
+            c.k2 = PK_ACC; c.a2 = 0; c.mat2 = mt;
+        } else { c.k2 = PK_TAB; c.a2 = rr.clade; }
+    }
+    {
+        std::vector<char> counted(n, 0);
+        for (const RepeatRun& rr : take) {
+            if (counted[(size_t)rr.consumer]) continue;
+            counted[(size_t)rr.consumer] = 1;
+            const MicroOp& c = mod[(size_t)rr.consumer];
+            if (c.k1 == PK_TAB && c.k2 == PK_TAB) out.twoTables++;
+            if (c.storeBuf < 0) out.unstoredConsumers++;
+        }
+    }
+    out.plan.segs = plan.segs; out.plan.deps = plan.deps; out.plan.launchOrder = plan.launchOrder; out.plan.snapPairs = plan.snapPairs; out.plan.leaves = plan.leaves;
+    for (PlanSeg& sg : out.plan.segs) {
+        const int s0 = sg.progStart, cnt = sg.progCount;
+        sg.progStart = (int)out.plan.prog.size();
+        for (int i = s0; i < s0 + cnt; i++) if (!gone[(size_t)i]) { out.plan.prog.push_back(mod[(size_t)i]); out.origin.push_back(i); }
+        sg.progCount = (int)out.plan.prog.size() - sg.progStart;
+    }
+    for (const RepeatRun& rr : take) {
+        const PlanRun& run = plan.runs[(size_t)rr.run];
+        PlanSeg sg; sg.progStart = (int)out.plan.prog.size(); sg.progCount = run.count; sg.partition = rr.clade; sg.wave = 0;
+        sg.depStart = 0; sg.depCount = 0; sg.tail = run.count; sg.next = -1;
+        for (int i = run.start; i < run.start + run.count; i++) {
+            MicroOp m = plan.prog[(size_t)i];
+            m.smode = PS_NONE; m.scaleIdx = PLAN_NONE;
+            if (i == run.start + run.count - 1) m.hold = 0;
+            out.plan.prog.push_back(m); out.origin.push_back(i);
+        }
+        out.lower.push_back(sg);
+    }
 }
 
 }  // namespace mi355

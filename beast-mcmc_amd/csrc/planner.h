@@ -16,6 +16,7 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <unordered_map>
 #include <vector>
 
 namespace mi355 {
@@ -24,7 +25,11 @@ constexpr int PLAN_MAX_STEPS = 32;       // capacity of a virtual definition (sn
 constexpr int PLAN_NONE = -1;
 
 // kinds / scale modes: numerically identical to WK_* / WS_* of kernels.h (static_assert in engine_internal.h)
-enum { PK_MEM = 0, PK_TIPS = 1, PK_ACC = 2, PK_H0 = 3, PK_H1 = 4, PK_H2 = 5 };
+enum { PK_MEM = 0, PK_TIPS = 1, PK_ACC = 2, PK_H0 = 3, PK_H1 = 4, PK_H2 = 5, PK_TAB = 7 };
+// PK_TAB (first or second child; only in programs emitRepeatPlan made, below): the child is a clade over compact tips whose value was
+// evaluated once per distinct sub-pattern into a class table; a = the clade (RepeatIndex id).  Not a hold slot: compare kinds against
+// PK_H0 .. PK_H2, not ">= PK_H0".
+inline bool isHoldKind(int k) { return k >= PK_H0 && k <= PK_H2; }
 enum { PS_NONE = 0, PS_READ = 1, PS_WRITE = 2 };
 
 struct MicroOp {
@@ -49,6 +54,9 @@ struct MicroOp {
 // the one that arrives LAST there carries on with that slice itself — everything it reads was stored by workgroups that counted
 // in before it (kernels_walk4.hip: "tickets").
 struct PlanSeg { int progStart, progCount, partition, wave, depStart, depCount, tail, next; };
+// micro-operations [start, start + count) of Plan::prog evaluate ONE definition inside its consumer's program (emitReal): the result of the
+// last of them is in ACC for the micro-operation that follows, or parked in a hold slot for a later one of the same slice
+struct PlanRun { int start, count; };
 
 struct Plan {
     std::vector<MicroOp> prog;
@@ -56,9 +64,10 @@ struct Plan {
     std::vector<int> deps;           // PlanSeg::depStart / depCount
     std::vector<int> launchOrder;    // permutation of segs: descending tail (critical path first), dependencies before dependants
     std::vector<int> snapPairs;      // (source matrix slot, destination snapshot slot) pairs to copy BEFORE the program runs
+    std::vector<PlanRun> runs;       // the definitions plan() evaluated inside a real operation's program, in program order (findRepeatRuns)
     int leaves = 0;                  // > 0: the slices form a forest (every slice has at most one dependant, none is empty) and this many of
                                      // them wait for nothing — the program can run on tickets (PlanSeg::next); 0: dependency flags only
-    void clear() { prog.clear(); segs.clear(); deps.clear(); launchOrder.clear(); snapPairs.clear(); leaves = 0; }
+    void clear() { prog.clear(); segs.clear(); deps.clear(); launchOrder.clear(); snapPairs.clear(); runs.clear(); leaves = 0; }
 };
 
 // Read-mode programs: where the reciprocal scale factors are applied.  A result that is not stored is seen by nobody but the
@@ -70,6 +79,86 @@ struct Plan {
 // engine builds, engine_walk.cpp).  false: the program rescales in write mode somewhere (nothing is folded then).
 struct FoldMap { std::vector<int> payStart, members; };
 bool foldScaleFactors(const Plan& plan, int maxMembers, FoldMap& out);
+
+// ---- repeated sub-patterns -----------------------------------------------------------------------------------------------
+// The partial of a node depends on the states of the tips below it and on nothing else of a pattern, and real alignments repeat: under a
+// clade of a dozen tips the 1e5 patterns of a 1000-taxon alignment show a few hundred distinct sub-patterns.  RepeatIndex keeps, per clade
+// over compact tips, the CLASS of every pattern (patterns of a class agree on every tip of the clade), the class count D and one
+// representative pattern per class (the smallest).  Built bottom-up from the children's classes (key = class(A) * D(B) + class(B); a tip's
+// class is its state code, every code >= 4 one class), memoised by the two child clades — tips as leaves — so that whatever a new operation
+// list keeps of the tree finds its clades here, whichever buffers the nodes sit in.  Pure host data; the engine owns what it derives for
+// the device (engine_walk.cpp) and drops everything when tip states change.
+class RepeatIndex {
+public:
+    struct Clade {
+        int a = -1, b = -1;              // children: a tip (< tipCount: its buffer) or a clade (tipCount + index)
+        int D = 0;
+        bool built = false, over = false;    // over: more classes than the limit (or a child that is) — no index
+        std::vector<std::uint16_t> cls;      // [P]
+        std::vector<int> rep;                // [D]: the smallest pattern of each class; classes are numbered by it
+        std::vector<int> tips;               // the clade's tips, left to right
+    };
+    void init(int tipCount, int patterns, int maxClasses);
+    void clear();                                    // forget every clade (the tips' states stay registered)
+    // Nothing is forgotten clade by clade (ids are what tables and kept programs name), and every list a topology move makes adds the
+    // clades on two paths to the root — so the index has a CAPACITY: past it the owner drops everything (clear(), and what it derived)
+    // and the live clades come back with the next list.  8 clades per tip + 1024: a tree's worth many times over.
+    std::size_t capacity() const { return capacity_; }
+    void setCapacity(std::size_t n) { capacity_ = n; }
+    bool overCapacity() const { return clades_.size() > capacity_; }
+    std::size_t bytes() const;                       // host memory of the indices kept
+    void setTip(int tip, const std::uint8_t* states) { if (tip >= 0 && tip < tipCount_) tip_[(std::size_t)tip] = states; }   // [P] state codes (kept by the caller); nullptr: none
+    int intern(int a, int b);                        // the clade over these two children (order does not matter), made on first sight
+    int find(int a, int b) const;                    // ... or -1
+    // index of clade `id`, children first; false: it has none.  budget: at most *budget clades are indexed by this call (counted down;
+    // false with clade(id).built still false: call again)
+    bool build(int id, int* budget = nullptr);
+    const Clade& clade(int id) const { return clades_[(std::size_t)(id - tipCount_)]; }
+    bool isTip(int id) const { return id < tipCount_; }
+    int tipCount() const { return tipCount_; }
+    int patterns() const { return P_; }
+    int maxClasses() const { return maxClasses_; }
+    std::size_t size() const { return clades_.size(); }
+    long builds = 0;                                 // clades indexed so far (tests count them)
+private:
+    int tipCount_ = 0, P_ = 0, maxClasses_ = 0;
+    std::size_t capacity_ = 1024;
+    std::vector<const std::uint8_t*> tip_;
+    std::vector<Clade> clades_;
+    std::unordered_map<std::uint64_t, int> memo_;
+    std::vector<int> table_;                         // build()'s scratch
+};
+
+// Where the class tables live: arenas laid out [C][P][4] like a partials buffer, back to back; a clade of D classes takes D rows padded to
+// whole groups of 128 (a slice of the walk starts at a multiple of 128 patterns) inside ONE arena.  A bump allocator: tables are never
+// freed one by one — when the arenas are full of clades no list names any more, everything is dropped and the live ones come back.
+struct RepeatRows {
+    int arenas = 0, P = 0, nextArena = 0, nextRow = 0;
+    void init(int arenaCount, int patterns) { arenas = arenaCount; P = patterns; reset(); }
+    void reset() { nextArena = 0; nextRow = 0; }
+    bool place(int D, int& arena, int& row) {           // false: no room (or a clade that no arena can hold)
+        const int pad = (D + 127) & ~127;
+        if (D <= 0 || pad > P || nextArena >= arenas) return false;
+        if (nextRow + pad > P) { if (nextArena + 1 >= arenas) return false; nextArena++; nextRow = 0; }
+        arena = nextArena; row = nextRow; nextRow += pad;
+        return true;
+    }
+};
+
+// A run of Plan::runs that can be taken from a class table: every leaf a compact tip, nothing stored, nothing rescaled in write mode, no
+// micro-operation of it pays reciprocals (`fold`: the plan's own FoldMap — its memberships are kept, the consumer pays what it paid; without
+// one every read-mode micro-operation pays for itself and such a run stays), its consumer in the same slice.
+struct RepeatRun { int run, clade, consumer; bool viaHold; };
+// the candidates of `plan`; a clade whose index is missing is built (`build`) or listed in `missing` and left out
+void findRepeatRuns(const Plan& plan, const FoldMap* fold, RepeatIndex& idx, bool build, std::vector<RepeatRun>& out, std::vector<int>* missing = nullptr);
+// The plan with the runs of `take` evaluated once per class.  out.plan: the UPPER program — the source's slices in the source's order, with its
+// dependencies, launch order and leaves, the runs gone and their consumers reading PK_TAB operands — and behind it in out.plan.prog the
+// LOWER programs, one slice per run (out.lower; PlanSeg::partition = the clade): the run's own micro-operations, paying nothing, the last
+// one's result to be stored as the clade's table.  origin[i]: the micro-operation of the source that out.plan.prog[i] came from.
+// twoTables: consumers with both children from tables;  unstoredConsumers: consumers that are not stored themselves — steps of a memory
+// definition evaluated behind its operand's program (planner.h memStepCap), the only unstored micro-operations with a definition as a child
+struct RepeatPlan { Plan plan; std::vector<PlanSeg> lower; std::vector<int> origin; int tableReads = 0, twoTables = 0, unstoredConsumers = 0; };
+void emitRepeatPlan(const Plan& plan, const std::vector<RepeatRun>& take, RepeatPlan& out);
 
 // Definition of a virtual buffer: one step per internal node of a small all-compact-tip subtree, in post-order (a step's
 // sub-steps precede it; the last step is the buffer's own node).  An operand of a step is a compact tip or an earlier

@@ -487,6 +487,16 @@ int beagleMi355WalkStats(int instance, long* out8);
  * creation, default 20 000); out[2]: folded reciprocal vectors in use by read-mode programs (one per stored node instead of one
  * per node: DESIGN.md 4.1); out[3]: how many times such vectors were (re)built from the per-node factors. */
 int beagleMi355WalkHealth(int instance, long* out4);
+/* Repeated sub-patterns (4 states): clades of compact tips evaluated once per distinct sub-pattern.  Since the last
+ * beagleMi355KernelTimer / KernelTimerRestart call — out[0]: class rows evaluated (a micro-operation of a class-table program over
+ * a clade of D classes counts D; divided by the pattern count: full-width micro-operations), out[1]: operands read from a class
+ * table, out[2]: class-table programs run (clades, counted per evaluation).  Since creation — out[3]: bytes of the table arena and
+ * of the tables' row vectors and representative tip rows, out[4]: clades indexed on the host, out[5]: host microseconds spent on
+ * indices and tables.  Since the last timer call again — out[6]: micro-operations with BOTH children read from class tables, out[7]:
+ * table operands of micro-operations that are not stored themselves (steps of a memory definition).  Since creation — out[8]: bytes
+ * of host memory the class indices take, out[9]: times they were dropped at their capacity (a chain of topology moves).  All zero where
+ * the feature is off (BEAGLE_MI355_NO_REPEATS=1, small buffers, write-mode evaluations). */
+int beagleMi355RepeatStats(int instance, long* out10);
 /* How the one-launch walks of a 4-state instance were run since its creation: out[0] launches on TICKETS (the program's slices form
  * a forest: only the slices without dependencies get workgroups, the workgroup that arrives last at a slice above runs it — nobody
  * waits; the default), out[1] launches on dependency FLAGS (every slice its own workgroups, which poll: programs whose slices do not

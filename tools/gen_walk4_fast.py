@@ -72,6 +72,9 @@ B_X, B_T1, B_T2, B_INV, B_STORE, B_HSLOT1, B_READ, B_WRITE = 0, 1, 2, 3, 4, 12, 
 # and the stage goes on as if the previous micro-operation had left it there.  Same arithmetic, same order, same bits.
 B_CHERRY = 15
 B_HREAD, B_HREAD1, B_MEM2, B_HWRITE, B_HREAD2 = 24, 25, 26, 27, 31
+# B_TAB1 / B_TAB2 (kernels.h WK_TAB): the first / second child is read from a class table — set together with B_X / B_MEM2, whose
+# out-of-line blocks branch to table_rows below; nothing on the loop's common path knows about them
+B_TAB1, B_TAB2 = 28, 29
 # bits 16..23 belong to the kernel that runs the program (k_walk4: its wait-table jump); here: the two tip-state loads of a fetch are
 # SKIPPED under B_NOLOAD1 / B_NOLOAD2 (round 6: the host sets them, in programs that do not rescale in write mode, for a child that is
 # no compact tip — half the children of a tree; a vector-memory instruction occupies the CU's address unit for ~16 cycles whatever it
@@ -186,6 +189,9 @@ def tip_columns(dst, t, tbl, off):
 
 
 outofline = []      # (label, [lines]) blocks placed after the loop
+# ... and behind all of those the table blocks (table_rows): programs without table operands — every partial update — never enter them, and
+# placed among the blocks such programs do enter they spread those over more instruction-cache lines (branch moves measured 3 % slower)
+coldline = []
 
 
 def fdiv_one(out, den, d0, r, t, n0, q):
@@ -340,6 +346,34 @@ def fetch(tag, slot):
         outofline.append([L("iv" + tag) + ":", "global_load_dwordx4 %s, %s, %s" % (v(INVS[slot], 4), v(SCALE), s(D + 6, 2)), "s_branch %s" % L("ivb" + tag)])
 
 
+def table_rows(label, dst, rows, arena, off_rows, off_arena, back, drain):
+    """A child from a class table (kernels.h WK_TAB), out of line and blocking: the descriptor field at DP + off_rows is the clade's row
+    vector — per pattern, at the pair's position like the tip states, the uint32 byte offset of the pattern's class row —, the one at
+    DP + off_arena (the descriptor's scaleW) the table arena; the lane's two rows are at arena + offset + c P 32.  Index load, wait,
+    the four row loads into dst (drain: and wait for them).  The wait in the middle lets every load issued before land too: the exact
+    stage waits, which count the row loads as they count a child from memory, then only wait for less than they have to.  The rows were
+    written by an earlier launch: no device-scope bit, they may stay in this XCD's L2 for the patterns that share them."""
+    blk = [label + ":",
+           "s_load_dwordx2 %s, %s, %d" % (s(rows, 2), s(DP, 2), off_rows),
+           "s_load_dwordx2 %s, %s, %d" % (s(arena, 2), s(DP, 2), off_arena),
+           "v_lshlrev_b32_e32 %s, 2, %s" % (v(T0), v(TIP)),
+           "s_waitcnt lgkmcnt(0)",
+           "global_load_dwordx2 %s, %s, %s" % (v(T0, 2), v(T0), s(rows, 2)),
+           "s_waitcnt vmcnt(0)",
+           "v_add_u32_e32 %s, %%[cP32], %s" % (v(T0), v(T0)),
+           "v_add_u32_e32 %s, %%[cP32], %s" % (v(T1), v(T1)),
+           "global_load_dwordx4 %s, %s, %s" % (v(dst, 4), v(T0), s(arena, 2)),
+           "global_load_dwordx4 %s, %s, %s offset:16" % (v(dst + 4, 4), v(T0), s(arena, 2)),
+           "global_load_dwordx4 %s, %s, %s" % (v(dst + 8, 4), v(T1), s(arena, 2)),
+           "global_load_dwordx4 %s, %s, %s offset:16" % (v(dst + 12, 4), v(T1), s(arena, 2))]
+    if drain:
+        blk.append("s_waitcnt vmcnt(0)")
+    blk.append("s_branch %s" % back)
+    if "notab" in EXPERIMENT:                          # (timing only, wrong results: what the gathers cost — profiles/repeats_sweep.txt)
+        return [label + ":", "s_branch %s" % back]
+    return blk
+
+
 def first_child_fetch(tag, SFLn, off_src1):
     """The first child of the FOLLOWING micro-operation (flags in SFLn), if it waits in an LDS hold slot or in memory, into XB —
     behind the last use of XB by the micro-operation at hand; ONE test on the common path.  off_src1: where DP finds that
@@ -359,6 +393,8 @@ def first_child_fetch(tag, SFLn, off_src1):
         blk.append("ds_read_b128 %s, %s offset:%d" % (v(XB + 4 * q, 4), v(T0), 1024 * q))
     blk.append("s_branch %s" % L("frb" + tag))
     blk += [L("x" + tag) + ":",
+            "s_bitcmp1_b32 %s, %d" % (s(SFLn), B_TAB1),
+            "s_cbranch_scc1 %s" % L("xt" + tag),
             "s_load_dwordx2 %s, %s, %d" % (s(SX, 2), s(DP, 2), off_src1),
             "s_waitcnt lgkmcnt(0)",
             "global_load_dwordx4 %s, %s, %s%s" % (v(XB, 4), v(PA), s(SX, 2), LOAD_POLICY),
@@ -367,6 +403,8 @@ def first_child_fetch(tag, SFLn, off_src1):
             "global_load_dwordx4 %s, %s, %s offset:16%s" % (v(XB + 12, 4), v(PB), s(SX, 2), LOAD_POLICY),
             "s_branch %s" % L("frb" + tag)]
     outofline.append(blk)
+    # (SSRC2: the second-child block's scratch pair, free in the middle of a stage)
+    coldline.append(table_rows(L("xt" + tag), XB, SX, SSRC2, off_src1, off_src1 + 40, L("frb" + tag), False))
 
 
 def stage(tag, cur):
@@ -474,8 +512,11 @@ def stage(tag, cur):
     ccblk = lines[:]
     del lines[:]
     lines.extend(save2)
-    m2blk[1:1] = ["s_bitcmp1_b32 %s, %d" % (s(SFL), B_CHERRY), "s_cbranch_scc1 %s" % L("cc" + tag)]
+    m2blk[1:1] = ["s_bitcmp1_b32 %s, %d" % (s(SFL), B_CHERRY), "s_cbranch_scc1 %s" % L("cc" + tag),
+                  "s_bitcmp1_b32 %s, %d" % (s(SFL), B_TAB2), "s_cbranch_scc1 %s" % L("m2t" + tag)]
     outofline.append(m2blk)
+    # (SX: the first-child block's scratch pair, free until the middle of the stage)
+    coldline.append(table_rows(L("m2t" + tag), ACC, SSRC2, SX, off_src2, off_src2 - 8 + 40, L("m2b" + tag), True))
     outofline.append(ccblk)
     e("ds_read_b64 %s, %s offset:160" % (v(SP, 2), v(spCur)))
     col0_reads(XB, tbvCur, 160)                  # (the first-child buffer: consumed by the first mat-vec, or not in use)
@@ -663,7 +704,7 @@ def build():
     e("s_sub_u32 %s, %s, 1" % (s(CNT), s(CNT)))
     e("s_cbranch_scc0 %s" % L("top"))
     e("s_branch %s" % L("end"))
-    for blk in outofline:
+    for blk in outofline + coldline:
         for l in blk:
             e(l)
     e(L("end") + ":")
