@@ -124,6 +124,7 @@ ABI_SYMBOLS = ["beagleGetVersion", "beagleGetCitation", "beagleGetResourceList",
               ["beagle" + k for k in _PROTOS] + \
               ["beagleMi355SetStream", "beagleMi355CalculateRootLogLikelihoodsDevice", "beagleMi355Synchronize",
                "beagleMi355KernelTimer", "beagleMi355DeviceBytes", "beagleMi355WalkStats", "beagleMi355GradientStats", "beagleMi355GetPartialsBatch", "beagleMi355SampleAncestralStates", "beagleMi355SampleMarkovJumps", "beagleMi355SampleMarkovJumpsUniformized",
+               "beagleMi355NodeHeightDerivatives",
                "beagleMi355GetPartialsPinned", "beagleMi355GetSiteLogLikelihoodsPinned",
                "beagleMi355KernelTimerCalls", "beagleMi355WalkHealth", "beagleMi355RepeatStats", "beagleMi355WalkLaunchInfo", "beagleMi355RootFusedCount", "beagleMi355SitePrefetchCount", "beagleMi355KernelTimerRestart", "beagleMi355GetDimensions", "beagleMi355GetCommUniqueId", "beagleMi355CommInit", "beagleMi355CommInfo", "beagleMi355CalculateRootLogLikelihoodsAllReduce"] + \
               ["beagleBasta" + k for k in ("AllocateCoalescentBuffers", "UpdatePartials", "AccumulatePartials", "GetBuffer", "GetBufferLength", "Stats",
@@ -530,6 +531,23 @@ class Beagle:
         self._check("sampleAncestralStates", f(self.instance, _ip(rows), rows.shape[0], categoryWeightsIndex, stateFrequenciesIndex,
                                                int(seed) & 0xFFFFFFFFFFFFFFFF, 1 if map else 0, states.ctypes.data, _ip(cats)))
         return states, cats
+
+    def nodeHeightDerivatives(self, nodes, rates, categoryWeightsIndex=0, first=True, second=True):
+        """d lnL / d h and d^2 lnL / d h^2 of the listed internal nodes in one call, from the partials on the device
+        (include/beagle_mi355.h beagleMi355NodeHeightDerivatives).  ``nodes``: [nodeCount][8] rows {pre(i), post(j), matrix(j),
+        dmatrix(j), post(k), matrix(k), dmatrix(k), dmatrix(i)} (dmatrix(i) = -1 at the root); ``rates``: [nodeCount][3] rows
+        {r_j, r_k, r_i}.  -> (first, second), each [nodeCount] or None when not asked for.  A result that is not finite raises
+        BeagleException with code -8."""
+        rows = _i(nodes).reshape(-1, 8)
+        r = _d(rates).reshape(-1, 3)
+        if r.shape[0] != rows.shape[0]:
+            raise ValueError("rates must have one row {r_j, r_k, r_i} per node")
+        n = rows.shape[0]
+        o1 = np.zeros(n) if first else None
+        o2 = np.zeros(n) if second else None
+        f = self._ext("beagleMi355NodeHeightDerivatives", [C.c_int, _IP, _DP, C.c_int, C.c_int, _DP, _DP])
+        self._check("nodeHeightDerivatives", f(self.instance, _ip(rows), _dp(r), n, categoryWeightsIndex, _dp(o1), _dp(o2)))
+        return o1, o2
 
     def sampleMarkovJumps(self, nodes, branchTimes, branchRates, eigenIndex, categoryRatesIndex, categoryWeightsIndex,
                           stateFrequenciesIndex, registers, registerFlags, seed, map=False, states=False, jumps=False,

@@ -7,6 +7,7 @@
 //   engine_root.cpp      the calls that observe a likelihood: root sums, the polled result page, site log-likelihoods
 //   engine_readback.cpp  partials and scale factors back to the host
 //   engine_sampling.cpp  the device samplers (ancestral draws, Markov jumps, uniformized histories)
+//   engine_nodeheight.cpp  node-height gradients and diagonal Hessians in one call
 //   engine_stats.cpp     stream, synchronisation, kernel timer, counters
 // each of them argument checks, buffer bookkeeping and one call into the files above.
 // All arithmetic is in the .hip files; these files validate indices, resolve buffer indices to device pointers and enqueue

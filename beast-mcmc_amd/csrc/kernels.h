@@ -448,6 +448,37 @@ void launchEdgeFinal(hipStream_t stream, const double* blockSums, int nRows, int
 // out[S*S] = sum over edges and patterns of the weighted pre x post cross products (see kernels_preorder.hip); partial: [edgeBlocks(P)][S*S]
 void launchCrossProducts(hipStream_t stream, const EdgeDesc* dEdges, int nEdges, const double* dEdgeLengths, const double* catWeights,
                          const double* catRates, const double* patternWeights, double* partial, double* out, int P, int S, int C, bool tiled);
+// ---- node-height derivatives (kernels_nodeheight.hip; beagleMi355NodeHeightDerivatives) -----------------------------------
+// One internal node i with children j, k: pre(i), post(j), post(k) read once, nothing written but the block sums.  Per pattern, with
+// x the children's partials (a compact state: its unit vector, all ones when missing), a = P x, b = Q a, c = Q b per child, q = pre(i),
+// u = Q_i^T q, v = Q_i^T u and <.> = sum_c w_c sum_s:
+//   D = <a_j a_k q>;  g_j = <b_j a_k q> / D, g_k likewise, g_i = <a_j a_k u> / D;  h_jj = <c_j a_k q> / D - g_j^2, h_kk likewise,
+//   h_jk = <b_j b_k q> / D - g_j g_k, h_ii = <a_j a_k v> / D - g_i^2, h_ij = <b_j a_k u> / D - g_i g_j, h_ik likewise
+//   first  = r_j g_j + r_k g_k - r_i g_i
+//   second = r_j^2 h_jj + r_k^2 h_kk + 2 r_j r_k h_jk + r_i^2 h_ii - 2 r_i r_j h_ij - 2 r_i r_k h_ik          (no i terms at the root: dI < 0)
+// blockSums[slot][edgeBlocks(P)][2] = {sum_p weight_p first, sum_p weight_p second} per 64 patterns; finish with launchEdgeFinal.
+struct NodeHeightJob {
+    const double* pre;           // pre-order partials of node i
+    const void*   postJ;         // post-order partials of child j (double*) or its compact states (uint8*, statesJ)
+    const void*   postK;
+    int           matJ, dJ;      // child j's branch matrix and differential matrix (indices into `matrices`, C*S*S doubles each)
+    int           matK, dK;
+    int           dI;            // node i's differential matrix, < 0 at the root
+    int           statesJ, statesK;
+    int           slot;
+    double        rJ, rK, rI;    // branch rates
+};
+static_assert(sizeof(NodeHeightJob) == 80, "NodeHeightJob layout");
+// 4 states, plain layout: a pattern per lane, 32-byte vector loads, the five matrices of a job wave-uniform; second = false leaves
+// every second-order term out (the second block sum is 0)
+void launchNodeHeight4(hipStream_t stream, const NodeHeightJob* dJobs, int nJobs, const double* matrices, const double* catWeights,
+                       const double* patternWeights, double* blockSums, int P, int C, bool second);
+// 2..64 states, either layout.  products: scratch of nodeHeightProductDoubles(nJobs, S, C) doubles the launcher fills first with
+// Q_j P_j, Q_j Q_j P_j (and k's) and Q_i Q_i per job, so that every vector the sums need is ONE matrix applied to a partial the
+// thread holds (b_j = (Q_j P_j) x_j ...).  false: LDS refused.
+size_t nodeHeightProductDoubles(int nJobs, int S, int C);
+bool launchNodeHeight(hipStream_t stream, const NodeHeightJob* dJobs, int nJobs, const double* matrices, double* products,
+                      const double* catWeights, const double* patternWeights, double* blockSums, int P, int S, int C, bool tiled, bool second);
 void launchTransposeMatrices(hipStream_t stream, double* matrices, const int* dSrcDst, int count, int S, int C);
 void launchFillFrequencies(hipStream_t stream, double* dest, const double* freqs, int P, int S, int C, bool tiled);
 

@@ -353,6 +353,31 @@ int beagleMi355GetPartialsBatch(int instance, const int* bufferIndices, const in
 #define BEAGLE_MI355_ANCESTRAL_MAP 1
 int beagleMi355SampleAncestralStates(int instance, const int* nodes, int nodeCount, int categoryWeightsIndex, int stateFrequenciesIndex,
                                      unsigned long long seed, int flags, unsigned char* outStates, int* outRateCategories);
+/* Node heights: d lnL / d h_i and d^2 lnL / d h_i^2 for every listed internal node i in ONE call, from the partials where they are —
+ * what DiscreteTraitNodeHeightDelegate.getNodeDerivatives computes from a getPartials per post-order and per pre-order buffer and a
+ * getTransitionMatrix per branch (DiscreteTraitNodeHeightDelegate.java:63-200; the NodeHeightGradient / NodeHeightHessian traits of
+ * the divergence-time HMC).  Call it after a gradient pass: post-order partials, the pre-order partials of the INTERNAL nodes, the
+ * branch matrices and the rate-scaled infinitesimal matrices (setDifferentialMatrix: Q x category rate, [C][S][S]) are all it reads.
+ *   nodes: [nodeCount][8], one row per internal node i with children j, k:
+ *          {pre(i), post(j), matrix(j), dmatrix(j), post(k), matrix(k), dmatrix(k), dmatrix(i)}; dmatrix(i) = -1 at the root.
+ *          post(.) may hold compact tip states (a state >= stateCount: all ones), a tip's partials or an internal node's.
+ *   rates: [nodeCount][3] = {r_j, r_k, r_i}, the branch rates (branch length = rate x height difference); r_i is ignored at the root.
+ *   outFirst, outSecond: [nodeCount]; either may be NULL, not both.
+ * Per pattern p and category c (weight w_c): x = the child's partial, a_j = P_j x_j, b_j = Q_j a_j, c_j = Q_j b_j (the same for k),
+ * q = pre(i), u = Q_i^T q, v = Q_i^T u, and with <.> = sum_c w_c sum_s
+ *   D    = <a_j a_k q>
+ *   g_j  = <b_j a_k q>/D      g_k = <a_j b_k q>/D      g_i = <a_j a_k u>/D
+ *   h_jj = <c_j a_k q>/D - g_j^2    h_kk likewise    h_jk = <b_j b_k q>/D - g_j g_k
+ *   h_ii = <a_j a_k v>/D - g_i^2    h_ij = <b_j a_k u>/D - g_i g_j    h_ik likewise
+ *   first[i]  = sum_p weight_p ( r_j g_j + r_k g_k - r_i g_i )
+ *   second[i] = sum_p weight_p ( r_j^2 h_jj + r_k^2 h_kk + 2 r_j r_k h_jk + r_i^2 h_ii - 2 r_i r_j h_ij - 2 r_i r_k h_ik )
+ * (the i terms dropped at the root).  Every ratio is free of scale factors: rescaled partials are read as they are.  The sums over
+ * patterns are formed in a fixed order: two calls return the same bits.  The sharded handle adds its shards' sums.
+ * BEAGLE_ERROR_OUT_OF_RANGE for a bad index, a pre(i) that holds tip states or nothing, NULL arguments, nodeCount < 1;
+ * BEAGLE_ERROR_NO_IMPLEMENTATION with more than one pattern partition or more than 64 states; BEAGLE_ERROR_FLOATING_POINT when a
+ * result is not finite — the outputs are still written.  An extension: no BEAST class calls it today. */
+int beagleMi355NodeHeightDerivatives(int instance, const int* nodes, const double* rates, int nodeCount, int categoryWeightsIndex,
+                                     double* outFirst, double* outSecond);
 /* Markov jumps: ONE call that draws the ancestral states as beagleMi355SampleAncestralStates does and, for every register k, row
  * r >= 1 and pattern p, forms the expected number of registered substitutions (a count register) or the expected reward (a reward
  * register) on row r's branch, conditioned on the drawn parent and child states — what MarkovJumpsBeagleTreeLikelihood.hookCalculation
