@@ -124,7 +124,7 @@ ABI_SYMBOLS = ["beagleGetVersion", "beagleGetCitation", "beagleGetResourceList",
               ["beagle" + k for k in _PROTOS] + \
               ["beagleMi355SetStream", "beagleMi355CalculateRootLogLikelihoodsDevice", "beagleMi355Synchronize",
                "beagleMi355KernelTimer", "beagleMi355DeviceBytes", "beagleMi355WalkStats", "beagleMi355GradientStats", "beagleMi355GetPartialsBatch", "beagleMi355SampleAncestralStates", "beagleMi355SampleMarkovJumps", "beagleMi355SampleMarkovJumpsUniformized",
-               "beagleMi355NodeHeightDerivatives",
+               "beagleMi355NodeHeightDerivatives", "beagleMi355SetTipEmission", "beagleMi355TipEmissionStats",
                "beagleMi355GetPartialsPinned", "beagleMi355GetSiteLogLikelihoodsPinned",
                "beagleMi355KernelTimerCalls", "beagleMi355WalkHealth", "beagleMi355RepeatStats", "beagleMi355WalkLaunchInfo", "beagleMi355RootFusedCount", "beagleMi355SitePrefetchCount", "beagleMi355KernelTimerRestart", "beagleMi355GetDimensions", "beagleMi355GetCommUniqueId", "beagleMi355CommInit", "beagleMi355CommInfo", "beagleMi355CalculateRootLogLikelihoodsAllReduce"] + \
               ["beagleBasta" + k for k in ("AllocateCoalescentBuffers", "UpdatePartials", "AccumulatePartials", "GetBuffer", "GetBufferLength", "Stats",
@@ -531,6 +531,22 @@ class Beagle:
         self._check("sampleAncestralStates", f(self.instance, _ip(rows), rows.shape[0], categoryWeightsIndex, stateFrequenciesIndex,
                                                int(seed) & 0xFFFFFFFFFFFFFFFF, 1 if map else 0, states.ctypes.data, _ip(cats)))
         return states, cats
+
+    def setTipEmission(self, tipIndex, codes, emission):
+        """A tip whose partials are the lookup ``emission[codes[p]]`` (include/beagle_mi355.h beagleMi355SetTipEmission): ``emission``
+        [K][S], ``codes`` [P] ints (one outside 0..K-1: missing) or None to keep the codes of the previous call and replace the table."""
+        e = _d(emission).reshape(-1, self.stateCount)
+        c = None if codes is None else _i(codes)
+        if c is not None and c.size < self.patternCount:
+            raise ValueError("codes must have one entry per pattern")
+        f = self._ext("beagleMi355SetTipEmission", [C.c_int, C.c_int, _IP, C.c_int, _DP])
+        self._check("setTipEmission", f(self.instance, tipIndex, _ip(c), e.shape[0], _dp(e)))
+
+    def tipEmissionStats(self):
+        """Tips with an emission table (include/beagle_mi355.h beagleMi355TipEmissionStats)."""
+        out = (C.c_long * 4)()
+        self._check("tipEmissionStats", self._ext("beagleMi355TipEmissionStats", [C.c_int, C.POINTER(C.c_long)])(self.instance, out))
+        return {"folded": int(out[0]), "expanded": int(out[1]), "fold_launches": int(out[2]), "demotions": int(out[3])}
 
     def nodeHeightDerivatives(self, nodes, rates, categoryWeightsIndex=0, first=True, second=True):
         """d lnL / d h and d^2 lnL / d h^2 of the listed internal nodes in one call, from the partials on the device

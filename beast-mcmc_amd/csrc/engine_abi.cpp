@@ -223,6 +223,7 @@ int beagleSetTipStates(int instance, int tipIndex, const int* inStates) {
     GET_INSTANCE(instance);
     if (badIndex(tipIndex, in->tipCount) || badIndex(tipIndex, in->partialsCount) || tipIndex >= in->compactCount)
         return BEAGLE_ERROR_OUT_OF_RANGE;
+    if (in->emis) dropTipEmission(in, tipIndex);                      // (beagleMi355SetTipEmission: the tip is the caller's again)
     int rc = materializeTipUsers(in, tipIndex); if (rc) return rc;   // virtual cherries defined by the OLD states
     rc = ensureStates(in, tipIndex); if (rc) return rc;
     setCompact(in, tipIndex, true);
@@ -251,7 +252,13 @@ int beagleGetTipStates(int instance, int tipIndex, int* outStates) {
         return mi355::shardedGetPerPatternInts(instance, outStates, [&](int h, int* v) { return beagleGetTipStates(h, tipIndex, v); });
     }
     GET_INSTANCE(instance);
-    if (badIndex(tipIndex, in->partialsCount) || !in->tipStates[tipIndex]) return BEAGLE_ERROR_OUT_OF_RANGE;
+    if (badIndex(tipIndex, in->partialsCount)) return BEAGLE_ERROR_OUT_OF_RANGE;
+    if (in->emis && tipIndex < in->tipCount && in->emis->tips[(size_t)tipIndex].K) {      // a tip with an emission table: its codes (one outside the table: K)
+        const TipEmission& t = in->emis->tips[(size_t)tipIndex];
+        for (int p = 0; p < in->P; p++) outStates[p] = t.codes[(size_t)p] == 255 ? t.K : (int)t.codes[(size_t)p];
+        return BEAGLE_SUCCESS;
+    }
+    if (!in->tipStates[tipIndex]) return BEAGLE_ERROR_OUT_OF_RANGE;
     std::vector<uint8_t> s(in->P);
     int rc = download(in, s.data(), in->tipStates[tipIndex], (size_t)in->P); if (rc) return rc;
     for (int p = 0; p < in->P; p++) outStates[p] = s[p];
@@ -265,6 +272,7 @@ int beagleSetTipPartials(int instance, int tipIndex, const double* inPartials) {
     }
     GET_INSTANCE(instance);
     if (badIndex(tipIndex, in->partialsCount)) return BEAGLE_ERROR_OUT_OF_RANGE;
+    if (in->emis) dropTipEmission(in, tipIndex);
     in->scaleOfPartial[tipIndex] = -1;                     // (caller's data: no scale factor of ours in it)
     int rc = materializeTipUsers(in, tipIndex); if (rc) return rc;
     clearVirtual(in, tipIndex);
@@ -300,6 +308,7 @@ int beagleSetPartials(int instance, int bufferIndex, const double* inPartials) {
     // (a held-back pre-order list has its own copy of its root's pre-order partial — the buffer the gradient delegates rewrite
     // before every list — and waits unless this is one of the other buffers it reads or writes)
     if (heldTouches(in, bufferIndex)) { int rcp = executeHeldPre(in); if (rcp) return rcp; }
+    if (in->emis) dropTipEmission(in, bufferIndex);
     in->scaleOfPartial[bufferIndex] = -1;                  // (caller's data: no scale factor of ours in it)
     int rc = materializeTipUsers(in, bufferIndex); if (rc) return rc;
     clearVirtual(in, bufferIndex);
@@ -756,6 +765,7 @@ int beagleUpdatePrePartials(int instance, const int* operations, int operationCo
         return mi355::shardedBroadcast(instance, [&](int h) { return beagleUpdatePrePartials(h, operations, operationCount, cumulativeScaleIndex); });
     }
     GET_INSTANCE_KEEP_PENDING(instance);                      // (runPreOperations decides what becomes of a list still held back)
+    DEMOTE_FOLDED_TIPS(in);                                   // (a pre-order pass reads tips' partials as data: engine_tipemission.cpp)
     return runPreOperations(in, operations, operationCount, cumulativeScaleIndex, true);
 }
 
@@ -773,6 +783,7 @@ int beagleCalculateCrossProductDifferentials(int instance, const int* postBuffer
         return rc;
     }
     GET_INSTANCE(instance);
+    DEMOTE_FOLDED_TIPS(in);
     if (outSumSquaredDerivatives) return BEAGLE_ERROR_NO_IMPLEMENTATION;       // BEAST passes null
     if (!postBufferIndices || !preBufferIndices || !categoryRateIndices || !categoryWeightsIndices || !edgeLengths || !outSumDerivatives)
         return BEAGLE_ERROR_OUT_OF_RANGE;
@@ -805,6 +816,7 @@ int beagleCalculateEdgeDifferentials(int instance, const int* postBufferIndices,
         return BEAGLE_SUCCESS;
     }
     GET_INSTANCE_KEEP_PENDING(instance);                      // (a held-back pre-order list is what this call wants to run with)
+    DEMOTE_FOLDED_TIPS(in);
     if (!postBufferIndices || !preBufferIndices || !derivativeMatrixIndices || !categoryWeightsIndices) return BEAGLE_ERROR_OUT_OF_RANGE;
     if (badIndex(categoryWeightsIndices[0], in->eigenCount)) return BEAGLE_ERROR_OUT_OF_RANGE;
     return edgeDifferentials(in, postBufferIndices, preBufferIndices, derivativeMatrixIndices, categoryWeightsIndices[0], count,
@@ -818,6 +830,7 @@ int beagleUpdatePrePartialsByPartition(int instance, const int* operations, int 
         return mi355::shardedBroadcast(instance, [&](int h) { return beagleUpdatePrePartialsByPartition(h, operations, operationCount); });
     }
     GET_INSTANCE(instance);
+    DEMOTE_FOLDED_TIPS(in);
     return runPreOperations(in, operations, operationCount, BEAGLE_OP_NONE, false, BEAGLE_PARTITION_OP_COUNT);
 }
 

@@ -20,6 +20,8 @@ namespace eng {
 size_t matrixSlotLayout(Instance* in) {
     size_t slots = std::max<size_t>(std::max<size_t>(1, in->matrixCount), (size_t)in->planner.matrixSlots());
     if (in->tiled) { in->preIdentity = (int)slots; in->preTransposed = (int)slots + 1; slots += 1 + PRE_SCRATCH; }
+    // ... and, once a tip has an emission table, a shadow slot per caller matrix index behind everything else (engine_tipemission.cpp)
+    if (in->emis) { in->emis->shadowBase = (int)slots; slots += (size_t)std::max(1, in->matrixCount); }
     return slots;
 }
 int uploadIdentityMatrix(Instance* in) {

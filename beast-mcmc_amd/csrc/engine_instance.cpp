@@ -175,6 +175,7 @@ void destroy(Instance* in) {
     in->pendingCopies.clear();
     if (in->ownStream) hipStreamSynchronize(in->ownStream);
     if (in->basta) bastaFree(in);
+    if (in->emis) freeTipEmissions(in);
     if (in->comm) { if (in->stream) hipStreamSynchronize(in->stream); ncclCommDestroy(in->comm); in->comm = nullptr; }
     if (in->stream && in->stream != in->ownStream) hipStreamSynchronize(in->stream);
     for (void* p : in->allocations) hipFree(p);

@@ -8,6 +8,7 @@
 //   engine_readback.cpp  partials and scale factors back to the host
 //   engine_sampling.cpp  the device samplers (ancestral draws, Markov jumps, uniformized histories)
 //   engine_nodeheight.cpp  node-height gradients and diagonal Hessians in one call
+//   engine_tipemission.cpp  tip error models: emission tables folded into the tip branch matrices
 //   engine_stats.cpp     stream, synchronisation, kernel timer, counters
 // each of them argument checks, buffer bookkeeping and one call into the files above.
 // All arithmetic is in the .hip files; these files validate indices, resolve buffer indices to device pointers and enqueue
@@ -57,6 +58,7 @@ constexpr int MEM_DEF_STEPS = 8;           // longest definition over a stored i
 constexpr int GRADIENT_VIRT_DEFAULT = 1;   // ... and what it does leave unstored by default: nodes over two tips (engine_create.cpp)
 
 struct Basta;                              // engine_basta.cpp
+struct TipEmissions;                       // engine_tipemission.cpp
 
 struct Instance {
     int device = 0;
@@ -241,6 +243,8 @@ struct Instance {
     char* eventDev = nullptr; size_t eventBytes = 0;
     // BASTA structured coalescent (beagleBastaAllocateCoalescentBuffers, engine_basta.cpp): null on every other instance
     Basta* basta = nullptr;
+    // tip error models (beagleMi355SetTipEmission, engine_tipemission.cpp): null on an instance that was never given an emission table
+    TipEmissions* emis = nullptr;
     long statMicroOps = 0, statStored = 0, statMemReads = 0, statTipReads = 0, statScaleReads = 0, statWalks = 0, statScaleWrites = 0;   // since the last timer reset
     hipStream_t stream = nullptr, ownStream = nullptr;
     int tipCount = 0, partialsCount = 0, compactCount = 0, S = 0, P = 0, eigenCount = 0, matrixCount = 0, C = 0, scaleCount = 0;
@@ -399,6 +403,39 @@ struct KeepWalkHeld {
     if (in->heldPre.held) { const int rcPending__ = executeHeldPre(in); if (rcPending__) return rcPending__; }
 
 inline bool badIndex(int i, int n) { return i < 0 || i >= n; }
+
+// ---- engine_tipemission.cpp: tips whose partials are a lookup E[code][state].  With K <= S codes such a tip stays a
+// compact tip and its branch matrix becomes M E^T, written into a SHADOW slot behind every other matrix slot of the instance (one
+// shadow per caller matrix index) in front of each operation list that names the tip; otherwise, and for every caller that needs the
+// tip's partials as data, the lookup is written out as a partials buffer on the device ("expanded").
+struct TipEmission {
+    int K = 0;                                           // 0: the tip has no emission
+    bool folded = false;                                 // route 1 (K <= S and no caller has needed the partials since the codes came); otherwise expanded
+    std::vector<uint8_t> codes;                          // [P], 255 = outside the table (missing)
+    std::vector<double> table;                           // [K][S] as the caller gave it
+    double* dTable = nullptr; size_t dTableDoubles = 0;  // ... on the device
+    uint8_t* dCodes = nullptr; bool codesOnDevice = false;      // expanded tips: the codes on the device
+};
+struct TipEmissions {
+    std::vector<TipEmission> tips;
+    int shadowBase = 0;                                  // matrix slot of caller index 0's shadow (engine_create.cpp matrixSlotLayout)
+    int foldedCount = 0, expandedCount = 0;
+    long foldLaunches = 0, demotions = 0;
+    std::vector<int> ops, useOf; std::vector<long> useStamp; long stamp = 0;      // runOperations' rewritten list; per matrix index who uses it in this list
+    std::vector<mi355::TipFoldJob> jobs;
+};
+inline bool foldedTip(const Instance* in, int X) { return in->emis && X >= 0 && X < in->tipCount && in->emis->tips[(size_t)X].folded; }
+// a matrix index an operation may name: the caller's, or (lists rewritten by foldTipOperations) a shadow slot
+inline bool badMatrix(const Instance* in, int m) {
+    return badIndex(m, in->matrixCount) && !(in->emis && m >= in->emis->shadowBase && m < in->emis->shadowBase + in->matrixCount);
+}
+// runOperations' pre-pass: *ops becomes the list with every folded tip's matrix index replaced by its shadow, and the shadows are written
+int foldTipOperations(Instance* in, const int** ops, int count, int tuple);
+int demoteFoldedTip(Instance* in, int tip);              // a folded tip becomes an expanded one (its partials exist)
+int demoteFoldedTips(Instance* in);                      // ... every folded tip
+void dropTipEmission(Instance* in, int tip);             // setTipStates / setTipPartials: the tip is the caller's again
+void freeTipEmissions(Instance* in);
+#define DEMOTE_FOLDED_TIPS(in) do { if ((in)->emis) { const int rcDemote__ = demoteFoldedTips(in); if (rcDemote__) return rcDemote__; } } while (0)
 // is this updatePartials call one the kernel timer brackets with an event pair?  (an event costs a barrier packet on the stream:
 // 6 us of an evaluation each — a sampled timer keeps that out of most of a timed region)
 inline bool timeThisCall(Instance* in) {

@@ -80,7 +80,7 @@ int runOperationsLevels(Instance* in, const int* ops, int count, int tuple, int 
         int part = 0, cum = globalCum;
         if (tuple == BEAGLE_PARTITION_OP_COUNT) { part = op[7]; cum = op[8]; }
         if (badIndex(dest, in->partialsCount) || badIndex(c1, in->partialsCount) || badIndex(c2, in->partialsCount) ||
-            badIndex(m1, in->matrixCount) || badIndex(m2, in->matrixCount) || badIndex(part, parts) ||
+            badMatrix(in, m1) || badMatrix(in, m2) || badIndex(part, parts) ||
             (wS != BEAGLE_OP_NONE && badIndex(wS, in->scaleCount)) || (rS != BEAGLE_OP_NONE && badIndex(rS, in->scaleCount)) ||
             (cum != BEAGLE_OP_NONE && badIndex(cum, in->scaleCount)))
             return BEAGLE_ERROR_OUT_OF_RANGE;
@@ -318,6 +318,8 @@ int foldCumulative(Instance* in, const int* ops, int count, int tuple, int globa
 }
 
 int runOperations(Instance* in, const int* ops, int count, int tuple, int globalCum) {
+    // tips with an emission table (engine_tipemission.cpp): the list names their shadow matrices, which are written first
+    if (in->emis) { const int rcf = foldTipOperations(in, &ops, count, tuple); if (rcf) return rcf; }
     if (in->walk) return runOperationsWalk(in, ops, count, tuple, globalCum);
     if (in->walkT) {
         // a list that rescales in write mode: the walk's write-mode form (kernels_mfma.hip k_walkT32W1) up to four categories; beyond

@@ -117,6 +117,7 @@ int beagleMi355NodeHeightDerivatives(int instance, const int* nodes, const doubl
         return finite ? BEAGLE_SUCCESS : BEAGLE_ERROR_FLOATING_POINT;
     }
     GET_INSTANCE(instance);
+    DEMOTE_FOLDED_TIPS(in);                     // (tips' partials are read as data: engine_tipemission.cpp)
     return nodeHeightDerivatives(in, nodes, rates, nodeCount, categoryWeightsIndex, outFirst, outSecond);
 }
 

@@ -34,6 +34,7 @@ static int exportPartials(Instance* in, const int* bufferIndices, const int* sca
         if (badIndex(b, in->partialsCount)) return BEAGLE_ERROR_OUT_OF_RANGE;
         if (scaleIndices && scaleIndices[k] != BEAGLE_OP_NONE && badIndex(scaleIndices[k], in->scaleCount)) return BEAGLE_ERROR_OUT_OF_RANGE;
         if (isVirt(in, b)) in->planner.keysOf(b, need);
+        if (foldedTip(in, b)) { const int rcd = demoteFoldedTip(in, b); if (rcd) return rcd; }      // (a tip with an emission table gets its partials: engine_tipemission.cpp)
     }
     if (!need.empty()) { int rc = materializeList(in, need); if (rc) return rc; }
     const size_t elems = (size_t)in->C * in->P * in->S, bytes = elems * sizeof(double);

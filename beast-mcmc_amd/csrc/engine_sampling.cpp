@@ -111,11 +111,13 @@ int beagleMi355SampleAncestralStates(int instance, const int* nodes, int nodeCou
             int pStart = 0, pEnd = 0;
             mi355::shardedBoundsOfHandle(instance, h, &pStart, &pEnd);
             GET_INSTANCE(h);
+            DEMOTE_FOLDED_TIPS(in);
             return sampleAncestral(in, nodes, nodeCount, categoryWeightsIndex, stateFrequenciesIndex, seed, flags, globalP, pStart,
                                    outStates, outRateCategories);
         });
     }
     GET_INSTANCE(instance);
+    DEMOTE_FOLDED_TIPS(in);                     // (the samplers read tips' partials as data: engine_tipemission.cpp)
     return sampleAncestral(in, nodes, nodeCount, categoryWeightsIndex, stateFrequenciesIndex, seed, flags, in->P, 0, outStates,
                            outRateCategories);
 }
@@ -223,6 +225,7 @@ int beagleMi355SampleMarkovJumps(int instance, const int* nodes, int nodeCount, 
             int pStart = 0, pEnd = 0;
             mi355::shardedBoundsOfHandle(instance, h, &pStart, &pEnd);
             GET_INSTANCE(h);
+            DEMOTE_FOLDED_TIPS(in);
             std::vector<double> rows(outRowTotals ? nRow : 0);
             const int r = sampleJumps(in, nodes, nodeCount, branchTimes, branchRates, eigenIndex, categoryRatesIndex, categoryWeightsIndex,
                                       stateFrequenciesIndex, registers, registerFlags, registerCount, seed, flags, globalP, pStart,
@@ -243,6 +246,7 @@ int beagleMi355SampleMarkovJumps(int instance, const int* nodes, int nodeCount, 
         return rc;
     }
     GET_INSTANCE(instance);
+    DEMOTE_FOLDED_TIPS(in);
     return sampleJumps(in, nodes, nodeCount, branchTimes, branchRates, eigenIndex, categoryRatesIndex, categoryWeightsIndex,
                        stateFrequenciesIndex, registers, registerFlags, registerCount, seed, flags, in->P, 0, outStates, outRateCategories,
                        outJumps, outPatternTotals, outRowTotals);
@@ -454,6 +458,7 @@ int beagleMi355SampleMarkovJumpsUniformized(int instance, const int* nodes, int 
             int pStart = 0, pEnd = 0;
             mi355::shardedBoundsOfHandle(instance, h, &pStart, &pEnd);
             GET_INSTANCE(h);
+            DEMOTE_FOLDED_TIPS(in);
             std::vector<double> rows(outRowTotals ? nRow : 0);
             UniformPass pass;
             const int r = uniformRun(in, nodes, nodeCount, branchTimes, branchRates, nodeHeights, infinitesimalMatrix, categoryRatesIndex,
@@ -495,6 +500,7 @@ int beagleMi355SampleMarkovJumpsUniformized(int instance, const int* nodes, int 
         return rcEvents ? rcEvents : rc;
     }
     GET_INSTANCE(instance);
+    DEMOTE_FOLDED_TIPS(in);
     UniformPass pass;
     int rc = uniformRun(in, nodes, nodeCount, branchTimes, branchRates, nodeHeights, infinitesimalMatrix, categoryRatesIndex,
                         categoryWeightsIndex, stateFrequenciesIndex, registers, registerFlags, registerCount, simulantCount, seed, flags,

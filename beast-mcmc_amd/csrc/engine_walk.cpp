@@ -370,7 +370,9 @@ int runPlan(Instance* in, const mi355::Plan& plan, long planTag, hipEvent_t reco
     // (a flat table over the matrix slots, entries put back behind the loop: a program on a new tree takes ~1 800 snapshots, and a hash
     // map of them cost 200 of the 270 us this resolution took)
     std::vector<int>& snapSrc = in->snapSourceOf;
-    if (snapSrc.size() < (size_t)in->planner.matrixSlots()) snapSrc.assign((size_t)in->planner.matrixSlots(), -1);
+    // (an instance with tip emissions: its lists name shadow slots, which lie behind every other slot — engine_tipemission.cpp)
+    const size_t snapSlots = in->emis ? (size_t)in->emis->shadowBase + (size_t)in->matrixCount : (size_t)in->planner.matrixSlots();
+    if (snapSrc.size() < snapSlots) snapSrc.assign(snapSlots, -1);
     for (size_t q = 0; q + 1 < plan.snapPairs.size(); q += 2) snapSrc[(size_t)plan.snapPairs[q + 1]] = plan.snapPairs[q];
     struct SnapReset { std::vector<int>& t; const std::vector<int>& pairs; ~SnapReset() { for (size_t q = 0; q + 1 < pairs.size(); q += 2) t[(size_t)pairs[q + 1]] = -1; } } snapReset{snapSrc, plan.snapPairs};
     auto gatherFrom = [&](int mat) { const int s = snapSrc[(size_t)mat]; return s < 0 ? mat : s; };
@@ -993,7 +995,7 @@ int runOperationsWalk(Instance* in, const int* ops, int count, int tuple, int gl
         int part = 0, cum = globalCum;
         if (tuple == BEAGLE_PARTITION_OP_COUNT) { part = op[7]; cum = op[8]; }
         if (badIndex(dest, in->partialsCount) || badIndex(c1, in->partialsCount) || badIndex(c2, in->partialsCount) ||
-            badIndex(m1, in->matrixCount) || badIndex(m2, in->matrixCount) || badIndex(part, parts) ||
+            badMatrix(in, m1) || badMatrix(in, m2) || badIndex(part, parts) ||
             (wS != BEAGLE_OP_NONE && badIndex(wS, in->scaleCount)) || (rS != BEAGLE_OP_NONE && badIndex(rS, in->scaleCount)) ||
             (cum != BEAGLE_OP_NONE && badIndex(cum, in->scaleCount)))
             return BEAGLE_ERROR_OUT_OF_RANGE;

@@ -610,4 +610,13 @@ void launchBastaReduce(hipStream_t stream, const int* ops, const int* intervals,
                        const double* partials, const double* sizes, const double* coalescent, double* e, double* f, double* g,
                        double* h, double* intervalLogL, double* out, int S);
 
+// ---- tip error models (kernels_tipemission.hip): a tip whose partials are a lookup E[code][state], K codes
+// matrices[dst][c][i][k] = sum_j matrices[src][c][i][j] E[k][j] (j ascending, no fused multiply-add), zero for k >= K: one job per
+// (branch matrix, folded tip) of an operation list, all of them in one launch
+struct TipFoldJob { int src, dst, K, pad; const double* emission; };
+void launchFoldTipEmission(hipStream_t stream, double* matrices, const TipFoldJob* dJobs, int nJobs, int S, int C);
+// dest[c][p][i] = E[codes[p]][i], ones for a code >= K, in the API layout or the T32 layout (its padded patterns zero)
+void launchExpandTipEmission(hipStream_t stream, double* dest, const uint8_t* codes, const double* emission, int K, int P, int S, int C,
+                             bool tiled);
+
 }  // namespace mi355

@@ -472,6 +472,29 @@ int beagleMi355SampleMarkovJumpsUniformized(int instance, const int* nodes, int 
                                             double* outJumps, double* outPatternTotals, double* outRowTotals, int* outEventCounts,
                                             long long eventCapacity, double* outEventHeights, unsigned char* outEventStates,
                                             long long* outEventTotal, long long* outFallbacks);
+/* Tip error models (SequenceErrorModel, HypermutantErrorModel, ambiguity codes): a tip whose partials are a LOOKUP.
+ *   codes [patternCount]: the observed code of every pattern; a code outside 0..codeCount-1 is missing (all ones, a factor of one).
+ *   emission [codeCount][stateCount]: emission[k * S + i] = the tip's partial for true state i at a pattern whose code is k.
+ * The tip's partials are partials[c][p][i] = emission[codes[p]][i] in every category — what beagleSetTipPartials would have been given.
+ * codes == NULL keeps the codes of the previous call and replaces the table (codeCount as in that call): the per-proposal call, codeCount * S
+ * doubles through the pinned staging ring.  With codes the call does for the tip what beagleSetTipStates does, on the codes.
+ * codeCount <= S: the tip stays a compact tip and every operation list that names it reads, instead of its branch matrix M, the
+ * product shadow[c][i][k] = sum_j M[c][i][j] * emission[k][j] (j ascending, no fused multiply-add; columns k >= codeCount zero), which
+ * one small launch in front of the list writes into a slot of the engine's own — on every beagleUpdatePartials[ByPartition] call, since
+ * the matrix or the table may have changed.  codeCount > S, a list that uses one matrix index for such a tip and for another child, and
+ * every call that reads a tip's partials as data (beagleUpdatePrePartials[ByPartition], the edge and cross-product differentials,
+ * beagleMi355SampleAncestralStates, both Markov-jump calls, beagleMi355NodeHeightDerivatives: every such tip; beagleGetPartials, ...Batch,
+ * ...Pinned: that tip) have the device write the partials buffer out from codes and table: from then on the tip is what
+ * beagleSetTipPartials leaves behind, written again whenever its table changes, until a call with codes chooses again.
+ * beagleGetTipStates returns the codes (one outside the table: codeCount).  A later beagleSetTipStates, beagleSetTipPartials or
+ * beagleSetPartials on the tip drops the emission.  One emission per tip for the whole instance, whatever its pattern partitions.
+ * The sharded handle splits the codes by pattern and gives every shard the table.
+ * Errors: BEAGLE_ERROR_OUT_OF_RANGE for codeCount outside 1..255, a bad tip index, emission NULL, codes NULL on a tip without codes or
+ * with another codeCount than they came with; BEAGLE_ERROR_NO_IMPLEMENTATION on a BASTA instance. */
+int beagleMi355SetTipEmission(int instance, int tipIndex, const int* codes, int codeCount, const double* emission);
+/* out4 = {tips folded into their branch matrices now, tips written out as partials now, fold launches since creation, tips turned from
+ * the first kind into the second since creation} (shard 0 of a sharded handle). */
+int beagleMi355TipEmissionStats(int instance, long* out4);
 /* For the JNI shim: getPartials / getSiteLogLikelihoods whose result STAYS in the engine's pinned host buffer — *outPinned,
  * *outCount doubles, valid until the next call on the instance — so that it reaches the Java array with one copy
  * (Set<Type>ArrayRegion) instead of two.  BEAGLE_ERROR_NO_IMPLEMENTATION on the sharded instance: use the ordinary call. */
