@@ -32,7 +32,7 @@ int accumulate(Instance* in, const int* idx, int count, int cum, double sign, in
         if (same) {
             void* dRows = nullptr;
             rc = uploadTransient(in, in->lastSums.rows.data(), in->lastSums.rows.size() * sizeof(int), &dRows); if (rc) return rc;
-            mi355::launchAccumulateSlices(live(in), in->scale[cum], in->sliceMant, in->sliceExp, (const int*)dRows, (int)in->lastSums.rows.size(), in->pairLen,
+            mi355::launchAccumulateSlices(live(in), in->scale[cum], in->sliceMant.as<double>(), in->sliceExp.as<int>(), (const int*)dRows, (int)in->lastSums.rows.size(), in->pairLen,
                                           in->dPairPos, sign, pStart, pEnd);
             in->statSliceAccum++;
             HIP_TRY(hipGetLastError());

@@ -29,10 +29,10 @@ struct Basta {
     double* buffers = nullptr;                           // [bufferCount][maxIntervals * S]
     double* intervalLogL = nullptr;                      // [maxIntervals + 1] terms of the last accumulate, [maxIntervals]: their sum
     // the operation list and its intervals as last sent to the device
-    int* hOps = nullptr; int* dOps = nullptr; size_t opsCap = 0; int opCount = -1;
-    int* hIntervals = nullptr; int* dIntervals = nullptr; size_t intervalsCap = 0; int intervalCount = -1;
-    double* hLengths = nullptr; double* dLengths = nullptr; size_t lengthsCap = 0;
-    int* hLink = nullptr; int* dLink = nullptr; int* dLeaves = nullptr; unsigned* dTickets = nullptr; size_t linkCap = 0;   // (hLink: [2 n link | n leaves])
+    int* hOps = nullptr; DevBuf dOps; size_t opsCap = 0; int opCount = -1;
+    int* hIntervals = nullptr; DevBuf dIntervals; size_t intervalsCap = 0; int intervalCount = -1;
+    double* hLengths = nullptr; DevBuf dLengths; size_t lengthsCap = 0;
+    int* hLink = nullptr; DevBuf dLink, dTickets; size_t linkCap = 0;   // (hLink: [2 n link | n leaves])
     hipEvent_t sent = nullptr;                           // the last copy out of the pinned buffers
     std::vector<int> writer, writes, intervalOf;         // analyse()'s scratch
     long statUploads = 0, statChainCalls = 0, statIntervalCalls = 0;
@@ -50,23 +50,17 @@ int bastaInstance(int instance, Instance** out) {
     return 0;
 }
 
-void release(Instance* in, void* p, size_t bytes) {
-    if (!p) return;
-    in->allocations.erase(std::find(in->allocations.begin(), in->allocations.end(), p));
-    in->deviceBytes -= bytes;
-    hipFree(p);
-}
-
-// pinned host + device pair of at least `count` elements (grow-only; growing waits for the copies in flight)
-template <class T> int growPair(Instance* in, T*& h, T*& d, size_t& cap, size_t count) {
+// pinned host + device pair of at least `count` elements (grow-only; growing waits for the copies in flight).  `cap` is what both
+// halves hold; it stays 0 when either allocation fails, so the next call starts over
+template <class T> int growPair(Instance* in, T*& h, DevBuf& d, size_t& cap, size_t count) {
     if (cap >= count) return 0;
     HIP_TRY(hipStreamSynchronize(live(in)));
     if (h) hipHostFree(h);
-    release(in, d, cap * sizeof(T));
-    h = nullptr; d = nullptr; cap = 0;
+    releaseDevice(in, d);
+    h = nullptr; cap = 0;
     const size_t n = count + count / 4 + 64;
     HIP_TRY(hipHostMalloc((void**)&h, n * sizeof(T), hipHostMallocDefault));
-    int rc = devAlloc(in, (void**)&d, n * sizeof(T)); if (rc) return rc;
+    int rc = growDevice(in, d, n * sizeof(T), n * sizeof(T), Grow::SyncIfHeld); if (rc) return rc;
     cap = n;
     return 0;
 }
@@ -144,8 +138,8 @@ int sendList(Instance* in, Basta* b, const int* ops, int n, const int* intervals
     if (opInts) memcpy(b->hOps, ops, opInts * sizeof(int));
     memcpy(b->hIntervals, intervals, (size_t)intervalCount * sizeof(int));
     hipStream_t s = live(in);
-    if (opInts) HIP_TRY(hipMemcpyAsync(b->dOps, b->hOps, opInts * sizeof(int), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(b->dIntervals, b->hIntervals, (size_t)intervalCount * sizeof(int), hipMemcpyHostToDevice, s));
+    if (opInts) HIP_TRY(hipMemcpyAsync(b->dOps.p, b->hOps, opInts * sizeof(int), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(b->dIntervals.p, b->hIntervals, (size_t)intervalCount * sizeof(int), hipMemcpyHostToDevice, s));
     HIP_TRY(hipEventRecord(b->sent, s));
     b->opCount = n; b->intervalCount = intervalCount;
     b->statUploads++;
@@ -217,9 +211,7 @@ int beagleBastaAllocateCoalescentBuffers(int instance, int coalescentBufferCount
         HIP_TRY(hipMemcpyAsync(vectors, old->vectors, std::min(vBytes, (size_t)old->vectorCount * S * sizeof(double)), hipMemcpyDeviceToDevice, s));
     if (old) {
         HIP_TRY(hipStreamSynchronize(s));
-        release(in, old->vectors, (size_t)old->vectorCount * S * sizeof(double));
-        release(in, old->buffers, (size_t)old->bufferCount * old->maxIntervals * S * sizeof(double));
-        release(in, old->intervalLogL, ((size_t)old->maxIntervals + 1) * sizeof(double));
+        devFree(in, old->vectors); devFree(in, old->buffers); devFree(in, old->intervalLogL);
     }
     b->vectors = vectors; b->buffers = buffers; b->intervalLogL = terms;
     b->vectorCount = partialsBufferCount; b->maxIntervals = maxCoalescentIntervalCount; b->bufferCount = coalescentBufferCount;
@@ -244,13 +236,12 @@ int beagleBastaUpdatePartials(int instance, const int* operations, int operation
     if (b->linkCap < (size_t)3 * n + 1) {
         HIP_TRY(hipStreamSynchronize(live(in)));
         if (b->hLink) hipHostFree(b->hLink);
-        release(in, b->dLink, b->linkCap * sizeof(int));
-        release(in, b->dTickets, b->linkCap / 3 * sizeof(unsigned));
-        b->hLink = nullptr; b->dLink = nullptr; b->dTickets = nullptr; b->linkCap = 0;
+        releaseDevice(in, b->dLink); releaseDevice(in, b->dTickets);
+        b->hLink = nullptr; b->linkCap = 0;
         const size_t cap = 3 * ((size_t)n + n / 4 + 64);
         HIP_TRY(hipHostMalloc((void**)&b->hLink, cap * sizeof(int), hipHostMallocDefault));
-        rc = devAlloc(in, (void**)&b->dLink, cap * sizeof(int)); if (rc) return rc;
-        rc = devAlloc(in, (void**)&b->dTickets, cap / 3 * sizeof(unsigned)); if (rc) return rc;
+        rc = growDevice(in, b->dLink, cap * sizeof(int), cap * sizeof(int), Grow::SyncIfHeld); if (rc) return rc;
+        rc = growDevice(in, b->dTickets, cap / 3 * sizeof(unsigned), cap / 3 * sizeof(unsigned), Grow::SyncIfHeld); if (rc) return rc;
         b->linkCap = cap;
     }
     HIP_TRY(hipEventSynchronize(b->sent));
@@ -262,9 +253,9 @@ int beagleBastaUpdatePartials(int instance, const int* operations, int operation
     hipStream_t s = live(in);
     HIP_TRY(hipMemsetAsync(coalescent, 0, (size_t)b->maxIntervals * sizeof(double), s));
     if (forest) {
-        HIP_TRY(hipMemcpyAsync(b->dLink, b->hLink, (size_t)3 * n * sizeof(int), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(b->dLink.p, b->hLink, (size_t)3 * n * sizeof(int), hipMemcpyHostToDevice, s));
         HIP_TRY(hipEventRecord(b->sent, s));
-        HIP_TRY(hipMemsetAsync(b->dTickets, 0, (size_t)n * sizeof(unsigned), s));
+        HIP_TRY(hipMemsetAsync(b->dTickets.p, 0, (size_t)n * sizeof(unsigned), s));
     }
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (timeThisCall(in)) {
@@ -278,14 +269,14 @@ int beagleBastaUpdatePartials(int instance, const int* operations, int operation
     }
     int launches = 0;
     if (forest) {
-        mi355::launchBastaChains(s, b->dOps, b->dLink, b->dLink + (size_t)2 * n, nLeaves, b->dTickets, in->matrices, b->vectors, sizes, coalescent, in->S);
+        mi355::launchBastaChains(s, b->dOps.as<int>(), b->dLink.as<int>(), b->dLink.as<int>() + (size_t)2 * n, nLeaves, b->dTickets.as<unsigned>(), in->matrices, b->vectors, sizes, coalescent, in->S);
         launches = 1;
         b->statChainCalls++;
     } else {
         for (int t = 0; t + 1 < intervalCount; t++) {
             const int count = intervals[t + 1] - intervals[t];
             if (count <= 0) continue;
-            mi355::launchBastaInterval(s, b->dOps, intervals[t], count, in->matrices, b->vectors, sizes, coalescent, in->S);
+            mi355::launchBastaInterval(s, b->dOps.as<int>(), intervals[t], count, in->matrices, b->vectors, sizes, coalescent, in->S);
             launches++;
         }
         if (n > 0) b->statIntervalCalls++;
@@ -315,14 +306,14 @@ int beagleBastaAccumulatePartials(int instance, const int* operations, int opera
     HIP_TRY(hipEventSynchronize(b->sent));
     if (nIntervals) memcpy(b->hLengths, intervalLengths, (size_t)nIntervals * sizeof(double));
     hipStream_t s = live(in);
-    if (nIntervals) HIP_TRY(hipMemcpyAsync(b->dLengths, b->hLengths, (size_t)nIntervals * sizeof(double), hipMemcpyHostToDevice, s));
+    if (nIntervals) HIP_TRY(hipMemcpyAsync(b->dLengths.p, b->hLengths, (size_t)nIntervals * sizeof(double), hipMemcpyHostToDevice, s));
     HIP_TRY(hipEventRecord(b->sent, s));
     // e, f, g, h: the four lowest buffers that do not hold the coalescent probabilities
     double* efgh[4]; int at = 0;
     const size_t stride = (size_t)b->maxIntervals * in->S;
     for (int k = 0; k < b->bufferCount && at < 4; k++) if (k != coalescentProbabilityIndex) efgh[at++] = b->buffers + k * stride;
     double* total = b->intervalLogL + b->maxIntervals;
-    mi355::launchBastaReduce(s, b->dOps, b->dIntervals, nIntervals, b->dLengths, b->vectors,
+    mi355::launchBastaReduce(s, b->dOps.as<int>(), b->dIntervals.as<int>(), nIntervals, b->dLengths.as<double>(), b->vectors,
                              in->freqs + (size_t)populationSizesIndex * in->S, b->buffers + coalescentProbabilityIndex * stride,
                              efgh[0], efgh[1], efgh[2], efgh[3], b->intervalLogL, total, in->S);
     HIP_TRY(hipGetLastError());

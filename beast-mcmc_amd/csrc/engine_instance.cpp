@@ -16,12 +16,41 @@ Instance* lookup(int h) {
     return g_instances[h];
 }
 
-int devAlloc(Instance* in, void** p, size_t bytes) {
+// Every device allocation of an instance is made here and recorded in Instance::allocations, which is all destroy() needs to know.
+// `counted`: the bytes are part of deviceBytes (engine_internal.h DevBufUncounted says which are not, and why).
+int devAlloc(Instance* in, void** p, size_t bytes, bool counted) {
     HIP_TRY(hipMalloc(p, bytes));
-    in->allocations.push_back(*p);
-    in->deviceBytes += bytes;
+    in->allocations.push_back({*p, bytes, counted});
+    if (counted) in->deviceBytes += bytes;
     return 0;
 }
+
+void devFree(Instance* in, void* p) {
+    if (!p) return;
+    auto a = std::find_if(in->allocations.begin(), in->allocations.end(), [p](const Instance::DevBlock& x) { return x.p == p; });
+    if (a != in->allocations.end()) { if (a->counted) in->deviceBytes -= a->bytes; *a = in->allocations.back(); in->allocations.pop_back(); }
+    hipFree(p);
+}
+void releaseDevice(Instance* in, DevBuf& b) { devFree(in, b.p); b.p = nullptr; b.bytes = 0; }
+
+int growDevice(Instance* in, DevBuf& b, size_t need, size_t want, Grow how, bool* grew) {
+    if (grew) *grew = false;
+    if (b.bytes >= need) return 0;
+    if (how == Grow::SyncAndFree || (how == Grow::SyncIfHeld && b.p)) HIP_TRY(hipStreamSynchronize(live(in)));
+    if (how != Grow::KeepOld) devFree(in, b.p);          // (KeepOld: the old block stays on the list)
+    b.p = nullptr; b.bytes = 0;
+    int rc = devAlloc(in, (void**)&b.p, want, b.counted); if (rc) { b.p = nullptr; return rc; }
+    b.bytes = want;
+    if (grew) *grew = true;
+    return 0;
+}
+
+int ScopedDevice::alloc(size_t bytes) {
+    reset();
+    if (hipMalloc(&p, bytes) != hipSuccess) { p = nullptr; return BEAGLE_ERROR_OUT_OF_MEMORY; }
+    return 0;
+}
+void ScopedDevice::reset() { if (p) { hipStreamSynchronize(live(in)); hipFree(p); p = nullptr; } }
 
 // Stage `bytes` of host data into the pinned ring; returns the ring offset (or <0).  Wrapping first
 // drains the stream, so a region is never overwritten while a copy from it is still in flight.
@@ -178,17 +207,9 @@ void destroy(Instance* in) {
     if (in->emis) freeTipEmissions(in);
     if (in->comm) { if (in->stream) hipStreamSynchronize(in->stream); ncclCommDestroy(in->comm); in->comm = nullptr; }
     if (in->stream && in->stream != in->ownStream) hipStreamSynchronize(in->stream);
-    for (void* p : in->allocations) hipFree(p);
-    if (in->bigStage) hipFree(in->bigStage);
-    if (in->matStream) hipFree(in->matStream);
-    if (in->walkFlags) hipFree(in->walkFlags);
-    if (in->sliceMant) hipFree(in->sliceMant);
-    if (in->sliceExp) hipFree(in->sliceExp);
-    for (auto& b : in->repeatPool) if (b.dev) hipFree(b.dev);
+    for (const Instance::DevBlock& a : in->allocations) hipFree(a.p);      // all device memory: slabs, model arrays, every DevBuf
     if (in->repeatStage) hipHostFree(in->repeatStage);
-    for (auto& r : in->resolved) if (r.dProg) hipFree(r.dProg);
     for (int k = 0; k < 2; k++) {
-        if (in->exportDev[k]) hipFree(in->exportDev[k]);
         if (in->exportHost[k]) hipHostFree(in->exportHost[k]);
         if (in->exportEvent[k]) hipEventDestroy(in->exportEvent[k]);
     }

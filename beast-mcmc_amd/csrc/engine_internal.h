@@ -15,6 +15,12 @@
 // kernels on the instance's HIP stream.  Results are only observed at calculateRootLogLikelihoods / get*, so every other
 // call returns as soon as its work is enqueued (SURVEY 8b "Threading").
 //
+// Device memory: every allocation of an instance goes through devAlloc onto Instance::allocations — the partials / scale / tip-state
+// slabs, the model arrays and matrix blocks, the staging ring's mirror, fold vectors, the repeat arena and pool, BASTA's arrays, tip
+// emission tables and codes, and every grow-on-demand DevBuf (samplers, edge scratch, cherry tables, pre-order program, fold range
+// check, matrix stream, walk flags, slice sums, kept programs, export buffers).  destroy() frees that list.  Not on it: pinned host
+// memory, events, streams, and the per-call ScopedDevice temporaries.
+//
 // There is no CPU path in this library: with no visible MI355X beagleCreateInstance returns BEAGLE_ERROR_NO_RESOURCE.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -60,6 +66,24 @@ constexpr int GRADIENT_VIRT_DEFAULT = 1;   // ... and what it does leave unstore
 struct Basta;                              // engine_basta.cpp
 struct TipEmissions;                       // engine_tipemission.cpp
 
+// A device buffer an instance owns and grows on demand (growDevice / releaseDevice below).  Its block is on Instance::allocations like
+// every other device allocation, so destroy() frees it without knowing the field.
+struct DevBuf {
+    char* p = nullptr; size_t bytes = 0;
+    bool counted = true;                                 // its bytes are part of Instance::deviceBytes (beagleMi355DeviceBytes)
+    template <class T> T* as() const { return reinterpret_cast<T*>(p); }
+};
+// KNOWN DEFECT, kept on purpose: the buffers declared with this type were never added to deviceBytes (matStream, bigStage, walkFlags,
+// sliceMant / sliceExp, Resolved::dProg, exportDev), so beagleMi355DeviceBytes under-counts what a walk instance holds.  The figure is
+// a benchmark output and a test's reference; counting them is a change of behaviour and belongs to a pull request of its own.
+struct DevBufUncounted : DevBuf { DevBufUncounted() { counted = false; } };
+// what growing does with the block it replaces
+enum class Grow {
+    SyncAndFree,                                         // drain the instance's stream (on the first allocation too), free the old block, allocate
+    SyncIfHeld,                                          // the same, but a buffer that holds nothing yet is allocated without draining
+    KeepOld                                              // no synchronisation: work in flight may still read the old block, which stays on the
+};                                                       // allocation list until the instance is destroyed; the field points at the new one
+
 struct Instance {
     int device = 0;
     // 4 states: every operation list runs as ONE launch of the pattern-walk kernel (kernels_walk4.hip), programmed by the
@@ -75,7 +99,7 @@ struct Instance {
     // laid out partition by partition, each padded to whole blocks of 128 patterns (kernels.h WalkSeg), so that the assembly
     // loop runs whatever the caller's partition boundaries are; one partition: walkPairIndex(p).
     std::vector<unsigned> pairPos; size_t pairLen = 0; std::vector<int> padStart; unsigned* dPairPos = nullptr;
-    char* matStream = nullptr; size_t matStreamBytes = 0;   // walk instances: the matrix stream of the program being run (k_gatherMatrices)
+    DevBufUncounted matStream;                              // walk instances: the matrix stream of the program being run (k_gatherMatrices)
     uint8_t* dummyTips = nullptr; double* onesScale = nullptr;   // walk instances: all-missing states / all-one factors for the operands a
                                                                  // micro-operation does not use (the assembly loop loads them unconditionally)
     long statFastWalks = 0;
@@ -88,7 +112,7 @@ struct Instance {
         std::vector<int> sumRows, wroteScale;            // write-mode programs: the device slices that leave their product of factors behind, the scale buffers the program writes (Instance::lastSums)
         std::vector<const double*> cm; long fused = 0;   // fused cherries (kernels.h WK_CHERRY): per device micro-operation the cherry's two branch matrices (empty: none fused), their number
         long memReads = 0, tipReads = 0, scaleReads = 0, scaleWrites = 0, stored = 0;
-        char* dProg = nullptr; size_t dProgBytes = 0; bool dProgValid = false;    // the packed program, resident on the device
+        DevBufUncounted dProg; bool dProgValid = false;    // the packed program, resident on the device
         std::vector<int> folds;                          // folded reciprocal vectors the program reads (Instance::folds)
         long foldEpoch = -1;                             // scaleWriteEpoch those vectors were last checked against
         long noFoldTag = 0;                              // the plan whose folds left the safe range: resolved with per-node factors
@@ -113,7 +137,7 @@ struct Instance {
     std::vector<double*> foldFree;                       // vectors of a dropped cache generation, reused
     long scaleWriteEpoch = 0;                            // bumped by everything that writes (or re-lays) a per-node scale buffer
     bool foldScales = true;
-    unsigned long long* foldWorst = nullptr; size_t foldWorstCount = 0;      // device: k_foldReciprocals' range check
+    DevBuf foldWorst;                                    // device: k_foldReciprocals' range check, a word per fold of a launch
     long resolveEpoch = 0;                               // bumped when pattern ranges change
     // Repeated sub-patterns (planner.h RepeatIndex): in a cached read-mode full evaluation, a clade of compact tips that the
     // plan evaluates inside its consumer's program (a plain definition) and whose patterns fall into at most repeatMaxClasses classes is
@@ -161,7 +185,7 @@ struct Instance {
     } heldPre;
     double* preRootCopy = nullptr;                       // the held list's own copy of its root's pre-order partial
     uint8_t* preDummyStates = nullptr;                   // [P] "missing": what a descriptor's unused tip pointer points at
-    void* dPreProg = nullptr; size_t dPreProgBytes = 0;  // the walk's program on the device (grow-only)
+    DevBuf dPreProg;                                     // the walk's program on the device (grow-only)
     // which scale buffer a partials buffer's last operation divided it by (-1: none / unknown), and that buffer's version then: the
     // pre-order walk multiplies a step into an internal node by the reciprocal of exactly that factor (kernels_preorder4.hip) and
     // is refused when the scale buffer has been written since (beagleUpdatePartials, the scale-factor calls)
@@ -181,7 +205,7 @@ struct Instance {
     // node under one more tip, by descriptors of their own (half the bytes, slower: a descriptor costs a stage whatever it computes).
     // (the initialisers below are overwritten at creation)
     bool gradientVirtual = false; int gradientVirtualSteps = GRADIENT_VIRT_STEPS;
-    void* edgeScratch = nullptr; size_t edgeScratchBytes = 0;    // per-64-pattern derivative sums of the edges of one call (grow-only)
+    DevBuf edgeScratch;                                  // per-64-pattern derivative sums of the edges of one call (grow-only)
     bool preWalk = true;                                 // BEAGLE_MI355_NO_PRE_WALK=1 at creation: always write the pre-order partials
     bool fuseGradient = true;                            // BEAGLE_MI355_NO_FUSED_GRADIENT=1 at creation: operation by operation (A/B runs)
     // 16..20 states: operation lists without write-mode rescaling run as the walk's programs on the T32 layout (kernels_mfma.hip
@@ -220,7 +244,7 @@ struct Instance {
     long statRootFused = 0;
     long statFoldedVectors = 0, statFoldBuilds = 0;      // read-mode programs: folded reciprocal vectors in use / (re)builds of them (engine_walk.cpp)
     unsigned* rootCounter = nullptr;                     // device word of k_rootSite's last-workgroup sum (kernels.hip)
-    double* cherryTables = nullptr; size_t cherryTableBytes = 0;   // 21..64 states: column tables of a list's virtual cherries (grow-only)
+    DevBuf cherryTables;                                 // 21..64 states: column tables of a list's virtual cherries (grow-only)
     int holdSlots = 3;                                   // what the planner was given
     bool eigenComplex = false;                           // created with BEAGLE_FLAG_EIGEN_COMPLEX: eigenvalue arrays are [S real parts | S imaginary parts]
     bool strictWaits = true;                             // a stage's wait does not count on the previous stage's stores retiring behind its
@@ -229,18 +253,17 @@ struct Instance {
     bool cherry = false;                                 // T32 instance with <= 20 states: tip-tip nodes are not stored (kernels.h CherryDesc)
     long statCherries = 0;
     double hostPlanUs = 0, hostRunUs = 0, hostPrepUs = 0, hostPlanHitUs = 0, hostRunHitUs = 0; long hostCalls = 0, hostHits = 0; bool hostTrace = false, lastResolveMiss = false;   // BEAGLE_MI355_HOST_TIMING=1: where updatePartials spends host time
-    char* bigStage = nullptr; size_t bigStageBytes = 0;  // device staging for programs that do not fit the ring
+    DevBufUncounted bigStage;                            // device staging for programs that do not fit the ring
     // read-back (getPartials): API-layout export buffers on the device and a pinned bounce buffer on the host
-    double* exportDev[2] = {nullptr, nullptr}; double* exportHost[2] = {nullptr, nullptr}; size_t exportBytes = 0;   // two chunks in flight
+    DevBufUncounted exportDev[2]; double* exportHost[2] = {nullptr, nullptr}; size_t exportBytes = 0;   // two chunks in flight
     hipEvent_t exportEvent[2] = {nullptr, nullptr};
     // ancestral-state draws (beagleMi355SampleAncestralStates): states [rows][P] | categories [P] | error word, grown on demand
-    char* ancestralDev = nullptr; size_t ancestralBytes = 0;
+    DevBuf ancestralDev;
     // Markov jumps (beagleMi355SampleMarkovJumps): registers, tables, per-block row sums, totals, outJumps stage, grown on demand
-    char* jumpDev = nullptr; size_t jumpBytes = 0;
+    DevBuf jumpDev;
     // uniformized Markov jumps (beagleMi355SampleMarkovJumpsUniformized): R^n table, rows, registers, sums, counts, grown on demand;
     // the event list of the last call that asked for one
-    char* uniformDev = nullptr; size_t uniformBytes = 0;
-    char* eventDev = nullptr; size_t eventBytes = 0;
+    DevBuf uniformDev, eventDev;
     // BASTA structured coalescent (beagleBastaAllocateCoalescentBuffers, engine_basta.cpp): null on every other instance
     Basta* basta = nullptr;
     // tip error models (beagleMi355SetTipEmission, engine_tipemission.cpp): null on an instance that was never given an emission table
@@ -251,7 +274,8 @@ struct Instance {
     size_t partialsBytes = 0;
     std::vector<double*> partials;
     std::vector<uint8_t*> tipStates;
-    std::vector<void*> allocations;
+    struct DevBlock { void* p; size_t bytes; bool counted; };
+    std::vector<DevBlock> allocations;                   // every device allocation of the instance: what destroy() frees
     char* slabCur = nullptr; int slabLeft = 0;
     char* scaleSlabCur = nullptr; int scaleSlabLeft = 0;
     char* stateSlabCur = nullptr; int stateSlabLeft = 0;
@@ -290,7 +314,7 @@ struct Instance {
     // 4 states: every slice of a walk program in ONE launch (engine_walk.cpp runPlan): per (slice, pattern group) flag words the
     // workgroups signal and poll with the launch's epoch.  BEAGLE_MI355_NO_WALK_FUSION=1 at creation: one launch per wave of slices
     bool fuseWaves = true;
-    unsigned* walkFlags = nullptr; size_t walkFlagBytes = 0; unsigned walkEpoch = 0;
+    DevBufUncounted walkFlags; unsigned walkEpoch = 0;   // [flags | tickets], each half of it walkFlags.bytes / 2
     // ... or, when the slices of a program form a forest (every stored slice root has one reader: planner.h PlanSeg::next), with no
     // waiting at all: only the slices without dependencies get workgroups, and the workgroup that arrives last at a slice above runs it
     // (kernels_walk4.hip "tickets"; walkTickets: per (slice, pattern group) arrival counts, zero between launches, in the same
@@ -313,7 +337,7 @@ struct Instance {
     // node (kernels.hip k_accumulateSlices; config A, ALWAYS rescaling: 250 us and 0.8 GB per evaluation).  Anything else — another list, a
     // scale buffer written since (scaleWriteEpoch) — takes the general kernel.  BEAGLE_MI355_NO_SLICE_SUMS=1 at creation: always the general kernel.
     bool sliceSums = true;
-    double* sliceMant = nullptr; int* sliceExp = nullptr; size_t sliceRows = 0;
+    DevBufUncounted sliceMant, sliceExp; size_t sliceRows = 0;      // (doubles; ints)
     struct LastSums { bool valid = false; long epoch = -1, gen = 0; std::vector<int> rows; int nWritten = 0; } lastSums;
     std::vector<long> scaleGen, scaleSeen; long sliceGen = 0, seenCounter = 0, statSliceAccum = 0;
     long statTicketWalks = 0, statFlagWalks = 0, lastLaunchRows = 0, lastLaunchSlices = 0;      // (beagleMi355WalkLaunchInfo)
@@ -348,7 +372,12 @@ extern std::vector<Instance*> g_instances;
 Instance* lookup(int h);
 
 // ---- engine_instance.cpp: memory, staging, resources
-int devAlloc(Instance* in, void** p, size_t bytes);
+int devAlloc(Instance* in, void** p, size_t bytes, bool counted = true);
+void devFree(Instance* in, void* p);                     // a block devAlloc gave out, off the list; synchronising is the caller's business
+// at least `need` bytes in b: when it has to grow it allocates `want` (>= need) and deals with the old block as `how` says.
+// *grew (nullable): the buffer's address changed.  A failed allocation leaves b empty, never half-set.
+int growDevice(Instance* in, DevBuf& b, size_t need, size_t want, Grow how, bool* grew = nullptr);
+void releaseDevice(Instance* in, DevBuf& b);             // (synchronising is the caller's business)
 long stage(Instance* in, const void* src, size_t bytes, size_t reserve = 0);
 int upload(Instance* in, void* dst, const void* src, size_t bytes);
 int uploadTransient(Instance* in, const void* src, size_t bytes, void** dptr);
@@ -402,6 +431,18 @@ struct KeepWalkHeld {
     GET_INSTANCE_KEEP_PENDING(h)                                 \
     if (in->heldPre.held) { const int rcPending__ = executeHeldPre(in); if (rcPending__) return rcPending__; }
 
+// A device temporary of one call: drains the instance's stream and frees the block when it leaves scope, on every exit path.  Not on
+// the allocation list and not counted — it never outlives the call.
+struct ScopedDevice {
+    Instance* in; void* p = nullptr;
+    explicit ScopedDevice(Instance* i) : in(i) {}
+    ScopedDevice(const ScopedDevice&) = delete; ScopedDevice& operator=(const ScopedDevice&) = delete;
+    int alloc(size_t bytes);                             // BEAGLE_ERROR_OUT_OF_MEMORY when there is none
+    template <class T> T* as() const { return static_cast<T*>(p); }
+    void reset();
+    ~ScopedDevice() { reset(); }
+};
+
 inline bool badIndex(int i, int n) { return i < 0 || i >= n; }
 
 // ---- engine_tipemission.cpp: tips whose partials are a lookup E[code][state].  With K <= S codes such a tip stays a
@@ -413,7 +454,7 @@ struct TipEmission {
     bool folded = false;                                 // route 1 (K <= S and no caller has needed the partials since the codes came); otherwise expanded
     std::vector<uint8_t> codes;                          // [P], 255 = outside the table (missing)
     std::vector<double> table;                           // [K][S] as the caller gave it
-    double* dTable = nullptr; size_t dTableDoubles = 0;  // ... on the device
+    DevBuf dTable;                                       // ... on the device (doubles)
     uint8_t* dCodes = nullptr; bool codesOnDevice = false;      // expanded tips: the codes on the device
 };
 struct TipEmissions {

@@ -223,17 +223,9 @@ int runOperationsLevels(Instance* in, const int* ops, int count, int tuple, int 
         dCherries = (const mi355::CherryDesc*)dC;
         if (in->S > 20) {                                // 21..64 states: the cherries' matrices as column tables in global memory
             const size_t bytes = mi355::cherryTableBytes((int)cherries.size(), in->S, in->C);
-            if (bytes > in->cherryTableBytes) {
-                HIP_TRY(hipStreamSynchronize(live(in)));
-                if (in->cherryTables) {
-                    for (auto& a : in->allocations) if (a == (void*)in->cherryTables) { a = in->allocations.back(); in->allocations.pop_back(); break; }
-                    hipFree(in->cherryTables); in->deviceBytes -= in->cherryTableBytes; in->cherryTables = nullptr; in->cherryTableBytes = 0;
-                }
-                void* q = nullptr; rc = devAlloc(in, &q, bytes + bytes / 4); if (rc) return rc;
-                in->cherryTables = (double*)q; in->cherryTableBytes = bytes + bytes / 4;
-            }
-            mi355::launchCherryTables(live(in), dCherries, (int)cherries.size(), in->matrices, in->S, in->C, in->cherryTables);
-            dCherryTables = in->cherryTables;
+            rc = growDevice(in, in->cherryTables, bytes, bytes + bytes / 4, Grow::SyncAndFree); if (rc) return rc;
+            dCherryTables = in->cherryTables.as<double>();
+            mi355::launchCherryTables(live(in), dCherries, (int)cherries.size(), in->matrices, in->S, in->C, in->cherryTables.as<double>());
         }
     }
     // ONE descriptor upload for the whole list (every extra copy is a dependent blit kernel between two

@@ -34,13 +34,15 @@ static int nodeHeightDerivatives(Instance* in, const int* nodes, const double* r
     const size_t productDoubles = general ? mi355::nodeHeightProductDoubles(1, in->S, in->C) : 0;
     if (general) chunk = std::min(chunk, std::max<size_t>(1, ((size_t)128 << 20) / (productDoubles * sizeof(double))));
     int rc = ensureEdgeScratch(in, chunk * (size_t)(nb + 1) * 2 * sizeof(double)); if (rc) return rc;
-    double *dBlock = (double*)in->edgeScratch, *dSums = dBlock + chunk * nb * 2, *dProducts = nullptr;
-    if (general && hipMalloc((void**)&dProducts, chunk * productDoubles * sizeof(double)) != hipSuccess) return BEAGLE_ERROR_OUT_OF_MEMORY;
+    double *dBlock = in->edgeScratch.as<double>(), *dSums = dBlock + chunk * nb * 2;
+    ScopedDevice products(in);                                      // (the general kernel's; freed, behind a drained stream, wherever the call ends)
+    if (general) { rc = products.alloc(chunk * productDoubles * sizeof(double)); if (rc) return rc; }
+    double* const dProducts = products.as<double>();
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (timeThisCall(in)) {
         if (in->eventsUsed == in->events.size()) {
             hipEvent_t a = nullptr, b = nullptr;
-            if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) { if (dProducts) hipFree(dProducts); return BEAGLE_ERROR_GENERAL; }
+            if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) return BEAGLE_ERROR_GENERAL;
             in->events.emplace_back(a, b);
         }
         e0 = in->events[in->eventsUsed].first; e1 = in->events[in->eventsUsed].second; in->eventsUsed++;
@@ -90,7 +92,7 @@ static int nodeHeightDerivatives(Instance* in, const int* nodes, const double* r
         }
     }
     if (e1) { in->eventsUsed--; in->timedCalls--; }                 // the call failed before its last launch: give the event pair back
-    if (dProducts) { hipStreamSynchronize(live(in)); hipFree(dProducts); }
+    products.reset();
     if (rc) return rc;
     if (hipGetLastError() != hipSuccess) return BEAGLE_ERROR_GENERAL;
     return finite ? BEAGLE_SUCCESS : BEAGLE_ERROR_FLOATING_POINT;

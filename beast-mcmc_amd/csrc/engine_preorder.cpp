@@ -27,16 +27,7 @@ int ensurePreScratch(Instance* in) {
 
 // the block sums of the derivative calls: kept between calls (hipMalloc/hipFree per call cost more than the small trees' kernels)
 int ensureEdgeScratch(Instance* in, size_t bytes) {
-    if (bytes <= in->edgeScratchBytes) return 0;
-    HIP_TRY(hipStreamSynchronize(live(in)));
-    if (in->edgeScratch) {
-        for (auto& a : in->allocations) if (a == in->edgeScratch) { a = in->allocations.back(); in->allocations.pop_back(); break; }
-        hipFree(in->edgeScratch); in->deviceBytes -= in->edgeScratchBytes; in->edgeScratch = nullptr; in->edgeScratchBytes = 0;
-    }
-    bytes = (bytes * 5 / 4 + 4095) & ~(size_t)4095;
-    int rc = devAlloc(in, &in->edgeScratch, bytes); if (rc) return rc;
-    in->edgeScratchBytes = bytes;
-    return 0;
+    return growDevice(in, in->edgeScratch, bytes, (bytes * 5 / 4 + 4095) & ~(size_t)4095, Grow::SyncAndFree);
 }
 
 int preLevelTwoPass(Instance* in, const OpDesc* ops, int nOps) {
@@ -502,7 +493,7 @@ static int fusedGradient(Instance* in, const std::vector<int>& edgeOf, const int
     std::vector<mi355::PreNodeJob> jobs; std::vector<int> start;
     heldJobs(in, edgeOf.data(), dIdx, jobs, start);
     int rc = ensureEdgeScratch(in, (size_t)count * (nb + 1) * 2 * sizeof(double)); if (rc) return rc;
-    double *dBlock = (double*)in->edgeScratch, *dSums = dBlock + (size_t)count * nb * 2;
+    double *dBlock = in->edgeScratch.as<double>(), *dSums = dBlock + (size_t)count * nb * 2;
     in->heldPre.held = false;                                      // (whatever happens below, the destinations are being written)
     rc = launchHeldLevels(in, jobs, start, wIdx, dBlock); if (rc) return rc;
     std::vector<double> sums((size_t)count * 2);
@@ -654,17 +645,16 @@ static int walkedGradient(Instance* in, const std::vector<int>& edgeOf, const in
     const size_t segBytes = ((size_t)nSegs * sizeof(mi355::PreWalkSeg) + 255) & ~(size_t)255;
     const size_t progBytes = prog.size() * sizeof(mi355::PreWalkOp);
     if (progBytes + segBytes > RING_BYTES / 2) return 1;
-    if (progBytes + segBytes > in->dPreProgBytes) {
-        HIP_TRY(hipStreamSynchronize(live(in)));
-        void* q = nullptr; int rc = devAlloc(in, &q, (progBytes + segBytes) * 2); if (rc) return rc;   // (the old, smaller one stays allocated until the instance goes)
-        in->dPreProg = q; in->dPreProgBytes = (progBytes + segBytes) * 2;
+    if (progBytes + segBytes > in->dPreProg.bytes) {
+        HIP_TRY(hipStreamSynchronize(live(in)));           // (this site drains although it keeps the old block: what is queued goes out first)
+        int rc = growDevice(in, in->dPreProg, progBytes + segBytes, (progBytes + segBytes) * 2, Grow::KeepOld); if (rc) return rc;
     }
     const size_t outPad = (outBytes + 255) & ~(size_t)255, prodBytes = (size_t)(count + 1) * in->C * 16 * sizeof(double), pairBytes = pairs.size() * sizeof(int);
     const size_t pairPad = (pairBytes + 255) & ~(size_t)255, nCherries = cherryPairs.size() / 2;
     const size_t cherryBytes = nCherries * in->C * 32 * sizeof(double), cherryPairBytes = cherryPairs.size() * sizeof(int);
     const size_t sumPad = (sumBytes + 255) & ~(size_t)255;              // (what follows the sums keeps a 256-byte alignment: 16-byte loads)
     int rc = ensureEdgeScratch(in, sumPad + outPad + prodBytes + pairPad + cherryBytes + cherryPairBytes); if (rc) return rc;
-    double *dSums = (double*)in->edgeScratch, *dOut = (double*)((char*)in->edgeScratch + sumPad), *dProducts = (double*)((char*)in->edgeScratch + sumPad + outPad);
+    double *dSums = in->edgeScratch.as<double>(), *dOut = (double*)(in->edgeScratch.p + sumPad), *dProducts = (double*)(in->edgeScratch.p + sumPad + outPad);
     int* dPairs = (int*)((char*)dProducts + prodBytes);
     double* dCherries = (double*)((char*)dPairs + pairPad);
     int* dCherryPairs = (int*)((char*)dCherries + cherryBytes);
@@ -678,9 +668,9 @@ static int walkedGradient(Instance* in, const std::vector<int>& edgeOf, const in
             (cherryRefs[k].which ? d.postB : d.postA) = dCherries + k * (size_t)in->C * 32;
         }
     }
-    rc = upload(in, in->dPreProg, segs.data(), (size_t)nSegs * sizeof(mi355::PreWalkSeg)); if (rc) return rc;
-    rc = upload(in, (char*)in->dPreProg + segBytes, prog.data(), progBytes); if (rc) return rc;
-    if (!mi355::launchPreWalk4(live(in), (const mi355::PreWalkOp*)((char*)in->dPreProg + segBytes), (const mi355::PreWalkSeg*)in->dPreProg, nSegs,
+    rc = upload(in, in->dPreProg.p, segs.data(), (size_t)nSegs * sizeof(mi355::PreWalkSeg)); if (rc) return rc;
+    rc = upload(in, in->dPreProg.p + segBytes, prog.data(), progBytes); if (rc) return rc;
+    if (!mi355::launchPreWalk4(live(in), (const mi355::PreWalkOp*)(in->dPreProg.p + segBytes), in->dPreProg.as<const mi355::PreWalkSeg>(), nSegs,
                                in->preRootCopy, in->matrices, dProducts, in->weights + (size_t)wIdx * in->C, in->patternWeights, dSums, in->P, in->C, h.holdSlots, anyPost)) return 1;
     if (in->hostTrace) fprintf(stderr, "[mi355] pre-order walk: %d segments, %zu descriptors, %d hold slots (%zu KB of LDS per workgroup)\n", nSegs, prog.size(), h.holdSlots,
                                (size_t)(h.holdSlots + (anyPost ? mi355::PW_POST_SLOTS : 0)) * in->C * 2);
@@ -721,8 +711,10 @@ int edgeDifferentials(Instance* in, const int* postIdx, const int* preIdx, const
     int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)count, ((size_t)256 << 20) / perEdgeBytes));
     chunk = std::min(chunk, 32768);
     int rc = ensureEdgeScratch(in, (size_t)chunk * (nb + 1) * 2 * sizeof(double)); if (rc) return rc;
-    double *dBlock = (double*)in->edgeScratch, *dSums = dBlock + (size_t)chunk * nb * 2, *dPer = nullptr;
-    if (outDerivatives && hipMalloc((void**)&dPer, (size_t)chunk * in->P * sizeof(double)) != hipSuccess) rc = BEAGLE_ERROR_OUT_OF_MEMORY;
+    double *dBlock = in->edgeScratch.as<double>(), *dSums = dBlock + (size_t)chunk * nb * 2;
+    ScopedDevice per(in);                                  // the per-pattern derivatives of a chunk
+    if (outDerivatives) rc = per.alloc((size_t)chunk * in->P * sizeof(double));
+    double* const dPer = per.as<double>();
     std::vector<mi355::EdgeDesc> descs;
     std::vector<double> sums;
     static const bool preNaive = labEnv("BEAGLE_MI355_PRE_NAIVE") && atoi(labEnv("BEAGLE_MI355_PRE_NAIVE")) != 0;
@@ -800,7 +792,6 @@ int edgeDifferentials(Instance* in, const int* postIdx, const int* preIdx, const
         }
         if (outDerivatives) rc = download(in, outDerivatives + (size_t)b * in->P, dPer, (size_t)m * in->P * sizeof(double));
     }
-    if (dPer) { hipStreamSynchronize(live(in)); hipFree(dPer); }
     return rc;
 }
 
@@ -826,11 +817,11 @@ int crossProducts(Instance* in, const int* postIdx, const int* preIdx, int rateI
     }
     const size_t nOut = (size_t)in->S * in->S;
     const int nb = mi355::edgeBlocks(in->P);
-    double *dPartial = nullptr, *dOut = nullptr;
-    HIP_TRY(hipMalloc((void**)&dPartial, (size_t)nb * nOut * sizeof(double)));
-    if (hipMalloc((void**)&dOut, nOut * sizeof(double)) != hipSuccess) { hipFree(dPartial); return BEAGLE_ERROR_OUT_OF_MEMORY; }
+    ScopedDevice partial(in), out(in);
+    int rc = partial.alloc((size_t)nb * nOut * sizeof(double)); if (rc) return rc;
+    rc = out.alloc(nOut * sizeof(double)); if (rc) return rc;
+    double *dPartial = partial.as<double>(), *dOut = out.as<double>();
     std::vector<double> sums(nOut);
-    int rc = 0;
     const size_t maxChunk = (RING_BYTES / 8) / sizeof(mi355::EdgeDesc);
     for (size_t b = 0; b < (size_t)count && !rc; b += maxChunk) {
         const size_t n = std::min(maxChunk, (size_t)count - b);
@@ -842,8 +833,6 @@ int crossProducts(Instance* in, const int* postIdx, const int* preIdx, int rateI
         rc = download(in, sums.data(), dOut, nOut * sizeof(double)); if (rc) break;
         for (size_t k = 0; k < nOut; k++) outSum[k] += sums[k];
     }
-    hipStreamSynchronize(live(in));
-    hipFree(dPartial); hipFree(dOut);
     return rc;
 }
 

@@ -44,13 +44,13 @@ static int exportPartials(Instance* in, const int* bufferIndices, const int* sca
     if (in->exportBytes < chunk * bytes) {
         HIP_TRY(hipStreamSynchronize(live(in)));
         for (int k = 0; k < 2; k++) {
-            if (in->exportDev[k]) hipFree(in->exportDev[k]);
+            releaseDevice(in, in->exportDev[k]);
             if (in->exportHost[k]) hipHostFree(in->exportHost[k]);
-            in->exportDev[k] = nullptr; in->exportHost[k] = nullptr;
+            in->exportHost[k] = nullptr;
         }
-        in->exportBytes = 0;
+        in->exportBytes = 0;                               // (a failure below leaves it so: the next call starts over)
         for (int k = 0; k < 2; k++) {
-            HIP_TRY(hipMalloc((void**)&in->exportDev[k], chunk * bytes));
+            int rc = growDevice(in, in->exportDev[k], chunk * bytes, chunk * bytes, Grow::SyncIfHeld); if (rc) return rc;
             HIP_TRY(hipHostMalloc((void**)&in->exportHost[k], chunk * bytes, hipHostMallocDefault));
             if (!in->exportEvent[k]) HIP_TRY(hipEventCreateWithFlags(&in->exportEvent[k], hipEventDisableTiming));
         }
@@ -71,9 +71,9 @@ static int exportPartials(Instance* in, const int* bufferIndices, const int* sca
                 int rc = ensureScale(in, scaleIndices[c * chunk + k]); if (rc) return rc;
                 sc = in->scale[scaleIndices[c * chunk + k]]; raw = in->scaleIsRaw[scaleIndices[c * chunk + k]];
             }
-            mi355::launchExportPartials(live(in), in->partials[b], sc, raw, in->exportDev[w] + k * elems, in->P, in->S, in->C, in->tiled);
+            mi355::launchExportPartials(live(in), in->partials[b], sc, raw, in->exportDev[w].as<double>() + k * elems, in->P, in->S, in->C, in->tiled);
         }
-        HIP_TRY(hipMemcpyAsync(in->exportHost[w], in->exportDev[w], n * bytes, hipMemcpyDeviceToHost, live(in)));
+        HIP_TRY(hipMemcpyAsync(in->exportHost[w], in->exportDev[w].p, n * bytes, hipMemcpyDeviceToHost, live(in)));
         HIP_TRY(hipEventRecord(in->exportEvent[w], live(in)));
         if (c >= 1 && out) {                               // chunk c - 1 has landed (or lands while this one is being produced)
             HIP_TRY(hipEventSynchronize(in->exportEvent[1 - w]));

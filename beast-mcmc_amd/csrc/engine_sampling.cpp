@@ -7,20 +7,8 @@
 
 using namespace mi355::eng;
 
-// Grow-only device scratch of an instance (ancestral draws, Markov jumps): at least `need` bytes, counted in deviceBytes.
-static int growScratch(Instance* in, char*& buf, size_t& bytes, size_t need) {
-    if (bytes >= need) return 0;
-    if (buf) {
-        HIP_TRY(hipStreamSynchronize(live(in)));
-        in->allocations.erase(std::find(in->allocations.begin(), in->allocations.end(), (void*)buf));
-        in->deviceBytes -= bytes;
-        hipFree(buf);
-        buf = nullptr; bytes = 0;
-    }
-    int rc = devAlloc(in, (void**)&buf, need); if (rc) return rc;
-    bytes = need;
-    return 0;
-}
+// Grow-only device scratch of an instance (ancestral draws, Markov jumps): exactly `need` bytes when it grows, counted in deviceBytes.
+static int growScratch(Instance* in, DevBuf& b, size_t need) { return growDevice(in, b, need, need, Grow::SyncIfHeld); }
 
 // Where a device-side draw left its results (in->ancestralDev): states [rows][P] | categories [P] | error word.
 struct AncestralDraw { uint8_t* states; int* cats; unsigned* error; };
@@ -53,9 +41,9 @@ static int drawAncestral(Instance* in, const int* nodes, int nodeCount, int wIdx
     }
     const size_t stateBytes = ((size_t)nodeCount * in->P + 255) & ~(size_t)255;
     const size_t tailBytes = (size_t)in->P * sizeof(int) + sizeof(unsigned);
-    int rc = growScratch(in, in->ancestralDev, in->ancestralBytes, stateBytes + tailBytes); if (rc) return rc;
-    d->states = (uint8_t*)in->ancestralDev;
-    d->cats = (int*)(in->ancestralDev + stateBytes);
+    int rc = growScratch(in, in->ancestralDev, stateBytes + tailBytes); if (rc) return rc;
+    d->states = in->ancestralDev.as<uint8_t>();
+    d->cats = (int*)(in->ancestralDev.p + stateBytes);
     d->error = (unsigned*)(d->cats + in->P);
     void* dRows = nullptr;
     rc = uploadTransient(in, rows.data(), rows.size() * sizeof(mi355::AncestralRow), &dRows); if (rc) return rc;
@@ -146,8 +134,8 @@ static int sampleJumps(Instance* in, const int* nodes, int nodeCount, const doub
     const size_t nReg = (size_t)K * SS, nCond = (size_t)K * R * C * SS, nPart = blocks * K * R, nRow = (size_t)K * R,
                  nPat = (size_t)K * P, nStage = (size_t)K * stageRows * P;
     const size_t doubles = 4 * nReg + nCond + nPart + nRow + nPat + nStage;
-    rc = growScratch(in, in->jumpDev, in->jumpBytes, doubles * sizeof(double) + mi355::MAX_JUMP_REGISTERS * sizeof(int)); if (rc) return rc;
-    double* dReg = (double*)in->jumpDev;
+    rc = growScratch(in, in->jumpDev, doubles * sizeof(double) + mi355::MAX_JUMP_REGISTERS * sizeof(int)); if (rc) return rc;
+    double* dReg = in->jumpDev.as<double>();
     double* dRateReg = dReg + nReg;
     double* dTmp = dRateReg + nReg;
     double* dM = dTmp + nReg;
@@ -329,8 +317,8 @@ static int uniformRun(Instance* in, const int* nodes, int nodeCount, const doubl
     const size_t oLong = oFlags + up(mi355::MAX_JUMP_REGISTERS * sizeof(int));
     const size_t oCounts = oLong + up(((size_t)P + 2) * sizeof(long long));
     const size_t bytes = oCounts + (history ? Rn * P * sizeof(int) : 0);
-    rc = growScratch(in, in->uniformDev, in->uniformBytes, bytes); if (rc) return rc;
-    char* base = in->uniformDev;
+    rc = growScratch(in, in->uniformDev, bytes); if (rc) return rc;
+    char* base = in->uniformDev.p;
     double* dTable = (double*)base;
     double* dReg = dTable + nTable;
     double* dPart = dReg + nReg;
@@ -411,10 +399,10 @@ static int uniformEvents(Instance* in, UniformPass* pass, double* outHeights, un
     if (pass->events == 0) return 0;
     const size_t n = (size_t)pass->events;
     const size_t stBytes = (2 * n + 255) & ~(size_t)255;
-    int rc = growScratch(in, in->eventDev, in->eventBytes, stBytes + n * sizeof(double)); if (rc) return rc;
+    int rc = growScratch(in, in->eventDev, stBytes + n * sizeof(double)); if (rc) return rc;
     mi355::UniformSiteArgs a = pass->args;
-    a.eventStates = (uint8_t*)in->eventDev;
-    a.eventHeights = (double*)(in->eventDev + stBytes);
+    a.eventStates = in->eventDev.as<uint8_t>();
+    a.eventHeights = (double*)(in->eventDev.p + stBytes);
     for (int r0 = 0; r0 < a.nRows; r0 += 65535)
         mi355::launchUniformSites(live(in), a, r0, std::min(a.nRows, r0 + 65535), true);
     HIP_TRY(hipGetLastError());

@@ -45,11 +45,8 @@ void dropTipEmission(Instance* in, int tip) {
 
 static int uploadTable(Instance* in, TipEmission& t) {
     const size_t n = (size_t)t.K * in->S;
-    if (n > t.dTableDoubles) {
-        int rc = devAlloc(in, (void**)&t.dTable, n * sizeof(double)); if (rc) return rc;      // (a smaller one stays owned by the instance)
-        t.dTableDoubles = n;
-    }
-    return upload(in, t.dTable, t.table.data(), n * sizeof(double));      // K S doubles through the pinned ring
+    int rc = growDevice(in, t.dTable, n * sizeof(double), n * sizeof(double), Grow::KeepOld); if (rc) return rc;
+    return upload(in, t.dTable.p, t.table.data(), n * sizeof(double));      // K S doubles through the pinned ring
 }
 
 // the tip's partials buffer from its codes and table: what beagleSetTipPartials leaves behind
@@ -61,7 +58,7 @@ static int expandTip(Instance* in, int tip) {
     rc = ensurePartials(in, tip); if (rc) return rc;
     if (!t.dCodes) { rc = devAlloc(in, (void**)&t.dCodes, ((size_t)in->P + 255) & ~(size_t)255); if (rc) return rc; }
     if (!t.codesOnDevice) { rc = upload(in, t.dCodes, t.codes.data(), (size_t)in->P); if (rc) return rc; t.codesOnDevice = true; }
-    mi355::launchExpandTipEmission(live(in), in->partials[tip], t.dCodes, t.dTable, t.K, in->P, in->S, in->C, in->tiled);
+    mi355::launchExpandTipEmission(live(in), in->partials[tip], t.dCodes, t.dTable.as<double>(), t.K, in->P, in->S, in->C, in->tiled);
     HIP_TRY(hipGetLastError());
     in->tipStates[tip] = nullptr;                          // the buffer holds partials now (the state slab stays owned by the instance)
     setCompact(in, tip, false);
@@ -111,7 +108,7 @@ int foldTipOperations(Instance* in, const int** opsInOut, int count, int tuple) 
                     E.useStamp[(size_t)m] = stamp; E.useOf[(size_t)m] = user;
                     if (user != OTHER) {
                         const TipEmission& t = E.tips[(size_t)c];
-                        E.jobs.push_back(mi355::TipFoldJob{m, E.shadowBase + m, t.K, 0, t.dTable});
+                        E.jobs.push_back(mi355::TipFoldJob{m, E.shadowBase + m, t.K, 0, t.dTable.as<double>()});
                     }
                 } else if (E.useOf[(size_t)m] != user) { E.useOf[(size_t)m] = -3; conflict = true; }
             }

@@ -65,12 +65,9 @@ static int refreshFolds(Instance* in, const std::vector<int>& ids, bool* anyBad)
             dst.push_back(f.recip);
         }
         start.push_back((int)srcs.size());
-        if (in->foldWorstCount < stale.size()) {
-            const size_t want = std::max<size_t>(stale.size() + stale.size() / 2, 256);
-            int rc = devAlloc(in, (void**)&in->foldWorst, want * sizeof(unsigned long long)); if (rc) return rc;
-            in->foldWorstCount = want;
-        }
-        HIP_TRY(hipMemsetAsync(in->foldWorst, 0, stale.size() * sizeof(unsigned long long), live(in)));
+        { int rc = growDevice(in, in->foldWorst, stale.size() * sizeof(unsigned long long),
+                              std::max<size_t>(stale.size() + stale.size() / 2, 256) * sizeof(unsigned long long), Grow::KeepOld); if (rc) return rc; }
+        HIP_TRY(hipMemsetAsync(in->foldWorst.p, 0, stale.size() * sizeof(unsigned long long), live(in)));
         const int chunk = 2048;                             // (jobs per launch: their pointer lists go through the staging ring)
         for (size_t b = 0; b < stale.size(); b += chunk) {
             const size_t e = std::min(stale.size(), b + chunk);
@@ -82,11 +79,11 @@ static int refreshFolds(Instance* in, const std::vector<int>& ids, bool* anyBad)
             rc = uploadTransient(in, st.data(), st.size() * sizeof(int), &dStart); if (rc) return rc;
             rc = uploadTransient(in, dst.data() + b, (e - b) * sizeof(double*), &dDst); if (rc) return rc;
             mi355::launchFoldReciprocals(live(in), (const double* const*)dSrcs, (const int*)dStart, (double* const*)dDst, (int)(e - b),
-                                         in->walkT ? in->P : (int)in->pairLen, in->foldWorst + b, in->walkT);
+                                         in->walkT ? in->P : (int)in->pairLen, in->foldWorst.as<unsigned long long>() + b, in->walkT);
         }
         HIP_TRY(hipGetLastError());
         std::vector<unsigned long long> worst(stale.size());
-        int rc = download(in, worst.data(), in->foldWorst, worst.size() * sizeof(unsigned long long)); if (rc) return rc;
+        int rc = download(in, worst.data(), in->foldWorst.p, worst.size() * sizeof(unsigned long long)); if (rc) return rc;
         for (size_t k = 0; k < stale.size(); k++) {
             double v; memcpy(&v, &worst[k], sizeof(v));
             in->folds[(size_t)stale[k]].bad = !(v <= FOLD_SAFE_MAX);
@@ -139,8 +136,7 @@ static Instance::RepeatTable* repeatTableFor(Instance* in, int clade, bool* full
     if (!blk) {
         Instance::RepeatBlock b;
         b.size = std::max(t.bytes, std::min<size_t>((size_t)16 << 20, expect * t.bytes));
-        if (hipMalloc((void**)&b.dev, b.size) != hipSuccess) { in->repeatRows = before; return nullptr; }
-        in->deviceBytes += b.size;
+        if (devAlloc(in, (void**)&b.dev, b.size)) { in->repeatRows = before; return nullptr; }
         in->repeatPool.push_back(b);
         blk = &in->repeatPool.back();
     }
@@ -340,13 +336,12 @@ int runPlan(Instance* in, const mi355::Plan& plan, long planTag, hipEvent_t reco
     std::vector<int>& wroteScale = slot ? slot->wroteScale : wroteLocal;
     sumRows.clear(); wroteScale.clear();
     if (sums && in->sliceRows < plan.segs.size()) {
+        // (both go whatever they hold: sliceRows is 0 after a change of the pair layout, and a failure below leaves it 0 — the next call starts over)
         HIP_TRY(hipStreamSynchronize(live(in)));
-        if (in->sliceMant) hipFree(in->sliceMant);
-        if (in->sliceExp) hipFree(in->sliceExp);
-        in->sliceMant = nullptr; in->sliceExp = nullptr; in->sliceRows = 0;
-        const size_t rows = plan.segs.size() + plan.segs.size() / 2 + 8;
-        HIP_TRY(hipMalloc((void**)&in->sliceMant, rows * in->pairLen * sizeof(double)));
-        HIP_TRY(hipMalloc((void**)&in->sliceExp, rows * in->pairLen * sizeof(int)));
+        releaseDevice(in, in->sliceMant); releaseDevice(in, in->sliceExp); in->sliceRows = 0;
+        const size_t rows = plan.segs.size() + plan.segs.size() / 2 + 8, cells = rows * in->pairLen;
+        int rcs = growDevice(in, in->sliceMant, cells * sizeof(double), cells * sizeof(double), Grow::SyncIfHeld); if (rcs) return rcs;
+        rcs = growDevice(in, in->sliceExp, cells * sizeof(int), cells * sizeof(int), Grow::SyncIfHeld); if (rcs) return rcs;
         in->sliceRows = rows;
         in->resolveEpoch++;
         in->lastSums.valid = false;
@@ -503,8 +498,8 @@ int runPlan(Instance* in, const mi355::Plan& plan, long planTag, hipEvent_t reco
         segs[si].progCount = (int)w.size() - segs[si].progStart;
         for (int q = 0; q < (asmLoop ? 3 : 2); q++) w.push_back(nop);
         if (sums && !sumRows.empty() && sumRows.back() == (int)si) {      // (this slice writes factors: where its product of them goes)
-            w.back().scaleW = in->sliceMant + si * in->pairLen;
-            w.back().store = (double*)(in->sliceExp + si * in->pairLen);
+            w.back().scaleW = in->sliceMant.as<double>() + si * in->pairLen;
+            w.back().store = (double*)(in->sliceExp.as<int>() + si * in->pairLen);
         }
         // the wait of every stage: "at most N vector-memory instructions outstanding".  Loads and stores share the counter.
         // DEFAULT (strict): N = the LOADS issued behind this micro-operation's own.  Sufficient under the one ordering rule the ISA
@@ -613,7 +608,7 @@ int runPlan(Instance* in, const mi355::Plan& plan, long planTag, hipEvent_t reco
     const size_t depOff = opBytes + segs.size() * sizeof(mi355::WalkSeg);
     char* dBase = nullptr;
     const char* stagedProg = nullptr;                             // the program as this call staged it, seen through the ring's device mapping
-    if (reuse && slot->dProgValid) dBase = slot->dProg;          // a cached plan's program is already on the device, bit for bit
+    if (reuse && slot->dProgValid) dBase = slot->dProg.p;          // a cached plan's program is already on the device, bit for bit
     else if (total <= RING_BYTES / 4) {
         const long off = stage(in, w.data(), opBytes, total);                    // reserves `total` bytes, copies the ops ...
         if (off < 0) return BEAGLE_ERROR_GENERAL;
@@ -625,30 +620,20 @@ int runPlan(Instance* in, const mi355::Plan& plan, long planTag, hipEvent_t reco
         dBase = in->dRing + off;
         if (in->kernelUploads) stagedProg = (const char*)in->hRingDev + off;
         if (slot) {                                   // keep a device copy for the next time this plan comes out of the cache
-            if (slot->dProgBytes < total) {
-                if (slot->dProg) { HIP_TRY(hipStreamSynchronize(live(in))); hipFree(slot->dProg); }
-                slot->dProg = nullptr; slot->dProgBytes = 0;
-                HIP_TRY(hipMalloc((void**)&slot->dProg, total + total / 4));
-                slot->dProgBytes = total + total / 4;
-            }
-            if (in->kernelUploads) { int rcq = queueCopy(in, slot->dProg, (size_t)off, total); if (rcq) return rcq; }     // (from the same staged bytes)
-            else HIP_TRY(hipMemcpyAsync(slot->dProg, in->dRing + off, total, hipMemcpyDeviceToDevice, live(in)));
+            { int rcg = growDevice(in, slot->dProg, total, total + total / 4, Grow::SyncIfHeld); if (rcg) return rcg; }
+            if (in->kernelUploads) { int rcq = queueCopy(in, slot->dProg.p, (size_t)off, total); if (rcq) return rcq; }     // (from the same staged bytes)
+            else HIP_TRY(hipMemcpyAsync(slot->dProg.p, in->dRing + off, total, hipMemcpyDeviceToDevice, live(in)));
             slot->dProgValid = true;
         }
     } else {                                  // a tree of > ~60 000 nodes: its own staging buffer, synchronous copy
         HIP_TRY(hipStreamSynchronize(live(in)));
-        if (in->bigStageBytes < total) {
-            if (in->bigStage) hipFree(in->bigStage);
-            in->bigStage = nullptr; in->bigStageBytes = 0;
-            HIP_TRY(hipMalloc((void**)&in->bigStage, total));
-            in->bigStageBytes = total;
-        }
-        HIP_TRY(hipMemcpy(in->bigStage, w.data(), opBytes, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(in->bigStage + opBytes, segs.data(), segs.size() * sizeof(mi355::WalkSeg), hipMemcpyHostToDevice));
-        if (!devDeps.empty()) HIP_TRY(hipMemcpy(in->bigStage + depOff, devDeps.data(), devDeps.size() * sizeof(int), hipMemcpyHostToDevice));
-        if (pairBytes) HIP_TRY(hipMemcpy(in->bigStage + opBytes + segBytes, plan.snapPairs.data(), pairBytes, hipMemcpyHostToDevice));
-        if (cmBytes) HIP_TRY(hipMemcpy(in->bigStage + cmOff, cm.data(), cmBytes, hipMemcpyHostToDevice));
-        dBase = in->bigStage;
+        { int rcg = growDevice(in, in->bigStage, total, total, Grow::SyncIfHeld); if (rcg) return rcg; }      // (its drain finds the stream idle: see above)
+        HIP_TRY(hipMemcpy(in->bigStage.p, w.data(), opBytes, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(in->bigStage.p + opBytes, segs.data(), segs.size() * sizeof(mi355::WalkSeg), hipMemcpyHostToDevice));
+        if (!devDeps.empty()) HIP_TRY(hipMemcpy(in->bigStage.p + depOff, devDeps.data(), devDeps.size() * sizeof(int), hipMemcpyHostToDevice));
+        if (pairBytes) HIP_TRY(hipMemcpy(in->bigStage.p + opBytes + segBytes, plan.snapPairs.data(), pairBytes, hipMemcpyHostToDevice));
+        if (cmBytes) HIP_TRY(hipMemcpy(in->bigStage.p + cmOff, cm.data(), cmBytes, hipMemcpyHostToDevice));
+        dBase = in->bigStage.p;
     }
     ph2 = PhaseClock::now();
     const bool fusedSnapshot = pairBytes && !in->walkT && in->fuseLaunches;          // 4 states: together with the gather below
@@ -658,14 +643,7 @@ int runPlan(Instance* in, const mi355::Plan& plan, long planTag, hipEvent_t reco
     // the matrix stream: both branch matrices of every micro-operation, in program order (after the snapshots they may name)
     const size_t streamBytes = in->walkT ? mi355::walkT32StreamBytes((int)w.size(), in->C, in->S) + 8192          // (the kernel's second fragment load reads up to 1.8 KB past an entry)
                                          : w.size() * (size_t)in->C * 40 * sizeof(double) * (cmBytes ? 2 : 1) + 1024;   // 2 x 5 columns x 4 per category; behind them the cherry region (kernels_walk4.hip)
-    if (in->matStreamBytes < streamBytes) {
-        HIP_TRY(hipStreamSynchronize(live(in)));
-        if (in->matStream) hipFree(in->matStream);
-        in->matStream = nullptr; in->matStreamBytes = 0;
-        const size_t want = std::max(streamBytes + streamBytes / 4, (size_t)1 << 20);
-        HIP_TRY(hipMalloc((void**)&in->matStream, want));
-        in->matStreamBytes = want;
-    }
+    { int rcg = growDevice(in, in->matStream, streamBytes, std::max(streamBytes + streamBytes / 4, (size_t)1 << 20), Grow::SyncAndFree); if (rcg) return rcg; }
     // 4 states, a program staged by this call (a partial update, a list the engine has not seen): its upload — and whatever else is
     // queued — rides in the gather's launch, which reads the program through the ring's mapping meanwhile (kernels_walk4.hip
     // k_gatherAndSnapshot): three launches per such evaluation instead of four.  Not when a queued copy lands in what the gather
@@ -674,7 +652,7 @@ int runPlan(Instance* in, const mi355::Plan& plan, long planTag, hipEvent_t reco
     if (uploadsRide) {
         const char* m0 = (const char*)in->matrices;
         const char* m1 = m0 + (size_t)std::max(1, in->planner.matrixSlots()) * in->C * in->S * in->S * sizeof(double);
-        const char* t0 = (const char*)in->matStream; const char* t1 = t0 + in->matStreamBytes;
+        const char* t0 = in->matStream.p; const char* t1 = t0 + in->matStream.bytes;
         const std::vector<Instance::PendingCopy>& pc = in->pendingCopies;
         for (size_t a = 0; a < pc.size() && uploadsRide; a++) {
             const char* d0 = (const char*)pc[a].dst; const char* d1 = d0 + pc[a].bytes;
@@ -699,15 +677,15 @@ int runPlan(Instance* in, const mi355::Plan& plan, long planTag, hipEvent_t reco
             for (int b = a + 1; b < L.n; b++)
                 if ((const char*)L.e[b].dst <= (const char*)L.e[a].dst && (const char*)L.e[a].dst + L.e[a].bytes <= (const char*)L.e[b].dst + L.e[b].bytes) L.e[a].bytes = 0;
         in->pendingCopies.clear();
-        mi355::launchGatherAndSnapshot(in->stream, (const mi355::WalkOp*)stagedProg, (int)w.size(), in->C, in->matStream, in->matrices,
+        mi355::launchGatherAndSnapshot(in->stream, (const mi355::WalkOp*)stagedProg, (int)w.size(), in->C, in->matStream.p, in->matrices,
                                        (const int*)(stagedProg + opBytes + segBytes), (int)(plan.snapPairs.size() / 2), in->C * in->S * in->S, &L, (int)blocks,
                                        cmBytes ? (const double* const*)(stagedProg + cmOff) : nullptr);
     }
-    else if (in->walkT) mi355::launchGatherFragments(live(in), (const mi355::WalkOp*)dBase, (int)w.size(), in->C, in->S, in->matStream);
-    else if (fusedSnapshot) mi355::launchGatherAndSnapshot(live(in), (const mi355::WalkOp*)dBase, (int)w.size(), in->C, in->matStream, in->matrices,
+    else if (in->walkT) mi355::launchGatherFragments(live(in), (const mi355::WalkOp*)dBase, (int)w.size(), in->C, in->S, in->matStream.p);
+    else if (fusedSnapshot) mi355::launchGatherAndSnapshot(live(in), (const mi355::WalkOp*)dBase, (int)w.size(), in->C, in->matStream.p, in->matrices,
                                                            (const int*)(dBase + opBytes + segBytes), (int)(plan.snapPairs.size() / 2), in->C * in->S * in->S, nullptr, 0,
                                                            cmBytes ? (const double* const*)(dBase + cmOff) : nullptr);
-    else mi355::launchGatherMatrices(live(in), (const mi355::WalkOp*)dBase, (int)w.size(), in->C, in->matStream,
+    else mi355::launchGatherMatrices(live(in), (const mi355::WalkOp*)dBase, (int)w.size(), in->C, in->matStream.p,
                                      cmBytes ? (const double* const*)(dBase + cmOff) : nullptr);
     if (labEnv("BEAGLE_MI355_DUMP_PLAN")) {           // development (LAB builds): the slices of this program, wave by wave
         fprintf(stderr, "[mi355] plan: %zu micro-ops in %zu slices (+ %zu class-table programs):", n, upN, lowN);
@@ -741,10 +719,10 @@ int runPlan(Instance* in, const mi355::Plan& plan, long planTag, hipEvent_t reco
     if (lowN) {
         const mi355::WalkSeg* dLow = (const mi355::WalkSeg*)(dBase + opBytes) + upN;
         if (in->fastWalk)
-            mi355::launchWalk4Fast(live(in), (const mi355::WalkOp*)dBase, dLow, (int)lowN, slot->lowerRange, in->matStream, in->P, in->C, (long)in->scaleStride,
+            mi355::launchWalk4Fast(live(in), (const mi355::WalkOp*)dBase, dLow, (int)lowN, slot->lowerRange, in->matStream.p, in->P, in->C, (long)in->scaleStride,
                                    nullptr, nullptr, 0, 0, nullptr, 0, nullptr, nullptr, 0, false, cmBytes ? (unsigned)(w.size() * (size_t)in->C * 40 * sizeof(double)) : 0u);
         else
-            mi355::launchWalk4(live(in), (const mi355::WalkOp*)dBase, dLow, (int)lowN, slot->lowerRange, in->matStream, in->P, in->C, (long)in->scaleStride);
+            mi355::launchWalk4(live(in), (const mi355::WalkOp*)dBase, dLow, (int)lowN, slot->lowerRange, in->matStream.p, in->P, in->C, (long)in->scaleStride);
         in->lowerLaunched = true;
     }
     if (fused) {
@@ -754,16 +732,12 @@ int runPlan(Instance* in, const mi355::Plan& plan, long planTag, hipEvent_t reco
         for (size_t i = 0; i < upN; i++) range = std::max(range, segs[i].pEnd - segs[i].pStart);
         const int flagStride = (in->P + 127) / 128 + 1;
         const size_t flagBytes = segs.size() * (size_t)flagStride * sizeof(unsigned);
-        if (in->walkFlagBytes < flagBytes) {
-            HIP_TRY(hipStreamSynchronize(live(in)));
-            if (in->walkFlags) hipFree(in->walkFlags);
-            in->walkFlags = nullptr; in->walkFlagBytes = 0; in->walkTickets = nullptr;
-            const size_t want = (std::max(flagBytes + flagBytes / 2, (size_t)1 << 16) + 255) & ~(size_t)255;
-            HIP_TRY(hipMalloc((void**)&in->walkFlags, 2 * want));               // [flags | tickets]
-            HIP_TRY(hipMemsetAsync(in->walkFlags, 0, 2 * want, live(in)));
-            in->walkFlagBytes = want;
-            in->walkTickets = (unsigned*)((char*)in->walkFlags + want);
-        }
+        const size_t want = (std::max(flagBytes + flagBytes / 2, (size_t)1 << 16) + 255) & ~(size_t)255;
+        bool grew = false;
+        in->walkTickets = nullptr;                                                  // (re-derived below: a failed growth leaves none)
+        { int rcg = growDevice(in, in->walkFlags, 2 * flagBytes, 2 * want, Grow::SyncAndFree, &grew); if (rcg) return rcg; }      // [flags | tickets]
+        if (grew) HIP_TRY(hipMemsetAsync(in->walkFlags.p, 0, in->walkFlags.bytes, live(in)));
+        in->walkTickets = (unsigned*)(in->walkFlags.p + in->walkFlags.bytes / 2);
         if (++in->walkEpoch == 0u) in->walkEpoch = 1u;
         Instance::PendingWalk& pw = in->pendingWalk;
         if (pw.valid) { int rcf = flushWalk(in); if (rcf) return rcf; }            // (cannot happen: every path here went through live())
@@ -815,15 +789,15 @@ int runPlan(Instance* in, const mi355::Plan& plan, long planTag, hipEvent_t reco
         for (size_t i = b; i < e; i++) range = std::max(range, segs[i].pEnd - segs[i].pStart);
         if (in->walkT) {
             if (!mi355::launchWalkT32(live(in), (const mi355::WalkOp*)dBase, (const mi355::WalkSeg*)(dBase + opBytes) + b, (int)(e - b), range,
-                                      in->matStream, in->P, in->S, in->C, in->holdSlots, anyScaleWriteIn(in, slot, reuse, statsAtEntry[3]))) return BEAGLE_ERROR_GENERAL;
+                                      in->matStream.p, in->P, in->S, in->C, in->holdSlots, anyScaleWriteIn(in, slot, reuse, statsAtEntry[3]))) return BEAGLE_ERROR_GENERAL;
         } else if (fast) {
             mi355::launchWalk4Fast(live(in), (const mi355::WalkOp*)dBase, (const mi355::WalkSeg*)(dBase + opBytes) + b, (int)(e - b), range,
-                                   in->matStream, in->P, in->C, (long)in->scaleStride, nullptr, nullptr, 0, 0, nullptr, 0, nullptr, nullptr, 0, false,
+                                   in->matStream.p, in->P, in->C, (long)in->scaleStride, nullptr, nullptr, 0, 0, nullptr, 0, nullptr, nullptr, 0, false,
                                    cmBytes ? (unsigned)(w.size() * (size_t)in->C * 40 * sizeof(double)) : 0u);
             in->statFastWalks++;
         } else
             mi355::launchWalk4(live(in), (const mi355::WalkOp*)dBase, (const mi355::WalkSeg*)(dBase + opBytes) + b, (int)(e - b), range,
-                               in->matStream, in->P, in->C, (long)in->scaleStride, lowN > 0);
+                               in->matStream.p, in->P, in->C, (long)in->scaleStride, lowN > 0);
         in->statWalks++;
         b = e;
     }
@@ -849,8 +823,8 @@ int flushWalk(Instance* in, const mi355::RootFused* root) {
         mi355::setWalkTrace(dTrace);
     }
 #endif
-    mi355::launchWalk4Fast(in->stream, pw.prog, pw.segs, pw.nSegs, pw.range, in->matStream, in->P, in->C, (long)in->scaleStride,
-                           pw.deps, in->walkFlags, pw.epoch, pw.flagStride, root, in->walkSpinLimit, in->walkSelfServed,
+    mi355::launchWalk4Fast(in->stream, pw.prog, pw.segs, pw.nSegs, pw.range, in->matStream.p, in->P, in->C, (long)in->scaleStride,
+                           pw.deps, in->walkFlags.as<unsigned>(), pw.epoch, pw.flagStride, root, in->walkSpinLimit, in->walkSelfServed,
                            pw.leaves > 0 ? in->walkTickets : nullptr, pw.leaves, in->xcdAware, pw.cherryOff);
 #ifdef BEAGLE_MI355_LAB
     if (dTrace) {
