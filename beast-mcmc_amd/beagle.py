@@ -325,6 +325,10 @@ class Beagle:
         assert a.size >= operationCount * 9
         self._check("updatePartialsByPartition", self._f["UpdatePartialsByPartition"](self.instance, _ip(a), operationCount))
 
+    def waitForPartials(self, destinationPartials, destinationPartialsCount):
+        a = _i(destinationPartials)
+        self._check("waitForPartials", self._f["WaitForPartials"](self.instance, _ip(a), destinationPartialsCount))
+
     def accumulateScaleFactors(self, scaleIndices, count, cumulativeScaleIndex):
         a = _i(scaleIndices)
         self._check("accumulateScaleFactors",

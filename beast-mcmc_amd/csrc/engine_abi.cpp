@@ -489,7 +489,8 @@ static int transitionMatrices(Instance* in, const int* eigenIdx, int eigenScalar
         if (off < 0) return BEAGLE_ERROR_GENERAL;
         memcpy(in->hRing + off + lenBytes, probIdx, idxBytes);
         const size_t eigStride = in->eigenComplex ? 40 : 36;
-        const double* eigSrc = in->eigen + eigStride * eigenScalar;
+        const double* const eigDst = in->eigen + eigStride * eigenScalar;
+        const double* eigSrc = eigDst;
         const double* ratesSrc = in->rates;                                   // (rate set 0)
         mi355::HostCopyList L;
         L.n = 0;
@@ -498,8 +499,9 @@ static int transitionMatrices(Instance* in, const int* eigenIdx, int eigenScalar
             mi355::HostCopyList::Entry& e = L.e[L.n++];
             e.dst = pc.dst; e.src = in->hRingDev + pc.ringOff; e.bytes = (unsigned)pc.bytes; e.firstBlock = blocks;
             blocks += (unsigned)((pc.bytes + 4095) / 4096);
-            // (the LAST queued upload of an array is the one that counts)
-            if (pc.dst == (void*)eigSrc && pc.bytes == eigStride * sizeof(double)) eigSrc = (const double*)(in->hRingDev + pc.ringOff);
+            // (the LAST queued upload of an array is the one that counts: compared with where the array lives, not with what an
+            // earlier queued upload of it has already redirected the source to)
+            if (pc.dst == (void*)eigDst && pc.bytes == eigStride * sizeof(double)) eigSrc = (const double*)(in->hRingDev + pc.ringOff);
             if (pc.dst == (void*)in->rates && pc.bytes >= (size_t)in->C * sizeof(double)) ratesSrc = (const double*)(in->hRingDev + pc.ringOff);
         }
         // (an array queued twice: the copies run side by side — an earlier one that a later one covers entirely is dropped; any

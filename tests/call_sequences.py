@@ -1,0 +1,1148 @@
+"""Seeded random call sequences over the single-partition ``beagle.Beagle`` method set, to be run on the engine and the CPU oracle in
+lockstep (tests/test_gpu_call_sequences.py) or on the oracle alone (tests/test_call_sequences_host.py).
+
+The generator is plain Python and numpy: it loads neither library.  ``generate(shape, seed, length)`` returns call records
+
+    {"m": method of beagle.Beagle, "a": [arguments as plain lists / numbers], "action": name in ACTIONS, "motif": letter or None,
+     "variant": variant of motif (d) / (f) or None}
+
+which survive a JSON round trip unchanged (``dump`` / ``load``).  ``execute(b, record, side)`` makes one call on a binding object and
+returns (return code, reads), a read being (kind, array); ``deviation(kind, got, want)`` is the normalised error of a read, so that one
+bound (1e-10) holds for every kind.
+
+Instance layout for T tips, N = 2T - 1 nodes (``Layout``): internal node n lives in partials buffer T + j (T - 1) + (n - T) of set j
+(j flips per node each time the node is written, as BufferIndexHelper does), its pre-order partials in T + 2 (T - 1) + n; the branch
+matrix of node n in slot j N + n, four spare slots behind them (two for products / sums / transposes / detached updates, two for
+differential matrices); scale buffer j (T - 1) + (n - T) per internal node and set, two cumulative ones behind them; two eigen /
+weight / frequency / category-rate slots; T compact buffers.
+
+The definedness model: the generator tracks which partials buffers, matrices and scale buffers hold a defined value (a scale buffer
+also whether it holds the factors of a rescaling operation, "raw", or accumulated logarithms, "log": a read-mode operation divides
+by raw factors only, accumulate / remove add into log buffers only), and which scale buffer each partials buffer was last written
+with.  Reads and consuming calls are emitted on defined inputs only, and never what the contract leaves open: an operation writing one
+of its own children, convolve / transpose onto an input, accumulate of a never-written buffer, a root call with count != 1, derivative
+indices to updateTransitionMatrices.  Branch matrices are always non-negative (differential matrices stay in their two spare slots).
+
+Replay of a failing sequence:  python tests/call_sequences.py --replay FILE --upto N  runs engine and oracle up to step N and prints
+the first diverging read; it stops at the first non-zero return code or exception.
+"""
+import json
+
+import numpy as np
+
+NONE = -1
+BOUND = 1e-10
+
+ACTIONS = (
+    "setEigenDecomposition", "setCategoryRates", "setCategoryRatesWithIndex", "setCategoryWeights", "setStateFrequencies",
+    "setPatternWeights",
+    "setTipStates", "setTipPartials", "setPartials", "compactToPartials", "setTipEmission",
+    "updateTransitionMatrices", "updateTransitionMatricesWithMultipleModels", "setTransitionMatrix", "convolveTransitionMatrices",
+    "addTransitionMatrices", "transposeTransitionMatrices", "getTransitionMatrix",
+    "updatePartials:none", "updatePartials:write", "updatePartials:read", "updatePartials:cumulative", "waitForPartials",
+    "resetScaleFactors", "accumulateScaleFactors", "removeScaleFactors", "copyScaleFactors", "getLogScaleFactors",
+    "calculateRootLogLikelihoods:root", "calculateRootLogLikelihoods:other", "calculateRootLogLikelihoods:cumulative",
+    "getSiteLogLikelihoods", "getPartials", "getPartials:scaled", "getPartialsBatch",
+    "setRootPrePartials", "updatePrePartials", "setDifferentialMatrix", "calculateEdgeDifferentials",
+    "calculateCrossProductDifferentials", "getPartials:pre",
+)
+EMISSION_STATES = (4, 20)                  # setTipEmission: 4- and 20-state shapes only
+MOTIFS = "abcdefghi"
+D_VARIANTS = ("getPartials", "getPartialsBatch", "getSiteLogLikelihoods", "getLogScaleFactors", "resetScaleFactors", "copyScaleFactors",
+              "setTransitionMatrix", "setCategoryWeights")
+F_VARIANTS = ("read_pre", "read_post", "write_post", "write_matrix", "write_pre", "scale_call", "model_call", "root_call")
+HOST_COPY_MAX = 12                         # uploads one launch carries (motif c queues more)
+
+
+def actions_for(S):
+    return tuple(a for a in ACTIONS if a != "setTipEmission" or S in EMISSION_STATES)
+
+
+class Layout:
+    def __init__(self, shape):
+        self.S, self.C, self.T, self.P = shape
+        T = self.T
+        self.N = 2 * T - 1
+        self.root = self.N - 1
+        self.pre_base = T + 2 * (T - 1)
+        self.partials_count = self.pre_base + self.N
+        self.matrix_count = 2 * self.N + 4
+        self.spare = [2 * self.N + k for k in range(4)]        # [0], [1]: probabilities; [2], [3]: differential matrices
+        self.cum = [2 * (T - 1), 2 * (T - 1) + 1]
+        self.scale_count = 2 * (T - 1) + 2
+        self.eigen_count = 2
+
+    def post(self, n, j):
+        return n if n < self.T else self.T + j * (self.T - 1) + (n - self.T)
+
+    def pre(self, n):
+        return self.pre_base + n
+
+    def matrix(self, n, j):
+        return j * self.N + n
+
+    def scale(self, n, j):
+        return j * (self.T - 1) + (n - self.T)
+
+    def create_args(self):
+        return (self.T, self.partials_count, self.T, self.S, self.P, self.eigen_count, self.matrix_count, self.C, self.scale_count)
+
+
+def _lst(a):
+    return np.asarray(a).tolist()
+
+
+def reversible_model(rng, S):
+    """(eigenvectors, inverse, eigenvalues, frequencies, Q) of a random reversible model at one substitution per unit time, from the
+    symmetric form D^1/2 Q D^-1/2"""
+    pi = rng.dirichlet(np.full(S, 20.0))
+    r = rng.uniform(0.5, 1.5, size=(S, S))
+    r = np.triu(r, 1)
+    r = r + r.T
+    q = r * pi[None, :]
+    q -= np.diag(q.sum(axis=1))
+    q /= -np.dot(pi, np.diag(q))
+    d = np.sqrt(pi)
+    lam, v = np.linalg.eigh(d[:, None] * q / d[None, :])
+    return v / d[:, None], v.T * d[None, :], lam, pi, q
+
+
+class Generator:
+    def __init__(self, shape, seed, length):
+        self.L = L = Layout(shape)
+        self.shape, self.seed, self.length = tuple(shape), seed, length
+        self.rng = np.random.default_rng([seed, L.S, L.C, L.T, L.P])
+        self.rec = []
+        self.motif = self.variant = None
+        T, N = L.T, L.N
+        rng = self.rng
+        # the tree: nodes joined pairwise, children before parents, the root last
+        self.left, self.right, self.parent = [NONE] * N, [NONE] * N, [NONE] * N
+        live = list(range(T))
+        for n in range(T, N):
+            a = live.pop(int(rng.integers(len(live))))
+            b = live.pop(int(rng.integers(len(live))))
+            self.left[n], self.right[n], self.parent[a], self.parent[b] = a, b, n, n
+            live.append(n)
+        self.level = [0] * N
+        for n in range(T, N):
+            self.level[n] = 1 + max(self.level[self.left[n]], self.level[self.right[n]])
+        self.internal = list(range(T, N))
+        self.length_of = rng.uniform(0.01, 1.0, size=N)
+        # model state
+        self.cur = [0] * N                      # buffer set holding node n's current partials
+        self.mcur = [0] * N                     # matrix set holding node n's current branch matrix
+        self.pdef = [False] * L.partials_count
+        self.pscale = [NONE] * L.partials_count
+        self.mdef = [None] * L.matrix_count     # None, "prob" or "diff"
+        self.sdef = [None] * L.scale_count      # None, "raw" or "log"
+        self.accumulated = {c: [] for c in L.cum}
+        self.tipkind = ["compact" if rng.random() < 2.0 / 3.0 else "partials" for _ in range(T)]
+        if "compact" not in self.tipkind:
+            self.tipkind[0] = "compact"
+        if "partials" not in self.tipkind:
+            self.tipkind[T - 1] = "partials"
+        self.models = [None, None]
+        self.rates = [None, None]
+        self.root_done = False
+        self.last_list = None
+        self.last_pre = None
+        self.d_count = self.f_count = 0
+
+    # ---- records ---------------------------------------------------------------------------------------------------------------
+    def emit(self, method, args, action):
+        self.rec.append({"m": method, "a": args, "action": action, "motif": self.motif, "variant": self.variant})
+
+    # ---- values ------------------------------------------------------------------------------------------------------------------
+    def tip_states(self, first_known=False):
+        L, rng = self.L, self.rng
+        s = rng.integers(0, L.S, size=L.P)
+        if not first_known:
+            s[rng.random(L.P) < 0.025] = L.S
+        return _lst(s)
+
+    def tip_partials(self):
+        L, rng = self.L, self.rng
+        p = rng.uniform(0.02, 0.1, size=(L.P, L.S))
+        p[np.arange(L.P), rng.integers(0, L.S, size=L.P)] = 1.0
+        return _lst(p.ravel())
+
+    def node_partials(self):
+        L = self.L
+        return _lst(self.rng.uniform(0.1, 1.0, size=L.C * L.P * L.S))
+
+    def weights(self):
+        return _lst(self.rng.dirichlet(np.full(self.L.C, 5.0)))
+
+    def category_rates(self):
+        r = self.rng.uniform(0.3, 2.0, size=self.L.C)
+        return _lst(r / r.mean())
+
+    def random_matrix(self):
+        L = self.L
+        m = self.rng.dirichlet(np.full(L.S, 1.0), size=L.C * L.S)
+        return _lst(m.ravel())
+
+    def a_length(self):
+        return float(self.rng.uniform(0.01, 1.0))
+
+    # ---- model calls ---------------------------------------------------------------------------------------------------------
+    def set_eigen(self, slot, same=False):
+        if not same or self.models[slot] is None:
+            self.models[slot] = reversible_model(self.rng, self.L.S)
+        u, ui, lam, _, _ = self.models[slot]
+        self.emit("setEigenDecomposition", [slot, _lst(u.ravel()), _lst(ui.ravel()), _lst(lam)], "setEigenDecomposition")
+
+    def set_rates(self, slot, indexed):
+        self.rates[slot] = self.category_rates()
+        if indexed or slot != 0:
+            self.emit("setCategoryRatesWithIndex", [slot, self.rates[slot]], "setCategoryRatesWithIndex")
+        else:
+            self.emit("setCategoryRates", [self.rates[0]], "setCategoryRates")
+
+    def set_weights(self, slot):
+        self.emit("setCategoryWeights", [slot, self.weights()], "setCategoryWeights")
+
+    def set_frequencies(self, slot):
+        self.emit("setStateFrequencies", [slot, _lst(self.rng.dirichlet(np.full(self.L.S, 20.0)))], "setStateFrequencies")
+
+    def set_pattern_weights(self):
+        self.emit("setPatternWeights", [_lst(self.rng.integers(1, 9, size=self.L.P).astype(float))], "setPatternWeights")
+
+    # ---- data calls ------------------------------------------------------------------------------------------------------------
+    def resend_tip(self, t=None):
+        t = int(self.rng.integers(self.L.T)) if t is None else t
+        if self.tipkind[t] == "compact":
+            self.emit("setTipStates", [t, self.tip_states(first_known=(t == self.first_compact))], "setTipStates")
+        else:
+            self.emit("setTipPartials", [t, self.tip_partials()], "setTipPartials")
+            self.tipkind[t] = "partials"
+        self.pdef[t] = True
+
+    def resend_tip_of_kind(self, kind):
+        tips = [t for t in range(self.L.T) if (self.tipkind[t] == "compact") == (kind == "compact")]
+        if tips:
+            self.resend_tip(tips[int(self.rng.integers(len(tips)))])
+        return bool(tips)
+
+    def compact_to_partials(self):
+        tips = [t for t in range(self.L.T) if self.tipkind[t] == "compact" and t != self.first_compact]
+        if not tips:
+            return False
+        t = tips[int(self.rng.integers(len(tips)))]
+        self.emit("setTipPartials", [t, self.tip_partials()], "compactToPartials")
+        self.tipkind[t] = "partials"
+        return True
+
+    def set_tip_emission(self):
+        """engine: setTipEmission(tip, codes, table); oracle: setTipPartials of the expanded table.  4 states: the sequence-error
+        model's table (every base read correctly with 1 - e, as any other with e / 3; tests/tip_models_reference.py expands it pattern
+        by pattern); 20 states: K rows (K <= S folds into the tip's matrix, K > S is expanded on the device)."""
+        L, rng = self.L, self.rng
+        if L.S not in EMISSION_STATES:
+            return False
+        tips = [t for t in range(L.T) if t != self.first_compact]
+        t = tips[int(rng.integers(len(tips)))]
+        if L.S == 4:
+            e = float(rng.uniform(0.001, 0.05))
+            table = np.full((4, 4), (1.0 - (1.0 - e)) / 3.0)
+            table[np.arange(4), np.arange(4)] = 1.0 - e
+            codes = rng.integers(0, 4, size=L.P)
+            codes[rng.random(L.P) < 0.02] = 4
+            extra = {"base_rate": e}
+        else:
+            K = int(rng.choice([L.S - 3, L.S, L.S + 5]))
+            table = rng.uniform(0.02, 0.1, size=(K, L.S))
+            table[np.arange(K), rng.integers(0, L.S, size=K)] = 1.0
+            codes = rng.integers(0, K, size=L.P)
+            codes[rng.random(L.P) < 0.02] = K
+            extra = {}
+        self.emit("setTipEmission", [t, _lst(codes), _lst(table), extra], "setTipEmission")
+        self.tipkind[t] = "emission"
+        self.pdef[t] = True
+        return True
+
+    def set_partials(self, b=None):
+        L = self.L
+        if b is None:
+            n = self.internal[int(self.rng.integers(len(self.internal)))]
+            b = L.post(n, int(self.rng.integers(2)))
+        self.emit("setPartials", [b, self.node_partials()], "setPartials")
+        self.pdef[b] = True
+        self.pscale[b] = NONE
+
+    # ---- matrix calls ----------------------------------------------------------------------------------------------------------
+    def branches(self):
+        return [n for n in range(self.L.N) if n != self.L.root]
+
+    def update_matrices(self, nodes=None, flip=True, slots=None, action="updateTransitionMatrices", multiple=False, eigen=None):
+        """new branch lengths for `nodes` into their (flipped) matrix slots, or detached lengths into the spare `slots`"""
+        L, rng = self.L, self.rng
+        if slots is None:
+            if nodes is None:
+                kind = rng.random()
+                nodes = self.branches()
+                if kind > 0.4:
+                    k = int(rng.integers(1, len(nodes)))
+                    nodes = sorted(_lst(rng.choice(nodes, size=k, replace=False)))
+            slots = []
+            for n in nodes:
+                if flip:
+                    self.mcur[n] ^= 1
+                slots.append(L.matrix(n, self.mcur[n]))
+                self.length_of[n] = self.a_length()
+            lengths = [float(self.length_of[n]) for n in nodes]
+        else:
+            lengths = [self.a_length() for _ in slots]
+        if multiple:
+            e = _lst(rng.integers(0, 2, size=len(slots)))
+            r = _lst(rng.integers(0, 2, size=len(slots)))
+            self.emit("updateTransitionMatricesWithMultipleModels", [e, r, slots, None, None, lengths, len(slots)],
+                      "updateTransitionMatricesWithMultipleModels")
+        else:
+            self.emit("updateTransitionMatrices", [int(rng.integers(2)) if eigen is None else eigen, slots, None, None, lengths, len(slots)], action)
+        for m in slots:
+            self.mdef[m] = "prob"
+        return slots
+
+    def prob_slots(self):
+        return [m for m in range(self.L.matrix_count) if self.mdef[m] == "prob"]
+
+    def set_transition_matrix(self, m=None):
+        if m is None:
+            m = self.prob_slots()[int(self.rng.integers(len(self.prob_slots())))] if self.rng.random() < 0.7 else self.L.spare[int(self.rng.integers(2))]
+        self.emit("setTransitionMatrix", [m, self.random_matrix(), 1.0], "setTransitionMatrix")
+        self.mdef[m] = "prob"
+        return m
+
+    def triples(self, method, result=None):
+        """1-3 triples; a later one may read an earlier result (a dependent chain)"""
+        L, rng = self.L, self.rng
+        k = 1 if result is not None else int(rng.integers(1, 4))
+        first, second, res = [], [], []
+        for i in range(k):
+            src = [m for m in self.prob_slots() if m not in L.spare[:2]] + res
+            r = result if result is not None else L.spare[i % 2]
+            pool = [m for m in src if m != r]
+            if i and rng.random() < 0.5:
+                a = res[-1] if res[-1] != r else pool[0]           # dependent on the triple before
+            else:
+                a = pool[int(rng.integers(len(pool)))]
+            b = pool[int(rng.integers(len(pool)))]
+            first.append(a); second.append(b); res.append(r)
+        n = len(res)
+        self.emit(method, [first, second, res, n], method)
+        for m in res:
+            self.mdef[m] = "prob"
+
+    def transpose(self):
+        L, rng = self.L, self.rng
+        src = [m for m in self.prob_slots() if m not in L.spare[:2]]
+        k = int(rng.integers(1, 3))
+        a = [src[int(rng.integers(len(src)))] for _ in range(k)]
+        self.emit("transposeTransitionMatrices", [a, L.spare[:k], k], "transposeTransitionMatrices")
+        for m in L.spare[:k]:
+            self.mdef[m] = "prob"
+
+    def get_matrix(self, m=None):
+        slots = [m for m in range(self.L.matrix_count) if self.mdef[m]]
+        m = slots[int(self.rng.integers(len(slots)))] if m is None else m
+        self.emit("getTransitionMatrix", [m], "getTransitionMatrix")
+
+    # ---- operation lists ---------------------------------------------------------------------------------------------------------
+    def pick_nodes(self):
+        """(nodes in list order): the whole tree, one subtree or one tip-to-root path; post-order or reverse level order"""
+        L, rng = self.L, self.rng
+        kind = rng.random()
+        if kind < 0.45:
+            nodes = list(self.internal)
+        elif kind < 0.7:
+            top = self.internal[int(rng.integers(len(self.internal)))]
+            nodes, stack = [], [top]
+            while stack:
+                n = stack.pop()
+                if n >= L.T:
+                    nodes.append(n)
+                    stack += [self.left[n], self.right[n]]
+        else:
+            n = self.parent[int(rng.integers(L.T))]
+            nodes = []
+            while n != NONE:
+                nodes.append(n)
+                n = self.parent[n]
+        if rng.random() < 0.5:
+            return self.post_order(nodes)
+        return sorted(nodes, key=lambda n: (self.level[n], n))
+
+    def post_order(self, nodes):
+        keep, out, stack = set(nodes), [], [(self.L.root, False)]
+        while stack:
+            n, done = stack.pop()
+            if n < self.L.T:
+                continue
+            if done:
+                if n in keep:
+                    out.append(n)
+            else:
+                stack += [(n, True), (self.right[n], False), (self.left[n], False)]
+        return out
+
+    def raw_scales(self):
+        return [s for s in range(self.L.scale_count) if self.sdef[s] == "raw"]
+
+    def log_scales(self):
+        return [s for s in range(self.L.scale_count) if self.sdef[s] == "log"]
+
+    def build_list(self, nodes, mode, flip=True, dest_set=None, again=None):
+        """7-int operations for `nodes` in that order; mode "none" / "write" / "read"; dest_set {node: set} overrides the flip.
+        `again`: one node of the list recomputed at the end of it into the buffer its parent's operation has read (sequential semantics)."""
+        L = self.L
+        ops, meta = [], {}
+        for k, n in enumerate(list(nodes) + ([again] if again is not None else [])):
+            if k >= len(nodes):
+                j = self.cur[n]                              # (the buffer it was written to earlier in this list, read since)
+            else:
+                j = dest_set[n] if dest_set is not None else (self.cur[n] ^ 1 if flip else self.cur[n])
+            dest = L.post(n, j)
+            l, r = self.left[n], self.right[n]
+            cl, cr = L.post(l, self.cur[l]), L.post(r, self.cur[r])
+            ws = rs = NONE
+            if mode == "write":
+                ws = L.scale(n, j)
+            elif mode == "read":
+                own = L.scale(n, self.cur[n])
+                raw = self.raw_scales()
+                rs = own if self.sdef[own] == "raw" else raw[int(self.rng.integers(len(raw)))]
+            ops += [dest, ws, rs, cl, L.matrix(l, self.mcur[l]), cr, L.matrix(r, self.mcur[r])]
+            self.cur[n] = j
+            meta[n] = j
+            self.pdef[dest] = True
+            self.pscale[dest] = ws if ws != NONE else rs
+            if ws != NONE:
+                self.sdef[ws] = "raw"
+        return ops, meta
+
+    def update_partials(self, mode=None, cum_on_call=None, nodes=None, flip=True, dest_set=None, again=False):
+        L, rng = self.L, self.rng
+        if mode is None:
+            mode = ("none", "write", "read")[int(rng.integers(3))]
+        if mode == "read" and not self.raw_scales():
+            mode = "write"
+        nodes = self.pick_nodes() if nodes is None else nodes
+        extra = None
+        if again and len(nodes) > 1:
+            extra = nodes[int(rng.integers(len(nodes) - 1))]
+        cum = NONE
+        if mode == "write" and (cum_on_call if cum_on_call is not None else rng.random() < 0.35) and self.log_scales():
+            logs = [c for c in L.cum if self.sdef[c] == "log"]
+            if logs:
+                cum = logs[int(rng.integers(len(logs)))]
+        ops, meta = self.build_list(nodes, mode, flip=flip, dest_set=dest_set, again=extra)
+        count = len(ops) // 7
+        if cum != NONE:
+            self.accumulated[cum] += [ops[7 * k + 1] for k in range(count)]
+        action = "updatePartials:cumulative" if cum != NONE else "updatePartials:" + mode
+        self.emit("updatePartials", [ops, count, cum], action)
+        self.last_list = {"ops": ops, "count": count, "nodes": list(nodes), "meta": meta, "mode": mode}
+        return ops
+
+    def repeat_list(self):
+        """the last list again, verbatim (no cumulative index)"""
+        ll = self.last_list
+        for k in range(ll["count"]):
+            op = ll["ops"][7 * k:7 * k + 7]
+            self.pdef[op[0]] = True
+            if op[1] != NONE:
+                self.sdef[op[1]] = "raw"
+            self.pscale[op[0]] = op[1] if op[1] != NONE else op[2]
+        for n, j in ll["meta"].items():
+            self.cur[n] = j
+        self.emit("updatePartials", [list(ll["ops"]), ll["count"], NONE], "updatePartials:" + ll["mode"])
+
+    def wait_for_partials(self):
+        b = [self.L.post(n, self.cur[n]) for n in self.internal[:2]]
+        self.emit("waitForPartials", [b, len(b)], "waitForPartials")
+
+    # ---- scale-buffer calls ----------------------------------------------------------------------------------------------------
+    def reset_scale(self, c=None):
+        c = self.L.cum[int(self.rng.integers(2))] if c is None else c
+        self.emit("resetScaleFactors", [c], "resetScaleFactors")
+        self.sdef[c] = "log"
+        if c in self.accumulated:
+            self.accumulated[c] = []
+
+    def a_log_cum(self):
+        logs = [c for c in self.L.cum if self.sdef[c] == "log"]
+        return logs[int(self.rng.integers(len(logs)))] if logs else None
+
+    def accumulate(self, c=None, idx=None):
+        c = self.a_log_cum() if c is None else c
+        src = [s for s in self.raw_scales() if s != c]
+        if c is None or not src:
+            return False
+        if idx is None:
+            current = [self.pscale[self.L.post(n, self.cur[n])] for n in self.internal]
+            current = [s for s in current if s != NONE and self.sdef[s] == "raw" and s != c]
+            pool = current if current and self.rng.random() < 0.7 else src
+            k = int(self.rng.integers(1, len(pool) + 1))
+            idx = sorted(set(_lst(self.rng.choice(pool, size=k, replace=False))))
+        self.emit("accumulateScaleFactors", [idx, len(idx), c], "accumulateScaleFactors")
+        self.accumulated.setdefault(c, []).extend(idx)
+        return True
+
+    def remove(self):
+        """takes out again some of what was accumulated (short chains: at most three buffers a call)"""
+        cands = [c for c in self.L.cum if self.sdef[c] == "log" and [s for s in self.accumulated[c] if self.sdef[s] == "raw"]]
+        if not cands:
+            return False
+        c = cands[int(self.rng.integers(len(cands)))]
+        have = sorted(set(s for s in self.accumulated[c] if self.sdef[s] == "raw"))
+        k = int(self.rng.integers(1, min(3, len(have)) + 1))
+        idx = sorted(_lst(self.rng.choice(have, size=k, replace=False)))
+        self.emit("removeScaleFactors", [idx, k, c], "removeScaleFactors")
+        for s in idx:
+            self.accumulated[c].remove(s)
+        return True
+
+    def copy_scale(self, dst=None, src=None):
+        L = self.L
+        defined = [s for s in range(L.scale_count) if self.sdef[s]]
+        if src is None:
+            src = defined[int(self.rng.integers(len(defined)))]
+            dst = L.cum[int(self.rng.integers(2))] if self.sdef[src] == "log" else int(self.rng.integers(L.scale_count - 2))
+            if dst == src:
+                return False
+        self.emit("copyScaleFactors", [dst, src], "copyScaleFactors")
+        self.sdef[dst] = self.sdef[src]
+        if dst in self.accumulated:
+            self.accumulated[dst] = list(self.accumulated.get(src, []))
+        return True
+
+    def get_scale(self, s=None):
+        defined = [k for k in range(self.L.scale_count) if self.sdef[k]]
+        s = defined[int(self.rng.integers(len(defined)))] if s is None else s
+        self.emit("getLogScaleFactors", [s], "getLogScaleFactors")
+
+    # ---- root calls and reads ----------------------------------------------------------------------------------------------------
+    def root_call(self, where=None, cum=None, b=None):
+        L, rng = self.L, self.rng
+        if where is None:
+            where = "root" if rng.random() < 0.6 else "other"
+        if b is None:
+            if where == "root":
+                b = L.post(L.root, self.cur[L.root])
+            else:
+                pool = [L.post(n, j) for n in self.internal for j in (0, 1) if self.pdef[L.post(n, j)] and L.post(n, j) != L.post(L.root, self.cur[L.root])]
+                b = pool[int(rng.integers(len(pool)))]
+        if cum is None:
+            cum = rng.random() < 0.4
+        c = NONE
+        if cum:
+            logs = self.log_scales()
+            c = logs[int(rng.integers(len(logs)))] if logs else NONE
+        action = "calculateRootLogLikelihoods:" + ("cumulative" if c != NONE else where)
+        self.emit("calculateRootLogLikelihoods", [[b], [int(rng.integers(2))], [int(rng.integers(2))], [c], 1], action)
+        self.root_done = True
+
+    def get_sites(self):
+        if not self.root_done:
+            self.root_call()
+        self.emit("getSiteLogLikelihoods", [], "getSiteLogLikelihoods")
+
+    def readable(self):
+        L = self.L
+        return [b for b in range(L.pre_base) if self.pdef[b] and not (b < L.T and self.tipkind[b] == "compact")]
+
+    def get_partials(self, b=None, scaled=None):
+        rng = self.rng
+        pool = self.readable()
+        b = pool[int(rng.integers(len(pool)))] if b is None else b
+        scaled = rng.random() < 0.4 if scaled is None else scaled
+        s = NONE
+        if scaled:
+            defined = [k for k in range(self.L.scale_count) if self.sdef[k]]
+            s = self.pscale[b] if self.pscale[b] != NONE and rng.random() < 0.5 else defined[int(rng.integers(len(defined)))]
+        self.emit("getPartials", [b, s], "getPartials:scaled" if s != NONE else "getPartials")
+
+    def get_partials_batch(self):
+        rng = self.rng
+        pool = self.readable()
+        k = int(rng.integers(2, 4))
+        b = [pool[int(rng.integers(len(pool)))] for _ in range(k)]
+        sc = None
+        if rng.random() < 0.4:
+            defined = [s for s in range(self.L.scale_count) if self.sdef[s]]
+            sc = [NONE if rng.random() < 0.5 else defined[int(rng.integers(len(defined)))] for _ in b]
+        self.emit("getPartialsBatch", [b, sc], "getPartialsBatch")
+
+    # ---- gradient calls --------------------------------------------------------------------------------------------------------
+    def set_root_pre(self):
+        L = self.L
+        self.emit("setRootPrePartials", [[L.pre(L.root)], [int(self.rng.integers(2))], 1], "setRootPrePartials")
+        self.pdef[L.pre(L.root)] = True
+
+    def update_pre(self, whole=None):
+        """pre-order operations from the root down: the whole tree, or the path to one internal node (both children of every node
+        on it)"""
+        L, rng = self.L, self.rng
+        if not self.pdef[L.pre(L.root)]:
+            self.set_root_pre()
+        whole = rng.random() < 0.6 if whole is None else whole
+        if whole:
+            parents, stack = [], [L.root]
+            while stack:
+                n = stack.pop()
+                if n >= L.T:
+                    parents.append(n)
+                    stack += [self.right[n], self.left[n]]
+        else:
+            n = self.internal[int(rng.integers(len(self.internal)))]
+            parents = []
+            while n != NONE:
+                parents.insert(0, n)
+                n = self.parent[n]
+        ops = []
+        for n in parents:
+            l, r = self.left[n], self.right[n]
+            for child, sib in ((l, r), (r, l)):
+                ops += [L.pre(child), NONE, NONE, L.pre(n), L.matrix(child, self.mcur[child]), L.post(sib, self.cur[sib]),
+                        L.matrix(sib, self.mcur[sib])]
+                self.pdef[L.pre(child)] = True
+        self.emit("updatePrePartials", [ops, len(ops) // 7, NONE], "updatePrePartials")
+        self.last_pre = {"ops": ops, "parents": parents}
+
+    def set_differential(self, k=0):
+        L = self.L
+        slot = int(self.rng.integers(2))
+        q = self.models[slot][4]
+        if k:
+            q = q @ q
+        m = np.concatenate([(q * r ** (k + 1)).ravel() for r in self.rates[slot]])
+        self.emit("setDifferentialMatrix", [L.spare[2 + k], _lst(m)], "setDifferentialMatrix")
+        self.mdef[L.spare[2 + k]] = "diff"
+
+    def edges_with_pre(self):
+        L = self.L
+        return [n for n in range(L.N) if n != L.root and self.pdef[L.pre(n)]]
+
+    def edge_differentials(self, want=None, all_edges=False):
+        L, rng = self.L, self.rng
+        if not self.edges_with_pre():
+            self.update_pre()
+        diffs = [m for m in L.spare[2:] if self.mdef[m] == "diff"]
+        if not diffs:
+            self.set_differential(0)
+            diffs = [L.spare[2]]
+        edges = self.edges_with_pre()
+        if not all_edges and rng.random() < 0.5:
+            edges = sorted(_lst(rng.choice(edges, size=int(rng.integers(1, len(edges) + 1)), replace=False)))
+        post = [L.post(n, self.cur[n]) for n in edges]
+        pre = [L.pre(n) for n in edges]
+        d = [diffs[int(rng.integers(len(diffs)))]] * len(edges)
+        # what is asked for: the sums alone (a held list can answer and stay held), sums of squares as well (it runs together with the
+        # derivatives), per-pattern values too (it has to run first)
+        want = [[False, False], [False, True], [True, True]][int(rng.integers(3)) if want is None else want]
+        self.emit("calculateEdgeDifferentials", [post, pre, d, [int(rng.integers(2))], len(edges), want], "calculateEdgeDifferentials")
+
+    def cross_products(self):
+        L, rng = self.L, self.rng
+        if not self.edges_with_pre():
+            self.update_pre()
+        edges = self.edges_with_pre()
+        post = [L.post(n, self.cur[n]) for n in edges]
+        pre = [L.pre(n) for n in edges]
+        self.emit("calculateCrossProductDifferentials", [post, pre, [int(rng.integers(2))], [int(rng.integers(2))],
+                                                         [float(self.length_of[n]) for n in edges], len(edges)],
+                  "calculateCrossProductDifferentials")
+
+    def get_pre_partials(self):
+        L = self.L
+        pool = [L.pre(n) for n in range(L.N) if self.pdef[L.pre(n)]]
+        if not pool:
+            self.update_pre()
+            pool = [L.pre(n) for n in range(L.N) if self.pdef[L.pre(n)]]
+        self.emit("getPartials", [pool[int(self.rng.integers(len(pool)))], NONE], "getPartials:pre")
+
+    # ---- the set-up every sequence starts with -------------------------------------------------------------------------------
+    def prelude(self):
+        L = self.L
+        self.first_compact = self.tipkind.index("compact")       # known in every pattern: no pattern is ambiguous at every tip
+        for slot in (0, 1):
+            self.set_eigen(slot)
+            self.set_rates(slot, indexed=True)
+            self.set_weights(slot)
+            self.set_frequencies(slot)
+        self.set_pattern_weights()
+        for t in range(L.T):
+            self.resend_tip(t)
+        for j in (0, 1):
+            self.mcur = [j] * L.N
+            self.update_matrices(nodes=self.branches(), flip=False)
+        self.update_matrices(slots=L.spare[:2])
+        self.mcur = [0] * L.N
+        self.cur = [1] * L.N
+        self.update_partials(mode="write", cum_on_call=False, nodes=self.post_order(self.internal))
+        self.reset_scale(L.cum[0])
+        self.accumulate(L.cum[0], [L.scale(n, 0) for n in self.internal])
+        self.reset_scale(L.cum[1])
+        self.root_call("root", cum=False)
+        self.set_differential(0)
+        self.prelude_end = len(self.rec)
+        self.gave_up = set()
+
+    # ---- motifs: the call orders the engine's deferral logic branches on -------------------------------------------------------
+    def motif_a(self):
+        """the same eigen slot set twice, then updateTransitionMatrices (the earlier of two queued copies is dropped)"""
+        slot = int(self.rng.integers(2))
+        self.mcur_reads(1)                                   # (a read first: nothing else is queued when the two uploads are)
+        self.set_eigen(slot)
+        self.set_eigen(slot, same=self.seed % 4 == 0)
+        self.update_matrices(nodes=self.branches()[:3], eigen=slot)
+        self.mcur_reads(3)
+
+    def mcur_reads(self, k):
+        for n in self.branches()[:k]:
+            self.get_matrix(self.L.matrix(n, self.mcur[n]))
+
+    def motif_b(self):
+        """setTransitionMatrix(m) then updateTransitionMatrices including m (the later call has to win), and the reverse order"""
+        n = self.branches()[int(self.rng.integers(len(self.branches())))]
+        m = self.L.matrix(n, self.mcur[n])
+        self.set_transition_matrix(m)
+        self.update_matrices(nodes=[n] + [x for x in self.branches()[:2] if x != n], flip=False)
+        self.get_matrix(m)
+        self.update_matrices(nodes=[n], flip=False)
+        self.set_transition_matrix(m)
+        self.get_matrix(m)
+
+    def motif_c(self):
+        """13 or more small uploads with no launch between them, then a launch"""
+        k = 0
+        while k < HOST_COPY_MAX + 1 + int(self.seed % 3):
+            pick = k % 5
+            if pick == 0:
+                self.set_weights(k // 5 % 2)
+            elif pick == 1:
+                self.set_frequencies(k // 5 % 2)
+            elif pick == 2:
+                self.set_rates(k // 5 % 2, indexed=True)
+            elif pick == 3:
+                self.set_pattern_weights()
+            else:
+                self.set_eigen(k // 5 % 2)
+            k += 1
+        self.update_matrices(nodes=self.branches())
+        self.update_partials(mode="none", nodes=self.post_order(self.internal))
+        self.root_call("root", cum=False)
+        self.get_sites()
+
+    def motif_d(self):
+        """updatePartials, then one kind of other call (by seed: over a shape's seeds every kind), then the root"""
+        L = self.L
+        self.variant = v = D_VARIANTS[(self.seed + 3 * self.d_count) % len(D_VARIANTS)]
+        self.d_count += 1
+        write = v in ("getLogScaleFactors", "resetScaleFactors", "copyScaleFactors")
+        self.update_matrices(nodes=self.branches())
+        self.update_partials(mode="write" if write else "none", cum_on_call=False, nodes=self.post_order(self.internal))
+        mid = self.internal[len(self.internal) // 2]
+        if v == "getPartials":
+            self.get_partials(L.post(mid, self.cur[mid]), scaled=False)
+        elif v == "getPartialsBatch":
+            self.emit("getPartialsBatch", [[L.post(L.root, self.cur[L.root]), L.post(mid, self.cur[mid])], None], "getPartialsBatch")
+        elif v == "getSiteLogLikelihoods":
+            self.get_sites()
+        elif v == "getLogScaleFactors":
+            self.get_scale(L.scale(mid, self.cur[mid]))
+        elif v == "resetScaleFactors":
+            self.reset_scale(L.cum[0])
+            self.accumulate(L.cum[0], [L.scale(n, self.cur[n]) for n in self.internal])
+        elif v == "copyScaleFactors":
+            self.reset_scale(L.cum[1])
+            self.accumulate(L.cum[1], [L.scale(n, self.cur[n]) for n in self.internal])
+            self.copy_scale(L.cum[0], L.cum[1])
+        elif v == "setTransitionMatrix":
+            self.set_transition_matrix(L.matrix(self.left[L.root], self.mcur[self.left[L.root]]))
+        elif v == "setCategoryWeights":
+            self.set_weights(0)
+            self.set_weights(1)
+        c = L.cum[0] if write else NONE
+        self.emit("calculateRootLogLikelihoods", [[L.post(L.root, self.cur[L.root])], [0], [0], [c], 1],
+                  "calculateRootLogLikelihoods:" + ("cumulative" if write else "root"))
+        self.root_done = True
+        self.get_sites()
+
+    def motif_e(self):
+        """root / site read three times in a row (the prefetch starts after two), a root whose site values are not read, a read"""
+        for k in range(3):
+            self.update_matrices(nodes=[self.branches()[k]])
+            self.update_partials(mode="none", nodes=self.post_order(self.internal))
+            self.root_call("root", cum=False)
+            self.get_sites()
+        self.update_matrices(nodes=[self.branches()[3]])
+        self.update_partials(mode="none", nodes=self.post_order(self.internal))
+        self.root_call("root", cum=False)
+        self.update_partials(mode="none", nodes=self.post_order(self.internal))
+        self.root_call("root", cum=False)
+        self.get_sites()
+
+    def motif_f(self):
+        """updatePrePartials and the edge derivatives, then with one call between them that reads, writes or leaves alone the list's
+        buffers and matrices (by seed)"""
+        L = self.L
+        self.variant = v = F_VARIANTS[(self.seed + 3 * self.f_count) % len(F_VARIANTS)]
+        self.f_count += 1
+        self.update_partials(mode="none", nodes=self.post_order(self.internal))
+        self.root_call("root", cum=False)
+        self.set_root_pre()
+        self.update_pre(whole=True)
+        # the order of a gradient evaluation first: setDifferentialMatrix leaves the list alone and the derivatives are answered from it
+        # — the sums alone (it stays held back) or with their squares (it runs together with them and is sent again)
+        self.set_differential(0)
+        first = (self.seed + self.f_count) % 2
+        self.edge_differentials(want=first, all_edges=True)
+        if first == 1:
+            self.update_pre(whole=True)
+        child = self.left[L.root]
+        inner = [n for n in self.internal if n != L.root]
+        node = inner[len(inner) // 2]
+        if v == "read_pre":
+            self.emit("getPartials", [L.pre(node), NONE], "getPartials:pre")
+        elif v == "read_post":
+            self.get_partials(L.post(node, self.cur[node]), scaled=False)
+        elif v == "write_post":
+            self.set_partials(L.post(node, self.cur[node]))
+        elif v == "write_matrix":
+            self.update_matrices(nodes=[child], flip=False)
+        elif v == "write_pre":
+            self.set_partials(L.pre(child))
+        elif v == "scale_call":
+            self.reset_scale(L.cum[1])
+        elif v == "model_call":
+            self.set_weights(0)
+            self.set_weights(1)
+        elif v == "root_call":
+            self.root_call("root", cum=False)
+            self.get_sites()
+        self.edge_differentials(want=(self.seed // 2 + self.f_count) % 2, all_edges=True)
+        self.edge_differentials(want=int(self.rng.integers(3)), all_edges=True)
+        if v == "scale_call":
+            self.get_scale(L.cum[1])
+        self.cross_products()
+        self.get_pre_partials()
+
+    def motif_g(self):
+        """the identical operation list twice with only matrices changed (a plan replayed from the cache), then the same list with
+        one buffer index flipped"""
+        L = self.L
+        nodes = self.post_order(self.internal)
+        self.update_partials(mode="none", nodes=nodes)
+        self.root_call("root", cum=False)
+        self.update_matrices(nodes=self.branches(), flip=False)
+        self.repeat_list()
+        self.root_call("root", cum=False)
+        meta = dict(self.last_list["meta"])
+        n = nodes[len(nodes) // 2]
+        meta[n] ^= 1
+        self.update_partials(mode="none", nodes=nodes, dest_set=meta)
+        self.root_call("root", cum=False)
+        self.get_partials(L.post(n, self.cur[n]), scaled=False)
+
+    def motif_h(self):
+        """copyScaleFactors raw -> cumulative slot and cumulative -> raw slot, then a read-mode list and an accumulate"""
+        L = self.L
+        nodes = self.post_order(self.internal)
+        self.update_partials(mode="write", cum_on_call=False, nodes=nodes)
+        a, b = nodes[0], nodes[1]
+        self.reset_scale(L.cum[0])
+        self.accumulate(L.cum[0], [L.scale(n, self.cur[n]) for n in nodes])
+        self.copy_scale(L.cum[1], L.scale(a, self.cur[a]))                     # raw factors into a cumulative slot
+        spare_raw = L.scale(b, self.cur[b] ^ 1)
+        self.copy_scale(spare_raw, L.cum[0])                                    # logarithms into a per-node slot
+        self.get_scale(L.cum[1])
+        self.get_scale(spare_raw)
+        self.update_matrices(nodes=self.branches()[:4])
+        self.update_partials(mode="read", nodes=nodes)
+        self.reset_scale(L.cum[0])
+        self.accumulate(L.cum[0], [L.scale(n, 0) for n in nodes if self.sdef[L.scale(n, 0)] == "raw"] + [L.cum[1]])
+        self.root_call("root", cum=True)
+        self.get_scale(L.cum[0])
+
+    def motif_i(self):
+        """convolve into a slot that the last list used as a branch matrix, then that list again"""
+        L = self.L
+        nodes = self.post_order(self.internal)
+        self.update_partials(mode="none", nodes=nodes)
+        self.root_call("root", cum=False)
+        child = self.left[nodes[-1]]
+        self.triples("convolveTransitionMatrices", result=L.matrix(child, self.mcur[child]))
+        self.repeat_list()
+        self.root_call("root", cum=False)
+        self.get_sites()
+
+    # ---- the weighted draw -----------------------------------------------------------------------------------------------------
+    def table(self):
+        rng = self.rng
+        return [
+            (2, "setEigenDecomposition", lambda: self.set_eigen(int(rng.integers(2)), same=rng.random() < 0.25)),
+            (1, "setCategoryRates", lambda: self.set_rates(0, indexed=False)),
+            (1, "setCategoryRatesWithIndex", lambda: self.set_rates(int(rng.integers(2)), indexed=True)),
+            (1, "setCategoryWeights", lambda: self.set_weights(int(rng.integers(2)))),
+            (1, "setStateFrequencies", lambda: self.set_frequencies(int(rng.integers(2)))),
+            (1, "setPatternWeights", self.set_pattern_weights),
+            (2, "setTipStates", lambda: self.resend_tip_of_kind("compact")),
+            (2, "setTipPartials", lambda: self.resend_tip_of_kind("partials")),
+            (2, "setPartials", self.set_partials),
+            (0.5, "compactToPartials", self.compact_to_partials),
+            (1.5, "setTipEmission", self.set_tip_emission),
+            (4, "updateTransitionMatrices", lambda: self.update_matrices(slots=self.L.spare[:int(rng.integers(1, 3))] if rng.random() < 0.2 else None)),
+            (2, "updateTransitionMatricesWithMultipleModels", lambda: self.update_matrices(multiple=True)),
+            (2, "setTransitionMatrix", self.set_transition_matrix),
+            (2, "convolveTransitionMatrices", lambda: self.triples("convolveTransitionMatrices")),
+            (2, "addTransitionMatrices", lambda: self.triples("addTransitionMatrices")),
+            (1.5, "transposeTransitionMatrices", self.transpose),
+            (3, "getTransitionMatrix", self.get_matrix),
+            (3, "updatePartials:none", lambda: self.update_partials(mode="none", again=rng.random() < 0.15)),
+            (3, "updatePartials:write", lambda: self.update_partials(mode="write", cum_on_call=False, again=rng.random() < 0.15)),
+            (3, "updatePartials:read", lambda: self.update_partials(mode="read")),
+            (2, "updatePartials:cumulative", lambda: self.update_partials(mode="write", cum_on_call=True)),
+            (1, "waitForPartials", self.wait_for_partials),
+            (2, "resetScaleFactors", self.reset_scale),
+            (3, "accumulateScaleFactors", self.accumulate),
+            (2, "removeScaleFactors", self.remove),
+            (2, "copyScaleFactors", self.copy_scale),
+            (3, "getLogScaleFactors", self.get_scale),
+            (4, "calculateRootLogLikelihoods:root", lambda: self.root_call("root", cum=False)),
+            (2, "calculateRootLogLikelihoods:other", lambda: self.root_call("other", cum=False)),
+            (3, "calculateRootLogLikelihoods:cumulative", lambda: self.root_call(cum=True)),
+            (3, "getSiteLogLikelihoods", self.get_sites),
+            (3, "getPartials", lambda: self.get_partials(scaled=False)),
+            (2, "getPartials:scaled", lambda: self.get_partials(scaled=True)),
+            (2, "getPartialsBatch", self.get_partials_batch),
+            (1.5, "setRootPrePartials", self.set_root_pre),
+            (3, "updatePrePartials", self.update_pre),
+            (1, "setDifferentialMatrix", lambda: self.set_differential(int(rng.integers(2)))),
+            (3, "calculateEdgeDifferentials", self.edge_differentials),
+            (1.5, "calculateCrossProductDifferentials", self.cross_products),
+            (2, "getPartials:pre", self.get_pre_partials),
+        ]
+
+    def draw(self):
+        """one drawn action: one this sequence has not made yet while there is any (every sequence makes every action), else by weight"""
+        rng = self.rng
+        table = [t for t in self.table() if t[1] in actions_for(self.L.S)]
+        seen = set(r["action"] for r in self.rec[self.prelude_end:])
+        missing = [t for t in table if t[1] not in seen and t[1] not in self.gave_up]
+        if missing:
+            t = missing[int(rng.integers(len(missing)))]
+            if t[2]() is False:
+                if t[1] == "removeScaleFactors":
+                    c = self.L.cum[0]
+                    self.reset_scale(c)
+                    if self.accumulate(c) is not False and self.remove() is not False:
+                        return
+                self.gave_up.add(t[1])                       # (no compact tip left to turn into a partials tip: it has happened)
+            return
+        w = np.array([t[0] for t in table], dtype=float)
+        while True:
+            k = int(rng.choice(len(table), p=w / w.sum()))
+            if table[k][2]() is not False:
+                return
+
+    def run(self):
+        self.prelude()
+        start = len(self.rec)
+        order = [MOTIFS[k] for k in self.rng.permutation(len(MOTIFS))]
+        budget = self.length
+        # the motifs at seeded positions: between two of them a seeded share of the calls the weighted draw fills
+        gaps = self.rng.dirichlet(np.full(len(order) + 1, 2.0))
+        for k, letter in enumerate(order):
+            self.motif, self.variant = letter, None
+            getattr(self, "motif_" + letter)()
+            self.motif = self.variant = None
+        motif_calls = len(self.rec) - start
+        fill = max(4, budget - motif_calls)
+        # (the motifs were generated to learn their size; generate again with the filler between them)
+        return motif_calls, [int(round(g * fill)) for g in gaps], order
+
+
+def generate(shape, seed, length=100):
+    """-> records.  `length`: calls after the set-up prelude, motifs included (at least what the motifs and a few drawn calls between
+    them need)."""
+    probe = Generator(shape, seed, length)
+    _, gaps, order = probe.run()
+    g = Generator(shape, seed, length)
+    g.rng = np.random.default_rng([seed, g.L.S, g.L.C, g.L.T, g.L.P, 1])
+    g.prelude()
+    for k, letter in enumerate(order):
+        target = len(g.rec) + gaps[k]
+        while len(g.rec) < target:
+            g.draw()
+        g.motif, g.variant = letter, None
+        getattr(g, "motif_" + letter)()
+        g.motif = g.variant = None
+    target = len(g.rec) + gaps[-1]
+    while len(g.rec) < target:
+        g.draw()
+    for _ in range(2 * len(ACTIONS)):                        # whatever action the sequence still lacks
+        seen = set(r["action"] for r in g.rec[g.prelude_end:])
+        if all(a in seen or a in g.gave_up for a in actions_for(g.L.S)):
+            break
+        g.draw()
+    return g.rec
+
+
+def dump(path, shape, seed, records):
+    with open(path, "w") as f:
+        json.dump({"shape": list(shape), "seed": seed, "records": records}, f)
+
+
+def load(path):
+    with open(path) as f:
+        d = json.load(f)
+    return tuple(d["shape"]), d["seed"], d["records"]
+
+
+# ---- running records on a binding object ---------------------------------------------------------------------------------------
+
+def create(shape, factory, **kw):
+    """factory: beagle.Beagle (or a callable with its signature) -> the instance of this shape's layout"""
+    return factory(*Layout(shape).create_args(), **kw)
+
+
+def expanded_emission(S, P, codes, table, extra):
+    """[P][S] partials of a tip with an emission table: row codes[p], all ones for a code outside the table; 4 states: the sequence-error
+    model restated pattern by pattern (tests/tip_models_reference.py)"""
+    codes, table = np.asarray(codes), np.asarray(table, dtype=float)
+    if S == 4 and "base_rate" in extra:
+        import tip_models_reference
+        return tip_models_reference.sequence_error_partials(codes, "all", extra["base_rate"], None, 0.0, False, 0.0, False)
+    out = np.ones((P, S))
+    ok = (codes >= 0) & (codes < len(table))
+    out[ok] = table[codes[ok]]
+    return out
+
+
+def execute(b, rec, side="engine"):
+    """One call.  side "oracle": the three calls the oracle has no entry point for are made from its own ones (setTipEmission: setTipPartials
+    of the expanded table; addTransitionMatrices: the numpy sum of its two matrices, then setTransitionMatrix; getPartialsBatch: single
+    getPartials calls; waitForPartials: nothing to wait for).  -> (return code, [(kind, array), ...])"""
+    m, a = rec["m"], rec["a"]
+    reads = []
+    try:
+        if m == "calculateRootLogLikelihoods":
+            out = [0.0]
+            b.calculateRootLogLikelihoods(a[0], a[1], a[2], a[3], a[4], out)
+            reads.append(("sum", np.array(out)))
+        elif m == "getSiteLogLikelihoods":
+            reads.append(("site", b.getSiteLogLikelihoods()))
+        elif m == "getLogScaleFactors":
+            reads.append(("scale", b.getLogScaleFactors(a[0])))
+        elif m == "getTransitionMatrix":
+            reads.append(("matrix", b.getTransitionMatrix(a[0])))
+        elif m == "getPartials":
+            reads.append(("partials", b.getPartials(a[0], a[1])))
+        elif m == "getPartialsBatch":
+            if side == "oracle":
+                for k, buf in enumerate(a[0]):
+                    reads.append(("partials", b.getPartials(buf, NONE if a[1] is None else a[1][k])))
+            else:
+                reads += [("partials", p) for p in b.getPartialsBatch(a[0], a[1])]
+        elif m == "calculateEdgeDifferentials":
+            s1, s2, per = b.calculateEdgeDifferentials(a[0], a[1], a[2], a[3], a[4], want_per_pattern=a[5][0], want_squared=a[5][1])
+            reads += [("deriv", x) for x in (s1, s2, per) if x is not None]
+        elif m == "calculateCrossProductDifferentials":
+            reads.append(("deriv", b.calculateCrossProductDifferentials(*a)))
+        elif m == "setTipEmission":
+            if side == "oracle":
+                b.setTipPartials(a[0], expanded_emission(b.stateCount, b.patternCount, a[1], a[2], a[3]))
+            else:
+                b.setTipEmission(a[0], a[1], a[2])
+        elif m == "addTransitionMatrices" and side == "oracle":
+            for f, s, r in zip(*a[:3]):
+                b.setTransitionMatrix(r, b.getTransitionMatrix(f) + b.getTransitionMatrix(s), 1.0)
+        elif m == "waitForPartials" and side == "oracle":
+            pass
+        else:
+            getattr(b, m)(*a)
+    except Exception as e:                                   # beagle.BeagleException
+        if not hasattr(e, "code"):
+            raise
+        return e.code, []
+    return 0, reads
+
+
+def deviation(kind, got, want):
+    """The error of a read, normalised so that the project's bound is 1e-10 for every kind: sums and site values relative; log scale
+    factors relative, against 1 where the value is smaller (a factor near 1 has a logarithm near 0); node partials against each
+    pattern's largest entry (tests/test_gpu_parity.py test_engine_matches_oracle), a transition matrix likewise against the largest entry
+    of each category's matrix; derivative outputs against max(1, largest value) (tests/test_gpu_gradients.py)."""
+    got, want = np.asarray(got, dtype=float), np.asarray(want, dtype=float)
+    if got.shape != want.shape:
+        return float("inf")
+    if not (np.isfinite(got).all() and np.isfinite(want).all()):
+        return float("nan")
+    if kind in ("sum", "site"):
+        return float(np.max(np.abs(got - want) / np.maximum(np.abs(want), 1e-300)))
+    if kind == "scale":
+        return float(np.max(np.abs(got - want) / np.maximum(np.abs(want), 1.0)))
+    if kind == "partials":
+        scale = np.maximum(np.abs(want).max(axis=(0, 2), keepdims=True), 1e-300)
+        return float(np.max(np.abs(got - want) / scale))
+    if kind == "matrix":
+        scale = np.maximum(np.abs(want).max(axis=(1, 2), keepdims=True), 1e-300)
+        return float(np.max(np.abs(got - want) / scale))
+    if kind == "deriv":
+        return float(np.max(np.abs(got - want)) / max(1.0, float(np.max(np.abs(want)))))
+    raise ValueError(kind)
+
+
+def describe(rec):
+    def short(x):
+        s = json.dumps(x)
+        return s if len(s) <= 60 else s[:57] + "..."
+    return "%s(%s)" % (rec["m"], ", ".join(short(x) for x in rec["a"]))
+
+
+def replay(path, upto=None, out=print):
+    """Engine and oracle side by side up to step `upto` (inclusive); prints the first diverging read and stops at the first non-zero
+    return code or exception.  -> the step it stopped at, or None."""
+    import os
+    import sys
+    here = os.path.dirname(os.path.abspath(__file__))
+    for p in (here, os.path.dirname(here)):
+        if p not in sys.path:
+            sys.path.insert(0, p)
+    import beast_mcmc_amd as bm
+    import helpers
+    shape, seed, records = load(path)
+    eng = create(shape, bm.beagle.Beagle)
+    ora = create(shape, bm.beagle.Beagle, library=helpers.oracle_library())
+    stopped = None
+    try:
+        for step, rec in enumerate(records if upto is None else records[:upto + 1]):
+            rc_e, reads_e = execute(eng, rec, "engine")
+            rc_o, reads_o = execute(ora, rec, "oracle")
+            if rc_e or rc_o:
+                out("step %d %s: return codes engine %d, oracle %d" % (step, describe(rec), rc_e, rc_o))
+                stopped = step
+                break
+            worst = max([deviation(k, g, w) for (k, g), (_, w) in zip(reads_e, reads_o)] + [0.0], key=lambda x: (x != x, x))
+            if not worst <= BOUND:
+                out("step %d %s: first diverging read, deviation %.3e (bound %.0e)" % (step, describe(rec), worst, BOUND))
+                stopped = step
+                break
+        else:
+            out("shape %s seed %d: no read diverges in %d steps" % (shape, seed, step + 1))
+    finally:
+        eng.finalize()
+        ora.finalize()
+    return stopped
+
+
+if __name__ == "__main__":
+    import argparse
+    ap = argparse.ArgumentParser(description="replay a recorded call sequence on the engine and the oracle")
+    ap.add_argument("--replay", required=True, metavar="FILE")
+    ap.add_argument("--upto", type=int, default=None, metavar="N")
+    args = ap.parse_args()
+    replay(args.replay, args.upto)

@@ -1,0 +1,155 @@
+"""Seeded random call sequences (tests/call_sequences.py) on the engine and the CPU oracle in lockstep.
+
+Almost every call into the engine is deferred or cached somewhere (uploads that ride in the next launch, a one-launch walk held back
+until the next call, a pre-order list held back until something reads or writes its buffers, plans replayed from a cache, virtual
+buffers, site values fetched ahead); every such mechanism has a scripted test that walks the order its author thought of.  Here the
+orders are generated: per (shape, seed) three instances execute the same records call by call —
+
+  * the engine on its defaults,
+  * a twin created under BEAGLE_MI355_COPY_ENGINE_UPLOADS=1 and BEAGLE_MI355_NO_PLAN_CACHE=1, the two switches whose row in
+    tests/test_gpu_switches.py SWITCHES promises the same bits,
+  * the CPU oracle —
+
+and AT EVERY CALL the three return codes are equal, every read of the default engine equals the twin's bit for bit, and is within the
+project's bounds of the oracle's (call_sequences.deviation: 1e-10 relative for sums, site values and log scale factors; node partials
+and pre-order partials within 1e-10 of each pattern's largest entry as test_gpu_parity.test_engine_matches_oracle normalises them, a
+transition matrix likewise against its largest entry; derivative outputs as test_gpu_gradients.test_gradient_matches_oracle's
+``close``).  tests/test_call_sequences_host.py measures that the oracle itself is within 1e-11 of its long-double mode on every read of
+every sequence used here.
+
+A mismatch names shape, seed, step and call, leaves the records in the test's tmp_path and gives the replay line.
+
+Route evidence (counters read at the end of each sequence, summed over a shape's seeds): on 4 states a root call answered inside the
+walk's launch, site values found prefetched, ticket walks, slice accumulations, pre-order lists answered held (fused or walked) and a
+held list forced to run by a later call; on 20 and 61 states the pattern walks.  NOT reached at these sizes: the class tables of
+repeated sub-patterns (repeatStats; the engine leaves them off below 64 KiB partials buffers) — tests/test_gpu_repeats.py holds them
+under BEAGLE_MI355_REPEATS_ANY_SIZE=1.
+
+One more parametrisation runs shape (4, 4, 12, 130) on the pattern-sharded handle (three shards on one GPU, as
+tests/test_gpu_sharded_instance.py creates it) against the oracle only; a read the handle answers with NO_IMPLEMENTATION is dropped.
+"""
+import collections
+import os
+
+import numpy as np
+import pytest
+
+import beast_mcmc_amd as bm
+import call_sequences as cs
+from test_call_sequences_host import CASES, SEEDS, SHAPES, case_id, records
+
+pytestmark = pytest.mark.gpu
+
+TWIN_ENV = {"BEAGLE_MI355_COPY_ENGINE_UPLOADS": "1", "BEAGLE_MI355_NO_PLAN_CACHE": "1"}
+READ_ONLY = ("getTransitionMatrix", "getLogScaleFactors", "getSiteLogLikelihoods", "getPartials", "getPartialsBatch",
+             "calculateEdgeDifferentials", "calculateCrossProductDifferentials")
+NO_IMPLEMENTATION = -7
+
+
+def created_under(env, make):
+    """make() with the BEAGLE_MI355_* switches `env` in force (the engine reads them when an instance is created)"""
+    old = {k: os.environ.get(k) for k in env}
+    os.environ.update(env)
+    try:
+        return make()
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
+def fail(what, shape, seed, step, recs, tmp_path):
+    path = str(tmp_path / ("sequence_S%d_C%d_T%d_P%d_seed%d.json" % (shape + (seed,))))
+    cs.dump(path, shape, seed, recs)
+    raise AssertionError("shape %s seed %d step %d %s: %s\nreplay: python tests/call_sequences.py --replay %s --upto %d"
+                         % (shape, seed, step, cs.describe(recs[step]), what, path, step))
+
+
+def counters(b):
+    info, grad = b.walkLaunchInfo(), b.gradientStats()
+    return {"rootFusedCount": b.rootFusedCount(), "sitePrefetchCount": b.sitePrefetchCount(), "ticket_walks": info["ticket_walks"],
+            "slice_accumulations": info["slice_accumulations"], "held_answered": grad["fused"] + grad["walked"], "late": grad["late"],
+            "walks": b.walkStats()["walks"]}
+
+
+def lockstep(shape, seed, oracle_lib, tmp_path, sharded=False):
+    """-> the default engine's counters at the end of the sequence"""
+    recs = records(shape, seed)
+    instances = []
+    try:
+        if sharded:
+            g = len(bm.beagle.engine().resource_list()) - 2
+            eng = created_under({"BEAGLE_MI355_SHARDS": "3"}, lambda: cs.create(shape, bm.beagle.Beagle, resourceList=(g + 1,)))
+            instances.append(eng)
+            twin = None
+        else:
+            eng = cs.create(shape, bm.beagle.Beagle)
+            instances.append(eng)
+            twin = created_under(TWIN_ENV, lambda: cs.create(shape, bm.beagle.Beagle))
+            instances.append(twin)
+        ora = cs.create(shape, bm.beagle.Beagle, library=oracle_lib)
+        instances.append(ora)
+        worst = collections.defaultdict(float)
+        for step, rec in enumerate(recs):
+            rc_e, got = cs.execute(eng, rec, "engine")
+            if sharded and rc_e == NO_IMPLEMENTATION:
+                assert rec["m"] in READ_ONLY, (step, cs.describe(rec))       # (only a read can be left out without the two sides parting)
+                continue
+            rc_o, want = cs.execute(ora, rec, "oracle")
+            if twin is not None:
+                rc_t, same = cs.execute(twin, rec, "engine")
+                if not (rc_e == rc_t == rc_o):
+                    fail("return codes engine %d, twin %d, oracle %d" % (rc_e, rc_t, rc_o), shape, seed, step, recs, tmp_path)
+                for k, ((kind, a), (_, b)) in enumerate(zip(got, same)):
+                    if not np.array_equal(a, b):
+                        fail("read %d (%s): the default engine and its twin (%s) differ, by at most %.3e"
+                             % (k, kind, " ".join(sorted(TWIN_ENV)), float(np.max(np.abs(a - b)))), shape, seed, step, recs, tmp_path)
+            elif rc_e != rc_o:
+                fail("return codes sharded engine %d, oracle %d" % (rc_e, rc_o), shape, seed, step, recs, tmp_path)
+            if len(got) != len(want):
+                fail("%d reads on the engine, %d on the oracle" % (len(got), len(want)), shape, seed, step, recs, tmp_path)
+            for k, ((kind, a), (_, b)) in enumerate(zip(got, want)):
+                d = cs.deviation(kind, a, b)
+                worst[kind] = max(worst[kind], d) if d == d else d
+                if not d <= cs.BOUND:
+                    fail("read %d (%s): engine against oracle %.3e, bound %.0e" % (k, kind, d, cs.BOUND), shape, seed, step, recs, tmp_path)
+        print("shape %s seed %d%s: largest deviation from the oracle by kind of read: %s"
+              % (shape, seed, ", sharded" if sharded else "", ", ".join("%s %.1e" % kv for kv in sorted(worst.items()))))
+        return counters(eng)
+    finally:
+        for b in instances:
+            b.finalize()
+
+
+_counters = {}
+
+
+@pytest.mark.parametrize("case", CASES, ids=case_id)
+def test_engine_twin_and_oracle_in_lockstep(case, oracle_lib, tmp_path):
+    shape, seed = case
+    _counters[case] = None                                   # (failed, unless the next line returns: not run a second time below)
+    _counters[case] = lockstep(shape, seed, oracle_lib, tmp_path)
+
+
+@pytest.mark.parametrize("shape", [s for s in SHAPES if s[0] in (4, 20, 61)], ids=lambda s: "S%d-C%d-T%d-P%d" % s)
+def test_the_sequences_take_the_deferred_routes(shape, oracle_lib, tmp_path):
+    """The sequences must not all fall back to a general path: the counters of the branches this module exists for, summed over the
+    shape's seeds (a sequence that the test above has not run is run here; one that failed there counts nothing)."""
+    total = collections.Counter()
+    for seed in SEEDS[shape]:
+        if (shape, seed) not in _counters:
+            _counters[(shape, seed)] = lockstep(shape, seed, oracle_lib, tmp_path)
+        total.update(_counters[(shape, seed)] or {})
+    print("shape %s: %s" % (shape, dict(total)))
+    if shape[0] == 4:
+        for key in ("rootFusedCount", "sitePrefetchCount", "ticket_walks", "slice_accumulations", "held_answered", "late"):
+            assert total[key] > 0, (key, dict(total))
+    else:
+        assert total["walks"] > 0, dict(total)
+
+
+@pytest.mark.parametrize("seed", [1, 2])
+def test_sharded_handle_and_oracle_in_lockstep(seed, oracle_lib, tmp_path):
+    lockstep((4, 4, 12, 130), seed, oracle_lib, tmp_path, sharded=True)
