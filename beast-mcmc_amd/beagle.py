@@ -124,7 +124,7 @@ ABI_SYMBOLS = ["beagleGetVersion", "beagleGetCitation", "beagleGetResourceList",
               ["beagle" + k for k in _PROTOS] + \
               ["beagleMi355SetStream", "beagleMi355CalculateRootLogLikelihoodsDevice", "beagleMi355Synchronize",
                "beagleMi355KernelTimer", "beagleMi355DeviceBytes", "beagleMi355WalkStats", "beagleMi355GradientStats", "beagleMi355GetPartialsBatch", "beagleMi355SampleAncestralStates", "beagleMi355SampleMarkovJumps", "beagleMi355SampleMarkovJumpsUniformized",
-               "beagleMi355NodeHeightDerivatives", "beagleMi355SetTipEmission", "beagleMi355TipEmissionStats",
+               "beagleMi355SimulateSequences", "beagleMi355NodeHeightDerivatives", "beagleMi355SetTipEmission", "beagleMi355TipEmissionStats",
                "beagleMi355GetPartialsPinned", "beagleMi355GetSiteLogLikelihoodsPinned",
                "beagleMi355KernelTimerCalls", "beagleMi355WalkHealth", "beagleMi355RepeatStats", "beagleMi355WalkLaunchInfo", "beagleMi355RootFusedCount", "beagleMi355SitePrefetchCount", "beagleMi355KernelTimerRestart", "beagleMi355GetDimensions", "beagleMi355GetCommUniqueId", "beagleMi355CommInit", "beagleMi355CommInfo", "beagleMi355CalculateRootLogLikelihoodsAllReduce"] + \
               ["beagleBasta" + k for k in ("AllocateCoalescentBuffers", "UpdatePartials", "AccumulatePartials", "GetBuffer", "GetBufferLength", "Stats",
@@ -534,6 +534,30 @@ class Beagle:
                                                            C.c_void_p, _IP])
         self._check("sampleAncestralStates", f(self.instance, _ip(rows), rows.shape[0], categoryWeightsIndex, stateFrequenciesIndex,
                                                int(seed) & 0xFFFFFFFFFFFFFFFF, 1 if map else 0, states.ctypes.data, _ip(cats)))
+        return states, cats
+
+    def simulateSequences(self, rows, site_count, weights_index, freqs_index, seed, root_states=None, rate_categories=None):
+        """An alignment drawn from the model down the tree on the device (include/beagle_mi355.h beagleMi355SimulateSequences).
+        ``rows``: [nodeCount][3] rows {outRow, matrixIndex, parentRow}, the root first; outRow -1: the node's states are not
+        returned.  ``root_states`` ([site_count], each < stateCount) and ``rate_categories`` ([site_count], each < categoryCount)
+        replace the root's draw and the category draw.  -> (states uint8 [1 + max outRow, site_count], categories int32
+        [site_count]).  A draw from a vector whose total was not finite and > 0 raises BeagleException with code -8."""
+        rows = _i(rows).reshape(-1, 3)
+        site_count = int(site_count)
+        n_out = int(rows[:, 0].max()) + 1 if rows.shape[0] else 0
+        if n_out < 1 or site_count < 1:
+            raise BeagleException("simulateSequences", -5)
+        states = np.zeros((n_out, site_count), dtype=np.uint8)
+        cats = np.zeros(site_count, dtype=np.int32)
+        root = None if root_states is None else np.ascontiguousarray(root_states, dtype=np.uint8)
+        given = None if rate_categories is None else _i(rate_categories)
+        if (root is not None and root.size != site_count) or (given is not None and given.size != site_count):
+            raise ValueError("root_states and rate_categories must have one entry per site")
+        f = self._ext("beagleMi355SimulateSequences", [C.c_int, _IP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_ulonglong, C.c_int,
+                                                       C.c_void_p, _IP, C.c_void_p, _IP])
+        self._check("simulateSequences", f(self.instance, _ip(rows), rows.shape[0], site_count, weights_index, freqs_index,
+                                           int(seed) & 0xFFFFFFFFFFFFFFFF, 0, None if root is None else root.ctypes.data, _ip(given),
+                                           states.ctypes.data, _ip(cats)))
         return states, cats
 
     def setTipEmission(self, tipIndex, codes, emission):

@@ -7,6 +7,7 @@
 //   engine_root.cpp      the calls that observe a likelihood: root sums, the polled result page, site log-likelihoods
 //   engine_readback.cpp  partials and scale factors back to the host
 //   engine_sampling.cpp  the device samplers (ancestral draws, Markov jumps, uniformized histories)
+//   engine_simulate.cpp  sequence simulation down the tree from the branch matrices
 //   engine_nodeheight.cpp  node-height gradients and diagonal Hessians in one call
 //   engine_tipemission.cpp  tip error models: emission tables folded into the tip branch matrices
 //   engine_stats.cpp     stream, synchronisation, kernel timer, counters
@@ -264,6 +265,9 @@ struct Instance {
     // uniformized Markov jumps (beagleMi355SampleMarkovJumpsUniformized): R^n table, rows, registers, sums, counts, grown on demand;
     // the event list of the last call that asked for one
     DevBuf uniformDev, eventDev;
+    // sequence simulation (beagleMi355SimulateSequences, engine_simulate.cpp): states [slots][chunk] | categories [chunk] | error
+    // word | cumulative tables | their meta words, grown on demand
+    DevBuf simulateDev;
     // BASTA structured coalescent (beagleBastaAllocateCoalescentBuffers, engine_basta.cpp): null on every other instance
     Basta* basta = nullptr;
     // tip error models (beagleMi355SetTipEmission, engine_tipemission.cpp): null on an instance that was never given an emission table

@@ -525,6 +525,30 @@ struct AncestralRow {
 void launchSampleAncestral(hipStream_t stream, const AncestralRow* dRows, int nRows, const double* catWeights, const double* freqs,
                            int P, int S, int C, bool tiled, int globalP, int pOffset, unsigned long long seed, bool map,
                            uint8_t* states, int* cats, unsigned* fpError);
+// ---- sequence simulation (kernels_simulate.hip; beagleMi355SimulateSequences) -------------------------------------------
+// One row of the pre-order node list, resolved on the host: its branch matrix [C][S][S] (nullptr at the root), the scratch row
+// ("slot") its states go to and the slot of its parent (-1 at the root); parentIsPrev: the parent is the row right before it, whose
+// states the site kernel still holds in a register.
+struct SimRow {
+    const double* matrix;
+    int parentSlot, slot, parentIsPrev, pad;
+};
+constexpr int SIM_SITES_PER_THREAD = 4;      // consecutive sites a thread carries: independent chains, one packed store per row
+// The cumulative tables of a call: doubles [(nRows - 1)][C][S] rows of S | the state frequencies' row of S | the category weights'
+// row of C, ints (meta) one per row.  A row holds the running maximum of the cumulative sums cum_i (sums in index order), so that
+// "the first i with u < cum_i" is "the number of entries that are not above u" whatever the signs of the terms; meta = the largest
+// index of a positive term.  A row whose total is not finite and > 0 is all NaN with meta -1: nothing is above u, and the draw
+// that falls through to meta finds the error there.
+inline size_t simTableRows(int nRows, int S, int C) { return (size_t)(nRows - 1) * C * S + 2; }
+inline size_t simTableDoubles(int nRows, int S, int C) { return (size_t)(nRows - 1) * C * S * S + S + C; }
+void launchSimTables(hipStream_t stream, const SimRow* dRows, int nRows, const double* catWeights, const double* freqs, int S, int C,
+                     double* table, int* meta);
+// states[slot][stride] (uint8; stride a multiple of 4) and cats[stride] for sites siteOffset .. siteOffset + nSites - 1 of an
+// alignment of siteCount sites, ONE launch.  haveRoot: slot rows[0].slot already holds the root's states; haveCats: cats is given.
+// *fpError |= 1 when a vector that was drawn from had a total that is not finite and > 0 (the state is then 0).
+void launchSimSites(hipStream_t stream, const SimRow* dRows, int nRows, const double* table, const int* meta, int S, int C,
+                    int nSites, size_t stride, unsigned long long siteCount, unsigned long long siteOffset, unsigned long long seed,
+                    bool haveRoot, bool haveCats, uint8_t* states, int* cats, unsigned* fpError);
 // ---- Markov jumps (kernels_markovjumps.hip; beagleMi355SampleMarkovJumps) ------------------------------------------------
 constexpr int MAX_JUMP_REGISTERS = 8;
 // One row of the node list: the branch's time and rate, its matrices [C][S][S] (nullptr at the root) and its parent row

@@ -353,6 +353,38 @@ int beagleMi355GetPartialsBatch(int instance, const int* bufferIndices, const in
 #define BEAGLE_MI355_ANCESTRAL_MAP 1
 int beagleMi355SampleAncestralStates(int instance, const int* nodes, int nodeCount, int categoryWeightsIndex, int stateFrequenciesIndex,
                                      unsigned long long seed, int flags, unsigned char* outStates, int* outRateCategories);
+/* Sequence simulation: ONE call that draws an alignment FROM the model, down the tree — what dr.app.beagle.tools.Partition.traverse
+ * computes from an updateTransitionMatrices and a getTransitionMatrix per branch and a randomChoicePDF per site in Java
+ * (Partition.java:292-431, :519-536; BeagleSequenceSimulator).  It reads branch matrices, category weights and state frequencies and
+ * nothing else: no partials, no patterns — siteCount is independent of the instance's pattern count, updatePartials need never have
+ * been called, and an instance with pattern partitions is served like any other (the caller offsets its matrix indices).
+ *   nodes: nodeCount triples {outRow, matrixIndex, parentRow} in pre-order — row 0 is the root {outRow, ignored, -1}, every other row
+ *          names its branch matrix and a parentRow smaller than its own index.  outRow: the row of outStates that receives the node's
+ *          states, -1 for a node the caller does not want (tips only = outputAncestralSequences false); every outRow >= 0 at most once.
+ *   outStates: [1 + max outRow][siteCount] bytes; rows no node names are left alone.  outRateCategories: [siteCount] or NULL.
+ *   inRateCategories (NULL: drawn): the rate category of every site, each < categoryCount.
+ *   inRootStates (NULL: drawn): the root's state at every site, each < stateCount (setRootSequence).
+ *   flags: none is defined; it must be 0.
+ * Rate category of site s: inRateCategories[s], else (categoryCount > 1) a draw from the category weights, else 0.  Root state:
+ * inRootStates[s], else a draw from the state frequencies.  Row r > 0: a draw from M[category][parentState][.] of its matrix as
+ * beagleGetTransitionMatrix returns it (the caller's matrices: a tip's folded emission table is not part of it).
+ * A draw over p_0 .. p_{n-1} is Partition.randomChoicePDF: cum_i = cum_{i-1} + p_i from cum_{-1} = 0.0 in index order (one IEEE
+ * addition each), the result is the first i with u < cum_i.  Where no i satisfies it — rounding has left the total below u — the
+ * reference returns an invalid index (-Integer.MAX_VALUE); HERE THE RESULT IS THE LARGEST INDEX WITH p_i > 0.  A vector that is
+ * drawn from and whose total cum_{n-1} is not finite and > 0 gives 0 for that draw; every other draw is still made, the outputs are
+ * written and the call returns BEAGLE_ERROR_FLOATING_POINT.
+ * u = SplitMix64 output number ctr + 1 from state `seed` as (z >> 11) * 2^-53 (beagleMi355SampleAncestralStates' numbers), with
+ * ctr = (row * siteCount + site) * 2 for a state and ctr = site * 2 + 1 for the rate category — stateless, so a host can restate
+ * every draw, and the bytes depend on the seed alone: not on the launch shape, not on the chunks the sites are processed in
+ * (BEAGLE_MI355_SIM_CHUNK_SITES=<n> overrides their size), not on the number of GPUs (the sharded handle, resource G+1, splits the
+ * SITES into contiguous ranges; every shard holds all matrices).
+ * The instance is left as it was found: partials, scale buffers, plans, tip states and folded tip emissions are not touched.
+ * BEAGLE_ERROR_OUT_OF_RANGE for nodes or outStates NULL, nodeCount < 1, siteCount < 1, non-zero flags, a bad weight, frequency or
+ * matrix index, a parent row that is not earlier than the row itself, an outRow below -1 or used twice, an input state >= stateCount
+ * or an input category >= categoryCount (or negative).  An extension: no BEAST class calls it today. */
+int beagleMi355SimulateSequences(int instance, const int* nodes, int nodeCount, int siteCount, int categoryWeightsIndex,
+                                 int stateFrequenciesIndex, unsigned long long seed, int flags, const unsigned char* inRootStates,
+                                 const int* inRateCategories, unsigned char* outStates, int* outRateCategories);
 /* Node heights: d lnL / d h_i and d^2 lnL / d h_i^2 for every listed internal node i in ONE call, from the partials where they are —
  * what DiscreteTraitNodeHeightDelegate.getNodeDerivatives computes from a getPartials per post-order and per pre-order buffer and a
  * getTransitionMatrix per branch (DiscreteTraitNodeHeightDelegate.java:63-200; the NodeHeightGradient / NodeHeightHessian traits of
