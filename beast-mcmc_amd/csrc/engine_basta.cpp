@@ -259,12 +259,7 @@ int beagleBastaUpdatePartials(int instance, const int* operations, int operation
     }
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (timeThisCall(in)) {
-        if (in->eventsUsed == in->events.size()) {
-            hipEvent_t x, y;
-            HIP_TRY(hipEventCreate(&x)); HIP_TRY(hipEventCreate(&y));
-            in->events.emplace_back(x, y);
-        }
-        e0 = in->events[in->eventsUsed].first; e1 = in->events[in->eventsUsed].second; in->eventsUsed++;
+        { int rce = nextTimerEvents(in, &e0, &e1); if (rce) return rce; }
         HIP_TRY(hipEventRecord(e0, s));
     }
     int launches = 0;

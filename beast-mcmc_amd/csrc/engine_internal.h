@@ -92,7 +92,6 @@ struct Instance {
     bool walk = false;
     mi355::WalkPlanner planner;
     mi355::Plan plan;                                    // scratch of the current call
-    std::vector<mi355::WalkOp> walkOps;                  // scratch: resolved program
     size_t scaleStride = 0;                              // walk instances: a scale buffer is [factors | reciprocals (pair-interleaved,
                                                          // kernels.h walkPairIndex)], this many doubles apart
     size_t statePairOff = 0;                             // walk instances: a tip's pair-interleaved states follow its plain ones, this many bytes on
@@ -104,25 +103,36 @@ struct Instance {
     uint8_t* dummyTips = nullptr; double* onesScale = nullptr;   // walk instances: all-missing states / all-one factors for the operands a
                                                                  // micro-operation does not use (the assembly loop loads them unconditionally)
     long statFastWalks = 0;
-    // what runPlan derived from a cached plan (planner.h plannedTag): the device program with its addresses resolved
+    // what a walk program stands for in the instance's counters (resetWalkCounters): added once per run, resolved or reused
+    struct WalkTraffic {
+        long memReads = 0, tipReads = 0, scaleReads = 0, scaleWrites = 0, stored = 0, fused = 0;      // (fused: cherries, kernels.h WK_CHERRY)
+        long microOps = 0;                               // of the walk proper (class-table programs: tableRows)
+        long tableRows = 0, tableReads = 0, repeatClades = 0, twoTables = 0, unstoredConsumers = 0;   // repeated sub-patterns (below)
+    };
+    // a plan resolved to device addresses (engine_walk.cpp resolveProgram).  A cached plan's (planner.h plannedTag) is kept in one of
+    // `resolved`; any other resolves into `scratch`, which is never reused and keeps nothing on the device.
     struct Resolved {
-        long tag = 0, epoch = -1;
-        std::vector<mi355::WalkOp> w; std::vector<mi355::WalkSeg> segs; std::vector<int> deps;
-        int maxRange = 0, sinks = 0;                     // (sinks: slices no other slice waits for — one: the whole program leads to its last slice)
+        bool kept = false;                               // one of `resolved`: dProg, folds, repeats and noFoldTag apply to kept programs only
+        long tag = 0, epoch = -1;                        // the plan and the resolveEpoch it was resolved under (scratch: tag stays 0)
+        std::vector<mi355::WalkOp> w; std::vector<mi355::WalkSeg> segs; std::vector<int> deps;      // deps: per device slice the device slices it waits for
+        // how the program is launched, decided when it is resolved (launchWalk / launchWaves)
+        bool oneLaunch = false;                          // every slice in ONE launch of the assembly loop, in `order`
+        std::vector<int> order;                          // oneLaunch: device slice -> slice of the plan in use (critical path first; on tickets the leaves first)
         int leaves = 0;                                  // > 0: the device program is laid out for a launch on tickets — its first `leaves` slices wait for nothing
+        int maxRange = 0, sinks = 0;                     // widest pattern range of a slice; slices no other slice waits for — one: the whole program leads to its last slice
+        std::vector<int> finalStore, finalPart, sinkRows;   // oneLaunch, per device slice: what PendingWalk carries of them when the launch is held back
         std::vector<int> sumRows, wroteScale;            // write-mode programs: the device slices that leave their product of factors behind, the scale buffers the program writes (Instance::lastSums)
-        std::vector<const double*> cm; long fused = 0;   // fused cherries (kernels.h WK_CHERRY): per device micro-operation the cherry's two branch matrices (empty: none fused), their number
-        long memReads = 0, tipReads = 0, scaleReads = 0, scaleWrites = 0, stored = 0;
-        DevBufUncounted dProg; bool dProgValid = false;    // the packed program, resident on the device
+        std::vector<const double*> cm;                   // fused cherries (kernels.h WK_CHERRY): per device micro-operation the cherry's two branch matrices (empty: none fused)
+        WalkTraffic traffic;                             // (traffic.scaleWrites > 0: a run of it writes per-node scale buffers — folds built from them are stale then)
+        DevBufUncounted dProg; bool dProgValid = false;    // the packed program (engine_walk.cpp PackedProgram), resident on the device
         std::vector<int> folds;                          // folded reciprocal vectors the program reads (Instance::folds)
         long foldEpoch = -1;                             // scaleWriteEpoch those vectors were last checked against
         long noFoldTag = 0;                              // the plan whose folds left the safe range: resolved with per-node factors
         // repeated sub-patterns (below): the program was made from `repeats.plan` instead of the planner's own; its last `lower` slices are
         // the class-table programs, launched in front of the others
         bool compressed = false; mi355::RepeatPlan repeats; int lowerRange = 0;
-        long tableRows = 0, tableReads = 0, repeatClades = 0, twoTables = 0, unstoredConsumers = 0;
         bool repeatsMissing = false;                     // a clade of it had no index yet: resolved again once the index is there
-    } resolved[8];                                       // (as many as the planner's cache has ways: planner.h CACHE_WAYS)
+    } resolved[8], scratch;                              // (as many as the planner's cache has ways: planner.h CACHE_WAYS)
     // Read mode, 4 states: a node that is not stored is seen by nobody but its parent, and a partial is linear in each child — so
     // the reciprocal scale factors of the unstored nodes below a stored one are applied ONCE, at that node, as one vector: the
     // entry-wise product of their reciprocal halves (a "fold"; built by k_foldReciprocals whenever a scale buffer has been written
@@ -239,7 +249,7 @@ struct Instance {
         std::vector<int> finalPart;                      // ... and its partition; sinkRows: the slices nothing waits for (a partitioned
         std::vector<int> sinkRows;                       // instance: one per partition in the list — their epilogues finish the partitions' roots)
     } pendingWalk;
-    std::vector<int> snapSourceOf;                       // runPlan's scratch: matrix slot -> the slot its snapshot is being taken from in this plan (-1 between calls)
+    std::vector<int> snapSourceOf;                       // resolveProgram's scratch: matrix slot -> the slot its snapshot is being taken from in this plan (-1 between calls)
     bool deferWalk = true;                               // BEAGLE_MI355_NO_ROOT_FUSION=1: never hold a launch back
     bool copyKeepsWalk = false;                          // (set around an upload the held walk does not read: engine_instance.cpp queueCopy)
     long statRootFused = 0;
@@ -249,7 +259,7 @@ struct Instance {
     int holdSlots = 3;                                   // what the planner was given
     bool eigenComplex = false;                           // created with BEAGLE_FLAG_EIGEN_COMPLEX: eigenvalue arrays are [S real parts | S imaginary parts]
     bool strictWaits = true;                             // a stage's wait does not count on the previous stage's stores retiring behind its
-                                                         // loads (runPlan); BEAGLE_MI355_STRICT_WAITS=0 at creation: it does (1 % faster)
+                                                         // loads (kernels.h walkStageWaits); BEAGLE_MI355_STRICT_WAITS=0 at creation: it does (1 % faster)
     bool virt = false;                                   // some partials buffers may be virtual (walk instances; T32 instances: cherries)
     bool cherry = false;                                 // T32 instance with <= 20 states: tip-tip nodes are not stored (kernels.h CherryDesc)
     long statCherries = 0;
@@ -315,7 +325,7 @@ struct Instance {
     // first error of a deferred operation; surfaces at the next call that observes results.  Atomic: the sharded handle's caller reads and
     // clears it (sharded.cpp takeAsyncError) while the shard's own worker thread may be setting it
     std::atomic<int> asyncError{0};
-    // 4 states: every slice of a walk program in ONE launch (engine_walk.cpp runPlan): per (slice, pattern group) flag words the
+    // 4 states: every slice of a walk program in ONE launch (engine_walk.cpp decideLaunch, launchWalk): per (slice, pattern group) flag words the
     // workgroups signal and poll with the launch's epoch.  BEAGLE_MI355_NO_WALK_FUSION=1 at creation: one launch per wave of slices
     bool fuseWaves = true;
     DevBufUncounted walkFlags; unsigned walkEpoch = 0;   // [flags | tickets], each half of it walkFlags.bytes / 2
@@ -329,7 +339,7 @@ struct Instance {
     bool xcdAware = true;
     // 4 states, assembly loop: a node over two compact tips that is not stored, pays no scale factors and is consumed by the very next
     // micro-operation is not a micro-operation of the device program at all: its consumer evaluates it inside its own stage (kernels.h
-    // WK_CHERRY; engine_walk.cpp runPlan).  Same arithmetic in the same order: bitwise the unfused program.  A third of a tree's nodes.
+    // WK_CHERRY; engine_walk.cpp ProgramResolver::microOp).  Same arithmetic in the same order: bitwise the unfused program.  A third of a tree's nodes.
     // BEAGLE_MI355_NO_CHERRY_FUSION=1 at creation: every micro-operation of the plan is one of the device program (A/B runs, tests)
     bool fuseCherries = true; long statFused = 0;
     // ... and the loop's fetch loads tip states only for children that ARE compact tips (kernels.h WF_NOLOAD1 / 2; programs without
@@ -489,6 +499,16 @@ inline bool timeThisCall(Instance* in) {
     in->timingTick = 0;
     in->timedCalls++;
     return true;
+}
+// the next HIP-event pair of the kernel timer for a call timeThisCall said yes to (one is created when none is left)
+inline int nextTimerEvents(Instance* in, hipEvent_t* first, hipEvent_t* second) {
+    if (in->eventsUsed == in->events.size()) {
+        hipEvent_t a = nullptr, b = nullptr;
+        HIP_TRY(hipEventCreate(&a)); HIP_TRY(hipEventCreate(&b));
+        in->events.emplace_back(a, b);
+    }
+    *first = in->events[in->eventsUsed].first; *second = in->events[in->eventsUsed].second; in->eventsUsed++;
+    return 0;
 }
 
 // ---- the pattern walk (4 states) ------------------------------------------------------------------------------------

@@ -234,14 +234,7 @@ int runOperationsLevels(Instance* in, const int* ops, int count, int tuple, int 
     // all level launches of the call (gaps between levels included — they are part of what the path costs).
     const size_t maxChunkOps = (RING_BYTES / 4) / sizeof(OpDesc);
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (timeThisCall(in)) {
-        if (in->eventsUsed == in->events.size()) {
-            hipEvent_t a, b;
-            HIP_TRY(hipEventCreate(&a)); HIP_TRY(hipEventCreate(&b));
-            in->events.emplace_back(a, b);
-        }
-        e0 = in->events[in->eventsUsed].first; e1 = in->events[in->eventsUsed].second; in->eventsUsed++;
-    }
+    if (timeThisCall(in)) { int rce = nextTimerEvents(in, &e0, &e1); if (rce) return rce; }
     int launches = 0;
     for (int chunkBegin = 0; chunkBegin < launchCount;) {
         const int chunkEnd = (int)std::min<size_t>((size_t)launchCount, (size_t)chunkBegin + maxChunkOps);

@@ -39,14 +39,7 @@ static int nodeHeightDerivatives(Instance* in, const int* nodes, const double* r
     if (general) { rc = products.alloc(chunk * productDoubles * sizeof(double)); if (rc) return rc; }
     double* const dProducts = products.as<double>();
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (timeThisCall(in)) {
-        if (in->eventsUsed == in->events.size()) {
-            hipEvent_t a = nullptr, b = nullptr;
-            if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) return BEAGLE_ERROR_GENERAL;
-            in->events.emplace_back(a, b);
-        }
-        e0 = in->events[in->eventsUsed].first; e1 = in->events[in->eventsUsed].second; in->eventsUsed++;
-    }
+    if (timeThisCall(in)) { int rce = nextTimerEvents(in, &e0, &e1); if (rce) return rce; }
     std::vector<mi355::NodeHeightJob> jobs;
     std::vector<double> sums;
     bool finite = true;

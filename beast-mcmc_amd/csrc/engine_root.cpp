@@ -219,7 +219,7 @@ int beagleCalculateRootLogLikelihoodsByPartition(int instance, const int* buffer
     in->sitePrefetched = false; in->siteReadStreak = 0;          // (per-partition sums rewrite siteLogL piece by piece: always the stream-ordered download)
     if (!in->tiled && partitionCount <= 480) {
         // 4-state walk instances, up to eight partitions: 128-pattern groups with the assembly loop's lane map (k_rootSite4WParts) — and
-        // when the walk that computes these roots is still held back (engine_walk.cpp runPlan) and its last slices are exactly the
+        // when the walk that computes these roots is still held back (engine_walk.cpp launchWalk) and its last slices are exactly the
         // named roots, the slices' own epilogues do it: no root launch at all
         const bool groups128 = in->walk && in->fuseLaunches && partitionCount <= mi355::ROOT_MAX_PARTS;
         if (groups128 && in->pendingWalk.valid && in->fuseRootParts) {

@@ -14,15 +14,18 @@ constexpr int FOLD_MAX_MEMBERS = 32;        // factors per fold: a longer run of
 // largest product of reciprocals a fold may hold (each is >= 1).  An unstored intermediate travels through registers and hold slots
 // UNSCALED by the members gathered so far, i.e. as small as 1 / product of its per-node-scaled size: with 1e100 its entries stay
 // normal numbers down to 1e-208 of the node's largest entry (per-node read mode keeps them down to 1e-308); beyond, the plan falls
-// back to per-node factors (runPlan: noFoldTag)
+// back to per-node factors (Resolved::noFoldTag)
 constexpr double FOLD_SAFE_MAX = 1e100;
+
+// a kept program is no longer good for reuse (its vectors keep their capacity)
+static inline void invalidate(Instance::Resolved& r) { r.tag = 0; r.dProgValid = false; r.folds.clear(); r.foldEpoch = -1; }
 
 // forget every fold (their vectors are kept for reuse) and every resolved program that may point at one
 static void dropFolds(Instance* in, bool keepVectors) {
     for (Instance::FoldVec& f : in->folds) if (keepVectors && f.recip) in->foldFree.push_back(f.recip);
     if (!keepVectors) in->foldFree.clear();                // (another layout: the old vectors stay with the instance until it is destroyed)
     in->folds.clear(); in->foldIndex.clear();
-    for (Instance::Resolved& r : in->resolved) { r.tag = 0; r.dProgValid = false; r.folds.clear(); r.foldEpoch = -1; }
+    for (Instance::Resolved& r : in->resolved) invalidate(r);
 }
 void forgetFolds(Instance* in) { dropFolds(in, false); scalesWritten(in); }
 
@@ -177,8 +180,9 @@ static inline const uint8_t* repeatTipRows(const Instance* in, const Instance::R
 static int prepareRepeats(Instance* in, const mi355::Plan& plan, const mi355::FoldMap* fold, Instance::Resolved* slot) {
     struct Spent { Instance* in; std::chrono::steady_clock::time_point t0;
                    ~Spent() { in->statRepeatBuildUs += (long)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(); } } spent{in, std::chrono::steady_clock::now()};
-    slot->compressed = false; slot->repeatsMissing = false; slot->tableRows = slot->tableReads = slot->repeatClades = 0; slot->lowerRange = 0;
-    slot->twoTables = slot->unstoredConsumers = 0;
+    slot->compressed = false; slot->repeatsMissing = false; slot->lowerRange = 0;
+    Instance::WalkTraffic& t = slot->traffic;
+    t.tableRows = t.tableReads = t.repeatClades = t.twoTables = t.unstoredConsumers = 0;
     // the index forgets nothing clade by clade: at its capacity everything goes (tables and kept programs with it) and this list's clades
     // are indexed afresh, here — once in thousands of topology moves
     if (in->repeatIndex.overCapacity()) { dropRepeatTables(in, true); in->statRepeatResets++; }
@@ -220,12 +224,12 @@ static int prepareRepeats(Instance* in, const mi355::Plan& plan, const mi355::Fo
     if (take.empty()) return 0;
     mi355::emitRepeatPlan(plan, take, slot->repeats);
     slot->compressed = true;
-    slot->tableReads = slot->repeats.tableReads; slot->repeatClades = (long)slot->repeats.lower.size();
-    slot->twoTables = slot->repeats.twoTables; slot->unstoredConsumers = slot->repeats.unstoredConsumers;
+    t.tableReads = slot->repeats.tableReads; t.repeatClades = (long)slot->repeats.lower.size();
+    t.twoTables = slot->repeats.twoTables; t.unstoredConsumers = slot->repeats.unstoredConsumers;
     for (const mi355::PlanSeg& sg : slot->repeats.lower) {
-        const Instance::RepeatTable& t = in->repeatTables[sg.partition];
-        slot->tableRows += (long)t.D * sg.progCount;
-        slot->lowerRange = std::max(slot->lowerRange, t.D);
+        const Instance::RepeatTable& tab = in->repeatTables[sg.partition];
+        t.tableRows += (long)tab.D * sg.progCount;
+        slot->lowerRange = std::max(slot->lowerRange, tab.D);
     }
     return 0;
 }
@@ -243,123 +247,131 @@ void repeatsIdle(Instance* in) {
     in->statRepeatBuildUs += (long)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
 }
 
-// did this run of a plan write per-node scale buffers?  (folds built from them are stale then)
-static inline bool anyScaleWriteIn(const Instance* in, const Instance::Resolved* slot, bool reuse, long writesAtEntry) {
-    return reuse ? slot->scaleWrites > 0 : in->statScaleWrites != writesAtEntry;
+// ---- a plan resolved to a device program (Instance::Resolved) -------------------------------------------------------------------
+static int ablateMode() {                              // (LAB builds only — TIMING EXPERIMENTS, wrong results: 1 no stores, 2 no partials loads, 4 no scale traffic, 8 no tip traffic)
+    static const int ablate = labEnv("BEAGLE_MI355_ABLATE") ? atoi(labEnv("BEAGLE_MI355_ABLATE")) : 0;
+    return ablate;
 }
+// the plan the device program is made from: the planner's, or the one with its repeated clades taken from class tables (prepareRepeats).
+// Its slices come first in Resolved::segs, the class-table programs behind them.
+static inline const mi355::Plan& planInUse(const Instance::Resolved& r, const mi355::Plan& plan) { return r.compressed ? r.repeats.plan : plan; }
+static inline size_t lowerSlices(const Instance::Resolved& r) { return r.compressed ? r.repeats.lower.size() : 0; }
 
-// Resolve a planned program to device addresses, upload it (ONE host-to-device copy: snapshot pairs, segments and
-// micro-operations travel together) and enqueue the snapshot copies and the walk.
-int runPlan(Instance* in, const mi355::Plan& plan, long planTag, hipEvent_t recordBeforeWalk) {
-    const size_t n = plan.prog.size();
-    typedef std::chrono::steady_clock PhaseClock;                    // (BEAGLE_MI355_HOST_TIMING=2: where a call that resolves a program spends its time)
-    PhaseClock::time_point ph0 = PhaseClock::now(), ph1 = ph0, ph2 = ph0, ph3 = ph0;
-    const long statsAtEntry[5] = {in->statMemReads, in->statTipReads, in->statScaleReads, in->statScaleWrites, in->statStored};
-    if (n == 0) {                                  // nothing to compute (every destination became virtual): the definitions'
-        if (plan.snapPairs.empty()) return 0;      // matrix snapshots still have to be taken
-        void* dPairs = nullptr;
-        int rc = uploadTransient(in, plan.snapPairs.data(), plan.snapPairs.size() * sizeof(int), &dPairs); if (rc) return rc;
-        mi355::launchSnapshotMatrices(live(in), in->matrices, (const int*)dPairs, (int)(plan.snapPairs.size() / 2), in->C * in->S * in->S);
-        HIP_TRY(hipGetLastError());
-        return 0;
+// Resolution: plan -> r.w / segs / deps / cm, how the program is launched and the traffic it stands for.  Everything that happens once per
+// program and not once per run is here: scale and partials buffers come into being (ensureScale, ensurePartials, scaleIsRaw), folds are
+// looked up (foldFor), class tables made (prepareRepeats), the slice-sum vectors grown.  Touches no counter of the instance: an error
+// leaves them as they were and r invalid.
+struct ProgramResolver {
+    Instance* const in; const mi355::Plan& plan; Instance::Resolved& r; const long planTag;
+    const int ablate = ablateMode();
+    const mi355::Plan* use = nullptr;                  // planInUse, once it is decided
+    size_t nUp = 0, nLow = 0;                          // its slices, the class-table programs behind them
+    mi355::FoldMap foldMap; bool fold = false;
+    bool asmLoop = false, ticket = false, sums = false, fuseOk = false;
+    unsigned skipLoads = 0;
+    std::vector<int> posOf, cur;                       // slice of the planner's plan -> device slice (-1: not emitted yet); a fold's member list
+    struct FusedAt { size_t at; int matA, matB; };
+    std::vector<FusedAt> fusedAt;
+    mi355::WalkOp nop;                                 // loads nothing, stores nothing
+    size_t matStride = 0, tipOff = 0;
+    // one slice while its micro-operations are emitted
+    struct Slice {
+        size_t si; bool low;                           // position in the device program; a class-table program (behind the slices of the walk proper)
+        const mi355::PlanSeg* ps; const Instance::RepeatTable* tab;
+        int lastStore = -1, lastHold = 0, cherry = -1; // what the micro-operation emitted last stores / parks (1 + slot); a cherry waiting to be fused into the next one
+    };
+
+    int org(int i) const { return r.compressed ? r.repeats.origin[(size_t)i] : i; }      // the planner's micro-operation (foldMap's index)
+    bool paysFactors(int j) const {
+        return fold ? foldMap.payStart[(size_t)org(j) + 1] > foldMap.payStart[(size_t)org(j)] : use->prog[(size_t)j].smode == mi355::PS_READ;
     }
-    // Device program: per segment its micro-operations, a no-op when their number is odd, and two more no-ops the
-    // kernel's descriptor prefetch may read (kernels.h WalkSeg).  For a plan that came out of the planner's cache the
-    // resolved program is kept as well: buffer addresses never change once a buffer exists.
-    static const int ablate = labEnv("BEAGLE_MI355_ABLATE") ? atoi(labEnv("BEAGLE_MI355_ABLATE")) : 0;     // (LAB builds only: wrong results)
-    Instance::Resolved* slot = planTag && !ablate ? &in->resolved[planTag & 7] : nullptr;
-    const bool reuse = slot && slot->tag == planTag && slot->epoch == in->resolveEpoch;
-    in->lastResolveMiss = !reuse;
-    in->lastPlanCached = planTag != 0;
-    std::vector<mi355::WalkOp>& w = slot ? slot->w : in->walkOps;
-    std::vector<mi355::WalkSeg> segsLocal;
-    std::vector<mi355::WalkSeg>& segs = slot ? slot->segs : segsLocal;
-    std::vector<int> depsLocal;
-    std::vector<int>& devDeps = slot ? slot->deps : depsLocal;     // per device slice: the device slices it waits for (one fused launch)
-    std::vector<const double*> cmLocal;
-    std::vector<int> sumRowsLocal, wroteLocal;                     // (a program outside the cache: Resolved::sumRows / wroteScale)
-    std::vector<const double*>& cm = slot ? slot->cm : cmLocal;    // per device micro-operation: a fused cherry's two matrices (k_gatherMatrices)
-    // 4 states, assembly loop: ALL slices in one launch, dispatched critical path first, every workgroup waiting for the slices
-    // whose stored results it reads (planner.h PlanSeg; kernels_walk4.hip) — instead of one launch per wave of slices
-    const bool fused = in->fuseWaves && in->fastWalk && !in->walkT && plan.launchOrder.size() == plan.segs.size();
-    const bool asmLoop = in->fastWalk && !in->walkT;          // k_walk4_fast runs this program (otherwise k_walk4 / k_walkT32)
+    int gatherFrom(int mat) const { const int s = in->snapSourceOf[(size_t)mat]; return s < 0 ? mat : s; }
+    // where a compact tip's states are read: the instance's array, or for a class-table program the representatives' rows
+    const uint8_t* tipSrc(const Slice& s, int buf) const { return s.low ? repeatTipRows(in, *s.tab, buf) : in->tipStates[buf] ? in->tipStates[buf] + tipOff : nullptr; }
+
+    int run();
+    void decideLaunch();
+    int chooseProgram();
+    int slice(size_t oi);
+    int microOp(Slice& s, int i);
+    void sliceEpilogue(const Slice& s);
+    void finish();
+};
+
+// Launch order, and tickets or flags.  4 states, assembly loop: ALL slices in one launch, dispatched critical path first, every workgroup
+// waiting for the slices whose stored results it reads (planner.h PlanSeg; kernels_walk4.hip) — instead of one launch per wave of slices
+void ProgramResolver::decideLaunch() {
+    asmLoop = in->fastWalk && !in->walkT;          // k_walk4_fast runs this program (otherwise k_walk4 / k_walkT32)
+    r.oneLaunch = in->fuseWaves && asmLoop && plan.launchOrder.size() == plan.segs.size();
     // ... on tickets when its slices form a forest: the slices without dependencies first (they are the launch's grid), in launch order
-    bool ticket = fused && in->useTickets && plan.leaves > 0;
+    ticket = r.oneLaunch && in->useTickets && plan.leaves > 0;
     // (a slice without micro-operations leaves the kernel before it counts itself in at its next slice, which would then never run and
     // whose ticket words would stay non-zero for the next launch: such a program runs on flags)
     for (size_t i = 0; i < plan.segs.size() && ticket; i++) if (plan.segs[i].progCount <= 0) ticket = false;
-    std::vector<int> order;
-    if (fused) {
-        order = plan.launchOrder;
-        if (ticket) std::stable_partition(order.begin(), order.end(), [&](int s) { return plan.segs[(size_t)s].depCount == 0; });
+    r.order.clear();
+    if (r.oneLaunch) {
+        r.order = plan.launchOrder;
+        if (ticket) std::stable_partition(r.order.begin(), r.order.end(), [&](int s) { return plan.segs[(size_t)s].depCount == 0; });
     }
-    int maxRange = 0;
-    // the plan the device program is made from: the planner's, or the one with its repeated clades taken from class tables (prepareRepeats)
-    const mi355::Plan* use = &plan;
-    if (reuse) {
-        maxRange = slot->maxRange;
-        if (slot->compressed) use = &slot->repeats.plan;
-        in->statTableRows += slot->tableRows; in->statTableReads += slot->tableReads; in->statRepeatClades += slot->repeatClades; in->statTwoTables += slot->twoTables; in->statUnstoredConsumers += slot->unstoredConsumers;
-        in->statMemReads += slot->memReads; in->statTipReads += slot->tipReads; in->statScaleReads += slot->scaleReads;
-        in->statScaleWrites += slot->scaleWrites; in->statStored += slot->stored; in->statFused += slot->fused;
-    } else {
-    const long s0[5] = {in->statMemReads, in->statTipReads, in->statScaleReads, in->statScaleWrites, in->statStored};
-    if (in->folds.size() > 4096) dropFolds(in, true);           // (tree shapes come and go; the vectors are reused)
-    if (slot) { slot->tag = 0; slot->dProgValid = false; slot->folds.clear(); slot->foldEpoch = -1; }
+    r.leaves = ticket ? plan.leaves : 0;
+}
+
+// Folds, class tables, slice sums: which plan the program is made from and what its micro-operations may use
+int ProgramResolver::chooseProgram() {
     // read-mode programs of cached (full-evaluation) plans fold the reciprocals of unstored nodes (Instance::folds, planner.h FoldMap)
-    mi355::FoldMap foldMap;
-    const bool fold = slot && in->foldScales && (in->walk || in->walkT) && slot->noFoldTag != planTag &&
-                      mi355::foldScaleFactors(plan, FOLD_MAX_MEMBERS, foldMap);
-    std::vector<int> cur;
+    fold = r.kept && r.noFoldTag != planTag && in->foldScales && (in->walk || in->walkT) && mi355::foldScaleFactors(plan, FOLD_MAX_MEMBERS, foldMap);
     // fused cherries (kernels.h WK_CHERRY): the assembly loop only, and no program that rescales in write mode anywhere (the cherry
     // halves of the kernel's table buffers share their LDS with the maximum buffers of write-mode rescaling)
     bool anyWrite = false;
     for (const mi355::MicroOp& q : plan.prog) if (q.smode == mi355::PS_WRITE) { anyWrite = true; break; }
     const bool noWrites = asmLoop && in->walk && !anyWrite;
-    if (slot) slot->compressed = false;
-    if (slot && in->repeatsOn && in->walk && !in->walkT && in->partitionCount == 1 && !anyWrite && in->planner.stepLimit == 0 && !plan.runs.empty() &&
+    use = &plan;
+    if (r.kept && in->repeatsOn && in->walk && !in->walkT && in->partitionCount == 1 && !anyWrite && in->planner.stepLimit == 0 && !plan.runs.empty() &&
         (in->fastWalk || in->C <= 8)) {                // (k_walk4's table variant: up to eight categories, kernels_walk4.hip)
-        int rcr = prepareRepeats(in, plan, fold ? &foldMap : nullptr, slot); if (rcr) return rcr;
-        if (slot->compressed) {
-            use = &slot->repeats.plan;
-            in->statTableRows += slot->tableRows; in->statTableReads += slot->tableReads; in->statRepeatClades += slot->repeatClades; in->statTwoTables += slot->twoTables; in->statUnstoredConsumers += slot->unstoredConsumers;
-        }
+        int rc = prepareRepeats(in, plan, fold ? &foldMap : nullptr, &r); if (rc) return rc;
+        if (r.compressed) use = &r.repeats.plan;
     }
-    const mi355::Plan& U = *use;
-    const bool compressed = slot && slot->compressed;
-    const size_t nUp = U.segs.size(), nLow = compressed ? slot->repeats.lower.size() : 0;
-    auto org = [&](int i) { return compressed ? slot->repeats.origin[(size_t)i] : i; };      // the planner's micro-operation (foldMap's index)
+    nUp = use->segs.size(); nLow = lowerSlices(r);
     // write-mode programs: every slice leaves the product of its factors behind (Instance::lastSums); the vectors are named by the last no-op
     // behind the slice's program.  They are the instance's, so growing them invalidates what other kept programs point at.
-    const bool sums = anyWrite && in->walk && !in->walkT && in->sliceSums && in->partitionCount == 1;
-    std::vector<int>& sumRows = slot ? slot->sumRows : sumRowsLocal;
-    std::vector<int>& wroteScale = slot ? slot->wroteScale : wroteLocal;
-    sumRows.clear(); wroteScale.clear();
+    sums = anyWrite && in->walk && !in->walkT && in->sliceSums && in->partitionCount == 1;
     if (sums && in->sliceRows < plan.segs.size()) {
         // (both go whatever they hold: sliceRows is 0 after a change of the pair layout, and a failure below leaves it 0 — the next call starts over)
         HIP_TRY(hipStreamSynchronize(live(in)));
         releaseDevice(in, in->sliceMant); releaseDevice(in, in->sliceExp); in->sliceRows = 0;
         const size_t rows = plan.segs.size() + plan.segs.size() / 2 + 8, cells = rows * in->pairLen;
-        int rcs = growDevice(in, in->sliceMant, cells * sizeof(double), cells * sizeof(double), Grow::SyncIfHeld); if (rcs) return rcs;
-        rcs = growDevice(in, in->sliceExp, cells * sizeof(int), cells * sizeof(int), Grow::SyncIfHeld); if (rcs) return rcs;
+        int rc = growDevice(in, in->sliceMant, cells * sizeof(double), cells * sizeof(double), Grow::SyncIfHeld); if (rc) return rc;
+        rc = growDevice(in, in->sliceExp, cells * sizeof(int), cells * sizeof(int), Grow::SyncIfHeld); if (rc) return rc;
         in->sliceRows = rows;
         in->resolveEpoch++;
         in->lastSums.valid = false;
     }
-    const bool fuseOk = noWrites && in->fuseCherries;
+    fuseOk = noWrites && in->fuseCherries;
     // ... and in such programs the loop's fetch skips the tip-state load of a child that is no compact tip (kernels.h WF_NOLOAD1 / 2): a
     // vector-memory instruction less on the CU's address unit for half the children of a tree.  Programs that rescale in write mode keep
-    // every fetch at its full size: their stage waits count on it (below).
-    const unsigned skipLoads = noWrites && in->skipTipLoads ? (mi355::WF_NOLOAD1 | mi355::WF_NOLOAD2) : 0u;
-    struct FusedAt { size_t at; int matA, matB; };
-    std::vector<FusedAt> fusedAt;
-    auto paysFactors = [&](int j) { return fold ? foldMap.payStart[(size_t)org(j) + 1] > foldMap.payStart[(size_t)org(j)] : U.prog[(size_t)j].smode == mi355::PS_READ; };
-    w.clear();
-    w.reserve(U.prog.size() + 6 * (nUp + nLow));
-    segs.assign(nUp + nLow, mi355::WalkSeg());
-    devDeps.clear();
-    std::vector<int> posOf(plan.segs.size(), -1);
-    const size_t matStride = (size_t)in->C * in->S * in->S;
+    // every fetch at its full size: their stage waits count on it (kernels.h walkStageWaits).
+    skipLoads = noWrites && in->skipTipLoads ? (mi355::WF_NOLOAD1 | mi355::WF_NOLOAD2) : 0u;
+    return 0;
+}
+
+// Device program: per slice its micro-operations, a no-op when their number is odd, and two more no-ops the kernel's descriptor
+// prefetch may read (kernels.h WalkSeg)
+int ProgramResolver::run() {
+    if (in->folds.size() > 4096) dropFolds(in, true);           // (tree shapes come and go; the vectors are reused)
+    invalidate(r);                                              // (an error halfway never leaves a reusable half-program)
+    r.traffic = Instance::WalkTraffic(); r.compressed = false;
+    r.sumRows.clear(); r.wroteScale.clear();
+    decideLaunch();
+    { int rc = chooseProgram(); if (rc) return rc; }
+    r.w.clear();
+    r.w.reserve(use->prog.size() + 6 * (nUp + nLow));
+    r.segs.assign(nUp + nLow, mi355::WalkSeg());
+    r.deps.clear();
+    posOf.assign(plan.segs.size(), -1);
+    r.maxRange = 0;
+    r.finalStore.assign(r.oneLaunch ? nUp : 0, -1); r.finalPart.assign(r.oneLaunch ? nUp : 0, 0);
+    matStride = (size_t)in->C * in->S * in->S;
+    tipOff = in->walkT ? 0 : in->statePairOff;          // the T32 walk reads the plain state arrays and the RAW scale factors
     // matrices whose snapshot is taken by THIS plan are gathered from the snapshot's source (same values; lets the snapshot copies and
     // the gather run in one launch: kernels_walk4.hip k_gatherAndSnapshot)
     // (a flat table over the matrix slots, entries put back behind the loop: a program on a new tree takes ~1 800 snapshots, and a hash
@@ -370,439 +382,500 @@ int runPlan(Instance* in, const mi355::Plan& plan, long planTag, hipEvent_t reco
     if (snapSrc.size() < snapSlots) snapSrc.assign(snapSlots, -1);
     for (size_t q = 0; q + 1 < plan.snapPairs.size(); q += 2) snapSrc[(size_t)plan.snapPairs[q + 1]] = plan.snapPairs[q];
     struct SnapReset { std::vector<int>& t; const std::vector<int>& pairs; ~SnapReset() { for (size_t q = 0; q + 1 < pairs.size(); q += 2) t[(size_t)pairs[q + 1]] = -1; } } snapReset{snapSrc, plan.snapPairs};
-    auto gatherFrom = [&](int mat) { const int s = snapSrc[(size_t)mat]; return s < 0 ? mat : s; };
-    const size_t tipOff = in->walkT ? 0 : in->statePairOff;          // the T32 walk reads the plain state arrays and the RAW scale factors
     { int rc = ensureWalkDummies(in); if (rc) return rc; }
-    mi355::WalkOp nop;
     memset(&nop, 0, sizeof(nop));
     nop.m1 = in->matrices; nop.m2 = in->matrices;
     nop.src1 = in->dummyTips; nop.src2 = in->dummyTips; nop.scale = in->onesScale;
-    nop.flags = (unsigned)((mi355::WK_TIPS << 5) | (mi355::WK_TIPS << 8)) | skipLoads;         // loads nothing, stores nothing
-    for (size_t oi = 0; oi < nUp + nLow; oi++) {
-        const size_t si = oi;                                   // position in the device program
-        const bool low = oi >= nUp;                             // a class-table program (behind the slices of the walk proper)
-        const mi355::PlanSeg& ps = low ? slot->repeats.lower[oi - nUp] : U.segs[fused ? (size_t)order[oi] : oi];
-        const Instance::RepeatTable* tab = low ? &in->repeatTables.find(ps.partition)->second : nullptr;      // (PlanSeg::partition of a lower slice: its clade)
-        if (!low) posOf[fused ? (size_t)order[oi] : oi] = (int)oi;
-        // where a compact tip's states are read: the instance's array, or for a class-table program the representatives' rows
-        auto tipSrc = [&](int buf) -> const uint8_t* { return low ? repeatTipRows(in, *tab, buf) : in->tipStates[buf] ? in->tipStates[buf] + tipOff : nullptr; };
-        segs[si].depStart = (int)devDeps.size();
-        if (fused && !low) for (int d = ps.depStart; d < ps.depStart + ps.depCount; d++) {
-            if (posOf[plan.deps[d]] < 0) return BEAGLE_ERROR_GENERAL;      // (a slice behind one that waits for it: the planner's order forbids it)
-            devDeps.push_back(posOf[plan.deps[d]]);
-        }
-        segs[si].depCount = (int)devDeps.size() - segs[si].depStart;
-        segs[si].progStart = (int)w.size();
-        int lastStore = -1, lastHold = 0, cherry = -1;    // what the micro-operation emitted last stores / parks (1 + slot); a cherry waiting to be fused into the next one
-        for (int i = ps.progStart; i < ps.progStart + ps.progCount; i++) {
-            mi355::MicroOp m = U.prog[i];
-            // A cherry that is consumed at once is fused into its consumer (kernels.h WK_CHERRY): tip x tip, not stored, not parked, pays no
-            // factors; the next micro-operation of the slice takes it as its second operand (ACC), multiplies by no reciprocals itself (the
-            // descriptor's scale field carries the cherry's second tip) and would not come to sit right behind the micro-operation that
-            // stores or parks its first child (the loop requests a first child from memory or from an LDS hold slot in the MIDDLE of the
-            // stage before — in front of that stage's store and hold-slot write: with the cherry's own stage between them that was safe).
-            if (fuseOk && i + 1 < ps.progStart + ps.progCount && m.k1 == mi355::PK_TIPS && m.k2 == mi355::PK_TIPS && m.storeBuf < 0 && m.hold == 0 &&
-                !paysFactors(i) && in->tipStates[m.a1] && in->tipStates[m.a2]) {
-                const mi355::MicroOp& nx = U.prog[(size_t)i + 1];
-                if (nx.k2 == mi355::PK_ACC && !paysFactors(i + 1) && !(nx.k1 == mi355::PK_MEM && lastStore == nx.a1) &&
-                    !(mi355::isHoldKind(nx.k1) && lastHold == nx.k1 - mi355::PK_H0 + 1)) { cherry = i; continue; }
-            }
-            // The kernels request a first child's partials one stage early — before the previous micro-operation's store
-            // is issued (kernels_walk4.hip WALK_STAGE).  The planner never emits that sequence (tests/native/plan_check.cpp
-            // checks every program for it); should one arrive anyway, a no-op in between restores the distance.
-            if ((int)w.size() > segs[si].progStart && m.k1 == mi355::PK_MEM && lastStore == m.a1) {
-                if (m.k2 == mi355::PK_ACC) { m.k2 = mi355::PK_MEM; m.a2 = m.a1; }      // the no-op overwrites ACC; the value is in memory as well
-                w.push_back(nop);
-            }
-            // (k_walk4 reads a first child from a class table one stage early, like a hold slot: not in front of a program's first stage)
-            if (!asmLoop && (int)w.size() == segs[si].progStart && m.k1 == mi355::PK_TAB) w.push_back(nop);
-            mi355::WalkOp d;
-            memset(&d, 0, sizeof(d));
-            d.src1 = in->dummyTips; d.src2 = in->dummyTips; d.scale = in->onesScale;     // unused operands stay readable (kernels.h launchWalk4Fast)
-            // (the counters are of full-width vectors: a class-table program's reads and stores are statTableRows)
-            if (m.k1 == mi355::PK_MEM) { d.src1 = in->partials[m.a1]; if (!d.src1 || isCompactTip(in, m.a1)) return BEAGLE_ERROR_OUT_OF_RANGE; in->statMemReads++; }
-            else if (m.k1 == mi355::PK_TIPS) { d.src1 = tipSrc(m.a1); if (!d.src1) return BEAGLE_ERROR_OUT_OF_RANGE; if (!low) in->statTipReads++; }
-            if (m.k2 == mi355::PK_MEM) { d.src2 = in->partials[m.a2]; if (!d.src2 || isCompactTip(in, m.a2)) return BEAGLE_ERROR_OUT_OF_RANGE; in->statMemReads++; }
-            else if (m.k2 == mi355::PK_TIPS) { d.src2 = tipSrc(m.a2); if (!d.src2) return BEAGLE_ERROR_OUT_OF_RANGE; if (!low) in->statTipReads++; }
-            // a child from a class table (kernels.h WK_TAB): its row vector, and the arena where a write-mode operation has its scale buffer
-            if (m.k1 == mi355::PK_TAB || m.k2 == mi355::PK_TAB) {
-                for (int which = 0; which < 2; which++) {
-                    if ((which ? m.k2 : m.k1) != mi355::PK_TAB) continue;
-                    const auto t = in->repeatTables.find(which ? m.a2 : m.a1);
-                    if (t == in->repeatTables.end()) return BEAGLE_ERROR_GENERAL;
-                    (which ? d.src2 : d.src1) = t->second.dev;
-                }
-                d.scaleW = in->repeatArena;
-            }
-            if (m.smode != mi355::PS_NONE) {
-                int rc = ensureScale(in, m.scaleIdx); if (rc) return rc;
-                if (m.smode == mi355::PS_WRITE) { if (in->walkT && !in->walkTWrite) return BEAGLE_ERROR_GENERAL; in->scaleIsRaw[m.scaleIdx] = 1; in->statScaleWrites++; d.scaleW = in->scale[m.scaleIdx];
-                                                  if (sums) { wroteScale.push_back(m.scaleIdx); if (sumRows.empty() || sumRows.back() != (int)si) sumRows.push_back((int)si); } }
-                else {
-                    if (!in->scaleIsRaw[m.scaleIdx]) return BEAGLE_ERROR_OUT_OF_RANGE;   // never written by a rescaling op
-                    if (!fold) {
-                        in->statScaleReads++;
-                        d.scale = in->scale[m.scaleIdx] + (in->walkT ? 0 : in->scaleStride);  // read mode multiplies by the reciprocal
-                    }
-                }
-            }
-            int smodeNow = m.smode;
-            if (fold) {                            // multiply by what the planner says this result pays for — nothing, one buffer's reciprocals, a fold
-                const int b0 = foldMap.payStart[(size_t)org(i)], b1 = foldMap.payStart[(size_t)org(i) + 1];
-                smodeNow = b1 > b0 ? mi355::PS_READ : mi355::PS_NONE;
-                if (b1 - b0 == 1) d.scale = in->scale[foldMap.members[(size_t)b0]] + (in->walkT ? 0 : in->scaleStride);
-                else if (b1 > b0) {
-                    cur.assign(foldMap.members.begin() + b0, foldMap.members.begin() + b1);
-                    const int f = foldFor(in, cur);
-                    if (f < 0) return BEAGLE_ERROR_OUT_OF_MEMORY;
-                    slot->folds.push_back(f);
-                    d.scale = in->folds[(size_t)f].recip;
-                }
-                if (b1 > b0) in->statScaleReads++;
-            }
-            if (m.storeBuf >= 0) {
-                int rc = ensurePartials(in, m.storeBuf); if (rc) return rc;
-                d.store = in->partials[m.storeBuf];
-                in->statStored++;
-            }
-            const bool tableStore = low && i == ps.progStart + ps.progCount - 1;      // a class-table program's result: rows of the arena
-            if (tableStore) d.store = in->repeatArena + (size_t)tab->arena * in->C * in->P * 4;
-            d.m1 = in->matrices + (size_t)gatherFrom(m.mat1) * matStride; d.m2 = in->matrices + (size_t)gatherFrom(m.mat2) * matStride;
-            int k2 = m.k2;
-            if (cherry >= 0) {
-                const mi355::MicroOp& c = U.prog[(size_t)cherry];
-                d.src2 = tipSrc(c.a1); d.scale = (const double*)tipSrc(c.a2);
-                if (!d.src2 || !d.scale) return BEAGLE_ERROR_OUT_OF_RANGE;
-                k2 = mi355::WK_CHERRY;
-                fusedAt.push_back(FusedAt{w.size(), gatherFrom(c.mat1), gatherFrom(c.mat2)});
-                if (!low) in->statTipReads += 2;
-                cherry = -1;
-            }
-            d.flags = mi355::walkFlags(m.k1, k2, m.hold, smodeNow, m.storeBuf >= 0 || tableStore);
-            if (asmLoop && m.k1 == mi355::PK_TAB) d.flags |= mi355::WF_X | mi355::WF_TAB1;
-            if (asmLoop && k2 == mi355::PK_TAB) d.flags |= mi355::WF_MEM2 | mi355::WF_TAB2;
-            if (m.k1 != mi355::PK_TIPS) d.flags |= skipLoads & mi355::WF_NOLOAD1;
-            if (k2 != mi355::PK_TIPS) d.flags |= skipLoads & mi355::WF_NOLOAD2;
-            if (ablate) {       // TIMING EXPERIMENTS ONLY (wrong results): 1 no stores, 2 no partials loads, 4 no scale traffic, 8 no tip traffic
-                if (ablate & 1) d.flags &= ~(unsigned)mi355::WF_STORE;
-                if (ablate & 2) d.flags &= ~(unsigned)mi355::WF_X;
-                if (ablate & 4) d.scale = in->onesScale;
-                if (ablate & 8) { if (m.k1 == mi355::PK_TIPS) d.src1 = in->dummyTips; if (m.k2 == mi355::PK_TIPS) d.src2 = in->dummyTips; }
-            }
-            w.push_back(d);
-            lastStore = m.storeBuf; lastHold = m.hold;
-        }
-        // (the kernels' software pipelines: the assembly loop is three micro-operations deep and leaves behind any stage — any
-        // length, three more readable descriptors —; the C++ kernel and the T32 walk are two deep: an even length, two more)
-        if (!asmLoop && !(in->walkT && in->S > 20) && ((int)w.size() - segs[si].progStart) % 2) w.push_back(nop);      // (k_walkT64 prefetches nothing across stages)
-        segs[si].progCount = (int)w.size() - segs[si].progStart;
-        for (int q = 0; q < (asmLoop ? 3 : 2); q++) w.push_back(nop);
-        if (sums && !sumRows.empty() && sumRows.back() == (int)si) {      // (this slice writes factors: where its product of them goes)
-            w.back().scaleW = in->sliceMant.as<double>() + si * in->pairLen;
-            w.back().store = (double*)(in->sliceExp.as<int>() + si * in->pairLen);
-        }
-        // the wait of every stage: "at most N vector-memory instructions outstanding".  Loads and stores share the counter.
-        // DEFAULT (strict): N = the LOADS issued behind this micro-operation's own.  Sufficient under the one ordering rule the ISA
-        // guides state for this counter — vector-memory LOADS return in the order they were issued: when at most N operations
-        // are outstanding and the N youngest loads are all younger than this stage's loads, an unfinished load of this stage
-        // would leave N + 1 unfinished, whatever the stores (of this or any earlier stage) do.
-        // BEAGLE_MI355_STRICT_WAITS=0: N also counts the stores issued in between, i.e. assumes that a younger store
-        // is never counted out before an older load.  That held in > 1e9 lane-trials (tests/test_gpu_vmcnt_order.py) — but it
-        // is an observation, not a documented guarantee, so it is not what ships by default.
-        // A smaller N than the true number only waits longer.
-        const int first = segs[si].progStart;
-        if (asmLoop) {
-            // The stage waits below count LOADS.  Stores share the counter: a stage that finds stores of the two micro-operations
-            // before it still unacknowledged waits for as many of them as its N falls short of "loads + stores".  With four loads per
-            // fetch that shortfall was covered by the loads of the fetch before (older than the stores, long landed); with three it
-            // is not — a write-mode evaluation (every micro-operation stores its factors) lost 8 % to it.  So a micro-operation
-            // whose fetch is in flight across such stores fetches four again: WF_INV on top, its scale address the all-ones array
-            // (a multiplication by one where it multiplies).  Behind write-mode rescaling only: behind the (rare) stored results of a
-            // read-mode program the padding costs what it saves (config A 503 / 503 / 507 us without, with, and with both; ALWAYS
-            // 1 053 / 1 003 / 1 005: profiles/r05_experiments.txt).  LAB builds: BEAGLE_MI355_WALK_PAD_FETCH = 0 never, 1 (default), 2 both.
-            static const int padMode = labEnv("BEAGLE_MI355_WALK_PAD_FETCH") ? atoi(labEnv("BEAGLE_MI355_WALK_PAD_FETCH")) : 1;
-            for (int i = first + segs[si].progCount - 1; i >= first + 2; i--) {      // (backwards: the test reads unpadded flags only of earlier ones — WF_INV is not what it looks at)
-                bool pad = false;
-                for (int b = 2; b <= 4 && i - b >= first && !pad; b++) {
-                    const unsigned f = w[i - b].flags;
-                    pad = (padMode >= 1 && ((f >> 13) & 3u) == (unsigned)mi355::WS_WRITE) || (padMode >= 2 && (f & mi355::WF_STORE));
-                }
-                if (pad) w[i].flags |= mi355::WF_INV;
-            }
-        }
-        for (int i = first; i < first + segs[si].progCount; i++) {
-            // k_walk4 (two deep): N = the fetch of the next micro-operation (+ the previous one's stores)
-            // (a micro-operation that rescales in write mode also stores its factors, from one of the workgroup's waves only: behind
-            // it the count is the strict one whatever the mode)
-            const bool prevWrites = i > first && ((w[i - 1].flags >> 13) & 3u) == (unsigned)mi355::WS_WRITE;
-            const int stores1 = (in->strictWaits || prevWrites) ? 0 : (i > first ? mi355::walkStoreCount(w[i - 1].flags) : 0);
-            if (!asmLoop) { w[i].flags |= mi355::walkWaitJump(std::min(mi355::walkFetchCount(w[i + 1].flags) + stores1, 12)); continue; }
-            // k_walk4_fast (three deep; a fetch is THREE small loads, four with the reciprocal scale factors: WF_INV).  Issue order around
-            // stage i: ... fetch(i) | first child of i - 1 from memory (4) | store(i - 2) | fetch(i + 1) | first child of i from memory
-            // (4) | store(i - 1) | fetch(i + 2) | WAIT.  A first child of i in memory has to have landed as well: then only what
-            // follows it counts.  (Loads only — the strict rule — whatever BEAGLE_MI355_STRICT_WAITS says: with two fetch sizes the
-            // code space has no room for the store counts of the lax rule, which bought 1 %.)
-            auto fetchLoads = [&](int j) { const unsigned f = w[j].flags;             // (matrix table; tip states, twice; reciprocals; a fused cherry's table half and tips)
-                                           return 1 + ((f & mi355::WF_NOLOAD1) ? 0 : 1) + ((f & mi355::WF_NOLOAD2) ? 0 : 1) + ((f & mi355::WF_INV) ? 1 : 0) + ((f & mi355::WF_CHERRY2) ? 3 : 0); };
-            const int x1 = i > first && (w[i - 1].flags & mi355::WF_X) ? 4 : 0;
-            const int nWait = (w[i].flags & mi355::WF_X) ? fetchLoads(i + 2) : fetchLoads(i + 1) + fetchLoads(i + 2) + x1;
-            w[i].flags |= mi355::walkWaitCode(nWait);
-        }
-        if (low) { segs[si].pStart = tab->row; segs[si].pEnd = tab->row + tab->D; segs[si].tStart = 0; segs[si].next = -1; continue; }
-        segs[si].pStart = in->partStart[ps.partition]; segs[si].pEnd = in->partEnd[ps.partition]; segs[si].tStart = in->padStart[ps.partition];
-        maxRange = std::max(maxRange, segs[si].pEnd - segs[si].pStart);
+    nop.flags = (unsigned)((mi355::WK_TIPS << 5) | (mi355::WK_TIPS << 8)) | skipLoads;
+    for (size_t oi = 0; oi < nUp + nLow; oi++) { int rc = slice(oi); if (rc) return rc; }
+    finish();
+    return 0;
+}
+
+int ProgramResolver::slice(size_t oi) {
+    Slice s;
+    s.si = oi; s.low = oi >= nUp;
+    const size_t planSlice = s.low ? 0 : r.oneLaunch ? (size_t)r.order[oi] : oi;      // (of the plan in use; a class-table program is none of them)
+    s.ps = s.low ? &r.repeats.lower[oi - nUp] : &use->segs[planSlice];
+    s.tab = s.low ? &in->repeatTables.find(s.ps->partition)->second : nullptr;      // (PlanSeg::partition of a lower slice: its clade)
+    if (!s.low) posOf[planSlice] = (int)oi;
+    mi355::WalkSeg& sg = r.segs[oi];
+    sg.depStart = (int)r.deps.size();
+    if (r.oneLaunch && !s.low) for (int d = s.ps->depStart; d < s.ps->depStart + s.ps->depCount; d++) {
+        if (posOf[plan.deps[d]] < 0) return BEAGLE_ERROR_GENERAL;      // (a slice behind one that waits for it: the planner's order forbids it)
+        r.deps.push_back(posOf[plan.deps[d]]);
     }
+    sg.depCount = (int)r.deps.size() - sg.depStart;
+    sg.progStart = (int)r.w.size();
+    for (int i = s.ps->progStart; i < s.ps->progStart + s.ps->progCount; i++) { int rc = microOp(s, i); if (rc) return rc; }
+    sliceEpilogue(s);
+    return 0;
+}
+
+// One micro-operation of the plan in use: its operands, what it multiplies by (scale buffer or fold), its store, a cherry fused into it, its flags
+int ProgramResolver::microOp(Slice& s, int i) {
+    const mi355::Plan& U = *use;
+    const mi355::PlanSeg& ps = *s.ps;
+    const int progStart = r.segs[s.si].progStart;
+    std::vector<mi355::WalkOp>& w = r.w;
+    Instance::WalkTraffic& t = r.traffic;
+    mi355::MicroOp m = U.prog[i];
+    // A cherry that is consumed at once is fused into its consumer (kernels.h WK_CHERRY): tip x tip, not stored, not parked, pays no
+    // factors; the next micro-operation of the slice takes it as its second operand (ACC), multiplies by no reciprocals itself (the
+    // descriptor's scale field carries the cherry's second tip) and would not come to sit right behind the micro-operation that
+    // stores or parks its first child (the loop requests a first child from memory or from an LDS hold slot in the MIDDLE of the
+    // stage before — in front of that stage's store and hold-slot write: with the cherry's own stage between them that was safe).
+    if (fuseOk && i + 1 < ps.progStart + ps.progCount && m.k1 == mi355::PK_TIPS && m.k2 == mi355::PK_TIPS && m.storeBuf < 0 && m.hold == 0 &&
+        !paysFactors(i) && in->tipStates[m.a1] && in->tipStates[m.a2]) {
+        const mi355::MicroOp& nx = U.prog[(size_t)i + 1];
+        if (nx.k2 == mi355::PK_ACC && !paysFactors(i + 1) && !(nx.k1 == mi355::PK_MEM && s.lastStore == nx.a1) &&
+            !(mi355::isHoldKind(nx.k1) && s.lastHold == nx.k1 - mi355::PK_H0 + 1)) { s.cherry = i; return 0; }
+    }
+    // The kernels request a first child's partials one stage early — before the previous micro-operation's store
+    // is issued (kernels_walk4.hip WALK_STAGE).  The planner never emits that sequence (tests/native/plan_check.cpp
+    // checks every program for it); should one arrive anyway, a no-op in between restores the distance.
+    if ((int)w.size() > progStart && m.k1 == mi355::PK_MEM && s.lastStore == m.a1) {
+        if (m.k2 == mi355::PK_ACC) { m.k2 = mi355::PK_MEM; m.a2 = m.a1; }      // the no-op overwrites ACC; the value is in memory as well
+        w.push_back(nop);
+    }
+    // (k_walk4 reads a first child from a class table one stage early, like a hold slot: not in front of a program's first stage)
+    if (!asmLoop && (int)w.size() == progStart && m.k1 == mi355::PK_TAB) w.push_back(nop);
+    mi355::WalkOp d;
+    memset(&d, 0, sizeof(d));
+    d.src1 = in->dummyTips; d.src2 = in->dummyTips; d.scale = in->onesScale;     // unused operands stay readable (kernels.h launchWalk4Fast)
+    // (the counters are of full-width vectors: a class-table program's reads and stores are tableRows)
+    if (m.k1 == mi355::PK_MEM) { d.src1 = in->partials[m.a1]; if (!d.src1 || isCompactTip(in, m.a1)) return BEAGLE_ERROR_OUT_OF_RANGE; t.memReads++; }
+    else if (m.k1 == mi355::PK_TIPS) { d.src1 = tipSrc(s, m.a1); if (!d.src1) return BEAGLE_ERROR_OUT_OF_RANGE; if (!s.low) t.tipReads++; }
+    if (m.k2 == mi355::PK_MEM) { d.src2 = in->partials[m.a2]; if (!d.src2 || isCompactTip(in, m.a2)) return BEAGLE_ERROR_OUT_OF_RANGE; t.memReads++; }
+    else if (m.k2 == mi355::PK_TIPS) { d.src2 = tipSrc(s, m.a2); if (!d.src2) return BEAGLE_ERROR_OUT_OF_RANGE; if (!s.low) t.tipReads++; }
+    // a child from a class table (kernels.h WK_TAB): its row vector, and the arena where a write-mode operation has its scale buffer
+    if (m.k1 == mi355::PK_TAB || m.k2 == mi355::PK_TAB) {
+        for (int which = 0; which < 2; which++) {
+            if ((which ? m.k2 : m.k1) != mi355::PK_TAB) continue;
+            const auto tb = in->repeatTables.find(which ? m.a2 : m.a1);
+            if (tb == in->repeatTables.end()) return BEAGLE_ERROR_GENERAL;
+            (which ? d.src2 : d.src1) = tb->second.dev;
+        }
+        d.scaleW = in->repeatArena;
+    }
+    if (m.smode != mi355::PS_NONE) {
+        int rc = ensureScale(in, m.scaleIdx); if (rc) return rc;
+        if (m.smode == mi355::PS_WRITE) {
+            if (in->walkT && !in->walkTWrite) return BEAGLE_ERROR_GENERAL;
+            in->scaleIsRaw[m.scaleIdx] = 1; t.scaleWrites++; d.scaleW = in->scale[m.scaleIdx];
+            if (sums) { r.wroteScale.push_back(m.scaleIdx); if (r.sumRows.empty() || r.sumRows.back() != (int)s.si) r.sumRows.push_back((int)s.si); }
+        } else {
+            if (!in->scaleIsRaw[m.scaleIdx]) return BEAGLE_ERROR_OUT_OF_RANGE;   // never written by a rescaling op
+            if (!fold) {
+                t.scaleReads++;
+                d.scale = in->scale[m.scaleIdx] + (in->walkT ? 0 : in->scaleStride);  // read mode multiplies by the reciprocal
+            }
+        }
+    }
+    int smodeNow = m.smode;
+    if (fold) {                            // multiply by what the planner says this result pays for — nothing, one buffer's reciprocals, a fold
+        const int b0 = foldMap.payStart[(size_t)org(i)], b1 = foldMap.payStart[(size_t)org(i) + 1];
+        smodeNow = b1 > b0 ? mi355::PS_READ : mi355::PS_NONE;
+        if (b1 - b0 == 1) d.scale = in->scale[foldMap.members[(size_t)b0]] + (in->walkT ? 0 : in->scaleStride);
+        else if (b1 > b0) {
+            cur.assign(foldMap.members.begin() + b0, foldMap.members.begin() + b1);
+            const int f = foldFor(in, cur);
+            if (f < 0) return BEAGLE_ERROR_OUT_OF_MEMORY;
+            r.folds.push_back(f);
+            d.scale = in->folds[(size_t)f].recip;
+        }
+        if (b1 > b0) t.scaleReads++;
+    }
+    if (m.storeBuf >= 0) {
+        int rc = ensurePartials(in, m.storeBuf); if (rc) return rc;
+        d.store = in->partials[m.storeBuf];
+        t.stored++;
+    }
+    const bool tableStore = s.low && i == ps.progStart + ps.progCount - 1;      // a class-table program's result: rows of the arena
+    if (tableStore) d.store = in->repeatArena + (size_t)s.tab->arena * in->C * in->P * 4;
+    d.m1 = in->matrices + (size_t)gatherFrom(m.mat1) * matStride; d.m2 = in->matrices + (size_t)gatherFrom(m.mat2) * matStride;
+    int k2 = m.k2;
+    if (s.cherry >= 0) {
+        const mi355::MicroOp& c = U.prog[(size_t)s.cherry];
+        d.src2 = tipSrc(s, c.a1); d.scale = (const double*)tipSrc(s, c.a2);
+        if (!d.src2 || !d.scale) return BEAGLE_ERROR_OUT_OF_RANGE;
+        k2 = mi355::WK_CHERRY;
+        fusedAt.push_back(FusedAt{w.size(), gatherFrom(c.mat1), gatherFrom(c.mat2)});
+        if (!s.low) t.tipReads += 2;
+        s.cherry = -1;
+    }
+    d.flags = mi355::walkFlags(m.k1, k2, m.hold, smodeNow, m.storeBuf >= 0 || tableStore);
+    if (asmLoop && m.k1 == mi355::PK_TAB) d.flags |= mi355::WF_X | mi355::WF_TAB1;
+    if (asmLoop && k2 == mi355::PK_TAB) d.flags |= mi355::WF_MEM2 | mi355::WF_TAB2;
+    if (m.k1 != mi355::PK_TIPS) d.flags |= skipLoads & mi355::WF_NOLOAD1;
+    if (k2 != mi355::PK_TIPS) d.flags |= skipLoads & mi355::WF_NOLOAD2;
+    if (ablate) {
+        if (ablate & 1) d.flags &= ~(unsigned)mi355::WF_STORE;
+        if (ablate & 2) d.flags &= ~(unsigned)mi355::WF_X;
+        if (ablate & 4) d.scale = in->onesScale;
+        if (ablate & 8) { if (m.k1 == mi355::PK_TIPS) d.src1 = in->dummyTips; if (m.k2 == mi355::PK_TIPS) d.src2 = in->dummyTips; }
+    }
+    w.push_back(d);
+    s.lastStore = m.storeBuf; s.lastHold = m.hold;
+    return 0;
+}
+
+// Behind a slice's micro-operations: the no-ops its kernel's pipeline needs, where its product of factors goes, the stage waits, its
+// pattern range and what a held launch has to know of it
+void ProgramResolver::sliceEpilogue(const Slice& s) {
+    std::vector<mi355::WalkOp>& w = r.w;
+    mi355::WalkSeg& sg = r.segs[s.si];
+    // (the kernels' software pipelines: the assembly loop is three micro-operations deep and leaves behind any stage — any
+    // length, three more readable descriptors —; the C++ kernel and the T32 walk are two deep: an even length, two more)
+    if (!asmLoop && !(in->walkT && in->S > 20) && ((int)w.size() - sg.progStart) % 2) w.push_back(nop);      // (k_walkT64 prefetches nothing across stages)
+    sg.progCount = (int)w.size() - sg.progStart;
+    for (int q = 0; q < (asmLoop ? 3 : 2); q++) w.push_back(nop);
+    if (sums && !r.sumRows.empty() && r.sumRows.back() == (int)s.si) {      // (this slice writes factors: where its product of them goes)
+        w.back().scaleW = in->sliceMant.as<double>() + s.si * in->pairLen;
+        w.back().store = (double*)(in->sliceExp.as<int>() + s.si * in->pairLen);
+    }
+    static const int padMode = labEnv("BEAGLE_MI355_WALK_PAD_FETCH") ? atoi(labEnv("BEAGLE_MI355_WALK_PAD_FETCH")) : 1;     // (LAB builds: 0 never, 1 the default, 2 both)
+    mi355::walkStageWaits(w.data(), sg.progStart, sg.progCount, asmLoop, in->strictWaits, padMode);
+    if (s.low) { sg.pStart = s.tab->row; sg.pEnd = s.tab->row + s.tab->D; sg.tStart = 0; sg.next = -1; return; }
+    const mi355::PlanSeg& ps = *s.ps;
+    sg.pStart = in->partStart[ps.partition]; sg.pEnd = in->partEnd[ps.partition]; sg.tStart = in->padStart[ps.partition];
+    r.maxRange = std::max(r.maxRange, sg.pEnd - sg.pStart);
+    if (r.oneLaunch) {
+        if (ps.progCount > 0) r.finalStore[s.si] = use->prog[(size_t)ps.progStart + ps.progCount - 1].storeBuf;
+        r.finalPart[s.si] = ps.partition;
+    }
+}
+
+// What takes the whole program: the ticket chain, the sinks, the cherry matrices; then r is valid
+void ProgramResolver::finish() {
     for (size_t oi = 0; oi < nUp; oi++) {          // (kernels.h WalkSeg::next: rows of THIS array)
-        const mi355::PlanSeg& ps = U.segs[fused ? (size_t)order[oi] : oi];
-        segs[oi].next = ticket && ps.next >= 0 ? posOf[(size_t)ps.next] : -1;
+        const mi355::PlanSeg& ps = use->segs[r.oneLaunch ? (size_t)r.order[oi] : oi];
+        r.segs[oi].next = ticket && ps.next >= 0 ? posOf[(size_t)ps.next] : -1;
     }
-    if (slot) slot->leaves = ticket ? plan.leaves : 0;
-    cm.clear();
+    r.sinks = 0; r.sinkRows.clear();
+    if (r.oneLaunch) {
+        std::vector<char> feeds(r.segs.size(), 0);
+        for (int d : r.deps) feeds[(size_t)d] = 1;
+        for (size_t i = 0; i < nUp; i++) if (!feeds[i] && r.segs[i].progCount > 0) r.sinkRows.push_back((int)i);
+        r.sinks = (int)r.sinkRows.size();
+    }
+    r.cm.clear();
     if (!fusedAt.empty()) {
-        cm.assign(2 * w.size(), nullptr);
-        for (const FusedAt& f : fusedAt) { cm[2 * f.at] = in->matrices + (size_t)f.matA * matStride; cm[2 * f.at + 1] = in->matrices + (size_t)f.matB * matStride; }
+        r.cm.assign(2 * r.w.size(), nullptr);
+        for (const FusedAt& f : fusedAt) { r.cm[2 * f.at] = in->matrices + (size_t)f.matA * matStride; r.cm[2 * f.at + 1] = in->matrices + (size_t)f.matB * matStride; }
     }
-    in->statFused += (long)fusedAt.size();
-    if (slot) slot->fused = (long)fusedAt.size();
-    if (slot) {
-        slot->tag = planTag; slot->epoch = in->resolveEpoch; slot->maxRange = maxRange;
-        slot->memReads = in->statMemReads - s0[0]; slot->tipReads = in->statTipReads - s0[1]; slot->scaleReads = in->statScaleReads - s0[2];
-        slot->scaleWrites = in->statScaleWrites - s0[3]; slot->stored = in->statStored - s0[4];
+    r.traffic.fused = (long)fusedAt.size();
+    for (const mi355::PlanSeg& sg : use->segs) r.traffic.microOps += sg.progCount;
+    if (r.kept) r.tag = planTag;
+    r.epoch = in->resolveEpoch;
+}
+
+static int resolveProgram(Instance* in, const mi355::Plan& plan, long planTag, Instance::Resolved& r) {
+    ProgramResolver pr{in, plan, r, planTag};
+    return pr.run();
+}
+
+// ---- running a resolved program ---------------------------------------------------------------------------------------------------
+// the one place where a program's traffic reaches the instance's counters
+static void accountTraffic(Instance* in, const Instance::Resolved& r) {
+    const Instance::WalkTraffic& t = r.traffic;
+    in->statMemReads += t.memReads; in->statTipReads += t.tipReads; in->statScaleReads += t.scaleReads;
+    in->statScaleWrites += t.scaleWrites; in->statStored += t.stored; in->statFused += t.fused; in->statMicroOps += t.microOps;
+    in->statTableRows += t.tableRows; in->statTableReads += t.tableReads; in->statRepeatClades += t.repeatClades;
+    in->statTwoTables += t.twoTables; in->statUnstoredConsumers += t.unstoredConsumers;
+}
+
+// the slices' products of factors this run leaves behind, and which scale buffers they cover (engine_abi.cpp accumulate)
+static void recordSliceSums(Instance* in, const Instance::Resolved& r) {
+    if (r.sumRows.empty()) return;
+    if (in->scaleGen.size() < (size_t)in->scaleCount) { in->scaleGen.assign((size_t)in->scaleCount, 0); in->scaleSeen.assign((size_t)in->scaleCount, 0); }
+    const long gen = ++in->sliceGen;
+    for (int idx : r.wroteScale) in->scaleGen[(size_t)idx] = gen;
+    in->lastSums.valid = true; in->lastSums.epoch = in->scaleWriteEpoch; in->lastSums.gen = gen; in->lastSums.rows = r.sumRows; in->lastSums.nWritten = (int)r.wroteScale.size();
+}
+
+// the folds a kept program reads are those of the scale buffers as they are now; *bad: one of them leaves the safe range
+static int refreshProgramFolds(Instance* in, Instance::Resolved& r, bool* bad) {
+    *bad = false;
+    if (r.folds.empty()) return 0;
+    if (r.foldEpoch != in->scaleWriteEpoch) {
+        int rc = refreshFolds(in, r.folds, bad); if (rc) return rc;
+        r.foldEpoch = in->scaleWriteEpoch;
+        if (*bad) return 0;
     }
+    in->statFoldedVectors = (long)r.folds.size();
+    return 0;
+}
+
+// The packed program: [micro-ops (64 B each) | segments (32 B each) | dependency lists | snapshot pairs | the matrices of fused cherries,
+// two pointers per micro-operation, where the program has any] — ONE host-to-device copy.  `dev`: where it is on the device; `staged`: the
+// program as this call staged it, seen through the ring's device mapping (nullptr: it was resident, or went by another route).
+struct PackedProgram {
+    struct Part { size_t off; const void* src; size_t bytes; } part[5];        // micro-ops, segments, dependencies, snapshot pairs, cherry matrices
+    size_t total = 0;
+    int nOps = 0, nPairs = 0;
+    char* dev = nullptr; const char* staged = nullptr;
+    PackedProgram(const Instance::Resolved& r, const mi355::Plan& plan) : nOps((int)r.w.size()), nPairs((int)(plan.snapPairs.size() / 2)) {
+        const size_t opBytes = r.w.size() * sizeof(mi355::WalkOp), segBytes = r.segs.size() * sizeof(mi355::WalkSeg), depBytes = r.deps.size() * sizeof(int);
+        const size_t pairBytes = plan.snapPairs.size() * sizeof(int), pairOff = opBytes + segBytes + ((depBytes + 31) & ~(size_t)31);
+        part[0] = Part{0, r.w.data(), opBytes};
+        part[1] = Part{opBytes, r.segs.data(), segBytes};
+        part[2] = Part{opBytes + segBytes, r.deps.data(), depBytes};
+        part[3] = Part{pairOff, plan.snapPairs.data(), pairBytes};
+        part[4] = Part{pairOff + ((pairBytes + 15) & ~(size_t)15), r.cm.data(), r.cm.size() * sizeof(const double*)};
+        total = part[4].off + part[4].bytes;
     }
-    if (anyScaleWriteIn(in, slot, reuse, statsAtEntry[3])) scalesWritten(in);
-    {   // the slices' products of factors this run leaves behind, and which scale buffers they cover (engine_abi.cpp accumulate)
-        const std::vector<int>& rows = slot ? slot->sumRows : sumRowsLocal;
-        const std::vector<int>& wrote = slot ? slot->wroteScale : wroteLocal;
-        if (!rows.empty()) {
-            if (in->scaleGen.size() < (size_t)in->scaleCount) { in->scaleGen.assign((size_t)in->scaleCount, 0); in->scaleSeen.assign((size_t)in->scaleCount, 0); }
-            const long gen = ++in->sliceGen;
-            for (int idx : wrote) in->scaleGen[(size_t)idx] = gen;
-            in->lastSums.valid = true; in->lastSums.epoch = in->scaleWriteEpoch; in->lastSums.gen = gen; in->lastSums.rows = rows; in->lastSums.nWritten = (int)wrote.size();
-        }
-    }
-    if (slot && !slot->folds.empty()) {
-        if (slot->foldEpoch != in->scaleWriteEpoch) {
-            bool bad = false;
-            int rcf = refreshFolds(in, slot->folds, &bad); if (rcf) return rcf;
-            slot->foldEpoch = in->scaleWriteEpoch;
-            if (bad) {                                 // out of range: this plan keeps per-node factors from now on
-                in->statMemReads = statsAtEntry[0]; in->statTipReads = statsAtEntry[1]; in->statScaleReads = statsAtEntry[2];
-                in->statScaleWrites = statsAtEntry[3]; in->statStored = statsAtEntry[4];
-                slot->noFoldTag = planTag; slot->tag = 0; slot->dProgValid = false; slot->folds.clear();
-                return runPlan(in, plan, planTag, recordBeforeWalk);
-            }
-        }
-        in->statFoldedVectors = (long)slot->folds.size();
-    }
-    // (from here on: UP = the plan the device program was made from; its slices come first in `segs`, the class-table programs behind them)
-    const mi355::Plan& UP = *use;
-    const size_t upN = UP.segs.size(), lowN = slot && slot->compressed ? slot->repeats.lower.size() : 0;
-    { long upperOps = 0; for (const mi355::PlanSeg& sg : UP.segs) upperOps += sg.progCount; in->statMicroOps += upperOps; }
-    ph1 = PhaseClock::now();
-    // pack: [micro-ops (64 B each) | segments (32 B each) | dependency lists | snapshot pairs] — ONE host-to-device copy
-    const size_t opBytes = w.size() * sizeof(mi355::WalkOp), segBytes = segs.size() * sizeof(mi355::WalkSeg) + ((devDeps.size() * sizeof(int) + 31) & ~(size_t)31);
-    // (... | the matrices of fused cherries, two pointers per micro-operation, where the program has any)
-    const size_t pairBytes = plan.snapPairs.size() * sizeof(int), cmOff = opBytes + segBytes + ((pairBytes + 15) & ~(size_t)15), cmBytes = cm.size() * sizeof(const double*);
-    const size_t total = cmOff + cmBytes;
-    const size_t depOff = opBytes + segs.size() * sizeof(mi355::WalkSeg);
-    char* dBase = nullptr;
-    const char* stagedProg = nullptr;                             // the program as this call staged it, seen through the ring's device mapping
-    if (reuse && slot->dProgValid) dBase = slot->dProg.p;          // a cached plan's program is already on the device, bit for bit
-    else if (total <= RING_BYTES / 4) {
-        const long off = stage(in, w.data(), opBytes, total);                    // reserves `total` bytes, copies the ops ...
-        if (off < 0) return BEAGLE_ERROR_GENERAL;
-        memcpy(in->hRing + off + opBytes, segs.data(), segs.size() * sizeof(mi355::WalkSeg));     // ... the rest is filled in behind them
-        if (!devDeps.empty()) memcpy(in->hRing + off + depOff, devDeps.data(), devDeps.size() * sizeof(int));
-        if (pairBytes) memcpy(in->hRing + off + opBytes + segBytes, plan.snapPairs.data(), pairBytes);
-        if (cmBytes) memcpy(in->hRing + off + cmOff, cm.data(), cmBytes);
-        { int rcq = queueCopy(in, in->dRing + off, (size_t)off, total); if (rcq) return rcq; }
-        dBase = in->dRing + off;
-        if (in->kernelUploads) stagedProg = (const char*)in->hRingDev + off;
-        if (slot) {                                   // keep a device copy for the next time this plan comes out of the cache
-            { int rcg = growDevice(in, slot->dProg, total, total + total / 4, Grow::SyncIfHeld); if (rcg) return rcg; }
-            if (in->kernelUploads) { int rcq = queueCopy(in, slot->dProg.p, (size_t)off, total); if (rcq) return rcq; }     // (from the same staged bytes)
-            else HIP_TRY(hipMemcpyAsync(slot->dProg.p, in->dRing + off, total, hipMemcpyDeviceToDevice, live(in)));
-            slot->dProgValid = true;
-        }
-    } else {                                  // a tree of > ~60 000 nodes: its own staging buffer, synchronous copy
+    const mi355::WalkOp* ops(const char* base) const { return (const mi355::WalkOp*)base; }
+    const mi355::WalkSeg* segs(const char* base) const { return (const mi355::WalkSeg*)(base + part[1].off); }
+    const int* deps(const char* base) const { return (const int*)(base + part[2].off); }
+    const int* pairs(const char* base) const { return (const int*)(base + part[3].off); }
+    const double* const* cherryMats(const char* base) const { return part[4].bytes ? (const double* const*)(base + part[4].off) : nullptr; }
+};
+// the matrix stream of a program: both branch matrices of every micro-operation, in program order; 4 states: 2 x 5 columns x 4 per
+// category, and behind them, where the program has fused cherries, the cherry region of the same size (kernels_walk4.hip)
+static inline unsigned cherryRegionOff(const Instance* in, const Instance::Resolved& r) {
+    return r.cm.empty() ? 0u : (unsigned)(r.w.size() * (size_t)in->C * 40 * sizeof(double));
+}
+static inline size_t matStreamBytes(const Instance* in, const Instance::Resolved& r) {
+    if (in->walkT) return mi355::walkT32StreamBytes((int)r.w.size(), in->C, in->S) + 8192;          // (the kernel's second fragment load reads up to 1.8 KB past an entry)
+    return r.w.size() * (size_t)in->C * 40 * sizeof(double) * (r.cm.empty() ? 1 : 2) + 1024;
+}
+
+// Put the program where the launches read it: a kept program that is resident stays where it is; otherwise through the staging ring (and
+// into the kept program's own device copy), or — a tree of > ~60 000 nodes — through a staging buffer of its own, synchronously
+static int stageProgram(Instance* in, Instance::Resolved& r, PackedProgram& pp) {
+    if (r.kept && r.dProgValid) { pp.dev = r.dProg.p; return 0; }          // a cached plan's program is already on the device, bit for bit
+    if (pp.total > RING_BYTES / 4) {
         HIP_TRY(hipStreamSynchronize(live(in)));
-        { int rcg = growDevice(in, in->bigStage, total, total, Grow::SyncIfHeld); if (rcg) return rcg; }      // (its drain finds the stream idle: see above)
-        HIP_TRY(hipMemcpy(in->bigStage.p, w.data(), opBytes, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(in->bigStage.p + opBytes, segs.data(), segs.size() * sizeof(mi355::WalkSeg), hipMemcpyHostToDevice));
-        if (!devDeps.empty()) HIP_TRY(hipMemcpy(in->bigStage.p + depOff, devDeps.data(), devDeps.size() * sizeof(int), hipMemcpyHostToDevice));
-        if (pairBytes) HIP_TRY(hipMemcpy(in->bigStage.p + opBytes + segBytes, plan.snapPairs.data(), pairBytes, hipMemcpyHostToDevice));
-        if (cmBytes) HIP_TRY(hipMemcpy(in->bigStage.p + cmOff, cm.data(), cmBytes, hipMemcpyHostToDevice));
-        dBase = in->bigStage.p;
+        { int rc = growDevice(in, in->bigStage, pp.total, pp.total, Grow::SyncIfHeld); if (rc) return rc; }      // (its drain finds the stream idle)
+        for (const PackedProgram::Part& q : pp.part) if (q.bytes) HIP_TRY(hipMemcpy(in->bigStage.p + q.off, q.src, q.bytes, hipMemcpyHostToDevice));
+        pp.dev = in->bigStage.p;
+        return 0;
     }
-    ph2 = PhaseClock::now();
-    const bool fusedSnapshot = pairBytes && !in->walkT && in->fuseLaunches;          // 4 states: together with the gather below
-    if (pairBytes && !fusedSnapshot)
-        mi355::launchSnapshotMatrices(live(in), in->matrices, (const int*)(dBase + opBytes + segBytes), (int)(plan.snapPairs.size() / 2),
-                                      in->C * in->S * in->S);
-    // the matrix stream: both branch matrices of every micro-operation, in program order (after the snapshots they may name)
-    const size_t streamBytes = in->walkT ? mi355::walkT32StreamBytes((int)w.size(), in->C, in->S) + 8192          // (the kernel's second fragment load reads up to 1.8 KB past an entry)
-                                         : w.size() * (size_t)in->C * 40 * sizeof(double) * (cmBytes ? 2 : 1) + 1024;   // 2 x 5 columns x 4 per category; behind them the cherry region (kernels_walk4.hip)
-    { int rcg = growDevice(in, in->matStream, streamBytes, std::max(streamBytes + streamBytes / 4, (size_t)1 << 20), Grow::SyncAndFree); if (rcg) return rcg; }
-    // 4 states, a program staged by this call (a partial update, a list the engine has not seen): its upload — and whatever else is
-    // queued — rides in the gather's launch, which reads the program through the ring's mapping meanwhile (kernels_walk4.hip
-    // k_gatherAndSnapshot): three launches per such evaluation instead of four.  Not when a queued copy lands in what the gather
-    // reads or writes (the matrix block, the stream), or two queued copies overlap in part: then they go first, in order (live()).
-    bool uploadsRide = !in->walkT && in->fuseLaunches && stagedProg && !in->pendingCopies.empty() && (int)in->pendingCopies.size() <= mi355::HOST_COPY_MAX;
-    if (uploadsRide) {
-        const char* m0 = (const char*)in->matrices;
-        const char* m1 = m0 + (size_t)std::max(1, in->planner.matrixSlots()) * in->C * in->S * in->S * sizeof(double);
-        const char* t0 = in->matStream.p; const char* t1 = t0 + in->matStream.bytes;
-        const std::vector<Instance::PendingCopy>& pc = in->pendingCopies;
-        for (size_t a = 0; a < pc.size() && uploadsRide; a++) {
-            const char* d0 = (const char*)pc[a].dst; const char* d1 = d0 + pc[a].bytes;
-            if ((d0 < m1 && m0 < d1) || (d0 < t1 && t0 < d1)) uploadsRide = false;
-            for (size_t b = a + 1; b < pc.size() && uploadsRide; b++) {
-                const char* e0 = (const char*)pc[b].dst; const char* e1 = e0 + pc[b].bytes;
-                if (d0 < e1 && e0 < d1 && !(e0 <= d0 && d1 <= e1)) uploadsRide = false;
-            }
+    const long off = stage(in, pp.part[0].src, pp.part[0].bytes, pp.total);      // reserves `total` bytes, copies the ops ...
+    if (off < 0) return BEAGLE_ERROR_GENERAL;
+    for (int k = 1; k < 5; k++) if (pp.part[k].bytes) memcpy(in->hRing + off + pp.part[k].off, pp.part[k].src, pp.part[k].bytes);      // ... the rest is filled in behind them
+    { int rc = queueCopy(in, in->dRing + off, (size_t)off, pp.total); if (rc) return rc; }
+    pp.dev = in->dRing + off;
+    if (in->kernelUploads) pp.staged = (const char*)in->hRingDev + off;
+    if (r.kept) {                                 // keep a device copy for the next time this plan comes out of the cache
+        { int rc = growDevice(in, r.dProg, pp.total, pp.total + pp.total / 4, Grow::SyncIfHeld); if (rc) return rc; }
+        if (in->kernelUploads) { int rc = queueCopy(in, r.dProg.p, (size_t)off, pp.total); if (rc) return rc; }     // (from the same staged bytes)
+        else HIP_TRY(hipMemcpyAsync(r.dProg.p, in->dRing + off, pp.total, hipMemcpyDeviceToDevice, live(in)));
+        r.dProgValid = true;
+    }
+    return 0;
+}
+
+// 4 states, a program staged by this call (a partial update, a list the engine has not seen): its upload — and whatever else is
+// queued — rides in the gather's launch, which reads the program through the ring's mapping meanwhile (kernels_walk4.hip
+// k_gatherAndSnapshot): three launches per such evaluation instead of four.  Not when a queued copy lands in what the gather
+// reads or writes (the matrix block, the stream), or two queued copies overlap in part: then they go first, in order (live()).
+static bool uploadsCanRide(const Instance* in, const PackedProgram& pp) {
+    if (in->walkT || !in->fuseLaunches || !pp.staged || in->pendingCopies.empty() || (int)in->pendingCopies.size() > mi355::HOST_COPY_MAX) return false;
+    const char* m0 = (const char*)in->matrices;
+    const char* m1 = m0 + (size_t)std::max(1, in->planner.matrixSlots()) * in->C * in->S * in->S * sizeof(double);
+    const char* t0 = in->matStream.p; const char* t1 = t0 + in->matStream.bytes;
+    const std::vector<Instance::PendingCopy>& pc = in->pendingCopies;
+    for (size_t a = 0; a < pc.size(); a++) {
+        const char* d0 = (const char*)pc[a].dst; const char* d1 = d0 + pc[a].bytes;
+        if ((d0 < m1 && m0 < d1) || (d0 < t1 && t0 < d1)) return false;
+        for (size_t b = a + 1; b < pc.size(); b++) {
+            const char* e0 = (const char*)pc[b].dst; const char* e1 = e0 + pc[b].bytes;
+            if (d0 < e1 && e0 < d1 && !(e0 <= d0 && d1 <= e1)) return false;
         }
     }
-    if (uploadsRide) {
-        if (in->pendingWalk.valid) { int rcw = flushWalk(in); if (rcw) return rcw; }          // (cannot be: queueCopy above launched it)
+    return true;
+}
+// the queued uploads as the copy list of one launch (the queue is empty afterwards); returns the 4 KiB blocks they take
+static unsigned takeQueuedCopies(Instance* in, mi355::HostCopyList& L) {
+    L.n = 0;
+    unsigned blocks = 0;
+    for (const Instance::PendingCopy& pc : in->pendingCopies) {
+        mi355::HostCopyList::Entry& e = L.e[L.n++];
+        e.dst = pc.dst; e.src = in->hRingDev + pc.ringOff; e.bytes = (unsigned)pc.bytes; e.firstBlock = blocks;
+        blocks += (unsigned)((pc.bytes + 4095) / 4096);
+    }
+    for (int a = 0; a < L.n; a++)                 // (an array queued twice: the later upload wins, the covered one is dropped)
+        for (int b = a + 1; b < L.n; b++)
+            if ((const char*)L.e[b].dst <= (const char*)L.e[a].dst && (const char*)L.e[a].dst + L.e[a].bytes <= (const char*)L.e[b].dst + L.e[b].bytes) L.e[a].bytes = 0;
+    in->pendingCopies.clear();
+    return blocks;
+}
+
+// The plan's matrix snapshots and the matrix stream (after the snapshots it may name); *rode: the queued uploads went in the same launch
+static int gatherMatrices(Instance* in, const Instance::Resolved& r, const PackedProgram& pp, bool* rode) {
+    const int elems = in->C * in->S * in->S;
+    const bool fusedSnapshot = pp.nPairs && !in->walkT && in->fuseLaunches;          // 4 states: together with the gather below
+    if (pp.nPairs && !fusedSnapshot) mi355::launchSnapshotMatrices(live(in), in->matrices, pp.pairs(pp.dev), pp.nPairs, elems);
+    const size_t streamBytes = matStreamBytes(in, r);
+    { int rc = growDevice(in, in->matStream, streamBytes, std::max(streamBytes + streamBytes / 4, (size_t)1 << 20), Grow::SyncAndFree); if (rc) return rc; }
+    *rode = uploadsCanRide(in, pp);
+    if (*rode) {
+        if (in->pendingWalk.valid) { int rc = flushWalk(in); if (rc) return rc; }          // (cannot be: queueCopy launched it)
         mi355::HostCopyList L;
-        L.n = 0;
-        unsigned blocks = 0;
-        for (const Instance::PendingCopy& pc : in->pendingCopies) {
-            mi355::HostCopyList::Entry& e = L.e[L.n++];
-            e.dst = pc.dst; e.src = in->hRingDev + pc.ringOff; e.bytes = (unsigned)pc.bytes; e.firstBlock = blocks;
-            blocks += (unsigned)((pc.bytes + 4095) / 4096);
-        }
-        for (int a = 0; a < L.n; a++)                 // (an array queued twice: the later upload wins, the covered one is dropped)
-            for (int b = a + 1; b < L.n; b++)
-                if ((const char*)L.e[b].dst <= (const char*)L.e[a].dst && (const char*)L.e[a].dst + L.e[a].bytes <= (const char*)L.e[b].dst + L.e[b].bytes) L.e[a].bytes = 0;
-        in->pendingCopies.clear();
-        mi355::launchGatherAndSnapshot(in->stream, (const mi355::WalkOp*)stagedProg, (int)w.size(), in->C, in->matStream.p, in->matrices,
-                                       (const int*)(stagedProg + opBytes + segBytes), (int)(plan.snapPairs.size() / 2), in->C * in->S * in->S, &L, (int)blocks,
-                                       cmBytes ? (const double* const*)(stagedProg + cmOff) : nullptr);
+        const unsigned blocks = takeQueuedCopies(in, L);
+        mi355::launchGatherAndSnapshot(in->stream, pp.ops(pp.staged), pp.nOps, in->C, in->matStream.p, in->matrices, pp.pairs(pp.staged), pp.nPairs, elems,
+                                       &L, (int)blocks, pp.cherryMats(pp.staged));
     }
-    else if (in->walkT) mi355::launchGatherFragments(live(in), (const mi355::WalkOp*)dBase, (int)w.size(), in->C, in->S, in->matStream.p);
-    else if (fusedSnapshot) mi355::launchGatherAndSnapshot(live(in), (const mi355::WalkOp*)dBase, (int)w.size(), in->C, in->matStream.p, in->matrices,
-                                                           (const int*)(dBase + opBytes + segBytes), (int)(plan.snapPairs.size() / 2), in->C * in->S * in->S, nullptr, 0,
-                                                           cmBytes ? (const double* const*)(dBase + cmOff) : nullptr);
-    else mi355::launchGatherMatrices(live(in), (const mi355::WalkOp*)dBase, (int)w.size(), in->C, in->matStream.p,
-                                     cmBytes ? (const double* const*)(dBase + cmOff) : nullptr);
-    if (labEnv("BEAGLE_MI355_DUMP_PLAN")) {           // development (LAB builds): the slices of this program, wave by wave
-        fprintf(stderr, "[mi355] plan: %zu micro-ops in %zu slices (+ %zu class-table programs):", n, upN, lowN);
-        for (size_t i = 0; i < upN; i++) {
-            const mi355::PlanSeg& ps = UP.segs[fused ? (size_t)order[i] : i];
-            fprintf(stderr, " w%d:%d", ps.wave, segs[i].progCount);
-            if (fused) fprintf(stderr, "(t%d d%d)", ps.tail, ps.depCount);
-        }
-        fprintf(stderr, "\n");
-        if (atoi(labEnv("BEAGLE_MI355_DUMP_PLAN")) > 1)
-            for (size_t i = 0; i < w.size(); i++)
-                fprintf(stderr, "[mi355]   %3zu: k1 %u k2 %u hold %u scale %u store %d\n", i, (w[i].flags >> 5) & 7, (w[i].flags >> 8) & 7, (w[i].flags >> 11) & 3,
-                        (w[i].flags >> 13) & 3, (w[i].flags & mi355::WF_STORE) ? 1 : 0);
+    else if (in->walkT) mi355::launchGatherFragments(live(in), pp.ops(pp.dev), pp.nOps, in->C, in->S, in->matStream.p);
+    else if (fusedSnapshot) mi355::launchGatherAndSnapshot(live(in), pp.ops(pp.dev), pp.nOps, in->C, in->matStream.p, in->matrices, pp.pairs(pp.dev), pp.nPairs, elems,
+                                                           nullptr, 0, pp.cherryMats(pp.dev));
+    else mi355::launchGatherMatrices(live(in), pp.ops(pp.dev), pp.nOps, in->C, in->matStream.p, pp.cherryMats(pp.dev));
+    return 0;
+}
+
+// development (LAB builds, BEAGLE_MI355_DUMP_PLAN): the slices of this program, wave by wave
+static void dumpPlan(const Instance::Resolved& r, const mi355::Plan& plan) {
+    if (!labEnv("BEAGLE_MI355_DUMP_PLAN")) return;
+    const mi355::Plan& UP = planInUse(r, plan);
+    const size_t lowN = lowerSlices(r), upN = r.segs.size() - lowN;
+    fprintf(stderr, "[mi355] plan: %zu micro-ops in %zu slices (+ %zu class-table programs):", plan.prog.size(), upN, lowN);
+    for (size_t i = 0; i < upN; i++) {
+        const mi355::PlanSeg& ps = UP.segs[r.oneLaunch ? (size_t)r.order[i] : i];
+        fprintf(stderr, " w%d:%d", ps.wave, r.segs[i].progCount);
+        if (r.oneLaunch) fprintf(stderr, "(t%d d%d)", ps.tail, ps.depCount);
     }
-    ph3 = PhaseClock::now();
-    if (in->hostTrace) {                               // (BEAGLE_MI355_HOST_TIMING=2: what the first few gather launches of the process were made of)
-        static std::atomic<int> left{6};
-        if (left.fetch_sub(1) > 0)
-            fprintf(stderr, "[mi355] gather launch: %zu micro-operations x %d categories%s, %zu matrix snapshots, program %s (%zu bytes), %zu queued uploads ride along\n",
-                    w.size(), in->C, cmBytes ? " + cherry region" : "", plan.snapPairs.size() / 2, stagedProg ? "staged by this call" : "on the device",
-                    total, uploadsRide ? (size_t)1 : (size_t)0);
-    }
-    if (in->hostTrace && !reuse && n >= 64) {
-        auto us = [](PhaseClock::time_point a, PhaseClock::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
-        fprintf(stderr, "[mi355] program of %zu micro-operations resolved: descriptors and waits %.1f us, upload %.1f us, stream + gather launch %.1f us\n", n, us(ph0, ph1), us(ph1, ph2), us(ph2, ph3));
-    }
-    if (recordBeforeWalk) HIP_TRY(hipEventRecord(recordBeforeWalk, live(in)));
-    // the class tables of this evaluation: every class-table program in ONE launch in front of the walk — they wait for nothing, and
-    // stream order is all the walk needs to find their rows written
-    in->lowerLaunched = false;
-    if (lowN) {
-        const mi355::WalkSeg* dLow = (const mi355::WalkSeg*)(dBase + opBytes) + upN;
-        if (in->fastWalk)
-            mi355::launchWalk4Fast(live(in), (const mi355::WalkOp*)dBase, dLow, (int)lowN, slot->lowerRange, in->matStream.p, in->P, in->C, (long)in->scaleStride,
-                                   nullptr, nullptr, 0, 0, nullptr, 0, nullptr, nullptr, 0, false, cmBytes ? (unsigned)(w.size() * (size_t)in->C * 40 * sizeof(double)) : 0u);
-        else
-            mi355::launchWalk4(live(in), (const mi355::WalkOp*)dBase, dLow, (int)lowN, slot->lowerRange, in->matStream.p, in->P, in->C, (long)in->scaleStride);
-        in->lowerLaunched = true;
-    }
-    if (fused) {
-        // ONE launch: slice y of the device program is dispatched before slice y + 1 (x fastest), every slice behind the ones it
-        // waits for; a workgroup signals flags[y][x] = epoch when its stores are out, its dependants poll for exactly that value
-        int range = 0;
-        for (size_t i = 0; i < upN; i++) range = std::max(range, segs[i].pEnd - segs[i].pStart);
-        const int flagStride = (in->P + 127) / 128 + 1;
-        const size_t flagBytes = segs.size() * (size_t)flagStride * sizeof(unsigned);
-        const size_t want = (std::max(flagBytes + flagBytes / 2, (size_t)1 << 16) + 255) & ~(size_t)255;
-        bool grew = false;
-        in->walkTickets = nullptr;                                                  // (re-derived below: a failed growth leaves none)
-        { int rcg = growDevice(in, in->walkFlags, 2 * flagBytes, 2 * want, Grow::SyncAndFree, &grew); if (rcg) return rcg; }      // [flags | tickets]
-        if (grew) HIP_TRY(hipMemsetAsync(in->walkFlags.p, 0, in->walkFlags.bytes, live(in)));
-        in->walkTickets = (unsigned*)(in->walkFlags.p + in->walkFlags.bytes / 2);
-        if (++in->walkEpoch == 0u) in->walkEpoch = 1u;
-        Instance::PendingWalk& pw = in->pendingWalk;
-        if (pw.valid) { int rcf = flushWalk(in); if (rcf) return rcf; }            // (cannot happen: every path here went through live())
-        pw.prog = (const mi355::WalkOp*)dBase; pw.segs = (const mi355::WalkSeg*)(dBase + opBytes); pw.deps = (const int*)(dBase + depOff);
-        pw.nSegs = (int)upN; pw.range = range; pw.flagStride = flagStride; pw.epoch = in->walkEpoch;
-        pw.leaves = slot && reuse ? slot->leaves : (ticket ? plan.leaves : 0);
-        pw.cherryOff = cmBytes ? (unsigned)(w.size() * (size_t)in->C * 40 * sizeof(double)) : 0u;
-        in->statFastWalks++; in->statWalks++;
-        // hold the launch back for the root call?  (one partition, the whole range, not inside a timer bracket)
-        // ... and only a program whose slices ALL lead to one last slice: the root call's result word then says that every workgroup
-        // of the launch is done (waitResult and its callers reset the staging ring on seeing it) — a forest's other trees could
-        // still be running behind the slice that publishes
-        int sinks = slot && reuse ? slot->sinks : 0;
-        if (!(slot && reuse)) {
-            std::vector<char> feeds(segs.size(), 0);
-            for (int d : devDeps) feeds[(size_t)d] = 1;
-            for (size_t i = 0; i < upN; i++) if (!feeds[i] && segs[i].progCount > 0) sinks++;
-            if (slot) slot->sinks = sinks;
-        }
-        // (a partitioned instance, round 6: up to eight partitions in the list, every one ending in ONE slice — the by-partition root call
-        // names them all or the launch goes out without it: engine_abi.cpp beagleCalculateRootLogLikelihoodsByPartition)
-        const bool holdParts = in->partitionCount > 1 && sinks >= 1 && sinks <= mi355::ROOT_MAX_PARTS && in->fuseRootParts;
-        const bool hold = in->deferWalk && in->fuseLaunches && !recordBeforeWalk && ((in->partitionCount == 1 && range == in->P && sinks == 1) || holdParts);
-        if (hold) {
-            pw.finalStore.assign(upN, -1);
-            pw.finalPart.assign(upN, 0);
-            pw.sinkRows.clear();
-            std::vector<char> feeds(segs.size(), 0);
-            for (int d : devDeps) feeds[(size_t)d] = 1;         // (the slot's own list: what it held when the program was resolved)
-            for (size_t i = 0; i < upN; i++) {
-                const mi355::PlanSeg& ps = UP.segs[(size_t)order[i]];
-                if (ps.progCount > 0) pw.finalStore[i] = UP.prog[(size_t)ps.progStart + ps.progCount - 1].storeBuf;
-                pw.finalPart[i] = ps.partition;
-                if (!feeds[i] && ps.progCount > 0) pw.sinkRows.push_back((int)i);
-            }
-            (void)live(in);                           // the program's copies and the gather are enqueued; only the walk itself waits
-            pw.valid = true;
-            return 0;
-        }
+    fprintf(stderr, "\n");
+    if (atoi(labEnv("BEAGLE_MI355_DUMP_PLAN")) > 1)
+        for (size_t i = 0; i < r.w.size(); i++)
+            fprintf(stderr, "[mi355]   %3zu: k1 %u k2 %u hold %u scale %u store %d\n", i, (r.w[i].flags >> 5) & 7, (r.w[i].flags >> 8) & 7, (r.w[i].flags >> 11) & 3,
+                    (r.w[i].flags >> 13) & 3, (r.w[i].flags & mi355::WF_STORE) ? 1 : 0);
+}
+
+// the class tables of this evaluation: every class-table program in ONE launch in front of the walk — they wait for nothing, and
+// stream order is all the walk needs to find their rows written
+static void launchClassTables(Instance* in, const Instance::Resolved& r, const PackedProgram& pp) {
+    const size_t lowN = lowerSlices(r);
+    in->lowerLaunched = lowN > 0;
+    if (!lowN) return;
+    const mi355::WalkSeg* dLow = pp.segs(pp.dev) + (r.segs.size() - lowN);
+    if (in->fastWalk)
+        mi355::launchWalk4Fast(live(in), pp.ops(pp.dev), dLow, (int)lowN, r.lowerRange, in->matStream.p, in->P, in->C, (long)in->scaleStride,
+                               nullptr, nullptr, 0, 0, nullptr, 0, nullptr, nullptr, 0, false, cherryRegionOff(in, r));
+    else
+        mi355::launchWalk4(live(in), pp.ops(pp.dev), dLow, (int)lowN, r.lowerRange, in->matStream.p, in->P, in->C, (long)in->scaleStride);
+}
+
+// ONE launch (Resolved::oneLaunch): slice y of the device program is dispatched before slice y + 1 (x fastest), every slice behind the ones
+// it waits for; a workgroup signals flags[y][x] = epoch when its stores are out, its dependants poll for exactly that value.  Launched
+// now (flushWalk: on tickets or flags), or held back for the root call.
+static int launchWalk(Instance* in, const Instance::Resolved& r, const PackedProgram& pp, bool timed) {
+    const size_t upN = r.segs.size() - lowerSlices(r);
+    const int flagStride = (in->P + 127) / 128 + 1;
+    const size_t flagBytes = r.segs.size() * (size_t)flagStride * sizeof(unsigned);
+    const size_t want = (std::max(flagBytes + flagBytes / 2, (size_t)1 << 16) + 255) & ~(size_t)255;
+    bool grew = false;
+    in->walkTickets = nullptr;                                                  // (re-derived below: a failed growth leaves none)
+    { int rc = growDevice(in, in->walkFlags, 2 * flagBytes, 2 * want, Grow::SyncAndFree, &grew); if (rc) return rc; }      // [flags | tickets]
+    if (grew) HIP_TRY(hipMemsetAsync(in->walkFlags.p, 0, in->walkFlags.bytes, live(in)));
+    in->walkTickets = (unsigned*)(in->walkFlags.p + in->walkFlags.bytes / 2);
+    if (++in->walkEpoch == 0u) in->walkEpoch = 1u;
+    Instance::PendingWalk& pw = in->pendingWalk;
+    if (pw.valid) { int rc = flushWalk(in); if (rc) return rc; }            // (cannot happen: every path here went through live())
+    pw.prog = pp.ops(pp.dev); pw.segs = pp.segs(pp.dev); pw.deps = pp.deps(pp.dev);
+    pw.nSegs = (int)upN; pw.range = r.maxRange; pw.flagStride = flagStride; pw.epoch = in->walkEpoch;
+    pw.leaves = r.leaves;
+    pw.cherryOff = cherryRegionOff(in, r);
+    in->statFastWalks++; in->statWalks++;
+    // hold the launch back for the root call?  (one partition, the whole range, not inside a timer bracket)
+    // ... and only a program whose slices ALL lead to one last slice: the root call's result word then says that every workgroup
+    // of the launch is done (waitResult and its callers reset the staging ring on seeing it) — a forest's other trees could
+    // still be running behind the slice that publishes
+    // (a partitioned instance, round 6: up to eight partitions in the list, every one ending in ONE slice — the by-partition root call
+    // names them all or the launch goes out without it: engine_abi.cpp beagleCalculateRootLogLikelihoodsByPartition)
+    const bool holdParts = in->partitionCount > 1 && r.sinks >= 1 && r.sinks <= mi355::ROOT_MAX_PARTS && in->fuseRootParts;
+    const bool hold = in->deferWalk && in->fuseLaunches && !timed && ((in->partitionCount == 1 && pw.range == in->P && r.sinks == 1) || holdParts);
+    if (hold) {
+        pw.finalStore = r.finalStore; pw.finalPart = r.finalPart; pw.sinkRows = r.sinkRows;
+        (void)live(in);                           // the program's copies and the gather are enqueued; only the walk itself waits
         pw.valid = true;
-        return flushWalk(in);
+        return 0;
     }
-    // one launch per wave of independent slices (a single one unless the planner cut the forest for a small shard)
+    pw.valid = true;
+    return flushWalk(in);
+}
+
+// one launch per wave of independent slices (a single one unless the planner cut the forest for a small shard)
+static int launchWaves(Instance* in, const Instance::Resolved& r, const mi355::Plan& UP, const PackedProgram& pp) {
+    const size_t lowN = lowerSlices(r), upN = r.segs.size() - lowN;
     for (size_t b = 0; b < upN;) {
         size_t e = b + 1;
         while (e < upN && UP.segs[e].wave == UP.segs[b].wave) e++;
         int range = 0;
-        const bool fast = in->fastWalk;                 // the assembly loop (BEAGLE_MI355_NO_FAST_WALK=1: the C++ reference kernel)
-        for (size_t i = b; i < e; i++) range = std::max(range, segs[i].pEnd - segs[i].pStart);
+        for (size_t i = b; i < e; i++) range = std::max(range, r.segs[i].pEnd - r.segs[i].pStart);
         if (in->walkT) {
-            if (!mi355::launchWalkT32(live(in), (const mi355::WalkOp*)dBase, (const mi355::WalkSeg*)(dBase + opBytes) + b, (int)(e - b), range,
-                                      in->matStream.p, in->P, in->S, in->C, in->holdSlots, anyScaleWriteIn(in, slot, reuse, statsAtEntry[3]))) return BEAGLE_ERROR_GENERAL;
-        } else if (fast) {
-            mi355::launchWalk4Fast(live(in), (const mi355::WalkOp*)dBase, (const mi355::WalkSeg*)(dBase + opBytes) + b, (int)(e - b), range,
+            if (!mi355::launchWalkT32(live(in), pp.ops(pp.dev), pp.segs(pp.dev) + b, (int)(e - b), range,
+                                      in->matStream.p, in->P, in->S, in->C, in->holdSlots, r.traffic.scaleWrites > 0)) return BEAGLE_ERROR_GENERAL;
+        } else if (in->fastWalk) {                 // the assembly loop (BEAGLE_MI355_NO_FAST_WALK=1: the C++ reference kernel)
+            mi355::launchWalk4Fast(live(in), pp.ops(pp.dev), pp.segs(pp.dev) + b, (int)(e - b), range,
                                    in->matStream.p, in->P, in->C, (long)in->scaleStride, nullptr, nullptr, 0, 0, nullptr, 0, nullptr, nullptr, 0, false,
-                                   cmBytes ? (unsigned)(w.size() * (size_t)in->C * 40 * sizeof(double)) : 0u);
+                                   cherryRegionOff(in, r));
             in->statFastWalks++;
         } else
-            mi355::launchWalk4(live(in), (const mi355::WalkOp*)dBase, (const mi355::WalkSeg*)(dBase + opBytes) + b, (int)(e - b), range,
+            mi355::launchWalk4(live(in), pp.ops(pp.dev), pp.segs(pp.dev) + b, (int)(e - b), range,
                                in->matStream.p, in->P, in->C, (long)in->scaleStride, lowN > 0);
         in->statWalks++;
         b = e;
     }
     HIP_TRY(hipGetLastError());
     return 0;
+}
+
+// nothing to compute (every destination became virtual): the definitions' matrix snapshots still have to be taken
+static int snapshotsOnly(Instance* in, const mi355::Plan& plan) {
+    if (plan.snapPairs.empty()) return 0;
+    void* dPairs = nullptr;
+    int rc = uploadTransient(in, plan.snapPairs.data(), plan.snapPairs.size() * sizeof(int), &dPairs); if (rc) return rc;
+    mi355::launchSnapshotMatrices(live(in), in->matrices, (const int*)dPairs, (int)(plan.snapPairs.size() / 2), in->C * in->S * in->S);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// Run a planned program: resolve it to device addresses (or take the kept resolution of a plan out of the planner's cache: buffer
+// addresses never change once a buffer exists), upload it where it is not resident and enqueue the snapshot copies, the gather and the walk.
+int runPlan(Instance* in, const mi355::Plan& plan, long planTag, hipEvent_t recordBeforeWalk) {
+    typedef std::chrono::steady_clock PhaseClock;                    // (BEAGLE_MI355_HOST_TIMING=2: where a call that resolves a program spends its time)
+    const PhaseClock::time_point ph0 = PhaseClock::now();
+    if (plan.prog.empty()) return snapshotsOnly(in, plan);
+    Instance::Resolved& r = planTag && !ablateMode() ? in->resolved[planTag & 7] : in->scratch;
+    r.kept = &r != &in->scratch;
+    bool reuse = r.kept && r.tag == planTag && r.epoch == in->resolveEpoch;
+    in->lastResolveMiss = !reuse;
+    in->lastPlanCached = planTag != 0;
+    if (!reuse) { int rc = resolveProgram(in, plan, planTag, r); if (rc) return rc; }
+    if (r.traffic.scaleWrites > 0) scalesWritten(in);          // (before the folds are compared with the epoch)
+    bool badFolds = false;
+    { int rc = refreshProgramFolds(in, r, &badFolds); if (rc) return rc; }
+    if (badFolds) {                                // out of range: this plan keeps per-node factors from now on (such a program reads no fold)
+        r.noFoldTag = planTag; reuse = false; in->lastResolveMiss = true;
+        int rc = resolveProgram(in, plan, planTag, r); if (rc) return rc;
+    }
+    accountTraffic(in, r);
+    recordSliceSums(in, r);
+    const PhaseClock::time_point ph1 = PhaseClock::now();
+    PackedProgram pp(r, plan);
+    { int rc = stageProgram(in, r, pp); if (rc) return rc; }
+    const PhaseClock::time_point ph2 = PhaseClock::now();
+    bool rode = false;
+    { int rc = gatherMatrices(in, r, pp, &rode); if (rc) return rc; }
+    dumpPlan(r, plan);
+    const PhaseClock::time_point ph3 = PhaseClock::now();
+    if (in->hostTrace) {                               // (BEAGLE_MI355_HOST_TIMING=2: what the first few gather launches of the process were made of)
+        static std::atomic<int> left{6};
+        if (left.fetch_sub(1) > 0)
+            fprintf(stderr, "[mi355] gather launch: %zu micro-operations x %d categories%s, %zu matrix snapshots, program %s (%zu bytes), %zu queued uploads ride along\n",
+                    r.w.size(), in->C, r.cm.empty() ? "" : " + cherry region", (size_t)pp.nPairs, pp.staged ? "staged by this call" : "on the device",
+                    pp.total, rode ? (size_t)1 : (size_t)0);
+    }
+    if (in->hostTrace && !reuse && plan.prog.size() >= 64) {
+        auto us = [](PhaseClock::time_point a, PhaseClock::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
+        fprintf(stderr, "[mi355] program of %zu micro-operations resolved: descriptors and waits %.1f us, upload %.1f us, stream + gather launch %.1f us\n", plan.prog.size(), us(ph0, ph1), us(ph1, ph2), us(ph2, ph3));
+    }
+    if (recordBeforeWalk) HIP_TRY(hipEventRecord(recordBeforeWalk, live(in)));
+    launchClassTables(in, r, pp);
+    if (r.oneLaunch) return launchWalk(in, r, pp, recordBeforeWalk != nullptr);
+    return launchWaves(in, r, planInUse(r, plan), pp);
 }
 
 // Launch the walk that was held back (engine_internal.h PendingWalk) — as it is, or with the slice `root` names finishing the evaluation.
@@ -949,10 +1022,7 @@ int runOperationsWalk(Instance* in, const int* ops, int count, int tuple, int gl
             const Clock::time_point t1 = Clock::now();
             hipEvent_t a = nullptr, b = nullptr;
             const bool launches = !in->planner.planned->prog.empty();
-            if (launches && timeThisCall(in)) {
-                if (in->eventsUsed == in->events.size()) { hipEvent_t x, y; HIP_TRY(hipEventCreate(&x)); HIP_TRY(hipEventCreate(&y)); in->events.emplace_back(x, y); }
-                a = in->events[in->eventsUsed].first; b = in->events[in->eventsUsed].second; in->eventsUsed++;
-            }
+            if (launches && timeThisCall(in)) { int rce = nextTimerEvents(in, &a, &b); if (rce) return rce; }
             int rc = runPlan(in, *in->planner.planned, in->planner.plannedTag, a); if (rc) return rc;
             if (b) { HIP_TRY(hipEventRecord(b, live(in))); in->pendingLaunches += in->lowerLaunched ? 2 : 1; }
             const double usRun = usSince(t1);
@@ -975,14 +1045,7 @@ int runOperationsWalk(Instance* in, const int* ops, int count, int tuple, int gl
             return BEAGLE_ERROR_OUT_OF_RANGE;
     }
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (timeThisCall(in)) {
-        if (in->eventsUsed == in->events.size()) {
-            hipEvent_t a, b;
-            HIP_TRY(hipEventCreate(&a)); HIP_TRY(hipEventCreate(&b));
-            in->events.emplace_back(a, b);
-        }
-        e0 = in->events[in->eventsUsed].first; e1 = in->events[in->eventsUsed].second; in->eventsUsed++;
-    }
+    if (timeThisCall(in)) { int rce = nextTimerEvents(in, &e0, &e1); if (rce) return rce; }
     int launches = 0;
     in->hostPrepUs += usSince(t0);
     for (int begin = 0; begin < count;) {

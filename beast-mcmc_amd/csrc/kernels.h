@@ -73,7 +73,7 @@ enum { WK_MEM = 0, WK_TIPS = 1, WK_ACC = 2, WK_H0 = 3, WK_H1 = 4, WK_H2 = 5, WK_
 // the operand; for the assembly loop the engine adds WF_X | WF_TAB1 (the row loads then count as a first child from memory in the
 // stage waits) or WF_MEM2 | WF_TAB2 (the blocking second-child path).
 // WK_CHERRY (second operand only, k_walk4_fast only; round 6): the child is a node over two compact tips whose own micro-operation the
-// engine has FUSED into this one (engine_walk.cpp runPlan): src2 = the states of its first tip, scale = those of its second (the
+// engine has FUSED into this one (engine_walk.cpp ProgramResolver::microOp): src2 = the states of its first tip, scale = those of its second (the
 // micro-operation multiplies by no reciprocals: WF_INV and WK_CHERRY exclude each other), the same entry of the matrix stream's cherry
 // region = its two branch-matrix tables.  The kernel forms the child's value — column x column, what the fused micro-operation would have left
 // in ACC, bit for bit — and goes on as for WK_ACC.  A third of a binary tree's internal nodes are such cherries.
@@ -94,7 +94,7 @@ enum { WF_X = 1, WF_T1 = 2, WF_T2 = 4, WF_INV = 8, WF_STORE = 16, WF_CHERRY2 = 1
 enum : unsigned { WF_HREAD = 1u << 24, WF_HREAD1 = 1u << 25, WF_MEM2 = 1u << 26, WF_HWRITE = 1u << 27, WF_NOLOAD1 = 1u << 16, WF_NOLOAD2 = 1u << 17,
                   WF_WAIT_SHIFT = 18, WF_HREAD2 = 1u << 31, WF_TAB1 = 1u << 28, WF_TAB2 = 1u << 29 };
 // k_walk4_fast's pipeline is three micro-operations deep: the wait of stage k is "at most N vector-memory instructions outstanding",
-// N = what was issued behind the small loads of k and may stay in flight (engine_walk.cpp runPlan).  A fetch is three loads, four
+// N = what was issued behind the small loads of k and may stay in flight (walkStageWaits below).  A fetch is three loads, four
 // for a micro-operation that multiplies by reciprocal scale factors (WF_INV), six with a fused cherry (WF_CHERRY2: its table half and
 // two more tip-state pairs), so N is 6..12, + 4 behind a first child from memory, or 3..6 when the stage's own first child comes from
 // memory; a tip-state load that is skipped (WF_NOLOAD1 / 2) takes one off.  Every count from 1 to 16 has its code (tools/gen_walk4_fast.py
@@ -110,7 +110,7 @@ struct WalkOp {              // 64 bytes = one scalar-cache line; every field is
     double*        store;    // partials buffer the result is written to (WF_STORE)
     const double*  scale;    // WF_INV: the reciprocals this result is multiplied by — a scale buffer's reciprocal half or a folded vector
                              // (engine_walk.cpp); otherwise a readable all-ones array (the assembly loop loads and multiplies only under WF_INV,
-                             // which also pads a fetch behind write-mode stores: runPlan)
+                             // which also pads a fetch behind write-mode stores: walkStageWaits)
     // (the first 48 bytes are what the assembly loop loads per micro-operation: s_load_dwordx8 at 0, s_load_dwordx4 at 32)
     unsigned       flags;    // WF_* | k1 << 5 | k2 << 8 | hold << 11 | scaleMode << 13 | waitJump << 16 (walkWaitJump)
     unsigned       pad0;
@@ -144,8 +144,60 @@ inline unsigned walkFlags(int k1, int k2, int hold, int smode, bool store) {
 // of k_walk4 (k_walk4_fast: 3, + 1 with WF_INV, + 4 with WF_X)
 inline int walkFetchCount(unsigned f) { return ((f & WF_X) ? 4 : 0) + ((f & WF_T1) ? 2 : 0) + ((f & WF_T2) ? 2 : 0) + ((f & WF_INV) ? 2 : 0) + 1; }
 inline int walkStoreCount(unsigned f) { return (f & WF_STORE) ? 4 : 0; }
-// flags field "waitJump" of micro-operation k: 8 N + 12 with N = walkFetchCount(k+1) (engine_walk.cpp runPlan, kernels_walk4.hip)
+// flags field "waitJump" of micro-operation k: 8 N + 12 with N = walkFetchCount(k+1) (walkStageWaits, kernels_walk4.hip)
 inline unsigned walkWaitJump(int n) { return (unsigned)(8 * n + 12) << 16; }
+// The wait of every stage of one slice, w[first .. first + count - 1] with every other flag bit final: "at most N vector-memory
+// instructions outstanding".  Loads and stores share the counter.  Reads the flags of the no-ops behind the slice (three for the
+// assembly loop, two otherwise), writes none of them.
+// DEFAULT (strict): N = the LOADS issued behind this micro-operation's own.  Sufficient under the one ordering rule the ISA
+// guides state for this counter — vector-memory LOADS return in the order they were issued: when at most N operations
+// are outstanding and the N youngest loads are all younger than this stage's loads, an unfinished load of this stage
+// would leave N + 1 unfinished, whatever the stores (of this or any earlier stage) do.
+// BEAGLE_MI355_STRICT_WAITS=0 (strictWaits false): N also counts the stores issued in between, i.e. assumes that a younger store
+// is never counted out before an older load.  That held in > 1e9 lane-trials (tests/test_gpu_vmcnt_order.py) — but it
+// is an observation, not a documented guarantee, so it is not what ships by default.
+// A smaller N than the true number only waits longer.
+// asmLoop: k_walk4_fast runs the program (otherwise a two-deep pipeline: k_walk4, k_walkT32).  padMode (LAB builds:
+// BEAGLE_MI355_WALK_PAD_FETCH): 0 never pad a fetch, 1 behind write-mode rescaling (the default), 2 also behind stored results.
+inline void walkStageWaits(WalkOp* w, int first, int count, bool asmLoop, bool strictWaits, int padMode) {
+    if (asmLoop) {
+        // The stage waits below count LOADS.  Stores share the counter: a stage that finds stores of the two micro-operations
+        // before it still unacknowledged waits for as many of them as its N falls short of "loads + stores".  With four loads per
+        // fetch that shortfall was covered by the loads of the fetch before (older than the stores, long landed); with three it
+        // is not — a write-mode evaluation (every micro-operation stores its factors) lost 8 % to it.  So a micro-operation
+        // whose fetch is in flight across such stores fetches four again: WF_INV on top, its scale address the all-ones array
+        // (a multiplication by one where it multiplies).  Behind write-mode rescaling only: behind the (rare) stored results of a
+        // read-mode program the padding costs what it saves (config A 503 / 503 / 507 us without, with, and with both; ALWAYS
+        // 1 053 / 1 003 / 1 005: profiles/r05_experiments.txt).
+        for (int i = first + count - 1; i >= first + 2; i--) {      // (backwards: the test reads unpadded flags only of earlier ones — WF_INV is not what it looks at)
+            bool pad = false;
+            for (int b = 2; b <= 4 && i - b >= first && !pad; b++) {
+                const unsigned f = w[i - b].flags;
+                pad = (padMode >= 1 && ((f >> 13) & 3u) == (unsigned)WS_WRITE) || (padMode >= 2 && (f & WF_STORE));
+            }
+            if (pad) w[i].flags |= WF_INV;
+        }
+    }
+    for (int i = first; i < first + count; i++) {
+        // k_walk4 (two deep): N = the fetch of the next micro-operation (+ the previous one's stores)
+        // (a micro-operation that rescales in write mode also stores its factors, from one of the workgroup's waves only: behind
+        // it the count is the strict one whatever the mode)
+        const bool prevWrites = i > first && ((w[i - 1].flags >> 13) & 3u) == (unsigned)WS_WRITE;
+        const int stores1 = (strictWaits || prevWrites) ? 0 : (i > first ? walkStoreCount(w[i - 1].flags) : 0);
+        const int next2 = walkFetchCount(w[i + 1].flags) + stores1;
+        if (!asmLoop) { w[i].flags |= walkWaitJump(next2 < 12 ? next2 : 12); continue; }
+        // k_walk4_fast (three deep; a fetch is THREE small loads, four with the reciprocal scale factors: WF_INV).  Issue order around
+        // stage i: ... fetch(i) | first child of i - 1 from memory (4) | store(i - 2) | fetch(i + 1) | first child of i from memory
+        // (4) | store(i - 1) | fetch(i + 2) | WAIT.  A first child of i in memory has to have landed as well: then only what
+        // follows it counts.  (Loads only — the strict rule — whatever BEAGLE_MI355_STRICT_WAITS says: with two fetch sizes the
+        // code space has no room for the store counts of the lax rule, which bought 1 %.)
+        auto fetchLoads = [&](int j) { const unsigned f = w[j].flags;             // (matrix table; tip states, twice; reciprocals; a fused cherry's table half and tips)
+                                       return 1 + ((f & WF_NOLOAD1) ? 0 : 1) + ((f & WF_NOLOAD2) ? 0 : 1) + ((f & WF_INV) ? 1 : 0) + ((f & WF_CHERRY2) ? 3 : 0); };
+        const int x1 = i > first && (w[i - 1].flags & WF_X) ? 4 : 0;
+        const int nWait = (w[i].flags & WF_X) ? fetchLoads(i + 2) : fetchLoads(i + 1) + fetchLoads(i + 2) + x1;
+        w[i].flags |= walkWaitCode(nWait);
+    }
+}
 // A program slice and the pattern range that executes it (one per partition of a partitioned instance).  The kernel is
 // software-pipelined two micro-operations deep: progCount must be EVEN and two more readable descriptors must follow
 // (k_walk4, k_walkT32); the assembly loop k_walk4_fast is three deep and leaves behind any stage: any progCount, three more descriptors.

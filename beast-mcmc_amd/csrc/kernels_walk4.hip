@@ -22,7 +22,7 @@
 // that (its s_waitcnt insertion assumes the worst path of the kind-dependent branches and drains the queue every
 // iteration), therefore every vector-memory instruction of the loop is inline assembly and the one wait per stage is EXACT:
 // "s_waitcnt vmcnt(N)", N = the loads of micro-operation k+1 (issued after those of k; loads return in issue order — with
-// BEAGLE_MI355_STRICT_WAITS=0 also the stores of k-1, see engine_walk.cpp runPlan) — which the host knows when it
+// BEAGLE_MI355_STRICT_WAITS=0 also the stores of k-1, see kernels.h walkStageWaits) — which the host knows when it
 // builds the program and passes in the descriptor; this kernel jumps into a table of s_waitcnt instructions.  Loads a
 // micro-operation does not need are BRANCHED around, not masked: a vector-memory instruction with 8 or 16 bytes per lane
 // occupies the CU's address unit for ~16 cycles whatever its EXEC mask or coalescing (tools/vmem_rate_probe.hip).
@@ -274,7 +274,7 @@ __device__ __forceinline__ void walk4Body(const unsigned MI355_CONST* __restrict
         const int k1n = (DNXT.flags >> 5) & 7;         /* a hold-slot operand of the NEXT micro-operation is read now */  \
         /* ... and operands from a class table (kernels.h WK_TAB; scaleW = the arena): the next one's first child where a hold-slot  \
            operand would go (a program's FIRST micro-operation has no stage before it: the host puts a no-op in front of one that   \
-           reads a table first, engine_walk.cpp runPlan) */                                                                       \
+           reads a table first, engine_walk.cpp microOp) */                                                                       \
         if constexpr (TAB) tableRowsIf((unsigned)k1n, NXT.xa0, NXT.xa1, NXT.xb0, NXT.xb1, o, DNXT.src1, DNXT.scaleW, c, P);     \
         if (k1n >= WK_H0 && k1n <= WK_H2) {                                                                               \
             const v2d* h = holdBase + (size_t)(k1n - WK_H0) * C * 256;                                                    \
@@ -354,7 +354,7 @@ __device__ __forceinline__ void walk4Body(const unsigned MI355_CONST* __restrict
     }
 #undef WALK_STAGE
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    // the last no-op behind the program names the vectors that receive the slice's product of factors (engine_walk.cpp runPlan; null: none)
+    // the last no-op behind the program names the vectors that receive the slice's product of factors (engine_walk.cpp sliceEpilogue; null: none)
     const unsigned MI355_CONST* last = prog + ((size_t)progStart + progCount + 1) * 16;
     const u64 mantTo = ((u64)last[11] << 32) | last[10], expTo = ((u64)last[5] << 32) | last[4];
     if (mantTo && c == 0) {
@@ -370,7 +370,7 @@ __global__ __launch_bounds__(MAXT, MINW) void k_walk4(const unsigned MI355_CONST
     walk4Body<MAXT, false>(prog, segs, matStream, P, C, recipOff);
 }
 // ... and with class-table operands: two waves per SIMD's worth of registers (up to eight categories: a workgroup of sixteen waves
-// has four per SIMD whatever it asks for, and programs with table operands are not made for it — engine_walk.cpp runPlan)
+// has four per SIMD whatever it asks for, and programs with table operands are not made for it — engine_walk.cpp decideLaunch)
 template <int MAXT>
 __global__ __launch_bounds__(MAXT, 2) void k_walk4Tab(const unsigned MI355_CONST* __restrict__ prog, const WalkSeg MI355_CONST* __restrict__ segs,
                                                       const v2d MI355_CONST* __restrict__ matStream, int P, int C, long recipOff) {
@@ -407,7 +407,7 @@ __global__ void k_gatherMatrices(const WalkOp* __restrict__ prog, int n, int C, 
 }
 
 // The same, and in the same launch the matrix snapshots of the plan's new definitions (kernels.hip k_snapshot): the stream's
-// entries of those definitions are gathered from the snapshots' SOURCES (engine_walk.cpp runPlan points m1 / m2 there), so the
+// entries of those definitions are gathered from the snapshots' SOURCES (engine_walk.cpp microOp points m1 / m2 there), so the
 // two halves do not depend on each other and one launch does for both.
 // ... and (round 5) the uploads queued on the instance — the program itself, when it was staged by this call: `prog` and `srcDst` are
 // then read through the host ring's device mapping, the copy blocks put the program where the walk will read it; a partial update
@@ -490,7 +490,7 @@ __global__ __launch_bounds__(MAXC * 64, 4) void k_walk4_fast(const unsigned MI35
                                                              unsigned long long spinLimit, unsigned* __restrict__ selfServed, const RootFused rootArgs,
                                                              unsigned* __restrict__ tickets, int xcdGroups, int nRows, unsigned cherryOff) {
     // hold[2][C][4 KiB], table[3][MAXC][320 B], then ONE region shared by the three 1 KiB maximum buffers of write-mode rescaling and
-    // the cherry halves of the table buffers, [3][MAXC][320 B] (a program that rescales in write mode has no fused cherries: runPlan)
+    // the cherry halves of the table buffers, [3][MAXC][320 B] (a program that rescales in write mode has no fused cherries: engine_walk.cpp chooseProgram)
     extern __shared__ v2d lds[];
     // Which (slice row y, pattern group bx) this workgroup is.  Plain: the 2-D grid, x fastest.  XCD-aware (xcdGroups > 0; SMALL launches on
     // tickets only — launchWalk4Fast says when): a 1-D grid in which the rows are taken eight at a time and workgroup id = group * 8 + row

@@ -143,7 +143,7 @@ def _chain_with(wl, scheme, env, moves=10):
                                          (4, 120, 640, "caterpillar"), (16, 30, 300, "yule")])
 def test_fused_cherries_give_the_bits_of_the_unfused_program(C, T, P, kind, scheme, oracle_lib):
     """Round 6: a node over two compact tips that is not stored, pays no scale factors and is taken by the very next micro-operation
-    is evaluated INSIDE that micro-operation's stage (kernels.h WK_CHERRY; engine_walk.cpp runPlan) — its own stage, a third of a
+    is evaluated INSIDE that micro-operation's stage (kernels.h WK_CHERRY; engine_walk.cpp microOp) — its own stage, a third of a
     tree's, disappears from the device program.  Same arithmetic in the same order: every log-likelihood, site value and node partial
     of a chain must equal, bit for bit, what the unfused program (BEAGLE_MI355_NO_CHERRY_FUSION=1) and the C++ kernel give, and the
     counters must say that cherries really were fused (read mode and no scaling; never in a program that rescales in write mode)."""
