@@ -124,7 +124,7 @@ ABI_SYMBOLS = ["beagleGetVersion", "beagleGetCitation", "beagleGetResourceList",
               ["beagle" + k for k in _PROTOS] + \
               ["beagleMi355SetStream", "beagleMi355CalculateRootLogLikelihoodsDevice", "beagleMi355Synchronize",
                "beagleMi355KernelTimer", "beagleMi355DeviceBytes", "beagleMi355WalkStats", "beagleMi355GradientStats", "beagleMi355GetPartialsBatch", "beagleMi355SampleAncestralStates", "beagleMi355SampleMarkovJumps", "beagleMi355SampleMarkovJumpsUniformized",
-               "beagleMi355SimulateSequences", "beagleMi355NodeHeightDerivatives", "beagleMi355SetTipEmission", "beagleMi355TipEmissionStats",
+               "beagleMi355SimulateSequences", "beagleMi355RobustCounts", "beagleMi355SimulateUnconditionedCounts", "beagleMi355NodeHeightDerivatives", "beagleMi355SetTipEmission", "beagleMi355TipEmissionStats",
                "beagleMi355GetPartialsPinned", "beagleMi355GetSiteLogLikelihoodsPinned",
                "beagleMi355KernelTimerCalls", "beagleMi355WalkHealth", "beagleMi355RepeatStats", "beagleMi355WalkLaunchInfo", "beagleMi355RootFusedCount", "beagleMi355SitePrefetchCount", "beagleMi355KernelTimerRestart", "beagleMi355GetDimensions", "beagleMi355GetCommUniqueId", "beagleMi355CommInit", "beagleMi355CommInfo", "beagleMi355CalculateRootLogLikelihoodsAllReduce"] + \
               ["beagleBasta" + k for k in ("AllocateCoalescentBuffers", "UpdatePartials", "AccumulatePartials", "GetBuffer", "GetBufferLength", "Stats",
@@ -632,6 +632,83 @@ class Beagle:
                                            eigenIndex, categoryRatesIndex, categoryWeightsIndex, stateFrequenciesIndex, _dp(regs),
                                            _ip(flags), K, int(seed) & 0xFFFFFFFFFFFFFFFF, 1 if map else 0, ptr("states"),
                                            ptr("categories"), ptr("jumps"), ptr("pattern_totals"), ptr("row_totals")))
+        return out
+
+    def robustCounts(self, others, nodes, branchLengths, eigenVectors, inverseEigenVectors, eigenValues, infinitesimalMatrix, registers,
+                     seeds, categoryWeightsIndices=(0, 0, 0), stateFrequenciesIndices=(0, 0, 0), map=False, include_rows=None,
+                     states=False, counts=False, site_totals=True, branch_totals=True, tables=False):
+        """Codon robust counts over three 4-state instances in one call (include/beagle_mi355.h beagleMi355RobustCounts): this
+        instance is codon position 1, ``others`` the two Beagle objects of positions 2 and 3.  ``nodes`` [3][nodeCount][3]: a node
+        list per position as for sampleAncestralStates; ``branchLengths`` [nodeCount] (branch rate x time); the 64-state product
+        chain's eigen system and Q; ``registers`` [K][64][64]; ``seeds`` [3]; ``include_rows`` [nodeCount] or None (all).  -> dict of
+        what was asked for: "states" uint8 [3, nodeCount, P], "counts" [K, nodeCount, P], "site_totals" [K, P], "branch_totals"
+        [K, nodeCount], "tables" [K, nodeCount, 64, 64].  A failed draw or a gathered value that is not finite raises
+        BeagleException with code -8."""
+        rows = _i(nodes).reshape(3, -1, 3)
+        n, P = rows.shape[1], self.patternCount
+        regs = _d(registers).reshape(-1, 64, 64)
+        K = regs.shape[0]
+        tau = _d(branchLengths).reshape(-1)
+        if tau.shape[0] != n:
+            raise ValueError("branchLengths must have one entry per row")
+        U, Ui, lam, Q = _d(eigenVectors).reshape(64, 64), _d(inverseEigenVectors).reshape(64, 64), _d(eigenValues).reshape(64), \
+            _d(infinitesimalMatrix).reshape(64, 64)
+        handles = _i([self.instance] + [o.instance for o in others])
+        w, fr = _i(list(categoryWeightsIndices)), _i(list(stateFrequenciesIndices))
+        sd = np.array([int(x) & 0xFFFFFFFFFFFFFFFF for x in seeds], dtype=np.uint64)
+        if handles.size != 3 or w.size != 3 or fr.size != 3 or sd.size != 3:
+            raise ValueError("three instances, weight indices, frequency indices and seeds")
+        inc = None if include_rows is None else np.ascontiguousarray(include_rows, dtype=np.uint8)
+        if inc is not None and inc.size != n:
+            raise ValueError("include_rows must have one entry per row")
+        out = {}
+        if states:
+            out["states"] = np.empty((3, n, P), dtype=np.uint8)
+        if counts:
+            out["counts"] = np.empty((K, n, P))
+        if site_totals:
+            out["site_totals"] = np.empty((K, P))
+        if branch_totals:
+            out["branch_totals"] = np.empty((K, n))
+        if tables:
+            out["tables"] = np.empty((K, n, 64, 64))
+
+        def ptr(key):
+            return out[key].ctypes.data if key in out else None
+
+        f = self._ext("beagleMi355RobustCounts", [_IP, _IP, C.c_int, _IP, _IP, C.c_void_p, C.c_int, _DP, _DP, _DP, _DP, _DP, _DP, C.c_int,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
+        self._check("robustCounts", f(_ip(handles), _ip(rows), n, _ip(w), _ip(fr), sd.ctypes.data, 1 if map else 0, _dp(tau), _dp(U),
+                                      _dp(Ui), _dp(lam), _dp(Q), _dp(regs), K, None if inc is None else inc.ctypes.data, ptr("states"),
+                                      ptr("counts"), ptr("site_totals"), ptr("branch_totals"), ptr("tables")))
+        return out
+
+    def simulateUnconditionedCounts(self, infinitesimalMatrix, startFrequencies, lengths, site_count, registers, seed, counts=True,
+                                    totals=True):
+        """One unconditional Gillespie history per (length, site) on the device (include/beagle_mi355.h
+        beagleMi355SimulateUnconditionedCounts); the instance only names the device.  ``infinitesimalMatrix`` [S][S], S = 2..64;
+        ``startFrequencies`` [S]; ``lengths`` [L]; ``registers`` [K][S][S].  -> dict: "counts" [K, L, site_count], "totals" [K, L].
+        A history cut at 100 000 jumps or a failed draw raises BeagleException with code -8."""
+        Q = _d(infinitesimalMatrix)
+        S = int(round(np.sqrt(Q.size)))
+        Q = Q.reshape(S, S)
+        pi = _d(startFrequencies).reshape(-1)
+        regs = _d(registers).reshape(-1, S, S)
+        ln = _d(lengths).reshape(-1)
+        if pi.shape[0] != S:
+            raise ValueError("startFrequencies must have one entry per state")
+        K, L, site_count = regs.shape[0], ln.shape[0], int(site_count)
+        out = {}
+        if counts:
+            out["counts"] = np.empty((K, L, max(site_count, 0)))
+        if totals:
+            out["totals"] = np.empty((K, L))
+        f = self._ext("beagleMi355SimulateUnconditionedCounts", [C.c_int, C.c_int, _DP, _DP, _DP, C.c_int, C.c_int, _DP, C.c_int,
+                                                                 C.c_ulonglong, C.c_void_p, C.c_void_p])
+        self._check("simulateUnconditionedCounts", f(self.instance, S, _dp(Q), _dp(pi), _dp(ln), L, site_count, _dp(regs), K,
+                                                     int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                     out["counts"].ctypes.data if counts else None,
+                                                     out["totals"].ctypes.data if totals else None))
         return out
 
     def sampleMarkovJumpsUniformized(self, nodes, branchTimes, branchRates, nodeHeights, infinitesimalMatrix, categoryRatesIndex,

@@ -8,6 +8,7 @@
 //   engine_readback.cpp  partials and scale factors back to the host
 //   engine_sampling.cpp  the device samplers (ancestral draws, Markov jumps, uniformized histories)
 //   engine_simulate.cpp  sequence simulation down the tree from the branch matrices
+//   engine_robustcounts.cpp  codon robust counts over three instances' draws, unconditioned count simulation
 //   engine_nodeheight.cpp  node-height gradients and diagonal Hessians in one call
 //   engine_tipemission.cpp  tip error models: emission tables folded into the tip branch matrices
 //   engine_stats.cpp     stream, synchronisation, kernel timer, counters
@@ -278,6 +279,9 @@ struct Instance {
     // sequence simulation (beagleMi355SimulateSequences, engine_simulate.cpp): states [slots][chunk] | categories [chunk] | error
     // word | cumulative tables | their meta words, grown on demand
     DevBuf simulateDev;
+    // codon robust counts (beagleMi355RobustCounts / beagleMi355SimulateUnconditionedCounts, engine_robustcounts.cpp), on the first
+    // instance of the call: model arrays, registers, tables, per-block sums, totals, outCounts stage, grown on demand
+    DevBuf robustDev;
     // BASTA structured coalescent (beagleBastaAllocateCoalescentBuffers, engine_basta.cpp): null on every other instance
     Basta* basta = nullptr;
     // tip error models (beagleMi355SetTipEmission, engine_tipemission.cpp): null on an instance that was never given an emission table
@@ -564,6 +568,15 @@ int executeHeldPre(Instance* in);
 int edgeDifferentials(Instance* in, const int* postIdx, const int* preIdx, const int* dIdx, int wIdx, int count,
                       double* outDerivatives, double* outSum, double* outSumSquared);
 int crossProducts(Instance* in, const int* postIdx, const int* preIdx, int rateIdx, int wIdx, const double* lengths, int count, double* outSum);
+
+// ---- engine_sampling.cpp
+// Where a device-side draw left its results (in->ancestralDev): states [rows][P] | categories [P] | error word.
+struct AncestralDraw { uint8_t* states; int* cats; unsigned* error; };
+// the draw of beagleMi355SampleAncestralStates left on the device (one launch on the instance's stream), and its copy-out
+int drawAncestral(Instance* in, const int* nodes, int nodeCount, int wIdx, int fIdx, unsigned long long seed, int flags, int globalP,
+                  int pOffset, AncestralDraw* d);
+int copyAncestral(Instance* in, const AncestralDraw& d, int nodeCount, int globalP, int pOffset, unsigned char* outStates,
+                  int* outCategories, unsigned* error);
 
 // ---- engine_create.cpp
 size_t matrixSlotLayout(Instance* in);

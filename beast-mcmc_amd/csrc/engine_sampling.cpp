@@ -10,12 +10,10 @@ using namespace mi355::eng;
 // Grow-only device scratch of an instance (ancestral draws, Markov jumps): exactly `need` bytes when it grows, counted in deviceBytes.
 static int growScratch(Instance* in, DevBuf& b, size_t need) { return growDevice(in, b, need, need, Grow::SyncIfHeld); }
 
-// Where a device-side draw left its results (in->ancestralDev): states [rows][P] | categories [P] | error word.
-struct AncestralDraw { uint8_t* states; int* cats; unsigned* error; };
-
-// The draw itself, left on the device: validation, materialising virtual buffers, ONE launch (kernels_ancestral.hip).
-static int drawAncestral(Instance* in, const int* nodes, int nodeCount, int wIdx, int fIdx, unsigned long long seed, int flags,
-                         int globalP, int pOffset, AncestralDraw* d) {
+// The draw itself, left on the device (AncestralDraw, engine_internal.h): validation, materialising virtual buffers, ONE launch
+// (kernels_ancestral.hip).
+int mi355::eng::drawAncestral(Instance* in, const int* nodes, int nodeCount, int wIdx, int fIdx, unsigned long long seed, int flags,
+                              int globalP, int pOffset, AncestralDraw* d) {
     if (in->partitionCount > 1) return BEAGLE_ERROR_NO_IMPLEMENTATION;
     if (badIndex(wIdx, in->eigenCount) || badIndex(fIdx, in->eigenCount)) return BEAGLE_ERROR_OUT_OF_RANGE;
     std::vector<int> need;
@@ -56,8 +54,8 @@ static int drawAncestral(Instance* in, const int* nodes, int nodeCount, int wIdx
 }
 
 // Copy-out of a draw: the states (queued; NULL: none), then the categories and the error word in one synchronising copy.
-static int copyAncestral(Instance* in, const AncestralDraw& d, int nodeCount, int globalP, int pOffset, unsigned char* outStates,
-                         int* outCategories, unsigned* error) {
+int mi355::eng::copyAncestral(Instance* in, const AncestralDraw& d, int nodeCount, int globalP, int pOffset, unsigned char* outStates,
+                              int* outCategories, unsigned* error) {
     if (outStates) {
         if (globalP == in->P)
             HIP_TRY(hipMemcpyAsync(outStates, d.states, (size_t)nodeCount * in->P, hipMemcpyDeviceToHost, live(in)));

@@ -626,6 +626,35 @@ void launchJumpSites(hipStream_t stream, const JumpRow* dRows, int nRows, int r0
                      unsigned* fpError);
 // out[k][r] = sum of blockPartials[.][k][r] over `blocks` workgroups in ascending order
 void launchJumpRowTotals(hipStream_t stream, const double* blockPartials, int blocks, int K, int nRows, double* out);
+// ---- codon robust counts (kernels_robustcounts.hip; beagleMi355RobustCounts, beagleMi355SimulateUnconditionedCounts) --------
+constexpr int ROBUST_STATES = 64;              // the 4 x 4 x 4 product chain
+constexpr int ROBUST_MAX_JUMPS = 100000;       // changes after which an unconditioned history is given up (header)
+// One row of the node list: tau = branch rate x time, the parent row (-1 at the root), whether the site totals include it
+struct RobustRow {
+    double tau;
+    int    parent;
+    int    include;
+};
+// rr, tmp, M: [K][64][64] scratch; M[k] = U^-1 ((Q o R_k, R's diagonal as 0) U) from the SUPPLIED Q and `eigen` (U | U^-1 | lambda)
+void launchRobustRegisters(hipStream_t stream, const double* eigen, const double* Q, const double* registers, int K, double* rr,
+                           double* tmp, double* M);
+// cond[k][r][64][64] = (U ((A o M_k) U^-1)) / |U (diag(e^(lambda tau)) U^-1)| for rows 1 .. nRows-1 (row 0 is left alone)
+void launchRobustTables(hipStream_t stream, const RobustRow* dRows, int nRows, const double* eigen, const double* M, int K,
+                        double* cond);
+// rows [r0, r1) of every site, the codon of (row, site) = s0 * 16 + s1 * 4 + s2: counts [K][r1-r0][P] (may be nullptr), running
+// site totals [K][P] over the included rows (read unless r0 == 0), blockPartials [jumpSiteBlocks(P)][K][nRows] (every row);
+// *fpError |= 2 when a gathered value is not finite
+void launchRobustSites(hipStream_t stream, const RobustRow* dRows, int nRows, int r0, int r1, const uint8_t* s0, const uint8_t* s1,
+                       const uint8_t* s2, const double* cond, int K, int P, double* counts, double* siteTotals,
+                       double* blockPartials, unsigned* fpError);
+// out[k][r] = sum of blockPartials[.][k][r] over `blocks` workgroups in ascending order; rows below firstRow: 0
+void launchRobustTotals(hipStream_t stream, const double* blockPartials, int blocks, int K, int nRows, int firstRow, double* out);
+int  unconditionedBlocks(int siteCount);      // workgroups per length row of launchUnconditioned
+// one unconditional Gillespie history per (length row in [l0, l1), site): values [K][l1-l0][siteCount] (may be nullptr),
+// blockPartials [unconditionedBlocks][K][lengthCount]; *fpError |= 1 for a draw that failed, |= 4 for a history cut at ROBUST_MAX_JUMPS
+void launchUnconditioned(hipStream_t stream, const double* Q, const double* freqs, const double* lengths, int lengthCount, int l0,
+                         int l1, int siteCount, const double* registers, int K, int S, unsigned long long seed, double* values,
+                         double* blockPartials, unsigned* fpError);
 // ---- uniformized Markov jumps (kernels_uniformized.hip; beagleMi355SampleMarkovJumpsUniformized) --------------------------
 // One row of the node list: the branch's time and rate, the parent's and the node's heights, its matrices [C][S][S] (nullptr at
 // the root) and its parent row

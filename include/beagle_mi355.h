@@ -504,6 +504,81 @@ int beagleMi355SampleMarkovJumpsUniformized(int instance, const int* nodes, int 
                                             double* outJumps, double* outPatternTotals, double* outRowTotals, int* outEventCounts,
                                             long long eventCapacity, double* outEventHeights, unsigned char* outEventStates,
                                             long long* outEventTotal, long long* outFallbacks);
+/* Codon robust counts ("renaissance counting", the per-site and per-branch dN/dS of CodonPartitionedRobustCounting): ONE call that
+ * draws the ancestral states of the three codon-position instances, joins them into codon states and gathers, for every register k,
+ * row r >= 1 and site p, the Minin-Suchard conditional mean count on row r's branch of the 64-state product chain of the three
+ * nucleotide models — what CodonPartitionedRobustCounting.computeAllExpectedCounts computes from three getStatesForNode read-backs
+ * and one MarkovJumpsCore table per branch and labelling (CodonPartitionedRobustCounting.java:216-307, ProductChainSubstitutionModel).
+ *   instances [3]: codon positions 1, 2, 3 — three DIFFERENT ordinary 4-state instances on one device with the same pattern count P
+ *          and one pattern partition each.  Patterns are sites: the reference requires uncompressed patterns (:138-146).
+ *   nodes [3][nodeCount][3]: nodes + q * nodeCount * 3 is position q's node list exactly as beagleMi355SampleAncestralStates takes it
+ *          ({bufferIndex, matrixIndex, parentRow}, row 0 the root); the parentRow columns of the three lists must agree.
+ *   categoryWeightsIndices [3], stateFrequenciesIndices [3], seeds [3], flags (BEAGLE_MI355_ANCESTRAL_MAP): per position, as for that
+ *          call.  Position q's states are byte for byte what beagleMi355SampleAncestralStates(instances[q], nodes[q], nodeCount,
+ *          categoryWeightsIndices[q], stateFrequenciesIndices[q], seeds[q], flags, ..) returns (same keys, same numbers); one shared
+ *          seed would give three identical alignments identical draws.  Rate categories of the instances are drawn and otherwise unused.
+ *   branchLengths [nodeCount]: tau_r = branch rate x time of row r's branch in the product chain's time; row 0 is ignored.
+ *   eigenVectors U, inverseEigenVectors U^-1 [64][64] row-major, eigenValues lambda [64] (real), infinitesimalMatrix Q [64][64]: the
+ *          product chain (ProductChainSubstitutionModel.java:301-362); state = s0 * 16 + s1 * 4 + s2, first position most significant.
+ *          Q is the SUPPLIED matrix, not one formed from the eigen system.  There are no rate categories (:81-87).
+ *   registers [registerCount][64][64], registerCount 1..8: R_k; the diagonal is never read (taken as 0).
+ *   includeRows [nodeCount] or NULL (all): rows with includeRows[r] != 0 enter outSiteTotals (includeExternalBranches /
+ *          includeInternalBranches); nothing else depends on it.
+ * Tables: rateReg_k = Q o R_k (MarkovJumpsSubstitutionModel.java:84-131), M_k = U^-1 (rateReg_k U); per row r >= 1 with tau = tau_r:
+ *   A[a][b] = |la - lb| < 1e-7 ? e^(la tau) tau : (e^(la tau) - e^(lb tau)) / (la - lb);  J = U ((A o M_k) U^-1)
+ *          (MarkovJumpsCore.java:84-103, 198-221);
+ *   P = |U (diag(e^(lambda tau)) U^-1)| entry by entry, the products e^(la tau) * U^-1[a][j] first (BaseSubstitutionModel.java:206-240):
+ *          the product chain's own matrix, not an instance's;  Cond_k,r = J / P entry by entry.  Row 0: 0.
+ * Every product is rounded on its own (no fused multiply-add) and every sum runs over its inner index in ascending order from 0.0.
+ * Outputs (any may be NULL, not all four; all deterministic — two identical calls give identical bits, and asking for fewer
+ * outputs does not change the bits of the others):
+ *   outStates [3][nodeCount][P] bytes or NULL: the three draws;
+ *   outCounts [K][nodeCount][P] = Cond_k,r[codon of parent(r) at p][codon of r at p], row 0: 0;
+ *   outSiteTotals [K][P] = sum over the included rows 1 .. nodeCount-1 in row order from 0.0;
+ *   outBranchTotals [K][nodeCount] = sum over the sites: per workgroup of 256 consecutive sites a wave's 64 by an xor-shuffle tree
+ *          (distances 32 .. 1), the four waves in wave order, then the workgroups in ascending order; row 0: 0;
+ *   outTables [K][nodeCount][64][64] = Cond.
+ * A zero-length branch leaves 0/0 off the diagonal of its table, as in the reference; the gather only reads its diagonal there, which
+ * is 0 — that is not an error.  BEAGLE_ERROR_FLOATING_POINT when a draw failed or a GATHERED value is not finite; everything else is
+ * still written.  BEAGLE_ERROR_OUT_OF_RANGE for a NULL input, nodeCount < 1, registerCount outside 1..8, an unknown flag bit, all
+ * four double outputs NULL, parent rows that disagree, the same instance named twice, and every error of
+ * beagleMi355SampleAncestralStates; BEAGLE_ERROR_NO_IMPLEMENTATION for a state count other than 4, differing pattern counts,
+ * differing devices, the sharded handle (resource G+1) and an instance with more than one pattern partition.
+ * The instances are left as they were found: plans, partials, scale buffers and the likelihood path stay bit for bit.
+ * Out of scope: useUniformization = "true" for robust counting (sampled codon histories), sharded and partitioned instances, product
+ * chains other than 4 x 4 x 4.  An extension: no BEAST class calls it today. */
+int beagleMi355RobustCounts(const int* instances, const int* nodes, int nodeCount, const int* categoryWeightsIndices,
+                            const int* stateFrequenciesIndices, const unsigned long long* seeds, int flags, const double* branchLengths,
+                            const double* eigenVectors, const double* inverseEigenVectors, const double* eigenValues,
+                            const double* infinitesimalMatrix, const double* registers, int registerCount,
+                            const unsigned char* includeRows, unsigned char* outStates, double* outCounts, double* outSiteTotals,
+                            double* outBranchTotals, double* outTables);
+/* Unconditioned counts: one unconditional Gillespie history per (length row l, site s) of a chain with stateCount (2..64) states —
+ * StateHistory.simulateUnconditionalOnEndingState (StateHistory.java:324-354) as CodonPartitionedRobustCounting
+ * .fillInUnconditionalTraitValues uses it (CodonPartitionedRobustCounting.java:619-647).  `instance` only names the device and the
+ * stream: nothing of the instance is read.  lengthCount = 1 with the expected tree length gives the u_ column per site; lengthCount =
+ * nodeCount with each branch's length is doUnconditionedPerBranch.  forceUnconditionalAverageRate needs nothing here: the caller
+ * passes the averaged chain's Q and frequencies.
+ *   infinitesimalMatrix Q [S][S] row-major, startFrequencies [S], lengths [lengthCount] (each finite and >= 0), registers [K][S][S].
+ * The history: cur = a draw from startFrequencies; t = 0; while t < length: rate = -Q[cur][cur]; a state with rate <= 0 ends the
+ * history; t = t + (-1.0 * log(1 - u)) / rate (MathUtils.nextExponential); if still t < length, next = a draw from Q's row cur with
+ * its own entry set to 0, register k adds R_k[cur][next], cur = next.  The value of register k is that sum over the jumps in time
+ * order from 0.0 — for the reference's 0/1 registers it equals getTotalRegisteredCounts.  Both draws are randomChoicePDF as
+ * beagleMi355SampleAncestralStates restates it (U = u * total, the fall-through rule included).  Length 0: all values 0.
+ * Random numbers (stateless): the history of (l, s) has the stream z = SplitMix64's output for key l * siteCount + s from the state
+ * seed ^ 0xBB67AE8584CAA73B, as a 64-bit integer; u_q = SplitMix64's (q + 1)-th output from state z as (x >> 11) * 2^-53; u_0 draws
+ * the start state, u_(2m+1) waiting time m, u_(2m+2) the state after it.
+ *   outCounts [K][lengthCount][siteCount] or NULL;  outTotals [K][lengthCount] or NULL = the sum over the sites in the fixed order of
+ *   beagleMi355RobustCounts' outBranchTotals.  Not both NULL.  The bits depend on the seed alone.
+ * A history is cut after 100 000 jumps (a caller's Q x length that would never finish): its value is what it had, everything else is
+ * written, and the call returns BEAGLE_ERROR_FLOATING_POINT — as it does when a draw's total weight is not finite and > 0.
+ * BEAGLE_ERROR_OUT_OF_RANGE for a NULL input, stateCount outside 2..64, registerCount outside 1..8, a Q or length that is not finite,
+ * a negative length, lengthCount or siteCount below 1, or both outputs NULL; BEAGLE_ERROR_NO_IMPLEMENTATION on the sharded handle.
+ * An extension: no BEAST class calls it today. */
+int beagleMi355SimulateUnconditionedCounts(int instance, int stateCount, const double* infinitesimalMatrix,
+                                           const double* startFrequencies, const double* lengths, int lengthCount, int siteCount,
+                                           const double* registers, int registerCount, unsigned long long seed, double* outCounts,
+                                           double* outTotals);
 /* Tip error models (SequenceErrorModel, HypermutantErrorModel, ambiguity codes): a tip whose partials are a LOOKUP.
  *   codes [patternCount]: the observed code of every pattern; a code outside 0..codeCount-1 is missing (all ones, a factor of one).
  *   emission [codeCount][stateCount]: emission[k * S + i] = the tip's partial for true state i at a pattern whose code is k.
