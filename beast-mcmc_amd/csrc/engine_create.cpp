@@ -303,6 +303,12 @@ int beagleCreateInstance(int tipCount, int partialsBufferCount, int compactBuffe
         in->planner.launchMachines = (double)(4 * cus) / (double)std::max(1, (patternCount + 127) / 128);
         if (labEnv("BEAGLE_MI355_SCHED_SIM") && atoi(labEnv("BEAGLE_MI355_SCHED_SIM")) == 0) in->planner.launchMachines = 0.0;
     }
+    // compressed evaluations are cut by their remaining work (engine_internal.h repeatSlicing)
+    in->repeatSlicing = in->repeatsOn && in->fastWalk && in->fuseWaves && in->useTickets && !switchOn("BEAGLE_MI355_NO_REPEAT_SLICING");
+    if (in->repeatSlicing) {
+        Instance* const self = in;
+        in->planner.repeatChunkRule = [self](long weight, int& chunk, int& top) { walkRepeatChunkOps(self, weight, chunk, top); };
+    }
     // result words live in coherent, device-mapped host memory: the final reduction kernel writes the sum straight into it
     // and the host only waits for the stream (no device-to-host copy behind the last kernel)
     ok = ok && hipHostMalloc((void**)&in->hResult, 4096, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess;

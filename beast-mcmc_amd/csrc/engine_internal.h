@@ -159,6 +159,11 @@ struct Instance {
     // uncompressed program.  One partition, buffers of 2 MiB and more (BEAGLE_MI355_REPEATS_ANY_SIZE=1: any size), BEAGLE_MI355_NO_REPEATS=1: off,
     // BEAGLE_MI355_REPEAT_MAX_FRAC=<1/n>: the class limit as a fraction of the pattern count.
     bool repeatsOn = false; int repeatMaxClasses = 0;
+    // repeatSlicing: lists that will be compressed are cut by what compression leaves of them (planner.h repeatWeights; engine_walk.cpp
+    // walkRepeatChunkOps) — repeatsOn, the assembly loop, all slices in one launch on tickets; BEAGLE_MI355_NO_REPEAT_SLICING=1: the cut
+    // of the uncompressed list.  repeatSlicingOff: a program cut this way had fewer than half of its definitions' micro-operations
+    // compressed (an alignment whose clades exceed the class limit): later lists are cut as uncompressed ones, until new tip states.
+    bool repeatSlicing = false, repeatSlicingOff = false;
     mi355::RepeatIndex repeatIndex;
     std::vector<std::vector<uint8_t>> hostTips;          // per tip: the state codes as uploaded (what the index is built from)
     long tipDataEpoch = 0, repeatEpoch = -1, repeatCompactEpoch = -1;     // setTipStates calls; what the index and the tables were made under
@@ -550,6 +555,7 @@ int materializeVirtual(Instance* in, int X);
 int materializeScaleUsers(Instance* in, int scaleIdx);
 int materializeTipUsers(Instance* in, int tip);
 int walkChunkOps(const Instance* in, int opCount);
+void walkRepeatChunkOps(const Instance* in, long weight, int& chunk, int& top);
 int runOperationsWalk(Instance* in, const int* ops, int count, int tuple, int globalCum);
 // ---- engine_levels.cpp
 int materializeCherries(Instance* in, const std::vector<int>& xs);

@@ -113,7 +113,7 @@ static void dropRepeatTables(Instance* in, bool index) {
     in->repeatRows.reset();
     if (index) { in->repeatIndex.clear(); in->repeatQueue.clear(); }
 }
-void repeatsForget(Instance* in) { if (in->repeatsOn && (in->repeatIndex.size() || !in->repeatTables.empty())) dropRepeatTables(in, true); }
+void repeatsForget(Instance* in) { in->repeatSlicingOff = false; if (in->repeatsOn && (in->repeatIndex.size() || !in->repeatTables.empty())) dropRepeatTables(in, true); }
 
 // the class table of `clade` (its index is built): rows of the arena, the row vector and the representatives' tip states on the device.
 // nullptr: no room (*full), or out of memory
@@ -330,6 +330,14 @@ int ProgramResolver::chooseProgram() {
         (in->fastWalk || in->C <= 8)) {                // (k_walk4's table variant: up to eight categories, kernels_walk4.hip)
         int rc = prepareRepeats(in, plan, fold ? &foldMap : nullptr, &r); if (rc) return rc;
         if (r.compressed) use = &r.repeats.plan;
+        // a list cut for compression (planner.h repeatWeights) of which less than half was compressed — not for want of an index that is
+        // still being built —: the lists behind it are cut as they were before (engine_internal.h repeatSlicingOff)
+        if (in->planner.lastWeighed > 0 && in->planner.plannedTag == planTag && !r.repeatsMissing) {
+            long inRuns = 0, taken = 0;
+            for (const mi355::PlanRun& run : plan.runs) inRuns += run.count;
+            if (r.compressed) for (const mi355::PlanSeg& sg : r.repeats.lower) taken += sg.progCount;
+            if (2 * taken < inRuns) in->repeatSlicingOff = true;
+        }
     }
     nUp = use->segs.size(); nLow = lowerSlices(r);
     // write-mode programs: every slice leaves the product of its factors behind (Instance::lastSums); the vectors are named by the last no-op
@@ -885,12 +893,12 @@ int flushWalk(Instance* in, const mi355::RootFused* root) {
     pw.valid = false;                                  // (before anything that could come back here through live())
     if (!in->pendingCopies.empty()) { int rc = flushUploads(in); if (rc) return rc; }
 #ifdef BEAGLE_MI355_LAB
-    // BEAGLE_MI355_WALK_TRACE=<n>: the n-th held-or-not one-launch walk of the instance with more than 20 slices is timed workgroup by workgroup
+    // BEAGLE_MI355_WALK_TRACE=<n>: the n-th held-or-not one-launch walk of the instance with more than one slice is timed workgroup by workgroup
     static const int traceAt = labEnv("BEAGLE_MI355_WALK_TRACE") ? atoi(labEnv("BEAGLE_MI355_WALK_TRACE")) : 0;
     static int traceSeen = 0;
     unsigned long long* dTrace = nullptr;
     const int groupsX = (pw.range + 127) / 128;
-    if (traceAt > 0 && pw.nSegs > 20 && ++traceSeen == traceAt) {
+    if (traceAt > 0 && pw.nSegs > 1 && ++traceSeen == traceAt) {
         HIP_TRY(hipMalloc((void**)&dTrace, (size_t)pw.nSegs * groupsX * 3 * sizeof(unsigned long long)));
         HIP_TRY(hipMemsetAsync(dTrace, 0, (size_t)pw.nSegs * groupsX * 3 * sizeof(unsigned long long), in->stream));
         mi355::setWalkTrace(dTrace);
@@ -960,6 +968,9 @@ int materializeTipUsers(Instance* in, int tip) {
 // 0.83 -> 0.33 ms per evaluation); with many it keeps more workgroups than the chip holds in the queue, so that a wave
 // waiting for its stores is replaced by another one instead of idling (1e5 patterns: 1.73 -> 1.37 ms).  Returns the target
 // number of micro-operations per subtree, 0 = one walk.  BEAGLE_MI355_CHUNK overrides (0 = never).
+// This is the cut of a list by its LENGTH: of every program that runs as many micro-operations as the list has operations — write-mode
+// evaluations, partial updates, materialisations, the gradient chain, partitioned instances, 16..64 states.  A list that will be
+// compressed (class tables) leaves a tenth of them in the walk and is cut by walkRepeatChunkOps below.
 int walkChunkOps(const Instance* in, int opCount) {
     static const int forced = labEnv("BEAGLE_MI355_CHUNK") ? atoi(labEnv("BEAGLE_MI355_CHUNK")) : -1;
     if (forced >= 0) return forced;
@@ -975,7 +986,8 @@ int walkChunkOps(const Instance* in, int opCount) {
     // slices can be longer — fewer stored slice roots, less polling — while the planner keeps the slices ABOVE the first wave
     // short (planner.h chunkTopOps: near the root few subtrees are left side by side).  12 500 patterns, kernel us per
     // evaluation at 40 / 56 / 72 / 96 / 128 micro-operations per first-wave slice: 130 / 122 / 113 / 114 / 114 with 16 above
-    // (135 / 122 / 141 / 127 / 122 with the same length above); 25 000 and more: flat (profiles/r04_experiments.txt).
+    // (135 / 122 / 141 / 127 / 122 with the same length above); 25 000 and more: flat (profiles/r04_experiments.txt) — a reading of
+    // UNCOMPRESSED programs, whose first wave was eleven twelfths of the work: it does not hold for compressed ones (walkRepeatChunkOps).
     // On tickets (round 6) the grid is the first wave alone: 12 500 patterns, kernel us at 40 / 56 / 70 / 96 / 128 / 150 per first-wave
     // slice with 8 above: 136 / 126 / 125 / 112 / 105 / 106 (16 above: 136 / 131 / 122 / 117 / 109 / 111; flags at their best: 108).
     // 6 250 patterns: 76 us at a divisor of 500, 80 at 765, 99 at 1 400; 25 000 and more: flat.  A partitioned instance's slices span one
@@ -990,6 +1002,24 @@ int walkChunkOps(const Instance* in, int opCount) {
     if (in->walkT && in->S > 20) return (int)std::min<long>(150, std::max<long>(8, (long)opCount * groups / 2600));
     const long div = in->walkT ? 1900 : !fused ? 2560 : !in->useTickets ? 1400 : ticketDiv > 0 ? ticketDiv : in->partitionCount > 1 ? 1400 : 765;
     return (int)std::min<long>(150, std::max<long>(24, (long)opCount * groups / div));
+}
+
+// The slice sizes of a list that will be compressed (engine_internal.h repeatSlicing), from its weight: the micro-operations compression
+// leaves and one per table row gathered (planner.h repeatWeights).  chunk / top arrive as walkChunkOps' and the instance's chunkTopOps.
+// BEAGLE_MI355_CHUNK / _CHUNK_TOP override here too.
+void walkRepeatChunkOps(const Instance* in, long weight, int& chunk, int& top) {
+    static const int forced = labEnv("BEAGLE_MI355_CHUNK") ? atoi(labEnv("BEAGLE_MI355_CHUNK")) : -1;
+    if (forced >= 0) { chunk = forced; return; }      // (the top size: taken from the environment at creation)
+    if (chunk <= 0) return;                           // (a list too short to cut at all: one walk, as before)
+    // Measured on the 1000-taxon coalescent tree, whose compressed program is 78 micro-operations and 76 gathers (evaluations/s at 24 / 32 /
+    // 48 / 64 / 80 / 100 per first-wave slice, one walk, and the cut of the uncompressed list; profiles/compressed_slicing.txt):
+    //   1e5 patterns     2 306 / 2 416 / 2 622 / 2 712 / 2 708 / 2 719, one walk 2 582, uncompressed cut 2 437 .. 2 452
+    //   25 000 patterns  5 009 / 5 409 / 6 075 / 6 482 /   -   / 6 305,                 uncompressed cut 5 456 .. 5 490
+    // Slices of 9 to 20 micro-operations that remain — eight of them where the uncompressed cut made eighteen of 1 to 12 — and one wave
+    // above them: the size above the first wave (8 or 32) has nothing left to act on and stays.  With fewer groups than compression is on
+    // for by default (BEAGLE_MI355_REPEATS_ANY_SIZE=1 only) the divisor of walkChunkOps sizes the slices, from the weight.
+    const long groups = (in->P + 127) / 128;
+    chunk = groups >= 128 ? 64 : (int)std::min<long>(64, std::max<long>(24, weight * groups / 765));
 }
 
 // 4 states: the operation list becomes one (or, for a list with hazards, a few) pattern-walk launches.
@@ -1014,6 +1044,8 @@ int runOperationsWalk(Instance* in, const int* ops, int count, int tuple, int gl
     // per-operation work below: it was range-checked and planned then, nothing has to be materialised or accumulated for it,
     // the planner re-establishes its definitions with one comparison per operation and the program is resident on the
     // device (config E, 6 436 operations: 116 -> 35 us of host time per call; profiles/r03_experiments.txt).
+    // (a list that will be compressed is cut by what is left of it: planner.h repeatWeights acts on closed lists without rescaling only)
+    in->planner.repeatWeights = in->repeatSlicing && !in->repeatSlicingOff && parts == 1 && allowVirtual && in->planner.stepLimit == 0;
     {
         bool simple = false;
         if (in->planner.replayCached(ops, count, tuple, parts, allowVirtual, walkChunkOps(in, count), &simple)) {

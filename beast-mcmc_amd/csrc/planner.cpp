@@ -477,17 +477,20 @@ int WalkPlanner::plan(const int* ops, int count, int tuple, int parts, bool allo
 
     // ---- closed list?  then the plan may be in the cache (planner.h)
     CacheEntry* fill = nullptr;
+    bool anyRescale = false;
+    lastWeighed = 0;
     if (cacheEnabled && count >= 16) {
         if (CacheEntry* hit = findCached(ops, count, tuple, parts, allowVirtual, chunkOps)) {
             stamp_++;
             replay(*hit, ops);
             cacheHits++;
-            return 0;
+            return 0;                                  // (replay() has set lastWeighed)
         }
         bool closed = true, simple = true;
         for (int k = 0; k < count && closed; k++) {
             const int* op = ops + (size_t)k * tuple;
             const int part = tuple > 7 ? op[7] : 0;
+            if (op[1] != OP_NONE) anyRescale = true;
             if (!compactTip[op[3]] && wStamp_[(size_t)op[3] * parts + part] != stamp_) closed = false;
             if (!compactTip[op[5]] && wStamp_[(size_t)op[5] * parts + part] != stamp_) closed = false;
             wStamp_[(size_t)op[0] * parts + part] = stamp_;
@@ -498,7 +501,7 @@ int WalkPlanner::plan(const int* ops, int count, int tuple, int parts, bool allo
         if (closed) {
             fill = &cache_[cacheNext_];
             cacheNext_ = (cacheNext_ + 1) % CACHE_WAYS;
-            fill->valid = false; fill->cleanAtEpoch = -1; fill->tag = ++cacheTagNext_; fill->count = count; fill->tuple = tuple; fill->parts = parts; fill->chunkOps = chunkOps;
+            fill->valid = false; fill->cleanAtEpoch = -1; fill->tag = ++cacheTagNext_; fill->count = count; fill->tuple = tuple; fill->parts = parts; fill->chunkOps = chunkOps; fill->repeatWeights = repeatWeights;
             fill->allowVirtual = allowVirtual; fill->stepLimit = allowVirtual ? stepLimit : 0; fill->memStepCap = allowVirtual ? memStepCap : 0; fill->tipEpoch = compactEpoch; fill->simple = simple;
             fill->ops.assign(ops, ops + (size_t)count * tuple);
         }
@@ -626,13 +629,17 @@ int WalkPlanner::plan(const int* ops, int count, int tuple, int parts, bool allo
         for (int k = 0; k < count; k++) if (!seen[info_[k].part]) { seen[info_[k].part] = 1; partsSeen.push_back(info_[k].part); }
     }
     lastWaves = 0;
+    // (planner.h repeatWeights: a closed list — one that is cached — of one partition in which nothing rescales)
+    const bool repeatW = repeatWeights && fill && parts == 1 && !anyRescale && allowVirtual;
+    int cutOps = chunkOps, cutTop = chunkTopOps;
+    bool ruled = !repeatW;
     std::vector<int> weight, chunkRoots, stack;
     for (int part : partsSeen) {
         int wave = 0;
         for (;;) {
             bool chunked = false;
-            const int chunk = (wave == 0 || chunkTopOps <= 0) ? chunkOps : std::min(chunkOps, chunkTopOps);
-            if (chunk > 0) {
+            int chunk = (wave == 0 || cutTop <= 0) ? cutOps : std::min(cutOps, cutTop);
+            if (chunk > 0 || !ruled) {
                 // micro-operations below every op that is still to be emitted (children precede parents in the list)
                 weight.assign(count, 0);
                 long total = 0;
@@ -646,6 +653,7 @@ int WalkPlanner::plan(const int* ops, int count, int tuple, int parts, bool allo
                         if (tip) continue;
                         if (prod >= 0 && !info_[prod].virtDest) { if (!info_[prod].emitted) w += weight[prod]; }
                         else if (virt_[key(buf, o.part)].on) {
+                            if (repeatW && plainDefinition(virt_[key(buf, o.part)])) { w += 1; continue; }      // (a table row gathered by this op)
                             w += virt_[key(buf, o.part)].nSteps;
                             const int a = anyMem ? operandOp(key(buf, o.part)) : -1;      // (a memory definition: its operand's program comes with it)
                             if (a >= 0 && !info_[a].emitted) w += weight[a];
@@ -654,7 +662,13 @@ int WalkPlanner::plan(const int* ops, int count, int tuple, int parts, bool allo
                     weight[k] = w;
                     if (!consumed[k]) total += w;
                 }
-                if (total > chunk + chunk / 2) {
+                if (!ruled) {                              // the whole plan's weight is known: the slice sizes that go with it
+                    ruled = true;
+                    lastWeighed = total;
+                    if (repeatChunkRule) repeatChunkRule(total, cutOps, cutTop);
+                    chunk = cutOps;
+                }
+                if (chunk > 0 && total > chunk + chunk / 2) {
                     chunkRoots.clear(); stack.clear();
                     for (int k = count - 1; k >= 0; k--) {
                         const OpInfo& o = info_[k];
@@ -709,7 +723,7 @@ int WalkPlanner::plan(const int* ops, int count, int tuple, int parts, bool allo
     }
     // launches run wave by wave: order the slices that way (stable: partitions keep their order inside a wave)
     std::stable_sort(out.segs.begin(), out.segs.end(), [](const PlanSeg& a, const PlanSeg& b) { return a.wave < b.wave; });
-    linkSlices(out);
+    linkSlices(out, repeatW);
     if (fill) {
         // (the entry TAKES the program — `out` is left with whatever the entry held — and `planned` names the entry's copy, as on
         // a hit; the definitions of unstored destinations are copied, steps in use only, over whatever the way held before)
@@ -722,7 +736,7 @@ int WalkPlanner::plan(const int* ops, int count, int tuple, int parts, bool allo
         for (int k = 0; k < count; k++)
             if (info_[k].virtDest) { const int kk = key(info_[k].dest, info_[k].part); virt_[kk].cacheTag = fill->tag; tagOf_[kk] = fill->tag; tagEpoch_++; fill->defs[k] = virt_[kk]; fill->defOn[k] = 1; }
         plannedTag = fill->tag;
-        fill->stored = lastStored; fill->memReads = lastMemReads; fill->holds = lastHolds; fill->waves = lastWaves;
+        fill->stored = lastStored; fill->memReads = lastMemReads; fill->holds = lastHolds; fill->waves = lastWaves; fill->weighed = lastWeighed;
         fill->valid = true;
     }
     return 0;
@@ -730,7 +744,13 @@ int WalkPlanner::plan(const int* ops, int count, int tuple, int parts, bool allo
 
 // Which slices read what other slices of the same plan store (planner.h PlanSeg): a slice reads a stored result only as a
 // PK_MEM operand, and only of a slice of an EARLIER wave of the same partition (tests/native/plan_check.cpp checks both).
-void WalkPlanner::linkSlices(Plan& out) {
+bool WalkPlanner::plainDefinition(const VirtDef& v) const {
+    if (v.memKey >= 0) return false;
+    for (int s = 0; s < v.nSteps; s++) if (v.steps[s].memA || v.steps[s].memB) return false;
+    return v.nSteps > 0;
+}
+
+void WalkPlanner::linkSlices(Plan& out, bool repeatDurations) {
     const size_t nKeys = (size_t)partialsCount_ * keyParts_;
     if (storedBy_.size() < nKeys) { storedBy_.assign(nKeys, -1); storedStamp_.assign(nKeys, 0); }
     linkStamp_++;
@@ -788,6 +808,21 @@ void WalkPlanner::linkSlices(Plan& out) {
     for (int s = 0; s < n; s++) out.launchOrder[s] = s;
     std::stable_sort(out.launchOrder.begin(), out.launchOrder.end(), [&](int a, int b) { return out.segs[a].tail > out.segs[b].tail; });
     if (launchMachines <= 0.0 || n < 3) return;
+    // how long a slice runs: its micro-operations — under planner.h repeatWeights with every run that reads tips only counted as the one
+    // gather it becomes
+    std::vector<int> duration(n);
+    for (int s = 0; s < n; s++) duration[s] = out.segs[s].progCount;
+    if (repeatDurations)
+        for (const PlanRun& run : out.runs) {
+            bool plain = run.count > 1;
+            for (int i = run.start; plain && i < run.start + run.count; i++) {
+                const MicroOp& m = out.prog[(size_t)i];
+                plain = m.storeBuf < 0 && m.k1 != PK_MEM && m.k2 != PK_MEM;
+            }
+            if (!plain) continue;
+            for (int s = 0; s < n; s++)
+                if (run.start >= out.segs[s].progStart && run.start < out.segs[s].progStart + out.segs[s].progCount) { duration[s] -= run.count - 1; break; }
+        }
     // List scheduling on `machines` identical machines, a slice taking its length: whenever a machine is free, the ready slice
     // (all of its dependencies finished) with the longest tail starts; the order of the starts is the launch order.
     const int machines = std::max(1, (int)(launchMachines + 0.5));
@@ -828,7 +863,7 @@ void WalkPlanner::linkSlices(Plan& out) {
         const int s = ready.front();
         ready.erase(ready.begin());
         order.push_back(s);
-        freeAt[m] = now + out.segs[s].progCount;
+        freeAt[m] = now + duration[s];
         running.emplace_back(freeAt[m], s);
     }
     if ((int)order.size() == n) out.launchOrder = order;
@@ -836,7 +871,7 @@ void WalkPlanner::linkSlices(Plan& out) {
 
 WalkPlanner::CacheEntry* WalkPlanner::findCached(const int* ops, int count, int tuple, int parts, bool allowVirtual, int chunkOps) {
     for (CacheEntry& e : cache_)
-        if (e.valid && e.count == count && e.tuple == tuple && e.parts == parts && e.chunkOps == chunkOps && e.allowVirtual == allowVirtual &&
+        if (e.valid && e.count == count && e.tuple == tuple && e.parts == parts && e.chunkOps == chunkOps && e.allowVirtual == allowVirtual && e.repeatWeights == repeatWeights &&
             e.stepLimit == (allowVirtual ? stepLimit : 0) && e.memStepCap == (allowVirtual ? memStepCap : 0) &&
             e.tipEpoch == compactEpoch && memcmp(e.ops.data(), ops, (size_t)count * tuple * sizeof(int)) == 0)
             return &e;
@@ -918,7 +953,7 @@ void WalkPlanner::replay(const CacheEntry& e, const int* ops) {
     }
     e.cleanAtEpoch = tagEpoch_;
     planned = &e.plan; plannedTag = e.tag;
-    lastStored = e.stored; lastMemReads = e.memReads; lastHolds = e.holds; lastWaves = e.waves;
+    lastStored = e.stored; lastMemReads = e.memReads; lastHolds = e.holds; lastWaves = e.waves; lastWeighed = e.weighed;
 }
 
 void WalkPlanner::planMaterialize(const std::vector<int>& keys, Plan& out) {
@@ -960,7 +995,11 @@ bool foldScaleFactors(const Plan& plan, int maxMembers, FoldMap& out) {
             acc.swap(cur);
         }
     }
+    // (a list is paid in the order of its buffer indices, not in the order its members were met: where a slice ends does not change
+    // the product's rounding — a memory definition evaluated behind its operand's program meets them in another order than one that reads
+    // the operand from memory)
     for (size_t i = 0; i < n; i++) {
+        std::sort(pays[i].begin(), pays[i].end());
         out.payStart[i] = (int)out.members.size();
         out.members.insert(out.members.end(), pays[i].begin(), pays[i].end());
     }

@@ -16,6 +16,7 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <functional>
 #include <unordered_map>
 #include <vector>
 
@@ -75,7 +76,7 @@ struct Plan {
 // factors it owes (its own and those its unstored operands passed on) to its consumer, and only a result that IS stored, that
 // ends its slice, or that has gathered `maxMembers` of them pays: one multiplication by the product of the members'
 // reciprocals.  foldScaleFactors says, per micro-operation of plan.prog, which scale buffers it pays for:
-// members[payStart[i] .. payStart[i + 1]) (none: it multiplies by nothing; one: that buffer's own reciprocals; several: a fold the
+// members[payStart[i] .. payStart[i + 1]), in ascending order (none: it multiplies by nothing; one: that buffer's own reciprocals; several: a fold the
 // engine builds, engine_walk.cpp).  false: the program rescales in write mode somewhere (nothing is folded then).
 struct FoldMap { std::vector<int> payStart, members; };
 bool foldScaleFactors(const Plan& plan, int maxMembers, FoldMap& out);
@@ -298,6 +299,16 @@ public:
     // One partition, no step limit, a walk with hold slots; a definition that nothing in its list consumes is stored after all (a root).
     // Part of a cached plan's identity.  0 (the default): off.
     int memStepCap = 0;
+    // repeatWeights: the engine will take this list's plain definitions — every leaf a compact tip — from class tables (RepeatIndex,
+    // emitRepeatPlan), so pass 2 weighs such a definition as what it leaves in the walk, ONE gather on its consumer, not as its steps, and
+    // linkSlices' schedule simulation takes a slice's duration the same way (PlanSeg::tail stays in program micro-operations).  Acts on
+    // closed lists of one partition without a rescaling operation — what the engine compresses; any other list is planned as without it.
+    // Part of a cached plan's identity.  lastWeighed: such a plan's weight in all, 0: the last plan() was not weighed this way.
+    bool repeatWeights = false;
+    long lastWeighed = 0;
+    // ... and the slice sizes of such a plan, chosen from its weight once pass 2 knows it (the engine's rule, engine_walk.cpp
+    // walkRepeatChunkOps): chunk and top arrive as plan()'s chunkOps and chunkTopOps and leave as what the plan is cut with.  None: as they are.
+    std::function<void(long weight, int& chunk, int& top)> repeatChunkRule;
     long cacheHits = 0;                  // plans served from the cache below
     long replayInPlace = 0;              // definitions a replay took over from another entry with their leaves unchanged (user lists edited in place)
     bool cacheEnabled = true;
@@ -327,7 +338,8 @@ private:
     bool onPath(const VirtDef& v, int idx) const;                    // is step memStep in the subtree of step idx
     void realInfo(int k);                // OpInfo::need / size of the (real) op k
     int virtNeed(int buf) const { return virt_[buf].nSteps ? virt_[buf].steps[virt_[buf].nSteps - 1].need : 0; }
-    void linkSlices(Plan& out);          // PlanSeg::dep*, tail and Plan::launchOrder
+    void linkSlices(Plan& out, bool repeatDurations = false);      // PlanSeg::dep*, tail and Plan::launchOrder
+    bool plainDefinition(const VirtDef& v) const;                  // every leaf a compact tip: what a class table can stand for (repeatWeights)
     std::vector<int> storedBy_, storedStamp_;          // per (buffer, partition): the slice of the current plan that stores it
     int linkStamp_ = 0;
 
@@ -359,7 +371,7 @@ private:
         bool valid = false;
         long tag = 0;
         int count = 0, tuple = 0, parts = 0, chunkOps = 0, stepLimit = 0, memStepCap = 0;
-        bool allowVirtual = false;
+        bool allowVirtual = false, repeatWeights = false;
         std::vector<int> ops;
         long tipEpoch = -1;                            // compactEpoch the plan was made under
         bool simple = false;                           // see replayCached
@@ -367,6 +379,7 @@ private:
         std::vector<VirtDef> defs;                     // per op: the definition its destination ends up with (on = false: real)
         std::vector<char> defOn;                       // defs[k].on
         int stored = 0, memReads = 0, holds = 0, waves = 0;
+        long weighed = 0;
         mutable long cleanAtEpoch = -1;                // tagEpoch_ right after the last replay of this entry (-1: never replayed since it was filled)
     };
     // (8: a chain under DYNAMIC rescaling cycles through 2 buffer-flip states x 2 scale-buffer sets of its read-mode list and the
