@@ -9,6 +9,7 @@ Layout (only what the hot path needs — SURVEY.md §8):
   ancestral.py        ancestral-state draws on the device (AncestralStateBeagleTreeLikelihood's caller side)
   markovjumps.py      Markov-jump counts and rewards on the device (MarkovJumpsBeagleTreeLikelihood's caller side)
   simulate.py         sequence simulation down the tree on the device (BeagleSequenceSimulator / Partition's caller side)
+  completehistory.py  complete substitution histories down the tree on the device (CompleteHistorySimulator's caller side)
   robustcounting.py   codon robust counts over three position instances (CodonPartitionedRobustCounting's caller side)
   nodeheight.py       node-height gradients and diagonal Hessians in one call (DiscreteTraitNodeHeightDelegate's caller side)
   tipmodels.py        tip error models as emission tables folded into the tip branch matrices (SequenceErrorModel's caller side)
@@ -19,5 +20,5 @@ Layout (only what the hot path needs — SURVEY.md §8):
 
 The directory name contains a hyphen, so import it through the root-level shim: ``import beast_mcmc_amd``.
 """
-from . import ancestral, basta, beagle, markovjumps, mds, multipartition, nodeheight, robustcounting, simulate, tipmodels, treelikelihood     # noqa: F401
+from . import ancestral, basta, beagle, completehistory, markovjumps, mds, multipartition, nodeheight, robustcounting, simulate, tipmodels, treelikelihood     # noqa: F401
 from .inputs import patterns, siterates, substmodel, synth, trees   # noqa: F401

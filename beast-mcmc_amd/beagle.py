@@ -124,7 +124,7 @@ ABI_SYMBOLS = ["beagleGetVersion", "beagleGetCitation", "beagleGetResourceList",
               ["beagle" + k for k in _PROTOS] + \
               ["beagleMi355SetStream", "beagleMi355CalculateRootLogLikelihoodsDevice", "beagleMi355Synchronize",
                "beagleMi355KernelTimer", "beagleMi355DeviceBytes", "beagleMi355WalkStats", "beagleMi355GradientStats", "beagleMi355GetPartialsBatch", "beagleMi355SampleAncestralStates", "beagleMi355SampleMarkovJumps", "beagleMi355SampleMarkovJumpsUniformized",
-               "beagleMi355SimulateSequences", "beagleMi355RobustCounts", "beagleMi355SimulateUnconditionedCounts", "beagleMi355NodeHeightDerivatives", "beagleMi355SetTipEmission", "beagleMi355TipEmissionStats",
+               "beagleMi355SimulateSequences", "beagleMi355SimulateCompleteHistories", "beagleMi355RobustCounts", "beagleMi355SimulateUnconditionedCounts", "beagleMi355NodeHeightDerivatives", "beagleMi355SetTipEmission", "beagleMi355TipEmissionStats",
                "beagleMi355GetPartialsPinned", "beagleMi355GetSiteLogLikelihoodsPinned",
                "beagleMi355KernelTimerCalls", "beagleMi355WalkHealth", "beagleMi355RepeatStats", "beagleMi355WalkLaunchInfo", "beagleMi355RootFusedCount", "beagleMi355SitePrefetchCount", "beagleMi355KernelTimerRestart", "beagleMi355GetDimensions", "beagleMi355GetCommUniqueId", "beagleMi355CommInit", "beagleMi355CommInfo", "beagleMi355CalculateRootLogLikelihoodsAllReduce"] + \
               ["beagleBasta" + k for k in ("AllocateCoalescentBuffers", "UpdatePartials", "AccumulatePartials", "GetBuffer", "GetBufferLength", "Stats",
@@ -559,6 +559,83 @@ class Beagle:
                                            int(seed) & 0xFFFFFFFFFFFFFFFF, 0, None if root is None else root.ctypes.data, _ip(given),
                                            states.ctypes.data, _ip(cats)))
         return states, cats
+
+    def simulateCompleteHistories(self, rows, site_count, branchLengths, infinitesimalMatrices, registers, registerFlags, seed,
+                                  nodeHeights=None, categoryRatesIndex=0, categoryWeightsIndex=0, stateFrequenciesIndex=0,
+                                  root_states=None, rate_categories=None, states=True, values=True, row_totals=True, site_totals=True,
+                                  history=False, event_capacity=None, retry=True):
+        """One substitution history per (branch, site), simulated down the tree on the device (include/beagle_mi355.h
+        beagleMi355SimulateCompleteHistories).  ``rows``: [nodeCount][3] rows {outRow, qIndex, parentRow}, the root first;
+        ``branchLengths`` [nodeCount] (branch rate x time); ``infinitesimalMatrices`` [qCount][S][S]; ``registers`` [K][S][S];
+        ``registerFlags`` [K] (JUMPS_REWARDS) or None; ``nodeHeights`` [nodeCount] (needed with ``history``).  -> dict of what was
+        asked for: "states" uint8 [1 + max outRow, site_count] and "categories" int32 [site_count], "values" [K, nodeCount,
+        site_count], "row_totals" [K, nodeCount], "site_totals" [K, site_count]; with ``history``: "event_counts" int32 [nodeCount,
+        site_count], "event_heights" [E], "event_states" uint8 [E, 2], "event_total".  The event buffer starts at ``event_capacity``
+        (default: a guess) and the call is made once more with the exact size when it was too small (``retry``; without it a full
+        buffer returns the other outputs and "rc" = -5 instead of raising).  A history cut at 100 000 jumps or a failed draw raises
+        BeagleException with code -8."""
+        rows = _i(rows).reshape(-1, 3)
+        n, S, site_count = rows.shape[0], self.stateCount, int(site_count)
+        Q = _d(infinitesimalMatrices).reshape(-1, S, S)
+        regs = _d(registers).reshape(-1, S, S)
+        K = regs.shape[0]
+        flags = None if registerFlags is None else _i(registerFlags).reshape(-1)
+        lengths = _d(branchLengths).reshape(-1)
+        heights = None if nodeHeights is None else _d(nodeHeights).reshape(-1)
+        root = None if root_states is None else np.ascontiguousarray(root_states, dtype=np.uint8)
+        given = None if rate_categories is None else _i(rate_categories)
+        if lengths.shape[0] != n or (heights is not None and heights.shape[0] != n) or (flags is not None and flags.shape[0] != K):
+            raise ValueError("branchLengths, nodeHeights and registerFlags must have one entry per row / register")
+        if (root is not None and root.size != site_count) or (given is not None and given.size != site_count):
+            raise ValueError("root_states and rate_categories must have one entry per site")
+        n_out = int(rows[:, 0].max()) + 1 if n else 0
+        if site_count < 1 or n < 1 or (states and n_out < 1):
+            raise BeagleException("simulateCompleteHistories", -5)
+        capacity = int(event_capacity) if event_capacity is not None else n * site_count // 4 + 1024
+        f = self._ext("beagleMi355SimulateCompleteHistories",
+                      [C.c_int, _IP, C.c_int, C.c_int, _DP, C.c_void_p, _DP, C.c_int, C.c_int, C.c_int, C.c_int, _DP, C.c_void_p,
+                       C.c_int, C.c_ulonglong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                       C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p])
+        for attempt in range(2):
+            out = {}
+            if states:
+                out["states"] = np.zeros((n_out, site_count), dtype=np.uint8)
+                out["categories"] = np.zeros(site_count, dtype=np.int32)
+            if values:
+                out["values"] = np.empty((K, n, site_count))
+            if row_totals:
+                out["row_totals"] = np.empty((K, n))
+            if site_totals:
+                out["site_totals"] = np.empty((K, site_count))
+            if history:
+                out["event_counts"] = np.empty((n, site_count), dtype=np.int32)
+                out["event_heights"] = np.empty(capacity)
+                out["event_states"] = np.empty((capacity, 2), dtype=np.uint8)
+            total = C.c_longlong(0)
+
+            def ptr(key):
+                return out[key].ctypes.data if key in out else None
+
+            rc = f(self.instance, _ip(rows), n, site_count, _dp(lengths), None if heights is None else heights.ctypes.data, _dp(Q),
+                   Q.shape[0], categoryRatesIndex, categoryWeightsIndex, stateFrequenciesIndex, _dp(regs),
+                   None if flags is None else flags.ctypes.data, K, int(seed) & 0xFFFFFFFFFFFFFFFF, 0,
+                   None if root is None else root.ctypes.data, None if given is None else given.ctypes.data, ptr("states"),
+                   ptr("categories"), ptr("values"), ptr("row_totals"), ptr("site_totals"), ptr("event_counts"),
+                   capacity if history else 0, ptr("event_heights"), ptr("event_states"), C.byref(total) if history else None)
+            if rc == -5 and history and total.value > capacity:
+                if retry and attempt == 0:
+                    capacity = int(total.value)
+                    continue
+                if not retry:
+                    out["rc"] = rc
+                    rc = 0
+            break
+        self._check("simulateCompleteHistories", rc)
+        if history:
+            out["event_total"] = int(total.value)
+            out["event_heights"] = out["event_heights"][:total.value]
+            out["event_states"] = out["event_states"][:total.value]
+        return out
 
     def setTipEmission(self, tipIndex, codes, emission):
         """A tip whose partials are the lookup ``emission[codes[p]]`` (include/beagle_mi355.h beagleMi355SetTipEmission): ``emission``

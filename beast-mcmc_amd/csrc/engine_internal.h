@@ -9,6 +9,7 @@
 //   engine_sampling.cpp  the device samplers (ancestral draws, Markov jumps, uniformized histories)
 //   engine_simulate.cpp  sequence simulation down the tree from the branch matrices
 //   engine_robustcounts.cpp  codon robust counts over three instances' draws, unconditioned count simulation
+//   engine_history.cpp   complete substitution histories simulated down the tree from the generators
 //   engine_nodeheight.cpp  node-height gradients and diagonal Hessians in one call
 //   engine_tipemission.cpp  tip error models: emission tables folded into the tip branch matrices
 //   engine_stats.cpp     stream, synchronisation, kernel timer, counters
@@ -287,6 +288,9 @@ struct Instance {
     // codon robust counts (beagleMi355RobustCounts / beagleMi355SimulateUnconditionedCounts, engine_robustcounts.cpp), on the first
     // instance of the call: model arrays, registers, tables, per-block sums, totals, outCounts stage, grown on demand
     DevBuf robustDev;
+    // complete histories (beagleMi355SimulateCompleteHistories, engine_history.cpp): a chunk's states, categories, values, sums and
+    // event counts, the generators' jump tables, the registers, the rows, grown on demand (the event list itself: eventDev)
+    DevBuf historyDev;
     // BASTA structured coalescent (beagleBastaAllocateCoalescentBuffers, engine_basta.cpp): null on every other instance
     Basta* basta = nullptr;
     // tip error models (beagleMi355SetTipEmission, engine_tipemission.cpp): null on an instance that was never given an emission table

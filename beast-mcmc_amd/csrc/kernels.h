@@ -697,6 +697,58 @@ void launchUniformSites(hipStream_t stream, const UniformSiteArgs& a, int r0, in
 void launchUniformPatternTotals(hipStream_t stream, const double* stage, int stageRows, int r0, int r1, int K, int P, double* patternTotals);
 // counts [nRows][P] -> offsets within each pattern (in place); patternOffsets [P + 1]: exclusive scan of the pattern sums, then the total
 void launchEventOffsets(hipStream_t stream, int* counts, int nRows, int P, long long* patternOffsets);
+// ---- complete substitution histories (kernels_history.hip; beagleMi355SimulateCompleteHistories) ---------------------------
+constexpr int HISTORY_MAX_STATES = 64;
+constexpr int HISTORY_MAX_JUMPS = 100000;      // changes after which a history is given up (header)
+constexpr int HISTORY_WAVE = 64;               // sites of one workgroup (one wave); a chunk of sites is a multiple of 4 of them
+constexpr int HISTORY_TOTAL_BLOCK = 256;       // sites of one block of the row totals' fixed order
+// One row of the node list: the branch's operational time, the parent's and the node's heights, its generator, the scratch rows
+// its states and its parent's states are kept in
+struct HistoryRow {
+    double length;
+    double hParent;
+    double hChild;
+    int    q;
+    int    slot;
+    int    parentSlot;
+    int    parentIsPrev;
+};
+// Jump tables: one line per (generator, state), then the frequencies' line and the category weights' line.  A line holds the
+// running maximum of the cumulative sums in index order (the state's own entry taken as 0), `total` its last cumulative sum,
+// `last` the largest index of a positive term (-1: the total is not finite and > 0), `rate` = -Q[i][i] (generator lines only).
+inline size_t historyLines(int qCount, int S) { return (size_t)qCount * S + 2; }
+inline size_t historyTableDoubles(int qCount, int S, int C) { return (size_t)qCount * S * S + S + C; }
+void launchHistoryTables(hipStream_t stream, const double* Q, int qCount, const double* catWeights, const double* freqs, int S, int C,
+                         double* table, double* total, double* rate, int* last);
+struct HistoryArgs {
+    const HistoryRow* rows;
+    const double* table;                 // the jump tables and their per-line words
+    const double* total;
+    const double* rate;
+    const int* last;
+    const double* catRates;              // [C]
+    const double* registers;             // [K][S][S]
+    uint8_t* states;                     // [slots][stride]: scratch rows of the chunk
+    int* cats;                           // [stride]
+    double* stage;                       // values [K][nRows][stride] (nullptr: not wanted)
+    double* siteTotals;                  // [K][stride]
+    double* wavePartials;                // [stride / 64][K][nRows] (nullptr: no row totals)
+    int* eventCounts;                    // [nRows][nSites] (nullptr: not counted)
+    const long long* siteOffsets;        // writing: [nSites + 1] first event of each site within the chunk
+    double* eventHeights;                // writing: the instance's event list
+    uint8_t* eventStates;
+    unsigned* fpError;                   // |= 1 for a draw that failed, |= 4 for a history cut at HISTORY_MAX_JUMPS
+    unsigned long long seed, siteCount, siteOffset;
+    long long eventBase;                 // writing: the chunk's first event in the instance's list
+    size_t stride;
+    int nRows, K, S, C, nSites, qCount, rewardMask, haveRoot, haveCats;
+};
+// sites siteOffset .. siteOffset + nSites - 1 of a call over siteCount sites, ONE launch: every history, its end state, every
+// register's value, the site totals, the per-wave row sums and the event counts (write = false), or the histories again with their
+// events written (write = true)
+void launchHistoryWalk(hipStream_t stream, const HistoryArgs& a, bool write);
+// rowTotals [K][nRows] (+)= the chunk's blocks of four waves in ascending order (first: from 0.0); row 0: 0
+void launchHistoryRowTotals(hipStream_t stream, const double* wavePartials, int waves, int K, int nRows, bool first, double* rowTotals);
 // out[0] = sum of n block sums in a fixed order
 void launchRootFinal(hipStream_t stream, const double* blockSums, int n, double* out, unsigned long long* flag = nullptr,
                      unsigned long long seq = 0);

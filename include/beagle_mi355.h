@@ -579,6 +579,74 @@ int beagleMi355SimulateUnconditionedCounts(int instance, int stateCount, const d
                                            const double* startFrequencies, const double* lengths, int lengthCount, int siteCount,
                                            const double* registers, int registerCount, unsigned long long seed, double* outCounts,
                                            double* outTotals);
+/* Complete histories: ONE call that simulates a substitution history on every branch, down the tree — what
+ * dr.app.beagle.tools.CompleteHistorySimulator.simulate computes with one StateHistory.simulateUnconditionalOnEndingState per (branch,
+ * site) in Java (CompleteHistorySimulator.java:384-496, StateHistory.java:324-354): the history on a branch starts from the parent's
+ * realised state, its ending state is the child's state, and every registered jump process keeps its realised value per (branch, site).
+ * It reads the instance's state count, the category rates, category weights and state frequencies at the given indices and nothing
+ * else: no matrices, no partials, no patterns — siteCount is free, updatePartials and updateTransitionMatrices need never have been
+ * called, a partitioned instance is served like any other, and the instance is left exactly as found.
+ *   nodes: nodeCount triples {outRow, qIndex, parentRow} in pre-order — row 0 is the root {outRow, ignored, -1}, every other row names
+ *          the generator it evolves under (0 .. qCount-1) and a parentRow smaller than its own index.  outRow as in
+ *          beagleMi355SimulateSequences: the row of outStates that receives the node's states, -1 for "not wanted", every value >= 0 at
+ *          most once.
+ *   branchLengths [nodeCount]: the operational time of row r's branch = branch rate x height difference (:483-486); finite, >= 0; row 0
+ *          is ignored.  nodeHeights [nodeCount] or NULL: only read for outEventHeights.
+ *   infinitesimalMatrices [qCount][S][S] row-major, qCount >= 1, every entry finite: one generator for the whole tree is qCount = 1, the
+ *          reference's branchSpecificLambda one generator per distinct branch value.
+ *   registers [registerCount][S][S], registerCount 1..8; registerFlags[k] (NULL: all 0) = BEAGLE_MI355_JUMPS_REWARDS for a reward
+ *          register, no other bit (the reference parses scaleByTime and ignores it, :286).
+ *   flags: none is defined; it must be 0.  inRootStates, inRateCategories (NULL: drawn): as in beagleMi355SimulateSequences.
+ * The rule.  Category c of site s: inRateCategories[s], else (categoryCount > 1) a draw from the category weights, else 0.  Root state:
+ * inRootStates[s], else a draw from the state frequencies.  Row r >= 1: tau = rate_c * branchLengths[r], cur = the parent's state at the
+ * site, t = 0.0; while t < tau: rate = -Q[cur][cur]; a state with rate <= 0 ends the history; t = t + (-1.0 * log(1 - u)) / rate
+ * (MathUtils.nextExponential); if still t < tau, next = a draw from Q's row cur with its own entry taken as 0 — a jump cur -> next at t —
+ * and cur = next.  The child's state is cur.  tau = 0 (a zero-length branch, a zero-rate category): no jump, the parent's state.
+ * A draw over w_0 .. w_{n-1} is MathUtils.randomChoicePDF in its CUMULATIVE form: cum_i = cum_{i-1} + w_i from cum_{-1} = 0.0 in index
+ * order (one IEEE addition each), total = cum_{n-1}, U = u * total, the result is the first i with U < cum_i, and where there is none
+ * THE LARGEST INDEX WITH w_i > 0.  (The subtract-and-test walk of beagleMi355SampleAncestralStates agrees with it except where the two
+ * roundings differ in the last bit; this call and its host restatement both use the cumulative form.)  A total that is not finite
+ * and > 0: the root state or category is 0, a history ends where it is, everything else is written and the call returns
+ * BEAGLE_ERROR_FLOATING_POINT.  A history is cut after 100 000 jumps: the state at the cut is the child's state, its values are what
+ * they had reached (a reward gets no final term), everything else is written and the call returns BEAGLE_ERROR_FLOATING_POINT.
+ * Register k of (row r, site s), summed over the history in time order from 0.0: a count register adds R_k[from][to] per jump — with
+ * integer entries (the reference's 0/1 registers) getTotalRegisteredCounts exactly; a reward register adds R_k[cur][cur] * (t - t_prev)
+ * per jump and R_k[cur][cur] * (tau - t_last) at the end (beagleMi355SampleMarkovJumpsUniformized's definition; getTotalReward up to
+ * the order of the additions).  Every product is rounded on its own (no fused multiply-add).
+ * Random numbers (stateless): the history of (row r, site s of the whole call) has the stream z = SplitMix64's output for key
+ * r * siteCount + s from the state seed ^ 0x3C6EF372FE94F82B, as a 64-bit integer; u_q = SplitMix64's (q + 1)-th output from state z as
+ * (x >> 11) * 2^-53.  Row 0: u_0 draws the root state, u_1 the category.  Row r >= 1: u_(2m) is waiting time m, u_(2m+1) the state
+ * after it.  The bytes depend on the seed alone: not on the launch shape, not on the chunks the sites are processed in
+ * (BEAGLE_MI355_HIST_CHUNK_SITES=<n> overrides their size, rounded up to a multiple of 256), not on the number of GPUs.
+ * Outputs (each may be NULL, not all of them; asking for fewer does not change the bits of the others):
+ *   outStates [1 + max outRow][siteCount] bytes, outRateCategories [siteCount]: as in beagleMi355SimulateSequences;
+ *   outValues [K][nodeCount][siteCount], row 0 all zero;
+ *   outRowTotals [K][nodeCount] = the sum over the sites (the reference's sumAcrossSites) in the fixed order of
+ *          beagleMi355RobustCounts' outBranchTotals: per block of 256 consecutive sites a wave's 64 by an xor-shuffle tree (distances
+ *          32 .. 1), the four waves in wave order, then the blocks in ascending order; row 0: 0;
+ *   outSiteTotals [K][siteCount] = the sum over rows 1 .. nodeCount-1 in row order from 0.0.
+ * Events, when any of outEventCounts, outEventHeights, outEventStates, outEventTotal is not NULL: outEventCounts [nodeCount][siteCount]
+ * = the jumps of every history; the events are ordered by site, then row, then time; outEventStates[2e], [2e+1] = event e's from and to
+ * states; outEventHeights[e] = h_parent + (t / tau) * (h_child - h_parent) (needs nodeHeights); *outEventTotal is always written.  More
+ * events than eventCapacity: no event is written, everything else is, and the call returns BEAGLE_ERROR_OUT_OF_RANGE — a second call
+ * with a buffer of *outEventTotal events is exact, because the streams are keyed.
+ * The sharded handle (resource G+1) splits the SITES into contiguous ranges; every shard gets everything else.  States, categories,
+ * values, site totals, event counts and events come back byte for byte as from one instance (a shard's events follow the earlier
+ * shards'); the row totals are the shards' sums — each in the order above, its blocks counted from its first site — added in shard order.
+ * BEAGLE_ERROR_OUT_OF_RANGE for a NULL nodes, branchLengths, infinitesimalMatrices or registers, nodeCount, siteCount or qCount below 1,
+ * a bad rates, weights or frequencies index, a qIndex outside 0..qCount-1, a parent row that is not earlier than the row itself, an
+ * outRow below -1 or used twice, a Q or length that is not finite, a negative length, an unknown register-flag bit, registerCount
+ * outside 1..8, non-zero flags, an input state >= stateCount or category outside 0..categoryCount-1, outEventHeights without
+ * nodeHeights, a negative eventCapacity, all outputs NULL; BEAGLE_ERROR_NO_IMPLEMENTATION for a state count outside 2..64 and on a
+ * BASTA instance.  An extension: no BEAST class calls it today. */
+int beagleMi355SimulateCompleteHistories(int instance, const int* nodes, int nodeCount, int siteCount, const double* branchLengths,
+                                         const double* nodeHeights, const double* infinitesimalMatrices, int qCount,
+                                         int categoryRatesIndex, int categoryWeightsIndex, int stateFrequenciesIndex,
+                                         const double* registers, const int* registerFlags, int registerCount, unsigned long long seed,
+                                         int flags, const unsigned char* inRootStates, const int* inRateCategories,
+                                         unsigned char* outStates, int* outRateCategories, double* outValues, double* outRowTotals,
+                                         double* outSiteTotals, int* outEventCounts, long long eventCapacity, double* outEventHeights,
+                                         unsigned char* outEventStates, long long* outEventTotal);
 /* Tip error models (SequenceErrorModel, HypermutantErrorModel, ambiguity codes): a tip whose partials are a LOOKUP.
  *   codes [patternCount]: the observed code of every pattern; a code outside 0..codeCount-1 is missing (all ones, a factor of one).
  *   emission [codeCount][stateCount]: emission[k * S + i] = the tip's partial for true state i at a pattern whose code is k.
