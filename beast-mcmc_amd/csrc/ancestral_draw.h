@@ -1,5 +1,6 @@
 // ancestral_draw.h — the stateless random numbers and the weighted draw shared by the device samplers (kernels_ancestral.hip,
-// kernels_uniformized.hip).  Device code only; include it from a .hip file that turns FMA contraction off.
+// kernels_simulate.hip, kernels_uniformized.hip, kernels_robustcounts.hip, kernels_history.hip).  Device code only; include it from
+// a .hip file that turns FMA contraction off.
 #pragma once
 
 #include <float.h>
@@ -7,13 +8,17 @@
 namespace mi355 {
 namespace draw {
 
-// SplitMix64: the (ctr + 1)-th output from state `seed`, as a double in [0, 1) with 53 random bits
-__device__ __forceinline__ double ancestralUniform(unsigned long long seed, unsigned long long ctr) {
-    unsigned long long z = seed + (ctr + 1ull) * 0x9E3779B97F4A7C15ull;
+// SplitMix64: the (key + 1)-th output from `state`, as a 64-bit integer (a draw, or the state of a stream of its own)
+__device__ __forceinline__ unsigned long long mix64(unsigned long long state, unsigned long long key) {
+    unsigned long long z = state + (key + 1ull) * 0x9E3779B97F4A7C15ull;
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return (double)(z >> 11) * 0x1.0p-53;
+    return z ^ (z >> 31);
+}
+
+// ... as a double in [0, 1) with 53 random bits
+__device__ __forceinline__ double ancestralUniform(unsigned long long seed, unsigned long long ctr) {
+    return (double)(mix64(seed, ctr) >> 11) * 0x1.0p-53;
 }
 
 // drawChoice over n weights w(i): MAP = first index of the strict maximum; otherwise randomChoicePDF with U = u * total, and the

@@ -29,6 +29,7 @@
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -43,6 +44,7 @@
 #include "../../include/beagle_mi355.h"
 #include "kernels.h"
 #include "planner.h"
+#include "scratch_layout.h"
 #include "sharded.h"
 
 namespace mi355 {
@@ -275,22 +277,14 @@ struct Instance {
     // read-back (getPartials): API-layout export buffers on the device and a pinned bounce buffer on the host
     DevBufUncounted exportDev[2]; double* exportHost[2] = {nullptr, nullptr}; size_t exportBytes = 0;   // two chunks in flight
     hipEvent_t exportEvent[2] = {nullptr, nullptr};
-    // ancestral-state draws (beagleMi355SampleAncestralStates): states [rows][P] | categories [P] | error word, grown on demand
-    DevBuf ancestralDev;
-    // Markov jumps (beagleMi355SampleMarkovJumps): registers, tables, per-block row sums, totals, outJumps stage, grown on demand
-    DevBuf jumpDev;
-    // uniformized Markov jumps (beagleMi355SampleMarkovJumpsUniformized): R^n table, rows, registers, sums, counts, grown on demand;
-    // the event list of the last call that asked for one
-    DevBuf uniformDev, eventDev;
-    // sequence simulation (beagleMi355SimulateSequences, engine_simulate.cpp): states [slots][chunk] | categories [chunk] | error
-    // word | cumulative tables | their meta words, grown on demand
-    DevBuf simulateDev;
-    // codon robust counts (beagleMi355RobustCounts / beagleMi355SimulateUnconditionedCounts, engine_robustcounts.cpp), on the first
-    // instance of the call: model arrays, registers, tables, per-block sums, totals, outCounts stage, grown on demand
-    DevBuf robustDev;
-    // complete histories (beagleMi355SimulateCompleteHistories, engine_history.cpp): a chunk's states, categories, values, sums and
-    // event counts, the generators' jump tables, the registers, the rows, grown on demand (the event list itself: eventDev)
-    DevBuf historyDev;
+    // The samplers' scratch, grown on demand (growScratch); what is inside each is the layout of scratch_layout.h named behind it:
+    DevBuf ancestralDev;                                 // ancestral-state draws (engine_sampling.cpp drawAncestral): ancestralLayout
+    DevBuf jumpDev;                                      // Markov jumps (sampleJumps): jumpLayout
+    DevBuf uniformDev;                                   // uniformized Markov jumps (uniformRun): uniformLayout
+    DevBuf eventDev;                                     // the event list of the last call that asked for one (growEvents): eventLayout
+    DevBuf simulateDev;                                  // sequence simulation (engine_simulate.cpp): simulateLayout
+    DevBuf robustDev;                                    // robust counts, on the call's first instance (engine_robustcounts.cpp): robustLayout / unconditionedLayout
+    DevBuf historyDev;                                   // complete histories (engine_history.cpp): historyLayout
     // BASTA structured coalescent (beagleBastaAllocateCoalescentBuffers, engine_basta.cpp): null on every other instance
     Basta* basta = nullptr;
     // tip error models (beagleMi355SetTipEmission, engine_tipemission.cpp): null on an instance that was never given an emission table
@@ -405,6 +399,9 @@ void devFree(Instance* in, void* p);                     // a block devAlloc gav
 // *grew (nullable): the buffer's address changed.  A failed allocation leaves b empty, never half-set.
 int growDevice(Instance* in, DevBuf& b, size_t need, size_t want, Grow how, bool* grew = nullptr);
 void releaseDevice(Instance* in, DevBuf& b);             // (synchronising is the caller's business)
+// the samplers' scratch: exactly `need` bytes when it grows
+inline int growScratch(Instance* in, DevBuf& b, size_t need) { return growDevice(in, b, need, need, Grow::SyncIfHeld); }
+static_assert(mi355::scratch::FLAG_SLOTS == mi355::MAX_JUMP_REGISTERS, "scratch_layout.h keeps one flag word per possible register");
 long stage(Instance* in, const void* src, size_t bytes, size_t reserve = 0);
 int upload(Instance* in, void* dst, const void* src, size_t bytes);
 int uploadTransient(Instance* in, const void* src, size_t bytes, void** dptr);
@@ -580,13 +577,75 @@ int edgeDifferentials(Instance* in, const int* postIdx, const int* preIdx, const
 int crossProducts(Instance* in, const int* postIdx, const int* preIdx, int rateIdx, int wIdx, const double* lengths, int count, double* outSum);
 
 // ---- engine_sampling.cpp
-// Where a device-side draw left its results (in->ancestralDev): states [rows][P] | categories [P] | error word.
+// Where a device-side draw left its results (in->ancestralDev, scratch_layout.h ancestralLayout)
 struct AncestralDraw { uint8_t* states; int* cats; unsigned* error; };
 // the draw of beagleMi355SampleAncestralStates left on the device (one launch on the instance's stream), and its copy-out
 int drawAncestral(Instance* in, const int* nodes, int nodeCount, int wIdx, int fIdx, unsigned long long seed, int flags, int globalP,
                   int pOffset, AncestralDraw* d);
 int copyAncestral(Instance* in, const AncestralDraw& d, int nodeCount, int globalP, int pOffset, unsigned char* outStates,
                   int* outCategories, unsigned* error);
+// every register's flags within `allowed` (flags == nullptr: none set)
+inline bool checkRegisterFlags(const int* flags, int K, int allowed) {
+    for (int k = 0; flags && k < K; k++) if (flags[k] & ~allowed) return false;
+    return true;
+}
+// Per-row values [K][R][P] leave through a stage of at most 256 MiB (and `cap` rows): the rows of one launch
+inline size_t stageRowCount(size_t R, size_t K, size_t P, size_t cap = SIZE_MAX) {
+    return std::max<size_t>(1, std::min<size_t>({R, (256ull << 20) / (K * P * sizeof(double)), cap}));
+}
+// rows r0 .. r1 - 1 of the stage [K][stride][P] (its row 0 = row r0) to out[k][R][globalP] at column pOffset, one copy per register —
+// linear where the instance has every column — then the synchronisation the next chunk's launch needs (it overwrites the stage)
+int copyStagedRows(Instance* in, const double* stage, size_t stride, size_t r0, size_t r1, int K, size_t R, size_t P, size_t globalP,
+                   size_t pOffset, double* out);
+// pattern totals [K][P] into their columns of outPatternTotals [K][globalP], this instance's row totals [K][R]; either may be NULL (queued)
+int copyJumpTotals(Instance* in, const double* dPat, const double* dRow, int K, size_t R, size_t P, size_t globalP, size_t pOffset,
+                   double* outPatternTotals, double* outRowTotals);
+// an event list of n events on the device (in->eventDev, scratch_layout.h eventLayout)
+int growEvents(Instance* in, size_t n, uint8_t** states, double** heights);
+// ... and its way out (either may be NULL), synchronised
+int copyEvents(Instance* in, size_t n, const uint8_t* states, const double* heights, unsigned char* outStates, double* outHeights);
+
+// ---- engine_simulate.cpp: the front end of the site-keyed simulators (sequences, complete histories).  A node list names per row
+// {outRow or -1, matrix or generator, parent row}; a node with an outRow keeps its states in scratch row ("slot") outRow, so that the
+// wanted rows leave as a few strided copies, the others behind the largest outRow.
+// The list's shape (outRow >= -1 and unique, parent before child) and the caller's root states and categories; *maxOut: the largest outRow
+int checkSiteCall(const int* nodes, int nodeCount, int siteCount, const unsigned char* inRootStates, const int* inRateCategories, int S,
+                  int C, int* maxOut);
+// rows[r].slot / parentSlot / parentIsPrev of every row (Row: SimRow, HistoryRow); *slots: scratch rows in all
+template <class Row>
+int assignSlots(const int* nodes, int nodeCount, int maxOut, std::vector<Row>& rows, size_t* slots) {
+    size_t next = (size_t)maxOut + 1;
+    for (int r = 0; r < nodeCount; r++) {
+        const int out = nodes[3 * r], parent = nodes[3 * r + 2];
+        const size_t slot = out >= 0 ? (size_t)out : next++;
+        if (slot > (size_t)INT_MAX) return BEAGLE_ERROR_OUT_OF_RANGE;
+        rows[r].slot = (int)slot;
+        rows[r].parentSlot = r == 0 ? -1 : rows[parent].slot;
+        rows[r].parentIsPrev = r > 0 && parent == r - 1;
+    }
+    *slots = next;
+    return 0;
+}
+// the sites of one launch: `wanted`, or the environment's `envName`=<n> (tests: chunk independence at a small size), no more than
+// `sites`, in whole `unit`s
+size_t chunkSites(const char* envName, size_t unit, size_t wanted, size_t sites);
+// the outRows of a list in ascending order, and their scratch rows' first `count` sites out to outStates[outRow][siteCount] at site
+// `first`: runs of consecutive rows as one strided copy each (queued)
+std::vector<int> wantedRows(const int* nodes, int nodeCount);
+int copyWantedRows(Instance* in, const std::vector<int>& wanted, const uint8_t* dStates, size_t chunk, size_t count, unsigned char* outStates,
+                   size_t siteCount, size_t first);
+// a call over siteCount sites on a handle of `shards` instances (a plain handle: one) of S states and C categories: the instances
+// take sites [siteCount k / n, siteCount (k + 1) / n) by order of arrival (the results are keyed on the site, so which takes which
+// part does not matter)
+struct SiteSplit {
+    int S = 0, C = 0, shards = 1, siteCount = 0; std::atomic<int> arrivals{0};
+    int init(int handle, int sites);
+    bool next(int* site0, int* site1) {
+        const int k = arrivals.fetch_add(1);
+        *site0 = (int)((long long)siteCount * k / shards); *site1 = (int)((long long)siteCount * (k + 1) / shards);
+        return k < shards;
+    }
+};
 
 // ---- engine_create.cpp
 size_t matrixSlotLayout(Instance* in);

@@ -1,8 +1,9 @@
 // engine_robustcounts.cpp — codon robust counting: the conditional counts of the 64-state product chain over three instances'
-// ancestral draws in one call, and the unconditioned count simulation; argument checks, the scratch layout, the launches.
+// ancestral draws in one call, and the unconditioned count simulation; argument checks and the launches.
 #include "engine_internal.h"
 
 using namespace mi355::eng;
+namespace scratch = mi355::scratch;
 
 namespace {
 
@@ -51,34 +52,19 @@ static int robustCounts(Instance* const* ins, const int* nodes, int nodeCount, c
             HIP_TRY(hipEventRecord(events.ev[q - 1], live(ins[q])));
         }
     }
-    const size_t stageRows = outCounts ? std::max<size_t>(1, std::min<size_t>(R, (256ull << 20) / ((size_t)K * P * sizeof(double)))) : 0;
-    // robustDev (doubles): U, U^-1, lambda [2 * 4096 + 64] | Q [4096] | registers [K][4096] | rateReg, tmp, M [3][K][4096]
-    //                      | cond [K][R][4096] | blockPartials [blocks][K][R] | branchTotals [K][R] | siteTotals [K][P]
-    //                      | outCounts stage [K][stageRows][P] | rows [R] | error word
-    const size_t nEig = 2 * (size_t)SS64 + mi355::ROBUST_STATES, nReg = (size_t)K * SS64, nCond = (size_t)K * R * SS64,
-                 nPart = blocks * K * R, nRow = (size_t)K * R, nSite = (size_t)K * P, nStage = (size_t)K * stageRows * P;
-    const size_t doubles = nEig + SS64 + 4 * nReg + nCond + nPart + nRow + nSite + nStage;
-    int rc = growDevice(in, in->robustDev, doubles * sizeof(double) + R * sizeof(mi355::RobustRow) + sizeof(unsigned),
-                        doubles * sizeof(double) + R * sizeof(mi355::RobustRow) + sizeof(unsigned), Grow::SyncIfHeld);
-    if (rc) return rc;
-    double* dEig = in->robustDev.as<double>();
-    double* dQ = dEig + nEig;
-    double* dReg = dQ + SS64;
-    double* dRateReg = dReg + nReg;
-    double* dTmp = dRateReg + nReg;
-    double* dM = dTmp + nReg;
-    double* dCond = dM + nReg;
-    double* dPart = dCond + nCond;
-    double* dRow = dPart + nPart;
-    double* dSite = dRow + nRow;
-    double* dStage = dSite + nSite;
-    mi355::RobustRow* dRows = (mi355::RobustRow*)(dStage + nStage);
-    unsigned* dErr = (unsigned*)(dRows + R);
+    const size_t stageRows = outCounts ? stageRowCount(R, K, P) : 0;
+    const scratch::RobustLayout L(mi355::ROBUST_STATES, P, K, R, blocks, stageRows, sizeof(mi355::RobustRow));
+    int rc = growScratch(in, in->robustDev, L.bytes()); if (rc) return rc;
+    char* base = in->robustDev.p;
+    double *dEig = L.eig.at(base), *dQ = L.Q.at(base), *dReg = L.reg.at(base), *dM = L.M.at(base), *dCond = L.cond.at(base),
+           *dPart = L.part.at(base), *dRow = L.row.at(base), *dSite = L.site.at(base), *dStage = L.stage.at(base);      // (dStage: NULL without outCounts)
+    mi355::RobustRow* dRows = L.rows.as<mi355::RobustRow>(base);
+    unsigned* dErr = L.error.at(base);
     rc = upload(in, dEig, U, SS64 * sizeof(double)); if (rc) return rc;
     rc = upload(in, dEig + SS64, Ui, SS64 * sizeof(double)); if (rc) return rc;
     rc = upload(in, dEig + 2 * SS64, lam, mi355::ROBUST_STATES * sizeof(double)); if (rc) return rc;
     rc = upload(in, dQ, Q, SS64 * sizeof(double)); if (rc) return rc;
-    rc = upload(in, dReg, registers, nReg * sizeof(double)); if (rc) return rc;
+    rc = upload(in, dReg, registers, L.reg.bytes()); if (rc) return rc;
     std::vector<mi355::RobustRow> rows(nodeCount);
     for (int r = 0; r < nodeCount; r++) {
         rows[r].tau = r == 0 ? 0.0 : branchLengths[r];
@@ -88,7 +74,7 @@ static int robustCounts(Instance* const* ins, const int* nodes, int nodeCount, c
     rc = upload(in, dRows, rows.data(), rows.size() * sizeof(mi355::RobustRow)); if (rc) return rc;
     HIP_TRY(hipMemsetAsync(dErr, 0, sizeof(unsigned), live(in)));
     for (int k = 0; k < K; k++) HIP_TRY(hipMemsetAsync(dCond + (size_t)k * R * SS64, 0, SS64 * sizeof(double), live(in)));      // row 0
-    mi355::launchRobustRegisters(live(in), dEig, dQ, dReg, K, dRateReg, dTmp, dM);
+    mi355::launchRobustRegisters(live(in), dEig, dQ, dReg, K, L.rateReg.at(base), L.tmp.at(base), dM);
     mi355::launchRobustTables(live(in), dRows, nodeCount, dEig, dM, K, dCond);
     HIP_TRY(hipGetLastError());
     for (int q = 0; q < 2; q++) HIP_TRY(hipStreamWaitEvent(live(in), events.ev[q], 0));
@@ -96,21 +82,17 @@ static int robustCounts(Instance* const* ins, const int* nodes, int nodeCount, c
     for (size_t r0 = 0; r0 < R; r0 += chunk) {
         const size_t r1 = std::min(R, r0 + chunk);
         mi355::launchRobustSites(live(in), dRows, nodeCount, (int)r0, (int)r1, d[0].states, d[1].states, d[2].states, dCond, K, P,
-                                 outCounts ? dStage : nullptr, dSite, dPart, dErr);
+                                 dStage, dSite, dPart, dErr);
         HIP_TRY(hipGetLastError());
-        if (!outCounts) continue;
-        for (int k = 0; k < K; k++)
-            HIP_TRY(hipMemcpyAsync(outCounts + ((size_t)k * R + r0) * P, dStage + (size_t)k * (r1 - r0) * P, (r1 - r0) * P * sizeof(double),
-                                   hipMemcpyDeviceToHost, live(in)));
-        HIP_TRY(hipStreamSynchronize(live(in)));           // (the next chunk overwrites the stage)
+        if (outCounts) { rc = copyStagedRows(in, dStage, r1 - r0, r0, r1, K, R, P, P, 0, outCounts); if (rc) return rc; }
     }
     if (outBranchTotals) {
-        mi355::launchRobustTotals(live(in), dPart, (int)blocks, K, nodeCount, 1, dRow);
+        mi355::launchBlockTotals(live(in), dPart, (int)blocks, K, nodeCount, 1, dRow);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(outBranchTotals, dRow, nRow * sizeof(double), hipMemcpyDeviceToHost, live(in)));
+        HIP_TRY(hipMemcpyAsync(outBranchTotals, dRow, L.row.bytes(), hipMemcpyDeviceToHost, live(in)));
     }
-    if (outSiteTotals) HIP_TRY(hipMemcpyAsync(outSiteTotals, dSite, nSite * sizeof(double), hipMemcpyDeviceToHost, live(in)));
-    if (outTables) HIP_TRY(hipMemcpyAsync(outTables, dCond, nCond * sizeof(double), hipMemcpyDeviceToHost, live(in)));
+    if (outSiteTotals) HIP_TRY(hipMemcpyAsync(outSiteTotals, dSite, L.site.bytes(), hipMemcpyDeviceToHost, live(in)));
+    if (outTables) HIP_TRY(hipMemcpyAsync(outTables, dCond, L.cond.bytes(), hipMemcpyDeviceToHost, live(in)));
     unsigned err = 0, drawErr = 0;
     rc = download(in, &err, dErr, sizeof(unsigned)); if (rc) return rc;
     for (int q = 0; q < 3; q++) {
@@ -126,44 +108,30 @@ static int robustCounts(Instance* const* ins, const int* nodes, int nodeCount, c
 // 256 MiB of staged values when outCounts is asked for), then the totals over the workgroups.
 static int unconditionedCounts(Instance* in, int S, const double* Q, const double* freqs, const double* lengths, int L, int sites,
                                const double* registers, int K, unsigned long long seed, double* outCounts, double* outTotals) {
-    const size_t SS = (size_t)S * S, blocks = (size_t)mi355::unconditionedBlocks(sites);
-    const size_t stageRows = outCounts ? std::max<size_t>(1, std::min<size_t>(L, (256ull << 20) / ((size_t)K * sites * sizeof(double)))) : 0;
-    // robustDev (doubles): Q [S][S] | frequencies [S] | lengths [L] | registers [K][S][S] | blockPartials [blocks][K][L]
-    //                      | totals [K][L] | outCounts stage [K][stageRows][sites] | error word
-    const size_t nReg = (size_t)K * SS, nPart = blocks * K * L, nTot = (size_t)K * L, nStage = (size_t)K * stageRows * sites;
-    const size_t doubles = SS + S + L + nReg + nPart + nTot + nStage;
-    int rc = growDevice(in, in->robustDev, doubles * sizeof(double) + sizeof(unsigned), doubles * sizeof(double) + sizeof(unsigned),
-                        Grow::SyncIfHeld);
-    if (rc) return rc;
-    double* dQ = in->robustDev.as<double>();
-    double* dFreq = dQ + SS;
-    double* dLen = dFreq + S;
-    double* dReg = dLen + L;
-    double* dPart = dReg + nReg;
-    double* dTot = dPart + nPart;
-    double* dStage = dTot + nTot;
-    unsigned* dErr = (unsigned*)(dStage + nStage);
-    rc = upload(in, dQ, Q, SS * sizeof(double)); if (rc) return rc;
-    rc = upload(in, dFreq, freqs, S * sizeof(double)); if (rc) return rc;
-    rc = upload(in, dLen, lengths, (size_t)L * sizeof(double)); if (rc) return rc;
-    rc = upload(in, dReg, registers, nReg * sizeof(double)); if (rc) return rc;
+    const size_t blocks = (size_t)mi355::unconditionedBlocks(sites);
+    const size_t stageRows = outCounts ? stageRowCount(L, K, sites) : 0;
+    const scratch::UnconditionedLayout Y(S, L, sites, K, blocks, stageRows);
+    int rc = growScratch(in, in->robustDev, Y.bytes()); if (rc) return rc;
+    char* base = in->robustDev.p;
+    double *dQ = Y.Q.at(base), *dFreq = Y.freq.at(base), *dLen = Y.len.at(base), *dReg = Y.reg.at(base), *dPart = Y.part.at(base),
+           *dTot = Y.tot.at(base), *dStage = Y.stage.at(base);              // (dStage: NULL without outCounts)
+    unsigned* dErr = Y.error.at(base);
+    rc = upload(in, dQ, Q, Y.Q.bytes()); if (rc) return rc;
+    rc = upload(in, dFreq, freqs, Y.freq.bytes()); if (rc) return rc;
+    rc = upload(in, dLen, lengths, Y.len.bytes()); if (rc) return rc;
+    rc = upload(in, dReg, registers, Y.reg.bytes()); if (rc) return rc;
     HIP_TRY(hipMemsetAsync(dErr, 0, sizeof(unsigned), live(in)));
     const size_t chunk = outCounts ? stageRows : (size_t)L;
     for (size_t l0 = 0; l0 < (size_t)L; l0 += chunk) {
         const size_t l1 = std::min<size_t>(L, l0 + chunk);
-        mi355::launchUnconditioned(live(in), dQ, dFreq, dLen, L, (int)l0, (int)l1, sites, dReg, K, S, seed, outCounts ? dStage : nullptr,
-                                   dPart, dErr);
+        mi355::launchUnconditioned(live(in), dQ, dFreq, dLen, L, (int)l0, (int)l1, sites, dReg, K, S, seed, dStage, dPart, dErr);
         HIP_TRY(hipGetLastError());
-        if (!outCounts) continue;
-        for (int k = 0; k < K; k++)
-            HIP_TRY(hipMemcpyAsync(outCounts + ((size_t)k * L + l0) * sites, dStage + (size_t)k * (l1 - l0) * sites,
-                                   (l1 - l0) * sites * sizeof(double), hipMemcpyDeviceToHost, live(in)));
-        HIP_TRY(hipStreamSynchronize(live(in)));           // (the next chunk overwrites the stage)
+        if (outCounts) { rc = copyStagedRows(in, dStage, l1 - l0, l0, l1, K, L, sites, sites, 0, outCounts); if (rc) return rc; }
     }
     if (outTotals) {
-        mi355::launchRobustTotals(live(in), dPart, (int)blocks, K, L, 0, dTot);
+        mi355::launchBlockTotals(live(in), dPart, (int)blocks, K, L, 0, dTot);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(outTotals, dTot, nTot * sizeof(double), hipMemcpyDeviceToHost, live(in)));
+        HIP_TRY(hipMemcpyAsync(outTotals, dTot, Y.tot.bytes(), hipMemcpyDeviceToHost, live(in)));
     }
     unsigned err = 0;
     rc = download(in, &err, dErr, sizeof(unsigned)); if (rc) return rc;

@@ -1,14 +1,60 @@
 // engine_sampling.cpp — the device samplers: ancestral-state draws, Markov-jump counts and rewards, uniformized histories; each one
-// call over a list of nodes, with its scratch layout.
+// call over a list of nodes.  Also what the other samplers' files share with them: the staged copy-out, the event list's buffer.
 #include "engine_internal.h"
 
 #include <cfloat>
 #include <map>
 
 using namespace mi355::eng;
+namespace scratch = mi355::scratch;
 
-// Grow-only device scratch of an instance (ancestral draws, Markov jumps): exactly `need` bytes when it grows, counted in deviceBytes.
-static int growScratch(Instance* in, DevBuf& b, size_t need) { return growDevice(in, b, need, need, Grow::SyncIfHeld); }
+int mi355::eng::copyStagedRows(Instance* in, const double* stage, size_t stride, size_t r0, size_t r1, int K, size_t R, size_t P,
+                               size_t globalP, size_t pOffset, double* out) {
+    for (int k = 0; k < K; k++) {
+        double* dst = out + ((size_t)k * R + r0) * globalP + pOffset;
+        const double* src = stage + (size_t)k * stride * P;
+        if (globalP == P)
+            HIP_TRY(hipMemcpyAsync(dst, src, (r1 - r0) * P * sizeof(double), hipMemcpyDeviceToHost, live(in)));
+        else
+            HIP_TRY(hipMemcpy2DAsync(dst, globalP * sizeof(double), src, P * sizeof(double), P * sizeof(double), r1 - r0,
+                                     hipMemcpyDeviceToHost, live(in)));
+    }
+    HIP_TRY(hipStreamSynchronize(live(in)));
+    return 0;
+}
+
+int mi355::eng::copyJumpTotals(Instance* in, const double* dPat, const double* dRow, int K, size_t R, size_t P, size_t globalP,
+                               size_t pOffset, double* outPatternTotals, double* outRowTotals) {
+    if (outPatternTotals)
+        HIP_TRY(hipMemcpy2DAsync(outPatternTotals + pOffset, globalP * sizeof(double), dPat, P * sizeof(double), P * sizeof(double),
+                                 (size_t)K, hipMemcpyDeviceToHost, live(in)));
+    if (outRowTotals) HIP_TRY(hipMemcpyAsync(outRowTotals, dRow, (size_t)K * R * sizeof(double), hipMemcpyDeviceToHost, live(in)));
+    return 0;
+}
+
+int mi355::eng::growEvents(Instance* in, size_t n, uint8_t** states, double** heights) {
+    const scratch::EventLayout L(n);
+    int rc = growScratch(in, in->eventDev, L.bytes()); if (rc) return rc;
+    *states = L.states.at(in->eventDev.p);
+    *heights = L.heights.at(in->eventDev.p);
+    return 0;
+}
+
+int mi355::eng::copyEvents(Instance* in, size_t n, const uint8_t* states, const double* heights, unsigned char* outStates,
+                           double* outHeights) {
+    if (outHeights) HIP_TRY(hipMemcpyAsync(outHeights, heights, n * sizeof(double), hipMemcpyDeviceToHost, live(in)));
+    if (outStates) HIP_TRY(hipMemcpyAsync(outStates, states, 2 * n, hipMemcpyDeviceToHost, live(in)));
+    HIP_TRY(hipStreamSynchronize(live(in)));
+    return 0;
+}
+
+// the registers [K][S][S] and their flags (NULL: none set) to the device
+static int uploadRegisters(Instance* in, double* dReg, const double* registers, size_t nReg, int* dFlags, const int* registerFlags, int K) {
+    std::vector<int> fl(K, 0);
+    if (registerFlags) for (int k = 0; k < K; k++) fl[k] = registerFlags[k];
+    int rc = upload(in, dReg, registers, nReg * sizeof(double)); if (rc) return rc;
+    return upload(in, dFlags, fl.data(), K * sizeof(int));
+}
 
 // The draw itself, left on the device (AncestralDraw, engine_internal.h): validation, materialising virtual buffers, ONE launch
 // (kernels_ancestral.hip).
@@ -37,12 +83,11 @@ int mi355::eng::drawAncestral(Instance* in, const int* nodes, int nodeCount, int
         row.matrix = r == 0 ? nullptr : in->matrices + n * nodes[3 * r + 1];
         row.parent = r == 0 ? -1 : nodes[3 * r + 2];
     }
-    const size_t stateBytes = ((size_t)nodeCount * in->P + 255) & ~(size_t)255;
-    const size_t tailBytes = (size_t)in->P * sizeof(int) + sizeof(unsigned);
-    int rc = growScratch(in, in->ancestralDev, stateBytes + tailBytes); if (rc) return rc;
-    d->states = in->ancestralDev.as<uint8_t>();
-    d->cats = (int*)(in->ancestralDev.p + stateBytes);
-    d->error = (unsigned*)(d->cats + in->P);
+    const scratch::AncestralLayout L(nodeCount, in->P);
+    int rc = growScratch(in, in->ancestralDev, L.bytes()); if (rc) return rc;
+    d->states = L.states.at(in->ancestralDev.p);
+    d->cats = L.cats.at(in->ancestralDev.p);
+    d->error = L.error.at(in->ancestralDev.p);                 // (right behind the categories: copyAncestral takes both in one copy)
     void* dRows = nullptr;
     rc = uploadTransient(in, rows.data(), rows.size() * sizeof(mi355::AncestralRow), &dRows); if (rc) return rc;
     HIP_TRY(hipMemsetAsync(d->error, 0, sizeof(unsigned), live(in)));
@@ -70,42 +115,38 @@ int mi355::eng::copyAncestral(Instance* in, const AncestralDraw& d, int nodeCoun
     return 0;
 }
 
+// The instance behind shard handle h of `handle` (a plain handle: itself) made ready for a sampler (the samplers read tips' partials
+// as data: engine_tipemission.cpp), and which patterns of how many it holds
+static int samplerInstance(int handle, int h, Instance** out, int* globalP, int* pStart) {
+    GET_INSTANCE(h);
+    DEMOTE_FOLDED_TIPS(in);
+    int pEnd = 0;
+    *out = in; *globalP = in->P; *pStart = 0;
+    if (mi355::isShardedHandle(handle)) { mi355::shardedBoundsOfHandle(handle, h, pStart, &pEnd); *globalP = mi355::shardedPatternCount(handle); }
+    return 0;
+}
+
 // One draw of every listed node's state per pattern (include/beagle_mi355.h beagleMi355SampleAncestralStates; what
 // AncestralStateBeagleTreeLikelihood.traverseSample computes from a getPartials per internal node and a getTransitionMatrix per
 // branch, AncestralStateBeagleTreeLikelihood.java:414-625).  Virtual buffers are materialised by one walk, as for a read-back; the
 // draw itself is ONE launch (kernels_ancestral.hip), then the states and categories come back in two copies.  The instance's
 // patterns are patterns pOffset .. pOffset + P - 1 of an alignment of globalP (the sharded handle): the random numbers are keyed
 // on the global pattern, and row r's states land at outStates + r * globalP + pOffset.
-static int sampleAncestral(Instance* in, const int* nodes, int nodeCount, int wIdx, int fIdx, unsigned long long seed, int flags,
-                           int globalP, int pOffset, unsigned char* outStates, int* outCategories) {
-    AncestralDraw d;
-    int rc = drawAncestral(in, nodes, nodeCount, wIdx, fIdx, seed, flags, globalP, pOffset, &d); if (rc) return rc;
-    unsigned err = 0;
-    rc = copyAncestral(in, d, nodeCount, globalP, pOffset, outStates, outCategories, &err); if (rc) return rc;
-    return err ? BEAGLE_ERROR_FLOATING_POINT : BEAGLE_SUCCESS;
-}
-
 extern "C" {
 
 int beagleMi355SampleAncestralStates(int instance, const int* nodes, int nodeCount, int categoryWeightsIndex, int stateFrequenciesIndex,
                                      unsigned long long seed, int flags, unsigned char* outStates, int* outRateCategories) {
     if (!nodes || nodeCount < 1 || !outStates) return BEAGLE_ERROR_OUT_OF_RANGE;
-    if (mi355::isShardedHandle(instance)) {
-        // every shard draws its own pattern range into its columns of the caller's arrays
-        const int globalP = mi355::shardedPatternCount(instance);
-        return mi355::shardedBroadcast(instance, [&](int h) {
-            int pStart = 0, pEnd = 0;
-            mi355::shardedBoundsOfHandle(instance, h, &pStart, &pEnd);
-            GET_INSTANCE(h);
-            DEMOTE_FOLDED_TIPS(in);
-            return sampleAncestral(in, nodes, nodeCount, categoryWeightsIndex, stateFrequenciesIndex, seed, flags, globalP, pStart,
-                                   outStates, outRateCategories);
-        });
-    }
-    GET_INSTANCE(instance);
-    DEMOTE_FOLDED_TIPS(in);                     // (the samplers read tips' partials as data: engine_tipemission.cpp)
-    return sampleAncestral(in, nodes, nodeCount, categoryWeightsIndex, stateFrequenciesIndex, seed, flags, in->P, 0, outStates,
-                           outRateCategories);
+    return mi355::shardedOrPlain(instance, [&](int h) {      // every shard draws its own pattern range into its columns of the caller's arrays
+        Instance* in = nullptr;
+        int globalP = 0, pStart = 0;
+        int rc = samplerInstance(instance, h, &in, &globalP, &pStart); if (rc) return rc;
+        AncestralDraw d;
+        rc = drawAncestral(in, nodes, nodeCount, categoryWeightsIndex, stateFrequenciesIndex, seed, flags, globalP, pStart, &d); if (rc) return rc;
+        unsigned err = 0;
+        rc = copyAncestral(in, d, nodeCount, globalP, pStart, outStates, outRateCategories, &err); if (rc) return rc;
+        return err ? (int)BEAGLE_ERROR_FLOATING_POINT : (int)BEAGLE_SUCCESS;
+    });
 }
 
 }  // extern "C"
@@ -126,27 +167,14 @@ static int sampleJumps(Instance* in, const int* nodes, int nodeCount, const doub
     int rc = drawAncestral(in, nodes, nodeCount, wIdx, fIdx, seed, flags, globalP, pOffset, &d); if (rc) return rc;
     const int S = in->S, C = in->C, P = in->P;
     const size_t SS = (size_t)S * S, R = (size_t)nodeCount, blocks = (size_t)mi355::jumpSiteBlocks(P);
-    const size_t stageRows = outJumps ? std::max<size_t>(1, std::min<size_t>(R, (256ull << 20) / ((size_t)K * P * sizeof(double)))) : 0;
-    // jumpDev (doubles): registers [K][S][S] | rateReg, tmp, M [3][K][S][S] | cond [K][R][C][S][S] | blockPartials [blocks][K][R]
-    //                    | rowTotals [K][R] | patternTotals [K][P] | outJumps stage [K][stageRows][P] | register flags int [K]
-    const size_t nReg = (size_t)K * SS, nCond = (size_t)K * R * C * SS, nPart = blocks * K * R, nRow = (size_t)K * R,
-                 nPat = (size_t)K * P, nStage = (size_t)K * stageRows * P;
-    const size_t doubles = 4 * nReg + nCond + nPart + nRow + nPat + nStage;
-    rc = growScratch(in, in->jumpDev, doubles * sizeof(double) + mi355::MAX_JUMP_REGISTERS * sizeof(int)); if (rc) return rc;
-    double* dReg = in->jumpDev.as<double>();
-    double* dRateReg = dReg + nReg;
-    double* dTmp = dRateReg + nReg;
-    double* dM = dTmp + nReg;
-    double* dCond = dM + nReg;
-    double* dPart = dCond + nCond;
-    double* dRow = dPart + nPart;
-    double* dPat = dRow + nRow;
-    double* dStage = dPat + nPat;
-    int* dFlags = (int*)(dStage + nStage);
-    std::vector<int> fl(K, 0);
-    if (registerFlags) for (int k = 0; k < K; k++) fl[k] = registerFlags[k];
-    rc = upload(in, dReg, registers, nReg * sizeof(double)); if (rc) return rc;
-    rc = upload(in, dFlags, fl.data(), K * sizeof(int)); if (rc) return rc;
+    const size_t stageRows = outJumps ? stageRowCount(R, K, P) : 0;
+    const scratch::JumpLayout L(S, C, P, K, R, blocks, stageRows);
+    rc = growScratch(in, in->jumpDev, L.bytes()); if (rc) return rc;
+    char* base = in->jumpDev.p;
+    double *dReg = L.reg.at(base), *dM = L.M.at(base), *dCond = L.cond.at(base), *dPart = L.part.at(base), *dRow = L.row.at(base),
+           *dPat = L.pat.at(base), *dStage = L.stage.at(base);           // (dStage: NULL without outJumps)
+    int* dFlags = L.flags.at(base);
+    rc = uploadRegisters(in, dReg, registers, L.reg.count, dFlags, registerFlags, K); if (rc) return rc;
     std::vector<mi355::JumpRow> rows(nodeCount);
     for (int r = 0; r < nodeCount; r++) {
         mi355::JumpRow& row = rows[r];
@@ -161,28 +189,20 @@ static int sampleJumps(Instance* in, const int* nodes, int nodeCount, const doub
     const mi355::JumpRow* dRows = (const mi355::JumpRow*)dRowsV;
     const double* eig = in->eigen + (2 * SS + S) * (size_t)eigenIndex;
     const double* rates = in->rates + (size_t)ratesIndex * C;
-    mi355::launchJumpRegisters(live(in), eig, dReg, dFlags, K, S, dRateReg, dTmp, dM);
+    mi355::launchJumpRegisters(live(in), eig, dReg, dFlags, K, S, L.rateReg.at(base), L.tmp.at(base), dM);
     mi355::launchJumpMatrices(live(in), dRows, nodeCount, eig, rates, dM, dFlags, K, S, C, dCond);
     HIP_TRY(hipGetLastError());
     const size_t chunk = outJumps ? stageRows : R;
     for (size_t r0 = 0; r0 < R; r0 += chunk) {
         const size_t r1 = std::min(R, r0 + chunk);
-        mi355::launchJumpSites(live(in), dRows, nodeCount, (int)r0, (int)r1, d.states, d.cats, dCond, K, S, C, P,
-                               outJumps ? dStage : nullptr, dPat, dPart, d.error);
+        mi355::launchJumpSites(live(in), dRows, nodeCount, (int)r0, (int)r1, d.states, d.cats, dCond, K, S, C, P, dStage, dPat, dPart,
+                               d.error);
         HIP_TRY(hipGetLastError());
-        if (!outJumps) continue;
-        for (int k = 0; k < K; k++)
-            HIP_TRY(hipMemcpy2DAsync(outJumps + ((size_t)k * R + r0) * globalP + pOffset, (size_t)globalP * sizeof(double),
-                                     dStage + (size_t)k * (r1 - r0) * P, (size_t)P * sizeof(double), (size_t)P * sizeof(double), r1 - r0,
-                                     hipMemcpyDeviceToHost, live(in)));
-        HIP_TRY(hipStreamSynchronize(live(in)));           // (the next chunk overwrites the stage)
+        if (outJumps) { rc = copyStagedRows(in, dStage, r1 - r0, r0, r1, K, R, P, globalP, pOffset, outJumps); if (rc) return rc; }
     }
-    mi355::launchJumpRowTotals(live(in), dPart, (int)blocks, K, nodeCount, dRow);
+    mi355::launchBlockTotals(live(in), dPart, (int)blocks, K, nodeCount, 1, dRow);
     HIP_TRY(hipGetLastError());
-    if (outPatternTotals)
-        HIP_TRY(hipMemcpy2DAsync(outPatternTotals + pOffset, (size_t)globalP * sizeof(double), dPat, (size_t)P * sizeof(double),
-                                 (size_t)P * sizeof(double), (size_t)K, hipMemcpyDeviceToHost, live(in)));
-    if (outRowTotals) HIP_TRY(hipMemcpyAsync(outRowTotals, dRow, nRow * sizeof(double), hipMemcpyDeviceToHost, live(in)));
+    rc = copyJumpTotals(in, dPat, dRow, K, R, P, globalP, pOffset, outPatternTotals, outRowTotals); if (rc) return rc;
     unsigned err = 0;
     rc = copyAncestral(in, d, nodeCount, globalP, pOffset, outStates, outCategories, &err); if (rc) return rc;
     return err ? BEAGLE_ERROR_FLOATING_POINT : BEAGLE_SUCCESS;
@@ -198,44 +218,28 @@ int beagleMi355SampleMarkovJumps(int instance, const int* nodes, int nodeCount, 
     if (!nodes || nodeCount < 1 || !branchTimes || !registers) return BEAGLE_ERROR_OUT_OF_RANGE;
     if (registerCount < 1 || registerCount > mi355::MAX_JUMP_REGISTERS) return BEAGLE_ERROR_OUT_OF_RANGE;
     if (!outJumps && !outPatternTotals && !outRowTotals) return BEAGLE_ERROR_OUT_OF_RANGE;
-    if (registerFlags)
-        for (int k = 0; k < registerCount; k++)
-            if (registerFlags[k] & ~(BEAGLE_MI355_JUMPS_REWARDS | BEAGLE_MI355_JUMPS_SCALE_BY_TIME)) return BEAGLE_ERROR_OUT_OF_RANGE;
+    if (!checkRegisterFlags(registerFlags, registerCount, BEAGLE_MI355_JUMPS_REWARDS | BEAGLE_MI355_JUMPS_SCALE_BY_TIME))
+        return BEAGLE_ERROR_OUT_OF_RANGE;
     const size_t nRow = (size_t)registerCount * nodeCount;
-    if (mi355::isShardedHandle(instance)) {
-        // every shard fills its own columns; the row totals are the shards' sums, added in shard (= pattern) order
-        const int globalP = mi355::shardedPatternCount(instance);
-        std::mutex mu;
-        std::vector<std::pair<int, std::vector<double>>> partial;
-        const int rc = mi355::shardedBroadcast(instance, [&](int h) {
-            int pStart = 0, pEnd = 0;
-            mi355::shardedBoundsOfHandle(instance, h, &pStart, &pEnd);
-            GET_INSTANCE(h);
-            DEMOTE_FOLDED_TIPS(in);
-            std::vector<double> rows(outRowTotals ? nRow : 0);
-            const int r = sampleJumps(in, nodes, nodeCount, branchTimes, branchRates, eigenIndex, categoryRatesIndex, categoryWeightsIndex,
-                                      stateFrequenciesIndex, registers, registerFlags, registerCount, seed, flags, globalP, pStart,
-                                      outStates, outRateCategories, outJumps, outPatternTotals, outRowTotals ? rows.data() : nullptr);
-            std::lock_guard<std::mutex> lock(mu);
-            partial.emplace_back(pStart, std::move(rows));
-            return r;
-        });
-        if (outRowTotals && (rc == BEAGLE_SUCCESS || rc == BEAGLE_ERROR_FLOATING_POINT)) {
-            std::sort(partial.begin(), partial.end(), [](const std::pair<int, std::vector<double>>& a,
-                                                         const std::pair<int, std::vector<double>>& b) { return a.first < b.first; });
-            for (size_t i = 0; i < nRow; i++) {
-                double s = partial[0].second[i];
-                for (size_t q = 1; q < partial.size(); q++) s = s + partial[q].second[i];
-                outRowTotals[i] = s;
-            }
-        }
-        return rc;
-    }
-    GET_INSTANCE(instance);
-    DEMOTE_FOLDED_TIPS(in);
-    return sampleJumps(in, nodes, nodeCount, branchTimes, branchRates, eigenIndex, categoryRatesIndex, categoryWeightsIndex,
-                       stateFrequenciesIndex, registers, registerFlags, registerCount, seed, flags, in->P, 0, outStates, outRateCategories,
-                       outJumps, outPatternTotals, outRowTotals);
+    // every shard (a plain handle: the instance) fills its own columns; the row totals are the shards' sums, added in shard (= pattern) order
+    std::mutex mu;
+    std::map<int, mi355::ShardPart> parts;
+    const int rc = mi355::shardedOrPlain(instance, [&](int h) {
+        Instance* in = nullptr;
+        int globalP = 0;
+        mi355::ShardPart part;
+        int r = samplerInstance(instance, h, &in, &globalP, &part.start); if (r) return r;
+        part.rowTotals.resize(outRowTotals ? nRow : 0);
+        r = sampleJumps(in, nodes, nodeCount, branchTimes, branchRates, eigenIndex, categoryRatesIndex, categoryWeightsIndex,
+                        stateFrequenciesIndex, registers, registerFlags, registerCount, seed, flags, globalP, part.start, outStates,
+                        outRateCategories, outJumps, outPatternTotals, outRowTotals ? part.rowTotals.data() : nullptr);
+        std::lock_guard<std::mutex> lock(mu);
+        parts[h] = std::move(part);
+        return r;
+    });
+    if (outRowTotals && (rc == BEAGLE_SUCCESS || rc == BEAGLE_ERROR_FLOATING_POINT))
+        mi355::sumRowTotals(mi355::orderedParts(parts), nRow, outRowTotals);
+    return rc;
 }
 
 }  // extern "C"
@@ -244,12 +248,11 @@ int beagleMi355SampleMarkovJumps(int instance, const int* nodes, int nodeCount, 
 // MarkovJumpsBeagleTreeLikelihood.computeSampledMarkovJumpsForBranch computes inside traverseSample with useUniformization = true,
 // MarkovJumpsBeagleTreeLikelihood.java:473-509).  The draw is drawAncestral's, left on the device; then kernels_uniformized.hip:
 // the R^n table, the histories per chunk of rows (at most 256 MiB of staged values), the pattern totals per chunk, the row totals
-// (launchJumpRowTotals), and with histories the event offsets.  Writing the events is a second step (uniformEvents) so that the
+// (launchBlockTotals), and with histories the event offsets.  Writing the events is a second step (uniformEvents) so that the
 // sharded handle can place every shard's list after the earlier shards' totals are known.
-struct UniformPass {
+struct UniformPass : mi355::ShardPart {                    // (start: the instance's first pattern)
     mi355::UniformSiteArgs args;
-    long long events = 0, fallbacks = 0;
-    bool wantEvents = false;
+    long long fallbacks = 0;
 };
 
 // mu = max_i -Q_ii in SubordinatedProcess.getMaxRate's order; R = Q / mu + I (constructDtmcMatrix).  false: mu not finite and > 0
@@ -289,7 +292,7 @@ static int uniformTableLength(double mu, const double* branchTimes, const double
 static int uniformRun(Instance* in, const int* nodes, int nodeCount, const double* branchTimes, const double* branchRates,
                       const double* nodeHeights, const double* Q, int ratesIndex, int wIdx, int fIdx, const double* registers,
                       const int* registerFlags, int K, int simulants, unsigned long long seed, int flags, int globalP, int pOffset,
-                      unsigned char* outStates, int* outCategories, double* outJumps, double* outPatternTotals, double* outRowTotals,
+                      unsigned char* outStates, int* outCategories, double* outJumps, double* outPatternTotals, bool rowTotals,
                       int* outEventCounts, bool history, UniformPass* pass) {
     if (badIndex(ratesIndex, in->eigenCount)) return BEAGLE_ERROR_OUT_OF_RANGE;
     const int S = in->S, C = in->C, P = in->P;
@@ -303,39 +306,22 @@ static int uniformRun(Instance* in, const int* nodes, int nodeCount, const doubl
     rc = download(in, catRates.data(), dRates, C * sizeof(double)); if (rc) return rc;
     const int N = uniformTableLength(mu, branchTimes, branchRates, nodeCount, catRates.data(), C);
     const size_t SS = (size_t)S * S, Rn = (size_t)nodeCount, blocks = (size_t)mi355::jumpSiteBlocks(P);
-    const size_t stageRows = std::max<size_t>(1, std::min<size_t>({Rn, (256ull << 20) / ((size_t)K * P * sizeof(double)), 65535}));
-    // uniformDev: table [N][S][S] | registers [K][S][S] | blockPartials [blocks][K][R] | rowTotals [K][R] | patternTotals [K][P]
-    //             | stage [K][stageRows][P] (doubles) | rows [R] | register flags int [K] | pattern offsets + total, fallbacks
-    //             long long [P + 2] | event counts int [R][P] (histories)
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t nTable = (size_t)N * SS, nReg = (size_t)K * SS, nPart = blocks * K * Rn, nRow = (size_t)K * Rn, nPat = (size_t)K * P,
-                 nStage = (size_t)K * stageRows * P;
-    const size_t oRows = up((nTable + nReg + nPart + nRow + nPat + nStage) * sizeof(double));
-    const size_t oFlags = oRows + up(Rn * sizeof(mi355::UniformRow));
-    const size_t oLong = oFlags + up(mi355::MAX_JUMP_REGISTERS * sizeof(int));
-    const size_t oCounts = oLong + up(((size_t)P + 2) * sizeof(long long));
-    const size_t bytes = oCounts + (history ? Rn * P * sizeof(int) : 0);
-    rc = growScratch(in, in->uniformDev, bytes); if (rc) return rc;
+    const size_t stageRows = stageRowCount(Rn, K, P, 65535);           // (65535: a grid's y extent)
+    const scratch::UniformLayout L(S, P, K, Rn, blocks, stageRows, N, sizeof(mi355::UniformRow), history);
+    rc = growScratch(in, in->uniformDev, L.bytes()); if (rc) return rc;
     char* base = in->uniformDev.p;
-    double* dTable = (double*)base;
-    double* dReg = dTable + nTable;
-    double* dPart = dReg + nReg;
-    double* dRow = dPart + nPart;
-    double* dPat = dRow + nRow;
-    double* dStage = dPat + nPat;
-    mi355::UniformRow* dRowsU = (mi355::UniformRow*)(base + oRows);
-    int* dFlags = (int*)(base + oFlags);
-    long long* dLong = (long long*)(base + oLong);
-    int* dCounts = history ? (int*)(base + oCounts) : nullptr;
+    double *dTable = L.table.at(base), *dReg = L.reg.at(base), *dPart = L.part.at(base), *dRow = L.row.at(base), *dPat = L.pat.at(base),
+           *dStage = L.stage.at(base);
+    mi355::UniformRow* dRowsU = L.rows.as<mi355::UniformRow>(base);
+    int* dFlags = L.flags.at(base);
+    long long* dLong = L.longs.at(base);
+    int* dCounts = L.counts.at(base);                       // (NULL without histories)
 
     std::vector<double> head(2 * SS, 0.0);
     for (int i = 0; i < S; i++) head[(size_t)i * S + i] = 1.0;
     std::copy(R.begin(), R.end(), head.begin() + SS);
     rc = upload(in, dTable, head.data(), head.size() * sizeof(double)); if (rc) return rc;
-    rc = upload(in, dReg, registers, nReg * sizeof(double)); if (rc) return rc;
-    std::vector<int> fl(K, 0);
-    if (registerFlags) for (int k = 0; k < K; k++) fl[k] = registerFlags[k];
-    rc = upload(in, dFlags, fl.data(), K * sizeof(int)); if (rc) return rc;
+    rc = uploadRegisters(in, dReg, registers, L.reg.count, dFlags, registerFlags, K); if (rc) return rc;
     std::vector<mi355::UniformRow> rows(nodeCount);
     for (int r = 0; r < nodeCount; r++) {
         mi355::UniformRow& row = rows[r];
@@ -363,19 +349,14 @@ static int uniformRun(Instance* in, const int* nodes, int nodeCount, const doubl
         mi355::launchUniformSites(live(in), a, (int)r0, (int)r1, false);
         mi355::launchUniformPatternTotals(live(in), dStage, (int)stageRows, (int)r0, (int)r1, K, P, dPat);
         HIP_TRY(hipGetLastError());
-        if (!outJumps) continue;
-        for (int k = 0; k < K; k++)
-            HIP_TRY(hipMemcpy2DAsync(outJumps + ((size_t)k * Rn + r0) * globalP + pOffset, (size_t)globalP * sizeof(double),
-                                     dStage + (size_t)k * stageRows * P, (size_t)P * sizeof(double), (size_t)P * sizeof(double), r1 - r0,
-                                     hipMemcpyDeviceToHost, live(in)));
-        HIP_TRY(hipStreamSynchronize(live(in)));           // (the next chunk overwrites the stage)
+        if (outJumps) { rc = copyStagedRows(in, dStage, stageRows, r0, r1, K, Rn, P, globalP, pOffset, outJumps); if (rc) return rc; }
     }
-    mi355::launchJumpRowTotals(live(in), dPart, (int)blocks, K, nodeCount, dRow);
+    mi355::launchBlockTotals(live(in), dPart, (int)blocks, K, nodeCount, 1, dRow);
     HIP_TRY(hipGetLastError());
-    if (outPatternTotals)
-        HIP_TRY(hipMemcpy2DAsync(outPatternTotals + pOffset, (size_t)globalP * sizeof(double), dPat, (size_t)P * sizeof(double),
-                                 (size_t)P * sizeof(double), (size_t)K, hipMemcpyDeviceToHost, live(in)));
-    if (outRowTotals) HIP_TRY(hipMemcpyAsync(outRowTotals, dRow, nRow * sizeof(double), hipMemcpyDeviceToHost, live(in)));
+    pass->start = pOffset;
+    pass->rowTotals.resize(rowTotals ? (size_t)K * Rn : 0);
+    rc = copyJumpTotals(in, dPat, dRow, K, Rn, P, globalP, pOffset, outPatternTotals, rowTotals ? pass->rowTotals.data() : nullptr);
+    if (rc) return rc;
     if (history) {
         if (outEventCounts)
             HIP_TRY(hipMemcpy2DAsync(outEventCounts + pOffset, (size_t)globalP * sizeof(int), dCounts, (size_t)P * sizeof(int),
@@ -393,21 +374,14 @@ static int uniformRun(Instance* in, const int* nodes, int nodeCount, const doubl
 }
 
 // The event list of the last uniformRun on `in`: the same histories again, written at outHeights / outStates (this instance's first event)
-static int uniformEvents(Instance* in, UniformPass* pass, double* outHeights, unsigned char* outStates) {
-    if (pass->events == 0) return 0;
-    const size_t n = (size_t)pass->events;
-    const size_t stBytes = (2 * n + 255) & ~(size_t)255;
-    int rc = growScratch(in, in->eventDev, stBytes + n * sizeof(double)); if (rc) return rc;
-    mi355::UniformSiteArgs a = pass->args;
-    a.eventStates = in->eventDev.as<uint8_t>();
-    a.eventHeights = (double*)(in->eventDev.p + stBytes);
+static int uniformEvents(Instance* in, const UniformPass& pass, double* outHeights, unsigned char* outStates) {
+    if (pass.events == 0) return 0;
+    mi355::UniformSiteArgs a = pass.args;
+    int rc = growEvents(in, (size_t)pass.events, &a.eventStates, &a.eventHeights); if (rc) return rc;
     for (int r0 = 0; r0 < a.nRows; r0 += 65535)
         mi355::launchUniformSites(live(in), a, r0, std::min(a.nRows, r0 + 65535), true);
     HIP_TRY(hipGetLastError());
-    if (outHeights) HIP_TRY(hipMemcpyAsync(outHeights, a.eventHeights, n * sizeof(double), hipMemcpyDeviceToHost, live(in)));
-    if (outStates) HIP_TRY(hipMemcpyAsync(outStates, a.eventStates, 2 * n, hipMemcpyDeviceToHost, live(in)));
-    HIP_TRY(hipStreamSynchronize(live(in)));
-    return 0;
+    return copyEvents(in, (size_t)pass.events, a.eventStates, a.eventHeights, outStates, outHeights);
 }
 
 extern "C" {
@@ -423,9 +397,8 @@ int beagleMi355SampleMarkovJumpsUniformized(int instance, const int* nodes, int 
     if (!nodes || nodeCount < 1 || !branchTimes || !registers || !infinitesimalMatrix) return BEAGLE_ERROR_OUT_OF_RANGE;
     if (registerCount < 1 || registerCount > mi355::MAX_JUMP_REGISTERS) return BEAGLE_ERROR_OUT_OF_RANGE;
     if (simulantCount < 1 || simulantCount > mi355::UNIFORM_MAX_SIMULANTS) return BEAGLE_ERROR_OUT_OF_RANGE;
-    if (registerFlags)
-        for (int k = 0; k < registerCount; k++)
-            if (registerFlags[k] & ~(BEAGLE_MI355_JUMPS_REWARDS | BEAGLE_MI355_JUMPS_SCALE_BY_TIME)) return BEAGLE_ERROR_OUT_OF_RANGE;
+    if (!checkRegisterFlags(registerFlags, registerCount, BEAGLE_MI355_JUMPS_REWARDS | BEAGLE_MI355_JUMPS_SCALE_BY_TIME))
+        return BEAGLE_ERROR_OUT_OF_RANGE;
     const bool wantEvents = outEventHeights || outEventStates;
     const bool history = outEventCounts || wantEvents || outEventTotal;
     if (!outJumps && !outPatternTotals && !outRowTotals && !history) return BEAGLE_ERROR_OUT_OF_RANGE;
@@ -433,71 +406,34 @@ int beagleMi355SampleMarkovJumpsUniformized(int instance, const int* nodes, int 
     if (wantEvents && eventCapacity < 0) return BEAGLE_ERROR_OUT_OF_RANGE;
     if (outEventTotal) *outEventTotal = 0;
     if (outFallbacks) *outFallbacks = 0;
-    const size_t nRow = (size_t)registerCount * nodeCount;
-    if (mi355::isShardedHandle(instance)) {
-        // phase 1: every shard draws, simulates and fills its own columns; phase 2: its events after the earlier shards' events
-        const int globalP = mi355::shardedPatternCount(instance);
-        std::mutex mu;
-        std::map<int, std::pair<int, std::vector<double>>> partial;      // shard handle -> (pStart, row totals)
-        std::map<int, UniformPass> passes;
-        int rc = mi355::shardedBroadcast(instance, [&](int h) {
-            int pStart = 0, pEnd = 0;
-            mi355::shardedBoundsOfHandle(instance, h, &pStart, &pEnd);
-            GET_INSTANCE(h);
-            DEMOTE_FOLDED_TIPS(in);
-            std::vector<double> rows(outRowTotals ? nRow : 0);
-            UniformPass pass;
-            const int r = uniformRun(in, nodes, nodeCount, branchTimes, branchRates, nodeHeights, infinitesimalMatrix, categoryRatesIndex,
-                                     categoryWeightsIndex, stateFrequenciesIndex, registers, registerFlags, registerCount, simulantCount,
-                                     seed, flags, globalP, pStart, outStates, outRateCategories, outJumps, outPatternTotals,
-                                     outRowTotals ? rows.data() : nullptr, outEventCounts, history, &pass);
-            std::lock_guard<std::mutex> lock(mu);
-            partial[h] = std::make_pair(pStart, std::move(rows));
-            passes[h] = pass;
-            return r;
-        });
-        if (rc != BEAGLE_SUCCESS && rc != BEAGLE_ERROR_FLOATING_POINT) return rc;
-        std::vector<std::pair<int, int>> order;                          // (pStart, handle) in shard order
-        for (auto& e : partial) order.emplace_back(e.second.first, e.first);
-        std::sort(order.begin(), order.end());
-        if (outRowTotals)
-            for (size_t i = 0; i < nRow; i++) {
-                double s = partial[order[0].second].second[i];
-                for (size_t q = 1; q < order.size(); q++) s = s + partial[order[q].second].second[i];
-                outRowTotals[i] = s;
-            }
-        long long total = 0, fallbacks = 0;
-        std::map<int, long long> first;
-        for (auto& o : order) {
-            first[o.second] = total;
-            total += passes[o.second].events;
-            fallbacks += passes[o.second].fallbacks;
-        }
-        if (outEventTotal) *outEventTotal = total;
-        if (outFallbacks) *outFallbacks = fallbacks;
-        if (!wantEvents) return rc;
-        if (total > eventCapacity) return BEAGLE_ERROR_OUT_OF_RANGE;
-        const int rcEvents = mi355::shardedBroadcast(instance, [&](int h) {
-            GET_INSTANCE(h);
-            const long long f = first[h];
-            return uniformEvents(in, &passes[h], outEventHeights ? outEventHeights + f : nullptr,
-                                 outEventStates ? outEventStates + 2 * f : nullptr);
-        });
-        return rcEvents ? rcEvents : rc;
-    }
-    GET_INSTANCE(instance);
-    DEMOTE_FOLDED_TIPS(in);
-    UniformPass pass;
-    int rc = uniformRun(in, nodes, nodeCount, branchTimes, branchRates, nodeHeights, infinitesimalMatrix, categoryRatesIndex,
-                        categoryWeightsIndex, stateFrequenciesIndex, registers, registerFlags, registerCount, simulantCount, seed, flags,
-                        in->P, 0, outStates, outRateCategories, outJumps, outPatternTotals, outRowTotals, outEventCounts, history, &pass);
+    // phase 1: every shard (a plain handle: the instance) draws, simulates and fills its own columns; phase 2: its events after the
+    // earlier shards' events.  The row totals are the shards' sums, added in shard (= pattern) order.
+    std::mutex mu;
+    std::map<int, UniformPass> passes;                              // shard handle -> its pass
+    const int rc = mi355::shardedOrPlain(instance, [&](int h) {
+        Instance* in = nullptr;
+        int globalP = 0, pStart = 0;
+        int r = samplerInstance(instance, h, &in, &globalP, &pStart); if (r) return r;
+        UniformPass pass;
+        r = uniformRun(in, nodes, nodeCount, branchTimes, branchRates, nodeHeights, infinitesimalMatrix, categoryRatesIndex,
+                       categoryWeightsIndex, stateFrequenciesIndex, registers, registerFlags, registerCount, simulantCount, seed, flags,
+                       globalP, pStart, outStates, outRateCategories, outJumps, outPatternTotals, outRowTotals != nullptr,
+                       outEventCounts, history, &pass);
+        std::lock_guard<std::mutex> lock(mu);
+        passes[h] = std::move(pass);
+        return r;
+    });
     if (rc != BEAGLE_SUCCESS && rc != BEAGLE_ERROR_FLOATING_POINT) return rc;
-    if (outEventTotal) *outEventTotal = pass.events;
-    if (outFallbacks) *outFallbacks = pass.fallbacks;
-    if (!wantEvents) return rc;
-    if (pass.events > eventCapacity) return BEAGLE_ERROR_OUT_OF_RANGE;
-    const int rcEvents = uniformEvents(in, &pass, outEventHeights, outEventStates);
-    return rcEvents ? rcEvents : rc;
+    const mi355::ShardParts order = mi355::orderedParts(passes);
+    if (outRowTotals) mi355::sumRowTotals(order, (size_t)registerCount * nodeCount, outRowTotals);
+    long long fallbacks = 0;
+    for (const auto& o : order) fallbacks += passes[o.first].fallbacks;
+    if (outFallbacks) *outFallbacks = fallbacks;
+    return mi355::placeEvents(instance, order, wantEvents, eventCapacity, outEventTotal, rc, [&](int h, long long first) {
+        GET_INSTANCE(h);
+        return uniformEvents(in, passes[h], outEventHeights ? outEventHeights + first : nullptr,
+                             outEventStates ? outEventStates + 2 * first : nullptr);
+    });
 }
 
 }  // extern "C"

@@ -624,8 +624,9 @@ int  jumpSiteBlocks(int P);                  // workgroups of launchJumpSites (r
 void launchJumpSites(hipStream_t stream, const JumpRow* dRows, int nRows, int r0, int r1, const uint8_t* states, const int* cats,
                      const double* cond, int K, int S, int C, int P, double* jumps, double* patternTotals, double* blockPartials,
                      unsigned* fpError);
-// out[k][r] = sum of blockPartials[.][k][r] over `blocks` workgroups in ascending order
-void launchJumpRowTotals(hipStream_t stream, const double* blockPartials, int blocks, int K, int nRows, double* out);
+// out[k][r] = sum of blockPartials[.][k][r] over `blocks` workgroups in ascending order; rows below firstRow: 0 (every sampler's
+// per-workgroup sums: Markov jumps, uniformized jumps, robust counts, unconditioned counts)
+void launchBlockTotals(hipStream_t stream, const double* blockPartials, int blocks, int K, int nRows, int firstRow, double* out);
 // ---- codon robust counts (kernels_robustcounts.hip; beagleMi355RobustCounts, beagleMi355SimulateUnconditionedCounts) --------
 constexpr int ROBUST_STATES = 64;              // the 4 x 4 x 4 product chain
 constexpr int ROBUST_MAX_JUMPS = 100000;       // changes after which an unconditioned history is given up (header)
@@ -647,8 +648,6 @@ void launchRobustTables(hipStream_t stream, const RobustRow* dRows, int nRows, c
 void launchRobustSites(hipStream_t stream, const RobustRow* dRows, int nRows, int r0, int r1, const uint8_t* s0, const uint8_t* s1,
                        const uint8_t* s2, const double* cond, int K, int P, double* counts, double* siteTotals,
                        double* blockPartials, unsigned* fpError);
-// out[k][r] = sum of blockPartials[.][k][r] over `blocks` workgroups in ascending order; rows below firstRow: 0
-void launchRobustTotals(hipStream_t stream, const double* blockPartials, int blocks, int K, int nRows, int firstRow, double* out);
 int  unconditionedBlocks(int siteCount);      // workgroups per length row of launchUnconditioned
 // one unconditional Gillespie history per (length row in [l0, l1), site): values [K][l1-l0][siteCount] (may be nullptr),
 // blockPartials [unconditionedBlocks][K][lengthCount]; *fpError |= 1 for a draw that failed, |= 4 for a history cut at ROBUST_MAX_JUMPS

@@ -33,14 +33,7 @@ namespace mi355 {
 namespace {
 
 using draw::ancestralUniform;
-
-// SplitMix64's output for `key` from `state`, as a 64-bit integer (the stream of one history)
-__device__ __forceinline__ unsigned long long mix64(unsigned long long state, unsigned long long key) {
-    unsigned long long z = state + (key + 1ull) * 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
+using draw::mix64;                           // (the stream of one history)
 
 constexpr unsigned long long HISTORY_SALT = 0x3C6EF372FE94F82Bull;
 

@@ -9,13 +9,14 @@
 // Three stages: the registers (k_jumpRegisters: Q, rateReg_k, M_k = U^-1 rateReg_k U), the conditional tables
 // Cond[k][r][c][S][S] = (U ((A o M_k) U^-1)) / P_r[c] (k_jumpMatrices*: one per (register, row, category)), and the per-site
 // gather (k_jumpSites: one thread per pattern walks the rows; per-row totals through a fixed reduction tree, then
-// k_jumpRowTotals over the workgroups in ascending order).  No float atomics: two identical calls give identical bits.
+// k_blockTotals over the workgroups in ascending order).  No float atomics: two identical calls give identical bits.
 //
 // Every product is rounded on its own (no FMA contraction in this file) and every sum runs over its index in ascending order
 // from 0.0, as the host restatement (tests/markov_jumps_reference.py) forms it: the two differ only where exp() does.
 #pragma clang fp contract(off)
 
 #include "kernels.h"
+#include "jump_aux.h"
 
 namespace mi355 {
 
@@ -63,11 +64,6 @@ __global__ __launch_bounds__(256) void k_jumpRegisters(const double* __restrict_
         for (int a = 0; a < S; a++) s = s + Ui[(size_t)i * S + a] * tk[(size_t)a * S + j];
         mk[e] = s;
     }
-}
-
-// A[a][b] of Minin & Suchard eq. 37 (MarkovJumpsCore.populateAuxInt) from ea = exp(lambda_a tau), eb = exp(lambda_b tau)
-__device__ __forceinline__ double auxInt(double la, double lb, double ea, double eb, double tau) {
-    return fabs(la - lb) < 1e-7 ? ea * tau : (ea - eb) / (la - lb);
 }
 
 // What a (k, r, c) shares: tau, the scale divisor, the zero-rate rule.  Returns false when rate_c <= 0 (the table is then 0, or
@@ -305,14 +301,14 @@ __global__ __launch_bounds__(256) void k_jumpSites(const JumpRow* __restrict__ r
     if (bad) atomicOr(fpError, 2u);
 }
 
-// out[k][r] = sum over the workgroups of k_jumpSites in ascending order (row 0: 0)
-__global__ __launch_bounds__(256) void k_jumpRowTotals(const double* __restrict__ blockPartials, int blocks, int K, int nRows,
-                                                       double* __restrict__ out) {
+// out[k][r] = sum over the workgroups of a site kernel in ascending order (rows below firstRow: 0)
+__global__ __launch_bounds__(256) void k_blockTotals(const double* __restrict__ blockPartials, int blocks, int K, int nRows,
+                                                     int firstRow, double* __restrict__ out) {
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= K * nRows) return;
     const int k = t / nRows, r = t - k * nRows;
     double s = 0.0;
-    if (r > 0)
+    if (r >= firstRow)
         for (int b = 0; b < blocks; b++) s = s + blockPartials[((size_t)b * K + k) * nRows + r];
     out[t] = s;
 }
@@ -353,9 +349,10 @@ void launchJumpSites(hipStream_t stream, const JumpRow* dRows, int nRows, int r0
                        K, S, C, P, jumps, patternTotals, blockPartials, fpError);
 }
 
-void launchJumpRowTotals(hipStream_t stream, const double* blockPartials, int blocks, int K, int nRows, double* out) {
+void launchBlockTotals(hipStream_t stream, const double* blockPartials, int blocks, int K, int nRows, int firstRow, double* out) {
     const int n = K * nRows;
-    hipLaunchKernelGGL(k_jumpRowTotals, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, blockPartials, blocks, K, nRows, out);
+    hipLaunchKernelGGL(k_blockTotals, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, blockPartials, blocks, K, nRows,
+                       firstRow, out);
 }
 
 }  // namespace mi355

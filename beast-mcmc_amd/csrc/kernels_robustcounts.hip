@@ -10,8 +10,8 @@
 // Four stages for the counts: the registers (k_robustRegisters: rateReg_k = Q o R_k from the SUPPLIED Q, M_k = U^-1 (rateReg_k U)),
 // the conditional tables Cond[k][r][64][64] = (U ((A o M_k) U^-1)) / |U (diag(e^(lambda tau)) U^-1)| (k_robustTables: one
 // workgroup per (register, row), three 64 x 64 operands in 96 KiB of LDS), the per-site gather over three state arrays
-// (k_robustSites: one thread per site walks the rows; per-row totals through a fixed reduction tree) and k_robustTotals over the
-// workgroups in ascending order.  No float atomics: two identical calls give identical bits.
+// (k_robustSites: one thread per site walks the rows; per-row totals through a fixed reduction tree) and k_blockTotals
+// (kernels_markovjumps.hip) over the workgroups in ascending order.  No float atomics: two identical calls give identical bits.
 //
 // Every product is rounded on its own (no FMA contraction in this file) and every sum runs over its index in ascending order
 // from 0.0, as the host restatement (tests/robust_counting_reference.py) forms it: the two differ only where exp() does.
@@ -19,6 +19,7 @@
 
 #include "kernels.h"
 #include "ancestral_draw.h"
+#include "jump_aux.h"
 
 namespace mi355 {
 
@@ -57,11 +58,6 @@ __global__ __launch_bounds__(256) void k_robustRegisters(const double* __restric
         for (int a = 0; a < S64; a++) s = s + Ui[i * S64 + a] * tk[a * S64 + j];
         mk[e] = s;
     }
-}
-
-// A[a][b] of Minin & Suchard eq. 37 (MarkovJumpsCore.populateAuxInt) from ea = exp(lambda_a tau), eb = exp(lambda_b tau)
-__device__ __forceinline__ double auxInt(double la, double lb, double ea, double eb, double tau) {
-    return fabs(la - lb) < 1e-7 ? ea * tau : (ea - eb) / (la - lb);
 }
 
 // One workgroup of 256 threads per (register k, row r >= 1).  LDS: T = A o M_k, Y = diag(e^(lambda tau)) U^-1, X = T U^-1, each
@@ -195,26 +191,6 @@ __global__ __launch_bounds__(256) void k_robustSites(const RobustRow* __restrict
     if (bad) atomicOr(fpError, 2u);
 }
 
-// out[k][r] = sum over the workgroups in ascending order (rows below firstRow: 0)
-__global__ __launch_bounds__(256) void k_robustTotals(const double* __restrict__ blockPartials, int blocks, int K, int nRows,
-                                                      int firstRow, double* __restrict__ out) {
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t >= K * nRows) return;
-    const int k = t / nRows, r = t - k * nRows;
-    double s = 0.0;
-    if (r >= firstRow)
-        for (int b = 0; b < blocks; b++) s = s + blockPartials[((size_t)b * K + k) * nRows + r];
-    out[t] = s;
-}
-
-// SplitMix64's output for `key` from `state`, as a 64-bit integer (the stream of one history)
-__device__ __forceinline__ unsigned long long mix64(unsigned long long state, unsigned long long key) {
-    unsigned long long z = state + (key + 1ull) * 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
 // One thread per (length row l = l0 + blockIdx.y, site); `values` (may be nullptr) holds rows lBase .. lBase + lRows - 1: StateHistory.simulateUnconditionalOnEndingState from a start state drawn
 // from `freqs`.  Q sits in LDS; the registers are read where a jump lands.  u_0: start state; u_(2m+1): waiting time m;
 // u_(2m+2): the state after it.
@@ -238,7 +214,7 @@ __global__ __launch_bounds__(256) void k_unconditioned(const double* __restrict_
     unsigned flag = 0;
     if (live) {
         const double length = lengths[l];
-        const unsigned long long z = mix64(seed ^ 0xBB67AE8584CAA73Bull, (unsigned long long)l * (unsigned long long)siteCount + s);
+        const unsigned long long z = draw::mix64(seed ^ 0xBB67AE8584CAA73Bull, (unsigned long long)l * (unsigned long long)siteCount + s);
         bool bad = false;
         int cur = draw::drawChoice([&](int i) { return freqs[i]; }, S, draw::ancestralUniform(z, 0), false, bad);
         if (bad) flag |= 1u;
@@ -299,12 +275,6 @@ void launchRobustSites(hipStream_t stream, const RobustRow* dRows, int nRows, in
                        double* blockPartials, unsigned* fpError) {
     hipLaunchKernelGGL(k_robustSites, dim3((unsigned)jumpSiteBlocks(P)), dim3(256), 0, stream, dRows, nRows, r0, r1, s0, s1, s2, cond,
                        K, P, counts, siteTotals, blockPartials, fpError);
-}
-
-void launchRobustTotals(hipStream_t stream, const double* blockPartials, int blocks, int K, int nRows, int firstRow, double* out) {
-    const int n = K * nRows;
-    hipLaunchKernelGGL(k_robustTotals, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, blockPartials, blocks, K, nRows,
-                       firstRow, out);
 }
 
 int unconditionedBlocks(int siteCount) { return (siteCount + 255) / 256; }

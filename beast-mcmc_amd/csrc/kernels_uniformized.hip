@@ -15,7 +15,7 @@
 //   k_uniformPatternTotals  one thread per pattern adds the chunk's rows in row order onto the running totals;
 //   k_eventRowOffsets + k_eventPatternScan  exclusive offsets of every (row, pattern)'s events in (pattern, row) order;
 //   k_uniformSites<WRITE>   the same histories again (the draws are keyed, so nothing is stored in between), their events written.
-// The row totals are launchJumpRowTotals' (kernels_markovjumps.hip) over the per-workgroup sums.
+// The row totals are launchBlockTotals' (kernels_markovjumps.hip) over the per-workgroup sums.
 //
 // A history never needs a per-thread array: the n + 1 exponential spacings whose running sums give the jump times are summed
 // once for the total and recomputed from the keyed stream on the walk.  No float atomics; every product is rounded on its own (no
@@ -64,10 +64,7 @@ __global__ __launch_bounds__(256) void k_uniformPowers(double* __restrict__ tabl
 
 // The stream of one (simulant, row, pattern): SplitMix64's output for key, from seed ^ 0x6A09E667F3BCC909, as a 64-bit state
 __device__ __forceinline__ unsigned long long historyStream(unsigned long long seed, unsigned long long key) {
-    unsigned long long z = (seed ^ 0x6A09E667F3BCC909ull) + (key + 1ull) * 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
+    return draw::mix64(seed ^ 0x6A09E667F3BCC909ull, key);
 }
 
 __device__ __forceinline__ double spacing(unsigned long long z, int q) { return -log(1.0 - ancestralUniform(z, (unsigned long long)q)); }

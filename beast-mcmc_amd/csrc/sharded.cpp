@@ -30,6 +30,7 @@
 #include <cstring>
 #include <deque>
 #include <functional>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -344,6 +345,30 @@ int shardedSumDoubles(int handle, int len, const std::function<int(int shardHand
     if (rc) return rc;
     for (int q = 0; q < len; q++) { double a = 0.0; for (int k = 0; k < n; k++) a += part[k][q]; outSum[q] = a; }
     return BEAGLE_SUCCESS;
+}
+
+void sortParts(ShardParts& parts) {
+    std::sort(parts.begin(), parts.end(), [](const ShardParts::value_type& a, const ShardParts::value_type& b) {
+        return std::make_pair(a.second->start, a.first) < std::make_pair(b.second->start, b.first);
+    });
+}
+void sumRowTotals(const ShardParts& ordered, size_t n, double* out) {
+    for (size_t i = 0; i < n; i++) {
+        double s = ordered[0].second->rowTotals[i];
+        for (size_t q = 1; q < ordered.size(); q++) s = s + ordered[q].second->rowTotals[i];
+        out[i] = s;
+    }
+}
+int placeEvents(int handle, const ShardParts& ordered, bool wanted, long long capacity, long long* outTotal, int rc,
+                const std::function<int(int shardHandle, long long first)>& write) {
+    long long total = 0;
+    std::map<int, long long> first;
+    for (const auto& o : ordered) { first[o.first] = total; total += o.second->events; }
+    if (outTotal) *outTotal = total;
+    if (!wanted) return rc;
+    if (total > capacity) return BEAGLE_ERROR_OUT_OF_RANGE;
+    const int rcWrite = shardedOrPlain(handle, [&](int h) { return write(h, first.at(h)); });
+    return rcWrite ? rcWrite : rc;
 }
 
 void shardedBounds(int handle, int shard, int* pStart, int* pEnd) {

@@ -2,6 +2,8 @@
 #pragma once
 #include <functional>
 #include <mutex>
+#include <utility>
+#include <vector>
 
 #include "../../include/beagle_mi355.h"
 
@@ -30,6 +32,10 @@ void shardedBoundsOfHandle(int handle, int shardHandle, int* pStart, int* pEnd);
 
 // the same call on every shard (each on its own host thread); first error wins
 int shardedBroadcast(int handle, const std::function<int(int shardHandle)>& call);
+// ... and a plain handle's call on the handle itself, for entry points whose two paths differ in nothing else
+inline int shardedOrPlain(int handle, const std::function<int(int shardHandle)>& call) {
+    return isShardedHandle(handle) ? shardedBroadcast(handle, call) : call(handle);
+}
 // the same call, answered by ONE shard — whichever arrives first; the others return 0 — for what every shard would answer alike (a
 // matrix, the counters of programs every shard runs the same way)
 template <class Call>
@@ -54,6 +60,25 @@ int shardedRootReduce(int handle, int count, const std::function<int(int shardHa
 // per-shard host vectors of `len` doubles that add up
 int shardedSumDoubles(int handle, int len, const std::function<int(int shardHandle, double* out)>& call, double* outSum);
 
+// What one shard (or the one instance of a plain handle) leaves of a sampler's call for the merge: where its part starts (first
+// pattern or site), its row totals, how many events it will write.
+struct ShardPart { int start = 0; long long events = 0; std::vector<double> rowTotals; };
+using ShardParts = std::vector<std::pair<int, const ShardPart*>>;      // (shard handle, its part)
+void sortParts(ShardParts& parts);             // ascending start
+template <class Map>                           // shard handle -> a ShardPart, or what derives from one
+ShardParts orderedParts(const Map& byHandle) {
+    ShardParts parts;
+    for (const auto& e : byHandle) parts.emplace_back(e.first, &e.second);
+    sortParts(parts);
+    return parts;
+}
+// out[i] = the parts' rowTotals[i] added in that order: s = p[0]; s = s + p[q] ...
+void sumRowTotals(const ShardParts& ordered, size_t n, double* out);
+// Every part's events go behind the earlier parts': *outTotal (nullable) = their number; then, when the list is wanted, it must fit
+// `capacity` (BEAGLE_ERROR_OUT_OF_RANGE) and write(shard handle, its first event) runs on every shard (a plain handle: called once).
+// rc: what the first phase returned, returned again unless writing fails.
+int placeEvents(int handle, const ShardParts& ordered, bool wanted, long long capacity, long long* outTotal, int rc,
+                const std::function<int(int shardHandle, long long first)>& write);
 
 // engine_root.cpp, for the reduction above: `count` doubles at device address dValues of (single-GPU) instance `instance` go to
 // the host through the instance's mapped result words — one small kernel behind whatever is on the instance's stream, then a

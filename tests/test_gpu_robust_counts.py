@@ -331,6 +331,24 @@ def test_unconditioned_equals_the_restatement(name, sites):
     tl.close()
 
 
+def test_unconditioned_stage_smaller_than_the_lengths():
+    """Two length rows of 2^24 + 256 sites are more than the 256 MiB stage holds: the counts leave in two launches of one row each.
+    A 0/1 register's values are whole numbers, so every sum of them is exact: the totals of the call without counts (one launch over
+    both rows) are the counts' sums, and row 0 is the one-row call's (its streams are keyed on l * sites + s: the same keys)."""
+    Q, pi, _ = cases.unconditioned_cases()["hky4"]
+    regs = np.ones((1, 4, 4))
+    sites, lengths = (1 << 24) + 256, [0.05, 0.02]
+    tl = BeagleTreeLikelihood(helpers.random_workload(4, 8, 4, 1, seed=1))
+    b = bm.beagle.Beagle.attach(tl)
+    res = b.simulateUnconditionedCounts(Q, pi, lengths, sites, regs, 77)
+    only = b.simulateUnconditionedCounts(Q, pi, lengths, sites, regs, 77, counts=False)
+    first = b.simulateUnconditionedCounts(Q, pi, lengths[:1], sites, regs, 77)
+    assert np.array_equal(res["totals"], only["totals"]) and np.array_equal(res["counts"].sum(axis=2), only["totals"])
+    assert res["totals"][0, 0] > res["totals"][0, 1] > 0.0
+    assert np.array_equal(res["counts"][:, 0], first["counts"][:, 0])
+    tl.close()
+
+
 def test_unconditioned_through_the_veneer_and_error_codes():
     case = Case(8, 300, seed=2)
     case.rc.registers = case.rc.registers[:2]
