@@ -124,7 +124,7 @@ ABI_SYMBOLS = ["beagleGetVersion", "beagleGetCitation", "beagleGetResourceList",
               ["beagle" + k for k in _PROTOS] + \
               ["beagleMi355SetStream", "beagleMi355CalculateRootLogLikelihoodsDevice", "beagleMi355Synchronize",
                "beagleMi355KernelTimer", "beagleMi355DeviceBytes", "beagleMi355WalkStats", "beagleMi355GradientStats", "beagleMi355GetPartialsBatch", "beagleMi355SampleAncestralStates", "beagleMi355SampleMarkovJumps", "beagleMi355SampleMarkovJumpsUniformized",
-               "beagleMi355SimulateSequences", "beagleMi355SimulateCompleteHistories", "beagleMi355RobustCounts", "beagleMi355SimulateUnconditionedCounts", "beagleMi355NodeHeightDerivatives", "beagleMi355SetTipEmission", "beagleMi355TipEmissionStats",
+               "beagleMi355SimulateSequences", "beagleMi355SimulateCompleteHistories", "beagleMi355RobustCounts", "beagleMi355SimulateUnconditionedCounts", "beagleMi355NodeHeightDerivatives", "beagleMi355UpdateDifferentialMatrices", "beagleMi355SetTipEmission", "beagleMi355TipEmissionStats",
                "beagleMi355GetPartialsPinned", "beagleMi355GetSiteLogLikelihoodsPinned",
                "beagleMi355KernelTimerCalls", "beagleMi355WalkHealth", "beagleMi355RepeatStats", "beagleMi355WalkLaunchInfo", "beagleMi355RootFusedCount", "beagleMi355SitePrefetchCount", "beagleMi355KernelTimerRestart", "beagleMi355GetDimensions", "beagleMi355GetCommUniqueId", "beagleMi355CommInit", "beagleMi355CommInfo", "beagleMi355CalculateRootLogLikelihoodsAllReduce"] + \
               ["beagleBasta" + k for k in ("AllocateCoalescentBuffers", "UpdatePartials", "AccumulatePartials", "GetBuffer", "GetBufferLength", "Stats",
@@ -669,6 +669,24 @@ class Beagle:
         f = self._ext("beagleMi355NodeHeightDerivatives", [C.c_int, _IP, _DP, C.c_int, C.c_int, _DP, _DP])
         self._check("nodeHeightDerivatives", f(self.instance, _ip(rows), _dp(r), n, categoryWeightsIndex, _dp(o1), _dp(o2)))
         return o1, o2
+
+    DIFFERENTIAL_EXACT, DIFFERENTIAL_FIRST_ORDER = 0, 1
+
+    def updateDifferentialMatrices(self, eigenIndices, categoryRatesIndices, differentials, differentialIndices, matrixIndices,
+                                   edgeLengths, count=None, mode=0):
+        """The differential matrix of every listed branch and category, formed on the device in one call (include/beagle_mi355.h
+        beagleMi355UpdateDifferentialMatrices).  ``differentials`` [D][S][S]: dQ / d theta; per branch its eigen system, rate set
+        and differential (each None: 0 for all), the matrix slot it writes and length x clock rate; ``mode``: DIFFERENTIAL_EXACT
+        (D = U (V o Phi) U^-1, so that dP / d theta = P D) or DIFFERENTIAL_FIRST_ORDER (D = dist x dQ)."""
+        S = self.stateCount
+        q = _d(differentials).reshape(-1, S, S)
+        e, r, d, m, t = _i(eigenIndices), _i(categoryRatesIndices), _i(differentialIndices), _i(matrixIndices), _d(edgeLengths)
+        n = m.size if count is None else int(count)
+        for a in (e, r, d, m, t):
+            if a is not None and a.size < n:
+                raise ValueError("every per-branch list must have one entry per branch")
+        f = self._ext("beagleMi355UpdateDifferentialMatrices", [C.c_int, _IP, _IP, _DP, C.c_int, _IP, _IP, _DP, C.c_int, C.c_int])
+        self._check("updateDifferentialMatrices", f(self.instance, _ip(e), _ip(r), _dp(q), q.shape[0], _ip(d), _ip(m), _dp(t), n, int(mode)))
 
     def sampleMarkovJumps(self, nodes, branchTimes, branchRates, eigenIndex, categoryRatesIndex, categoryWeightsIndex,
                           stateFrequenciesIndex, registers, registerFlags, seed, map=False, states=False, jumps=False,

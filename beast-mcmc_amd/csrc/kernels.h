@@ -322,6 +322,20 @@ void launchConvolveMatrices(hipStream_t stream, double* matrices, const int* dFi
 // C_c = A_c + B_c per category (a result may be one of its own operands: entry by entry)
 void launchAddMatrices(hipStream_t stream, double* matrices, const int* dFirst, const int* dSecond, const int* dResult, int count, int S, int C);
 
+// ---- substitution-parameter differential matrices (kernels_differential.hip; beagleMi355UpdateDifferentialMatrices) ---------
+// V = U^-1 dQ U for `pairCount` (eigen system, differential) pairs, entries with |V_ij| < 1e-10 set to 0: dPairs holds {eigen index,
+// differential index} per pair, dQ the call's differentials [.][S][S], V receives [pairCount][S][S].  S <= 64.
+void launchDifferentialRotate(hipStream_t stream, double* V, const double* eigen, const double* dQ, const int* dPairs, int pairCount,
+                              int S, bool complexEigen);
+// slot dIdx[u], category c = U (V[dPair[u]] o Phi(dLen[u] * rate(c))) U^-1 for `count` branches (device arrays of that length: slot,
+// length, eigen index, rate set, pair).  One thread per (branch, category) up to 8 states, one workgroup from 9 to 64.
+void launchDifferentialExact(hipStream_t stream, double* matrices, const double* eigen, const double* rates, const double* V,
+                             const int* dIdx, const double* dLen, const int* dEig, const int* dRate, const int* dPair,
+                             int count, int S, int C, bool complexEigen);
+// slot dIdx[u], category c = dLen[u] * rate(c) * dQ[dDiff[u]]
+void launchDifferentialFirstOrder(hipStream_t stream, double* matrices, const double* rates, const double* dQ, const int* dIdx,
+                                  const double* dLen, const int* dRate, const int* dDiff, int count, int S, int C);
+
 // One dependency level of pruning operations: `nOps` independent ops, descriptors on the device.
 // maxRange = max over ops of (pEnd - pStart).
 void launchPruneLevel(hipStream_t stream, const OpDesc* dOps, int nOps, const double* matrices,

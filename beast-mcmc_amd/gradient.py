@@ -17,8 +17,12 @@ from . import beagle as _b
 class BranchGradient:
     """One full evaluation = post-order partials, root lnL, pre-order partials, d lnL / d(branch length) per node."""
 
-    def __init__(self, workload, library=None, rescale=False, resource_list=(1,), double_buffer=False):
-        """double_buffer: lay the post-order partials and the branch matrices out in two sets and alternate between them from
+    def __init__(self, workload, library=None, rescale=False, resource_list=(1,), double_buffer=False, extra_matrices=0,
+                 eigen_count=1, requirement_flags=0):
+        """extra_matrices: matrix slots behind the two differential slots, first at ``extra_index`` (substgradient.py keeps one
+        differential matrix per branch there); eigen_count, requirement_flags: as the instance is created (eigen system 0 is the
+        workload's).
+        double_buffer: lay the post-order partials and the branch matrices out in two sets and alternate between them from
         one evaluation to the next, as BufferIndexHelper does for the reference (BufferIndexHelper.java:65-85 index = i + 0 or
         i + doubleBufferCount; BeagleDataLikelihoodDelegate.java:853 flipOffset per updated node; a gradient chain updates
         every node, so here the whole set flips)."""
@@ -39,8 +43,10 @@ class BranchGradient:
         # scale buffers: one per internal node and the cumulative one; with double buffering two such sets, flipped together with
         # the partials (BeagleDataLikelihoodDelegate.java:237 scaleBufferHelper, :874 / :917 flipOffset)
         self._scale_set = internal + 1 if (double_buffer and rescale) else 0
-        self.b = _b.Beagle(self.T, self.pre_offset + self.N, self.T, self.S, self.P, 1, matrices + 2, self.C,
-                           ((2 if double_buffer else 1) * (internal + 1) if rescale else 0), resourceList=resource_list, library=library)
+        self.extra_index = matrices + 2
+        self.b = _b.Beagle(self.T, self.pre_offset + self.N, self.T, self.S, self.P, eigen_count, matrices + 2 + extra_matrices, self.C,
+                           ((2 if double_buffer else 1) * (internal + 1) if rescale else 0), resourceList=resource_list,
+                           requirementFlags=requirement_flags, library=library)
         for t in range(self.T):
             self.b.setTipStates(t, wl.tip_states[t])
         self.b.setPatternWeights(wl.weights)

@@ -136,15 +136,13 @@ def _codons():
     return out
 
 
-def gy94(kappa, omega, codon_pi=None):
-    """GY94CodonModel.java:165-188: rate 0 for multi-position changes, kappa for synonymous
-    transitions, 1 for synonymous transversions, kappa*omega / omega for the non-synonymous ones;
-    Q_ij = rate * pi_j."""
+def gy94_rates(kappa, omega):
+    """GY94CodonModel.java:165-188, the 61 * 60 / 2 relative rates in upper-triangle order: 0 for multi-position changes, kappa for
+    synonymous transitions, 1 for synonymous transversions, kappa*omega / omega for the non-synonymous ones (affine in kappa and
+    in omega)."""
     cods = _codons()
     s = len(cods)
     assert s == 61
-    if codon_pi is None:
-        codon_pi = np.full(s, 1.0 / s)
     purines = set("AG")
     rates = []
     for i in range(s):
@@ -161,7 +159,14 @@ def gy94(kappa, omega, codon_pi=None):
             if ai != aj:
                 r *= omega
             rates.append(r)
-    q = reversible_q(rates, codon_pi)
+    return rates
+
+
+def gy94(kappa, omega, codon_pi=None):
+    """The GY94 codon model over the 61 sense codons: Q_ij = rate * pi_j with the rates of ``gy94_rates``."""
+    if codon_pi is None:
+        codon_pi = np.full(61, 1.0 / 61)
+    q = reversible_q(gy94_rates(kappa, omega), codon_pi)
     return decompose_reversible(q, codon_pi), np.asarray(codon_pi, dtype=np.float64)
 
 

@@ -410,6 +410,37 @@ int beagleMi355SimulateSequences(int instance, const int* nodes, int nodeCount, 
  * result is not finite — the outputs are still written.  An extension: no BEAST class calls it today. */
 int beagleMi355NodeHeightDerivatives(int instance, const int* nodes, const double* rates, int nodeCount, int categoryWeightsIndex,
                                      double* outFirst, double* outSecond);
+/* Substitution-parameter gradients: the "differential mass matrix" of every listed branch and rate category, formed on the device in
+ * ONE call — what BranchSubstitutionParameterDelegate.cacheDifferentialMassMatrix (BranchSubstitutionParameterDelegate.java:62-81),
+ * HomogeneousSubstitutionParameterGradient and ArbitrarySubstitutionGeneratorGradient form per branch on the host with
+ * DifferentiableSubstitutionModelUtil.getExactDifferentialMassMatrix (DifferentiableSubstitutionModelUtil.java:57-171) and upload with a
+ * beagleSetDifferentialMatrix per branch.  beagleCalculateEdgeDifferentials over the written slots then yields d lnL / d theta per branch.
+ *   eigenIndices, categoryRatesIndices [count]: the branch's eigen system and rate set; NULL = 0 for every branch.
+ *   inDifferentials [differentialCount][S][S], row-major: dQ / d theta of every parameter (and model) of the call.
+ *   differentialIndices [count]: which of them the branch uses; NULL = 0 for every branch.
+ *   matrixIndices [count]: the slot of the transition-matrix pool that receives the branch's C matrices, category-major as
+ *          beagleSetDifferentialMatrix takes them; no slot twice in one call.
+ *   edgeLengths [count]: branch length x clock rate.  With dist = edgeLengths[k] x rate(c) of the branch's rate set:
+ * BEAGLE_MI355_DIFFERENTIAL_EXACT: D = U (V o Phi) U^-1 with V = U^-1 dQ U, entries of V with |V_ij| < 1e-10 set to 0 (the reference's
+ *   setZeros), Phi_ij = dist where i = j or |lambda_i - lambda_j| < 1e-10, otherwise (1 - exp((lambda_j - lambda_i) dist)) /
+ *   (lambda_i - lambda_j), and 0 where V_ij is 0: then dP / d theta = P D.  On an EIGEN_COMPLEX instance the 2 x 2 blocks of conjugate pairs
+ *   (real-complex, complex-real, complex-complex and its special case of equal pairs) follow lines 88-160 of the same file with the
+ *   exp-cosine and exp-sine integrals of lines 210-222; pairs are found as beagleUpdateTransitionMatrices finds them.
+ * BEAGLE_MI355_DIFFERENTIAL_FIRST_ORDER: D = dist x dQ.
+ * (The reference's affine-corrected form is not offered: its rule hangs on an eigenvalue being exactly 0.0.)
+ * V is formed once per distinct (eigen system, differential) pair of the call; every sum runs over its index in ascending order, so a
+ * slot receives the same bits whatever else the call lists, in whatever order, and on every shard.  Writing a slot does for it what
+ * beagleSetTransitionMatrix does; a held-back pre-order list runs first only if it reads one of the written slots.  The sharded handle
+ * gives the call to every shard (matrices are replicated).
+ * BEAGLE_ERROR_OUT_OF_RANGE for a bad index, a slot named twice, another mode, differentialCount < 1, inDifferentials, matrixIndices or
+ * edgeLengths NULL with count > 0, and for arguments that exceed half the 16 MiB staging ring;
+ * BEAGLE_ERROR_NO_IMPLEMENTATION with more than 64 states and on a BASTA instance.  count <= 0: success, nothing is launched.
+ * An extension: no BEAST class calls it today. */
+#define BEAGLE_MI355_DIFFERENTIAL_EXACT        0
+#define BEAGLE_MI355_DIFFERENTIAL_FIRST_ORDER  1
+int beagleMi355UpdateDifferentialMatrices(int instance, const int* eigenIndices, const int* categoryRatesIndices,
+                                          const double* inDifferentials, int differentialCount, const int* differentialIndices,
+                                          const int* matrixIndices, const double* edgeLengths, int count, int mode);
 /* Markov jumps: ONE call that draws the ancestral states as beagleMi355SampleAncestralStates does and, for every register k, row
  * r >= 1 and pattern p, forms the expected number of registered substitutions (a count register) or the expected reward (a reward
  * register) on row r's branch, conditioned on the drawn parent and child states — what MarkovJumpsBeagleTreeLikelihood.hookCalculation
