@@ -220,12 +220,19 @@ int beagleCreateInstance(int tipCount, int partialsBufferCount, int compactBuffe
     // with hold slots, where a store is what an evaluation waits for (buffers of 2 MiB and more: the definition cap of 24); one
     // partition (the planner's users list of a stored operand is per buffer); not the gradient chain (planner.h stepLimit).  The T32 /
     // T64 walks (16..64 states) keep every such node stored.  BEAGLE_MI355_NO_MEM_DEFS=1: off;  BEAGLE_MI355_MEM_DEF_STEPS=n: the
-    // cap, on any 4-state walk instance (0: off).
+    // cap, on any 4-state walk instance (0: off).  A full evaluation whose list has come before — the steady state of a chain of model
+    // moves — is planned under the definition cap, 24: 43 stored nodes per evaluation of config A instead of 59 (planner.h memStepCapSeen,
+    // profiles/table_reuse.txt); BEAGLE_MI355_MEM_DEF_SEEN_STEPS=n: that cap (at or below the other: one cap for every list, which
+    // BEAGLE_MI355_MEM_DEF_STEPS alone asks for too).
     {
-        int memSteps = maxVirtSteps == 24 ? MEM_DEF_STEPS : 0;
-        if (getenv("BEAGLE_MI355_MEM_DEF_STEPS")) memSteps = std::max(0, std::min(maxVirtSteps, atoi(getenv("BEAGLE_MI355_MEM_DEF_STEPS"))));
-        if (switchOn("BEAGLE_MI355_NO_MEM_DEFS") || !in->walk || in->walkT || !virtualOn || in->holdSlots < 2) memSteps = 0;
+        int memSteps = maxVirtSteps == 24 ? MEM_DEF_STEPS : 0, seenSteps = maxVirtSteps == 24 ? MEM_DEF_SEEN_STEPS : 0;
+        if (getenv("BEAGLE_MI355_MEM_DEF_STEPS")) { memSteps = std::max(0, std::min(maxVirtSteps, atoi(getenv("BEAGLE_MI355_MEM_DEF_STEPS")))); seenSteps = 0; }
+        if (getenv("BEAGLE_MI355_MEM_DEF_SEEN_STEPS")) seenSteps = std::max(0, std::min(maxVirtSteps, atoi(getenv("BEAGLE_MI355_MEM_DEF_SEEN_STEPS"))));
+        if (switchOn("BEAGLE_MI355_NO_MEM_DEFS") || !in->walk || in->walkT || !virtualOn || in->holdSlots < 2) memSteps = seenSteps = 0;
         in->planner.memStepCap = memSteps;
+        in->planner.memStepCapSeen = seenSteps;
+        // (a definition longer than this that a list only reads is stored when it is first read: engine_internal.h memDefInlineSteps)
+        if (getenv("BEAGLE_MI355_MEM_DEF_INLINE_STEPS")) in->memDefInlineSteps = std::max(0, atoi(getenv("BEAGLE_MI355_MEM_DEF_INLINE_STEPS")));
     }
     // Repeated sub-patterns (engine_internal.h repeatsOn): where a node's vector is long enough for the arithmetic to be what an
     // evaluation costs — the gate of the memory definitions —; BEAGLE_MI355_REPEATS_ANY_SIZE=1: on any 4-state walk instance;

@@ -67,6 +67,8 @@ constexpr int SLAB_BUFFERS = 32;           // partials buffers per hipMalloc
 constexpr int PRE_SCRATCH = 32;            // pre-order ops per two-pass chunk on the T32 layout
 constexpr int GRADIENT_VIRT_STEPS = 2;     // longest definition a gradient chain can leave unstored (Instance::gradientVirtual)
 constexpr int MEM_DEF_STEPS = 8;           // longest definition over a stored internal node (planner.h memStepCap; engine_create.cpp)
+constexpr int MEM_DEF_SEEN_STEPS = 24;     // ... in the plan of a closed list that has come a second time (planner.h memStepCapSeen)
+constexpr int MEM_DEF_INLINE_STEPS = 8;    // ... and the longest one a list that only READS it evaluates inside its own program (Instance::memDefInlineSteps)
 constexpr int GRADIENT_VIRT_DEFAULT = 1;   // ... and what it does leave unstored by default: nodes over two tips (engine_create.cpp)
 
 struct Basta;                              // engine_basta.cpp
@@ -168,6 +170,13 @@ struct Instance {
     // of the uncompressed list.  repeatSlicingOff: a program cut this way had fewer than half of its definitions' micro-operations
     // compressed (an alignment whose clades exceed the class limit): later lists are cut as uncompressed ones, until new tip states.
     bool repeatSlicing = false, repeatSlicingOff = false;
+    // memDefInlineSteps: a list that reads a memory definition of MORE steps than this without producing its stored operand — a branch move
+    // passing the node as a sibling — gives it real data first, once (runOperationsWalk): every later move reads the node from memory, as
+    // it reads a stored one, and the next full evaluation defines it again.  Shorter ones are evaluated inside the list's own program every
+    // time, as they always were.  BEAGLE_MI355_MEM_DEF_INLINE_STEPS=n at creation (at or above the cap: never).
+    int memDefInlineSteps = MEM_DEF_INLINE_STEPS;
+    int closedListRun = 0;                               // closed lists of 16 operations and more (the planner keeps their plans: read mode or write mode)
+                                                         // planned or replayed since the last list that was not one (planner.h preferSeenCap)
     mi355::RepeatIndex repeatIndex;
     std::vector<std::vector<uint8_t>> hostTips;          // per tip: the state codes as uploaded (what the index is built from)
     long tipDataEpoch = 0, repeatEpoch = -1, repeatCompactEpoch = -1;     // setTipStates calls; what the index and the tables were made under

@@ -1046,9 +1046,11 @@ int runOperationsWalk(Instance* in, const int* ops, int count, int tuple, int gl
     // device (config E, 6 436 operations: 116 -> 35 us of host time per call; profiles/r03_experiments.txt).
     // (a list that will be compressed is cut by what is left of it: planner.h repeatWeights acts on closed lists without rescaling only)
     in->planner.repeatWeights = in->repeatSlicing && !in->repeatSlicingOff && parts == 1 && allowVirtual && in->planner.stepLimit == 0;
+    in->planner.preferSeenCap = in->closedListRun >= 2;
     {
         bool simple = false;
         if (in->planner.replayCached(ops, count, tuple, parts, allowVirtual, walkChunkOps(in, count), &simple)) {
+            in->closedListRun++;
             const double usPlan = usSince(t0);
             in->hostPlanUs += usPlan; in->hostPlanHitUs += usPlan; in->hostHits++;
             const Clock::time_point t1 = Clock::now();
@@ -1090,12 +1092,15 @@ int runOperationsWalk(Instance* in, const int* ops, int count, int tuple, int gl
         }
         std::vector<int> need;
         in->planner.mustMaterializeBefore(sub, n, tuple, need);
+        // (long memory definitions the list only reads — a branch move's siblings — are stored once, not walked by every move that passes them)
+        if (allowVirtual && in->planner.stepLimit == 0) in->planner.longMemoryOperands(sub, n, tuple, in->memDefInlineSteps, need);
         if (!need.empty()) { int rc = materializeList(in, need); if (rc) return rc; }
         in->hostPrepUs += usSince(t1); t1 = Clock::now();
         const long hitsBefore = in->planner.cacheHits;
         int rc = in->planner.plan(sub, n, tuple, parts, allowVirtual, in->plan, walkChunkOps(in, n));
         if (rc) return rc;
         const bool hit = in->planner.cacheHits != hitsBefore;
+        in->closedListRun = in->planner.plannedTag ? in->closedListRun + 1 : 0;
         double usPlanThis = 0.0;
         { const double us = usSince(t1); usPlanThis = us; in->hostPlanUs += us; if (hit) { in->hostPlanHitUs += us; in->hostHits++; } }
         t1 = Clock::now();

@@ -128,7 +128,7 @@ bool WalkPlanner::buildVirtual(int X, int c1, bool tip1, bool mem1, int m1, int 
         last.need = std::min(std::max(na, 1 + nb), std::max(nb, 1 + na));
         if (last.need > maxNeed) return false;
     }
-    if (nv.nSteps >= (nv.memKey >= 0 ? std::min(cap, memStepCap) : cap)) return false;
+    if (nv.nSteps >= (nv.memKey >= 0 ? std::min(cap, memCapNow_) : cap)) return false;
     pairs.push_back(last.originA); pairs.push_back(snapSlot(X, nv.nSteps, 0));
     pairs.push_back(last.originB); pairs.push_back(snapSlot(X, nv.nSteps, 1));
     nv.steps[nv.nSteps++] = last;
@@ -193,6 +193,24 @@ void WalkPlanner::mustMaterializeBefore(const int* ops, int count, int tuple, st
         for (int k = 0; k < count; k++)
             for (int u : tipUsers_[ops[(size_t)k * tuple]])
                 if (wStamp_[u] != stamp_) out.push_back(u);
+}
+
+void WalkPlanner::longMemoryOperands(const int* ops, int count, int tuple, int minSteps, std::vector<int>& out) {
+    if (!enabled_ || memStepCap <= 0 || keyParts_ != 1 || minSteps >= memCapSeen()) return;
+    stamp_++;
+    const size_t nKeys = (size_t)partialsCount_;
+    if (wStamp_.size() < nKeys) { wStamp_.assign(nKeys, 0); rStamp_.assign(nKeys, 0); wOp_.assign(nKeys, 0); }
+    for (int k = 0; k < count; k++) wStamp_[(size_t)ops[(size_t)k * tuple]] = stamp_;
+    for (int k = 0; k < count; k++) {
+        const int* op = ops + (size_t)k * tuple;
+        for (int c : {op[3], op[5]}) {
+            const VirtDef& v = virt_[(size_t)c];
+            // (a child this list writes is redefined by it; a definition whose stored operand the list writes is evaluated behind that
+            // operand's program, or was given real data by mustMaterializeBefore)
+            if (!v.on || v.memKey < 0 || v.nSteps <= minSteps || wStamp_[(size_t)c] == stamp_ || wStamp_[(size_t)v.memKey] == stamp_) continue;
+            if (std::find(out.begin(), out.end(), c) == out.end()) out.push_back(c);
+        }
+    }
 }
 
 // ---- memory definitions (planner.h memStepCap) ---------------------------------------------------------------------
@@ -466,6 +484,7 @@ int WalkPlanner::plan(const int* ops, int count, int tuple, int parts, bool allo
     out.clear();
     planned = &out; plannedTag = 0;
     lastStored = lastMemReads = lastHolds = 0;
+    memCapNow_ = memStepCap;
     if (count <= 0) return 0;
     parts_ = parts;
     const size_t nKeys = (size_t)partialsCount_ * parts, nS = (size_t)scaleCount_ * parts;
@@ -479,12 +498,18 @@ int WalkPlanner::plan(const int* ops, int count, int tuple, int parts, bool allo
     CacheEntry* fill = nullptr;
     bool anyRescale = false;
     lastWeighed = 0;
+    int promoteWay = -1;
     if (cacheEnabled && count >= 16) {
         if (CacheEntry* hit = findCached(ops, count, tuple, parts, allowVirtual, chunkOps)) {
-            stamp_++;
-            replay(*hit, ops);
-            cacheHits++;
-            return 0;                                  // (replay() has set lastWeighed)
+            if (!promotable(*hit, allowVirtual)) {
+                stamp_++;
+                replay(*hit, ops);
+                cacheHits++;
+                return 0;                              // (replay() has set lastWeighed)
+            }
+            hit->valid = false;                        // the list's second coming: planned again under the longer cap (planner.h memStepCapSeen),
+            memCapNow_ = memCapSeen();                 // into the way it had: no other kept plan is evicted for it
+            promoteWay = (int)(hit - cache_);
         }
         bool closed = true, simple = true;
         for (int k = 0; k < count && closed; k++) {
@@ -499,10 +524,14 @@ int WalkPlanner::plan(const int* ops, int count, int tuple, int parts, bool allo
         }
         stamp_++;                                      // the marks above must not look like producers to pass 1
         if (closed) {
-            fill = &cache_[cacheNext_];
-            cacheNext_ = (cacheNext_ + 1) % CACHE_WAYS;
-            fill->valid = false; fill->cleanAtEpoch = -1; fill->tag = ++cacheTagNext_; fill->count = count; fill->tuple = tuple; fill->parts = parts; fill->chunkOps = chunkOps; fill->repeatWeights = repeatWeights;
-            fill->allowVirtual = allowVirtual; fill->stepLimit = allowVirtual ? stepLimit : 0; fill->memStepCap = allowVirtual ? memStepCap : 0; fill->tipEpoch = compactEpoch; fill->simple = simple;
+            if (preferSeenCap) memCapNow_ = memCapSeen();
+            // (a way's tags are 8 g + way + 1, g counted per way: unique, and the tags of the eight ways differ in their low three bits,
+            // which is how the engine finds the program it keeps for a plan — engine_walk.cpp runPlan)
+            const int way = promoteWay >= 0 ? promoteWay : cacheNext_;
+            if (promoteWay < 0) cacheNext_ = (cacheNext_ + 1) % CACHE_WAYS;
+            fill = &cache_[way];
+            fill->valid = false; fill->cleanAtEpoch = -1; fill->tag = ++wayGen_[way] * CACHE_WAYS + way + 1; fill->count = count; fill->tuple = tuple; fill->parts = parts; fill->chunkOps = chunkOps; fill->repeatWeights = repeatWeights;
+            fill->allowVirtual = allowVirtual; fill->stepLimit = allowVirtual ? stepLimit : 0; fill->memStepCap = allowVirtual ? memCapNow_ : 0; fill->tipEpoch = compactEpoch; fill->simple = simple;
             fill->ops.assign(ops, ops + (size_t)count * tuple);
         }
     }
@@ -869,10 +898,15 @@ void WalkPlanner::linkSlices(Plan& out, bool repeatDurations) {
     if ((int)order.size() == n) out.launchOrder = order;
 }
 
+// a kept plan made under the first-sight cap while lists that come again have a longer one
+bool WalkPlanner::promotable(const CacheEntry& e, bool allowVirtual) const {
+    return allowVirtual && e.parts == 1 && e.stepLimit == 0 && e.memStepCap > 0 && e.memStepCap < memCapSeen();
+}
+
 WalkPlanner::CacheEntry* WalkPlanner::findCached(const int* ops, int count, int tuple, int parts, bool allowVirtual, int chunkOps) {
     for (CacheEntry& e : cache_)
         if (e.valid && e.count == count && e.tuple == tuple && e.parts == parts && e.chunkOps == chunkOps && e.allowVirtual == allowVirtual && e.repeatWeights == repeatWeights &&
-            e.stepLimit == (allowVirtual ? stepLimit : 0) && e.memStepCap == (allowVirtual ? memStepCap : 0) &&
+            e.stepLimit == (allowVirtual ? stepLimit : 0) && (e.memStepCap == (allowVirtual ? memStepCap : 0) || e.memStepCap == (allowVirtual ? memCapSeen() : 0)) &&
             e.tipEpoch == compactEpoch && memcmp(e.ops.data(), ops, (size_t)count * tuple * sizeof(int)) == 0)
             return &e;
     return nullptr;
@@ -883,6 +917,7 @@ bool WalkPlanner::replayCached(const int* ops, int count, int tuple, int parts, 
     allowVirtual = allowVirtual && enabled_;
     CacheEntry* e = findCached(ops, count, tuple, parts, allowVirtual, chunkOps);
     if (!e || (simple && !e->simple)) return false;    // (asked for a simple list only: nothing has been touched)
+    if (promotable(*e, allowVirtual)) return false;    // (plan() plans it again: planner.h memStepCapSeen)
     // memory definitions: a simple list skips mustMaterializeBefore, so nothing but this entry's own definitions may read what the list
     // overwrites (a branch move in between leaves such readers behind: that evaluation takes the long way) — looked at only when a
     // definition has changed hands since this entry's last replay

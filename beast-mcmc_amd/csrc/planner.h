@@ -257,6 +257,11 @@ public:
     // rewrites (unless the list redefines them anyway), and a virtual destination that is its own child.
     void mustMaterializeBefore(const int* ops, int count, int tuple, std::vector<int>& out);
 
+    // Memory definitions of more than `minSteps` steps that this (hazard-free) list reads as a child of one of its operations without
+    // writing them or their stored operand: every evaluation of such a list would walk the whole definition, full width, where a stored
+    // node costs one read — the engine gives them real data once instead (engine_internal.h memDefInlineSteps).  Appends KEYS to `out`.
+    void longMemoryOperands(const int* ops, int count, int tuple, int minSteps, std::vector<int>& out);
+
     // Plan a hazard-free list.  Indices must have been range-checked by the caller; partitionCount must be the planner's.
     // `allowVirtual`: destinations may become virtual.  Returns 0, or a BEAGLE error code.
     // `chunkOps` > 0 (few pattern groups, so a launch cannot fill the chip with one walk per group): the forest is cut
@@ -299,6 +304,17 @@ public:
     // One partition, no step limit, a walk with hold slots; a definition that nothing in its list consumes is stored after all (a root).
     // Part of a cached plan's identity.  0 (the default): off.
     int memStepCap = 0;
+    // memStepCapSeen > memStepCap: the cap of a closed list that comes a SECOND time.  A list is planned with memStepCap when it is first
+    // seen — partial updates, which are planned every time, and the full evaluation behind an accepted topology or branch move, whose list is
+    // new, among them: long definitions make the branch moves behind them walk their steps —; when the same closed list comes again (a chain
+    // of model moves alternates between two of them) its cache entry is dropped and the list planned once more under this cap, and that is
+    // the program every later evaluation of the list replays.  0: memStepCap for every list.
+    int memStepCapSeen = 0;
+    // ... and a NEW closed list is planned under the longer cap at once while the caller says that full evaluations are all it has been
+    // asked for lately (the engine: the last two lists were closed ones, of any kind — a chain of model moves whose scale buffers have just
+    // flipped meets new lists too, and the write-mode list of the flip is one of the two)
+    bool preferSeenCap = false;
+    int memCapSeen() const { return memStepCapSeen > memStepCap && memStepCap > 0 ? memStepCapSeen : memStepCap; }
     // repeatWeights: the engine will take this list's plain definitions — every leaf a compact tip — from class tables (RepeatIndex,
     // emitRepeatPlan), so pass 2 weighs such a definition as what it leaves in the walk, ONE gather on its consumer, not as its steps, and
     // linkSlices' schedule simulation takes a slice's duration the same way (PlanSeg::tail stays in program micro-operations).  Acts on
@@ -342,6 +358,7 @@ private:
     bool plainDefinition(const VirtDef& v) const;                  // every leaf a compact tip: what a class table can stand for (repeatWeights)
     std::vector<int> storedBy_, storedStamp_;          // per (buffer, partition): the slice of the current plan that stores it
     int linkStamp_ = 0;
+    int memCapNow_ = 0;                                // the cap of the list being planned (memStepCap, or memCapSeen())
 
     int partialsCount_ = 0, tipCount_ = 0, matrixCount_ = 0, scaleCount_ = 0, maxSteps_ = 6, keyParts_ = 1;
     bool enabled_ = false;
@@ -388,8 +405,9 @@ private:
     static constexpr int CACHE_WAYS = 8;
     CacheEntry cache_[CACHE_WAYS];
     int cacheNext_ = 0;
-    long cacheTagNext_ = 0;
+    long wayGen_[CACHE_WAYS] = {0, 0, 0, 0, 0, 0, 0, 0};      // fills of each way (a plan's tag: plan())
     void replay(const CacheEntry& e, const int* ops);
+    bool promotable(const CacheEntry& e, bool allowVirtual) const;
     CacheEntry* findCached(const int* ops, int count, int tuple, int parts, bool allowVirtual, int chunkOps);
 };
 
