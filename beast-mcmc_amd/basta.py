@@ -211,6 +211,24 @@ class BastaLikelihood:
                                   COALESCENT_PROBABILITY_INDEX, out)
         return float(out[0])
 
+    def sample_states(self, replicates=1, seed=0, map=False, as_written=False, states=True, occupancy=False, changes=False,
+                      root_frequencies=None):
+        """Demes of every lineage at every sub-interval boundary, ``replicates`` draws from the vectors and matrices of the last
+        ``log_likelihood`` (``BastaLikelihood.traverseSampleByCoalescentIntervals``, BastaLikelihood.java:755-943; the rule is in
+        include/beagle_mi355.h beagleBastaSampleStates).  ``root_frequencies``: the substitution model's frequencies (uniform by
+        default); they go to the frequencies index the population sizes do not occupy.  ``as_written``: the matrix indexed as the
+        reference's interval-by-interval route indexes it.  -> a dict of the arrays asked for: ``states`` uint8
+        [replicates][partials_count] (255: a buffer the list does not touch), ``occupancy`` [intervals][S], ``changes`` [S][S];
+        ``bad``: a draw met a total that is not finite and positive."""
+        if self.traversal is None:
+            raise ValueError("sample_states draws from the last evaluation: call log_likelihood first")
+        tr, b = self.traversal, self.beagle
+        f = np.full(self.state_count, 1.0 / self.state_count) if root_frequencies is None else np.asarray(root_frequencies, dtype=np.float64)
+        b.setStateFrequencies(1 - self.sizes_index, f)
+        flags = (1 if map else 0) | (b.BASTA_STATES_AS_WRITTEN if as_written else 0)
+        return b.sampleBastaStates(tr.operations, tr.operations.shape[0], tr.intervals, tr.intervals.shape[0], 1 - self.sizes_index,
+                                   replicates, seed, flags, states=states, occupancy=occupancy, changes=changes)
+
     def partials(self, buffer):
         return self.beagle.getPartials(buffer).reshape(self.state_count)
 

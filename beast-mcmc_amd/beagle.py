@@ -127,7 +127,7 @@ ABI_SYMBOLS = ["beagleGetVersion", "beagleGetCitation", "beagleGetResourceList",
                "beagleMi355SimulateSequences", "beagleMi355SimulateCompleteHistories", "beagleMi355RobustCounts", "beagleMi355SimulateUnconditionedCounts", "beagleMi355NodeHeightDerivatives", "beagleMi355UpdateDifferentialMatrices", "beagleMi355SetTipEmission", "beagleMi355TipEmissionStats",
                "beagleMi355GetPartialsPinned", "beagleMi355GetSiteLogLikelihoodsPinned",
                "beagleMi355KernelTimerCalls", "beagleMi355WalkHealth", "beagleMi355RepeatStats", "beagleMi355WalkLaunchInfo", "beagleMi355RootFusedCount", "beagleMi355SitePrefetchCount", "beagleMi355KernelTimerRestart", "beagleMi355GetDimensions", "beagleMi355GetCommUniqueId", "beagleMi355CommInit", "beagleMi355CommInfo", "beagleMi355CalculateRootLogLikelihoodsAllReduce"] + \
-              ["beagleBasta" + k for k in ("AllocateCoalescentBuffers", "UpdatePartials", "AccumulatePartials", "GetBuffer", "GetBufferLength", "Stats",
+              ["beagleBasta" + k for k in ("AllocateCoalescentBuffers", "UpdatePartials", "AccumulatePartials", "GetBuffer", "GetBufferLength", "Stats", "SampleStates", "StatesStats",
                                            "UpdatePartialsGrad", "UpdateTransitionMatricesGrad", "AccumulatePartialsGrad")]
 BASTA_OPERATION_SIZE = 8
 
@@ -910,6 +910,39 @@ class Beagle:
         """(uploads of an operation list, updates run as one launch, updates run interval by interval, partialsBufferCount)"""
         out = (C.c_long * 4)()
         self._check("bastaStats", self._ext("beagleBastaStats", [C.c_int, C.POINTER(C.c_long)])(self.instance, out))
+        return tuple(out)
+
+    BASTA_STATES_AS_WRITTEN = 2
+
+    def sampleBastaStates(self, operations, operationCount, intervals, intervalCount, stateFrequenciesIndex, replicateCount, seed,
+                          flags=0, partialsBufferCount=None, states=True, occupancy=False, changes=False):
+        """beagleBastaSampleStates -> {"states": uint8 [replicateCount][partialsBufferCount], "occupancy": [intervalCount - 1][S],
+        "changes": [S][S], "bad": a draw met a total that is not finite and positive} (the arrays that were asked for)."""
+        ops, iv = _i(operations), _i(intervals)
+        if partialsBufferCount is None:
+            partialsBufferCount = self.bastaStats()[3]
+        s = self.stateCount
+        out = {}
+        if states:
+            out["states"] = np.empty((max(replicateCount, 0), partialsBufferCount), dtype=np.uint8)
+        if occupancy:
+            out["occupancy"] = np.zeros((max(intervalCount - 1, 0), s))
+        if changes:
+            out["changes"] = np.zeros((s, s))
+        f = self._ext("beagleBastaSampleStates", [C.c_int, _IP, C.c_int, _IP, C.c_int, C.c_int, C.c_int, C.c_ulonglong, C.c_int,
+                                                  C.c_void_p, _DP, _DP])
+        rc = f(self.instance, _ip(ops), operationCount, _ip(iv), intervalCount, stateFrequenciesIndex, replicateCount,
+               seed & 0xFFFFFFFFFFFFFFFF, flags, out["states"].ctypes.data if states else None,
+               _dp(out["occupancy"]) if occupancy else None, _dp(out["changes"]) if changes else None)
+        out["bad"] = rc == -8
+        if not out["bad"]:
+            self._check("sampleBastaStates", rc)
+        return out
+
+    def bastaStatesStats(self):
+        """(sampleBastaStates calls, launches of the last one per chunk of replicates, its chunks, its chains)"""
+        out = (C.c_long * 4)()
+        self._check("bastaStatesStats", self._ext("beagleBastaStatesStats", [C.c_int, C.POINTER(C.c_long)])(self.instance, out))
         return tuple(out)
 
     def walkStats(self):

@@ -16,6 +16,10 @@
 // The 8-int list is the bulk of the traffic (16 MB at 1000 tips).  It is copied once into a pinned staging buffer and sent from
 // there with one asynchronous copy; beagleBastaAccumulatePartials compares the list it is handed with the staged one — length,
 // then contents (memcmp) — and uploads nothing when they are equal, which is what follows every beagleBastaUpdatePartials.
+//
+// beagleBastaSampleStates draws a deme for every vector of such a list from the stored vectors and matrices, any number of
+// replicates in one call (kernels_basta_states.hip).  The dependency runs the other way — a vector's state needs its reader's —
+// so the same forest is cut into chains by planStates() and run one launch per level of coalescences, per chunk of replicates.
 #include "engine_internal.h"
 
 namespace mi355 {
@@ -36,6 +40,12 @@ struct Basta {
     hipEvent_t sent = nullptr;                           // the last copy out of the pinned buffers
     std::vector<int> writer, writes, intervalOf;         // analyse()'s scratch
     long statUploads = 0, statChainCalls = 0, statIntervalCalls = 0;
+    // beagleBastaSampleStates: the chains of the resident list (planStates; valid while planUpload == statUploads), its scratch
+    // (scratch_layout.h BastaStatesLayout) and counters
+    std::vector<int> steps, chains, levelStart;          // [step][4] | [chain][4], by level | the levels' first chains, then the chain count
+    DevBuf dPlan; long planUpload = -1;                  // device: [steps | chains]
+    DevBuf statesDev;
+    long statStatesCalls = 0, statStatesLaunches = 0, statStatesChunks = 0;
 };
 
 namespace {
@@ -144,6 +154,54 @@ int sendList(Instance* in, Basta* b, const int* ops, int n, const int* intervals
     b->opCount = n; b->intervalCount = intervalCount;
     b->statUploads++;
     return 0;
+}
+
+// The chains of beagleBastaSampleStates and their steps (kernels.h BastaStatesArgs) for a list analyse() accepts in which, moreover, no
+// vector — one the caller stored included — is read twice: every vector then has one state.  false: not such a list.
+bool planStates(Basta* b, const int* ops, int n, const int* intervals, int intervalCount) {
+    std::vector<int> link((size_t)2 * n), leaves(n);
+    int nLeaves = 0;
+    if (!analyse(b, ops, n, intervals, intervalCount, link.data(), leaves.data(), &nLeaves)) return false;
+    std::vector<char> read(b->vectorCount, 0);
+    std::vector<int> down((size_t)2 * n, -1);                // per operation: the operations that wrote in1 / in2
+    for (int k = 0; k < n; k++) {
+        const int* op = ops + (size_t)k * BASTA_OP;
+        for (int side = 0; side < 2; side++) {
+            const int x = op[side ? 3 : 1];
+            if (x < 0) continue;
+            if (read[x]) return false;
+            read[x] = 1;
+            if (b->writes[x]) down[(size_t)2 * k + side] = b->writer[x];
+        }
+    }
+    b->steps.clear(); b->chains.clear(); b->levelStart.clear();
+    std::vector<int> level, next;                            // 4 * operation + 2 * (second input) + (its dest is a root)
+    for (int k = 0; k < n; k++)
+        if (link[2 * k] < 0) {                                               // nothing reads its result: a root
+            level.push_back(4 * k + 1);
+            if (ops[(size_t)k * BASTA_OP + 3] >= 0) level.push_back(4 * k + 3);
+        }
+    while (!level.empty()) {
+        b->levelStart.push_back((int)b->chains.size() / 4);
+        for (int c : level) {
+            int k = c >> 2, side = (c >> 1) & 1;
+            const int firstStep = (int)(b->steps.size() / 4);
+            const int flags = (c & 1 ? mi355::BASTA_CHAIN_ROOT | (side == 0 ? mi355::BASTA_CHAIN_STORES_ROOT : 0) : 0);
+            const int top = ops[(size_t)k * BASTA_OP];
+            for (;;) {
+                const int* op = ops + (size_t)k * BASTA_OP;
+                for (int v : {op[side ? 3 : 1], op[side ? 4 : 2], op[3] >= 0 ? op[side ? 6 : 5] : -1, b->intervalOf[k]}) b->steps.push_back(v);
+                const int w = down[(size_t)2 * k + side];
+                if (w < 0) break;                                            // what the caller stored
+                if (ops[(size_t)w * BASTA_OP + 3] >= 0) { next.push_back(4 * w); next.push_back(4 * w + 2); break; }      // its chains: the next level
+                k = w; side = 0;
+            }
+            for (int v : {firstStep, (int)(b->steps.size() / 4) - firstStep, top, flags}) b->chains.push_back(v);
+        }
+        level.swap(next); next.clear();
+    }
+    b->levelStart.push_back((int)b->chains.size() / 4);
+    return true;
 }
 
 }  // namespace
@@ -347,6 +405,98 @@ int beagleBastaStats(int instance, long* out4) {
     if (!b) return BEAGLE_ERROR_NO_IMPLEMENTATION;
     if (!out4) return BEAGLE_ERROR_OUT_OF_RANGE;
     out4[0] = b->statUploads; out4[1] = b->statChainCalls; out4[2] = b->statIntervalCalls; out4[3] = (long)b->vectorCount;
+    return BEAGLE_SUCCESS;
+}
+
+int beagleBastaSampleStates(int instance, const int* operations, int operationCount, const int* intervals, int intervalCount,
+                            int stateFrequenciesIndex, int replicateCount, unsigned long long seed, int flags,
+                            unsigned char* outStates, double* outOccupancy, double* outChanges) {
+    Instance* in = nullptr;
+    int rc = bastaInstance(instance, &in); if (rc) return rc;
+    Basta* b = in->basta;
+    if (!b) return BEAGLE_ERROR_NO_IMPLEMENTATION;
+    if (replicateCount < 1 || (flags & ~(BEAGLE_MI355_ANCESTRAL_MAP | BEAGLE_MI355_BASTA_STATES_AS_WRITTEN)) || in->S > 255 ||
+        (!outStates && !outOccupancy && !outChanges)) return BEAGLE_ERROR_OUT_OF_RANGE;
+    rc = checkList(in, b, operations, operationCount, intervals, intervalCount, stateFrequenciesIndex, b->coalescentIndex);
+    if (rc) return rc;
+    if (operationCount < 1) return BEAGLE_ERROR_OUT_OF_RANGE;
+    if (in->heldPre.held) { rc = executeHeldPre(in); if (rc) return rc; }
+    const int n = operationCount, S = in->S;
+    const size_t V = (size_t)b->vectorCount, nIntervals = (size_t)intervalCount - 1;
+    bool fresh = false;
+    rc = sendList(in, b, operations, n, intervals, intervalCount, &fresh); if (rc) return rc;
+    hipStream_t s = live(in);
+    if (b->planUpload != b->statUploads) {                   // the chains of the resident list
+        b->planUpload = -1;
+        if (!planStates(b, operations, n, intervals, intervalCount)) return BEAGLE_ERROR_NO_IMPLEMENTATION;
+        const size_t stepBytes = b->steps.size() * sizeof(int), chainBytes = b->chains.size() * sizeof(int);
+        rc = growDevice(in, b->dPlan, stepBytes + chainBytes, stepBytes + chainBytes, Grow::SyncIfHeld); if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(b->dPlan.p, b->steps.data(), stepBytes, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(b->dPlan.p + stepBytes, b->chains.data(), chainBytes, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipStreamSynchronize(s));                    // (the vectors are the plan's host copy: free to change from here on)
+        b->planUpload = b->statUploads;
+    }
+    const int levels = (int)b->levelStart.size() - 1;
+    // replicates per pass: whole waves, at most 256 MiB of states (BEAGLE_MI355_BASTA_STATES_CHUNK=<n>: tests of chunk independence)
+    const size_t R = (size_t)replicateCount;
+    const size_t wanted = std::min<size_t>(std::max<size_t>(64, (256ull << 20) / V / 64 * 64), (size_t)65535 * 64);
+    const size_t chunk = chunkSites("BEAGLE_MI355_BASTA_STATES_CHUNK", 64, wanted, R);
+    const mi355::scratch::BastaStatesLayout L(V, chunk, nIntervals, (size_t)S, outStates != nullptr);
+    rc = growScratch(in, b->statesDev, L.bytes()); if (rc) return rc;
+    char* base = b->statesDev.p;
+    mi355::BastaStatesArgs a{};
+    a.steps = b->dPlan.as<int4>(); a.chains = b->dPlan.as<int4>() + b->steps.size() / 4;
+    a.matrices = in->matrices; a.partials = b->vectors; a.freqs = in->freqs + (size_t)stateFrequenciesIndex * S;
+    a.states = L.states.at(base);
+    a.occupancy = outOccupancy ? L.occupancy.at(base) : nullptr;
+    a.changes = outChanges ? L.changes.at(base) : nullptr;
+    a.error = L.error.at(base);
+    a.seed = seed; a.S = S; a.stride = (int)chunk;
+    a.map = (flags & BEAGLE_MI355_ANCESTRAL_MAP) != 0; a.asWritten = (flags & BEAGLE_MI355_BASTA_STATES_AS_WRITTEN) != 0;
+    uint8_t* dStage = L.stage.at(base);
+    HIP_TRY(hipMemsetAsync(base + L.occupancy.offset, 0, L.bytes() - L.occupancy.offset, s));      // counters and the error word
+    long chunks = 0;
+    const bool timed = timeThisCall(in);
+    for (size_t r0 = 0; r0 < R; r0 += chunk, chunks++) {
+        a.r0 = (int)r0; a.count = (int)std::min(chunk, R - r0);
+        HIP_TRY(hipMemsetAsync(a.states, 0xFF, L.states.bytes(), s));
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        if (timed) {                                         // (a timed call: every chunk's launches, not its copy-out)
+            { int rce = nextTimerEvents(in, &e0, &e1); if (rce) return rce; }
+            HIP_TRY(hipEventRecord(e0, s));
+        }
+        for (int lv = 0; lv < levels; lv++)
+            mi355::launchBastaStates(s, a, b->levelStart[lv], b->levelStart[lv + 1] - b->levelStart[lv]);
+        if (e1) { HIP_TRY(hipEventRecord(e1, s)); in->pendingLaunches += levels; }
+        HIP_TRY(hipGetLastError());
+        if (outStates) {
+            mi355::launchBastaStatesTranspose(s, a.states, (int)V, (int)chunk, a.count, dStage);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(outStates + r0 * V, dStage, (size_t)a.count * V, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));                // (the next chunk overwrites the stage)
+        }
+    }
+    b->statStatesCalls++; b->statStatesLaunches = levels; b->statStatesChunks = chunks;
+    // the counters and the error word in one copy
+    const size_t tailWords = L.occupancy.count + L.changes.count + 1;
+    std::vector<unsigned long long> tail(tailWords);
+    rc = download(in, tail.data(), base + L.occupancy.offset, L.bytes() - L.occupancy.offset); if (rc) return rc;
+    if (in->asyncError) { const int e = in->asyncError.exchange(0); if (e) return e; }
+    if (outOccupancy) for (size_t i = 0; i < L.occupancy.count; i++) outOccupancy[i] = (double)tail[i];
+    if (outChanges) for (size_t i = 0; i < L.changes.count; i++) outChanges[i] = (double)tail[L.occupancy.count + i];
+    unsigned err = 0;
+    memcpy(&err, &tail[L.occupancy.count + L.changes.count], sizeof(unsigned));
+    return err ? BEAGLE_ERROR_FLOATING_POINT : BEAGLE_SUCCESS;
+}
+
+int beagleBastaStatesStats(int instance, long* out4) {
+    Instance* in = nullptr;
+    int rc = bastaInstance(instance, &in); if (rc) return rc;
+    Basta* b = in->basta;
+    if (!b) return BEAGLE_ERROR_NO_IMPLEMENTATION;
+    if (!out4) return BEAGLE_ERROR_OUT_OF_RANGE;
+    out4[0] = b->statStatesCalls; out4[1] = b->statStatesLaunches; out4[2] = b->statStatesChunks;
+    out4[3] = b->planUpload == b->statUploads ? (long)b->chains.size() / 4 : 0;
     return BEAGLE_SUCCESS;
 }
 

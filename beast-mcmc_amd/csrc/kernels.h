@@ -779,6 +779,31 @@ void launchBastaInterval(hipStream_t stream, const int* ops, int first, int coun
 void launchBastaReduce(hipStream_t stream, const int* ops, const int* intervals, int nIntervals, const double* lengths,
                        const double* partials, const double* sizes, const double* coalescent, double* e, double* f, double* g,
                        double* h, double* intervalLogL, double* out, int S);
+// ---- ... its lineage demes (kernels_basta_states.hip; beagleBastaSampleStates).  The draw runs from the roots outwards in CHAINS: a
+// chain starts at one input of a coalescence (or at the one input of a root that is no coalescence), draws that input's state from the
+// state of the operation's `dest`, and follows the one-input operations that produced the input, one draw each, until it reaches a
+// vector the list does not produce or the `dest` of the next coalescence — whose two chains are one level further down.
+// The host lays every chain's draws out in the order the wave makes them, so that the wave chases no pointers and can ask for the
+// next step while it draws the current one:
+// steps: [step] = {input vector, matrix, acc vector of a coalescence's input or -1, interval}, a chain's steps one after another;
+// chains: [chain] = {first step, steps, the vector whose state the chain starts from, BASTA_CHAIN_* bits}.
+constexpr int BASTA_CHAIN_ROOT = 1;      // that vector is a root: its state is drawn here (by both chains of a root coalescence alike) ...
+constexpr int BASTA_CHAIN_STORES_ROOT = 2;   // ... and stored by this one
+struct BastaStatesArgs {
+    const int4* steps; const int4* chains;
+    const double* matrices; const double* partials; const double* freqs;
+    uint8_t* states;                     // [vector][stride]: replicate r0 + l of the chunk at column l
+    unsigned long long* occupancy;       // [interval][S] or null
+    unsigned long long* changes;         // [S][S] or null
+    unsigned* error;                     // set when a draw met a total that is not finite and positive
+    unsigned long long seed;
+    int S, stride, r0, count;            // the chunk: replicates r0 .. r0 + count - 1, count <= stride
+    int map, asWritten;
+};
+// the chains [first, first + n) — one level — for every replicate of the chunk: a wave per (chain, 64 replicates)
+void launchBastaStates(hipStream_t stream, const BastaStatesArgs& a, int first, int n);
+// out[l][v] = states[v][l] for l < count, v < vectors
+void launchBastaStatesTranspose(hipStream_t stream, const uint8_t* states, int vectors, int stride, int count, uint8_t* out);
 
 // ---- tip error models (kernels_tipemission.hip): a tip whose partials are a lookup E[code][state], K codes
 // matrices[dst][c][i][k] = sum_j matrices[src][c][i][j] E[k][j] (j ascending, no fused multiply-add), zero for k >= K: one job per

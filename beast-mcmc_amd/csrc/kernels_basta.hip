@@ -22,13 +22,13 @@
 #pragma clang fp contract(off)
 
 #include "kernels.h"
+#include "basta_stage.h"
 
 namespace mi355 {
 
 namespace {
 
 constexpr int BASTA_ROWS = 4;          // rows of the result per lane: up to 256 states
-constexpr int BASTA_LDS_STATES = 64;   // up to here an operation's matrix is staged in LDS (33 KB at 64 states)
 
 // row i of M (leading dimension ld) times v, in index order
 template <class MatrixPtr>
@@ -36,30 +36,6 @@ __device__ __forceinline__ double bastaRow(MatrixPtr M, int ld, int i, const dou
     double sum = 0.0;
     for (int j = 0; j < S; j++) sum += M[(size_t)i * ld + j] * v[j];
     return sum;
-}
-
-// S <= BASTA_LDS_STATES: the operation's matrix is staged in LDS with coalesced reads (odd leading dimension: a lane reads its own
-// row): all 64 lanes over the S * S entries, sixteen loads in flight per lane before the first is waited for (a loop that stores
-// each value as it arrives is a chain of 58 L2 latencies at 61 states: 19 us an operation).  The row of entry `at` is
-// at / S by a multiply and a shift: exact for at < 4096 and S <= 64 (magic = 2^18 / S + 1 overshoots at / S by less than 1 / 64).
-__device__ __forceinline__ void bastaStage(const double* g, double* stage, int S, int ld) {
-    const int n = S * S, pad = ld - S;
-    const unsigned magic = (1u << 18) / (unsigned)S + 1u;
-    if (n <= 64) {                                        // (up to 8 states: one load)
-        const int at = threadIdx.x;
-        if (at < n) stage[at + (int)(((unsigned)at * magic) >> 18) * pad] = g[at];
-        return;
-    }
-    for (int base = threadIdx.x; base < n; base += 64 * 16) {
-        double r[16];
-#pragma unroll
-        for (int u = 0; u < 16; u++) { const int at = base + 64 * u; r[u] = at < n ? g[at] : 0.0; }
-#pragma unroll
-        for (int u = 0; u < 16; u++) {
-            const int at = base + 64 * u;
-            if (at < n) stage[at + (int)(((unsigned)at * magic) >> 18) * pad] = r[u];
-        }
-    }
 }
 
 // M p for the rows of this lane: from the staged copy (LDS) or, above BASTA_LDS_STATES, straight from memory
@@ -212,7 +188,6 @@ __global__ __launch_bounds__(64) void k_bastaTotal(const double* __restrict__ in
     }
 }
 
-inline bool bastaStaged(int S) { return S <= BASTA_LDS_STATES; }
 inline size_t bastaUpdateLds(int S) { return ((size_t)3 * S + (bastaStaged(S) ? (size_t)S * (S | 1) : 0)) * sizeof(double); }
 
 }  // namespace

@@ -129,5 +129,16 @@ struct HistoryLayout : Carver {
     }
 };
 
+// BASTA lineage demes (engine_basta.cpp Basta::statesDev): states [vectors][chunk] | (256) outStates stage [chunk][vectors]
+//             | (256) occupancy [intervals][S] | changes [S][S] (64-bit counters) | error word
+struct BastaStatesLayout : Carver {
+    Section<uint8_t> states, stage; Section<unsigned long long> occupancy, changes; Section<unsigned> error;
+    BastaStatesLayout(size_t vectors, size_t chunk, size_t intervals, size_t S, bool copyOut) {
+        states = take<uint8_t>(vectors * chunk); align(256);
+        stage = take<uint8_t>(copyOut ? chunk * vectors : 0); align(256);
+        occupancy = take<unsigned long long>(intervals * S); changes = take<unsigned long long>(S * S); error = take<unsigned>(1);
+    }
+};
+
 }  // namespace scratch
 }  // namespace mi355

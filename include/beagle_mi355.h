@@ -815,6 +815,49 @@ int beagleBastaGetBuffer(int instance, int index, double* out);
 int beagleBastaGetBufferLength(int instance, int index);
 /* out4 = {uploads of an operation list so far, updates run as one launch, updates run interval by interval, partialsBufferCount}. */
 int beagleBastaStats(int instance, long* out4);
+/* Draw a deme for every lineage at every sub-interval boundary, replicateCount times, in one call (an extension: BastaJNIWrapper has no
+ * native for it; what BastaLikelihood.traverseSampleByCoalescentIntervals computes from one getPartials and one getTransitionMatrices per
+ * branch-interval operation, BastaLikelihood.java:755-943).  operations / intervals: the list of beagleBastaUpdatePartials, staged and
+ * compared as beagleBastaAccumulatePartials does it (a list equal to the resident one is not uploaded again).  The vectors and matrices
+ * are read as they stand: call beagleBastaUpdatePartials first.
+ *
+ * The rule.  A vector nothing in the list reads is a ROOT (the reference's lists have one: `dest` of the last operation); its state is
+ * drawn from the weights p[root]_i f_i, f = the frequencies at stateFrequenciesIndex.  Then the operations are visited from the last
+ * interval to the first.  With s the state already drawn for the operation's `dest`, each input (in1 with matrix1, and in2 with matrix2
+ * when in2 >= 0) gets a state drawn from
+ *     w_j = M[s][j] p[in]_j,      M the matrix as stored (as beagleGetTransitionMatrix returns it):
+ * the S terms whose sum beagleBastaUpdatePartials forms as left_s / right_s, so the draw is the exact conditional under the approximation
+ * the likelihood itself makes; at a coalescence the two children are drawn independently given s.  THIS ORIENTATION IS THE DEFAULT: it is
+ * the one consistent with the likelihood, and what the reference's node-by-node route computes from the untransposed exp(Qt)
+ * (BastaLikelihood.java:1036-1038, 1086-1091).  The reference's interval-by-interval route indexes the stored (transposed) matrix the
+ * other way round (:938), which differs for an asymmetric Q; BEAGLE_MI355_BASTA_STATES_AS_WRITTEN selects that reading,
+ *     w_j = M[j][s] p[in]_j,
+ * so that a literal restatement of :911-943 can be compared bit for bit.
+ * Fixed tips: an input vector with exactly one positive entry gives that entry's index without a draw (:846-867, applied to any input).
+ * Draws: randomChoicePDF's rule with U = u * total, the largest index of a positive weight when rounding lets the walk fall through, as
+ * beagleMi355SampleAncestralStates; BEAGLE_MI355_ANCESTRAL_MAP: the first index of the strict maximum instead.  The uniform of vector b
+ * in replicate r is the (b + 1)-th output of the SplitMix64 stream whose state is the (r + 1)-th output of the stream of `seed`, its top
+ * 53 bits: a state depends on the seed, the replicate and the buffer number only, not on how the call is cut into launches.
+ *
+ * Outputs (each may be NULL, not all):
+ *   outStates    [replicateCount][partialsBufferCount]: the state of every vector, 255 for one the list neither reads nor writes; acc1 /
+ *                acc2 of a coalescence get the state of the input they were formed from.  Copied out in chunks of replicates.
+ *   outOccupancy [intervalCount - 1][S]: over all replicates, the number of input vectors of interval k's operations in state i
+ *                (lineages per deme at the young end of the interval).
+ *   outChanges   [S][S]: over all replicates and all inputs, the number with `dest` state a and input state b.
+ * Both count arrays are integer sums (64-bit on the device) returned as doubles: exact, whatever the order.
+ * The number of launches is the depth of the list in coalescences (beagleBastaStatesStats), per chunk of replicates.
+ * BEAGLE_ERROR_NO_IMPLEMENTATION: the sharded handle, an instance without BASTA buffers, a list in which a vector is written twice, read
+ * by two operations, or read in the interval that writes it.  BEAGLE_ERROR_OUT_OF_RANGE: replicateCount < 1, a bad index, unknown flag
+ * bits, S > 255, no output.  BEAGLE_ERROR_FLOATING_POINT: a draw met a total that is not finite and positive; the outputs are still
+ * written, with state 0 there. */
+#define BEAGLE_MI355_BASTA_STATES_AS_WRITTEN 2
+int beagleBastaSampleStates(int instance, const int* operations, int operationCount, const int* intervals, int intervalCount,
+                            int stateFrequenciesIndex, int replicateCount, unsigned long long seed, int flags,
+                            unsigned char* outStates, double* outOccupancy, double* outChanges);
+/* out4 = {beagleBastaSampleStates calls so far, kernel launches of the last one per chunk of replicates (its depth in coalescences),
+ * chunks of replicates of the last one, chains of the last one}. */
+int beagleBastaStatesStats(int instance, long* out4);
 /* The gradient natives of BastaJNIWrapper: not built, BEAGLE_ERROR_NO_IMPLEMENTATION. */
 int beagleBastaUpdatePartialsGrad(int instance, const int* operations, int operationCount, const int* intervals, int intervalCount,
                                   int populationSizesIndex, int coalescentProbabilityIndex);
