@@ -130,6 +130,30 @@ def traverse(tree, rate=1.0, sub_intervals=1):
     return out
 
 
+def interval_distances(traversal):
+    """Per list interval, the rate-scaled length its matrix was formed with (``TransitionMatrixOperation.time``; 0 for an interval
+    without operations)."""
+    time = dict(traversal.matrices)
+    ops, starts = traversal.operations, traversal.intervals
+    return np.asarray([time[int(ops[starts[k], 2])] if starts[k + 1] > starts[k] else 0.0 for k in range(len(starts) - 1)])
+
+
+def migration_rate_chain_rule(w, frequencies):
+    """From the S x S intermediate to the rates parameter's order (StructuredCoalescentLikelihoodGradient.java:134-154): the upper
+    triangle row by row, then the lower triangle column by column, each (W[i][j] - W[i][i]) pi_j."""
+    w, pi = np.asarray(w), np.asarray(frequencies)
+    s = w.shape[0]
+    upper = [(w[i, j] - w[i, i]) * pi[j] for i in range(s) for j in range(i + 1, s)]
+    lower = [(w[i, j] - w[i, i]) * pi[j] for j in range(s) for i in range(j + 1, s)]
+    return np.asarray(upper + lower, dtype=w.dtype)
+
+
+def population_size_chain_rule(theta_gradient, sizes):
+    """d/dN from d/d(1/N) (StructuredCoalescentLikelihoodGradient.java:181-190)."""
+    sizes = np.asarray(sizes)
+    return np.asarray(theta_gradient) / -(sizes * sizes)
+
+
 class BastaLikelihood:
     """The BASTA log-density of ``tree`` with the tips in ``tip_demes`` (a deme index per tip, or [T][S] vectors).
 
@@ -228,6 +252,30 @@ class BastaLikelihood:
         flags = (1 if map else 0) | (b.BASTA_STATES_AS_WRITTEN if as_written else 0)
         return b.sampleBastaStates(tr.operations, tr.operations.shape[0], tr.intervals, tr.intervals.shape[0], 1 - self.sizes_index,
                                    replicates, seed, flags, states=states, occupancy=occupancy, changes=changes)
+
+    def gradient(self, wrt="both", frequencies=None, adjoints=False):
+        """The gradient of the last ``log_likelihood`` (include/beagle_mi355.h beagleBastaGradient; what
+        ``StructuredCoalescentLikelihoodGradient`` returns for wrtParameter "migrationRate" / "populationSize").  ``wrt``:
+        "migration", "population" or "both".  -> a dict of
+          ``theta`` [S]            with respect to 1 / size (the reference's intermediate)
+          ``population_sizes`` [S] = -theta / N^2 (StructuredCoalescentLikelihoodGradient.java:181-190)
+          ``migration`` [S][S]     the intermediate W
+          ``migration_rates`` [S (S - 1)], with ``frequencies``: ``migration_rate_chain_rule(W, frequencies)``
+          ``adjoints`` [partials_count][S], when asked for;   ``bad``: a value is not finite."""
+        if wrt not in ("both", "migration", "population"):
+            raise ValueError("wrt: 'migration', 'population' or 'both'")
+        if self.traversal is None:
+            raise ValueError("gradient differentiates the last evaluation: call log_likelihood first")
+        tr, b = self.traversal, self.beagle
+        migration, population = wrt != "population", wrt != "migration"
+        out = b.bastaGradient(tr.operations, tr.operations.shape[0], tr.intervals, tr.intervals.shape[0], tr.lengths,
+                              interval_distances(tr) if migration else None, self.sizes_index, COALESCENT_PROBABILITY_INDEX,
+                              population_sizes=population, migration=migration, adjoints=adjoints)
+        if population:
+            out["population_sizes"] = population_size_chain_rule(out["theta"], self.sizes)
+        if migration and frequencies is not None:
+            out["migration_rates"] = migration_rate_chain_rule(out["migration"], frequencies)
+        return out
 
     def partials(self, buffer):
         return self.beagle.getPartials(buffer).reshape(self.state_count)

@@ -128,7 +128,7 @@ ABI_SYMBOLS = ["beagleGetVersion", "beagleGetCitation", "beagleGetResourceList",
                "beagleMi355GetPartialsPinned", "beagleMi355GetSiteLogLikelihoodsPinned",
                "beagleMi355KernelTimerCalls", "beagleMi355WalkHealth", "beagleMi355RepeatStats", "beagleMi355WalkLaunchInfo", "beagleMi355RootFusedCount", "beagleMi355SitePrefetchCount", "beagleMi355KernelTimerRestart", "beagleMi355GetDimensions", "beagleMi355GetCommUniqueId", "beagleMi355CommInit", "beagleMi355CommInfo", "beagleMi355CalculateRootLogLikelihoodsAllReduce"] + \
               ["beagleBasta" + k for k in ("AllocateCoalescentBuffers", "UpdatePartials", "AccumulatePartials", "GetBuffer", "GetBufferLength", "Stats", "SampleStates", "StatesStats",
-                                           "UpdatePartialsGrad", "UpdateTransitionMatricesGrad", "AccumulatePartialsGrad")]
+                                           "Gradient", "GradientStats", "UpdatePartialsGrad", "UpdateTransitionMatricesGrad", "AccumulatePartialsGrad")]
 BASTA_OPERATION_SIZE = 8
 
 
@@ -943,6 +943,38 @@ class Beagle:
         """(sampleBastaStates calls, launches of the last one per chunk of replicates, its chunks, its chains)"""
         out = (C.c_long * 4)()
         self._check("bastaStatesStats", self._ext("beagleBastaStatesStats", [C.c_int, C.POINTER(C.c_long)])(self.instance, out))
+        return tuple(out)
+
+    def bastaGradient(self, operations, operationCount, intervals, intervalCount, intervalLengths, intervalDistances,
+                      populationSizesIndex, coalescentProbabilityIndex, flags=0, partialsBufferCount=None, population_sizes=True,
+                      migration=True, adjoints=False):
+        """beagleBastaGradient -> {"theta": [S] (with respect to 1 / size), "migration": [S][S], "adjoints": [partialsBufferCount][S],
+        "bad": a returned value is not finite} (the arrays that were asked for)."""
+        ops, iv, ln = _i(operations), _i(intervals), _d(intervalLengths)
+        dist = None if intervalDistances is None else _d(intervalDistances)
+        if partialsBufferCount is None:
+            partialsBufferCount = self.bastaStats()[3]
+        s = self.stateCount
+        out = {}
+        if population_sizes:
+            out["theta"] = np.zeros(s)
+        if migration:
+            out["migration"] = np.zeros((s, s))
+        if adjoints:
+            out["adjoints"] = np.zeros((partialsBufferCount, s))
+        f = self._ext("beagleBastaGradient", [C.c_int, _IP, C.c_int, _IP, C.c_int, _DP, _DP, C.c_int, C.c_int, C.c_int, _DP, _DP, _DP])
+        rc = f(self.instance, _ip(ops), operationCount, _ip(iv), intervalCount, _dp(ln), None if dist is None else _dp(dist),
+               populationSizesIndex, coalescentProbabilityIndex, flags, _dp(out["theta"]) if population_sizes else None,
+               _dp(out["migration"]) if migration else None, _dp(out["adjoints"]) if adjoints else None)
+        out["bad"] = rc == -8
+        if not out["bad"]:
+            self._check("bastaGradient", rc)
+        return out
+
+    def bastaGradientStats(self):
+        """(bastaGradient calls, kernel launches of the last one, its levels of coalescences, its chains)"""
+        out = (C.c_long * 4)()
+        self._check("bastaGradientStats", self._ext("beagleBastaGradientStats", [C.c_int, C.POINTER(C.c_long)])(self.instance, out))
         return tuple(out)
 
     def walkStats(self):

@@ -20,6 +20,9 @@
 // beagleBastaSampleStates draws a deme for every vector of such a list from the stored vectors and matrices, any number of
 // replicates in one call (kernels_basta_states.hip).  The dependency runs the other way — a vector's state needs its reader's —
 // so the same forest is cut into chains by planStates() and run one launch per level of coalescences, per chunk of replicates.
+//
+// beagleBastaGradient walks the same chains with one adjoint vector per buffer (kernels_basta_gradient.hip) and reduces adjoints and
+// vectors to the migration-rate and population-size gradients; the three gradient natives of BastaJNIWrapper stay unbuilt.
 #include "engine_internal.h"
 
 namespace mi355 {
@@ -43,9 +46,15 @@ struct Basta {
     // beagleBastaSampleStates: the chains of the resident list (planStates; valid while planUpload == statUploads), its scratch
     // (scratch_layout.h BastaStatesLayout) and counters
     std::vector<int> steps, chains, levelStart;          // [step][4] | [chain][4], by level | the levels' first chains, then the chain count
-    DevBuf dPlan; long planUpload = -1;                  // device: [steps | chains]
+    std::vector<int> chainAux, stepNumbers;              // what beagleBastaGradient needs besides: [chain][4] | [step] (kernels.h BastaGradientArgs)
+    DevBuf dPlan; long planUpload = -1;                  // device: [steps | chains | chainAux | stepNumbers]
     DevBuf statesDev;
     long statStatesCalls = 0, statStatesLaunches = 0, statStatesChunks = 0;
+    // beagleBastaGradient: interval lengths and distances as last sent ([2][intervals]), its scratch (scratch_layout.h
+    // BastaGradientLayout) and counters
+    double* hTimes = nullptr; DevBuf dTimes; size_t timesCap = 0;
+    DevBuf gradientDev;
+    long statGradientCalls = 0, statGradientLaunches = 0, statGradientLevels = 0;
 };
 
 namespace {
@@ -174,8 +183,8 @@ bool planStates(Basta* b, const int* ops, int n, const int* intervals, int inter
             if (b->writes[x]) down[(size_t)2 * k + side] = b->writer[x];
         }
     }
-    b->steps.clear(); b->chains.clear(); b->levelStart.clear();
-    std::vector<int> level, next;                            // 4 * operation + 2 * (second input) + (its dest is a root)
+    b->steps.clear(); b->chains.clear(); b->levelStart.clear(); b->chainAux.clear(); b->stepNumbers.clear();
+    std::vector<int> level, next;                           // 4 * operation + 2 * (second input) + (its dest is a root)
     for (int k = 0; k < n; k++)
         if (link[2 * k] < 0) {                                               // nothing reads its result: a root
             level.push_back(4 * k + 1);
@@ -188,9 +197,14 @@ bool planStates(Basta* b, const int* ops, int n, const int* intervals, int inter
             const int firstStep = (int)(b->steps.size() / 4);
             const int flags = (c & 1 ? mi355::BASTA_CHAIN_ROOT | (side == 0 ? mi355::BASTA_CHAIN_STORES_ROOT : 0) : 0);
             const int top = ops[(size_t)k * BASTA_OP];
+            {
+                const int* op = ops + (size_t)k * BASTA_OP;
+                for (int v : {op[3] >= 0 ? op[side ? 5 : 6] : -1, op[7], side, 0}) b->chainAux.push_back(v);
+            }
             for (;;) {
                 const int* op = ops + (size_t)k * BASTA_OP;
                 for (int v : {op[side ? 3 : 1], op[side ? 4 : 2], op[3] >= 0 ? op[side ? 6 : 5] : -1, b->intervalOf[k]}) b->steps.push_back(v);
+                b->stepNumbers.push_back(ops[(size_t)intervals[b->intervalOf[k]] * BASTA_OP + 7]);      // (where e, f, g, h of the interval live)
                 const int w = down[(size_t)2 * k + side];
                 if (w < 0) break;                                            // what the caller stored
                 if (ops[(size_t)w * BASTA_OP + 3] >= 0) { next.push_back(4 * w); next.push_back(4 * w + 2); break; }      // its chains: the next level
@@ -202,6 +216,25 @@ bool planStates(Basta* b, const int* ops, int n, const int* intervals, int inter
     }
     b->levelStart.push_back((int)b->chains.size() / 4);
     return true;
+}
+
+// the chains of the resident list on the device, planned and sent when the list has changed since
+int residentPlan(Instance* in, Basta* b, const int* ops, int n, const int* intervals, int intervalCount) {
+    if (b->planUpload == b->statUploads) return 0;
+    b->planUpload = -1;
+    if (!planStates(b, ops, n, intervals, intervalCount)) return BEAGLE_ERROR_NO_IMPLEMENTATION;
+    hipStream_t s = live(in);
+    size_t bytes = 0;
+    for (const std::vector<int>* v : {&b->steps, &b->chains, &b->chainAux, &b->stepNumbers}) bytes += v->size() * sizeof(int);
+    int rc = growDevice(in, b->dPlan, bytes, bytes, Grow::SyncIfHeld); if (rc) return rc;
+    size_t at = 0;
+    for (const std::vector<int>* v : {&b->steps, &b->chains, &b->chainAux, &b->stepNumbers}) {      // (16-byte records first)
+        HIP_TRY(hipMemcpyAsync(b->dPlan.p + at, v->data(), v->size() * sizeof(int), hipMemcpyHostToDevice, s));
+        at += v->size() * sizeof(int);
+    }
+    HIP_TRY(hipStreamSynchronize(s));                        // (the vectors are the plan's host copy: free to change from here on)
+    b->planUpload = b->statUploads;
+    return 0;
 }
 
 }  // namespace
@@ -227,6 +260,7 @@ void bastaFree(Instance* in) {
     if (b->hIntervals) hipHostFree(b->hIntervals);
     if (b->hLengths) hipHostFree(b->hLengths);
     if (b->hLink) hipHostFree(b->hLink);
+    if (b->hTimes) hipHostFree(b->hTimes);
     if (b->sent) hipEventDestroy(b->sent);
     delete b;
     in->basta = nullptr;
@@ -426,16 +460,7 @@ int beagleBastaSampleStates(int instance, const int* operations, int operationCo
     bool fresh = false;
     rc = sendList(in, b, operations, n, intervals, intervalCount, &fresh); if (rc) return rc;
     hipStream_t s = live(in);
-    if (b->planUpload != b->statUploads) {                   // the chains of the resident list
-        b->planUpload = -1;
-        if (!planStates(b, operations, n, intervals, intervalCount)) return BEAGLE_ERROR_NO_IMPLEMENTATION;
-        const size_t stepBytes = b->steps.size() * sizeof(int), chainBytes = b->chains.size() * sizeof(int);
-        rc = growDevice(in, b->dPlan, stepBytes + chainBytes, stepBytes + chainBytes, Grow::SyncIfHeld); if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(b->dPlan.p, b->steps.data(), stepBytes, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(b->dPlan.p + stepBytes, b->chains.data(), chainBytes, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipStreamSynchronize(s));                    // (the vectors are the plan's host copy: free to change from here on)
-        b->planUpload = b->statUploads;
-    }
+    rc = residentPlan(in, b, operations, n, intervals, intervalCount); if (rc) return rc;
     const int levels = (int)b->levelStart.size() - 1;
     // replicates per pass: whole waves, at most 256 MiB of states (BEAGLE_MI355_BASTA_STATES_CHUNK=<n>: tests of chunk independence)
     const size_t R = (size_t)replicateCount;
@@ -496,6 +521,87 @@ int beagleBastaStatesStats(int instance, long* out4) {
     if (!b) return BEAGLE_ERROR_NO_IMPLEMENTATION;
     if (!out4) return BEAGLE_ERROR_OUT_OF_RANGE;
     out4[0] = b->statStatesCalls; out4[1] = b->statStatesLaunches; out4[2] = b->statStatesChunks;
+    out4[3] = b->planUpload == b->statUploads ? (long)b->chains.size() / 4 : 0;
+    return BEAGLE_SUCCESS;
+}
+
+int beagleBastaGradient(int instance, const int* operations, int operationCount, const int* intervals, int intervalCount,
+                        const double* intervalLengths, const double* intervalDistances, int populationSizesIndex,
+                        int coalescentProbabilityIndex, int flags, double* outPopulationSizes, double* outMigration, double* outAdjoints) {
+    Instance* in = nullptr;
+    int rc = bastaInstance(instance, &in); if (rc) return rc;
+    Basta* b = in->basta;
+    if (!b) return BEAGLE_ERROR_NO_IMPLEMENTATION;
+    if (flags != 0 || (!outPopulationSizes && !outMigration && !outAdjoints)) return BEAGLE_ERROR_OUT_OF_RANGE;
+    rc = checkList(in, b, operations, operationCount, intervals, intervalCount, populationSizesIndex, coalescentProbabilityIndex);
+    if (rc) return rc;
+    if (operationCount < 1 || !intervalLengths || (outMigration && !intervalDistances)) return BEAGLE_ERROR_OUT_OF_RANGE;
+    if (b->bufferCount < 5 || intervalCount - 1 > b->maxIntervals) return BEAGLE_ERROR_OUT_OF_RANGE;      // probabilities, e, f, g, h
+    if (in->S > mi355::BASTA_GRADIENT_MAX_STATES) return BEAGLE_ERROR_NO_IMPLEMENTATION;
+    if (in->heldPre.held) { rc = executeHeldPre(in); if (rc) return rc; }
+    const int n = operationCount, S = in->S, nIntervals = intervalCount - 1;
+    const size_t V = (size_t)b->vectorCount, entries = (size_t)S * S + S;
+    bool fresh = false;
+    rc = sendList(in, b, operations, n, intervals, intervalCount, &fresh); if (rc) return rc;
+    rc = residentPlan(in, b, operations, n, intervals, intervalCount); if (rc) return rc;
+    // lengths, then distances, through the pinned pair
+    rc = growPair(in, b->hTimes, b->dTimes, b->timesCap, (size_t)2 * nIntervals); if (rc) return rc;
+    HIP_TRY(hipEventSynchronize(b->sent));
+    memcpy(b->hTimes, intervalLengths, (size_t)nIntervals * sizeof(double));
+    if (intervalDistances) memcpy(b->hTimes + nIntervals, intervalDistances, (size_t)nIntervals * sizeof(double));
+    hipStream_t s = live(in);
+    HIP_TRY(hipMemcpyAsync(b->dTimes.p, b->hTimes, (size_t)(intervalDistances ? 2 : 1) * nIntervals * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(b->sent, s));
+    const mi355::scratch::BastaGradientLayout L(V, (size_t)nIntervals, (size_t)S);
+    rc = growScratch(in, b->gradientDev, L.bytes()); if (rc) return rc;
+    char* base = b->gradientDev.p;
+    // e, f, g, h: the four lowest buffers that do not hold the coalescent probabilities, formed as beagleBastaAccumulatePartials forms them
+    double* efgh[4]; int at = 0;
+    const size_t stride = (size_t)b->maxIntervals * S;
+    for (int k = 0; k < b->bufferCount && at < 4; k++) if (k != coalescentProbabilityIndex) efgh[at++] = b->buffers + k * stride;
+    mi355::BastaGradientArgs a{};
+    a.steps = b->dPlan.as<int4>(); a.chains = a.steps + b->steps.size() / 4; a.chainAux = a.chains + b->chains.size() / 4;
+    a.stepNumbers = reinterpret_cast<const int*>(a.chainAux + b->chainAux.size() / 4);
+    a.ops = b->dOps.as<int>(); a.intervals = b->dIntervals.as<int>();
+    a.matrices = in->matrices; a.partials = b->vectors; a.sizes = in->freqs + (size_t)populationSizesIndex * S;
+    a.coalescent = b->buffers + coalescentProbabilityIndex * stride;
+    a.e = efgh[0]; a.f = efgh[1]; a.g = efgh[2]; a.h = efgh[3];
+    a.lengths = b->dTimes.as<double>(); a.distances = intervalDistances ? b->dTimes.as<double>() + nIntervals : nullptr;
+    a.adjoints = L.adjoints.at(base); a.w = L.w.at(base); a.parts = L.parts.at(base); a.out = L.out.at(base);
+    a.S = S;
+    const int levels = (int)b->levelStart.size() - 1;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (timeThisCall(in)) {
+        { int rce = nextTimerEvents(in, &e0, &e1); if (rce) return rce; }
+        HIP_TRY(hipEventRecord(e0, s));
+    }
+    mi355::launchBastaReduce(s, a.ops, a.intervals, nIntervals, a.lengths, b->vectors, a.sizes, a.coalescent, efgh[0], efgh[1], efgh[2], efgh[3],
+                             b->intervalLogL, b->intervalLogL + b->maxIntervals, S);
+    HIP_TRY(hipMemsetAsync(a.adjoints, 0, L.adjoints.bytes(), s));           // (a vector the list does not touch, a root coalescence's dest)
+    for (int lv = 0; lv < levels; lv++) mi355::launchBastaGradientSweep(s, a, b->levelStart[lv], b->levelStart[lv + 1] - b->levelStart[lv]);
+    mi355::launchBastaGradientReduce(s, a, nIntervals);
+    const int launches = levels + 4;                         // the levels, the two launches behind e, f, g, h and the two reductions
+    if (e1) { HIP_TRY(hipEventRecord(e1, s)); in->pendingLaunches += launches; }
+    HIP_TRY(hipGetLastError());
+    b->statGradientCalls++; b->statGradientLaunches = launches; b->statGradientLevels = levels;
+    std::vector<double> out(entries), adjoints(outAdjoints ? V * S : 0);
+    if (outAdjoints) HIP_TRY(hipMemcpyAsync(adjoints.data(), a.adjoints, adjoints.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    rc = download(in, out.data(), a.out, entries * sizeof(double)); if (rc) return rc;
+    if (in->asyncError) { const int e = in->asyncError.exchange(0); if (e) return e; }
+    bool finite = true;
+    if (outMigration) for (size_t i = 0; i < (size_t)S * S; i++) { outMigration[i] = out[i]; finite = finite && std::isfinite(out[i]); }
+    if (outPopulationSizes) for (int i = 0; i < S; i++) { outPopulationSizes[i] = out[(size_t)S * S + i]; finite = finite && std::isfinite(out[(size_t)S * S + i]); }
+    if (outAdjoints) for (size_t i = 0; i < adjoints.size(); i++) { outAdjoints[i] = adjoints[i]; finite = finite && std::isfinite(adjoints[i]); }
+    return finite ? BEAGLE_SUCCESS : BEAGLE_ERROR_FLOATING_POINT;
+}
+
+int beagleBastaGradientStats(int instance, long* out4) {
+    Instance* in = nullptr;
+    int rc = bastaInstance(instance, &in); if (rc) return rc;
+    Basta* b = in->basta;
+    if (!b) return BEAGLE_ERROR_NO_IMPLEMENTATION;
+    if (!out4) return BEAGLE_ERROR_OUT_OF_RANGE;
+    out4[0] = b->statGradientCalls; out4[1] = b->statGradientLaunches; out4[2] = b->statGradientLevels;
     out4[3] = b->planUpload == b->statUploads ? (long)b->chains.size() / 4 : 0;
     return BEAGLE_SUCCESS;
 }

@@ -804,6 +804,28 @@ struct BastaStatesArgs {
 void launchBastaStates(hipStream_t stream, const BastaStatesArgs& a, int first, int n);
 // out[l][v] = states[v][l] for l < count, v < vectors
 void launchBastaStatesTranspose(hipStream_t stream, const uint8_t* states, int vectors, int stride, int count, uint8_t* out);
+// ---- ... and its gradient (kernels_basta_gradient.hip; beagleBastaGradient, the rule is in include/beagle_mi355.h): the adjoint of
+// every vector, from the roots outwards over the same chains.  Besides steps and chains the wave needs, per step, the interval number
+// where e and g of the step's interval live (stepNumbers), and per chain what the coalescence at its top adds:
+// chainAux: [chain] = {acc vector of the coalescence's OTHER input or -1, the coalescence's interval number, side (0: in1), 0}.
+constexpr int BASTA_GRADIENT_MAX_STATES = 256;
+struct BastaGradientArgs {
+    const int4* steps; const int4* chains; const int4* chainAux; const int* stepNumbers;
+    const int* ops; const int* intervals;
+    const double* matrices; const double* partials; const double* sizes; const double* coalescent;
+    const double* e; const double* f; const double* g; const double* h;
+    const double* lengths;               // [interval]
+    const double* distances;             // [interval] or null: no migration-rate gradient
+    double* adjoints;                    // [vector][S], zeroed by the caller
+    double* w;                           // [vector][S]: at a coalescence's dest, (adjoint - <adjoint, vector> + 1) / J
+    double* parts;                       // [interval][S * S + S]: an interval's share of W, then of G_theta
+    double* out;                         // [S * S + S]
+    int S;
+};
+// the chains [first, first + n) — one level: a wave per chain, lane = state
+void launchBastaGradientSweep(hipStream_t stream, const BastaGradientArgs& a, int first, int n);
+// parts: per interval the sums over its operations in list order (a workgroup each); out: the intervals added in index order
+void launchBastaGradientReduce(hipStream_t stream, const BastaGradientArgs& a, int nIntervals);
 
 // ---- tip error models (kernels_tipemission.hip): a tip whose partials are a lookup E[code][state], K codes
 // matrices[dst][c][i][k] = sum_j matrices[src][c][i][j] E[k][j] (j ascending, no fused multiply-add), zero for k >= K: one job per

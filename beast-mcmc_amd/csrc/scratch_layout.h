@@ -140,5 +140,16 @@ struct BastaStatesLayout : Carver {
     }
 };
 
+// BASTA gradient (engine_basta.cpp Basta::gradientDev): adjoints [vectors][S] | w [vectors][S] | (256) per-interval shares
+//             [intervals][S * S + S] | (256) out [S * S + S]
+struct BastaGradientLayout : Carver {
+    Doubles adjoints, w, parts, out;
+    BastaGradientLayout(size_t vectors, size_t intervals, size_t S) {
+        adjoints = take<double>(vectors * S); w = take<double>(vectors * S); align(256);
+        parts = take<double>(intervals * (S * S + S)); align(256);
+        out = take<double>(S * S + S);
+    }
+};
+
 }  // namespace scratch
 }  // namespace mi355

@@ -858,7 +858,56 @@ int beagleBastaSampleStates(int instance, const int* operations, int operationCo
 /* out4 = {beagleBastaSampleStates calls so far, kernel launches of the last one per chunk of replicates (its depth in coalescences),
  * chunks of replicates of the last one, chains of the last one}. */
 int beagleBastaStatesStats(int instance, long* out4);
-/* The gradient natives of BastaJNIWrapper: not built, BEAGLE_ERROR_NO_IMPLEMENTATION. */
+/* The gradient of the log-density beagleBastaAccumulatePartials returns, with respect to the migration rates and the population sizes, in
+ * one call (an extension, as beagleBastaSampleStates: the reference does not define what BastaJNIWrapper's gradient natives compute — its
+ * GRADIENT-mode reduction calls the likelihood native — but it does pin the arithmetic of the pure-Java delegate,
+ * GenericBastaLikelihoodDelegate.peelPartialsGrad :443-534, peelPopSizeSGrad :536-603, reduceWithinIntervalGrad :680-753,
+ * reduceAcrossIntervalsGrad / ...GradPopSize :622-678).  The Java code carries S^2 tangent vectors per buffer forwards, O(N S^4); the same
+ * numbers come out of ONE adjoint sweep at the cost of a likelihood, O(N S^2), and that is what this call runs.  It reads the vectors,
+ * matrices and coalescent probabilities as beagleBastaUpdatePartials of the same list left them, forms e, f, g, h itself (as
+ * beagleBastaAccumulatePartials does: beagleBastaGetBuffer reads the same afterwards), and uploads no list that is already resident.
+ *
+ * The rule.  For an operation {dest, in1, m1, in2, m2, acc1, acc2, number} of list interval k: V[x] the stored vector of buffer x,
+ * theta_i = 1 / size_i, J = probabilities[number], len_k = intervalLengths[k], t_k = intervalDistances[k] (the rate-scaled length the
+ * interval's matrices were formed with, TransitionMatrixOperation.time), e and g the sums of the interval's start and end vectors as
+ * beagleBastaAccumulatePartials forms them.  For a one-input operation acc1 == dest, so "the end vector of side 0" is V[acc1] in both
+ * kinds of operation.  The log-density is
+ *     L = sum_k [ -len_k / 4 sum_i (e_i^2 - f_i + g_i^2 - h_i) theta_i + log J_k ].
+ * Lambda[x] = dL / dV[x] with every buffer treated as free.  With c_k = (-len_k / 2) theta (a vector), walking the list in reverse:
+ *     start vectors (in1, in2) receive the direct term  c_k (e_k - V[x]),   end vectors (acc1, acc2)  c_k (g_k - V[x]);
+ *     one-input operation:  Lambda[dest] = (what its reader left, 0 for a root) + the end term;
+ *                           Lambda[in1]  = M1^T Lambda[dest] + the start term;
+ *     coalescence:          w = ((Lambda[dest] - <Lambda[dest], V[dest]>) + 1) / J        (Lambda[dest]: what its reader left, 0 for a root)
+ *                           Lambda[acc1] = (w V[acc2]) theta + the end term,   Lambda[acc2] = (w V[acc1]) theta + the end term,
+ *                           Lambda[in1]  = M1^T Lambda[acc1] + the start term,  Lambda[in2] = M2^T Lambda[acc2] + the start term.
+ * (M^T x)_j = sum_i M[i][j] x_i and <x, y> = sum_i x_i y_i run in index order from 0; products are rounded before they are added (no
+ * fused multiply-add), so Lambda is a function of the inputs alone, bit for bit.  The outputs:
+ *     outPopulationSizes [S], with respect to theta (the reference's intermediate; d/dN_a = -G_a / N_a^2 is the caller's chain rule):
+ *         G[a] = sum_k ( (-len_k / 4) (((e^2 - f) + g^2) - h)_{k,a} + sum over the interval's coalescences of (w_a V[acc1]_a) V[acc2]_a )
+ *     outMigration [S * S], row-major a * S + b, the reference's first-order form dP ~ t P E_ab (for the stored, transposed matrices:
+ *         row b += t * row a):      W[a][b] = sum_k sum over the interval's operations and their sides of (t_k V[acc]_a) Lambda[acc]_b
+ *     outAdjoints [partialsBufferCount * S]: Lambda, 0 for a buffer the list does not touch.
+ * Inside an interval the operations are added in list order (side 0 before side 1), then the intervals in index order
+ * from 0: the same bits on every call, whatever the launch geometry.
+ * The chain rule to the rates (StructuredCoalescentLikelihoodGradient.java:134-154) is the caller's too.
+ *
+ * Two defects of the reference are NOT part of the contract.  MigrationRateGradientDispatch.clearStorage is empty (:274) while
+ * peelPartialsGrad accumulates with += into stale storage (:508), so a second Java call returns other numbers: the contract is what a
+ * FIRST call on zeroed storage computes.  And `sizesOffset *= sizesOffset * stateCount` (:496, :570) is 0 for the only offset ever
+ * passed (0), which is what is restated.
+ *
+ * intervalDistances may be NULL when outMigration is NULL.  Each output may be NULL, not all.  flags: none defined, pass 0.
+ * Kernel launches: one per level of coalescences plus four (e-h and their total, the two reductions); beagleBastaGradientStats.
+ * BEAGLE_ERROR_NO_IMPLEMENTATION: the sharded handle, an instance without BASTA buffers, more than 256 states, a list
+ * beagleBastaSampleStates refuses.  BEAGLE_ERROR_OUT_OF_RANGE: a bad index, no operation, no output, no lengths, unknown flag bits,
+ * coalescentBufferCount < 5.  BEAGLE_ERROR_FLOATING_POINT: a returned value is not finite (a coalescence with J = 0); the outputs are
+ * written then too, and in no other case but success. */
+int beagleBastaGradient(int instance, const int* operations, int operationCount, const int* intervals, int intervalCount,
+                        const double* intervalLengths, const double* intervalDistances, int populationSizesIndex,
+                        int coalescentProbabilityIndex, int flags, double* outPopulationSizes, double* outMigration, double* outAdjoints);
+/* out4 = {beagleBastaGradient calls so far, kernel launches of the last one, its levels of coalescences, its chains}. */
+int beagleBastaGradientStats(int instance, long* out4);
+/* The gradient natives of BastaJNIWrapper: not built, BEAGLE_ERROR_NO_IMPLEMENTATION (the gradient: beagleBastaGradient). */
 int beagleBastaUpdatePartialsGrad(int instance, const int* operations, int operationCount, const int* intervals, int intervalCount,
                                   int populationSizesIndex, int coalescentProbabilityIndex);
 int beagleBastaUpdateTransitionMatricesGrad(int instance, const int* transitionMatrixIndices, const double* branchLengths, int count);
