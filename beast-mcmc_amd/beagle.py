@@ -124,7 +124,7 @@ ABI_SYMBOLS = ["beagleGetVersion", "beagleGetCitation", "beagleGetResourceList",
               ["beagle" + k for k in _PROTOS] + \
               ["beagleMi355SetStream", "beagleMi355CalculateRootLogLikelihoodsDevice", "beagleMi355Synchronize",
                "beagleMi355KernelTimer", "beagleMi355DeviceBytes", "beagleMi355WalkStats", "beagleMi355GradientStats", "beagleMi355GetPartialsBatch", "beagleMi355SampleAncestralStates", "beagleMi355SampleMarkovJumps", "beagleMi355SampleMarkovJumpsUniformized",
-               "beagleMi355SimulateSequences", "beagleMi355SimulateCompleteHistories", "beagleMi355RobustCounts", "beagleMi355SimulateUnconditionedCounts", "beagleMi355NodeHeightDerivatives", "beagleMi355UpdateDifferentialMatrices", "beagleMi355SetTipEmission", "beagleMi355TipEmissionStats",
+               "beagleMi355SimulateSequences", "beagleMi355SimulateCompleteHistories", "beagleMi355RobustCounts", "beagleMi355SimulateUnconditionedCounts", "beagleMi355NodeHeightDerivatives", "beagleMi355UpdateDifferentialMatrices", "beagleMi355SetReversibleModels", "beagleMi355GetEigenDecomposition", "beagleMi355EigenStats", "beagleMi355SetTipEmission", "beagleMi355TipEmissionStats",
                "beagleMi355GetPartialsPinned", "beagleMi355GetSiteLogLikelihoodsPinned",
                "beagleMi355KernelTimerCalls", "beagleMi355WalkHealth", "beagleMi355RepeatStats", "beagleMi355WalkLaunchInfo", "beagleMi355RootFusedCount", "beagleMi355SitePrefetchCount", "beagleMi355KernelTimerRestart", "beagleMi355GetDimensions", "beagleMi355GetCommUniqueId", "beagleMi355CommInit", "beagleMi355CommInfo", "beagleMi355CalculateRootLogLikelihoodsAllReduce"] + \
               ["beagleBasta" + k for k in ("AllocateCoalescentBuffers", "UpdatePartials", "AccumulatePartials", "GetBuffer", "GetBufferLength", "Stats", "SampleStates", "StatesStats",
@@ -197,6 +197,7 @@ class Beagle:
         self.lib = library or engine()
         self._f = self.lib.fn
         self.stateCount, self.patternCount, self.categoryCount = stateCount, patternCount, categoryCount
+        self.eigenComplex = bool(requirementFlags & FLAG_EIGEN_COMPLEX)          # (eigenvalue arrays are [S real | S imaginary parts])
         self.details = InstanceDetails()
         rl = _i(list(resourceList)) if resourceList is not None else None
         h = self._f["CreateInstance"](tipCount, partialsBufferCount, compactBufferCount, stateCount, patternCount,
@@ -687,6 +688,38 @@ class Beagle:
                 raise ValueError("every per-branch list must have one entry per branch")
         f = self._ext("beagleMi355UpdateDifferentialMatrices", [C.c_int, _IP, _IP, _DP, C.c_int, _IP, _IP, _DP, C.c_int, C.c_int])
         self._check("updateDifferentialMatrices", f(self.instance, _ip(e), _ip(r), _dp(q), q.shape[0], _ip(d), _ip(m), _dp(t), n, int(mode)))
+
+    def setReversibleModels(self, eigenIndices, relativeRates, frequencies):
+        """The eigen systems of time-reversible models, decomposed on the device in one call (include/beagle_mi355.h
+        beagleMi355SetReversibleModels): model k — ``relativeRates[k]`` [S (S - 1) / 2], the upper triangle in row order, and
+        ``frequencies[k]`` [S] — into eigen slot ``eigenIndices[k]``, which then holds what setEigenDecomposition would have been
+        handed.  Nothing comes back and the host does not wait."""
+        S = self.stateCount
+        e = _i(eigenIndices).reshape(-1)
+        r = _d(relativeRates).reshape(-1, S * (S - 1) // 2) if S > 1 else _d(np.zeros((e.size, 0)))
+        f = _d(frequencies).reshape(-1, S)
+        if r.shape[0] != e.size or f.shape[0] != e.size:
+            raise ValueError("one row of rates and one of frequencies per eigen index")
+        fn = self._ext("beagleMi355SetReversibleModels", [C.c_int, _IP, C.c_int, _DP, _DP, C.c_int])
+        self._check("setReversibleModels", fn(self.instance, _ip(e), e.size, _dp(r), _dp(f), 0))
+
+    def getEigenDecomposition(self, eigenIndex, complex_eigen=None):
+        """-> (U [S][S], U^-1 [S][S], eigenvalues [S], or [2 S] on an EIGEN_COMPLEX instance) of an eigen slot, however it was filled
+        (include/beagle_mi355.h beagleMi355GetEigenDecomposition).  Drains the instance's stream.  ``complex_eigen``: for a binding
+        attached to an instance it did not create (default: as this binding created it)."""
+        S = self.stateCount
+        if complex_eigen is None:
+            complex_eigen = getattr(self, "eigenComplex", False)
+        u, ui, lam = np.empty((S, S)), np.empty((S, S)), np.empty(2 * S if complex_eigen else S)
+        fn = self._ext("beagleMi355GetEigenDecomposition", [C.c_int, C.c_int, _DP, _DP, _DP])
+        self._check("getEigenDecomposition", fn(self.instance, eigenIndex, _dp(u), _dp(ui), _dp(lam)))
+        return u, ui, lam
+
+    def eigenStats(self):
+        """What setReversibleModels has done (include/beagle_mi355.h beagleMi355EigenStats)."""
+        out = (C.c_longlong * 4)()
+        self._check("eigenStats", self._ext("beagleMi355EigenStats", [C.c_int, C.POINTER(C.c_longlong)])(self.instance, out))
+        return {"calls": int(out[0]), "models": int(out[1]), "max_sweeps": int(out[2]), "capped": int(out[3])}
 
     def sampleMarkovJumps(self, nodes, branchTimes, branchRates, eigenIndex, categoryRatesIndex, categoryWeightsIndex,
                           stateFrequenciesIndex, registers, registerFlags, seed, map=False, states=False, jumps=False,

@@ -13,6 +13,7 @@
 //   engine_nodeheight.cpp  node-height gradients and diagonal Hessians in one call
 //   engine_tipemission.cpp  tip error models: emission tables folded into the tip branch matrices
 //   engine_differential.cpp  substitution-parameter differential matrices of every branch in one call
+//   engine_eigen.cpp     eigen systems of reversible models decomposed on the device in one call, an eigen slot back to the host
 //   engine_stats.cpp     stream, synchronisation, kernel timer, counters
 // each of them argument checks, buffer bookkeeping and one call into the files above.
 // All arithmetic is in the .hip files; these files validate indices, resolve buffer indices to device pointers and enqueue
@@ -296,6 +297,8 @@ struct Instance {
     DevBuf robustDev;                                    // robust counts, on the call's first instance (engine_robustcounts.cpp): robustLayout / unconditionedLayout
     DevBuf historyDev;                                   // complete histories (engine_history.cpp): historyLayout
     DevBuf differentialDev;                              // differential matrices (engine_differential.cpp): the rotated dQ of a call, [pairs][S][S] doubles
+    DevBuf eigenSweepsDev;                               // reversible-model decompositions (engine_eigen.cpp): the sweeps of the last call's models, ints
+    long statEigenCalls = 0, statEigenModels = 0; int eigenLastCount = 0;      // (beagleMi355EigenStats)
     // BASTA structured coalescent (beagleBastaAllocateCoalescentBuffers, engine_basta.cpp): null on every other instance
     Basta* basta = nullptr;
     // tip error models (beagleMi355SetTipEmission, engine_tipemission.cpp): null on an instance that was never given an emission table

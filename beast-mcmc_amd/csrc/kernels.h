@@ -336,6 +336,14 @@ void launchDifferentialExact(hipStream_t stream, double* matrices, const double*
 void launchDifferentialFirstOrder(hipStream_t stream, double* matrices, const double* rates, const double* dQ, const int* dIdx,
                                   const double* dLen, const int* dRate, const int* dDiff, int count, int S, int C);
 
+// ---- eigen systems of time-reversible models (kernels_eigen.hip; beagleMi355SetReversibleModels) ------------------------------
+constexpr int EIGEN_SWEEP_CAP = 30;          // Jacobi sweeps after which a model counts as failed (its eigenvalues become NaN)
+// `count` models, model k from models[k] = {relative rates [S (S - 1) / 2], upper triangle in row order | frequencies [S]} into eigen
+// slot slots[k] (U | U^-1 | lambda, [S] more zeros on a complex instance); sweeps[k] = the sweeps it took, negated when it hit the cap.
+// 2 <= S <= 64.  false: the kernel's LDS was not granted (nothing is launched).
+bool launchEigenReversible(hipStream_t stream, double* eigen, const double* models, const int* slots, int* sweeps, int count, int S,
+                           bool complexEigen);
+
 // One dependency level of pruning operations: `nOps` independent ops, descriptors on the device.
 // maxRange = max over ops of (pEnd - pStart).
 void launchPruneLevel(hipStream_t stream, const OpDesc* dOps, int nOps, const double* matrices,

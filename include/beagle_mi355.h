@@ -441,6 +441,33 @@ int beagleMi355NodeHeightDerivatives(int instance, const int* nodes, const doubl
 int beagleMi355UpdateDifferentialMatrices(int instance, const int* eigenIndices, const int* categoryRatesIndices,
                                           const double* inDifferentials, int differentialCount, const int* differentialIndices,
                                           const int* matrixIndices, const double* edgeLengths, int count, int mode);
+/* Eigen systems of time-reversible models, decomposed on the device in ONE call — what the caller of beagleSetEigenDecomposition
+ * computes per model on the host (SubstitutionModelDelegate.java:272-288; BaseSubstitutionModel.java:256-289, 314-319) and uploads with
+ * one call per model.  After it, eigen slot eigenIndices[k] holds what beagleSetEigenDecomposition would have been handed for model k.
+ *   relativeRates [count][S (S - 1) / 2]: the upper triangle of r in row order;  frequencies [count][S].
+ * Q_ij = r_ij pi_j (i != j), rows summing to zero; n = -sum_i pi_i Q_ii; A_ij = sqrt(pi_i) r_ij sqrt(pi_j), A_ii = Q_ii (symmetric by
+ * construction); A = V diag(mu) V^T by cyclic Jacobi in a fixed rotation order (csrc/kernels_eigen.hip), to off(A) <= eps ||A||_F;
+ * U = Pi^-1/2 V, U^-1 = V^T Pi^1/2, lambda = mu / n, eigenvalues ascending with columns and rows to match; the S imaginary parts of an
+ * EIGEN_COMPLEX instance are zeros.  A model that has not converged after 30 sweeps (none is known to need more than 8) gets NaN
+ * eigenvalues — a likelihood behind it answers BEAGLE_ERROR_FLOATING_POINT — and is counted by beagleMi355EigenStats.
+ * The call is queued behind everything queued on the instance; nothing is read back and the host does not wait.  A held-back
+ * pre-order list stays held.  A later beagleSetEigenDecomposition into a written slot is always uploaded.  Input goes through the
+ * staging ring; a list over half the ring is split into several launches, so no list is refused for its size.  A slot receives the
+ * same bits whatever else the call lists, in whatever order or split, and on every shard: the sharded handle gives the call to every
+ * shard (eigen systems are replicated).
+ * BEAGLE_ERROR_OUT_OF_RANGE for a NULL pointer, count < 0, an index outside the eigen buffers or named twice, non-zero flags, a
+ * frequency that is not finite and > 0, a rate that is not finite and >= 0, a model whose n is not finite and > 0;
+ * BEAGLE_ERROR_NO_IMPLEMENTATION with more than 64 states.  Everything is checked before anything is queued: a refused call leaves
+ * every slot as it was.  count == 0: success, nothing is launched.  An extension: no BEAST class calls it today. */
+int beagleMi355SetReversibleModels(int instance, const int* eigenIndices, int count, const double* relativeRates,
+                                   const double* frequencies, int flags);
+/* Eigen slot eigenIndex back on the host, however it was filled: outEigenVectors and outInverseEigenVectors [S][S], outEigenValues [S]
+ * ([2 S] on an EIGEN_COMPLEX instance).  Drains the instance's stream.  The sharded handle reads shard 0. */
+int beagleMi355GetEigenDecomposition(int instance, int eigenIndex, double* outEigenVectors, double* outInverseEigenVectors,
+                                     double* outEigenValues);
+/* out4 = {beagleMi355SetReversibleModels calls since creation, models they decomposed, the most Jacobi sweeps a model of the last call
+ * took, models of the last call that hit the cap of 30} (shard 0 of a sharded handle).  Drains the instance's stream. */
+int beagleMi355EigenStats(int instance, long long* out4);
 /* Markov jumps: ONE call that draws the ancestral states as beagleMi355SampleAncestralStates does and, for every register k, row
  * r >= 1 and pattern p, forms the expected number of registered substitutions (a count register) or the expected reward (a reward
  * register) on row r's branch, conditioned on the drawn parent and child states — what MarkovJumpsBeagleTreeLikelihood.hookCalculation
