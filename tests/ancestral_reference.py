@@ -34,6 +34,26 @@ def uniforms(seed, rows, patterns, pattern_count, kind):
     return (splitmix64(seed, ctr) >> np.uint64(11)).astype(np.float64) * 2.0 ** -53
 
 
+UNDECIDED = 1e-8
+
+
+def near_a_boundary(weights, u, use_map, tol=UNDECIDED):
+    """bool, of the weights' shape: the draw would come out differently under a relative change of `tol` in the weights — some running
+    sum lies within tol x total of u x total, or (use_map) the largest and the second-largest weight lie within tol x total."""
+    total = np.zeros_like(weights[0])
+    for w in weights:
+        total = total + w
+    if use_map:
+        top = np.sort(np.stack(weights), axis=0)[-2:]
+        return (top[1] - top[0]) <= tol * total
+    near = np.zeros(total.shape, dtype=bool)
+    cum = np.zeros_like(total)
+    for w in weights:
+        cum = cum + w
+        near |= np.abs(u * total - cum) <= tol * total
+    return near
+
+
 def draw_choice(weights, u, use_map):
     """weights: list of n arrays (one per choice, all of one shape), u: array of that shape -> (choice int64, bad bool)."""
     total = np.zeros_like(weights[0])
@@ -59,12 +79,13 @@ def draw_choice(weights, u, use_map):
 
 
 def sample(rows, partials_of, matrix_of, tip_states_of, is_compact, category_weights, frequencies, seed, use_map=False,
-           patterns=None, pattern_count=None):
+           patterns=None, pattern_count=None, undecided=None):
     """The draw for `rows` ([n][3] {buffer, matrix, parentRow}, root first).
 
     partials_of(buffer) -> [C, P, S] as getPartials(buffer, NONE) returns it; matrix_of(matrix) -> [C, S, S] (getTransitionMatrix);
     tip_states_of(buffer) -> [P] (getTipStates); is_compact(buffer) -> bool.  `patterns`: restate only these pattern indices
     (default all); `pattern_count`: the alignment's P (the random-number counter's stride; default the partials' P).
+    `undecided`: a bool array [len(patterns)] that is set where some draw of the pattern lies `near_a_boundary`.
     -> (states uint8 [n, len(patterns)], categories int32 [len(patterns)], any_bad)."""
     rows = np.asarray(rows, dtype=np.int64).reshape(-1, 3)
     root = partials_of(int(rows[0, 0]))
@@ -82,12 +103,16 @@ def sample(rows, partials_of, matrix_of, tip_states_of, is_compact, category_wei
                 s = s + root[c, pats, k]
             wc.append(s * category_weights[c])
         cats, bad = draw_choice(wc, uniforms(seed, 0, pats, GP, 1), use_map)
+        if undecided is not None:
+            undecided |= near_a_boundary(wc, uniforms(seed, 0, pats, GP, 1), use_map)
         any_bad |= bool(bad.any())
     else:
         cats = np.zeros(len(pats), dtype=np.int64)
     states = np.zeros((len(rows), len(pats)), dtype=np.uint8)
     rp = root[cats, pats, :]
     s0, bad = draw_choice([rp[:, i] * frequencies[i] for i in range(S)], uniforms(seed, 0, pats, GP, 0), use_map)
+    if undecided is not None:
+        undecided |= near_a_boundary([rp[:, i] * frequencies[i] for i in range(S)], uniforms(seed, 0, pats, GP, 0), use_map)
     any_bad |= bool(bad.any())
     states[0] = s0
     for r in range(1, len(rows)):
@@ -98,12 +123,16 @@ def sample(rows, partials_of, matrix_of, tip_states_of, is_compact, category_wei
             tip = np.asarray(tip_states_of(b))[pats].astype(np.int64)
             drawn, bad = draw_choice([M[:, i] for i in range(S)], u, use_map)
             unknown = tip >= S
+            if undecided is not None:
+                undecided |= unknown & near_a_boundary([M[:, i] for i in range(S)], u, use_map)
             any_bad |= bool((bad & unknown).any())
             states[r] = np.where(unknown, drawn, tip)
         else:
             part = partials_of(b)[cats, pats, :]
             drawn, bad = draw_choice([part[:, i] * M[:, i] for i in range(S)], u, use_map)
             any_bad |= bool(bad.any())
+            if undecided is not None:
+                undecided |= near_a_boundary([part[:, i] * M[:, i] for i in range(S)], u, use_map)
             states[r] = drawn
     return states, cats.astype(np.int32), any_bad
 

@@ -1,14 +1,35 @@
 """Seeded random call sequences over the single-partition ``beagle.Beagle`` method set, to be run on the engine and the CPU oracle in
 lockstep (tests/test_gpu_call_sequences.py) or on the oracle alone (tests/test_call_sequences_host.py).
 
-The generator is plain Python and numpy: it loads neither library.  ``generate(shape, seed, length)`` returns call records
+The generator is plain Python and numpy: it loads neither library (the extension profile takes the threshold guard of its differential
+matrices from tests/differential_matrices_reference.py).  ``generate(shape, seed, length, profile)`` returns call records
 
-    {"m": method of beagle.Beagle, "a": [arguments as plain lists / numbers], "action": name in ACTIONS, "motif": letter or None,
-     "variant": variant of motif (d) / (f) or None}
+    {"m": method of beagle.Beagle, "a": [arguments as plain lists / numbers], "action": name in ACTIONS (+ ACTIONS_EXT), "motif": letter
+     or None, "variant": variant of a motif that has variants, or None}
 
-which survive a JSON round trip unchanged (``dump`` / ``load``).  ``execute(b, record, side)`` makes one call on a binding object and
-returns (return code, reads), a read being (kind, array); ``deviation(kind, got, want)`` is the normalised error of a read, so that one
-bound (1e-10) holds for every kind.
+which survive a JSON round trip unchanged (``dump`` / ``load``; a profile other than "base" travels in the file).  ``execute(b,
+record, side)`` makes one call on a binding object and returns (return code, reads), a read being (kind, array); ``deviation(kind,
+got, want)`` is the normalised error of a read, so that one bound (1e-10) holds for every kind.
+
+Two profiles.  "base" (the default) is the method set of ACTIONS with motifs (a)-(i); its sequences are pinned record for record by
+tests/golden/call_sequence_digests.json.  "extensions" (shapes of at most 64 states) adds ACTIONS_EXT — the one-call entry points
+sampleAncestralStates, sampleMarkovJumps, simulateSequences, nodeHeightDerivatives, updateDifferentialMatrices, setReversibleModels
+and getEigenDecomposition, each of which decides for itself what happens to the deferred state (whether a held pre-order list runs,
+whether unstored nodes are materialised, whether a folded tip is demoted, whether an upload shadow is cleared) — and motifs
+  (j) a held whole-tree pre-order list, one of five of those calls, the edge derivatives' sums;
+  (k) setReversibleModels(slot), every branch matrix from that slot, partials, a root call, Markov jumps on that slot (variant
+      "reupload": the slot's previous values uploaded behind the device's write — an upload that must not be skipped);
+  (l) a sampler right behind a whole-tree list with flipped buffers and no root call (variants with setTipEmission on a tip first);
+  (m) a differential matrix written by the device over a branch matrix that the held list reads, the matrix put back, the child's
+      pre-order partial read.
+The oracle has none of these calls: ``execute_extension`` makes them from its own calls and the numpy restatements that the
+extensions' own tests use.  New kinds of read: "states" / "cats" (a draw: equal on every decided pattern — ancestral_reference
+.near_a_boundary — with at most UNDECIDED_CAP of a sequence's (sampler call, pattern) pairs undecided), "exact" (the device's draw
+against the restatement over what the SAME instance reads back after the call: byte for byte), "jumps" (Markov-jump values, restated
+for the device's own states), "eigen" (an eigen system through what it reconstructs); node-height derivatives are "deriv".  The
+generator also tracks, for these calls, which (eigen slot, rate slot, length) every branch matrix was built from and whether that
+slot has changed since (sampleMarkovJumps is emitted over matrices of one unchanged pair only), and what kind of matrix a
+differential slot holds (nodeHeightDerivatives wants Q x category rate).
 
 Instance layout for T tips, N = 2T - 1 nodes (``Layout``): internal node n lives in partials buffer T + j (T - 1) + (n - T) of set j
 (j flips per node each time the node is written, as BufferIndexHelper does), its pre-order partials in T + 2 (T - 1) + n; the branch
@@ -21,7 +42,8 @@ also whether it holds the factors of a rescaling operation, "raw", or accumulate
 by raw factors only, accumulate / remove add into log buffers only), and which scale buffer each partials buffer was last written
 with.  Reads and consuming calls are emitted on defined inputs only, and never what the contract leaves open: an operation writing one
 of its own children, convolve / transpose onto an input, accumulate of a never-written buffer, a root call with count != 1, derivative
-indices to updateTransitionMatrices.  Branch matrices are always non-negative (differential matrices stay in their two spare slots).
+indices to updateTransitionMatrices.  Branch matrices are non-negative whenever something consumes them (differential matrices stay
+in their two spare slots, but for motif (m), which puts the branch's matrix back before any consumer).
 
 Replay of a failing sequence:  python tests/call_sequences.py --replay FILE --upto N  runs engine and oracle up to step N and prints
 the first diverging read; it stops at the first non-zero return code or exception.
@@ -46,16 +68,42 @@ ACTIONS = (
     "setRootPrePartials", "updatePrePartials", "setDifferentialMatrix", "calculateEdgeDifferentials",
     "calculateCrossProductDifferentials", "getPartials:pre",
 )
+# profile "extensions": the one-call entry points of include/beagle_mi355.h that sit on top of the deferral logic
+ACTIONS_EXT = ("sampleAncestralStates", "sampleMarkovJumps", "simulateSequences", "nodeHeightDerivatives", "updateDifferentialMatrices",
+               "setReversibleModels", "getEigenDecomposition")
+PROFILES = ("base", "extensions")
+EXT_MAX_STATES = 64                        # several of them answer NO_IMPLEMENTATION above 64 states
 EMISSION_STATES = (4, 20)                  # setTipEmission: 4- and 20-state shapes only
 MOTIFS = "abcdefghi"
+MOTIFS_EXT = "jklm"
+J_VARIANTS = ("updateDifferentialMatrices", "setReversibleModels", "nodeHeightDerivatives", "sampleAncestralStates", "simulateSequences")
+K_VARIANTS = ("plain", "reupload")
+L_VARIANTS = ("ancestral", "jumps", "emission_ancestral", "emission_jumps")
+SITE_COUNTS = (1, 5, 130, 259)             # simulateSequences: across the four-sites-per-thread word and a workgroup
+JUMPS_REWARDS, JUMPS_SCALE_BY_TIME = 1, 2
+UNDECIDED_CAP = 0.01                       # of a sequence's (sampler call, pattern) pairs
 D_VARIANTS = ("getPartials", "getPartialsBatch", "getSiteLogLikelihoods", "getLogScaleFactors", "resetScaleFactors", "copyScaleFactors",
               "setTransitionMatrix", "setCategoryWeights")
 F_VARIANTS = ("read_pre", "read_post", "write_post", "write_matrix", "write_pre", "scale_call", "model_call", "root_call")
 HOST_COPY_MAX = 12                         # uploads one launch carries (motif c queues more)
 
 
-def actions_for(S):
-    return tuple(a for a in ACTIONS if a != "setTipEmission" or S in EMISSION_STATES)
+def actions_for(S, profile="base"):
+    base = tuple(a for a in ACTIONS if a != "setTipEmission" or S in EMISSION_STATES)
+    return base + ACTIONS_EXT if profile == "extensions" else base
+
+
+def motifs_for(profile="base"):
+    return MOTIFS + MOTIFS_EXT if profile == "extensions" else MOTIFS
+
+
+def variants_for(S, profile="base"):
+    """every (motif, variant) that a 4-state shape's seeds hold together: of motifs (d) and (f) over the base profile's 8 seeds, of (j),
+    (k) and (l) over the extension profile's 4 (of (l), the two emission variants exist at 4 and 20 states)"""
+    if profile != "extensions":
+        return set(("d", v) for v in D_VARIANTS) | set(("f", v) for v in F_VARIANTS)
+    out = set(("j", v) for v in J_VARIANTS) | set(("k", v) for v in K_VARIANTS)
+    return out | set(("l", v) for v in (L_VARIANTS if S in EMISSION_STATES else L_VARIANTS[:2]))
 
 
 class Layout:
@@ -99,6 +147,11 @@ def reversible_model(rng, S):
     r = rng.uniform(0.5, 1.5, size=(S, S))
     r = np.triu(r, 1)
     r = r + r.T
+    return decompose_reversible(r, pi)
+
+
+def decompose_reversible(r, pi):
+    """the same from symmetric exchange rates r [S][S] and frequencies: numpy's eigh of the symmetric form"""
     q = r * pi[None, :]
     q -= np.diag(q.sum(axis=1))
     q /= -np.dot(pi, np.diag(q))
@@ -107,8 +160,18 @@ def reversible_model(rng, S):
     return v / d[:, None], v.T * d[None, :], lam, pi, q
 
 
+def symmetric_rates(upper, S):
+    """the upper triangle in row order (what setReversibleModels takes) -> symmetric [S][S], zero diagonal"""
+    r = np.zeros((S, S))
+    r[np.triu_indices(S, 1)] = np.asarray(upper, dtype=float)
+    return r + r.T
+
+
 class Generator:
-    def __init__(self, shape, seed, length):
+    def __init__(self, shape, seed, length, profile="base"):
+        if profile not in PROFILES or (profile == "extensions" and shape[0] > EXT_MAX_STATES):
+            raise ValueError("profile %r at %d states" % (profile, shape[0]))
+        self.profile = profile
         self.L = L = Layout(shape)
         self.shape, self.seed, self.length = tuple(shape), seed, length
         self.rng = np.random.default_rng([seed, L.S, L.C, L.T, L.P])
@@ -148,6 +211,11 @@ class Generator:
         self.last_list = None
         self.last_pre = None
         self.d_count = self.f_count = 0
+        # what the extension actions need to know (no random number is drawn for it: the base profile's records do not depend on it)
+        self.eigen_version = [0, 0]             # bumped whenever an eigen slot's content may have changed
+        self.rates_version = [0, 0]
+        self.mfrom = [None] * L.matrix_count    # (eigen slot, its version, rate slot, its version, length) a probability matrix was built from
+        self.dkind = {}                         # differential slot -> "Qrate" (Q x category rate), "QQ" or "D" (written by the device)
 
     # ---- records ---------------------------------------------------------------------------------------------------------------
     def emit(self, method, args, action):
@@ -191,10 +259,12 @@ class Generator:
         if not same or self.models[slot] is None:
             self.models[slot] = reversible_model(self.rng, self.L.S)
         u, ui, lam, _, _ = self.models[slot]
+        self.eigen_version[slot] += 1
         self.emit("setEigenDecomposition", [slot, _lst(u.ravel()), _lst(ui.ravel()), _lst(lam)], "setEigenDecomposition")
 
     def set_rates(self, slot, indexed):
         self.rates[slot] = self.category_rates()
+        self.rates_version[slot] += 1
         if indexed or slot != 0:
             self.emit("setCategoryRatesWithIndex", [slot, self.rates[slot]], "setCategoryRatesWithIndex")
         else:
@@ -300,9 +370,12 @@ class Generator:
             self.emit("updateTransitionMatricesWithMultipleModels", [e, r, slots, None, None, lengths, len(slots)],
                       "updateTransitionMatricesWithMultipleModels")
         else:
-            self.emit("updateTransitionMatrices", [int(rng.integers(2)) if eigen is None else eigen, slots, None, None, lengths, len(slots)], action)
-        for m in slots:
+            e = [int(rng.integers(2)) if eigen is None else eigen] * len(slots)
+            r = [0] * len(slots)
+            self.emit("updateTransitionMatrices", [e[0], slots, None, None, lengths, len(slots)], action)
+        for k, m in enumerate(slots):
             self.mdef[m] = "prob"
+            self.mfrom[m] = (e[k], self.eigen_version[e[k]], r[k], self.rates_version[r[k]], lengths[k])
         return slots
 
     def prob_slots(self):
@@ -313,6 +386,7 @@ class Generator:
             m = self.prob_slots()[int(self.rng.integers(len(self.prob_slots())))] if self.rng.random() < 0.7 else self.L.spare[int(self.rng.integers(2))]
         self.emit("setTransitionMatrix", [m, self.random_matrix(), 1.0], "setTransitionMatrix")
         self.mdef[m] = "prob"
+        self.mfrom[m] = None
         return m
 
     def triples(self, method, result=None):
@@ -334,6 +408,7 @@ class Generator:
         self.emit(method, [first, second, res, n], method)
         for m in res:
             self.mdef[m] = "prob"
+            self.mfrom[m] = None
 
     def transpose(self):
         L, rng = self.L, self.rng
@@ -343,6 +418,7 @@ class Generator:
         self.emit("transposeTransitionMatrices", [a, L.spare[:k], k], "transposeTransitionMatrices")
         for m in L.spare[:k]:
             self.mdef[m] = "prob"
+            self.mfrom[m] = None
 
     def get_matrix(self, m=None):
         slots = [m for m in range(self.L.matrix_count) if self.mdef[m]]
@@ -620,6 +696,7 @@ class Generator:
         m = np.concatenate([(q * r ** (k + 1)).ravel() for r in self.rates[slot]])
         self.emit("setDifferentialMatrix", [L.spare[2 + k], _lst(m)], "setDifferentialMatrix")
         self.mdef[L.spare[2 + k]] = "diff"
+        self.dkind[L.spare[2 + k]] = "QQ" if k else "Qrate"
 
     def edges_with_pre(self):
         L = self.L
@@ -662,6 +739,224 @@ class Generator:
             self.update_pre()
             pool = [L.pre(n) for n in range(L.N) if self.pdef[L.pre(n)]]
         self.emit("getPartials", [pool[int(self.rng.integers(len(pool)))], NONE], "getPartials:pre")
+
+    # ---- profile "extensions": the one-call entry points --------------------------------------------------------------------
+    def a_seed(self):
+        return int(self.rng.integers(1, 2 ** 62))
+
+    def preorder_rows(self, whole=None):
+        """-> (nodes, rows {post buffer, branch matrix, parent row}, compact buffers): the pre-order list of the whole tree or of the
+        subtree under a random internal node, over the current buffers and matrices (all defined)"""
+        L, rng = self.L, self.rng
+        whole = rng.random() < 0.5 if whole is None else whole
+        top = L.root if whole else self.internal[int(rng.integers(len(self.internal)))]
+        nodes, rows, stack = [], [], [(top, NONE)]
+        while stack:
+            n, parent_row = stack.pop()
+            assert self.pdef[L.post(n, self.cur[n])] and (n == top or self.mdef[L.matrix(n, self.mcur[n])] == "prob")
+            nodes.append(n)
+            rows.append([L.post(n, self.cur[n]), 0 if n == top else L.matrix(n, self.mcur[n]), parent_row])
+            if n >= L.T:
+                stack += [(self.right[n], len(rows) - 1), (self.left[n], len(rows) - 1)]
+        return nodes, rows, [n for n in nodes if n < L.T and self.tipkind[n] == "compact"]
+
+    def sample_ancestral(self, whole=None):
+        rng = self.rng
+        _, rows, compact = self.preorder_rows(whole)
+        self.emit("sampleAncestralStates", [rows, int(rng.integers(2)), int(rng.integers(2)), self.a_seed(), bool(rng.random() < 1.0 / 3.0),
+                                            compact], "sampleAncestralStates")
+
+    def jump_source(self, nodes):
+        """the (eigen slot, rate slot) that every branch matrix of `nodes` (the first is the list's root) was built from, at the branch's
+        length and unchanged since; else None"""
+        L = self.L
+        src = set()
+        for n in nodes[1:]:
+            f = self.mfrom[L.matrix(n, self.mcur[n])]
+            if f is None or f[1] != self.eigen_version[f[0]] or f[3] != self.rates_version[f[2]] or f[4] != float(self.length_of[n]):
+                return None
+            src.add((f[0], f[2]))
+        return src.pop() if len(src) == 1 else None
+
+    def prepare_jumps(self, nodes, eigen=None):
+        """sampleMarkovJumps forms Q and the times' distances from ONE eigen slot and rate slot: every branch matrix from them, else
+        first an updateTransitionMatrices over all branches"""
+        src = self.jump_source(nodes)
+        if src is None or (eigen is not None and src[0] != eigen):
+            self.update_matrices(nodes=self.branches(), eigen=eigen)
+            src = self.jump_source(nodes)
+        return src
+
+    def sample_jumps(self, whole=None, eigen=None):
+        """one count register (every substitution weighted by a random R) and one reward register, scaled by time"""
+        L, rng = self.L, self.rng
+        nodes, rows, compact = self.preorder_rows(whole)
+        src = self.prepare_jumps(nodes, eigen)
+        rows = [[r[0], 0 if k == 0 else L.matrix(nodes[k], self.mcur[nodes[k]]), r[2]] for k, r in enumerate(rows)]    # (matrix sets may have flipped)
+        times = [0.0] + [float(self.length_of[n]) for n in nodes[1:]]
+        registers = [_lst(rng.uniform(0.0, 1.0, size=(L.S, L.S))), _lst(np.diag(rng.uniform(0.0, 2.0, size=L.S)))]
+        self.emit("sampleMarkovJumps", [rows, times, src[0], src[1], int(rng.integers(2)), int(rng.integers(2)), registers,
+                                        [0, JUMPS_REWARDS | JUMPS_SCALE_BY_TIME], self.a_seed(), bool(rng.random() < 1.0 / 3.0), compact],
+                  "sampleMarkovJumps")
+
+    def simulate(self):
+        L, rng = self.L, self.rng
+        _, rows, _ = self.preorder_rows()
+        rows = [[k, r[1], r[2]] for k, r in enumerate(rows)]               # every row's states come back, in row order
+        sites = int(SITE_COUNTS[int(rng.integers(len(SITE_COUNTS)))])
+        root = cats = None
+        if rng.random() < 1.0 / 3.0:
+            root, cats = _lst(rng.integers(0, L.S, size=sites)), _lst(rng.integers(0, L.C, size=sites))
+        self.emit("simulateSequences", [rows, sites, int(rng.integers(2)), int(rng.integers(2)), self.a_seed(), root, cats],
+                  "simulateSequences")
+
+    def node_height(self):
+        """one row per internal node whose pre-order partial is defined; the differential slot holds Q x category rate"""
+        L, rng = self.L, self.rng
+        if self.dkind.get(L.spare[2]) != "Qrate":
+            self.set_differential(0)
+        if not [i for i in self.internal if self.pdef[L.pre(i)]]:
+            self.update_pre()
+        dq = L.spare[2]
+        rows, rates, compact = [], [], []
+        for i in self.internal:
+            if not self.pdef[L.pre(i)]:
+                continue
+            j, k = self.left[i], self.right[i]
+            rows.append([L.pre(i), L.post(j, self.cur[j]), L.matrix(j, self.mcur[j]), dq, L.post(k, self.cur[k]), L.matrix(k, self.mcur[k]),
+                         dq, NONE if i == L.root else dq])
+            rates.append(_lst(rng.uniform(0.5, 2.0, size=3)))
+            compact += [t for t in (j, k) if t < L.T and self.tipkind[t] == "compact"]
+        first, second = [(True, False), (False, True), (True, True)][int(rng.integers(3))]
+        self.emit("nodeHeightDerivatives", [rows, rates, int(rng.integers(2)), first, second, sorted(set(compact))], "nodeHeightDerivatives")
+
+    def update_differential(self, slots=None, lengths=None):
+        """D of dQ = the derivative of the eigen slot's unnormalised generator in one exchange rate (rows sum to zero) into differential
+        slots, at lengths of the tree's branches; EXACT inputs are kept away from the 1e-10 thresholds (another exchange rate is drawn
+        until differential_matrices_reference.assert_guard holds)"""
+        import differential_matrices_reference as dm
+        L, rng = self.L, self.rng
+        if slots is None:
+            slots = [[L.spare[2]], [L.spare[3]], L.spare[2:]][int(rng.integers(3))]
+        e = _lst(rng.integers(0, 2, size=len(slots)))
+        r = _lst(rng.integers(0, 2, size=len(slots)))
+        mode = dm.EXACT if rng.random() < 2.0 / 3.0 else dm.FIRST_ORDER
+        dqs = []
+        for slot in sorted(set(e)):
+            u, ui, lam, pi, _ = self.models[slot]
+            for attempt in range(20):
+                a, b = sorted(_lst(rng.choice(L.S, size=2, replace=False)))
+                dq = np.zeros((L.S, L.S))
+                dq[a, b], dq[b, a] = pi[b], pi[a]
+                dq -= np.diag(dq.sum(axis=1))
+                if mode != dm.EXACT:
+                    break
+                try:
+                    dm.assert_guard(dm.rotate(u, ui, dq)[1], lam, L.S)
+                    break
+                except AssertionError:
+                    continue
+            else:
+                mode = dm.FIRST_ORDER
+            dqs.append(_lst(dq))
+        d = [sorted(set(e)).index(x) for x in e]
+        if lengths is None:
+            lengths = [float(self.length_of[self.branches()[int(rng.integers(L.N - 1))]]) for _ in slots]
+        self.emit("updateDifferentialMatrices", [e, r, dqs, d, list(slots), lengths, int(mode)], "updateDifferentialMatrices")
+        for m in slots:
+            self.mdef[m] = "diff"
+            self.mfrom[m] = None
+            self.dkind[m] = "D"
+
+    def set_reversible(self, slots=None):
+        """one or both eigen slots decomposed on the device; everything set_eigen keeps is kept here"""
+        L, rng = self.L, self.rng
+        if slots is None:
+            slots = [[0], [1], [0, 1], [1, 0]][int(rng.integers(4))]
+        rates, freqs = [], []
+        for slot in slots:
+            upper = rng.uniform(0.5, 1.5, size=L.S * (L.S - 1) // 2)
+            pi = rng.dirichlet(np.full(L.S, 20.0))
+            self.models[slot] = decompose_reversible(symmetric_rates(upper, L.S), pi)
+            self.eigen_version[slot] += 1
+            rates.append(_lst(upper))
+            freqs.append(_lst(pi))
+        self.emit("setReversibleModels", [list(slots), rates, freqs], "setReversibleModels")
+
+    def get_eigen(self, slot=None):
+        self.emit("getEigenDecomposition", [int(self.rng.integers(2)) if slot is None else slot], "getEigenDecomposition")
+
+    def gradient_set_up(self):
+        """what motifs (j) and (m) start from: a whole-tree list, a root call, the differential slot, a held whole-tree pre-order list"""
+        self.update_partials(mode="none", nodes=self.post_order(self.internal))
+        self.root_call("root", cum=False)
+        self.set_differential(0)
+        self.set_root_pre()
+        self.update_pre(whole=True)
+
+    def motif_j(self):
+        """a whole-tree updatePrePartials (held back on 4 states), one of the calls that decide for themselves whether the list runs,
+        the edge derivatives' sums (which a list still held answers); two variants per sequence"""
+        L = self.L
+        for k in (0, 1):
+            self.variant = v = J_VARIANTS[(2 * self.seed + k) % len(J_VARIANTS)]
+            self.gradient_set_up()
+            if v == "updateDifferentialMatrices":
+                self.update_differential(slots=[L.spare[3]])
+            elif v == "setReversibleModels":
+                self.set_reversible([int(self.rng.integers(2))])
+            elif v == "nodeHeightDerivatives":
+                self.node_height()
+            elif v == "sampleAncestralStates":
+                self.sample_ancestral(whole=True)
+            elif v == "simulateSequences":
+                self.simulate()
+            self.edge_differentials(want=0, all_edges=True)
+
+    def motif_k(self):
+        """a model move on the device: setReversibleModels(slot), every branch matrix from that slot, the partials, a root call, the
+        Markov jumps on that slot (Q from an eigen system the device wrote); variant "reupload": the slot's PREVIOUS values are
+        uploaded behind the device's write — an upload that a stale host shadow would skip"""
+        slot = int(self.rng.integers(2))
+        self.variant = v = K_VARIANTS[self.seed % 2]
+        previous = self.models[slot]
+        self.set_reversible([slot])
+        if v == "reupload":
+            self.models[slot] = previous
+            self.set_eigen(slot, same=True)
+        self.update_matrices(nodes=self.branches(), eigen=slot)
+        self.update_partials(mode="none", nodes=self.post_order(self.internal))
+        self.root_call("root", cum=False)
+        self.sample_jumps(whole=True, eigen=slot)
+        self.get_eigen(slot)
+
+    def motif_l(self):
+        """a sampler right behind a whole-tree list with flipped buffers and no root call (unstored nodes, a held walk); at 4 and 20
+        states also with a tip's emission table set first (a folded tip that the sampler has to demote)"""
+        L = self.L
+        pool = L_VARIANTS if L.S in EMISSION_STATES else L_VARIANTS[:2]
+        self.variant = v = pool[self.seed % len(pool)]
+        if v.startswith("emission"):
+            self.set_tip_emission()
+        if v.endswith("jumps"):
+            self.prepare_jumps([L.root] + self.branches())
+        self.update_partials(mode="none", nodes=self.post_order(self.internal))
+        if v.endswith("jumps"):
+            self.sample_jumps(whole=True)
+        else:
+            self.sample_ancestral(whole=True)
+
+    def motif_m(self):
+        """a differential matrix written over a branch matrix that the held pre-order list reads (the list has to run first), the
+        branch's matrix put back, the child's pre-order partial read"""
+        L = self.L
+        self.gradient_set_up()
+        child = self.left[L.root]
+        m = L.matrix(child, self.mcur[child])
+        self.update_differential(slots=[m], lengths=[float(self.length_of[child])])
+        self.dkind.pop(m, None)
+        self.update_matrices(nodes=[child], flip=False)
+        self.emit("getPartials", [L.pre(child), NONE], "getPartials:pre")
 
     # ---- the set-up every sequence starts with -------------------------------------------------------------------------------
     def prelude(self):
@@ -924,15 +1219,23 @@ class Generator:
             (3, "calculateEdgeDifferentials", self.edge_differentials),
             (1.5, "calculateCrossProductDifferentials", self.cross_products),
             (2, "getPartials:pre", self.get_pre_partials),
-        ]
+        ] + ([
+            (4, "sampleAncestralStates", self.sample_ancestral),
+            (4, "sampleMarkovJumps", self.sample_jumps),
+            (3, "simulateSequences", self.simulate),
+            (4, "nodeHeightDerivatives", self.node_height),
+            (4, "updateDifferentialMatrices", self.update_differential),
+            (3, "setReversibleModels", self.set_reversible),
+            (3, "getEigenDecomposition", self.get_eigen),
+        ] if self.profile == "extensions" else [])
 
-    def draw(self):
-        """one drawn action: one this sequence has not made yet while there is any (every sequence makes every action), else by weight"""
+    def draw(self, lacking_only=False):
+        """one drawn action: one this sequence has not made yet while there is any (every sequence makes every action), else by weight
+        (extension profile: half of the draws by weight all the same — what is still lacking at the end is made then)"""
         rng = self.rng
-        table = [t for t in self.table() if t[1] in actions_for(self.L.S)]
-        seen = set(r["action"] for r in self.rec[self.prelude_end:])
-        missing = [t for t in table if t[1] not in seen and t[1] not in self.gave_up]
-        if missing:
+        table = [t for t in self.table() if t[1] in actions_for(self.L.S, self.profile)]
+        missing = [t for t in table if t[1] in self.lacking()]
+        if missing and (self.profile == "base" or lacking_only or rng.random() < 0.5):
             t = missing[int(rng.integers(len(missing)))]
             if t[2]() is False:
                 if t[1] == "removeScaleFactors":
@@ -948,10 +1251,20 @@ class Generator:
             if table[k][2]() is not False:
                 return
 
+    def lacking(self):
+        """the actions this sequence has not made yet (extension profile, whose shapes have fewer seeds: not twice yet) and has not
+        given up on"""
+        need = 2 if self.profile == "extensions" else 1
+        count = {}
+        for r in self.rec[self.prelude_end:]:
+            count[r["action"]] = count.get(r["action"], 0) + 1
+        return [a for a in actions_for(self.L.S, self.profile) if count.get(a, 0) < need and a not in self.gave_up]
+
     def run(self):
         self.prelude()
         start = len(self.rec)
-        order = [MOTIFS[k] for k in self.rng.permutation(len(MOTIFS))]
+        motifs = motifs_for(self.profile)
+        order = [motifs[k] for k in self.rng.permutation(len(motifs))]
         budget = self.length
         # the motifs at seeded positions: between two of them a seeded share of the calls the weighted draw fills
         gaps = self.rng.dirichlet(np.full(len(order) + 1, 2.0))
@@ -960,17 +1273,17 @@ class Generator:
             getattr(self, "motif_" + letter)()
             self.motif = self.variant = None
         motif_calls = len(self.rec) - start
-        fill = max(4, budget - motif_calls)
+        fill = max(4 if self.profile == "base" else 60, budget - motif_calls)     # (the 13 motifs of the extension profile use the budget up)
         # (the motifs were generated to learn their size; generate again with the filler between them)
         return motif_calls, [int(round(g * fill)) for g in gaps], order
 
 
-def generate(shape, seed, length=100):
+def generate(shape, seed, length=100, profile="base"):
     """-> records.  `length`: calls after the set-up prelude, motifs included (at least what the motifs and a few drawn calls between
-    them need)."""
-    probe = Generator(shape, seed, length)
+    them need).  `profile`: "base", or "extensions" with ACTIONS_EXT and motifs (j)-(m) in the draw as well."""
+    probe = Generator(shape, seed, length, profile)
     _, gaps, order = probe.run()
-    g = Generator(shape, seed, length)
+    g = Generator(shape, seed, length, profile)
     g.rng = np.random.default_rng([seed, g.L.S, g.L.C, g.L.T, g.L.P, 1])
     g.prelude()
     for k, letter in enumerate(order):
@@ -983,23 +1296,27 @@ def generate(shape, seed, length=100):
     target = len(g.rec) + gaps[-1]
     while len(g.rec) < target:
         g.draw()
-    for _ in range(2 * len(ACTIONS)):                        # whatever action the sequence still lacks
-        seen = set(r["action"] for r in g.rec[g.prelude_end:])
-        if all(a in seen or a in g.gave_up for a in actions_for(g.L.S)):
+    for _ in range(2 * len(ACTIONS) * (2 if profile == "extensions" else 1)):          # whatever action the sequence still lacks
+        if not g.lacking():
             break
-        g.draw()
+        g.draw(lacking_only=True)
     return g.rec
 
 
-def dump(path, shape, seed, records):
+def dump(path, shape, seed, records, profile="base"):
+    """(a base sequence's file is what it always was; another profile's name travels in it)"""
+    d = {"shape": list(shape), "seed": seed, "records": records}
+    if profile != "base":
+        d["profile"] = profile
     with open(path, "w") as f:
-        json.dump({"shape": list(shape), "seed": seed, "records": records}, f)
+        json.dump(d, f)
 
 
-def load(path):
+def load(path, with_profile=False):
     with open(path) as f:
         d = json.load(f)
-    return tuple(d["shape"]), d["seed"], d["records"]
+    out = (tuple(d["shape"]), d["seed"], d["records"])
+    return out + (d.get("profile", "base"),) if with_profile else out
 
 
 # ---- running records on a binding object ---------------------------------------------------------------------------------------
@@ -1022,14 +1339,169 @@ def expanded_emission(S, P, codes, table, extra):
     return out
 
 
-def execute(b, rec, side="engine"):
+def sent(b):
+    """What the host has handed to the instance behind `b` and a restatement needs again: eigen systems, category rates and weights,
+    frequencies, pattern weights, compact tip states — kept on the binding object by ``execute``, on every side alike."""
+    if not hasattr(b, "_sent"):
+        b._sent = {"eigen": {}, "rates": {}, "weights": {}, "freqs": {}, "pattern_weights": None, "tips": {}}
+    return b._sent
+
+
+def remember(b, m, a):
+    S = b.stateCount
+    if m == "setEigenDecomposition":
+        sent(b)["eigen"][a[0]] = (np.array(a[1], dtype=float).reshape(S, S), np.array(a[2], dtype=float).reshape(S, S), np.array(a[3], dtype=float))
+    elif m == "setCategoryRates":
+        sent(b)["rates"][0] = np.array(a[0], dtype=float)
+    elif m == "setCategoryRatesWithIndex":
+        sent(b)["rates"][a[0]] = np.array(a[1], dtype=float)
+    elif m == "setCategoryWeights":
+        sent(b)["weights"][a[0]] = np.array(a[1], dtype=float)
+    elif m == "setStateFrequencies":
+        sent(b)["freqs"][a[0]] = np.array(a[1], dtype=float)
+    elif m == "setPatternWeights":
+        sent(b)["pattern_weights"] = np.array(a[0], dtype=float)
+    elif m == "setTipStates":
+        sent(b)["tips"][a[0]] = np.array(a[1], dtype=np.int32)
+    elif m == "setReversibleModels":
+        for slot, upper, pi in zip(*a):
+            sent(b)["eigen"][slot] = decompose_reversible(symmetric_rates(upper, S), np.array(pi, dtype=float))[:3]
+
+
+def packed_eigen(u, ui, lam):
+    return np.concatenate([np.ravel(u), np.ravel(ui), np.ravel(lam)])
+
+
+def execute_extension(b, rec, side, info):
+    """One call of ACTIONS_EXT.  side "oracle": made from the oracle's own calls and the numpy restatements the extensions' tests use
+    (updateDifferentialMatrices: differential_matrices_reference.slot, then setDifferentialMatrix; setReversibleModels: numpy's eigh
+    of the symmetric form, then setEigenDecomposition; the five calls that return values: ancestral_reference.sample,
+    simulate_reference.simulate, node_height_reference.row_derivatives, markov_jumps_reference.tables and site_values over the
+    oracle's getPartials and getTransitionMatrix and the tip states it was sent; getEigenDecomposition: what was sent).
+
+    The two samplers and the Markov-jump call: right after the call EVERY side reads back what the restatement needs from its own
+    instance (so the three stay in step, and the call itself ran in whatever deferred state the sequence left) and restates the
+    draw; read "exact" is the number of bytes in which the device's states and categories differ from that restatement (0 on the
+    oracle, which has nothing else).  info["undecided"]: the patterns (sites) on which some draw of the restatement lies next to a
+    boundary; info["device"] (oracle side): the engine's reads of the same record — the Markov-jump values are restated for the
+    device's own states and categories, so that a legitimately different draw does not show as a numeric error."""
+    import ancestral_reference
+    import differential_matrices_reference
+    import markov_jumps_reference
+    import node_height_reference
+    import simulate_reference
+    m, a = rec["m"], rec["a"]
+    S, C, P = b.stateCount, b.categoryCount, b.patternCount
+    have = sent(b)
+    cache = {}
+
+    def matrix_of(slot):
+        if slot not in cache:
+            cache[slot] = np.asarray(b.getTransitionMatrix(slot), dtype=float).reshape(C, S, S)
+        return cache[slot]
+
+    def tip_states_of(t):                                    # (the oracle has no getTipStates: a compact tip's states are what it was sent)
+        return b.getTipStates(t) if b.lib.has("GetTipStates") else have["tips"][t]
+
+    def post_of(buf, compact):
+        if buf in compact:
+            return node_height_reference.expand_states(tip_states_of(buf), S, C)
+        return b.getPartials(buf, NONE)
+
+    reads = []
+    if m in ("sampleAncestralStates", "sampleMarkovJumps"):
+        if m == "sampleAncestralStates":
+            rows, w, f, seed, use_map, compact = a
+        else:
+            rows, times, e, r, w, f, registers, flags, seed, use_map, compact = a
+        st = ca = res = None
+        if side != "oracle" and m == "sampleAncestralStates":
+            st, ca = b.sampleAncestralStates(rows, w, f, seed, map=use_map)
+        elif side != "oracle":
+            res = b.sampleMarkovJumps(rows, times, None, e, r, w, f, registers, flags, seed, map=use_map, states=True, jumps=True)
+            st, ca = res["states"], res["categories"]
+        und = np.zeros(P, dtype=bool)
+        rs, rc, bad = ancestral_reference.sample(rows, b.getPartials, matrix_of, tip_states_of, lambda x: x in compact, have["weights"][w],
+                                                 have["freqs"][f], seed, use_map=use_map, undecided=und)
+        if bad:
+            return -8, []
+        info["undecided"] = und
+        if side == "oracle":
+            st, ca = rs, rc
+        reads += [("states", st), ("cats", ca), ("exact", np.array([float(np.sum(st != rs) + np.sum(ca != rc))]))]
+        if m == "sampleMarkovJumps":
+            if side == "oracle":
+                dev = info.get("device")
+                vs, vc = (dev[0][1], dev[1][1]) if dev else (rs, rc)
+                u, ui, lam = have["eigen"][e]
+                mats = np.stack([np.zeros((C, S, S))] + [matrix_of(row[1]) for row in rows[1:]])
+                kinds = ["rewards" if fl & JUMPS_REWARDS else "counts" for fl in flags]
+                cond = markov_jumps_reference.tables(u, ui, lam, [np.array(x, dtype=float) for x in registers], kinds,
+                                                     [bool(fl & JUMPS_SCALE_BY_TIME) for fl in flags], times, None, have["rates"][r], mats)
+                vals, tot, row_tot = markov_jumps_reference.site_values(cond, np.asarray(vs), [row[2] for row in rows], vc)
+            else:
+                vals, tot, row_tot = res["jumps"], res["pattern_totals"], res["row_totals"]
+            reads += [("jumps", vals), ("jumps", tot), ("jumps", row_tot)]
+    elif m == "simulateSequences":
+        rows, sites, w, f, seed, root, cats = a
+        st = ca = None
+        if side != "oracle":
+            st, ca = b.simulateSequences(rows, sites, w, f, seed, root_states=root, rate_categories=cats)
+        und = np.zeros(sites, dtype=bool)
+        rs, rc, bad = simulate_reference.simulate(rows, matrix_of, have["weights"][w], have["freqs"][f], seed, sites, root_states=root,
+                                                  rate_categories=cats, undecided=und)
+        if bad:
+            return -8, []
+        info["undecided"] = und
+        if side == "oracle":
+            st, ca = rs, rc
+        reads += [("states", st), ("cats", ca), ("exact", np.array([float(np.sum(st != rs) + np.sum(ca != rc))]))]
+    elif m == "nodeHeightDerivatives":
+        rows, rates, w, first, second, compact = a
+        if side == "oracle":
+            o1, o2 = node_height_reference.row_derivatives(rows, rates, lambda buf: post_of(buf, compact), lambda buf: b.getPartials(buf, NONE),
+                                                           matrix_of, have["weights"][w], have["pattern_weights"], first, second)
+            if not all(np.isfinite(x).all() for x in (o1, o2) if x is not None):
+                return -8, []
+        else:
+            o1, o2 = b.nodeHeightDerivatives(rows, rates, w, first=first, second=second)
+        reads += [("deriv", x) for x in (o1, o2) if x is not None]
+    elif m == "updateDifferentialMatrices":
+        e, r, dqs, d, slots, lengths, mode = a
+        if side == "oracle":
+            for k, slot in enumerate(slots):
+                u, ui, lam = have["eigen"][e[k]]
+                D = differential_matrices_reference.slot(u, ui, lam, np.array(dqs[d[k]], dtype=float), lengths[k], have["rates"][r[k]], mode)
+                b.setDifferentialMatrix(slot, D.ravel())
+        else:
+            b.updateDifferentialMatrices(e, r, dqs, d, slots, lengths, len(slots), mode)
+    elif m == "setReversibleModels":
+        if side == "oracle":
+            for slot, upper, pi in zip(*a):
+                u, ui, lam = decompose_reversible(symmetric_rates(upper, S), np.array(pi, dtype=float))[:3]
+                b.setEigenDecomposition(slot, u.ravel(), ui.ravel(), lam)
+        else:
+            b.setReversibleModels(*a)
+    elif m == "getEigenDecomposition":
+        reads.append(("eigen", packed_eigen(*(have["eigen"][a[0]] if side == "oracle" else b.getEigenDecomposition(a[0])))))
+    else:
+        raise ValueError(m)
+    return 0, reads
+
+
+def execute(b, rec, side="engine", info=None):
     """One call.  side "oracle": the three calls the oracle has no entry point for are made from its own ones (setTipEmission: setTipPartials
     of the expanded table; addTransitionMatrices: the numpy sum of its two matrices, then setTransitionMatrix; getPartialsBatch: single
-    getPartials calls; waitForPartials: nothing to wait for).  -> (return code, [(kind, array), ...])"""
+    getPartials calls; waitForPartials: nothing to wait for), and so are those of ACTIONS_EXT (``execute_extension``; `info`: a dict
+    it reads "device" from and writes "undecided" into).  -> (return code, [(kind, array), ...])"""
     m, a = rec["m"], rec["a"]
     reads = []
     try:
-        if m == "calculateRootLogLikelihoods":
+        if m in ACTIONS_EXT:
+            rc, reads = execute_extension(b, rec, side, {} if info is None else info)
+            if rc:
+                return rc, []
+        elif m == "calculateRootLogLikelihoods":
             out = [0.0]
             b.calculateRootLogLikelihoods(a[0], a[1], a[2], a[3], a[4], out)
             reads.append(("sum", np.array(out)))
@@ -1068,14 +1540,27 @@ def execute(b, rec, side="engine"):
         if not hasattr(e, "code"):
             raise
         return e.code, []
+    remember(b, m, a)
     return 0, reads
 
 
-def deviation(kind, got, want):
+def deviation(kind, got, want, undecided=None):
     """The error of a read, normalised so that the project's bound is 1e-10 for every kind: sums and site values relative; log scale
     factors relative, against 1 where the value is smaller (a factor near 1 has a logarithm near 0); node partials against each
     pattern's largest entry (tests/test_gpu_parity.py test_engine_matches_oracle), a transition matrix likewise against the largest entry
-    of each category's matrix; derivative outputs against max(1, largest value) (tests/test_gpu_gradients.py)."""
+    of each category's matrix; derivative outputs against max(1, largest value) (tests/test_gpu_gradients.py), and so the node-height
+    derivatives and the Markov-jump values (tests/test_gpu_gradients.py ``close``).  An eigen system (U, U^-1, lambda packed) is not
+    unique: the larger of |U diag(lambda) U^-1 - Q| / max |Q|, Q the other side's reconstruction, and |U U^-1 - I|.  States and
+    categories of a draw: the number of entries that differ on the patterns (last axis) outside `undecided`; "exact": the number of
+    bytes by which a side differed from the restatement over its own reads.  Any count above 0 is above the bound."""
+    if kind in ("states", "cats"):
+        got, want = np.asarray(got), np.asarray(want)
+        if got.shape != want.shape:
+            return float("inf")
+        differ = got != want
+        if undecided is not None:
+            differ = differ & ~np.asarray(undecided, dtype=bool)
+        return float(np.sum(differ))
     got, want = np.asarray(got, dtype=float), np.asarray(want, dtype=float)
     if got.shape != want.shape:
         return float("inf")
@@ -1091,8 +1576,15 @@ def deviation(kind, got, want):
     if kind == "matrix":
         scale = np.maximum(np.abs(want).max(axis=(1, 2), keepdims=True), 1e-300)
         return float(np.max(np.abs(got - want) / scale))
-    if kind == "deriv":
+    if kind in ("deriv", "jumps"):
         return float(np.max(np.abs(got - want)) / max(1.0, float(np.max(np.abs(want)))))
+    if kind == "exact":
+        return float(np.max(np.abs(got - want)) + np.max(np.abs(got)))
+    if kind == "eigen":
+        S = int(round((np.sqrt(1.0 + 8.0 * got.size) - 1.0) / 4.0))
+        (ug, ig, lg), (uw, iw, lw) = ((x[:S * S].reshape(S, S), x[S * S:2 * S * S].reshape(S, S), x[2 * S * S:]) for x in (got, want))
+        q = (uw * lw[None, :]) @ iw
+        return float(max(np.max(np.abs((ug * lg[None, :]) @ ig - q)) / np.max(np.abs(q)), np.max(np.abs(ug @ ig - np.eye(S)))))
     raise ValueError(kind)
 
 
@@ -1121,12 +1613,14 @@ def replay(path, upto=None, out=print):
     try:
         for step, rec in enumerate(records if upto is None else records[:upto + 1]):
             rc_e, reads_e = execute(eng, rec, "engine")
-            rc_o, reads_o = execute(ora, rec, "oracle")
+            info = {"device": reads_e}
+            rc_o, reads_o = execute(ora, rec, "oracle", info)
             if rc_e or rc_o:
                 out("step %d %s: return codes engine %d, oracle %d" % (step, describe(rec), rc_e, rc_o))
                 stopped = step
                 break
-            worst = max([deviation(k, g, w) for (k, g), (_, w) in zip(reads_e, reads_o)] + [0.0], key=lambda x: (x != x, x))
+            worst = max([deviation(k, g, w, undecided=info.get("undecided")) for (k, g), (_, w) in zip(reads_e, reads_o)] + [0.0],
+                        key=lambda x: (x != x, x))
             if not worst <= BOUND:
                 out("step %d %s: first diverging read, deviation %.3e (bound %.0e)" % (step, describe(rec), worst, BOUND))
                 stopped = step

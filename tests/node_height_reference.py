@@ -82,6 +82,53 @@ def node_derivatives(tree, post_of, pre_of, matrix_of, q_of, rates, category_wei
     return first, sec
 
 
+def row_derivatives(rows, rates, post_of, pre_of, matrix_of, category_weights, pattern_weights, first=True, second=True):
+    """The call's own rows, each from the buffers and slots it names and nothing else (include/beagle_mi355.h
+    beagleMi355NodeHeightDerivatives: D, g and h as written there), so that it is defined in any state of an instance — ``node_derivatives``
+    above wants every node's pre-order partial and agrees with this where the buffers belong to one evaluation.
+    rows [n][8] {pre(i), post(j), matrix(j), dmatrix(j), post(k), matrix(k), dmatrix(k), dmatrix(i) or -1}; rates [n][3] {r_j, r_k, r_i};
+    post_of(buffer), pre_of(buffer) -> [C, P, S]; matrix_of(slot) -> [C, S, S].  -> (first, second), [n] each, None when not asked for."""
+    cw = np.asarray(category_weights, dtype=float)
+    pw = np.asarray(pattern_weights, dtype=float)
+    rows = np.asarray(rows, dtype=np.int64).reshape(-1, 8)
+    rates = np.asarray(rates, dtype=float).reshape(-1, 3)
+
+    def red(v):
+        return np.einsum("c,cp->p", cw, v.sum(axis=2))
+
+    o1 = np.zeros(len(rows)) if first else None
+    o2 = np.zeros(len(rows)) if second else None
+    for n, (row, (rj, rk, ri)) in enumerate(zip(rows, rates)):
+        pi_, pj, mj, dj, pk, mk, dk, di = (int(x) for x in row)
+        q = pre_of(pi_)
+        Qj, Qk = matrix_of(dj), matrix_of(dk)
+        aj, ak = _mv(matrix_of(mj), post_of(pj)), _mv(matrix_of(mk), post_of(pk))
+        bj, bk = _mv(Qj, aj), _mv(Qk, ak)
+        D = red(aj * ak * q)
+        gj, gk = red(bj * ak * q) / D, red(aj * bk * q) / D
+        f = rj * gj + rk * gk
+        if di >= 0:
+            u = _mtv(matrix_of(di), q)
+            gi = red(aj * ak * u) / D
+            f = f - ri * gi
+        if first:
+            o1[n] = float(np.dot(pw, f))
+        if not second:
+            continue
+        hjj = red(_mv(Qj, bj) * ak * q) / D - gj * gj
+        hkk = red(aj * _mv(Qk, bk) * q) / D - gk * gk
+        hjk = red(bj * bk * q) / D - gj * gk
+        s = rj * rj * hjj + rk * rk * hkk + 2.0 * rj * rk * hjk
+        if di >= 0:
+            v = _mtv(matrix_of(di), u)
+            hii = red(aj * ak * v) / D - gi * gi
+            hij = red(bj * ak * u) / D - gi * gj
+            hik = red(aj * bk * u) / D - gi * gk
+            s = s + ri * ri * hii - 2.0 * ri * rj * hij - 2.0 * ri * rk * hik
+        o2[n] = float(np.dot(pw, s))
+    return o1, o2
+
+
 def from_plan(plan, second=True, compact=None):
     """`node_derivatives` over what the engine library behind `plan` (a nodeheight.NodeHeightGradient after prepare()) reads back.
     compact: the tips that hold compact states (default: all of them), expanded from the workload's states."""

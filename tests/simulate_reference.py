@@ -11,7 +11,7 @@ oracle's, or any callable — so the states must agree with the device's byte fo
 """
 import numpy as np
 
-from ancestral_reference import DBL_MAX, splitmix64
+from ancestral_reference import DBL_MAX, UNDECIDED, splitmix64
 
 
 def uniforms(seed, row, sites, site_count, kind):
@@ -38,19 +38,25 @@ def cumulative(p):
     return cum, last_positive, bad
 
 
-def draw(cum, last_positive, bad, u):
-    """One draw per leading index: cum [m, n], last_positive [m], bad [m], u [m] -> (choice int64 [m], bad [m])."""
+def draw(cum, last_positive, bad, u, undecided=None):
+    """One draw per leading index: cum [m, n], last_positive [m], bad [m], u [m] -> (choice int64 [m], bad [m]).  `undecided`: a bool
+    array [m] that is set where u lies within UNDECIDED x total of some running sum (the draw could come out differently under that
+    relative change of p)."""
     with np.errstate(invalid="ignore"):
         above = u[:, None] < cum
+        if undecided is not None:
+            undecided |= (np.abs(u[:, None] - cum) <= UNDECIDED * cum[:, -1:]).any(axis=1)
     first = np.argmax(above, axis=1)                       # the first True; 0 when there is none
     choice = np.where(above.any(axis=1), first, last_positive)
     return np.where(bad, 0, choice), bad
 
 
-def simulate(rows, matrix_of, category_weights, frequencies, seed, site_count, root_states=None, rate_categories=None, sites=None):
+def simulate(rows, matrix_of, category_weights, frequencies, seed, site_count, root_states=None, rate_categories=None, sites=None,
+             undecided=None):
     """The call for `rows` ([n][3] {outRow, matrixIndex, parentRow}, root first; outRow is not looked at).
 
     matrix_of(matrixIndex) -> [C, S, S] as getTransitionMatrix returns it.  `sites`: restate only these site indices (default all).
+    `undecided`: a bool array [len(sites)] that is set where some draw of the site lies next to a boundary (``draw``).
     -> (states uint8 [n, len(sites)] BY ROW OF THE LIST, categories int32 [len(sites)], any_bad)."""
     rows = np.asarray(rows, dtype=np.int64).reshape(-1, 3)
     w = np.asarray(category_weights, dtype=np.float64)
@@ -64,7 +70,7 @@ def simulate(rows, matrix_of, category_weights, frequencies, seed, site_count, r
     elif C > 1:
         cum, last, bad = cumulative(w)
         cats, b = draw(np.broadcast_to(cum, (n, C)), np.broadcast_to(last, n), np.broadcast_to(bad, n),
-                       uniforms(seed, 0, sites, site_count, 1))
+                       uniforms(seed, 0, sites, site_count, 1), undecided)
         any_bad |= bool(b.any())
     else:
         cats = np.zeros(n, dtype=np.int64)
@@ -74,7 +80,7 @@ def simulate(rows, matrix_of, category_weights, frequencies, seed, site_count, r
     else:
         cum, last, bad = cumulative(f)
         s0, b = draw(np.broadcast_to(cum, (n, S)), np.broadcast_to(last, n), np.broadcast_to(bad, n),
-                     uniforms(seed, 0, sites, site_count, 0))
+                     uniforms(seed, 0, sites, site_count, 0), undecided)
         any_bad |= bool(b.any())
         states[0] = s0
     tables = {}
@@ -84,7 +90,7 @@ def simulate(rows, matrix_of, category_weights, frequencies, seed, site_count, r
             tables[m] = cumulative(np.asarray(matrix_of(m), dtype=np.float64).reshape(C, S, S))
         cum, last, bad = tables[m]
         ps = states[parent].astype(np.int64)
-        s, b = draw(cum[cats, ps], last[cats, ps], bad[cats, ps], uniforms(seed, r, sites, site_count, 0))
+        s, b = draw(cum[cats, ps], last[cats, ps], bad[cats, ps], uniforms(seed, r, sites, site_count, 0), undecided)
         any_bad |= bool(b.any())
         states[r] = s
     return states, cats.astype(np.int32), any_bad

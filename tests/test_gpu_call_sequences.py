@@ -27,6 +27,18 @@ under BEAGLE_MI355_REPEATS_ANY_SIZE=1.
 
 One more parametrisation runs shape (4, 4, 12, 130) on the pattern-sharded handle (three shards on one GPU, as
 tests/test_gpu_sharded_instance.py creates it) against the oracle only; a read the handle answers with NO_IMPLEMENTATION is dropped.
+
+The generator's second profile, "extensions", puts the one-call entry points into the generated orders — sampleAncestralStates,
+sampleMarkovJumps, simulateSequences, nodeHeightDerivatives, updateDifferentialMatrices, setReversibleModels, getEigenDecomposition
+— with motifs (j)-(m) around the decisions each of them makes about the deferred state (tests/call_sequences.py).  The same three
+instances, the same three conditions at every call, on the five shapes of at most 64 states, and two seeds on the sharded handle
+(NO_IMPLEMENTATION tolerated on calls that return values and change nothing).  What is compared: node-height derivatives and
+Markov-jump values as derivative outputs are (the jump values restated on the oracle's side for the DEVICE's states and categories);
+an eigen system through U diag(lambda) U^-1 against the oracle side's Q, relative to max |Q|, and U U^-1 against I; the states and
+categories of every draw twice — byte for byte against the restatement over what the same instance reads back right after the call
+(read "exact"), and against the restatement over the oracle's reads on every decided pattern, with at most 1 % of a sequence's
+(sampler call, pattern) pairs undecided.  Route evidence over a 4-state shape's seeds: a held pre-order list both run late and
+answered while held, models decomposed on the device, a folded tip demoted by a sampler, one-launch walks.
 """
 import collections
 import os
@@ -36,13 +48,14 @@ import pytest
 
 import beast_mcmc_amd as bm
 import call_sequences as cs
-from test_call_sequences_host import CASES, SEEDS, SHAPES, case_id, records
+from test_call_sequences_host import CASES, CASES_EXT, SEEDS, SEEDS_EXT, SHAPES, SHAPES_EXT, case_id, records
 
 pytestmark = pytest.mark.gpu
 
 TWIN_ENV = {"BEAGLE_MI355_COPY_ENGINE_UPLOADS": "1", "BEAGLE_MI355_NO_PLAN_CACHE": "1"}
 READ_ONLY = ("getTransitionMatrix", "getLogScaleFactors", "getSiteLogLikelihoods", "getPartials", "getPartialsBatch",
              "calculateEdgeDifferentials", "calculateCrossProductDifferentials")
+RETURNS_VALUES = ("sampleAncestralStates", "sampleMarkovJumps", "simulateSequences", "nodeHeightDerivatives", "getEigenDecomposition")
 NO_IMPLEMENTATION = -7
 
 
@@ -60,9 +73,9 @@ def created_under(env, make):
                 os.environ[k] = v
 
 
-def fail(what, shape, seed, step, recs, tmp_path):
+def fail(what, shape, seed, step, recs, tmp_path, profile="base"):
     path = str(tmp_path / ("sequence_S%d_C%d_T%d_P%d_seed%d.json" % (shape + (seed,))))
-    cs.dump(path, shape, seed, recs)
+    cs.dump(path, shape, seed, recs, profile)
     raise AssertionError("shape %s seed %d step %d %s: %s\nreplay: python tests/call_sequences.py --replay %s --upto %d"
                          % (shape, seed, step, cs.describe(recs[step]), what, path, step))
 
@@ -71,12 +84,12 @@ def counters(b):
     info, grad = b.walkLaunchInfo(), b.gradientStats()
     return {"rootFusedCount": b.rootFusedCount(), "sitePrefetchCount": b.sitePrefetchCount(), "ticket_walks": info["ticket_walks"],
             "slice_accumulations": info["slice_accumulations"], "held_answered": grad["fused"] + grad["walked"], "late": grad["late"],
-            "walks": b.walkStats()["walks"]}
+            "walks": b.walkStats()["walks"], "eigen_calls": b.eigenStats()["calls"], "demotions": b.tipEmissionStats()["demotions"]}
 
 
-def lockstep(shape, seed, oracle_lib, tmp_path, sharded=False):
+def lockstep(shape, seed, oracle_lib, tmp_path, sharded=False, profile="base"):
     """-> the default engine's counters at the end of the sequence"""
-    recs = records(shape, seed)
+    recs = records(shape, seed, profile)
     instances = []
     try:
         if sharded:
@@ -92,31 +105,42 @@ def lockstep(shape, seed, oracle_lib, tmp_path, sharded=False):
         ora = cs.create(shape, bm.beagle.Beagle, library=oracle_lib)
         instances.append(ora)
         worst = collections.defaultdict(float)
+        pairs = undecided = 0
         for step, rec in enumerate(recs):
             rc_e, got = cs.execute(eng, rec, "engine")
             if sharded and rc_e == NO_IMPLEMENTATION:
-                assert rec["m"] in READ_ONLY, (step, cs.describe(rec))       # (only a read can be left out without the two sides parting)
+                # (only a call that returns values and changes nothing can be left out without the two sides parting)
+                assert rec["m"] in READ_ONLY + RETURNS_VALUES, (step, cs.describe(rec))
                 continue
-            rc_o, want = cs.execute(ora, rec, "oracle")
+            info = {"device": got}
+            rc_o, want = cs.execute(ora, rec, "oracle", info)
+            if "undecided" in info:
+                pairs += info["undecided"].size
+                undecided += int(info["undecided"].sum())
             if twin is not None:
                 rc_t, same = cs.execute(twin, rec, "engine")
                 if not (rc_e == rc_t == rc_o):
-                    fail("return codes engine %d, twin %d, oracle %d" % (rc_e, rc_t, rc_o), shape, seed, step, recs, tmp_path)
+                    fail("return codes engine %d, twin %d, oracle %d" % (rc_e, rc_t, rc_o), shape, seed, step, recs, tmp_path, profile)
                 for k, ((kind, a), (_, b)) in enumerate(zip(got, same)):
                     if not np.array_equal(a, b):
                         fail("read %d (%s): the default engine and its twin (%s) differ, by at most %.3e"
-                             % (k, kind, " ".join(sorted(TWIN_ENV)), float(np.max(np.abs(a - b)))), shape, seed, step, recs, tmp_path)
+                             % (k, kind, " ".join(sorted(TWIN_ENV)), float(np.max(np.abs(a.astype(float) - b.astype(float))))),
+                             shape, seed, step, recs, tmp_path, profile)
             elif rc_e != rc_o:
-                fail("return codes sharded engine %d, oracle %d" % (rc_e, rc_o), shape, seed, step, recs, tmp_path)
+                fail("return codes sharded engine %d, oracle %d" % (rc_e, rc_o), shape, seed, step, recs, tmp_path, profile)
             if len(got) != len(want):
-                fail("%d reads on the engine, %d on the oracle" % (len(got), len(want)), shape, seed, step, recs, tmp_path)
+                fail("%d reads on the engine, %d on the oracle" % (len(got), len(want)), shape, seed, step, recs, tmp_path, profile)
             for k, ((kind, a), (_, b)) in enumerate(zip(got, want)):
-                d = cs.deviation(kind, a, b)
+                d = cs.deviation(kind, a, b, undecided=info.get("undecided"))
                 worst[kind] = max(worst[kind], d) if d == d else d
                 if not d <= cs.BOUND:
-                    fail("read %d (%s): engine against oracle %.3e, bound %.0e" % (k, kind, d, cs.BOUND), shape, seed, step, recs, tmp_path)
-        print("shape %s seed %d%s: largest deviation from the oracle by kind of read: %s"
-              % (shape, seed, ", sharded" if sharded else "", ", ".join("%s %.1e" % kv for kv in sorted(worst.items()))))
+                    fail("read %d (%s): engine against oracle %.3e, bound %.0e" % (k, kind, d, cs.BOUND), shape, seed, step, recs, tmp_path, profile)
+        print("shape %s seed %d%s%s: largest deviation from the oracle by kind of read: %s%s"
+              % (shape, seed, ", sharded" if sharded else "", "" if profile == "base" else ", " + profile,
+                 ", ".join("%s %.1e" % kv for kv in sorted(worst.items())),
+                 "; %d of %d (sampler call, pattern) pairs undecided" % (undecided, pairs) if pairs else ""))
+        if undecided > cs.UNDECIDED_CAP * pairs:
+            fail("%d of %d (sampler call, pattern) pairs undecided" % (undecided, pairs), shape, seed, len(recs) - 1, recs, tmp_path, profile)
         return counters(eng)
     finally:
         for b in instances:
@@ -153,3 +177,33 @@ def test_the_sequences_take_the_deferred_routes(shape, oracle_lib, tmp_path):
 @pytest.mark.parametrize("seed", [1, 2])
 def test_sharded_handle_and_oracle_in_lockstep(seed, oracle_lib, tmp_path):
     lockstep((4, 4, 12, 130), seed, oracle_lib, tmp_path, sharded=True)
+
+
+# ---- profile "extensions": the one-call entry points in the generated orders ------------------------------------------------------
+_counters_ext = {}
+
+
+@pytest.mark.parametrize("case", CASES_EXT, ids=case_id)
+def test_extension_calls_engine_twin_and_oracle_in_lockstep(case, oracle_lib, tmp_path):
+    shape, seed = case
+    _counters_ext[case] = None
+    _counters_ext[case] = lockstep(shape, seed, oracle_lib, tmp_path, profile="extensions")
+
+
+@pytest.mark.parametrize("shape", [s for s in SHAPES_EXT if s[0] == 4], ids=lambda s: "S%d-C%d-T%d-P%d" % s)
+def test_the_extension_sequences_reach_the_deferral_decisions(shape, oracle_lib, tmp_path):
+    """Summed over a 4-state shape's seeds: a held pre-order list was both run by a later call and answered while held around the
+    new calls, models were decomposed on the device, a sampler demoted a folded tip, and one-launch walks ran."""
+    total = collections.Counter()
+    for seed in SEEDS_EXT[shape]:
+        if (shape, seed) not in _counters_ext:
+            _counters_ext[(shape, seed)] = lockstep(shape, seed, oracle_lib, tmp_path, profile="extensions")
+        total.update(_counters_ext[(shape, seed)] or {})
+    print("shape %s, extensions: %s" % (shape, dict(total)))
+    for key in ("late", "held_answered", "eigen_calls", "demotions", "walks"):
+        assert total[key] > 0, (key, dict(total))
+
+
+@pytest.mark.parametrize("seed", [1, 2])
+def test_extension_calls_sharded_handle_and_oracle_in_lockstep(seed, oracle_lib, tmp_path):
+    lockstep((4, 4, 12, 130), seed, oracle_lib, tmp_path, sharded=True, profile="extensions")

@@ -66,6 +66,32 @@ def test_first_is_the_chain_rule_over_the_branch_gradient():
     g.close()
 
 
+@pytest.mark.parametrize("S,C,T,P,seed", [(4, 3, 9, 70, 1), (7, 2, 6, 50, 3)])
+def test_row_restatement_equals_the_tree_restatement_on_one_evaluation(S, C, T, P, seed):
+    """``row_derivatives`` reads only what the call's rows name (the form the generated call sequences need, where buffers may belong
+    to different evaluations); on the buffers of ONE evaluation it is the restatement that is pinned against finite differences
+    below, to rounding: 1e-12 of max(1, largest value)."""
+    wl, g = _plan(S, C, T, P, seed)
+    g.prepare()
+    first, second = nr.from_plan(g)
+    rows, rates = g.node_rows()
+    compact = set(range(g.T))
+
+    def post_of(buf):
+        if buf in compact:
+            return nr.expand_states(wl.tip_states[buf], S, C)
+        return g.b.getPartials(buf, -1).reshape(C, P, S)
+
+    f, s = nr.row_derivatives(rows, rates, post_of, lambda buf: g.b.getPartials(buf, -1).reshape(C, P, S),
+                              lambda m: g.b.getTransitionMatrix(m).reshape(C, S, S), wl.cat_weights, wl.weights)
+    for got, want in ((f, first), (s, second)):
+        assert np.max(np.abs(got - want)) <= 1e-12 * max(1.0, float(np.max(np.abs(want))))
+    only, none = nr.row_derivatives(rows, rates, post_of, lambda buf: g.b.getPartials(buf, -1).reshape(C, P, S),
+                                    lambda m: g.b.getTransitionMatrix(m).reshape(C, S, S), wl.cat_weights, wl.weights, second=False)
+    assert none is None and np.array_equal(only, f)
+    g.close()
+
+
 @pytest.mark.parametrize("S,C,T,P,seed", [(4, 4, 9, 300, 1), (4, 2, 12, 200, 2), (7, 2, 6, 50, 3)])
 def test_restatement_matches_finite_differences_of_the_oracle(S, C, T, P, seed):
     """Central differences of the oracle's lnL in the height h of node i — moving h by d changes the two child branches by
