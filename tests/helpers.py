@@ -137,9 +137,9 @@ def walk_stats(tl):
     return raw.walkStats()
 
 
-def two_partitions(S, T, sizes, seed):
-    """One tree and len(sizes) partitions of it, partition k with its own model (gamma shape 0.4 + 0.5 k) and sizes[k] unique
-    patterns simulated on the tree, 3 % of the tip states unknown."""
+def two_partitions(S, T, sizes, seed, categories=4):
+    """One tree and len(sizes) partitions of it, partition k with its own model (gamma shape 0.4 + 0.5 k, `categories` rate categories)
+    and sizes[k] unique patterns simulated on the tree, 3 % of the tip states unknown."""
     rng = np.random.default_rng(seed)
     wls = []
     tree = None
@@ -150,10 +150,10 @@ def two_partitions(S, T, sizes, seed):
         else:
             eig, pi = substmodel.random_reversible(S, rng)
         if tree is None:
-            wl = synth.make_workload("part0", T, n, eig, pi, alpha=0.4 + 0.5 * k, categories=4, seed=seed)
+            wl = synth.make_workload("part0", T, n, eig, pi, alpha=0.4 + 0.5 * k, categories=categories, seed=seed)
             tree = wl.tree
         else:
-            rates, props = GammaSiteRateModel(alpha=0.4 + 0.5 * k, gamma_categories=4).category_rates_and_proportions()
+            rates, props = GammaSiteRateModel(alpha=0.4 + 0.5 * k, gamma_categories=categories).category_rates_and_proportions()
             tips = synth.simulate_unique_patterns(tree, eig, np.asarray(pi), rates, props, n, rng).astype(np.int32)
             tips[rng.random(tips.shape) < 0.03] = S
             wl = Workload("part%d" % k, tree, eig, pi, rates, props, np.ascontiguousarray(tips),

@@ -40,7 +40,7 @@ class Case:
 
     def __init__(self, S, K, oracle_lib, scaling=False, seed=0, shared_model=False, sizes=None, ids=None, resource=(1,), T=10, C=4, env=None):
         sizes, ids = (sizes, ids) if sizes is not None else LAYOUTS[K]
-        self.tree, wls = helpers.two_partitions(S, T, sizes, seed=seed + 31 * S + K)
+        self.tree, wls = helpers.two_partitions(S, T, sizes, seed=seed + 31 * S + K, categories=C)
         # every partition integrates its root with the same category weights and state frequencies (a whole-range root call names
         # one set of them for all patterns); the substitution models and category rates are the partitions' own unless shared_model
         m = wls[0]
