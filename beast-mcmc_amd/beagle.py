@@ -124,7 +124,7 @@ ABI_SYMBOLS = ["beagleGetVersion", "beagleGetCitation", "beagleGetResourceList",
               ["beagle" + k for k in _PROTOS] + \
               ["beagleMi355SetStream", "beagleMi355CalculateRootLogLikelihoodsDevice", "beagleMi355Synchronize",
                "beagleMi355KernelTimer", "beagleMi355DeviceBytes", "beagleMi355WalkStats", "beagleMi355GradientStats", "beagleMi355GetPartialsBatch", "beagleMi355SampleAncestralStates", "beagleMi355SampleMarkovJumps", "beagleMi355SampleMarkovJumpsUniformized",
-               "beagleMi355SimulateSequences", "beagleMi355SimulateCompleteHistories", "beagleMi355RobustCounts", "beagleMi355SimulateUnconditionedCounts", "beagleMi355NodeHeightDerivatives", "beagleMi355UpdateDifferentialMatrices", "beagleMi355SetReversibleModels", "beagleMi355GetEigenDecomposition", "beagleMi355EigenStats", "beagleMi355SetTipEmission", "beagleMi355TipEmissionStats",
+               "beagleMi355SimulateSequences", "beagleMi355SimulateCompleteHistories", "beagleMi355RobustCounts", "beagleMi355SimulateUnconditionedCounts", "beagleMi355NodeHeightDerivatives", "beagleMi355UpdateDifferentialMatrices", "beagleMi355SetReversibleModels", "beagleMi355GetEigenDecomposition", "beagleMi355EigenStats", "beagleMi355UpdateTransitionMatricesFromGenerators", "beagleMi355GeneratorStats", "beagleMi355SetTipEmission", "beagleMi355TipEmissionStats",
                "beagleMi355GetPartialsPinned", "beagleMi355GetSiteLogLikelihoodsPinned",
                "beagleMi355KernelTimerCalls", "beagleMi355WalkHealth", "beagleMi355RepeatStats", "beagleMi355WalkLaunchInfo", "beagleMi355RootFusedCount", "beagleMi355SitePrefetchCount", "beagleMi355KernelTimerRestart", "beagleMi355GetDimensions", "beagleMi355GetCommUniqueId", "beagleMi355CommInit", "beagleMi355CommInfo", "beagleMi355CalculateRootLogLikelihoodsAllReduce"] + \
               ["beagleBasta" + k for k in ("AllocateCoalescentBuffers", "UpdatePartials", "AccumulatePartials", "GetBuffer", "GetBufferLength", "Stats", "SampleStates", "StatesStats",
@@ -720,6 +720,28 @@ class Beagle:
         out = (C.c_longlong * 4)()
         self._check("eigenStats", self._ext("beagleMi355EigenStats", [C.c_int, C.POINTER(C.c_longlong)])(self.instance, out))
         return {"calls": int(out[0]), "models": int(out[1]), "max_sweeps": int(out[2]), "capped": int(out[3])}
+
+    def updateTransitionMatricesFromGenerators(self, generators, generatorIndices, categoryRateIndices, probabilityIndices,
+                                               edgeLengths, count=None):
+        """exp(Q d) for every listed branch and category straight from the generators, no eigen system (include/beagle_mi355.h
+        beagleMi355UpdateTransitionMatricesFromGenerators).  ``generators`` [G][S][S]: what getInfinitesimalMatrix returns; per
+        entry its generator and rate set (each None: 0 for all), the matrix slot it writes and its edge length.  Nothing comes
+        back and the host does not wait."""
+        S = self.stateCount
+        q = _d(generators).reshape(-1, S, S)
+        g, r, m, t = _i(generatorIndices), _i(categoryRateIndices), _i(probabilityIndices), _d(edgeLengths)
+        n = m.size if count is None else int(count)
+        for a in (g, r, m, t):
+            if a is not None and a.size < n:
+                raise ValueError("every per-entry list must have one entry per matrix")
+        f = self._ext("beagleMi355UpdateTransitionMatricesFromGenerators", [C.c_int, _DP, C.c_int, _IP, _IP, _IP, _DP, C.c_int])
+        self._check("updateTransitionMatricesFromGenerators", f(self.instance, _dp(q), q.shape[0], _ip(g), _ip(r), _ip(m), _dp(t), n))
+
+    def generatorStats(self):
+        """What updateTransitionMatricesFromGenerators has done (include/beagle_mi355.h beagleMi355GeneratorStats)."""
+        out = (C.c_long * 4)()
+        self._check("generatorStats", self._ext("beagleMi355GeneratorStats", [C.c_int, C.POINTER(C.c_long)])(self.instance, out))
+        return {"calls": int(out[0]), "matrices": int(out[1]), "max_squarings": int(out[2]), "refused": int(out[3])}
 
     def sampleMarkovJumps(self, nodes, branchTimes, branchRates, eigenIndex, categoryRatesIndex, categoryWeightsIndex,
                           stateFrequenciesIndex, registers, registerFlags, seed, map=False, states=False, jumps=False,

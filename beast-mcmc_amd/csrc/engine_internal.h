@@ -14,6 +14,7 @@
 //   engine_tipemission.cpp  tip error models: emission tables folded into the tip branch matrices
 //   engine_differential.cpp  substitution-parameter differential matrices of every branch in one call
 //   engine_eigen.cpp     eigen systems of reversible models decomposed on the device in one call, an eigen slot back to the host
+//   engine_generator.cpp transition matrices straight from generators in one call, no eigen system
 //   engine_stats.cpp     stream, synchronisation, kernel timer, counters
 // each of them argument checks, buffer bookkeeping and one call into the files above.
 // All arithmetic is in the .hip files; these files validate indices, resolve buffer indices to device pointers and enqueue
@@ -400,6 +401,9 @@ struct Instance {
     std::vector<double> shEigen, shFreqs, shWeights, shRates;      // host shadows of the small model arrays ...
     std::vector<char> okEigen, okFreqs, okWeights, okRates;         // ... valid flags per index
     std::string resourceName;
+    DevBuf generatorDev;                                 // matrices from generators (engine_generator.cpp): the power tables of a launch, [generators][21][S][S] doubles
+    DevBuf generatorStatsDev;                            // ... and two words the kernels keep: the largest s, the matrices refused
+    long statGeneratorCalls = 0, statGeneratorMatrices = 0;                    // (beagleMi355GeneratorStats)
 };
 
 extern std::mutex g_mutex;

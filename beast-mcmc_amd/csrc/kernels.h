@@ -344,6 +344,18 @@ constexpr int EIGEN_SWEEP_CAP = 30;          // Jacobi sweeps after which a mode
 bool launchEigenReversible(hipStream_t stream, double* eigen, const double* models, const int* slots, int* sweeps, int count, int S,
                            bool complexEigen);
 
+// ---- transition matrices from generators (kernels_generator.hip; beagleMi355UpdateTransitionMatricesFromGenerators) ----
+constexpr int GENERATOR_TERMS = 21;            // B^0 .. B^20 per generator: the power table is [generator][21][S][S] doubles
+constexpr int GENERATOR_MAX_SQUARINGS = 40;    // a matrix that would need more is written as NaN and counted
+// tables[g] = {I, B, B^2 .. B^20}, B = Q[g] / mu[g] + I, for `count` generators (Q [count][S][S], mu [count], device arrays).  One
+// thread per generator up to 8 states, one workgroup from 9 to 64.  false: no kernel for this S.
+bool launchGeneratorPowers(hipStream_t stream, double* tables, const double* Q, const double* mu, int count, int S);
+// slot dIdx[u], category c = exp(Q[dGen[u]] dLen[u] rate(c)) from the tables (header arithmetic) for `count` entries (device arrays of
+// that length: slot, length, generator of the tables, rate set).  stats: {largest s, matrices refused} device words.  One thread per
+// (entry, category) up to 8 states, one workgroup from 9 to 64 (squarings on the matrix cores from 16).
+bool launchGeneratorMatrices(hipStream_t stream, double* matrices, const double* rates, const double* tables, const double* mu,
+                             const int* dIdx, const double* dLen, const int* dGen, const int* dRate, unsigned* stats, int count, int S, int C);
+
 // One dependency level of pruning operations: `nOps` independent ops, descriptors on the device.
 // maxRange = max over ops of (pEnd - pStart).
 void launchPruneLevel(hipStream_t stream, const OpDesc* dOps, int nOps, const double* matrices,

@@ -468,6 +468,43 @@ int beagleMi355GetEigenDecomposition(int instance, int eigenIndex, double* outEi
 /* out4 = {beagleMi355SetReversibleModels calls since creation, models they decomposed, the most Jacobi sweeps a model of the last call
  * took, models of the last call that hit the cap of 30} (shard 0 of a sharded handle).  Drains the instance's stream. */
 int beagleMi355EigenStats(int instance, long long* out4);
+/* Transition matrices straight from generators, in ONE call and with no eigen system — for the models that have no real or no
+ * well-conditioned one (ComplexSubstitutionModel, BSSVS / GLM rate matrices, BASTA's migration matrices; a defective generator is as
+ * good as any other here).  Slot probabilityIndices[e] receives exp(Q_g d) for each of the C categories, as
+ * beagleUpdateTransitionMatrices leaves them, by uniformization with scaling and squaring.
+ *   generators [generatorCount][S][S] row-major: what getInfinitesimalMatrix returns (already normalised).  Rows need not sum to zero.
+ *   generatorIndices [count] (NULL: 0 for every entry): the generator g of entry e.
+ *   categoryRateIndices [count] (NULL: rate set 0): the rate set of entry e, as in beagleUpdateTransitionMatricesWithMultipleModels.
+ *   probabilityIndices [count]: the slot of entry e, no slot twice in one call;  edgeLengths [count].
+ * For generator g: mu = max_i -Q_ii (scanned upwards from i = 0, a later entry replaces an earlier one only if greater);
+ *   B = Q / mu entry by entry, then + 1 on the diagonal;  B^0 = I, B^1 = B, B^k = B^(k-1) B for k = 2 .. 20, the inner index summed
+ *   upwards from 0.0, every product rounded on its own (no fused multiply-add).
+ * For entry e and category c: d = edgeLengths[e] * rate_c (one product, as beagleUpdateTransitionMatrices forms its distance);
+ *   x = mu d;  s = the smallest integer >= 0 with x 2^-s <= 1;  tau = x 2^-s (exact);  w_0 = exp(-tau), w_k = w_(k-1) tau / k;
+ *   T = sum_{k = 0 .. 20} w_k B^k, k upwards;  then s times T <- T T.
+ * B and every T are non-negative, so nothing cancels: every entry is >= 0, structural zeros stay exact zeros, d = 0 gives I exactly, and
+ * the componentwise relative error is of the order of (2^s + 20) eps (tests/generator_matrices_reference.py).  The power tables are
+ * formed once per generator of the call.  The squarings run on the fp64 matrix cores from 16 states up (there the inner index is summed
+ * four at a time) and with fused multiply-adds below; every sum has a fixed order and there are no atomics on values, so a slot's bits
+ * depend on (Q_g, edgeLengths[e], rate_c) alone: not on its place in the list, on the split into launches, on the other generators of the
+ * call or on the shard.  s > 40 (and an x that is not finite) writes NaN into that matrix and is counted by beagleMi355GeneratorStats — a
+ * likelihood behind it answers BEAGLE_ERROR_FLOATING_POINT.
+ * The call is queued behind everything queued on the instance; nothing is read back and the host does not wait.  Writing a slot does
+ * for it what beagleUpdateTransitionMatrices does; a held-back pre-order list runs first only if it reads one of the written slots.
+ * Input goes through the staging ring and the power tables (21 S^2 doubles a generator) through a scratch buffer: a list over either
+ * budget is split into several launches, so no list is refused for its size.  It works on EIGEN_REAL and EIGEN_COMPLEX instances, on
+ * partitioned ones and on instances with BASTA buffers, and writes matrix slots only.  The sharded handle gives the call to every shard.
+ * BEAGLE_ERROR_OUT_OF_RANGE for generators, probabilityIndices or edgeLengths NULL, count < 0, generatorCount < 1, an index out of range, a
+ * slot named twice, a Q entry that is not finite, a negative off-diagonal, a positive diagonal, mu not finite and > 0, an edge length
+ * not finite or < 0;  BEAGLE_ERROR_NO_IMPLEMENTATION with more than 64 states.  Everything is checked before anything is queued: a
+ * refused call leaves every slot as it was.  count == 0: success, nothing is launched.  Derivative matrices are not offered.
+ * An extension: no BEAST class calls it today. */
+int beagleMi355UpdateTransitionMatricesFromGenerators(int instance, const double* generators, int generatorCount,
+                                                      const int* generatorIndices, const int* categoryRateIndices,
+                                                      const int* probabilityIndices, const double* edgeLengths, int count);
+/* out4 = {beagleMi355UpdateTransitionMatricesFromGenerators calls since creation, matrices (entry x category) they wrote, the largest s
+ * of any of them, matrices refused (NaN) for s > 40} (shard 0 of a sharded handle).  Drains the instance's stream. */
+int beagleMi355GeneratorStats(int instance, long* out4);
 /* Markov jumps: ONE call that draws the ancestral states as beagleMi355SampleAncestralStates does and, for every register k, row
  * r >= 1 and pattern p, forms the expected number of registered substitutions (a count register) or the expected reward (a reward
  * register) on row r's branch, conditioned on the drawn parent and child states — what MarkovJumpsBeagleTreeLikelihood.hookCalculation
