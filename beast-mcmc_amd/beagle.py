@@ -126,7 +126,7 @@ ABI_SYMBOLS = ["beagleGetVersion", "beagleGetCitation", "beagleGetResourceList",
                "beagleMi355KernelTimer", "beagleMi355DeviceBytes", "beagleMi355WalkStats", "beagleMi355GradientStats", "beagleMi355GetPartialsBatch", "beagleMi355SampleAncestralStates", "beagleMi355SampleMarkovJumps", "beagleMi355SampleMarkovJumpsUniformized",
                "beagleMi355SimulateSequences", "beagleMi355SimulateCompleteHistories", "beagleMi355RobustCounts", "beagleMi355SimulateUnconditionedCounts", "beagleMi355NodeHeightDerivatives", "beagleMi355UpdateDifferentialMatrices", "beagleMi355SetReversibleModels", "beagleMi355GetEigenDecomposition", "beagleMi355EigenStats", "beagleMi355UpdateTransitionMatricesFromGenerators", "beagleMi355GeneratorStats", "beagleMi355SetTipEmission", "beagleMi355TipEmissionStats",
                "beagleMi355GetPartialsPinned", "beagleMi355GetSiteLogLikelihoodsPinned",
-               "beagleMi355KernelTimerCalls", "beagleMi355WalkHealth", "beagleMi355RepeatStats", "beagleMi355WalkLaunchInfo", "beagleMi355RootFusedCount", "beagleMi355SitePrefetchCount", "beagleMi355KernelTimerRestart", "beagleMi355GetDimensions", "beagleMi355GetCommUniqueId", "beagleMi355CommInit", "beagleMi355CommInfo", "beagleMi355CalculateRootLogLikelihoodsAllReduce"] + \
+               "beagleMi355KernelTimerCalls", "beagleMi355WalkHealth", "beagleMi355RepeatStats", "beagleMi355TableOperandStats", "beagleMi355WalkLaunchInfo", "beagleMi355RootFusedCount", "beagleMi355SitePrefetchCount", "beagleMi355KernelTimerRestart", "beagleMi355GetDimensions", "beagleMi355GetCommUniqueId", "beagleMi355CommInit", "beagleMi355CommInfo", "beagleMi355CalculateRootLogLikelihoodsAllReduce"] + \
               ["beagleBasta" + k for k in ("AllocateCoalescentBuffers", "UpdatePartials", "AccumulatePartials", "GetBuffer", "GetBufferLength", "Stats", "SampleStates", "StatesStats",
                                            "Gradient", "GradientStats", "UpdatePartialsGrad", "UpdateTransitionMatricesGrad", "AccumulatePartialsGrad")]
 BASTA_OPERATION_SIZE = 8
@@ -1049,6 +1049,13 @@ class Beagle:
         keys = ("table_rows", "table_reads", "repeat_clades", "table_bytes", "clades_indexed", "index_host_us", "two_table_nodes",
                 "tables_under_definitions", "index_host_bytes", "index_resets")
         return {k: int(out[i]) for i, k in enumerate(keys)}
+
+    def tableOperandStats(self):
+        """Class-table operands in the assembly loop's programs since the last kernelTimer call (include/beagle_mi355.h beagleMi355TableOperandStats)."""
+        out = (C.c_long * 4)()
+        self._check("tableOperandStats", self._ext("beagleMi355TableOperandStats", [C.c_int, C.POINTER(C.c_long)])(self.instance, out))
+        return {"table_first_children": int(out[0]), "behind_memory_first_child": int(out[1]), "behind_fused_cherry": int(out[2]),
+                "max_classes": int(out[3])}
 
     def walkHealth(self):
         """The one-launch walk since instance creation (include/beagle_mi355.h beagleMi355WalkHealth)."""

@@ -117,6 +117,9 @@ struct Instance {
         long memReads = 0, tipReads = 0, scaleReads = 0, scaleWrites = 0, stored = 0, fused = 0;      // (fused: cherries, kernels.h WK_CHERRY)
         long microOps = 0;                               // of the walk proper (class-table programs: tableRows)
         long tableRows = 0, tableReads = 0, repeatClades = 0, twoTables = 0, unstoredConsumers = 0;   // repeated sub-patterns (below)
+        // ... as the device program has them (ProgramResolver::microOp; beagleMi355TableOperandStats): first children read from tables, those
+        // directly behind a micro-operation whose first child comes from memory / that has a fused cherry, the most classes of a table read
+        long tabFirst = 0, tabFirstBehindMem = 0, tabFirstBehindCherry = 0, tabMaxClasses = 0;
     };
     // a plan resolved to device addresses (engine_walk.cpp resolveProgram).  A cached plan's (planner.h plannedTag) is kept in one of
     // `resolved`; any other resolves into `scratch`, which is never reused and keeps nothing on the device.
@@ -182,7 +185,7 @@ struct Instance {
     mi355::RepeatIndex repeatIndex;
     std::vector<std::vector<uint8_t>> hostTips;          // per tip: the state codes as uploaded (what the index is built from)
     long tipDataEpoch = 0, repeatEpoch = -1, repeatCompactEpoch = -1;     // setTipStates calls; what the index and the tables were made under
-    struct RepeatTable { int D = 0, arena = 0, row = 0; char* dev = nullptr; size_t bytes = 0, tipStride = 0; std::vector<int> tips; };   // dev: [row vector | tip rows]
+    struct RepeatTable { int D = 0, arena = 0, row = 0; char* dev = nullptr; size_t bytes = 0, tipStride = 0; std::vector<int> tips; };   // dev: [row vector (uint16 class ids, kernels.h WK_TAB) | tip rows]
     std::unordered_map<int, RepeatTable> repeatTables;   // by clade
     // where the tables' row vectors and tip rows live: a few large device blocks handed out front to back (all of it is given up at
     // once, dropRepeatTables), filled by stream-ordered copies out of a pinned staging buffer — no allocation and no blocking copy per table
@@ -192,6 +195,7 @@ struct Instance {
     double* repeatArena = nullptr; int repeatArenas = 0; mi355::RepeatRows repeatRows;      // [arenas][C][P][4]; who has which rows
     std::vector<int> repeatQueue;                        // clades waiting for their index (built where the host waits for a result)
     long statTableRows = 0, statTableReads = 0, statRepeatClades = 0, statTwoTables = 0, statUnstoredConsumers = 0;      // since the last timer reset
+    long statTabFirst = 0, statTabFirstBehindMem = 0, statTabFirstBehindCherry = 0, statTabMaxClasses = 0;               // (the same)
     size_t repeatTableCap = 0;                           // most tables kept (three times what the last compressed plan took): past it, as when the arena is full
     bool lastPlanCached = false;                         // the last runPlan ran a cached full-evaluation plan (the result wait behind it is long enough for index work)
     long statRepeatResets = 0;                           // times the indices were dropped at their capacity, since creation

@@ -115,6 +115,8 @@ static void dropRepeatTables(Instance* in, bool index) {
 }
 void repeatsForget(Instance* in) { in->repeatSlicingOff = false; if (in->repeatsOn && (in->repeatIndex.size() || !in->repeatTables.empty())) dropRepeatTables(in, true); }
 
+// the row vector of a class table: the pattern's class id (uint16) at its pair position (kernels.h WK_TAB), padded to 256 bytes
+static inline size_t repeatRowBytes(const Instance* in) { return (in->pairLen * sizeof(uint16_t) + 255) & ~(size_t)255; }
 // the class table of `clade` (its index is built): rows of the arena, the row vector and the representatives' tip states on the device.
 // nullptr: no room (*full), or out of memory
 static Instance::RepeatTable* repeatTableFor(Instance* in, int clade, bool* full) {
@@ -123,12 +125,13 @@ static Instance::RepeatTable* repeatTableFor(Instance* in, int clade, bool* full
     const mi355::RepeatIndex::Clade& c = in->repeatIndex.clade(clade);
     const int P = in->P, Dpad = (c.D + 127) & ~127;
     if (Dpad > P || !in->repeatArena) return nullptr;
+    if (c.D > 65535) return nullptr;                  // (a class id is 16 bits in the row vector, as it is in the index)
     if (in->repeatTableCap && in->repeatTables.size() >= in->repeatTableCap) { *full = true; return nullptr; }
     Instance::RepeatTable t;
     const mi355::RepeatRows before = in->repeatRows;
     if (!in->repeatRows.place(c.D, t.arena, t.row)) { *full = true; return nullptr; }
     t.D = c.D; t.tips = c.tips; t.tipStride = (size_t)Dpad;
-    const size_t rowBytes = (in->pairLen * sizeof(unsigned) + 255) & ~(size_t)255;
+    const size_t rowBytes = repeatRowBytes(in);
     t.bytes = rowBytes + t.tips.size() * t.tipStride + 256;
     t.bytes = (t.bytes + 255) & ~(size_t)255;
     // device room from the pool, host room in the pinned staging buffer (wrapping it waits for the copies still reading it: the first
@@ -154,10 +157,10 @@ static Instance::RepeatTable* repeatTableFor(Instance* in, int clade, bool* full
     if (in->repeatStageSize - in->repeatStageUsed < t.bytes) { (void)hipStreamSynchronize(live(in)); in->repeatStageUsed = 0; }
     unsigned char* const h = reinterpret_cast<unsigned char*>(in->repeatStage + in->repeatStageUsed);
     memset(h, 4, t.bytes);                            // (padding of the tip rows: "missing")
-    unsigned* rows = reinterpret_cast<unsigned*>(h);
-    const size_t base = (size_t)t.arena * in->C * P + (size_t)t.row;
-    for (size_t q = 0; q < in->pairLen; q++) rows[q] = (unsigned)(base * 32);
-    for (int p = 0; p < P; p++) rows[in->pairPos[(size_t)p]] = (unsigned)((base + c.cls[(size_t)p]) * 32);
+    // (the table's first row is not in the entries: a consumer's descriptor carries its address, ProgramResolver::microOp)
+    uint16_t* rows = reinterpret_cast<uint16_t*>(h);
+    memset(rows, 0, rowBytes);
+    for (int p = 0; p < P; p++) rows[in->pairPos[(size_t)p]] = c.cls[(size_t)p];
     for (size_t k = 0; k < t.tips.size(); k++) {
         const std::vector<uint8_t>& st = in->hostTips[(size_t)t.tips[k]];
         unsigned char* dst = h + rowBytes + k * t.tipStride;
@@ -169,7 +172,7 @@ static Instance::RepeatTable* repeatTableFor(Instance* in, int clade, bool* full
     return &in->repeatTables.emplace(clade, std::move(t)).first->second;
 }
 static inline const uint8_t* repeatTipRows(const Instance* in, const Instance::RepeatTable& t, int tip) {
-    const size_t rowBytes = (in->pairLen * sizeof(unsigned) + 255) & ~(size_t)255;
+    const size_t rowBytes = repeatRowBytes(in);
     for (size_t k = 0; k < t.tips.size(); k++) if (t.tips[k] == tip) return (const uint8_t*)t.dev + rowBytes + k * t.tipStride;
     return nullptr;
 }
@@ -456,15 +459,20 @@ int ProgramResolver::microOp(Slice& s, int i) {
     else if (m.k1 == mi355::PK_TIPS) { d.src1 = tipSrc(s, m.a1); if (!d.src1) return BEAGLE_ERROR_OUT_OF_RANGE; if (!s.low) t.tipReads++; }
     if (m.k2 == mi355::PK_MEM) { d.src2 = in->partials[m.a2]; if (!d.src2 || isCompactTip(in, m.a2)) return BEAGLE_ERROR_OUT_OF_RANGE; t.memReads++; }
     else if (m.k2 == mi355::PK_TIPS) { d.src2 = tipSrc(s, m.a2); if (!d.src2) return BEAGLE_ERROR_OUT_OF_RANGE; if (!s.low) t.tipReads++; }
-    // a child from a class table (kernels.h WK_TAB): its row vector, and the arena where a write-mode operation has its scale buffer
+    // a child from a class table (kernels.h WK_TAB): its row vector, and where a write-mode operation has its scale buffer the address
+    // of the table's first row — the first table child's; a second one's as a distance from it, in rows
     if (m.k1 == mi355::PK_TAB || m.k2 == mi355::PK_TAB) {
+        long firstRow = -1;
         for (int which = 0; which < 2; which++) {
             if ((which ? m.k2 : m.k1) != mi355::PK_TAB) continue;
             const auto tb = in->repeatTables.find(which ? m.a2 : m.a1);
             if (tb == in->repeatTables.end()) return BEAGLE_ERROR_GENERAL;
             (which ? d.src2 : d.src1) = tb->second.dev;
+            const long row = (long)tb->second.arena * in->C * in->P + tb->second.row;
+            t.tabMaxClasses = std::max(t.tabMaxClasses, (long)tb->second.D);
+            if (firstRow < 0) { firstRow = row; d.scaleW = in->repeatArena + (size_t)row * 4; }
+            else d.tab2 = (int)(row - firstRow);
         }
-        d.scaleW = in->repeatArena;
     }
     if (m.smode != mi355::PS_NONE) {
         int rc = ensureScale(in, m.scaleIdx); if (rc) return rc;
@@ -513,7 +521,15 @@ int ProgramResolver::microOp(Slice& s, int i) {
         s.cherry = -1;
     }
     d.flags = mi355::walkFlags(m.k1, k2, m.hold, smodeNow, m.storeBuf >= 0 || tableStore);
-    if (asmLoop && m.k1 == mi355::PK_TAB) d.flags |= mi355::WF_X | mi355::WF_TAB1;
+    if (asmLoop && m.k1 == mi355::PK_TAB) {
+        d.flags |= mi355::WF_X | mi355::WF_TAB1;
+        t.tabFirst++;
+        if ((int)w.size() > progStart) {
+            const unsigned pf = w.back().flags;
+            if ((pf & mi355::WF_X) && !(pf & mi355::WF_TAB1)) t.tabFirstBehindMem++;
+            if (pf & mi355::WF_CHERRY2) t.tabFirstBehindCherry++;
+        }
+    }
     if (asmLoop && k2 == mi355::PK_TAB) d.flags |= mi355::WF_MEM2 | mi355::WF_TAB2;
     if (m.k1 != mi355::PK_TIPS) d.flags |= skipLoads & mi355::WF_NOLOAD1;
     if (k2 != mi355::PK_TIPS) d.flags |= skipLoads & mi355::WF_NOLOAD2;
@@ -543,7 +559,7 @@ void ProgramResolver::sliceEpilogue(const Slice& s) {
         w.back().store = (double*)(in->sliceExp.as<int>() + s.si * in->pairLen);
     }
     static const int padMode = labEnv("BEAGLE_MI355_WALK_PAD_FETCH") ? atoi(labEnv("BEAGLE_MI355_WALK_PAD_FETCH")) : 1;     // (LAB builds: 0 never, 1 the default, 2 both)
-    mi355::walkStageWaits(w.data(), sg.progStart, sg.progCount, asmLoop, in->strictWaits, padMode);
+    mi355::walkStageWaits(w.data(), sg.progStart, sg.progCount, asmLoop, in->strictWaits, padMode, /* tableIds */ asmLoop);
     if (s.low) { sg.pStart = s.tab->row; sg.pEnd = s.tab->row + s.tab->D; sg.tStart = 0; sg.next = -1; return; }
     const mi355::PlanSeg& ps = *s.ps;
     sg.pStart = in->partStart[ps.partition]; sg.pEnd = in->partEnd[ps.partition]; sg.tStart = in->padStart[ps.partition];
@@ -591,6 +607,8 @@ static void accountTraffic(Instance* in, const Instance::Resolved& r) {
     in->statScaleWrites += t.scaleWrites; in->statStored += t.stored; in->statFused += t.fused; in->statMicroOps += t.microOps;
     in->statTableRows += t.tableRows; in->statTableReads += t.tableReads; in->statRepeatClades += t.repeatClades;
     in->statTwoTables += t.twoTables; in->statUnstoredConsumers += t.unstoredConsumers;
+    in->statTabFirst += t.tabFirst; in->statTabFirstBehindMem += t.tabFirstBehindMem; in->statTabFirstBehindCherry += t.tabFirstBehindCherry;
+    in->statTabMaxClasses = std::max(in->statTabMaxClasses, t.tabMaxClasses);
 }
 
 // the slices' products of factors this run leaves behind, and which scale buffers they cover (engine_abi.cpp accumulate)

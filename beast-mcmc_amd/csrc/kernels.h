@@ -67,11 +67,16 @@ bool grantDynamicLds(const void* kernel, size_t bytes);
 enum { WK_MEM = 0, WK_TIPS = 1, WK_ACC = 2, WK_H0 = 3, WK_H1 = 4, WK_H2 = 5, WK_CHERRY = 6, WK_TAB = 7 };
 // WK_TAB (first or second operand; 4 states): the child is a clade whose value an earlier launch evaluated once per distinct sub-pattern
 // (planner.h RepeatIndex, engine_walk.cpp).  src1 / src2 = the clade's ROW VECTOR: per pattern, pair-interleaved like the tip states, the
-// byte offset (uint32) of the pattern's class row from the start of the table arena — laid out [C][P][4] like a partials buffer, or
-// several of them back to back —, whose address the descriptor carries in scaleW (such a micro-operation never rescales in write mode).
-// The lane's two rows are read at arena + offset + c P 32: an index load, a wait, the row loads.  k_walk4 does that where it consumes
-// the operand; for the assembly loop the engine adds WF_X | WF_TAB1 (the row loads then count as a first child from memory in the
-// stage waits) or WF_MEM2 | WF_TAB2 (the blocking second-child path).
+// pattern's CLASS ID (uint16: a lane's pair is one aligned dword, first pattern in the low half; padding positions hold 0).  The table's
+// rows lie in the table arena — laid out [C][P][4] like a partials buffer, or several of them back to back — from the table's first row
+// on: the descriptor carries that address, arena + (arena index . C . P + first row) . 32, in scaleW (such a micro-operation never
+// rescales in write mode) for its first table child (first or second operand); where BOTH children are tables, tab2 holds the second
+// one's address as a signed distance from scaleW in rows (units of 32 bytes; 0 where only one child is a table).  The lane's two rows
+// are read at base + 32 id + c P 32.  k_walk4 loads the ids where it consumes the operand: an index load, a wait, the row loads.  For the
+// assembly loop the engine adds WF_X | WF_TAB1 (the row loads then count as a first child from memory in the stage waits) or WF_MEM2 |
+// WF_TAB2 (the blocking second-child path); the loop requests the ids two stages ahead, right behind the micro-operation's fetch (WF_TABFAR),
+// into the pipeline slot's tip-state register of that child, so that only the row loads are left where the operand is consumed
+// (walkStageWaits, tableIds).
 // WK_CHERRY (second operand only, k_walk4_fast only; round 6): the child is a node over two compact tips whose own micro-operation the
 // engine has FUSED into this one (engine_walk.cpp ProgramResolver::microOp): src2 = the states of its first tip, scale = those of its second (the
 // micro-operation multiplies by no reciprocals: WF_INV and WK_CHERRY exclude each other), the same entry of the matrix stream's cherry
@@ -92,7 +97,11 @@ enum { WF_X = 1, WF_T1 = 2, WF_T2 = 4, WF_INV = 8, WF_STORE = 16, WF_CHERRY2 = 1
 // k_walk4 keeps its wait-table jump there (walkWaitJump) — "the fetch skips the first / second tip-state load" (WF_NOLOAD1 / 2: the
 // child is no compact tip; set in programs that do not rescale in write mode) and the stage's wait as a 4-bit code (walkWaitCode)
 enum : unsigned { WF_HREAD = 1u << 24, WF_HREAD1 = 1u << 25, WF_MEM2 = 1u << 26, WF_HWRITE = 1u << 27, WF_NOLOAD1 = 1u << 16, WF_NOLOAD2 = 1u << 17,
-                  WF_WAIT_SHIFT = 18, WF_HREAD2 = 1u << 31, WF_TAB1 = 1u << 28, WF_TAB2 = 1u << 29 };
+                  WF_WAIT_SHIFT = 18, WF_HREAD2 = 1u << 31, WF_TAB1 = 1u << 28, WF_TAB2 = 1u << 29,
+                  // (walkStageWaits, tableIds) WF_TABFAR, the bit above the wait code: behind this stage's wait the loop requests the class ids
+                  // of the table children of the micro-operation TWO ahead, which the stage has just fetched; WF_TABSYNC: nobody requested
+                  // this micro-operation's ids — a slice's first two, which have no stage two in front of them: its table block loads them
+                  WF_TABFAR = 1u << 22, WF_TABSYNC = 1u << 23 };
 // k_walk4_fast's pipeline is three micro-operations deep: the wait of stage k is "at most N vector-memory instructions outstanding",
 // N = what was issued behind the small loads of k and may stay in flight (walkStageWaits below).  A fetch is three loads, four
 // for a micro-operation that multiplies by reciprocal scale factors (WF_INV), six with a fused cherry (WF_CHERRY2: its table half and
@@ -113,7 +122,7 @@ struct WalkOp {              // 64 bytes = one scalar-cache line; every field is
                              // which also pads a fetch behind write-mode stores: walkStageWaits)
     // (the first 48 bytes are what the assembly loop loads per micro-operation: s_load_dwordx8 at 0, s_load_dwordx4 at 32)
     unsigned       flags;    // WF_* | k1 << 5 | k2 << 8 | hold << 11 | scaleMode << 13 | waitJump << 16 (walkWaitJump)
-    unsigned       pad0;
+    int            tab2;     // WK_TAB on both children: the second table's first row, in rows behind scaleW (see WK_TAB); otherwise 0
     double*        scaleW;   // WS_WRITE: the scale buffer that receives the factors (plain layout) and, recipOff doubles on, their reciprocals
     const double*  m1;       // first / second child's branch matrix, category 0 ([C][4][4] doubles): read by
     const double*  m2;       // k_gatherMatrices, which lays them out as the stream the walk reads
@@ -159,7 +168,12 @@ inline unsigned walkWaitJump(int n) { return (unsigned)(8 * n + 12) << 16; }
 // A smaller N than the true number only waits longer.
 // asmLoop: k_walk4_fast runs the program (otherwise a two-deep pipeline: k_walk4, k_walkT32).  padMode (LAB builds:
 // BEAGLE_MI355_WALK_PAD_FETCH): 0 never pad a fetch, 1 behind write-mode rescaling (the default), 2 also behind stored results.
-inline void walkStageWaits(WalkOp* w, int first, int count, bool asmLoop, bool strictWaits, int padMode) {
+// tableIds (the assembly loop as generated today; false: the loop that loaded a table child's row ids where it consumed them, behind a
+// full wait): sets WF_TABSYNC on a slice's first two micro-operations where they have table children and WF_TABFAR on micro-operation i
+// where i + 2 has table children and is not one of those; behind the wait of a stage with WF_TABFAR the loop issues one load per table
+// child of i + 2 — the lane's two class ids, the first child's in front of the second's —, and the block that reads a FIRST table
+// child's rows runs in the middle of the stage before its use, without a wait of its own: that stage's wait lets the id load land too.
+inline void walkStageWaits(WalkOp* w, int first, int count, bool asmLoop, bool strictWaits, int padMode, bool tableIds = false) {
     if (asmLoop) {
         // The stage waits below count LOADS.  Stores share the counter: a stage that finds stores of the two micro-operations
         // before it still unacknowledged waits for as many of them as its N falls short of "loads + stores".  With four loads per
@@ -194,7 +208,19 @@ inline void walkStageWaits(WalkOp* w, int first, int count, bool asmLoop, bool s
         auto fetchLoads = [&](int j) { const unsigned f = w[j].flags;             // (matrix table; tip states, twice; reciprocals; a fused cherry's table half and tips)
                                        return 1 + ((f & WF_NOLOAD1) ? 0 : 1) + ((f & WF_NOLOAD2) ? 0 : 1) + ((f & WF_INV) ? 1 : 0) + ((f & WF_CHERRY2) ? 3 : 0); };
         const int x1 = i > first && (w[i - 1].flags & WF_X) ? 4 : 0;
-        const int nWait = (w[i].flags & WF_X) ? fetchLoads(i + 2) : fetchLoads(i + 1) + fetchLoads(i + 2) + x1;
+        int nWait = (w[i].flags & WF_X) ? fetchLoads(i + 2) : fetchLoads(i + 1) + fetchLoads(i + 2) + x1;
+        if (tableIds) {
+            // Issue order with the class ids: ... fetch(i) | WAIT(i - 2) | ids(i) | first child of i - 1 | fetch(i + 1) | WAIT(i - 1) | ids(i + 1) |
+            // first child of i | fetch(i + 2) | WAIT.  The ids of i + 1 lie between fetch(i + 1) and what follows it: they count; and where
+            // i + 1 reads a table FIRST child — in the middle of THIS stage — its ids have to have landed: only a second child's ids and
+            // fetch(i + 2) are behind them (a first child of i from memory too, but then the stage waits for that anyway).
+            auto prefetched = [&](int j) { return j - first >= 2 && j < first + count; };
+            const unsigned fn = w[i + 1].flags;
+            const int ids2 = (fn & WF_TAB2) ? 1 : 0;
+            if (i - first < 2 && (w[i].flags & (WF_TAB1 | WF_TAB2))) w[i].flags |= WF_TABSYNC;
+            if (prefetched(i + 2) && (w[i + 2].flags & (WF_TAB1 | WF_TAB2))) w[i].flags |= WF_TABFAR;
+            if (prefetched(i + 1) && !(w[i].flags & WF_X)) nWait = (fn & WF_TAB1) ? ids2 + fetchLoads(i + 2) : nWait + ids2;
+        }
         w[i].flags |= walkWaitCode(nWait);
     }
 }

@@ -65,9 +65,11 @@ struct Fetched {
 struct Desc {                 // a WalkOp in SGPRs (11 dwords; the matrices come through the stream, not the descriptor)
     u64 src1, src2, store, scale, scaleW;
     unsigned flags;
+    int tab2;                 // (k_walk4Tab only: where a second table child's rows begin, in rows behind scaleW — kernels.h WK_TAB)
 };
 // scalar loads of exactly the dwords in use: an unused lane of a wider load would be a register the allocator hands out
 // while the load is still pending
+template <bool TAB = false>
 __device__ __forceinline__ Desc loadDesc(const unsigned MI355_CONST* p) {
     const u32x8 a = *reinterpret_cast<const u32x8 MI355_CONST*>(p);
     Desc r;
@@ -75,6 +77,8 @@ __device__ __forceinline__ Desc loadDesc(const unsigned MI355_CONST* p) {
     r.scale = ((u64)a.s7 << 32) | a.s6;
     r.flags = p[8];                                  // (kernels.h WalkOp: flags at byte 32, scaleW at 40)
     r.scaleW = ((u64)p[11] << 32) | p[10];
+    r.tab2 = 0;
+    if constexpr (TAB) r.tab2 = (int)p[9];
     return r;
 }
 
@@ -202,18 +206,19 @@ __device__ __forceinline__ v4d tipColumn(const char* tbl, unsigned s) {
     return v4d{lo.x, lo.y, hi.x, hi.y};
 }
 
-// A WK_TAB operand (kernels.h): the class rows of the lane's two patterns — the offsets from the clade's row vector (uint32 per pattern at
-// the pattern's pair position), then 32 bytes per pattern at arena + offset + c P 32.  Blocking: per pattern index load, wait, row loads;
+// A WK_TAB operand (kernels.h): the class rows of the lane's two patterns — the uint16 class ids from the clade's row vector (at the
+// pattern's pair position), then 32 bytes per pattern at base + 32 id + c P 32, base = the table's first row.  Blocking: per pattern
+// index load, wait, row loads (the assembly loop requests the ids with its fetch; this kernel needs no prefetch);
 // every load issued before has landed by then, so the exact stage waits around it only wait for less.  Branched around inside the
 // block where the operand kind is another (`kind`: the 3-bit field), like the groups of fetchIssue: the registers keep their contents.
-__device__ __forceinline__ void tableRowsIf(unsigned kind, v2d& a0, v2d& a1, v2d& b0, v2d& b1, const LaneOffsets& o, u64 rows, u64 arena, int c, int P) {
-    const u64 base = arena + (u64)((unsigned)c * (unsigned)P * 32u);
+__device__ __forceinline__ void tableRowsIf(unsigned kind, v2d& a0, v2d& a1, v2d& b0, v2d& b1, const LaneOffsets& o, u64 rows, u64 table, int c, int P) {
+    const u64 base = table + (u64)((unsigned)c * (unsigned)P * 32u);
     unsigned i;                                       // (one pattern after the other: one index register)
     asm volatile("s_cmp_eq_u32 %[kind], 7\n\t"
                  "s_cbranch_scc0 .Ltr%=\n\t"
-                 "v_lshlrev_b32 %[i], 2, %[tA]\n\tglobal_load_dword %[i], %[i], %[rows]\n\ts_waitcnt vmcnt(0)\n\t"
+                 "v_lshlrev_b32 %[i], 1, %[tA]\n\tglobal_load_ushort %[i], %[i], %[rows]\n\ts_waitcnt vmcnt(0)\n\tv_lshlrev_b32 %[i], 5, %[i]\n\t"
                  "global_load_dwordx4 %[a0], %[i], %[base]\n\tglobal_load_dwordx4 %[a1], %[i], %[base] offset:16\n\t"
-                 "v_lshlrev_b32 %[i], 2, %[tB]\n\tglobal_load_dword %[i], %[i], %[rows]\n\ts_waitcnt vmcnt(0)\n\t"
+                 "v_lshlrev_b32 %[i], 1, %[tB]\n\tglobal_load_ushort %[i], %[i], %[rows]\n\ts_waitcnt vmcnt(0)\n\tv_lshlrev_b32 %[i], 5, %[i]\n\t"
                  "global_load_dwordx4 %[b0], %[i], %[base]\n\tglobal_load_dwordx4 %[b1], %[i], %[base] offset:16\n\ts_waitcnt vmcnt(0)\n"
                  ".Ltr%=:"
                  : [a0] "+v"(a0), [a1] "+v"(a1), [b0] "+v"(b0), [b1] "+v"(b1), [i] "=&v"(i)
@@ -257,7 +262,7 @@ __device__ __forceinline__ void walk4Body(const unsigned MI355_CONST* __restrict
     double pmA = 1.0, pmB = 1.0;
     int peA = 0, peB = 0;
     const unsigned MI355_CONST* dp = prog + (size_t)progStart * 16;   // the host pads every segment: progCount is even and
-    Desc D0 = loadDesc(dp), D1 = loadDesc(dp + 16);                    // two more descriptors (no-ops) follow it
+    Desc D0 = loadDesc<TAB>(dp), D1 = loadDesc<TAB>(dp + 16);          // two more descriptors (no-ops) follow it
     // the matrix stream: entry k is the [C] matrix tables of the program's k-th micro-operation (k_gatherMatrices)
     const unsigned strmStep = (unsigned)C * WALK_TABLE_BYTES;
     u64 strm = (u64)(matStream) + (u64)progStart * strmStep;
@@ -271,8 +276,9 @@ __device__ __forceinline__ void walk4Body(const unsigned MI355_CONST* __restrict
     {                                                                                                                     \
         const unsigned fl = DCUR.flags;                                                                                   \
         const u64 dStore = DCUR.store, dScale = DCUR.scaleW, dSrc2 = DCUR.src2;                                            \
+        const int dTab2 = DCUR.tab2;                                                                                      \
         const int k1n = (DNXT.flags >> 5) & 7;         /* a hold-slot operand of the NEXT micro-operation is read now */  \
-        /* ... and operands from a class table (kernels.h WK_TAB; scaleW = the arena): the next one's first child where a hold-slot  \
+        /* ... and operands from a class table (kernels.h WK_TAB; scaleW = its first row): the next one's first child where a hold-slot  \
            operand would go (a program's FIRST micro-operation has no stage before it: the host puts a no-op in front of one that   \
            reads a table first, engine_walk.cpp microOp) */                                                                       \
         if constexpr (TAB) tableRowsIf((unsigned)k1n, NXT.xa0, NXT.xa1, NXT.xb0, NXT.xb1, o, DNXT.src1, DNXT.scaleW, c, P);     \
@@ -294,7 +300,7 @@ __device__ __forceinline__ void walk4Body(const unsigned MI355_CONST* __restrict
         else if (k2 == WK_ACC) matvecDpp2(*reinterpret_cast<const double*>(tb + WALK_TABLE_M2 + spOff), ACCa, ACCb, ga, gb);   \
         else if (TAB && k2 == WK_TAB) {                /* the second child from a class table: like a second child in memory, below */ \
             v2d y0 = v2d{1.0, 1.0}, y1 = y0, y2 = y0, y3 = y0;                                                            \
-            tableRowsIf(7u, y0, y1, y2, y3, o, dSrc2, dScale, c, P);                                                      \
+            tableRowsIf(7u, y0, y1, y2, y3, o, dSrc2, dScale + (u64)((long)dTab2 * 32), c, P);                            \
             matvecDpp2(*reinterpret_cast<const double*>(tb + WALK_TABLE_M2 + spOff), v4d{y0.x, y0.y, y1.x, y1.y},         \
                        v4d{y2.x, y2.y, y3.x, y3.y}, ga, gb);                                                              \
         } else {                                         /* both children in memory (rare): the second one is not prefetched */ \
@@ -309,7 +315,7 @@ __device__ __forceinline__ void walk4Body(const unsigned MI355_CONST* __restrict
            LDS wait also waits for them: issued HERE, behind the stage's LDS reads, they have the arithmetic below to land */ \
         v4d ra = fa * ga, rb = fb * gb;                                                                                   \
         asm volatile("" : "+v"(ra), "+v"(rb));         /* (keeps the loads below behind the products' LDS wait) */         \
-        DCUR = loadDesc(dp + 32);                                                                                         \
+        DCUR = loadDesc<TAB>(dp + 32);                                                                                    \
         dp += 16;                                                                                                         \
         if (smode == WS_READ) { ra = ra * CUR.inva; rb = rb * CUR.invb; }                                                 \
         else if (smode == WS_WRITE) {                                                                                     \

@@ -815,6 +815,12 @@ int beagleMi355WalkHealth(int instance, long* out4);
  * of host memory the class indices take, out[9]: times they were dropped at their capacity (a chain of topology moves).  All zero where
  * the feature is off (BEAGLE_MI355_NO_REPEATS=1, small buffers, write-mode evaluations). */
 int beagleMi355RepeatStats(int instance, long* out10);
+/* Class-table operands as the device programs of the assembly loop read them (4 states), since the last beagleMi355KernelTimer /
+ * KernelTimerRestart call — out[0]: micro-operations whose FIRST child is read from a class table, out[1]: those that come directly
+ * behind a micro-operation whose own first child is read from memory, out[2]: those directly behind a micro-operation with a fused
+ * cherry (the two neighbours whose loads lie between a table child's class ids and its rows), out[3]: the largest class count of a
+ * table read.  All zero where the feature is off or another kernel runs the programs. */
+int beagleMi355TableOperandStats(int instance, long* out4);
 /* How the one-launch walks of a 4-state instance were run since its creation: out[0] launches on TICKETS (the program's slices form
  * a forest: only the slices without dependencies get workgroups, the workgroup that arrives last at a slice above runs it — nobody
  * waits; the default), out[1] launches on dependency FLAGS (every slice its own workgroups, which poll: programs whose slices do not

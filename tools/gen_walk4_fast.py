@@ -75,6 +75,12 @@ B_HREAD, B_HREAD1, B_MEM2, B_HWRITE, B_HREAD2 = 24, 25, 26, 27, 31
 # B_TAB1 / B_TAB2 (kernels.h WK_TAB): the first / second child is read from a class table — set together with B_X / B_MEM2, whose
 # out-of-line blocks branch to table_rows below; nothing on the loop's common path knows about them
 B_TAB1, B_TAB2 = 28, 29
+# B_TABFAR (kernels.h WF_TABFAR), the bit above the stage's wait code: the micro-operation TWO AHEAD — the one this stage has just fetched,
+# its descriptor still in D — reads a child from a class table: behind its wait the stage requests that child's class ids (table_ids).
+# Read as a fifth bit of the wait code it sends the stage through the second half of the wait jump table, so the common path and the hot
+# out-of-line blocks are, byte for byte, those of a loop that knows no tables: programs without table operands (every partial update) run
+# the code they ran.  B_TABSYNC (WF_TABSYNC): nobody requested this micro-operation's ids (a slice's first two) — its table block does.
+B_TABFAR, B_TABSYNC = 22, 23
 # bits 16..23 belong to the kernel that runs the program (k_walk4: its wait-table jump); here: the two tip-state loads of a fetch are
 # SKIPPED under B_NOLOAD1 / B_NOLOAD2 (round 6: the host sets them, in programs that do not rescale in write mode, for a child that is
 # no compact tip — half the children of a tree; a vector-memory instruction occupies the CU's address unit for ~16 cycles whatever it
@@ -346,27 +352,62 @@ def fetch(tag, slot):
         outofline.append([L("iv" + tag) + ":", "global_load_dwordx4 %s, %s, %s" % (v(INVS[slot], 4), v(SCALE), s(D + 6, 2)), "s_branch %s" % L("ivb" + tag)])
 
 
-def table_rows(label, dst, rows, arena, off_rows, off_arena, back, drain):
-    """A child from a class table (kernels.h WK_TAB), out of line and blocking: the descriptor field at DP + off_rows is the clade's row
-    vector — per pattern, at the pair's position like the tip states, the uint32 byte offset of the pattern's class row —, the one at
-    DP + off_arena (the descriptor's scaleW) the table arena; the lane's two rows are at arena + offset + c P 32.  Index load, wait,
-    the four row loads into dst (drain: and wait for them).  The wait in the middle lets every load issued before land too: the exact
-    stage waits, which count the row loads as they count a child from memory, then only wait for less than they have to.  The rows were
-    written by an earlier launch: no device-scope bit, they may stay in this XCD's L2 for the patterns that share them."""
+def table_ids(tag, slot):
+    """Behind the wait of a stage whose flags carry B_TABFAR (the second half of the wait jump table branches here): the class ids of the
+    table children of the micro-operation the stage has just fetched into `slot` (descriptor in D, flags in DFL) — per child the pair's two
+    uint16 ids, ONE dword of the clade's row vector (descriptor field src1 / src2), into the child's tip-state register of the slot: a
+    table child is no tip, and whatever the fetch loaded there landed before (loads return in order).  Cold."""
+    return [L("tf" + tag) + ":",
+            "v_lshlrev_b32_e32 %s, 1, %s" % (v(T0), v(TIP)),
+            "s_bitcmp1_b32 %s, %d" % (s(DFL), B_TAB1),
+            "s_cbranch_scc0 %s" % L("tf2" + tag),
+            "global_load_dword %s, %s, %s" % (v(T1S[slot]), v(T0), s(D, 2)),
+            L("tf2" + tag) + ":",
+            "s_bitcmp1_b32 %s, %d" % (s(DFL), B_TAB2),
+            "s_cbranch_scc0 %s" % L("wd" + tag),
+            "global_load_dword %s, %s, %s" % (v(T2S[slot]), v(T0), s(D + 2, 2)),
+            "s_branch %s" % L("wd" + tag)]
+
+
+def table_rows(label, dst, ids, flags, base, off_rows, off_base, second, back):
+    """A child from a class table (kernels.h WK_TAB), out of line: the row loads.  `ids` holds the pair's two class ids (uint16 each),
+    requested two stages ago (table_ids) and landed behind a stage wait (kernels.h walkStageWaits) — or, under B_TABSYNC in `flags`
+    (a slice's first two micro-operations), not requested at all: then the block loads them from the row vector, the descriptor field
+    at DP + off_rows, and waits (every load issued before lands too: the stage waits then only wait for less than they have to).  The
+    descriptor's scaleW field at DP + off_base is the address of the table's first row — of the first table child; for a SECOND table
+    child (`second`) the signed distance in rows in the word in front of it is added.  The lane's two rows are at base + 32 id + c P 32:
+    the four row loads into dst — a second child drains them, like a second child from memory; a first child's are counted by the stage
+    waits as they count a child from memory.  The rows were written by an earlier launch: no device-scope bit, they may stay in this
+    XCD's L2 for the patterns that share them."""
     blk = [label + ":",
-           "s_load_dwordx2 %s, %s, %d" % (s(rows, 2), s(DP, 2), off_rows),
-           "s_load_dwordx2 %s, %s, %d" % (s(arena, 2), s(DP, 2), off_arena),
-           "v_lshlrev_b32_e32 %s, 2, %s" % (v(T0), v(TIP)),
+           "s_bitcmp1_b32 %s, %d" % (s(flags), B_TABSYNC),
+           "s_cbranch_scc0 %s" % (label[:-3] + "i_%="),
+           "s_load_dwordx2 %s, %s, %d" % (s(SSRC2, 2), s(DP, 2), off_rows),
+           "v_lshlrev_b32_e32 %s, 1, %s" % (v(T0), v(TIP)),
            "s_waitcnt lgkmcnt(0)",
-           "global_load_dwordx2 %s, %s, %s" % (v(T0, 2), v(T0), s(rows, 2)),
+           "global_load_dword %s, %s, %s" % (v(ids), v(T0), s(SSRC2, 2)),
            "s_waitcnt vmcnt(0)",
-           "v_add_u32_e32 %s, %%[cP32], %s" % (v(T0), v(T0)),
-           "v_add_u32_e32 %s, %%[cP32], %s" % (v(T1), v(T1)),
-           "global_load_dwordx4 %s, %s, %s" % (v(dst, 4), v(T0), s(arena, 2)),
-           "global_load_dwordx4 %s, %s, %s offset:16" % (v(dst + 4, 4), v(T0), s(arena, 2)),
-           "global_load_dwordx4 %s, %s, %s" % (v(dst + 8, 4), v(T1), s(arena, 2)),
-           "global_load_dwordx4 %s, %s, %s offset:16" % (v(dst + 12, 4), v(T1), s(arena, 2))]
-    if drain:
+           label[:-3] + "i_%=:"]
+    if second:
+        blk += ["s_load_dwordx2 %s, %s, %d" % (s(base, 2), s(DP, 2), off_base),
+                "s_load_dword %s, %s, %d" % (s(SSRC2), s(DP, 2), off_base - 4)]
+    else:
+        blk += ["s_load_dwordx2 %s, %s, %d" % (s(base, 2), s(DP, 2), off_base)]
+    blk += ["v_and_b32_e32 %s, 0xffff, %s" % (v(T0), v(ids)),
+            "v_lshrrev_b32_e32 %s, 16, %s" % (v(T1), v(ids)),
+            "v_lshl_add_u32 %s, %s, 5, %%[cP32]" % (v(T0), v(T0)),
+            "v_lshl_add_u32 %s, %s, 5, %%[cP32]" % (v(T1), v(T1)),
+            "s_waitcnt lgkmcnt(0)"]
+    if second:
+        blk += ["s_ashr_i32 %s, %s, 31" % (s(SSRC2 + 1), s(SSRC2)),
+                "s_lshl_b64 %s, %s, 5" % (s(SSRC2, 2), s(SSRC2, 2)),
+                "s_add_u32 %s, %s, %s" % (s(base), s(base), s(SSRC2)),
+                "s_addc_u32 %s, %s, %s" % (s(base + 1), s(base + 1), s(SSRC2 + 1))]
+    blk += ["global_load_dwordx4 %s, %s, %s" % (v(dst, 4), v(T0), s(base, 2)),
+            "global_load_dwordx4 %s, %s, %s offset:16" % (v(dst + 4, 4), v(T0), s(base, 2)),
+            "global_load_dwordx4 %s, %s, %s" % (v(dst + 8, 4), v(T1), s(base, 2)),
+            "global_load_dwordx4 %s, %s, %s offset:16" % (v(dst + 12, 4), v(T1), s(base, 2))]
+    if second:
         blk.append("s_waitcnt vmcnt(0)")
     blk.append("s_branch %s" % back)
     if "notab" in EXPERIMENT:                          # (timing only, wrong results: what the gathers cost — profiles/repeats_sweep.txt)
@@ -374,10 +415,10 @@ def table_rows(label, dst, rows, arena, off_rows, off_arena, back, drain):
     return blk
 
 
-def first_child_fetch(tag, SFLn, off_src1):
+def first_child_fetch(tag, SFLn, off_src1, ids):
     """The first child of the FOLLOWING micro-operation (flags in SFLn), if it waits in an LDS hold slot or in memory, into XB —
     behind the last use of XB by the micro-operation at hand; ONE test on the common path.  off_src1: where DP finds that
-    descriptor's src1 now."""
+    descriptor's src1 now; ids: the register its fetch requested a table child's class ids into (table_rows)."""
     e("s_and_b32 %s, %s, 0x%x" % (s(ST), s(SFLn), (1 << B_HREAD) | (1 << B_X)))
     e("s_cbranch_scc1 %s" % L("fr" + tag))
     e(L("frb" + tag) + ":")
@@ -404,7 +445,7 @@ def first_child_fetch(tag, SFLn, off_src1):
             "s_branch %s" % L("frb" + tag)]
     outofline.append(blk)
     # (SSRC2: the second-child block's scratch pair, free in the middle of a stage)
-    coldline.append(table_rows(L("xt" + tag), XB, SX, SSRC2, off_src1, off_src1 + 40, L("frb" + tag), False))
+    coldline.append(table_rows(L("xt" + tag), XB, ids, SFLn, SX, off_src1, off_src1 + 40, False, L("frb" + tag)))
 
 
 def stage(tag, cur):
@@ -420,7 +461,7 @@ def stage(tag, cur):
     # wait for this micro-operation's loads: N = what was issued after them and may stay outstanding — the fetches of k + 1 and
     # k + 2 (8), a first child of k - 1 from memory (+4), stores where the engine counts them (engine_walk.cpp runPlan);
     # 4 when this micro-operation's own first child comes from memory (requested a stage ago, behind the fetch of k + 1)
-    e("s_and_b32 %s, %s, 0x%x" % (s(ST), s(SFL), 15 << B_WAIT0))
+    e("s_and_b32 %s, %s, 0x%x" % (s(ST), s(SFL), 31 << B_WAIT0))            # (the wait code and B_TABFAR above it)
     e("s_cbranch_scc1 %s" % L("ws" + tag))
     novm = "novmwait" in EXPERIMENT
     e("s_nop 0" if novm else "s_waitcnt vmcnt(%d)" % WAIT_N[0])
@@ -429,7 +470,7 @@ def stage(tag, cur):
     # folded program) and code 2 (both fetch four: programs that pay at every node — partial updates, write-mode lists) by a test
     # each, the rest through a jump table of (wait, branch) pairs
     blk = [L("ws" + tag) + ":",
-           "s_bfe_u32 %s, %s, 0x%x" % (s(ST), s(SFL), (4 << 16) | B_WAIT0),
+           "s_bfe_u32 %s, %s, 0x%x" % (s(ST), s(SFL), (5 << 16) | B_WAIT0),
            "s_cmp_eq_u32 %s, 1" % s(ST),
            "s_cbranch_scc0 %s" % L("wu" + tag),
            "s_nop 0" if novm else "s_waitcnt vmcnt(%d)" % WAIT_N[1],
@@ -451,7 +492,11 @@ def stage(tag, cur):
     # and entry 0 is never taken, so the table proper starts at entry 1 = + 20 + 8 - 8: the constant above is 20 - 8 = 12)
     for code in range(1, 16):
         blk += ["s_nop 0" if novm else "s_waitcnt vmcnt(%d)" % WAIT_N[code], "s_branch %s" % L("wd" + tag)]
+    # the second half (B_TABFAR above the code): the same waits, then the class ids of the micro-operation just fetched (table_ids)
+    for code in range(16):
+        blk += ["s_nop 0" if novm else "s_waitcnt vmcnt(%d)" % WAIT_N[code], "s_branch %s" % L("tf" + tag)]
     outofline.append(blk)
+    coldline.append(table_ids(tag, far))
     off_src2 = -3 * 64 + 8
     off_src1_next = -2 * 64
     off_store = -4 * 64 + 16
@@ -515,8 +560,8 @@ def stage(tag, cur):
     m2blk[1:1] = ["s_bitcmp1_b32 %s, %d" % (s(SFL), B_CHERRY), "s_cbranch_scc1 %s" % L("cc" + tag),
                   "s_bitcmp1_b32 %s, %d" % (s(SFL), B_TAB2), "s_cbranch_scc1 %s" % L("m2t" + tag)]
     outofline.append(m2blk)
-    # (SX: the first-child block's scratch pair, free until the middle of the stage)
-    coldline.append(table_rows(L("m2t" + tag), ACC, SSRC2, SX, off_src2, off_src2 - 8 + 40, L("m2b" + tag), True))
+    # (SX: the first-child block's scratch pair, free until the middle of the stage; SSRC2: this path's own)
+    coldline.append(table_rows(L("m2t" + tag), ACC, Tt2, SFL, SX, off_src2, off_src2 - 8 + 40, True, L("m2b" + tag)))
     outofline.append(ccblk)
     e("ds_read_b64 %s, %s offset:160" % (v(SP, 2), v(spCur)))
     col0_reads(XB, tbvCur, 160)                  # (the first-child buffer: consumed by the first mat-vec, or not in use)
@@ -524,7 +569,7 @@ def stage(tag, cur):
     matvec(G, ACC, SP, None, col0v=XB)
     e(L("mul" + tag) + ":")
     # the first child of micro-operation k + 1, where it has to be fetched (XB is free from here on)
-    first_child_fetch(tag, FLS[nxt], off_src1_next)
+    first_child_fetch(tag, FLS[nxt], off_src1_next, T1S[nxt])
     # descriptor k + 3: behind every LDS wait of the stage (scalar loads share the counter with LDS and return out of order)
     e("s_load_dwordx8 %s, %s, 0x0" % (s(D, 8), s(DP, 2)))
     e("s_load_dwordx4 %s, %s, 0x20" % (s(DFL, 4), s(DP, 2)))
@@ -686,7 +731,7 @@ def build():
     e("s_load_dwordx4 %s, %s, 0x60" % (s(DFL, 4), s(DP, 2)))
     e("s_waitcnt lgkmcnt(0)")
     fetch("q", 1)
-    first_child_fetch("p", FLS[0], 0)
+    first_child_fetch("p", FLS[0], 0, T1S[0])
     e("s_load_dwordx8 %s, %s, 0x80" % (s(D, 8), s(DP, 2)))
     e("s_load_dwordx4 %s, %s, 0xa0" % (s(DFL, 4), s(DP, 2)))
     e("s_add_u32 %s, %s, 0xc0" % (s(DP), s(DP)))
