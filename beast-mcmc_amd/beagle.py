@@ -124,7 +124,7 @@ ABI_SYMBOLS = ["beagleGetVersion", "beagleGetCitation", "beagleGetResourceList",
               ["beagle" + k for k in _PROTOS] + \
               ["beagleMi355SetStream", "beagleMi355CalculateRootLogLikelihoodsDevice", "beagleMi355Synchronize",
                "beagleMi355KernelTimer", "beagleMi355DeviceBytes", "beagleMi355WalkStats", "beagleMi355GradientStats", "beagleMi355GetPartialsBatch", "beagleMi355SampleAncestralStates", "beagleMi355SampleMarkovJumps", "beagleMi355SampleMarkovJumpsUniformized",
-               "beagleMi355SimulateSequences", "beagleMi355SimulateCompleteHistories", "beagleMi355RobustCounts", "beagleMi355SimulateUnconditionedCounts", "beagleMi355NodeHeightDerivatives", "beagleMi355UpdateDifferentialMatrices", "beagleMi355SetReversibleModels", "beagleMi355GetEigenDecomposition", "beagleMi355EigenStats", "beagleMi355UpdateTransitionMatricesFromGenerators", "beagleMi355GeneratorStats", "beagleMi355SetTipEmission", "beagleMi355TipEmissionStats",
+               "beagleMi355SimulateSequences", "beagleMi355SimulateCompleteHistories", "beagleMi355RobustCounts", "beagleMi355SimulateUnconditionedCounts", "beagleMi355NodeHeightDerivatives", "beagleMi355UpdateDifferentialMatrices", "beagleMi355SetReversibleModels", "beagleMi355GetEigenDecomposition", "beagleMi355EigenStats", "beagleMi355UpdateTransitionMatricesFromGenerators", "beagleMi355GeneratorStats", "beagleMi355NodePatternLikelihoods", "beagleMi355NodePatternStats", "beagleMi355SetTipEmission", "beagleMi355TipEmissionStats",
                "beagleMi355GetPartialsPinned", "beagleMi355GetSiteLogLikelihoodsPinned",
                "beagleMi355KernelTimerCalls", "beagleMi355WalkHealth", "beagleMi355RepeatStats", "beagleMi355TableOperandStats", "beagleMi355WalkLaunchInfo", "beagleMi355RootFusedCount", "beagleMi355SitePrefetchCount", "beagleMi355KernelTimerRestart", "beagleMi355GetDimensions", "beagleMi355GetCommUniqueId", "beagleMi355CommInit", "beagleMi355CommInfo", "beagleMi355CalculateRootLogLikelihoodsAllReduce"] + \
               ["beagleBasta" + k for k in ("AllocateCoalescentBuffers", "UpdatePartials", "AccumulatePartials", "GetBuffer", "GetBufferLength", "Stats", "SampleStates", "StatesStats",
@@ -742,6 +742,34 @@ class Beagle:
         out = (C.c_long * 4)()
         self._check("generatorStats", self._ext("beagleMi355GeneratorStats", [C.c_int, C.POINTER(C.c_long)])(self.instance, out))
         return {"calls": int(out[0]), "matrices": int(out[1]), "max_squarings": int(out[2]), "refused": int(out[3])}
+
+    def nodePatternLikelihoods(self, nodes, nodeLogWeights, deathState, categoryWeightsIndex=0, stateFrequenciesIndex=0,
+                               node_terms=False, flags=0):
+        """The stochastic Dollo node-pattern likelihood of every pattern in one call (include/beagle_mi355.h
+        beagleMi355NodePatternLikelihoods).  ``nodes``: [nodeCount][4] rows {bufferIndex, scaleBufferIndex, child1Row, child2Row}
+        in post-order (a tip: both child rows -1); ``nodeLogWeights`` [nodeCount].  -> (log pattern values [P], node terms
+        [nodeCount, P] or None, the pattern-weighted sum, return code): the code is 0, or -8 (FLOATING_POINT) when the sum is not
+        finite — the arrays are written either way; every other code raises BeagleException."""
+        rows = _i(nodes).reshape(-1, 4)
+        w = _d(nodeLogWeights)
+        if w.size < rows.shape[0]:
+            raise ValueError("one log weight per row")
+        log_pattern = np.empty(self.patternCount)
+        terms = np.empty((rows.shape[0], self.patternCount)) if node_terms else None
+        total = C.c_double(0.0)
+        f = self._ext("beagleMi355NodePatternLikelihoods", [C.c_int, _IP, _DP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _DP, _DP,
+                                                            C.POINTER(C.c_double)])
+        rc = f(self.instance, _ip(rows), _dp(w), rows.shape[0], deathState, categoryWeightsIndex, stateFrequenciesIndex, flags,
+               _dp(log_pattern), _dp(terms), C.byref(total))
+        if rc != 0 and rc != -8:
+            raise BeagleException("nodePatternLikelihoods", rc)
+        return log_pattern, terms, total.value, rc
+
+    def nodePatternStats(self):
+        """What nodePatternLikelihoods has done (include/beagle_mi355.h beagleMi355NodePatternStats)."""
+        out = (C.c_long * 4)()
+        self._check("nodePatternStats", self._ext("beagleMi355NodePatternStats", [C.c_int, C.POINTER(C.c_long)])(self.instance, out))
+        return {"calls": int(out[0]), "rows": int(out[1]), "empty_patterns": int(out[2]), "materialised": int(out[3])}
 
     def sampleMarkovJumps(self, nodes, branchTimes, branchRates, eigenIndex, categoryRatesIndex, categoryWeightsIndex,
                           stateFrequenciesIndex, registers, registerFlags, seed, map=False, states=False, jumps=False,

@@ -637,6 +637,27 @@ struct AncestralRow {
 void launchSampleAncestral(hipStream_t stream, const AncestralRow* dRows, int nRows, const double* catWeights, const double* freqs,
                            int P, int S, int C, bool tiled, int globalP, int pOffset, unsigned long long seed, bool map,
                            uint8_t* states, int* cats, unsigned* fpError);
+// ---- stochastic Dollo node-pattern likelihood (kernels_nodepattern.hip; beagleMi355NodePatternLikelihoods) ---------------
+// One row of the post-order node list, resolved on the host: the node's partials (plain [C][P][S] or T32) OR its compact tip states
+// (uint8 [P]), its own scale buffer (nullptr: none; raw: factors, not their logarithms), log of its birth weight, its children's
+// rows (-1, -1: a tip) and the scratch slots of the row and of its children — a slot is handed out again once its row's parent has
+// read it.
+struct NodePatternRow {
+    const double*  partials;
+    const uint8_t* states;
+    const double*  scale;
+    double         logWeight;
+    int            child1, child2;
+    int            scaleRaw;
+    int            slot, slot1, slot2;
+};
+int  nodePatternBlocks(int P);               // workgroups over P patterns (entries of blockSums)
+// Patterns [p0, p0 + count) of the instance's P, p0 a multiple of 256: logPattern [P] and blockSums [nodePatternBlocks(P)] at their
+// global places; lambda (doubles) and below (ints) are [slots][stride] scratch and terms (nullptr: not wanted) the [nRows][stride]
+// stage, column p - p0.  blockSums[b] = sum of patternWeights[p] * logPattern[p] over the block's patterns by a fixed tree.
+void launchNodePattern(hipStream_t stream, const NodePatternRow* dRows, int nRows, const double* catWeights, const double* freqs,
+                       const double* patternWeights, int P, int S, int C, bool tiled, int deathState, int p0, int count, int stride,
+                       double* lambda, int* below, double* terms, double* logPattern, double* blockSums);
 // ---- sequence simulation (kernels_simulate.hip; beagleMi355SimulateSequences) -------------------------------------------
 // One row of the pre-order node list, resolved on the host: its branch matrix [C][S][S] (nullptr at the root), the scratch row
 // ("slot") its states go to and the slot of its parent (-1 at the root); parentIsPrev: the parent is the row right before it, whose

@@ -1,7 +1,7 @@
 // scratch_layout.h — what is inside the samplers' grow-on-demand device buffers (engine_internal.h Instance::ancestralDev, jumpDev,
-// uniformDev, eventDev, simulateDev, robustDev, historyDev): a carver that lays sections out one after another, and per buffer a
-// layout that names its sections from plain integers.  Host only, plain C++17, no HIP: tests/native/scratch_layout_check.cpp compiles
-// it alone and checks every layout's offsets, order and alignment.  The .cpp files resolve sections to pointers (at / as) and grow the
+// uniformDev, nodePatternDev, eventDev, simulateDev, robustDev, historyDev): a carver that lays sections out one after another, and per
+// buffer a layout that names its sections from plain integers.  Host only, plain C++17, no HIP: tests/native/scratch_layout_check.cpp
+// (NodePatternLayout: node_pattern_layout_check.cpp) compiles it alone and checks every layout's offsets, order and alignment.  The .cpp files resolve sections to pointers (at / as) and grow the
 // buffer to bytes(); they keep no offset arithmetic.
 #pragma once
 #include <cstddef>
@@ -65,6 +65,17 @@ struct UniformLayout : Carver {
         flags = take<int>(FLAG_SLOTS); align(256);
         longs = take<long long>(P + 2); align(256);
         counts = take<int>(history ? R * P : 0);
+    }
+};
+
+// nodePatternDev: log pattern values [P] | block sums [blocks] | the sum | Lambda [slots][chunk] | term stage [R][chunk]
+//                 (outNodeLogTerms) | (256) extant tips below [slots][chunk]
+struct NodePatternLayout : Carver {
+    Doubles logPattern, blockSums, sum, lambda, terms; Ints below;
+    NodePatternLayout(size_t slots, size_t R, size_t P, size_t chunk, size_t blocks, bool wantTerms) {
+        logPattern = take<double>(P); blockSums = take<double>(blocks); sum = take<double>(1); lambda = take<double>(slots * chunk);
+        terms = take<double>(wantTerms ? R * chunk : 0); align(256);
+        below = take<int>(slots * chunk);
     }
 };
 

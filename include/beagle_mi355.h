@@ -505,6 +505,48 @@ int beagleMi355UpdateTransitionMatricesFromGenerators(int instance, const double
 /* out4 = {beagleMi355UpdateTransitionMatricesFromGenerators calls since creation, matrices (entry x category) they wrote, the largest s
  * of any of them, matrices refused (NaN) for s > 40} (shard 0 of a sharded handle).  Drains the instance's stream. */
 int beagleMi355GeneratorStats(int instance, long* out4);
+/* The stochastic Dollo (ALS) node-pattern likelihood: ONE call behind an ordinary pruning pass — what
+ * AbstractObservationProcess.nodePatternLikelihood computes from a getPartials per node (tips included), a getLogScaleFactors per
+ * internal node and a host loop over nodes x patterns x states (oldevomodel/MSSD/AbstractObservationProcess.java:174-210,
+ * AnyTipObservationProcess.java:97-168, oldevomodel/treelikelihood/ScaleFactorsHelper.java:83-140).
+ *   nodes [nodeCount][4] in post-order: {bufferIndex, scaleBufferIndex, child1Row, child2Row}.  A tip has both child rows -1 and its
+ *          buffer holds compact states or partials; an internal row's children are two different earlier rows, and a row is a child at
+ *          most once.  scaleBufferIndex: the buffer with the log factors the node's partials were divided by, or -1 (ignored on a tip row).
+ *   nodeLogWeights [nodeCount]: logw_i = log(getNodeSurvivalProbability(i)), 0 at the root.
+ *   deathState in [0, stateCount).
+ * For row i and pattern j:
+ *   site_ij   = sum_c w_c (sum_s pi_s x_i[c][j][s]), s and c upwards from 0.0 (a compact tip: pi_state, or sum_s pi_s for a code >=
+ *               stateCount).  The reference reads one category's worth of partials and so only runs with ONE category; the
+ *               category-weighted sum is this library's extension.
+ *   Lambda_ij = (Lambda_child1 + Lambda_child2) + the row's own log scale factor; 0 on a tip row.
+ *   extant_tj = 1 unless tip row t's code at j contains the death state: a compact tip, state < stateCount and != deathState; a tip held
+ *               as partials, partial[category 0][j][deathState] == 0.
+ *   below_ij  = sum of extant over the tip rows under i;  incl_ij = below_ij >= sum_t extant_tj.
+ *   term_ij   = (log site_ij + Lambda_ij) + logw_i where incl_ij, else -inf.
+ *   outLogPattern[j] = log sum_i exp(term_ij) by a running-maximum log-sum-exp over the rows in list order: (m, s) starts at (-inf, 0);
+ *               a term above m makes s = s exp(m - term) + 1 and m = term, any other adds exp(term - m) to s; the result is m + log s,
+ *               -inf where no row is included.  The reference forms the sum in linear space, which underflows on large trees; where it
+ *               does not, exp(outLogPattern[j]) is its cumLike[j].  A term that is NaN or +inf makes the pattern's value NaN.
+ *   outNodeLogTerms [nodeCount][patternCount] or NULL: term_ij.
+ *   outSum (may be NULL) = sum_j patternWeight_j outLogPattern[j]: per 256 patterns by a fixed tree, then those sums in ascending order.
+ *   flags: none is defined; it must be 0.
+ * Nothing of the instance changes (buffers that the 4-state walk left unstored are materialised, as for beagleGetPartials; tips with a
+ * folded emission table get their partials); a held-back pre-order list stays held unless it writes a listed buffer.  No atomics on
+ * values: two calls return the same bits.  The rows are walked whole; a call whose scratch (Lambda and the extant count of the rows
+ * pending at once, and with outNodeLogTerms a stage of every row) would pass 256 MiB is run in chunks of patterns
+ * (BEAGLE_MI355_NODEPATTERN_CHUNK=<patterns> in the environment, read at every call: tests).  On the sharded handle every
+ * shard fills its own pattern columns — the bits per pattern are those of one instance — and outSum adds the shards' sums in shard order.
+ * 2..255 states, any category count.  BEAGLE_ERROR_OUT_OF_RANGE for a bad index, a row that is not post-order, deathState outside
+ * [0, stateCount), flags != 0, nodeCount < 1, nodes, nodeLogWeights or outLogPattern NULL, a buffer nothing was ever written to;
+ * BEAGLE_ERROR_NO_IMPLEMENTATION on an instance with pattern partitions or BASTA buffers or more than 255 states;
+ * BEAGLE_ERROR_FLOATING_POINT when the sum is not finite (the outputs are still written); BEAGLE_ERROR_OUT_OF_MEMORY when the scratch
+ * cannot be had.  An extension: no BEAST class calls it today (ALSBeagleTreeLikelihood.calculateLogLikelihood throws). */
+int beagleMi355NodePatternLikelihoods(int instance, const int* nodes, const double* nodeLogWeights, int nodeCount, int deathState,
+                                      int categoryWeightsIndex, int stateFrequenciesIndex, int flags, double* outLogPattern,
+                                      double* outNodeLogTerms, double* outSum);
+/* out4 = {beagleMi355NodePatternLikelihoods calls since creation, rows they walked, patterns they found included in no row, buffers
+ * materialised for them} (the sum over the shards of a sharded handle). */
+int beagleMi355NodePatternStats(int instance, long* out4);
 /* Markov jumps: ONE call that draws the ancestral states as beagleMi355SampleAncestralStates does and, for every register k, row
  * r >= 1 and pattern p, forms the expected number of registered substitutions (a count register) or the expected reward (a reward
  * register) on row r's branch, conditioned on the drawn parent and child states — what MarkovJumpsBeagleTreeLikelihood.hookCalculation
