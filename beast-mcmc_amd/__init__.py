@@ -15,6 +15,7 @@ Layout (only what the hot path needs — SURVEY.md §8):
   substgradient.py    substitution-parameter gradients through differential matrices formed on the device (BranchSubstitutionParameterDelegate's caller side)
   eigensystems.py     eigen systems of a set of reversible models decomposed on the device in one call (SubstitutionModelDelegate's caller side)
   generators.py       branch matrices straight from generators, no eigen system, in one call (SubstitutionModelDelegate's caller side for models without one)
+  epochs.py           branch matrices of epoch models: the product of a branch's per-epoch matrices in one call (EpochBranchModel and SubstitutionModelDelegate's caller side)
   stochasticdollo.py  the stochastic Dollo (ALS) likelihood: node-pattern likelihoods on the device in one call (ALSTreeLikelihood's caller side)
   tipmodels.py        tip error models as emission tables folded into the tip branch matrices (SequenceErrorModel's caller side)
   basta.py            the BASTA structured-coalescent likelihood on the device (BeagleBastaLikelihoodDelegate's caller side)
@@ -24,5 +25,5 @@ Layout (only what the hot path needs — SURVEY.md §8):
 
 The directory name contains a hyphen, so import it through the root-level shim: ``import beast_mcmc_amd``.
 """
-from . import ancestral, basta, beagle, completehistory, eigensystems, generators, markovjumps, mds, multipartition, nodeheight, robustcounting, simulate, stochasticdollo, substgradient, tipmodels, treelikelihood     # noqa: F401
+from . import ancestral, basta, beagle, completehistory, eigensystems, epochs, generators, markovjumps, mds, multipartition, nodeheight, robustcounting, simulate, stochasticdollo, substgradient, tipmodels, treelikelihood     # noqa: F401
 from .inputs import patterns, siterates, substmodel, synth, trees   # noqa: F401

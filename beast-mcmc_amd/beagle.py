@@ -124,7 +124,7 @@ ABI_SYMBOLS = ["beagleGetVersion", "beagleGetCitation", "beagleGetResourceList",
               ["beagle" + k for k in _PROTOS] + \
               ["beagleMi355SetStream", "beagleMi355CalculateRootLogLikelihoodsDevice", "beagleMi355Synchronize",
                "beagleMi355KernelTimer", "beagleMi355DeviceBytes", "beagleMi355WalkStats", "beagleMi355GradientStats", "beagleMi355GetPartialsBatch", "beagleMi355SampleAncestralStates", "beagleMi355SampleMarkovJumps", "beagleMi355SampleMarkovJumpsUniformized",
-               "beagleMi355SimulateSequences", "beagleMi355SimulateCompleteHistories", "beagleMi355RobustCounts", "beagleMi355SimulateUnconditionedCounts", "beagleMi355NodeHeightDerivatives", "beagleMi355UpdateDifferentialMatrices", "beagleMi355SetReversibleModels", "beagleMi355GetEigenDecomposition", "beagleMi355EigenStats", "beagleMi355UpdateTransitionMatricesFromGenerators", "beagleMi355GeneratorStats", "beagleMi355NodePatternLikelihoods", "beagleMi355NodePatternStats", "beagleMi355SetTipEmission", "beagleMi355TipEmissionStats",
+               "beagleMi355SimulateSequences", "beagleMi355SimulateCompleteHistories", "beagleMi355RobustCounts", "beagleMi355SimulateUnconditionedCounts", "beagleMi355NodeHeightDerivatives", "beagleMi355UpdateDifferentialMatrices", "beagleMi355SetReversibleModels", "beagleMi355GetEigenDecomposition", "beagleMi355EigenStats", "beagleMi355UpdateTransitionMatricesFromGenerators", "beagleMi355GeneratorStats", "beagleMi355UpdateTransitionMatricesWithEpochs", "beagleMi355EpochStats", "beagleMi355NodePatternLikelihoods", "beagleMi355NodePatternStats", "beagleMi355SetTipEmission", "beagleMi355TipEmissionStats",
                "beagleMi355GetPartialsPinned", "beagleMi355GetSiteLogLikelihoodsPinned",
                "beagleMi355KernelTimerCalls", "beagleMi355WalkHealth", "beagleMi355RepeatStats", "beagleMi355TableOperandStats", "beagleMi355WalkLaunchInfo", "beagleMi355RootFusedCount", "beagleMi355SitePrefetchCount", "beagleMi355KernelTimerRestart", "beagleMi355GetDimensions", "beagleMi355GetCommUniqueId", "beagleMi355CommInit", "beagleMi355CommInfo", "beagleMi355CalculateRootLogLikelihoodsAllReduce"] + \
               ["beagleBasta" + k for k in ("AllocateCoalescentBuffers", "UpdatePartials", "AccumulatePartials", "GetBuffer", "GetBufferLength", "Stats", "SampleStates", "StatesStats",
@@ -742,6 +742,28 @@ class Beagle:
         out = (C.c_long * 4)()
         self._check("generatorStats", self._ext("beagleMi355GeneratorStats", [C.c_int, C.POINTER(C.c_long)])(self.instance, out))
         return {"calls": int(out[0]), "matrices": int(out[1]), "max_squarings": int(out[2]), "refused": int(out[3])}
+
+    def updateTransitionMatricesWithEpochs(self, segmentOffsets, segmentEigenIndices, segmentLengths, categoryRateIndices,
+                                           probabilityIndices, count=None, flags=0):
+        """The branch matrices of an epoch model in one call: slot probabilityIndices[e] receives the product of the transition
+        matrices of segments segmentOffsets[e] .. segmentOffsets[e + 1] - 1, root end first (include/beagle_mi355.h
+        beagleMi355UpdateTransitionMatricesWithEpochs).  Per segment its eigen slot and length, per entry its rate set (None: 0
+        for all) and slot.  Nothing comes back and the host does not wait."""
+        o, e, t = _i(segmentOffsets), _i(segmentEigenIndices), _d(segmentLengths)
+        r, m = _i(categoryRateIndices), _i(probabilityIndices)
+        n = m.size if count is None else int(count)
+        if o.size < n + 1 or m.size < n or (r is not None and r.size < n):
+            raise ValueError("count + 1 offsets, one slot (and one rate set) per entry")
+        if n > 0 and (e.size < o[n] or t.size < o[n]):
+            raise ValueError("one eigen index and one length per segment")
+        f = self._ext("beagleMi355UpdateTransitionMatricesWithEpochs", [C.c_int, _IP, _IP, _DP, _IP, _IP, C.c_int, C.c_int])
+        self._check("updateTransitionMatricesWithEpochs", f(self.instance, _ip(o), _ip(e), _dp(t), _ip(r), _ip(m), n, int(flags)))
+
+    def epochStats(self):
+        """What updateTransitionMatricesWithEpochs has done (include/beagle_mi355.h beagleMi355EpochStats)."""
+        out = (C.c_long * 4)()
+        self._check("epochStats", self._ext("beagleMi355EpochStats", [C.c_int, C.POINTER(C.c_long)])(self.instance, out))
+        return {"calls": int(out[0]), "matrices": int(out[1]), "segments": int(out[2]), "longest": int(out[3])}
 
     def nodePatternLikelihoods(self, nodes, nodeLogWeights, deathState, categoryWeightsIndex=0, stateFrequenciesIndex=0,
                                node_terms=False, flags=0):

@@ -347,7 +347,7 @@ int beagleSetEigenDecomposition(int instance, int eigenIndex, const double* U, c
     const size_t S = in->S, nLambda = in->eigenComplex ? 2 * S : S, stride = 2 * S * S + nLambda;
     if (in->eigenComplex) {
         // imaginary parts come as adjacent conjugate pairs (b, -b) — ComplexSubstitutionModel.java:121-173 walks them that way, and
-        // the kernel (kernels.hip iexpEntry) reads the row after a pair's first row: a lone or unmatched entry is refused here
+        // the kernel (transition_body.h iexpEntry) reads the row after a pair's first row: a lone or unmatched entry is refused here
         for (size_t k = 0; k < S; k++) {
             const double im = lambda[S + k];
             if (im == 0.0) continue;

@@ -15,6 +15,7 @@
 //   engine_differential.cpp  substitution-parameter differential matrices of every branch in one call
 //   engine_eigen.cpp     eigen systems of reversible models decomposed on the device in one call, an eigen slot back to the host
 //   engine_generator.cpp transition matrices straight from generators in one call, no eigen system
+//   engine_epoch.cpp     branch matrices of epoch models (products of per-segment transition matrices) in one call
 //   engine_nodepattern.cpp  the stochastic Dollo node-pattern likelihood over a post-order node list in one call
 //   engine_stats.cpp     stream, synchronisation, kernel timer, counters
 // each of them argument checks, buffer bookkeeping and one call into the files above.
@@ -409,6 +410,7 @@ struct Instance {
     DevBuf generatorDev;                                 // matrices from generators (engine_generator.cpp): the power tables of a launch, [generators][21][S][S] doubles
     DevBuf generatorStatsDev;                            // ... and two words the kernels keep: the largest s, the matrices refused
     long statGeneratorCalls = 0, statGeneratorMatrices = 0;                    // (beagleMi355GeneratorStats)
+    long statEpochCalls = 0, statEpochMatrices = 0, statEpochSegments = 0, statEpochLongest = 0;      // (beagleMi355EpochStats)
     DevBuf nodePatternDev;                               // stochastic Dollo node-pattern likelihood (engine_nodepattern.cpp): nodePatternLayout
     long statNodePatternCalls = 0, statNodePatternRows = 0, statNodePatternEmpty = 0, statNodePatternMaterialised = 0;      // (beagleMi355NodePatternStats)
 };

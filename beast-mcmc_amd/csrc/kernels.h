@@ -328,7 +328,7 @@ void launchPublish(hipStream_t stream, const double* src, int n, double* dst, un
 // P(t) = U diag(exp(lambda * t * r_c)) U^-1, negatives clamped to 0, for `count` branches.
 // dIdx/dLen/dEig/dRate: device arrays of length `count`: destination matrix index, edge length,
 // eigen-system index and category-rate-set index per branch.
-// complexEigen: eigen systems are [U | U^-1 | Re lambda (S) | Im lambda (S)] in real block form (kernels.hip iexpEntry)
+// complexEigen: eigen systems are [U | U^-1 | Re lambda (S) | Im lambda (S)] in real block form (transition_body.h iexpEntry)
 void launchTransitionMatrices(hipStream_t stream, double* matrices, const double* eigen, const double* rates,
                               const int* dIdx, const double* dLen, const int* dEig, const int* dRate,
                               int count, int S, int C, bool complexEigen = false);
@@ -381,6 +381,13 @@ bool launchGeneratorPowers(hipStream_t stream, double* tables, const double* Q, 
 // (entry, category) up to 8 states, one workgroup from 9 to 64 (squarings on the matrix cores from 16).
 bool launchGeneratorMatrices(hipStream_t stream, double* matrices, const double* rates, const double* tables, const double* mu,
                              const int* dIdx, const double* dLen, const int* dGen, const int* dRate, unsigned* stats, int count, int S, int C);
+
+// ---- branch matrices of epoch models (kernels_epoch.hip; beagleMi355UpdateTransitionMatricesWithEpochs) ----
+// slot dSlot[u], category c = the left fold of the transition matrices of segments dOff[u] .. dOff[u + 1] - 1 (eigen system dSegEig[j],
+// length dSegLen[j], rate set dRate[u]) for `count` entries; all device arrays.  One thread per (entry, category) up to 8 states, one
+// workgroup from 9 to 64 (products on the matrix cores from 16).  false: no kernel for this S, or the kernel's LDS was not granted.
+bool launchEpochMatrices(hipStream_t stream, double* matrices, const double* eigen, const double* rates, const int* dSlot, const int* dRate,
+                         const int* dOff, const int* dSegEig, const double* dSegLen, int count, int S, int C, bool complexEigen);
 
 // One dependency level of pruning operations: `nOps` independent ops, descriptors on the device.
 // maxRange = max over ops of (pEnd - pStart).

@@ -19,6 +19,7 @@
 //   k_accumulate                AbstractLikelihoodCore.java:442-458 as a persistent cumulative buffer
 #include "kernels.h"
 #include "root_site4.h"
+#include "transition_body.h"
 #include <stdlib.h>
 #include <algorithm>
 #include <map>
@@ -61,22 +62,7 @@ void launchPublish(hipStream_t stream, const double* src, int n, double* dst, un
 // ------------------------------------------------------------------------------------------------
 // transition matrices
 // ------------------------------------------------------------------------------------------------
-// complexEigen (an EIGEN_COMPLEX instance: BeagleTreeLikelihood.java:353-355, the asymmetric discrete-trait models): the
-// eigenvalue array holds S real parts, then S imaginary parts, and U / U^-1 are the REAL block form — a conjugate pair
-// a +/- b i sits in rows i, i+1 (imaginary parts b, -b) and contributes exp(a t) [cos b t, sin b t; -sin b t, cos b t] on those
-// two rows of U^-1 (ComplexSubstitutionModel.java:121-173).  Row k of a pair is its FIRST row iff an even number of rows
-// with a nonzero imaginary part precede it without a gap (the reference walks the rows in order and skips the second).
-__device__ __forceinline__ double iexpEntry(const double* __restrict__ Ui, const double* __restrict__ lam, int S, int k, int j, double dist, int complexEigen) {
-    const double im = complexEigen ? lam[S + k] : 0.0;
-    if (im == 0.0) return Ui[k * S + j] * exp(dist * lam[k]);
-    int run = 0;
-    for (int q = k - 1; q >= 0 && lam[S + q] != 0.0; q--) run++;
-    const int first = (run & 1) ? k - 1 : k;
-    const double b = lam[S + first];
-    const double expat = exp(dist * lam[first]), c = expat * cos(dist * b), sn = expat * sin(dist * b);
-    return first == k ? c * Ui[k * S + j] + sn * Ui[(k + 1) * S + j] : c * Ui[k * S + j] - sn * Ui[(k - 1) * S + j];
-}
-
+// (the arithmetic of one matrix, and what complexEigen means: transition_body.h — the epoch kernels form their segments with it too)
 __global__ __launch_bounds__(256) void k_transition(double* __restrict__ matrices, const double* __restrict__ eigen,
                                                     const double* __restrict__ rates, const int* __restrict__ dIdx,
                                                     const double* __restrict__ dLen, const int* __restrict__ dEig,
@@ -88,44 +74,8 @@ __global__ __launch_bounds__(256) void k_transition(double* __restrict__ matrice
     const double* Ui = U + (size_t)S * S;
     const double* lam = Ui + (size_t)S * S;
     const double dist = dLen[u] * rates[(size_t)dRate[u] * C + c];
-    // (one exponential per eigenvalue, not per entry: S instead of S x S of them — 3 721 at 61 states — the same values)
-    double* ek = sh + (size_t)S * S;
-    if (!complexEigen) {
-        for (int k = threadIdx.x; k < S; k += blockDim.x) ek[k] = exp(dist * lam[k]);
-        __syncthreads();
-    }
-    for (int e = threadIdx.x; e < S * S; e += blockDim.x) {
-        const int k = e / S;
-        sh[e] = complexEigen ? iexpEntry(Ui, lam, S, k, e - k * S, dist, 1) : Ui[e] * ek[k];
-    }
-    __syncthreads();
     double* M = matrices + ((size_t)dIdx[u] * C + c) * S * S;
-    // a thread forms a 4 x 4 block of entries: eight loads per sixteen multiply-adds instead of two per one (round 6: the 1 592 matrices
-    // of a 61-state evaluation 127 -> ~40 us); every entry still sums over k in ascending order — the same bits as entry by entry
-    const int nb = (S + 3) >> 2;
-    for (int b = threadIdx.x; b < nb * nb; b += blockDim.x) {
-        const int bi = b / nb, bj = b - bi * nb, i0 = 4 * bi, j0 = 4 * bj;
-        const double* u0 = U + (size_t)(i0 < S ? i0 : S - 1) * S;
-        const double* u1 = U + (size_t)(i0 + 1 < S ? i0 + 1 : S - 1) * S;
-        const double* u2 = U + (size_t)(i0 + 2 < S ? i0 + 2 : S - 1) * S;
-        const double* u3 = U + (size_t)(i0 + 3 < S ? i0 + 3 : S - 1) * S;
-        const int c0 = j0 < S ? j0 : S - 1, c1 = j0 + 1 < S ? j0 + 1 : S - 1, c2 = j0 + 2 < S ? j0 + 2 : S - 1, c3 = j0 + 3 < S ? j0 + 3 : S - 1;
-        double a[4][4] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}};
-        for (int k = 0; k < S; k++) {
-            const double* row = sh + (size_t)k * S;
-            const double v[4] = {row[c0], row[c1], row[c2], row[c3]};
-            const double w[4] = {u0[k], u1[k], u2[k], u3[k]};
-#pragma unroll
-            for (int r = 0; r < 4; r++)
-#pragma unroll
-                for (int q = 0; q < 4; q++) a[r][q] += w[r] * v[q];
-        }
-#pragma unroll
-        for (int r = 0; r < 4; r++)
-#pragma unroll
-            for (int q = 0; q < 4; q++)
-                if (i0 + r < S && j0 + q < S) M[(size_t)(i0 + r) * S + j0 + q] = a[r][q] > 0.0 ? a[r][q] : 0.0;
-    }
+    transitionMatrixBody(sh, U, Ui, lam, S, dist, complexEigen, [M, S](int i, int j, double v) { M[(size_t)i * S + j] = v; });
 }
 
 // More than 90 states (S x S doubles exceed what a workgroup may ask of the LDS): per eigenvalue only its exponential — for
@@ -178,19 +128,11 @@ __global__ __launch_bounds__(256) void k_transition4(double* __restrict__ matric
     if (t >= count * C) return;
     const int u = t / C, c = t - u * C;
     const double* U = eigen + (size_t)(complexEigen ? 40 : 36) * dEig[u];
-    const double* Ui = U + 16;
-    const double* lam = U + 32;
     const double dist = dLen[u] * rates[(size_t)dRate[u] * C + c];
-    double ie[16];
-    if (complexEigen) { for (int e = 0; e < 16; e++) ie[e] = iexpEntry(Ui, lam, 4, e >> 2, e & 3, dist, 1); }
-    else for (int k = 0; k < 4; k++) { const double ex = exp(dist * lam[k]); for (int j = 0; j < 4; j++) ie[k * 4 + j] = Ui[k * 4 + j] * ex; }
+    double m[16];
+    transitionMatrixThread<4>(m, U, dist, complexEigen);
     double* M = matrices + ((size_t)dIdx[u] * C + c) * 16;
-    for (int i = 0; i < 4; i++)
-        for (int j = 0; j < 4; j++) {
-            double s = 0.0;
-            for (int k = 0; k < 4; k++) s += U[i * 4 + k] * ie[k * 4 + j];
-            M[i * 4 + j] = s > 0.0 ? s : 0.0;
-        }
+    for (int e = 0; e < 16; e++) M[e] = m[e];
 }
 
 
@@ -213,19 +155,11 @@ __global__ __launch_bounds__(256) void k_transition4Fused(double* __restrict__ m
     __syncthreads();
     if (!live) return;
     const double* U = sEig;
-    const double* Ui = U + 16;
-    const double* lam = U + 32;
     const double dist = myLen * (C <= 16 ? sRate[c] : ratesSrc[c]);
-    double ie[16];
-    if (complexEigen) { for (int e = 0; e < 16; e++) ie[e] = iexpEntry(Ui, lam, 4, e >> 2, e & 3, dist, 1); }
-    else for (int k = 0; k < 4; k++) { const double ex = exp(dist * lam[k]); for (int j = 0; j < 4; j++) ie[k * 4 + j] = Ui[k * 4 + j] * ex; }
+    double m[16];
+    transitionMatrixThread<4>(m, U, dist, complexEigen);
     double* M = matrices + ((size_t)myIdx * C + c) * 16;
-    for (int i = 0; i < 4; i++)
-        for (int j = 0; j < 4; j++) {
-            double s = 0.0;
-            for (int k = 0; k < 4; k++) s += U[i * 4 + k] * ie[k * 4 + j];
-            M[i * 4 + j] = s > 0.0 ? s : 0.0;
-        }
+    for (int e = 0; e < 16; e++) M[e] = m[e];
 }
 
 void launchTransitionMatrices4Fused(hipStream_t stream, double* matrices, const double* eigSrc, const double* ratesSrc, const int* idx,

@@ -505,6 +505,44 @@ int beagleMi355UpdateTransitionMatricesFromGenerators(int instance, const double
 /* out4 = {beagleMi355UpdateTransitionMatricesFromGenerators calls since creation, matrices (entry x category) they wrote, the largest s
  * of any of them, matrices refused (NaN) for s > 40} (shard 0 of a sharded handle).  Drains the instance's stream. */
 int beagleMi355GeneratorStats(int instance, long* out4);
+/* Branch matrices of epoch models in ONE call: a branch that crosses epoch boundaries gets the product of its segments' transition
+ * matrices — what SubstitutionModelDelegate builds from one updateTransitionMatrices per eigen system into a pool of extra matrix
+ * buffers and rounds of convolveTransitionMatrices (treelikelihood/SubstitutionModelDelegate.java:162-405).
+ *   segmentOffsets [count + 1]: entry e owns segments segmentOffsets[e] .. segmentOffsets[e + 1] - 1; segmentOffsets[0] == 0, strictly
+ *          increasing (every entry has a segment).  Segments come in the order of BranchModel.Mapping.getOrder(): root end first.
+ *   segmentEigenIndices, segmentLengths [segmentOffsets[count]]: the eigen slot and the length (finite, >= 0) of each segment.
+ *   categoryRateIndices [count] (NULL: rate set 0): the rate set of entry e, as in beagleUpdateTransitionMatricesWithMultipleModels.
+ *   probabilityIndices [count]: the slot of entry e, no slot twice in one call.   flags: must be 0.
+ * For entry e with segments j = 0 .. n - 1 and category c, M_j is what beagleUpdateTransitionMatrices leaves in a slot for (eigen slot
+ * k_j, length l_j, the entry's rate set, category c): the distance l_j * rate_c is one product, the sums over the eigen index run upwards,
+ * negative entries become 0, on real and on complex (conjugate-pair) eigen systems alike — the same code, so the same bits.  The slot
+ * receives the left fold ((M_0 M_1) M_2) ... M_(n-1), the order the reference's deque produces (first x second -> result, pushed to the
+ * front); an entry with n = 1 receives exactly M_0.
+ * A product is sum_k a_ik b_kj, not clamped (as beagleConvolveTransitionMatrices).  Its order is fixed per state count:
+ *   up to 15 states: k upwards from 0.0, one fused multiply-add per k;
+ *   16 .. 64 states: on the fp64 matrix cores (v_mfma_f64_4x4x4), k four at a time in ascending order, each instruction adding its four
+ *          products to the running sum, which starts at 0.0 (rows and columns are padded with zeros to a multiple of 4: the padded steps
+ *          add 0 x 0).
+ * There are no atomics on values, so a slot's bits depend on its own segments, rate set and category alone: not on its place in the
+ * list, on the split into launches, on the other entries or on the shard.
+ * The eigen systems, category rates and matrix slots are read and written where they are on the device (an eigen slot may have been
+ * written by beagleMi355SetReversibleModels just before).  The call is queued behind everything queued on the instance; nothing is read
+ * back and the host does not wait.  Writing a slot does for it what beagleUpdateTransitionMatrices does; a held-back pre-order list runs
+ * first only if it reads one of the written slots.  Input goes through the staging ring: a list over its budget is split into several
+ * launches (BEAGLE_MI355_EPOCH_CHUNK=<entries> in the environment, read at every call, forces a smaller split), so no list is refused for
+ * its size.  It works on EIGEN_REAL and EIGEN_COMPLEX instances, on partitioned ones and on instances with BASTA buffers, and writes
+ * matrix slots only.  The sharded handle gives the call to every shard.
+ * BEAGLE_ERROR_OUT_OF_RANGE for a NULL segmentOffsets, segmentEigenIndices, segmentLengths or probabilityIndices, count < 0, offsets that
+ * do not start at 0 or do not increase strictly (an entry without a segment), an index out of range, a slot named twice, a length not
+ * finite or < 0, flags != 0;  BEAGLE_ERROR_NO_IMPLEMENTATION with more than 64 states.  Everything is checked before anything is queued: a
+ * refused call leaves every slot as it was.  count == 0: success, nothing is read or launched.  Derivative matrices are not offered.
+ * An extension: no BEAST class calls it today. */
+int beagleMi355UpdateTransitionMatricesWithEpochs(int instance, const int* segmentOffsets, const int* segmentEigenIndices,
+                                                  const double* segmentLengths, const int* categoryRateIndices,
+                                                  const int* probabilityIndices, int count, int flags);
+/* out4 = {beagleMi355UpdateTransitionMatricesWithEpochs calls since creation, matrices (entry x category) they wrote, segments they
+ * processed, the longest entry (segments) of the last call} (shard 0 of a sharded handle).  Host counters: nothing is drained. */
+int beagleMi355EpochStats(int instance, long* out4);
 /* The stochastic Dollo (ALS) node-pattern likelihood: ONE call behind an ordinary pruning pass — what
  * AbstractObservationProcess.nodePatternLikelihood computes from a getPartials per node (tips included), a getLogScaleFactors per
  * internal node and a host loop over nodes x patterns x states (oldevomodel/MSSD/AbstractObservationProcess.java:174-210,
