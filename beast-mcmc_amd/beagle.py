@@ -124,7 +124,7 @@ ABI_SYMBOLS = ["beagleGetVersion", "beagleGetCitation", "beagleGetResourceList",
               ["beagle" + k for k in _PROTOS] + \
               ["beagleMi355SetStream", "beagleMi355CalculateRootLogLikelihoodsDevice", "beagleMi355Synchronize",
                "beagleMi355KernelTimer", "beagleMi355DeviceBytes", "beagleMi355WalkStats", "beagleMi355GradientStats", "beagleMi355GetPartialsBatch", "beagleMi355SampleAncestralStates", "beagleMi355SampleMarkovJumps", "beagleMi355SampleMarkovJumpsUniformized",
-               "beagleMi355SimulateSequences", "beagleMi355SimulateCompleteHistories", "beagleMi355RobustCounts", "beagleMi355SimulateUnconditionedCounts", "beagleMi355NodeHeightDerivatives", "beagleMi355UpdateDifferentialMatrices", "beagleMi355SetReversibleModels", "beagleMi355GetEigenDecomposition", "beagleMi355EigenStats", "beagleMi355UpdateTransitionMatricesFromGenerators", "beagleMi355GeneratorStats", "beagleMi355UpdateTransitionMatricesWithEpochs", "beagleMi355EpochStats", "beagleMi355NodePatternLikelihoods", "beagleMi355NodePatternStats", "beagleMi355SetTipEmission", "beagleMi355TipEmissionStats",
+               "beagleMi355SimulateSequences", "beagleMi355SimulateCompleteHistories", "beagleMi355RobustCounts", "beagleMi355SimulateUnconditionedCounts", "beagleMi355NodeHeightDerivatives", "beagleMi355UpdateDifferentialMatrices", "beagleMi355SetReversibleModels", "beagleMi355GetEigenDecomposition", "beagleMi355EigenStats", "beagleMi355UpdateTransitionMatricesFromGenerators", "beagleMi355GeneratorStats", "beagleMi355UpdateTransitionMatricesWithEpochs", "beagleMi355EpochStats", "beagleMi355NodePatternLikelihoods", "beagleMi355NodePatternStats", "beagleMi355NodePosteriors", "beagleMi355NodePosteriorStats", "beagleMi355SetTipEmission", "beagleMi355TipEmissionStats",
                "beagleMi355GetPartialsPinned", "beagleMi355GetSiteLogLikelihoodsPinned",
                "beagleMi355KernelTimerCalls", "beagleMi355WalkHealth", "beagleMi355RepeatStats", "beagleMi355TableOperandStats", "beagleMi355WalkLaunchInfo", "beagleMi355RootFusedCount", "beagleMi355SitePrefetchCount", "beagleMi355KernelTimerRestart", "beagleMi355GetDimensions", "beagleMi355GetCommUniqueId", "beagleMi355CommInit", "beagleMi355CommInfo", "beagleMi355CalculateRootLogLikelihoodsAllReduce"] + \
               ["beagleBasta" + k for k in ("AllocateCoalescentBuffers", "UpdatePartials", "AccumulatePartials", "GetBuffer", "GetBufferLength", "Stats", "SampleStates", "StatesStats",
@@ -792,6 +792,46 @@ class Beagle:
         out = (C.c_long * 4)()
         self._check("nodePatternStats", self._ext("beagleMi355NodePatternStats", [C.c_int, C.POINTER(C.c_long)])(self.instance, out))
         return {"calls": int(out[0]), "rows": int(out[1]), "empty_patterns": int(out[2]), "materialised": int(out[3])}
+
+    def nodePosteriors(self, nodes, categoryWeightsIndex=0, full=True, map=False, totals=False, categories=False, flags=0, out=None):
+        """Marginal state posteriors of every listed node and pattern in one call (include/beagle_mi355.h
+        beagleMi355NodePosteriors).  ``nodes``: [nodeCount][2] rows {post-order buffer, pre-order buffer}.  -> (dict of what was
+        asked for, return code): "posteriors" [nodeCount, P, S] (full), "map_states" uint8 [nodeCount, P] and "map_probabilities"
+        [nodeCount, P] (map), "totals" [nodeCount, S] (totals), "categories" [P, C] of the first row (categories).  The code is 0,
+        or -8 (FLOATING_POINT) when some pattern's likelihood was 0 or not finite — the arrays are written either way, NaN there;
+        every other code raises BeagleException.  ``out``: a dict this method returned for the same shape — its arrays are
+        written again instead of new ones (a caller that asks every step)."""
+        rows = _i(nodes).reshape(-1, 2)
+        n, P, S = rows.shape[0], self.patternCount, self.stateCount
+        shapes = {}
+        if full:
+            shapes["posteriors"] = ((n, P, S), np.float64)
+        if map:
+            shapes["map_states"] = ((n, P), np.uint8)
+            shapes["map_probabilities"] = ((n, P), np.float64)
+        if totals:
+            shapes["totals"] = ((n, S), np.float64)
+        if categories:
+            shapes["categories"] = ((P, self.categoryCount), np.float64)
+        old, out = out or {}, {}
+        for key, (shape, dtype) in shapes.items():
+            a = old.get(key)
+            reuse = a is not None and a.shape == shape and a.dtype == dtype and a.flags.c_contiguous and a.flags.writeable
+            out[key] = a if reuse else np.empty(shape, dtype=dtype)
+        ms = out.get("map_states")
+        f = self._ext("beagleMi355NodePosteriors", [C.c_int, _IP, C.c_int, C.c_int, C.c_int, _DP, C.POINTER(C.c_ubyte), _DP, _DP, _DP])
+        rc = f(self.instance, _ip(rows), n, categoryWeightsIndex, int(flags), _dp(out.get("posteriors")),
+               ms.ctypes.data_as(C.POINTER(C.c_ubyte)) if ms is not None else None, _dp(out.get("map_probabilities")),
+               _dp(out.get("totals")), _dp(out.get("categories")))
+        if rc != 0 and rc != -8:
+            raise BeagleException("nodePosteriors", rc)
+        return out, rc
+
+    def nodePosteriorStats(self):
+        """What nodePosteriors has done (include/beagle_mi355.h beagleMi355NodePosteriorStats)."""
+        out = (C.c_long * 4)()
+        self._check("nodePosteriorStats", self._ext("beagleMi355NodePosteriorStats", [C.c_int, C.POINTER(C.c_long)])(self.instance, out))
+        return {"calls": int(out[0]), "rows": int(out[1]), "materialised": int(out[2]), "launches": int(out[3])}
 
     def sampleMarkovJumps(self, nodes, branchTimes, branchRates, eigenIndex, categoryRatesIndex, categoryWeightsIndex,
                           stateFrequenciesIndex, registers, registerFlags, seed, map=False, states=False, jumps=False,

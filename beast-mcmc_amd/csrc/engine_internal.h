@@ -17,6 +17,7 @@
 //   engine_generator.cpp transition matrices straight from generators in one call, no eigen system
 //   engine_epoch.cpp     branch matrices of epoch models (products of per-segment transition matrices) in one call
 //   engine_nodepattern.cpp  the stochastic Dollo node-pattern likelihood over a post-order node list in one call
+//   engine_nodeposterior.cpp  marginal node state posteriors from resident pre- and post-order partials in one call
 //   engine_stats.cpp     stream, synchronisation, kernel timer, counters
 // each of them argument checks, buffer bookkeeping and one call into the files above.
 // All arithmetic is in the .hip files; these files validate indices, resolve buffer indices to device pointers and enqueue
@@ -413,6 +414,8 @@ struct Instance {
     long statEpochCalls = 0, statEpochMatrices = 0, statEpochSegments = 0, statEpochLongest = 0;      // (beagleMi355EpochStats)
     DevBuf nodePatternDev;                               // stochastic Dollo node-pattern likelihood (engine_nodepattern.cpp): nodePatternLayout
     long statNodePatternCalls = 0, statNodePatternRows = 0, statNodePatternEmpty = 0, statNodePatternMaterialised = 0;      // (beagleMi355NodePatternStats)
+    DevBuf nodePosteriorDev;                             // marginal node state posteriors (engine_nodeposterior.cpp): nodePosteriorLayout
+    long statNodePosteriorCalls = 0, statNodePosteriorRows = 0, statNodePosteriorMaterialised = 0, statNodePosteriorLaunches = 0;   // (beagleMi355NodePosteriorStats)
 };
 
 extern std::mutex g_mutex;

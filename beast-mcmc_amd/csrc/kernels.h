@@ -665,6 +665,30 @@ int  nodePatternBlocks(int P);               // workgroups over P patterns (entr
 void launchNodePattern(hipStream_t stream, const NodePatternRow* dRows, int nRows, const double* catWeights, const double* freqs,
                        const double* patternWeights, int P, int S, int C, bool tiled, int deathState, int p0, int count, int stride,
                        double* lambda, int* below, double* terms, double* logPattern, double* blockSums);
+// ---- marginal node state posteriors (kernels_nodeposterior.hip; beagleMi355NodePosteriors) --------------------------------
+// One row of the node list, resolved on the host: the node's post-order partials (plain [C][P][S] or T32) OR its compact tip states
+// (uint8 [P]; statesPost != 0), its pre-order partials, and the row of the launch's outputs it fills.
+struct NodePosteriorRow {
+    const void*   post;
+    const double* pre;
+    int           statesPost;
+    int           slot;
+};
+static_assert(sizeof(NodePosteriorRow) == 24, "NodePosteriorRow layout");
+constexpr int NODE_POSTERIOR_MAX_ROWS = 65535;       // rows of one launch (the grid's second dimension)
+// Per row, pattern p and state s: m[s] = sum_c (pre_c[p][s] * post_c[p][s]) * w_c (c ascending from 0.0), Z = sum_s m[s] (s ascending
+// from 0.0), posterior = m[s] / Z — NaN, and *fpError = 1, where Z is 0 or not finite.  Outputs of the launch's rows, each nullptr
+// when not wanted: posteriors [nRows][P][S], mapStates (uint8) and mapProbabilities [nRows][P] (the first s with the strictly largest
+// posterior), blockSums [edgeBlocks(P)][nRows][S] = sum of patternWeights[p] * posterior over the block's 64 patterns by a fixed
+// tree (v[i] += v[i + off], off = 32, 16 .. 1); finish those with launchBlockTotals(blockSums, edgeBlocks(P), 1, nRows * S, 0, out).
+// false: the state count needs more LDS than a workgroup can have.
+bool launchNodePosteriors(hipStream_t stream, const NodePosteriorRow* dRows, int nRows, const double* catWeights,
+                          const double* patternWeights, int P, int S, int C, bool tiled, double* posteriors, uint8_t* mapStates,
+                          double* mapProbabilities, double* blockSums, unsigned* fpError);
+// categories [P][C] of ONE row: n_c = (sum_s pre_c[p][s] * post_c[p][s]) * w_c (s ascending from 0.0), D = sum_c n_c (c ascending
+// from 0.0), n_c / D — NaN, and *fpError = 1, where D is 0 or not finite
+void launchNodePosteriorCategories(hipStream_t stream, const NodePosteriorRow* dRow, const double* catWeights, int P, int S, int C,
+                                   bool tiled, double* categories, unsigned* fpError);
 // ---- sequence simulation (kernels_simulate.hip; beagleMi355SimulateSequences) -------------------------------------------
 // One row of the pre-order node list, resolved on the host: its branch matrix [C][S][S] (nullptr at the root), the scratch row
 // ("slot") its states go to and the slot of its parent (-1 at the root); parentIsPrev: the parent is the row right before it, whose

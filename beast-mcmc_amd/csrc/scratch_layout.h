@@ -1,5 +1,5 @@
 // scratch_layout.h — what is inside the samplers' grow-on-demand device buffers (engine_internal.h Instance::ancestralDev, jumpDev,
-// uniformDev, nodePatternDev, eventDev, simulateDev, robustDev, historyDev): a carver that lays sections out one after another, and per
+// uniformDev, nodePatternDev, nodePosteriorDev, eventDev, simulateDev, robustDev, historyDev): a carver that lays sections out one after another, and per
 // buffer a layout that names its sections from plain integers.  Host only, plain C++17, no HIP: tests/native/scratch_layout_check.cpp
 // (NodePatternLayout: node_pattern_layout_check.cpp) compiles it alone and checks every layout's offsets, order and alignment.  The .cpp files resolve sections to pointers (at / as) and grow the
 // buffer to bytes(); they keep no offset arithmetic.
@@ -76,6 +76,20 @@ struct NodePatternLayout : Carver {
         logPattern = take<double>(P); blockSums = take<double>(blocks); sum = take<double>(1); lambda = take<double>(slots * chunk);
         terms = take<double>(wantTerms ? R * chunk : 0); align(256);
         below = take<int>(slots * chunk);
+    }
+};
+
+// nodePosteriorDev: posteriors stage [rows][P][S] (outPosteriors) | MAP probabilities [rows][P] | block sums [blocks][rows][S] and
+//                   totals [rows][S] (outStateTotals) | category posteriors [P][C] | (256) MAP states [rows][P] | (256) error word
+//                   — rows: those of one launch; a section the call did not ask for is empty
+struct NodePosteriorLayout : Carver {
+    Doubles posteriors, mapProb, blockSums, totals, categories; Section<uint8_t> mapStates; Section<unsigned> error;
+    NodePosteriorLayout(size_t rows, size_t P, size_t S, size_t C, size_t blocks, bool full, bool map, bool wantTotals, bool cats) {
+        posteriors = take<double>(full ? rows * P * S : 0); mapProb = take<double>(map ? rows * P : 0);
+        blockSums = take<double>(wantTotals ? blocks * rows * S : 0); totals = take<double>(wantTotals ? rows * S : 0);
+        categories = take<double>(cats ? P * C : 0); align(256);
+        mapStates = take<uint8_t>(map ? rows * P : 0); align(256);
+        error = take<unsigned>(1);
     }
 };
 

@@ -585,6 +585,49 @@ int beagleMi355NodePatternLikelihoods(int instance, const int* nodes, const doub
 /* out4 = {beagleMi355NodePatternLikelihoods calls since creation, rows they walked, patterns they found included in no row, buffers
  * materialised for them} (the sum over the shards of a sharded handle). */
 int beagleMi355NodePatternStats(int instance, long* out4);
+/* Marginal node state posteriors P(state of node i = s | pattern): ONE call behind a pruning pass and a pre-order pass — what
+ * NodePosteriorTreeLikelihood.calculatePosteriors computes from a getPartials and a getNodeMatrix per node and host loops over nodes x
+ * patterns x states^2 (oldevomodel/treelikelihood/NodePosteriorTreeLikelihood.java:119-235), from the partials where they are.
+ *   nodes [nodeCount][2] = {post(i), pre(i)}.  post(i): a compact tip's states (a state >= stateCount counts as all ones), a tip's
+ *          partials, an internal node's partials, stored or left unstored by the 4-state walk.  pre(i): a partials buffer a pre-order list
+ *          wrote — at the root what setRootPrePartials / setPartials put there.  A node may be listed more than once.
+ *   flags: none is defined; it must be 0.
+ * For row r, pattern p and state s, with w the weights of categoryWeightsIndex:
+ *   m[s]         = sum_c (pre_c[p][s] * post_c[p][s]) * w_c, c upwards from 0.0, every product rounded on its own (no fused multiply-add);
+ *   Z            = sum_s m[s], s upwards from 0.0;
+ *   posterior[s] = m[s] / Z.
+ * Z is the pattern's likelihood up to its scale factors at every node, so the ratio needs no matrix and no scale buffer: scaled partials
+ * are read as they are.  The reference reads one category's matrices and so is meaningful with ONE category, where this is its value; the
+ * category-weighted marginal is this library's extension.
+ * Outputs — any may be NULL, not all:
+ *   outPosteriors [nodeCount][patternCount][stateCount].
+ *   outMapStates [nodeCount][patternCount]: the first s with the strictly largest posterior (drawChoice's rule under useMAP);
+ *   outMapProbabilities [nodeCount][patternCount]: that posterior.
+ *   outStateTotals [nodeCount][stateCount] = sum_p patternWeight_p posterior[p][s]: per 64 patterns by a fixed tree (v[i] += v[i + off]
+ *          for off = 32, 16 .. 1; patterns past the end count 0.0), then those sums in ascending order from 0.0.  No atomics: two calls
+ *          return the same bits.
+ *   outCategoryPosteriors [patternCount][categoryCount], of the FIRST listed row (every node gives the same measure up to rounding):
+ *          n_c = (sum_s pre_c[p][s] * post_c[p][s]) * w_c, s upwards from 0.0;  D = sum_c n_c, c upwards from 0.0;  entry = n_c / D.
+ * A pattern of a row whose Z (for the categories: D) is 0 or not finite makes the call return BEAGLE_ERROR_FLOATING_POINT: every output
+ * is still written, that (row, pattern) is NaN with MAP state 0, and it is left out of no total — the row's totals are NaN too.
+ * Nothing of the instance changes (buffers that the 4-state walk left unstored are materialised, as for beagleGetPartials; tips with a
+ * folded emission table get their partials; a held-back pre-order list runs first).  The rows are cut into launches whose descriptors
+ * fit a quarter of the staging ring and whose output scratch stays within 256 MiB (BEAGLE_MI355_NODE_POSTERIOR_CHUNK=<rows> in the
+ * environment, read at every call: tests); the bits do not depend on the cut, nor on the order of the list.  On the sharded handle
+ * every shard fills its own pattern columns — the bits per pattern are those of one instance — and outStateTotals adds the shards' sums
+ * in shard order.  2..255 states, any category count.
+ * BEAGLE_ERROR_OUT_OF_RANGE for a bad index, a pre(i) that holds tip states or was never written, a post(i) never written, flags != 0,
+ * nodes NULL, nodeCount < 1, every output NULL; BEAGLE_ERROR_NO_IMPLEMENTATION on an instance with pattern partitions or BASTA buffers
+ * or more than 255 states; BEAGLE_ERROR_OUT_OF_MEMORY when the scratch cannot be had.  An extension: no BEAST class calls it today
+ * (NodePosteriorTreeLikelihood is deprecated and runs on the Java cores only). */
+int beagleMi355NodePosteriors(int instance, const int* nodes, int nodeCount, int categoryWeightsIndex, int flags,
+                              double* outPosteriors, unsigned char* outMapStates, double* outMapProbabilities,
+                              double* outStateTotals, double* outCategoryPosteriors);
+/* out4 = {beagleMi355NodePosteriors calls since creation, node rows they covered, operands materialised for them, kernel launches}
+ * (one shard's counters on a sharded handle: every shard runs the same rows).  Operands materialised: the distinct unstored buffers
+ * among a call's listed ones when it arrived (a node listed twice counts once) — whether the held-back pre-order list that ran first
+ * or the call itself then gave them real data. */
+int beagleMi355NodePosteriorStats(int instance, long* out4);
 /* Markov jumps: ONE call that draws the ancestral states as beagleMi355SampleAncestralStates does and, for every register k, row
  * r >= 1 and pattern p, forms the expected number of registered substitutions (a count register) or the expected reward (a reward
  * register) on row r's branch, conditioned on the drawn parent and child states — what MarkovJumpsBeagleTreeLikelihood.hookCalculation
