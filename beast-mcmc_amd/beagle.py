@@ -124,7 +124,7 @@ ABI_SYMBOLS = ["beagleGetVersion", "beagleGetCitation", "beagleGetResourceList",
               ["beagle" + k for k in _PROTOS] + \
               ["beagleMi355SetStream", "beagleMi355CalculateRootLogLikelihoodsDevice", "beagleMi355Synchronize",
                "beagleMi355KernelTimer", "beagleMi355DeviceBytes", "beagleMi355WalkStats", "beagleMi355GradientStats", "beagleMi355GetPartialsBatch", "beagleMi355SampleAncestralStates", "beagleMi355SampleMarkovJumps", "beagleMi355SampleMarkovJumpsUniformized",
-               "beagleMi355SimulateSequences", "beagleMi355SimulateCompleteHistories", "beagleMi355RobustCounts", "beagleMi355SimulateUnconditionedCounts", "beagleMi355NodeHeightDerivatives", "beagleMi355UpdateDifferentialMatrices", "beagleMi355SetReversibleModels", "beagleMi355GetEigenDecomposition", "beagleMi355EigenStats", "beagleMi355UpdateTransitionMatricesFromGenerators", "beagleMi355GeneratorStats", "beagleMi355UpdateTransitionMatricesWithEpochs", "beagleMi355EpochStats", "beagleMi355NodePatternLikelihoods", "beagleMi355NodePatternStats", "beagleMi355NodePosteriors", "beagleMi355NodePosteriorStats", "beagleMi355SetTipEmission", "beagleMi355TipEmissionStats",
+               "beagleMi355SimulateSequences", "beagleMi355SimulateCompleteHistories", "beagleMi355RobustCounts", "beagleMi355SimulateUnconditionedCounts", "beagleMi355NodeHeightDerivatives", "beagleMi355UpdateDifferentialMatrices", "beagleMi355SetReversibleModels", "beagleMi355GetEigenDecomposition", "beagleMi355EigenStats", "beagleMi355UpdateTransitionMatricesFromGenerators", "beagleMi355GeneratorStats", "beagleMi355UpdateTransitionMatricesWithEpochs", "beagleMi355EpochStats", "beagleMi355NodePatternLikelihoods", "beagleMi355NodePatternStats", "beagleMi355NodePosteriors", "beagleMi355NodePosteriorStats", "beagleMi355PlacementScores", "beagleMi355PlacementStats", "beagleMi355SetTipEmission", "beagleMi355TipEmissionStats",
                "beagleMi355GetPartialsPinned", "beagleMi355GetSiteLogLikelihoodsPinned",
                "beagleMi355KernelTimerCalls", "beagleMi355WalkHealth", "beagleMi355RepeatStats", "beagleMi355TableOperandStats", "beagleMi355WalkLaunchInfo", "beagleMi355RootFusedCount", "beagleMi355SitePrefetchCount", "beagleMi355KernelTimerRestart", "beagleMi355GetDimensions", "beagleMi355GetCommUniqueId", "beagleMi355CommInit", "beagleMi355CommInfo", "beagleMi355CalculateRootLogLikelihoodsAllReduce"] + \
               ["beagleBasta" + k for k in ("AllocateCoalescentBuffers", "UpdatePartials", "AccumulatePartials", "GetBuffer", "GetBufferLength", "Stats", "SampleStates", "StatesStats",
@@ -832,6 +832,34 @@ class Beagle:
         out = (C.c_long * 4)()
         self._check("nodePosteriorStats", self._ext("beagleMi355NodePosteriorStats", [C.c_int, C.POINTER(C.c_long)])(self.instance, out))
         return {"calls": int(out[0]), "rows": int(out[1]), "materialised": int(out[2]), "launches": int(out[3])}
+
+    def placementScores(self, candidates, sitePatterns, queryCodes, codeTable, categoryWeightsIndex=0, flags=0, log_table=False):
+        """Scores of attaching every query at every candidate in one call (include/beagle_mi355.h beagleMi355PlacementScores).
+        ``candidates``: [candidateCount][7] rows {parentPre, siblingPost, siblingMatrix, childPost, upperMatrix, lowerMatrix,
+        pendantMatrix}; ``sitePatterns`` [siteCount] (-1 skips a site); ``queryCodes`` uint8 [queryCount][siteCount] (255 = missing);
+        ``codeTable`` [codeCount][S].  -> (scores [queryCount, candidateCount], log table [candidateCount, P, codeCount] or None,
+        return code): the code is 0, or -8 (FLOATING_POINT) when some pattern's likelihood was 0 or not finite — the arrays are
+        written either way, NaN there; every other code raises BeagleException."""
+        rows = _i(candidates).reshape(-1, 7)
+        sites = _i(sitePatterns).reshape(-1)
+        codes = np.ascontiguousarray(queryCodes, dtype=np.uint8).reshape(-1, max(1, sites.shape[0]))
+        table = np.ascontiguousarray(codeTable, dtype=np.float64).reshape(-1, self.stateCount)
+        K, Q, X = rows.shape[0], codes.shape[0], table.shape[0]
+        scores = np.empty((Q, K), dtype=np.float64)
+        logs = np.empty((K, self.patternCount, X), dtype=np.float64) if log_table else None
+        f = self._ext("beagleMi355PlacementScores", [C.c_int, _IP, C.c_int, C.c_int, _IP, C.c_int, C.POINTER(C.c_ubyte), C.c_int, _DP, C.c_int,
+                                                     C.c_int, _DP, _DP])
+        rc = f(self.instance, _ip(rows), K, categoryWeightsIndex, _ip(sites), sites.shape[0], codes.ctypes.data_as(C.POINTER(C.c_ubyte)), Q,
+               _dp(table), X, int(flags), _dp(scores), _dp(logs))
+        if rc != 0 and rc != -8:
+            raise BeagleException("placementScores", rc)
+        return scores, logs, rc
+
+    def placementStats(self):
+        """What placementScores has done (include/beagle_mi355.h beagleMi355PlacementStats)."""
+        out = (C.c_long * 4)()
+        self._check("placementStats", self._ext("beagleMi355PlacementStats", [C.c_int, C.POINTER(C.c_long)])(self.instance, out))
+        return {"calls": int(out[0]), "candidates": int(out[1]), "materialised": int(out[2]), "launches": int(out[3])}
 
     def sampleMarkovJumps(self, nodes, branchTimes, branchRates, eigenIndex, categoryRatesIndex, categoryWeightsIndex,
                           stateFrequenciesIndex, registers, registerFlags, seed, map=False, states=False, jumps=False,

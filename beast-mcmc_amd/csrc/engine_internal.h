@@ -18,6 +18,7 @@
 //   engine_epoch.cpp     branch matrices of epoch models (products of per-segment transition matrices) in one call
 //   engine_nodepattern.cpp  the stochastic Dollo node-pattern likelihood over a post-order node list in one call
 //   engine_nodeposterior.cpp  marginal node state posteriors from resident pre- and post-order partials in one call
+//   engine_placement.cpp  scores of attaching new sequences at candidate points of the tree in one call
 //   engine_stats.cpp     stream, synchronisation, kernel timer, counters
 // each of them argument checks, buffer bookkeeping and one call into the files above.
 // All arithmetic is in the .hip files; these files validate indices, resolve buffer indices to device pointers and enqueue
@@ -416,6 +417,8 @@ struct Instance {
     long statNodePatternCalls = 0, statNodePatternRows = 0, statNodePatternEmpty = 0, statNodePatternMaterialised = 0;      // (beagleMi355NodePatternStats)
     DevBuf nodePosteriorDev;                             // marginal node state posteriors (engine_nodeposterior.cpp): nodePosteriorLayout
     long statNodePosteriorCalls = 0, statNodePosteriorRows = 0, statNodePosteriorMaterialised = 0, statNodePosteriorLaunches = 0;   // (beagleMi355NodePosteriorStats)
+    DevBuf placementDev;                                 // placement scores (engine_placement.cpp): placementLayout
+    long statPlacementCalls = 0, statPlacementCandidates = 0, statPlacementMaterialised = 0, statPlacementLaunches = 0;   // (beagleMi355PlacementStats)
 };
 
 extern std::mutex g_mutex;

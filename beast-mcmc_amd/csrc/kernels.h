@@ -689,6 +689,47 @@ bool launchNodePosteriors(hipStream_t stream, const NodePosteriorRow* dRows, int
 // from 0.0), n_c / D — NaN, and *fpError = 1, where D is 0 or not finite
 void launchNodePosteriorCategories(hipStream_t stream, const NodePosteriorRow* dRow, const double* catWeights, int P, int S, int C,
                                    bool tiled, double* categories, unsigned* fpError);
+// ---- placement scores (kernels_placement.hip; beagleMi355PlacementScores) --------------------------------------------------
+// One candidate attachment, resolved on the host: the parent's pre-order partials; the sibling's post-order partials OR compact
+// states (sibStates != 0) with its branch matrix [C][S][S] (both nullptr: no sibling factor); the child's post-order partials OR compact
+// states (childStates != 0); the matrices parent -> attachment point (nullptr: identity) and attachment point -> child; which pendant
+// table of the call (launchPendantTables) is its own; the row of the launch's table it fills.
+struct PlacementCandidate {
+    const double* pre;
+    const void*   sib;
+    const double* mSib;
+    const void*   child;
+    const double* mUp;
+    const double* mLow;
+    int           pendant;
+    int           sibStates;
+    int           childStates;
+    int           slot;
+};
+static_assert(sizeof(PlacementCandidate) == 64, "PlacementCandidate layout");
+constexpr int PLACEMENT_MAX_CANDIDATES = 65535;      // candidates of one launch (the grid's second dimension)
+constexpr int PLACEMENT_SEGMENT = 8192;              // (pattern, code) entries one accumulator of the score product runs over
+// out [nSlots][C][S][X]: G[m][c][a][x] = sum_b M_{slots[m]},c[a][b] * codeTable[x][b], b ascending from 0.0
+void launchPendantTables(hipStream_t stream, const double* matrices, const int* dSlots, int nSlots, const double* codeTable, int S, int C,
+                         int X, double* out);
+// Per candidate k, pattern p, category c and state a (every sum ascending from 0.0):
+//   u(a) = pre(a) * sum_b Msib[a][b] sib(b)   (pre(a) without a sibling; compact states: 1.0 at the state, all ones when it is >= S)
+//   t(a) = sum_a' u(a') Mup[a'][a]            (u(a) without an upper matrix)
+//   e(a) = t(a) * sum_b Mlow[a][b] child(b)
+//   D   += w_c * sum_a e(a),   N[x] += w_c * sum_a e(a) G_c[a][x]
+// table [slot][P][X] = log(N[x] / D) — NaN, and *fpError = 1, where D is 0 or not finite; -inf where N[x] is 0.
+// false: too many candidates, or the state count needs more LDS than a workgroup can have.
+bool launchPlacementTable(hipStream_t stream, const PlacementCandidate* dCands, int nCands, const double* catWeights, const double* pendant,
+                          int P, int S, int C, int X, bool tiled, double* table, unsigned* fpError);
+int  placementPatternBlock(int S, int X);            // patterns a workgroup of launchPlacementTable takes (0: none fit)
+// counts [nQueries][P][X] += 1 per site with sitePatterns[site] >= 0 and a code < X (integer atomics); the caller zeroes counts
+void launchPlacementCounts(hipStream_t stream, const int* sitePatterns, const uint8_t* codes, int nQueries, int siteCount, int P, int X,
+                           int* counts);
+// scores [nQueries][nCands] = sum over j = p X + x of counts[q][j] * table[k][j], terms with a count of 0 left out: per segment of
+// PLACEMENT_SEGMENT entries ascending from 0.0 into partial [placementSegments][nQueries][nCands], then the segments ascending from 0.0
+int  placementSegments(int P, int X);
+void launchPlacementScores(hipStream_t stream, const int* counts, const double* table, int nQueries, int nCands, int P, int X, double* partial,
+                           double* scores);
 // ---- sequence simulation (kernels_simulate.hip; beagleMi355SimulateSequences) -------------------------------------------
 // One row of the pre-order node list, resolved on the host: its branch matrix [C][S][S] (nullptr at the root), the scratch row
 // ("slot") its states go to and the slot of its parent (-1 at the root); parentIsPrev: the parent is the row right before it, whose

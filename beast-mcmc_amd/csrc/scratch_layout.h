@@ -1,5 +1,5 @@
 // scratch_layout.h — what is inside the samplers' grow-on-demand device buffers (engine_internal.h Instance::ancestralDev, jumpDev,
-// uniformDev, nodePatternDev, nodePosteriorDev, eventDev, simulateDev, robustDev, historyDev): a carver that lays sections out one after another, and per
+// uniformDev, nodePatternDev, nodePosteriorDev, placementDev, eventDev, simulateDev, robustDev, historyDev): a carver that lays sections out one after another, and per
 // buffer a layout that names its sections from plain integers.  Host only, plain C++17, no HIP: tests/native/scratch_layout_check.cpp
 // (NodePatternLayout: node_pattern_layout_check.cpp) compiles it alone and checks every layout's offsets, order and alignment.  The .cpp files resolve sections to pointers (at / as) and grow the
 // buffer to bytes(); they keep no offset arithmetic.
@@ -89,6 +89,22 @@ struct NodePosteriorLayout : Carver {
         blockSums = take<double>(wantTotals ? blocks * rows * S : 0); totals = take<double>(wantTotals ? rows * S : 0);
         categories = take<double>(cats ? P * C : 0); align(256);
         mapStates = take<uint8_t>(map ? rows * P : 0); align(256);
+        error = take<unsigned>(1);
+    }
+};
+
+// placementDev: pendant tables [pendants][C][S][X] | code table [X][S] | log table [candidates][P][X] (outLogTable) | segment sums
+//               [segments][queries][candidates] | scores [queries][candidates] | (256) counts [queries][P][X] | (256) site patterns
+//               [sites] | pendant matrix slots [pendants] | (256) query codes [queries][sites] | (256) error word
+//               — candidates, queries: those of one launch
+struct PlacementLayout : Carver {
+    Doubles pendant, codeTable, table, partial, scores; Ints counts, sitePatterns, slots; Section<uint8_t> codes; Section<unsigned> error;
+    PlacementLayout(size_t candidates, size_t queries, size_t pendants, size_t sites, size_t segments, size_t P, size_t S, size_t C, size_t X) {
+        pendant = take<double>(pendants * C * S * X); codeTable = take<double>(X * S); table = take<double>(candidates * P * X);
+        partial = take<double>(segments * queries * candidates); scores = take<double>(queries * candidates); align(256);
+        counts = take<int>(queries * P * X); align(256);
+        sitePatterns = take<int>(sites); slots = take<int>(pendants); align(256);
+        codes = take<uint8_t>(queries * sites); align(256);
         error = take<unsigned>(1);
     }
 };

@@ -628,6 +628,49 @@ int beagleMi355NodePosteriors(int instance, const int* nodes, int nodeCount, int
  * among a call's listed ones when it arrived (a node listed twice counts once) — whether the held-back pre-order list that ran first
  * or the call itself then gave them real data. */
 int beagleMi355NodePosteriorStats(int instance, long* out4);
+/* Placement scores: for every (new sequence q, candidate attachment k), lnL(tree with q attached at k) - lnL(tree) over the sites kept,
+ * in ONE call behind a pruning pass and a pre-order pass.  The reference's online inference (src/dr/app/realtime:
+ * CheckPointTreeModifier.incorporateAdditionalTaxa :434-800, SimpleDistanceMatrix.calculatePairwiseDistance :63-93) places a new taxon next
+ * to the existing taxon with the smallest p-distance; this is the likelihood that heuristic stands in for.
+ *   candidates [candidateCount][7] = {parentPre, siblingPost, siblingMatrix, childPost, upperMatrix, lowerMatrix, pendantMatrix}.  The
+ *          first four are the buffers of a pre-order operation for the branch; the last three are matrices the caller forms with
+ *          updateTransitionMatrices in spare slots: P(parent -> attachment point), P(attachment point -> child), P(attachment point ->
+ *          new tip).  siblingPost and siblingMatrix may both be BEAGLE_OP_NONE (no sibling factor), upperMatrix may be BEAGLE_OP_NONE
+ *          (identity): {pre(root), NONE, NONE, post(root), NONE, P(x), pendant} is an attachment above the root.  siblingPost and
+ *          childPost: a compact tip's states (a state >= stateCount counts as all ones), a tip's partials, an internal node's partials,
+ *          stored or left unstored by the 4-state walk.
+ *   sitePatterns [siteCount]: the pattern of each alignment site; -1 skips the site.
+ *   queryCodes [queryCount][siteCount]: the code of each query at each site; 255 = missing, the site adds exactly 0.0.
+ *   codeTable [codeCount][stateCount]: the emission row of each code (a state: a unit row; an ambiguity: several ones; any reals).
+ *   flags: none is defined; it must be 0.
+ * With M[a][b] = P(a -> b), w the weights of categoryWeightsIndex and g_x the row of code x, per candidate k, pattern p, category c:
+ *   s_c(a) = sum_b Msib_c[a][b] post_sib,c,p(b)  (1 without a sibling);   u_c(a) = pre_parent,c,p(a) s_c(a);
+ *   t_c(a) = sum_a' u_c(a') Mup_c[a'][a]  (u_c without an upper matrix);  l_c(a) = sum_b Mlow_c[a][b] post_child,c,p(b);
+ *   e_c(a) = t_c(a) l_c(a);   D_p = sum_c w_c sum_a e_c(a);   N_p,x = sum_c w_c sum_a e_c(a) sum_b Mpend_c[a][b] g_x(b);
+ *   T_k[p][x] = log(N_p,x / D_p);   score[q][k] = sum over the sites i kept of T_k[sitePatterns[i]][queryCodes[q][i]].
+ * Every per-pattern scale factor of the three partials cancels in N / D, so no scale buffer is named and rescaled instances work as
+ * they are.  Pattern weights are not read.  The score is formed as sum_j n[q][j] T_k[j] over j = p codeCount + x with n the exact
+ * (integer) number of kept sites of q with pattern p and code x: segments of 8192 entries, each ascending from 0.0, then the segments
+ * ascending from 0.0; a term with n = 0 is left out, so an entry of T that no site of q uses never reaches q's score.  The order
+ * depends on (patternCount, codeCount) alone: two calls, a permuted or split candidate list and any chunk size give the same bits.
+ *   outScores [queryCount][candidateCount];  outLogTable (may be NULL) [candidateCount][patternCount][codeCount] = T.
+ * N = 0 gives -inf (an impossible observation, no error).  A pattern of a candidate whose D is 0 or not finite makes the call return
+ * BEAGLE_ERROR_FLOATING_POINT after everything is written: that row of T is NaN, and so is every score that uses it.
+ * Nothing of the instance changes (buffers that the 4-state walk left unstored are materialised, as for beagleGetPartials; tips with a
+ * folded emission table get their partials; a held-back pre-order list runs first).  Candidates are cut into launches whose log table
+ * stays within 256 MiB and queries into launches whose counts do (BEAGLE_MI355_PLACEMENT_CHUNK=<candidates>,
+ * BEAGLE_MI355_PLACEMENT_QUERY_CHUNK=<queries> in the environment, read at every call: tests).  2..255 states, any category count.
+ * BEAGLE_ERROR_OUT_OF_RANGE, before anything runs, for a bad buffer, matrix or weights index, a buffer never written, a sibling named
+ * without its matrix, a pattern index >= patternCount or < -1, a code >= codeCount other than 255, codeCount > 255, flags != 0, a NULL
+ * input or a count < 1.  BEAGLE_ERROR_NO_IMPLEMENTATION — deliberately out of scope — on an instance with pattern partitions, on an
+ * instance with BASTA buffers, on a sharded handle, and with more than 255 states.  BEAGLE_ERROR_OUT_OF_MEMORY when the scratch
+ * cannot be had.  An extension: no BEAST class calls it today. */
+int beagleMi355PlacementScores(int instance, const int* candidates, int candidateCount, int categoryWeightsIndex,
+                               const int* sitePatterns, int siteCount, const unsigned char* queryCodes, int queryCount,
+                               const double* codeTable, int codeCount, int flags, double* outScores, double* outLogTable);
+/* out4 = {beagleMi355PlacementScores calls since creation, candidates they covered, operands materialised for them, kernel launches}.
+ * Operands materialised: the distinct unstored buffers among a call's listed ones when it arrived. */
+int beagleMi355PlacementStats(int instance, long* out4);
 /* Markov jumps: ONE call that draws the ancestral states as beagleMi355SampleAncestralStates does and, for every register k, row
  * r >= 1 and pattern p, forms the expected number of registered substitutions (a count register) or the expected reward (a reward
  * register) on row r's branch, conditioned on the drawn parent and child states — what MarkovJumpsBeagleTreeLikelihood.hookCalculation
