@@ -11,7 +11,7 @@ which survive a JSON round trip unchanged (``dump`` / ``load``; a profile other 
 record, side)`` makes one call on a binding object and returns (return code, reads), a read being (kind, array); ``deviation(kind,
 got, want)`` is the normalised error of a read, so that one bound (1e-10) holds for every kind.
 
-Two profiles.  "base" (the default) is the method set of ACTIONS with motifs (a)-(i); its sequences are pinned record for record by
+Three profiles ("extensions" and "queries" are described below and behind it).  "base" (the default) is the method set of ACTIONS with motifs (a)-(i); its sequences are pinned record for record by
 tests/golden/call_sequence_digests.json.  "extensions" (shapes of at most 64 states) adds ACTIONS_EXT — the one-call entry points
 sampleAncestralStates, sampleMarkovJumps, simulateSequences, nodeHeightDerivatives, updateDifferentialMatrices, setReversibleModels
 and getEigenDecomposition, each of which decides for itself what happens to the deferred state (whether a held pre-order list runs,
@@ -31,6 +31,30 @@ generator also tracks, for these calls, which (eigen slot, rate slot, length) ev
 slot has changed since (sampleMarkovJumps is emitted over matrices of one unchanged pair only), and what kind of matrix a
 differential slot holds (nodeHeightDerivatives wants Q x category rate).
 
+"queries" (shapes of at most 64 states; its sequences leave those of the other two profiles record for record what they were:
+tests/golden/call_sequence_digests_extensions.json pins the second profile's) is ACTIONS plus setReversibleModels plus ACTIONS_Q — the
+five entry points merged after the second profile was written: updateTransitionMatricesFromGenerators,
+updateTransitionMatricesWithEpochs, nodePosteriors, nodePatternLikelihoods, placementScores — with motifs (a)-(i) and
+  (n) nodePosteriors over every internal node behind a held whole-tree pre-order list, the edge derivatives' sums (variants: the
+      post-order buffers freshly flipped with no root call; setPartials into a listed pre-order buffer between list and call);
+  (o) nodePatternLikelihoods over the whole tree behind that list, which does not write its buffers, the edge sums (variants "plain",
+      "raw" and "log" scale buffers, "emission": a folded tip demoted under the list);
+  (p) a branch matrix that the held list reads rewritten by the generator call or the epoch call (variants "_spare": a spare slot,
+      the list stays held), the edge sums, the child's pre-order partial, the matrix put back;
+  (q) placementScores right behind a whole-tree list with flipped buffers and no root call (variant with setTipEmission first, the
+      tip a candidate's child), then a root call;
+  (r) setReversibleModels(slot), every branch matrix by an epoch call over both slots, partials, a root call (variant "reupload").
+The oracle's side of the two matrix calls is generator_matrices_reference.yardstick / epoch_matrices_reference.yardstick rounded to
+double, then setTransitionMatrix (an epoch entry of ONE segment: the oracle's own updateTransitionMatricesWithMultipleModels; every
+sequence has one); of the three that return values, node_posteriors_reference, stochastic_dollo_reference and placement_reference over
+the oracle's getPartials, getLogScaleFactors and getTransitionMatrix and the compact states it was sent.  Kinds of read: "posterior"
+(posteriors, category posteriors, MAP probabilities, state totals over the sum of the pattern weights: absolute difference), "logval"
+(log pattern values, node terms, log tables, scores: against max(1, |value|)), the sum of a node-pattern call as "sum", MAP states as
+"states" (undecided where the oracle side's two largest posteriors lie within MAP_MARGIN), node terms' -inf entries as a "states"
+mask, and "exact" for the device's posteriors against node_posteriors_reference.posteriors over the same instance's read-back.
+nodePatternLikelihoods takes its death state from the compact tip states the generator itself sent, so that every pattern has a tip
+outside it (where no state does — a subtree over one compact tip — the whole tree is taken; the action is given up if that fails too).
+
 Instance layout for T tips, N = 2T - 1 nodes (``Layout``): internal node n lives in partials buffer T + j (T - 1) + (n - T) of set j
 (j flips per node each time the node is written, as BufferIndexHelper does), its pre-order partials in T + 2 (T - 1) + n; the branch
 matrix of node n in slot j N + n, four spare slots behind them (two for products / sums / transposes / detached updates, two for
@@ -49,6 +73,7 @@ Replay of a failing sequence:  python tests/call_sequences.py --replay FILE --up
 the first diverging read; it stops at the first non-zero return code or exception.
 """
 import json
+import types
 
 import numpy as np
 
@@ -71,11 +96,23 @@ ACTIONS = (
 # profile "extensions": the one-call entry points of include/beagle_mi355.h that sit on top of the deferral logic
 ACTIONS_EXT = ("sampleAncestralStates", "sampleMarkovJumps", "simulateSequences", "nodeHeightDerivatives", "updateDifferentialMatrices",
                "setReversibleModels", "getEigenDecomposition")
-PROFILES = ("base", "extensions")
+# profile "queries": the five one-call entry points merged after that profile was written (setReversibleModels rides along, so that
+# eigen slots the device wrote are in play for the epoch call)
+ACTIONS_Q = ("updateTransitionMatricesFromGenerators", "updateTransitionMatricesWithEpochs", "nodePosteriors", "nodePatternLikelihoods",
+             "placementScores")
+PROFILES = ("base", "extensions", "queries")
 EXT_MAX_STATES = 64                        # several of them answer NO_IMPLEMENTATION above 64 states
 EMISSION_STATES = (4, 20)                  # setTipEmission: 4- and 20-state shapes only
 MOTIFS = "abcdefghi"
 MOTIFS_EXT = "jklm"
+MOTIFS_Q = "nopqr"
+N_VARIANTS = ("flipped", "set_pre")
+O_VARIANTS = ("plain", "raw", "log", "emission")
+P_VARIANTS = ("generators", "epochs", "generators_spare", "epochs_spare")
+Q_VARIANTS = ("plain", "emission")
+R_VARIANTS = ("plain", "reupload")
+MISSING_CODE = 255                         # placementScores: a query's code at a site it does not cover
+MAP_MARGIN = 1e-8                          # nodePosteriors: a pattern is undecided where the two largest posteriors lie this close
 J_VARIANTS = ("updateDifferentialMatrices", "setReversibleModels", "nodeHeightDerivatives", "sampleAncestralStates", "simulateSequences")
 K_VARIANTS = ("plain", "reupload")
 L_VARIANTS = ("ancestral", "jumps", "emission_ancestral", "emission_jumps")
@@ -85,21 +122,38 @@ UNDECIDED_CAP = 0.01                       # of a sequence's (sampler call, patt
 D_VARIANTS = ("getPartials", "getPartialsBatch", "getSiteLogLikelihoods", "getLogScaleFactors", "resetScaleFactors", "copyScaleFactors",
               "setTransitionMatrix", "setCategoryWeights")
 F_VARIANTS = ("read_pre", "read_post", "write_post", "write_matrix", "write_pre", "scale_call", "model_call", "root_call")
+QUERY_FILL = 40                            # drawn calls between the motifs of a query sequence, at the least
 HOST_COPY_MAX = 12                         # uploads one launch carries (motif c queues more)
 
 
 def actions_for(S, profile="base"):
     base = tuple(a for a in ACTIONS if a != "setTipEmission" or S in EMISSION_STATES)
+    if profile == "queries":
+        return base + ("setReversibleModels",) + ACTIONS_Q
     return base + ACTIONS_EXT if profile == "extensions" else base
 
 
 def motifs_for(profile="base"):
+    if profile == "queries":
+        return MOTIFS + MOTIFS_Q
     return MOTIFS + MOTIFS_EXT if profile == "extensions" else MOTIFS
+
+
+def o_variants(S):
+    return O_VARIANTS if S in EMISSION_STATES else O_VARIANTS[:3]
+
+
+def q_variants(S):
+    return Q_VARIANTS if S in EMISSION_STATES else Q_VARIANTS[:1]
 
 
 def variants_for(S, profile="base"):
     """every (motif, variant) that a 4-state shape's seeds hold together: of motifs (d) and (f) over the base profile's 8 seeds, of (j),
-    (k) and (l) over the extension profile's 4 (of (l), the two emission variants exist at 4 and 20 states)"""
+    (k) and (l) over the extension profile's 4 (of (l), the two emission variants exist at 4 and 20 states), of (n)-(r) over the
+    query profile's 4 (the emission variants of (o) and (q) likewise)"""
+    if profile == "queries":
+        return (set(("n", v) for v in N_VARIANTS) | set(("o", v) for v in o_variants(S)) | set(("p", v) for v in P_VARIANTS)
+                | set(("q", v) for v in q_variants(S)) | set(("r", v) for v in R_VARIANTS))
     if profile != "extensions":
         return set(("d", v) for v in D_VARIANTS) | set(("f", v) for v in F_VARIANTS)
     out = set(("j", v) for v in J_VARIANTS) | set(("k", v) for v in K_VARIANTS)
@@ -169,7 +223,7 @@ def symmetric_rates(upper, S):
 
 class Generator:
     def __init__(self, shape, seed, length, profile="base"):
-        if profile not in PROFILES or (profile == "extensions" and shape[0] > EXT_MAX_STATES):
+        if profile not in PROFILES or (profile != "base" and shape[0] > EXT_MAX_STATES):
             raise ValueError("profile %r at %d states" % (profile, shape[0]))
         self.profile = profile
         self.L = L = Layout(shape)
@@ -216,6 +270,10 @@ class Generator:
         self.rates_version = [0, 0]
         self.mfrom = [None] * L.matrix_count    # (eigen slot, its version, rate slot, its version, length) a probability matrix was built from
         self.dkind = {}                         # differential slot -> "Qrate" (Q x category rate), "QQ" or "D" (written by the device)
+        # what the query actions need to know (likewise: nothing is drawn for it, and no record of the other two profiles reads it)
+        self.tip_sent = {}                      # compact tip -> the states last sent to it
+        self.weights_set = False                # setPatternWeights has been called (nodePosteriors' totals)
+        self.single_epoch = False               # an epoch entry with one segment has been emitted
 
     # ---- records ---------------------------------------------------------------------------------------------------------------
     def emit(self, method, args, action):
@@ -278,12 +336,14 @@ class Generator:
 
     def set_pattern_weights(self):
         self.emit("setPatternWeights", [_lst(self.rng.integers(1, 9, size=self.L.P).astype(float))], "setPatternWeights")
+        self.weights_set = True
 
     # ---- data calls ------------------------------------------------------------------------------------------------------------
     def resend_tip(self, t=None):
         t = int(self.rng.integers(self.L.T)) if t is None else t
         if self.tipkind[t] == "compact":
-            self.emit("setTipStates", [t, self.tip_states(first_known=(t == self.first_compact))], "setTipStates")
+            self.tip_sent[t] = self.tip_states(first_known=(t == self.first_compact))
+            self.emit("setTipStates", [t, self.tip_sent[t]], "setTipStates")
         else:
             self.emit("setTipPartials", [t, self.tip_partials()], "setTipPartials")
             self.tipkind[t] = "partials"
@@ -886,9 +946,10 @@ class Generator:
     def get_eigen(self, slot=None):
         self.emit("getEigenDecomposition", [int(self.rng.integers(2)) if slot is None else slot], "getEigenDecomposition")
 
-    def gradient_set_up(self):
-        """what motifs (j) and (m) start from: a whole-tree list, a root call, the differential slot, a held whole-tree pre-order list"""
-        self.update_partials(mode="none", nodes=self.post_order(self.internal))
+    def gradient_set_up(self, mode="none"):
+        """what motifs (j) and (m) — and (n), (o), (p) — start from: a whole-tree list, a root call, the differential slot, a held
+        whole-tree pre-order list"""
+        self.update_partials(mode=mode, cum_on_call=False, nodes=self.post_order(self.internal))
         self.root_call("root", cum=False)
         self.set_differential(0)
         self.set_root_pre()
@@ -957,6 +1018,272 @@ class Generator:
         self.dkind.pop(m, None)
         self.update_matrices(nodes=[child], flip=False)
         self.emit("getPartials", [L.pre(child), NONE], "getPartials:pre")
+
+    # ---- profile "queries": the five entry points merged after the extension profile -------------------------------------------
+    def pick(self, pool):
+        return pool[int(self.rng.integers(len(pool)))]
+
+    def generator_matrices(self, slots=None, lengths=None):
+        """exp(Q d) from one or two generators, each the Q of an eigen slot's model, into one to four slots: current branch matrices at
+        their branches' lengths, or the two spare product slots at the length of some branch"""
+        L, rng = self.L, self.rng
+        models = [[0], [1], [0, 1]][int(rng.integers(3))]
+        if slots is None:
+            pool = [L.matrix(n, self.mcur[n]) for n in self.branches()] + L.spare[:2]
+            slots = sorted(_lst(rng.choice(pool, size=int(rng.integers(1, 5)), replace=False)))
+        if lengths is None:
+            lengths = [float(self.length_of[m % L.N if m < 2 * L.N else self.pick(self.branches())]) for m in slots]
+        g = _lst(rng.integers(0, len(models), size=len(slots)))
+        r = _lst(rng.integers(0, 2, size=len(slots)))
+        self.emit("updateTransitionMatricesFromGenerators", [[_lst(self.models[s][4]) for s in models], g, r, list(slots), list(lengths),
+                                                             len(slots)], "updateTransitionMatricesFromGenerators")
+        for m in slots:
+            self.mdef[m] = "prob"
+            self.mfrom[m] = None
+
+    def epoch_matrices(self, nodes=None, slots=None, lengths=None, flip=False, must=None):
+        """One to three entries (or one per node of `nodes`), each the left fold of one to three segments over the two eigen slots whose
+        lengths add up to the branch's; one rate set per entry.  The first entry of a sequence has a single segment (the oracle side
+        makes such an entry with its own updateTransitionMatricesWithMultipleModels).  `must`: an eigen slot every entry reads (and
+        with two segments or more the other one as well)."""
+        L, rng = self.L, self.rng
+        if nodes is None:
+            nodes = sorted(_lst(rng.choice(self.branches(), size=int(rng.integers(1, 4)), replace=False)))
+            spare = list(L.spare[:2])
+            slots = [spare.pop(0) if spare and rng.random() < 0.3 else L.matrix(n, self.mcur[n]) for n in nodes]
+        elif slots is None:
+            slots = []
+            for n in nodes:
+                if flip:
+                    self.mcur[n] ^= 1
+                slots.append(L.matrix(n, self.mcur[n]))
+        offsets, eig, seg, rate = [0], [], [], []
+        for i, n in enumerate(nodes):
+            k = 1 if (i == 0 and not self.single_epoch) else int(rng.integers(1, 4))
+            self.single_epoch = self.single_epoch or k == 1
+            e = _lst(rng.integers(0, 2, size=k))
+            if must is not None:
+                e[0] = must
+                if k > 1:
+                    e[1] = 1 - must
+            t = float(self.length_of[n]) if lengths is None else lengths[i]
+            eig += e
+            seg += [t] if k == 1 else _lst(rng.dirichlet(np.full(k, 2.0)) * t)
+            offsets.append(len(eig))
+            rate.append(int(rng.integers(2)))
+        self.emit("updateTransitionMatricesWithEpochs", [offsets, eig, seg, rate, list(slots), len(slots)], "updateTransitionMatricesWithEpochs")
+        for m in slots:
+            self.mdef[m] = "prob"
+            self.mfrom[m] = None
+
+    def nodes_with_pre(self):
+        return [n for n in range(self.L.N) if self.pdef[self.L.pre(n)]]
+
+    def compact_among(self, buffers):
+        return sorted(set(b for b in buffers if 0 <= b < self.L.T and self.tipkind[b] == "compact"))
+
+    def node_posteriors(self, nodes=None):
+        """rows {post, pre} over nodes whose pre-order buffer is defined (tips of every kind among them); at least one output"""
+        L, rng = self.L, self.rng
+        if not self.nodes_with_pre():
+            self.update_pre()
+        if nodes is None:
+            pool = self.nodes_with_pre()
+            if rng.random() < 0.6:
+                pool = sorted(_lst(rng.choice(pool, size=int(rng.integers(1, len(pool) + 1)), replace=False)))
+            nodes = pool
+        rows = [[L.post(n, self.cur[n]), L.pre(n)] for n in nodes]
+        full, use_map, totals, cats = (bool(x) for x in rng.random(4) < np.array([0.7, 0.5, 0.4, 0.4]))
+        totals = totals and self.weights_set
+        if not (full or use_map or totals or cats):
+            full = True
+        self.emit("nodePosteriors", [rows, int(rng.integers(2)), full, use_map, totals, cats, self.compact_among(r[0] for r in rows)],
+                  "nodePosteriors")
+
+    def death_states(self, tips):
+        """the states d for which every pattern has a compact tip among `tips` whose state is known and is not d"""
+        L = self.L
+        sent = [np.asarray(self.tip_sent[t]) for t in tips if self.tipkind[t] == "compact"]
+        if not sent:
+            return []
+        sent = np.stack(sent)
+        return [d for d in range(L.S) if np.all(np.any((sent < L.S) & (sent != d), axis=0))]
+
+    def node_pattern(self, whole=None, scale=None):
+        """the post-order rows {buffer, scale buffer or -1, child rows} of the whole tree or of a subtree.  An internal row's scale
+        buffer: -1, the buffer its partials were last written with while that holds raw factors, or a defined buffer of logarithms
+        (`scale`: "raw" — the first of these where there is one —, or {node: buffer}, -1 for the others)."""
+        L, rng = self.L, self.rng
+        whole = rng.random() < 0.6 if whole is None else whole
+        top = L.root if whole else self.pick(self.internal)
+        while True:
+            nodes, stack = [], [(top, False)]
+            while stack:
+                n, done = stack.pop()
+                if done or n < L.T:
+                    nodes.append(n)
+                else:
+                    stack += [(n, True), (self.right[n], False), (self.left[n], False)]
+            death = self.death_states([n for n in nodes if n < L.T])
+            if death or top == L.root:
+                break
+            top = L.root
+        if not death:
+            return False
+        row_of = {n: k for k, n in enumerate(nodes)}
+        rows = []
+        for n in nodes:
+            if n < L.T:
+                rows.append([n, NONE, NONE, NONE])
+                continue
+            own = self.pscale[L.post(n, self.cur[n])]
+            options = [NONE] + ([own] if own != NONE and self.sdef[own] == "raw" else [])
+            if isinstance(scale, dict):
+                sc = scale.get(n, NONE)
+            elif scale == "raw":
+                sc = options[-1]
+            else:
+                sc = self.pick(options + ([self.pick(self.log_scales())] if self.log_scales() else []))
+            rows.append([L.post(n, self.cur[n]), sc, row_of[self.left[n]], row_of[self.right[n]]])
+        self.emit("nodePatternLikelihoods", [rows, _lst(rng.uniform(-3.0, 0.0, size=len(rows))), int(self.pick(death)), int(rng.integers(2)),
+                                             int(rng.integers(2)), bool(rng.random() < 0.5), self.compact_among(r[0] for r in rows)],
+                  "nodePatternLikelihoods")
+
+    def code_table(self):
+        """S + 1 codes as tests/test_gpu_placement.py code_table builds them: the states 0 .. S - 2, a partially ambiguous row (the last
+        two states), a real-valued emission row"""
+        S = self.L.S
+        return [np.eye(S)[s] for s in range(S - 1)] + [np.r_[np.zeros(S - 2), 1.0, 1.0], self.rng.uniform(0.05, 1.0, size=S)]
+
+    def placement(self, tip_child=None):
+        """two to six candidates: the first above the root, the second with a tip as its child (`tip_child`: that one), the others
+        on any branch under a parent whose pre-order buffer is defined; lower, upper and pendant matrices from the spare slots or from
+        any slot that holds probabilities"""
+        L, rng = self.L, self.rng
+        if not self.pdef[L.pre(L.root)]:
+            self.set_root_pre()
+
+        def pool():
+            return [n for n in self.branches() if self.pdef[L.pre(self.parent[n])]]
+        if not [n for n in pool() if n < L.T] or (tip_child is not None and tip_child not in pool()):
+            self.update_pre(whole=True)
+        tip = self.pick([n for n in pool() if n < L.T]) if tip_child is None else tip_child
+        where = [L.root, tip] + [self.pick(pool() + [L.root]) for _ in range(int(rng.integers(0, 5)))]
+        spare = [m for m in L.spare[:2] if self.mdef[m] == "prob"]
+
+        def matrix():
+            return self.pick(spare) if spare and rng.random() < 0.6 else self.pick(self.prob_slots())
+        rows = []
+        for n in where:
+            if n == L.root:
+                rows.append([L.pre(n), NONE, NONE, L.post(n, self.cur[n]), NONE, matrix(), matrix()])
+                continue
+            p = self.parent[n]
+            s = self.right[p] if self.left[p] == n else self.left[p]
+            assert self.mdef[L.matrix(s, self.mcur[s])] == "prob"
+            rows.append([L.pre(p), L.post(s, self.cur[s]), L.matrix(s, self.mcur[s]), L.post(n, self.cur[n]),
+                         NONE if rng.random() < 0.25 else matrix(), matrix(), matrix()])
+        sites = int(self.pick(SITE_COUNTS))
+        patterns = rng.integers(0, L.P, size=sites)
+        patterns[rng.random(sites) < 0.05] = NONE
+        queries = int(rng.integers(1, 4))
+        codes = rng.integers(0, L.S + 1, size=(queries, sites))
+        codes[rng.random((queries, sites)) < 0.05] = MISSING_CODE
+        self.emit("placementScores", [rows, _lst(patterns), _lst(codes), _lst(np.stack(self.code_table())), int(rng.integers(2)),
+                                      bool(rng.random() < 0.5), self.compact_among([r[1] for r in rows] + [r[3] for r in rows])],
+                  "placementScores")
+
+    def motif_n(self):
+        """nodePosteriors behind a held whole-tree pre-order list (it always runs the list), over every internal node, then the edge
+        derivatives' sums.  Variant "flipped": the post-order buffers freshly flipped by a whole-tree list with no root call behind it
+        (unstored at 4 states); "set_pre": setPartials into one listed pre-order buffer between the list and the call (the list has
+        to run before the setPartials, the call has to read what was set)"""
+        L = self.L
+        self.variant = v = N_VARIANTS[self.seed % 2]
+        self.gradient_set_up()
+        if v == "flipped":
+            self.update_partials(mode="none", nodes=self.post_order(self.internal))
+        else:
+            inner = [n for n in self.internal if n != L.root]
+            self.set_partials(L.pre(inner[len(inner) // 2]))
+        self.node_posteriors(nodes=list(self.internal))
+        self.edge_differentials(want=0, all_edges=True)
+
+    def motif_o(self):
+        """nodePatternLikelihoods over the whole tree behind a held whole-tree pre-order list that does not write its buffers (on 4
+        states the list may stay held, or run late because something is materialised), then the edge derivatives' sums.  Variants:
+        "plain"; "emission" (4 and 20 states): setTipEmission on a tip before the set-up, so the call demotes a folded tip under the
+        list; "raw": the partials written with scale factors, every row naming its raw buffer; "log": likewise, the root's row naming
+        a cumulative buffer that holds them all"""
+        L = self.L
+        pool = o_variants(L.S)
+        self.variant = v = pool[self.seed % len(pool)]
+        if v == "emission":
+            self.set_tip_emission()
+        if v == "log":
+            self.update_partials(mode="write", cum_on_call=False, nodes=self.post_order(self.internal))
+            self.reset_scale(L.cum[1])
+            self.accumulate(L.cum[1], [L.scale(n, self.cur[n]) for n in self.internal])
+            self.root_call("root", cum=False)
+            self.set_differential(0)
+            self.set_root_pre()
+            self.update_pre(whole=True)
+        else:
+            self.gradient_set_up(mode="write" if v == "raw" else "none")
+        self.node_pattern(whole=True, scale={"raw": "raw", "log": {L.root: L.cum[1]}}.get(v))
+        self.edge_differentials(want=0, all_edges=True)
+
+    def motif_p(self):
+        """a branch matrix rewritten on the device behind a held whole-tree pre-order list — the matrix of the root's left child, which
+        the list reads (it has to run first, over the old matrix), at another branch's length; variants "_spare": a spare slot
+        (the list stays held) —, the edge derivatives' sums, the child's pre-order partial, the matrix put back"""
+        L = self.L
+        self.variant = v = P_VARIANTS[self.seed % len(P_VARIANTS)]
+        self.gradient_set_up()
+        child = self.left[L.root]
+        m = L.spare[0] if v.endswith("_spare") else L.matrix(child, self.mcur[child])
+        other = max(self.branches(), key=lambda n: abs(self.length_of[n] - self.length_of[child]))
+        if v.startswith("generators"):
+            self.generator_matrices(slots=[m], lengths=[float(self.length_of[other])])
+        else:
+            self.epoch_matrices(nodes=[child], slots=[m], lengths=[float(self.length_of[other])])
+        self.edge_differentials(want=0, all_edges=True)
+        self.emit("getPartials", [L.pre(child), NONE], "getPartials:pre")
+        self.update_matrices(nodes=[child], flip=False)
+
+    def motif_q(self):
+        """placementScores right behind a whole-tree list with flipped buffers and no root call (motif (l)'s situation); at 4 and 20
+        states also with a tip's emission table set first, that tip being the child of one candidate; then a root call: what
+        materialising and demoting left behind must still evaluate"""
+        L = self.L
+        pool = q_variants(L.S)
+        self.variant = v = pool[(self.seed // 2) % len(pool)]
+        tip = None
+        if v == "emission":
+            self.set_tip_emission()
+            tip = self.rec[-1]["a"][0]
+        if len(self.nodes_with_pre()) < L.N:
+            self.update_pre(whole=True)
+        self.update_partials(mode="none", nodes=self.post_order(self.internal))
+        self.placement(tip_child=tip)
+        self.root_call("root", cum=False)
+        self.get_sites()
+
+    def motif_r(self):
+        """epochs over an eigen slot the device wrote: setReversibleModels(slot), every branch's matrix from segments over both slots,
+        the partials, a root call; variant "reupload": the slot's previous values uploaded behind the device's write and in front
+        of the epoch call — motif (k)'s upload that must not be skipped"""
+        slot = int(self.rng.integers(2))
+        self.variant = v = R_VARIANTS[(self.seed // 2) % 2]
+        previous = self.models[slot]
+        self.set_reversible([slot])
+        if v == "reupload":
+            self.models[slot] = previous
+            self.set_eigen(slot, same=True)
+        self.epoch_matrices(nodes=self.branches(), flip=True, must=slot)
+        self.update_partials(mode="none", nodes=self.post_order(self.internal))
+        self.root_call("root", cum=False)
+        self.get_sites()
 
     # ---- the set-up every sequence starts with -------------------------------------------------------------------------------
     def prelude(self):
@@ -1227,7 +1554,14 @@ class Generator:
             (4, "updateDifferentialMatrices", self.update_differential),
             (3, "setReversibleModels", self.set_reversible),
             (3, "getEigenDecomposition", self.get_eigen),
-        ] if self.profile == "extensions" else [])
+        ] if self.profile == "extensions" else []) + ([
+            (3, "setReversibleModels", self.set_reversible),
+            (4, "updateTransitionMatricesFromGenerators", self.generator_matrices),
+            (4, "updateTransitionMatricesWithEpochs", self.epoch_matrices),
+            (4, "nodePosteriors", self.node_posteriors),
+            (4, "nodePatternLikelihoods", self.node_pattern),
+            (4, "placementScores", self.placement),
+        ] if self.profile == "queries" else [])
 
     def draw(self, lacking_only=False):
         """one drawn action: one this sequence has not made yet while there is any (every sequence makes every action), else by weight
@@ -1254,7 +1588,7 @@ class Generator:
     def lacking(self):
         """the actions this sequence has not made yet (extension profile, whose shapes have fewer seeds: not twice yet) and has not
         given up on"""
-        need = 2 if self.profile == "extensions" else 1
+        need = 2 if self.profile != "base" else 1
         count = {}
         for r in self.rec[self.prelude_end:]:
             count[r["action"]] = count.get(r["action"], 0) + 1
@@ -1273,7 +1607,8 @@ class Generator:
             getattr(self, "motif_" + letter)()
             self.motif = self.variant = None
         motif_calls = len(self.rec) - start
-        fill = max(4 if self.profile == "base" else 60, budget - motif_calls)     # (the 13 motifs of the extension profile use the budget up)
+        # (the 13 motifs of the extension profile and the 14 of the query profile use the budget up)
+        fill = max({"base": 4, "extensions": 60}.get(self.profile, QUERY_FILL), budget - motif_calls)
         # (the motifs were generated to learn their size; generate again with the filler between them)
         return motif_calls, [int(round(g * fill)) for g in gaps], order
 
@@ -1296,7 +1631,7 @@ def generate(shape, seed, length=100, profile="base"):
     target = len(g.rec) + gaps[-1]
     while len(g.rec) < target:
         g.draw()
-    for _ in range(2 * len(ACTIONS) * (2 if profile == "extensions" else 1)):          # whatever action the sequence still lacks
+    for _ in range(2 * len(ACTIONS) * (2 if profile != "base" else 1)):          # whatever action the sequence still lacks
         if not g.lacking():
             break
         g.draw(lacking_only=True)
@@ -1373,7 +1708,8 @@ def packed_eigen(u, ui, lam):
 
 
 def execute_extension(b, rec, side, info):
-    """One call of ACTIONS_EXT.  side "oracle": made from the oracle's own calls and the numpy restatements the extensions' tests use
+    """One call of ACTIONS_EXT or ACTIONS_Q (the latter: the module docstring's paragraph on the "queries" profile; nodePosteriors reads
+    its operands back on every side, the other four on the oracle's side only).  side "oracle": made from the oracle's own calls and the numpy restatements the extensions' tests use
     (updateDifferentialMatrices: differential_matrices_reference.slot, then setDifferentialMatrix; setReversibleModels: numpy's eigh
     of the symmetric form, then setEigenDecomposition; the five calls that return values: ancestral_reference.sample,
     simulate_reference.simulate, node_height_reference.row_derivatives, markov_jumps_reference.tables and site_values over the
@@ -1484,6 +1820,117 @@ def execute_extension(b, rec, side, info):
             b.setReversibleModels(*a)
     elif m == "getEigenDecomposition":
         reads.append(("eigen", packed_eigen(*(have["eigen"][a[0]] if side == "oracle" else b.getEigenDecomposition(a[0])))))
+    elif m == "updateTransitionMatricesFromGenerators":
+        gens, g, r, slots, lengths, count = a
+        if side == "oracle":
+            import generator_matrices_reference
+            for k, slot in enumerate(slots):
+                q = np.array(gens[g[k]], dtype=float)
+                mat = [generator_matrices_reference.yardstick(q, float(np.float64(lengths[k]) * np.float64(rate))) for rate in have["rates"][r[k]]]
+                b.setTransitionMatrix(slot, np.stack(mat).astype(np.float64).ravel(), 1.0)
+        else:
+            b.updateTransitionMatricesFromGenerators(gens, g, r, slots, lengths, count)
+    elif m == "updateTransitionMatricesWithEpochs":
+        offsets, eig, seg, rate, slots, count = a
+        if side == "oracle":
+            import epoch_matrices_reference
+            systems = {k: types.SimpleNamespace(evec=e[0], ievc=e[1], evals=e[2]) for k, e in have["eigen"].items()}
+            for k, slot in enumerate(slots):
+                entry = [(eig[j], seg[j]) for j in range(offsets[k], offsets[k + 1])]
+                if len(entry) == 1:                          # (exactly what the oracle's own call leaves in the slot)
+                    b.updateTransitionMatricesWithMultipleModels([entry[0][0]], [rate[k]], [slot], None, None, [entry[0][1]], 1)
+                else:
+                    mat = [epoch_matrices_reference.yardstick(systems, entry, x) for x in have["rates"][rate[k]]]
+                    b.setTransitionMatrix(slot, np.stack(mat).astype(np.float64).ravel(), 1.0)
+        else:
+            b.updateTransitionMatricesWithEpochs(offsets, eig, seg, rate, slots, count)
+    elif m == "nodePosteriors":
+        import node_posteriors_reference
+        rows, w, full, use_map, totals, cats, compact = a
+        out = None
+        if side != "oracle":
+            out, rc = b.nodePosteriors(rows, w, full=full, map=use_map, totals=totals, categories=cats)
+            if rc:
+                return rc, []
+        pre = np.stack([b.getPartials(row[1], NONE) for row in rows])
+        post = np.stack([post_of(row[0], compact) for row in rows])
+        ref, _, bad = node_posteriors_reference.posteriors(pre, post, have["weights"][w])
+        if side == "oracle":
+            if bad.any():
+                return -8, []
+            out = {"posteriors": ref, "categories": node_posteriors_reference.category_posteriors(pre[0], post[0], have["weights"][w])}
+            out["map_states"], out["map_probabilities"] = node_posteriors_reference.map_states(ref)
+            if totals:
+                out["totals"] = np.asarray(node_posteriors_reference.state_totals(ref, have["pattern_weights"]), dtype=np.float64)
+            if use_map:
+                top = np.sort(ref, axis=2)[:, :, -2:]
+                info["undecided"] = np.any(top[:, :, 1] - top[:, :, 0] <= MAP_MARGIN, axis=0)
+        if full:
+            reads += [("posterior", out["posteriors"]),
+                      ("exact", np.array([0.0 if side == "oracle" else float(np.sum(out["posteriors"] != ref))]))]
+        if use_map:
+            reads += [("states", out["map_states"]), ("posterior", out["map_probabilities"])]
+        if totals:
+            reads.append(("posterior", out["totals"] / float(np.sum(have["pattern_weights"]))))
+        if cats:
+            reads.append(("posterior", out["categories"]))
+    elif m == "nodePatternLikelihoods":
+        rows, logw, death, w, f, node_terms, compact = a
+        if side != "oracle":
+            logp, terms, total, rc = b.nodePatternLikelihoods(rows, logw, death, w, f, node_terms=node_terms)
+            if rc:
+                return rc, []
+        else:
+            import stochastic_dollo_reference as sd
+            # the restatement numbers tips first: the tip rows in list order, then the internal rows in list order (still post-order)
+            tip_rows = [k for k, row in enumerate(rows) if row[2] < 0]
+            number = {k: i for i, k in enumerate(tip_rows + [k for k, row in enumerate(rows) if row[2] >= 0])}
+            R, T = len(rows), len(tip_rows)
+            left, right = np.full(R, NONE), np.full(R, NONE)
+            partials, own = [None] * R, np.zeros((R, P))
+            states, as_partials = np.zeros((T, P), dtype=np.int64), {}
+            weights_by_node = np.zeros(R)
+            for k, row in enumerate(rows):
+                n = number[k]
+                partials[n] = post_of(row[0], compact)
+                weights_by_node[n] = logw[k]
+                if row[2] < 0 and row[0] in compact:
+                    states[n] = tip_states_of(row[0])
+                elif row[2] < 0:
+                    as_partials[n] = partials[n][0]
+                else:
+                    left[n], right[n] = number[row[2]], number[row[3]]
+                    if row[1] != NONE:
+                        own[n] = b.getLogScaleFactors(row[1])
+            tree = types.SimpleNamespace(node_count=R, tip_count=T, left=left, right=right, postorder=lambda: range(R))
+            _, incl = sd.inclusion(tree, sd.tip_extant(states, as_partials, S, death))
+            by_node, _ = sd.log_terms(tree, [number[k] for k in range(R)], np.stack(partials), own, incl, have["freqs"][f], have["weights"][w],
+                                      weights_by_node, np.float64)
+            logp, terms = sd.log_cum(by_node, np.float64), by_node
+            total = float(np.sum(have["pattern_weights"] * logp))
+            if not np.isfinite(total):
+                return -8, []
+        reads.append(("logval", logp))
+        if node_terms:                                       # (a row that is not included has the term -inf: compared as a mask)
+            there = np.asarray(terms) != -np.inf
+            reads += [("states", there.astype(np.uint8)), ("logval", np.where(there, terms, 0.0))]
+        reads.append(("sum", np.array([total])))
+    elif m == "placementScores":
+        rows, patterns, codes, table, w, log_table, compact = a
+        if side != "oracle":
+            scores, logs, rc = b.placementScores(rows, patterns, codes, table, w, log_table=log_table)
+            if rc:
+                return rc, []
+        else:
+            import placement_reference
+            operands = [(b.getPartials(pre, NONE), None if sib == NONE else post_of(sib, compact), None if sib == NONE else matrix_of(m_sib),
+                         post_of(child, compact), None if m_up == NONE else matrix_of(m_up), matrix_of(m_low), matrix_of(m_pend))
+                        for pre, sib, m_sib, child, m_up, m_low, m_pend in rows]
+            logs = placement_reference.log_tables(operands, have["weights"][w], np.array(table, dtype=float).reshape(-1, S))
+            scores = placement_reference.scores(logs, patterns, codes)
+            if not (np.isfinite(logs).all() and np.isfinite(scores).all()):
+                return -8, []
+        reads += ([("logval", logs)] if log_table else []) + [("logval", scores)]
     else:
         raise ValueError(m)
     return 0, reads
@@ -1497,7 +1944,7 @@ def execute(b, rec, side="engine", info=None):
     m, a = rec["m"], rec["a"]
     reads = []
     try:
-        if m in ACTIONS_EXT:
+        if m in ACTIONS_EXT or m in ACTIONS_Q:
             rc, reads = execute_extension(b, rec, side, {} if info is None else info)
             if rc:
                 return rc, []
@@ -1568,8 +2015,10 @@ def deviation(kind, got, want, undecided=None):
         return float("nan")
     if kind in ("sum", "site"):
         return float(np.max(np.abs(got - want) / np.maximum(np.abs(want), 1e-300)))
-    if kind == "scale":
+    if kind in ("scale", "logval"):
         return float(np.max(np.abs(got - want) / np.maximum(np.abs(want), 1.0)))
+    if kind == "posterior":
+        return float(np.max(np.abs(got - want)))
     if kind == "partials":
         scale = np.maximum(np.abs(want).max(axis=(0, 2), keepdims=True), 1e-300)
         return float(np.max(np.abs(got - want) / scale))

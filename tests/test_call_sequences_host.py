@@ -30,8 +30,23 @@ sequence), and
     (61, 1, 6, 37)      1.8e-13
     (7, 2, 8, 67)       3.9e-15
 
-The base profile's sequences are pinned record for record: tests/golden/call_sequence_digests.json holds the sha256 of each one's
-dumped file, written before the generator learned the second profile.
+And for the third profile, "queries" (updateTransitionMatricesFromGenerators, updateTransitionMatricesWithEpochs, nodePosteriors,
+nodePatternLikelihoods, placementScores and motifs (n)-(r), on the same shapes and seeds): posteriors, log pattern values, node terms,
+log tables and scores within 1e-11 of the long-double run, MAP states equal to its on every decided pattern (undecided: the two largest
+posteriors within 1e-8), at most 1 % of the (sampler or MAP call, pattern) pairs undecided.  No input had to be drawn differently and no
+seed replaced: the generator's branch lengths (0.01 .. 1), the code table's real-valued row (0.05 .. 1) and the log weights (-3 .. 0)
+keep every log value a few units from 0.  Measured: no pair undecided (0 .. 514 pairs a sequence), and
+
+    (S, C, T, P)        largest deviation, queries
+    (4, 4, 12, 130)     9.3e-15
+    (4, 3, 9, 257)      1.5e-14
+    (20, 2, 8, 33)      1.5e-14
+    (61, 1, 6, 37)      2.0e-14
+    (7, 2, 8, 67)       1.1e-14
+
+The sequences of the first two profiles are pinned record for record: tests/golden/call_sequence_digests.json holds the sha256 of each
+base sequence's dumped file, written before the generator learned the second profile, and
+tests/golden/call_sequence_digests_extensions.json those of the extension profile, written before it learned the third.
 """
 import collections
 import hashlib
@@ -55,12 +70,16 @@ CONDITIONING_BOUND = 1e-11
 SHAPES_EXT = [s for s in SHAPES if s[0] <= cs.EXT_MAX_STATES]
 SEEDS_EXT = {shape: list(range(1, 5 if shape[0] == 4 else 3)) for shape in SHAPES_EXT}
 CASES_EXT = [(shape, seed) for shape in SHAPES_EXT for seed in SEEDS_EXT[shape]]
-PROFILE_CASES = [c + ("base",) for c in CASES] + [c + ("extensions",) for c in CASES_EXT]
-DIGESTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "call_sequence_digests.json")
+# profile "queries": the same shapes and seeds as "extensions".  No seed had to be replaced here either.
+CASES_Q = list(CASES_EXT)
+PROFILE_CASES = [c + ("base",) for c in CASES] + [c + ("extensions",) for c in CASES_EXT] + [c + ("queries",) for c in CASES_Q]
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+DIGESTS = os.path.join(GOLDEN, "call_sequence_digests.json")
+DIGESTS_EXT = os.path.join(GOLDEN, "call_sequence_digests_extensions.json")
 
 
 def seeds_of(shape, profile="base"):
-    return SEEDS_EXT[shape] if profile == "extensions" else SEEDS[shape]
+    return SEEDS[shape] if profile == "base" else SEEDS_EXT[shape]
 
 
 def length_for(seed):
@@ -112,6 +131,19 @@ def test_the_base_sequences_are_record_for_record_what_they_were(tmp_path):
             assert hashlib.sha256(f.read()).hexdigest() == want[case_id((shape, seed))], (shape, seed)
 
 
+def test_the_extension_sequences_are_record_for_record_what_they_were(tmp_path):
+    """The same for the extension profile: the sha256 of every one of its sequences' dumped files, written before the generator
+    learned the third profile, "queries"."""
+    with open(DIGESTS_EXT) as f:
+        want = json.load(f)
+    assert sorted(want) == sorted(case_id(c + ("extensions",)) for c in CASES_EXT)
+    path = str(tmp_path / "sequence.json")
+    for shape, seed in CASES_EXT:
+        cs.dump(path, shape, seed, records(shape, seed, "extensions"), "extensions")
+        with open(path, "rb") as f:
+            assert hashlib.sha256(f.read()).hexdigest() == want[case_id((shape, seed, "extensions"))], (shape, seed)
+
+
 @pytest.mark.parametrize("case", PROFILE_CASES[::5], ids=case_id)
 def test_same_seed_same_records_and_json_round_trip(case, tmp_path):
     shape, seed, profile = case
@@ -130,12 +162,13 @@ def prelude_length(shape, seed, profile="base"):
     return g.prelude_end
 
 
-@pytest.mark.parametrize("shape", SHAPES + [s + ("extensions",) for s in SHAPES_EXT],
+@pytest.mark.parametrize("shape", SHAPES + [s + ("extensions",) for s in SHAPES_EXT] + [s + ("queries",) for s in SHAPES_EXT],
                          ids=lambda s: "S%d-C%d-T%d-P%d" % s[:4] + "".join("-" + x for x in s[4:]))
 def test_every_action_and_motif_is_there(shape):
     """Coverage is a condition: over a shape's seeds every action at least 3 times (counted behind the set-up calls), every motif in
-    every sequence; a 4-state shape's seeds together hold every variant of the motifs that have variants."""
-    shape, profile = shape[:4], "extensions" if len(shape) > 4 else "base"
+    every sequence; a 4-state shape's seeds together hold every variant of the motifs that have variants.  Query profile: every
+    sequence also holds an epoch entry with a single segment, a placement candidate above the root and one whose child is a tip."""
+    shape, profile = shape[:4], shape[4] if len(shape) > 4 else "base"
     count, variants = collections.Counter(), set()
     for seed in seeds_of(shape, profile):
         recs = records(shape, seed, profile)
@@ -144,6 +177,13 @@ def test_every_action_and_motif_is_there(shape):
         assert set(r["motif"] for r in tail if r["motif"]) == set(cs.motifs_for(profile)), seed
         variants |= set((r["motif"], r["variant"]) for r in tail if r["variant"])
         assert all(r["action"] in cs.actions_for(shape[0], profile) for r in recs)
+        if profile == "queries":
+            epochs = [r["a"][0] for r in recs if r["m"] == "updateTransitionMatricesWithEpochs"]
+            assert any(b - a == 1 for off in epochs for a, b in zip(off, off[1:])), seed
+            for r in recs:
+                if r["m"] == "placementScores":
+                    assert 2 <= len(r["a"][0]) <= 6 and len(r["a"][3]) == shape[0] + 1
+                    assert any(c[1] == cs.NONE and c[2] == cs.NONE for c in r["a"][0]) and any(c[3] < shape[2] for c in r["a"][0]), seed
     short = {a: count[a] for a in cs.actions_for(shape[0], profile) if count[a] < 3}
     assert not short, short
     if shape[0] == 4:
@@ -167,6 +207,9 @@ def test_the_open_cases_of_the_contract_are_never_emitted():
                 assert all(i != o for i, o in zip(a[0], a[1]))
             elif m == "calculateRootLogLikelihoods":
                 assert a[4] == 1
+            elif m in ("updateTransitionMatricesFromGenerators", "updateTransitionMatricesWithEpochs"):
+                slots = a[3] if m.endswith("Generators") else a[4]
+                assert len(set(slots)) == len(slots) == a[-1]                  # (no slot twice in one call)
             elif m.startswith("updateTransitionMatrices"):
                 assert a[-4] is None and a[-3] is None
 
@@ -227,6 +270,27 @@ def test_deviation_of_the_new_kinds_sees_what_it_should():
     assert cs.deviation("exact", np.array([0.0]), np.array([0.0])) == 0.0
     assert cs.deviation("exact", np.array([3.0]), np.array([0.0])) > 1.0 and cs.deviation("exact", np.array([3.0]), np.array([3.0])) > 1.0
     assert cs.deviation("jumps", np.array([2.0, 1e-9]), np.array([2.0, 0.0])) == pytest.approx(5e-10)
+    # the query profile's kinds: posteriors (and category posteriors, MAP probabilities, totals over the sum of the pattern weights)
+    # by their absolute difference; a log value against max(1, |value|); MAP states on the decided patterns only
+    post = rng.dirichlet(np.full(4, 2.0), size=(3, 9))
+    off = post.copy()
+    off[1, 4, 2] += 1e-8
+    assert cs.deviation("posterior", post, post.copy()) == 0.0
+    assert cs.deviation("posterior", off, post) == pytest.approx(1e-8) and cs.deviation("posterior", off, post) > cs.BOUND
+    logs = np.array([[-0.02, -5.0], [-700.0, -1e-12]])
+    assert cs.deviation("logval", logs, logs.copy()) == 0.0
+    assert cs.deviation("logval", logs + np.array([[1e-8, 0.0], [0.0, 0.0]]), logs) == pytest.approx(1e-8)     # (a value near 0: absolute)
+    assert cs.deviation("logval", logs * np.array([[1.0, 1.0], [1.0 + 1e-8, 1.0]]), logs) == pytest.approx(1e-8, rel=1e-3)
+    assert cs.deviation("logval", logs * np.array([[1.0, 1.0], [1.0 + 1e-12, 1.0]]), logs) < cs.BOUND
+    assert cs.deviation("logval", np.array([-np.inf]), np.array([-np.inf])) != cs.deviation("logval", np.array([-np.inf]), np.array([-np.inf]))
+    assert cs.deviation("sum", np.array([-1234.5 * (1.0 + 1e-8)]), np.array([-1234.5])) == pytest.approx(1e-8, rel=1e-3)
+    ms = np.argmax(post, axis=2).astype(np.uint8)
+    other = ms.copy()
+    other[0, 7] = (other[0, 7] + 1) % 4
+    und = np.zeros(9, dtype=bool)
+    assert cs.deviation("states", other, ms, undecided=und) == 1.0
+    und[7] = True
+    assert cs.deviation("states", other, ms, undecided=und) == 0.0
 
 
 def test_a_draw_next_to_a_boundary_is_reported_undecided():
@@ -275,3 +339,38 @@ def test_motifs_k_and_m_would_show_the_wrong_decision(case, oracle_lib):
     other = list(recs)
     other[m[-4]:m[-1]] = [recs[m[-3]], recs[m[-2]], recs[m[-4]]]
     assert worst_over(shape, recs, other, [(m[-1], m[-1])], oracle_lib) > 1e4 * cs.BOUND
+
+
+@pytest.mark.parametrize("case", [c for c in CASES_Q if c[0][0] == 4], ids=case_id)
+def test_motifs_n_p_and_r_would_show_the_wrong_decision(case, oracle_lib):
+    """The same for the query profile's motifs, whichever of them the seed holds in the variant that matters: (p) without "_spare"
+    with the pre-order list run only after the branch's matrix was rewritten — what a list left held would do; (r, variant
+    "reupload") without the setEigenDecomposition behind setReversibleModels; (n, variant "set_pre") with the posteriors taken
+    before the setPartials into the pre-order buffer — what a call that did not see the write would return."""
+    shape, seed = case
+    recs = records(shape, seed, "queries")
+    played = 0
+    p = [i for i, r in enumerate(recs) if r["motif"] == "p"]
+    if not recs[p[0]]["variant"].endswith("_spare"):
+        assert [recs[i]["m"] for i in p[-5:-3]] + [recs[i]["m"] for i in p[-3:]] == \
+            ["updatePrePartials", recs[p[-4]]["m"], "calculateEdgeDifferentials", "getPartials", "updateTransitionMatrices"]
+        assert recs[p[-4]]["m"] in ("updateTransitionMatricesFromGenerators", "updateTransitionMatricesWithEpochs")
+        other = list(recs)
+        other[p[-5]], other[p[-4]] = recs[p[-4]], recs[p[-5]]
+        assert worst_over(shape, recs, other, [(p[-3], p[-3]), (p[-2], p[-2])], oracle_lib) > 1e4 * cs.BOUND
+        played += 1
+    r = [i for i, x in enumerate(recs) if x["motif"] == "r"]
+    if recs[r[0]]["variant"] == "reupload":
+        drop = [i for i in r if recs[i]["m"] == "setEigenDecomposition"]
+        assert len(drop) == 1 and recs[drop[0] - 1]["m"] == "setReversibleModels"
+        other = recs[:drop[0]] + recs[drop[0] + 1:]
+        assert worst_over(shape, recs, other, [(i, i - 1) for i in r if i > drop[0]], oracle_lib) > 1e4 * cs.BOUND
+        played += 1
+    n = [i for i, x in enumerate(recs) if x["motif"] == "n"]
+    if recs[n[0]]["variant"] == "set_pre":
+        assert [recs[i]["m"] for i in n[-4:]] == ["updatePrePartials", "setPartials", "nodePosteriors", "calculateEdgeDifferentials"]
+        other = list(recs)
+        other[n[-3]], other[n[-2]] = recs[n[-2]], recs[n[-3]]
+        assert worst_over(shape, recs, other, [(n[-2], n[-3])], oracle_lib) > 1e4 * cs.BOUND
+        played += 1
+    assert played, "each of the seeds 1 .. 4 holds one of the three at the least"

@@ -39,23 +39,40 @@ categories of every draw twice — byte for byte against the restatement over wh
 (read "exact"), and against the restatement over the oracle's reads on every decided pattern, with at most 1 % of a sequence's
 (sampler call, pattern) pairs undecided.  Route evidence over a 4-state shape's seeds: a held pre-order list both run late and
 answered while held, models decomposed on the device, a folded tip demoted by a sampler, one-launch walks.
+
+The third profile, "queries", does the same for the five entry points merged since — updateTransitionMatricesFromGenerators,
+updateTransitionMatricesWithEpochs, nodePosteriors, nodePatternLikelihoods, placementScores — with motifs (n)-(r): the same shapes
+and seeds, the same three instances and conditions, two seeds on the sharded handle (where placementScores answers NO_IMPLEMENTATION
+before it changes anything and is left out; the four others run).  What is compared: the matrices the two matrix calls wrote through
+every later read; posteriors, category posteriors, MAP probabilities and state totals (over the sum of the pattern weights) by their
+absolute difference; MAP states on every decided pattern; log pattern values, node terms, log tables and scores against max(1,
+|value|), the node-pattern sum as a log-likelihood; and the device's posteriors byte for byte against
+node_posteriors_reference.posteriors over what the same instance reads back (read "exact").  Route evidence over a 4-state shape's
+seeds: a held list both run late and answered while held, buffers materialised by each of nodePosteriors, placementScores and
+nodePatternLikelihoods, generator and epoch calls, a demoted folded tip, models decomposed on the device — every one of these counters
+is reached at these sizes.
+
+Every sequence prints its wall time.  Measured on an MI355X, in one run, per sequence (200 .. 226 calls, three instances): extensions
+0.06 .. 0.16 s (0.35 s for the first of the process), queries 0.04 .. 0.17 s — the 61-state shape is the slowest of both, 0.16 / 0.17 s.
 """
 import collections
 import os
+import time
 
 import numpy as np
 import pytest
 
 import beast_mcmc_amd as bm
 import call_sequences as cs
-from test_call_sequences_host import CASES, CASES_EXT, SEEDS, SEEDS_EXT, SHAPES, SHAPES_EXT, case_id, records
+from test_call_sequences_host import CASES, CASES_EXT, CASES_Q, SEEDS, SEEDS_EXT, SHAPES, SHAPES_EXT, case_id, records
 
 pytestmark = pytest.mark.gpu
 
 TWIN_ENV = {"BEAGLE_MI355_COPY_ENGINE_UPLOADS": "1", "BEAGLE_MI355_NO_PLAN_CACHE": "1"}
 READ_ONLY = ("getTransitionMatrix", "getLogScaleFactors", "getSiteLogLikelihoods", "getPartials", "getPartialsBatch",
              "calculateEdgeDifferentials", "calculateCrossProductDifferentials")
-RETURNS_VALUES = ("sampleAncestralStates", "sampleMarkovJumps", "simulateSequences", "nodeHeightDerivatives", "getEigenDecomposition")
+RETURNS_VALUES = ("sampleAncestralStates", "sampleMarkovJumps", "simulateSequences", "nodeHeightDerivatives", "getEigenDecomposition",
+                  "nodePosteriors", "nodePatternLikelihoods", "placementScores")
 NO_IMPLEMENTATION = -7
 
 
@@ -80,17 +97,24 @@ def fail(what, shape, seed, step, recs, tmp_path, profile="base"):
                          % (shape, seed, step, cs.describe(recs[step]), what, path, step))
 
 
-def counters(b):
+def counters(b, queries=False):
+    """`queries`: what the stats getters of the query profile's five calls report as well (not on the sharded handle)"""
     info, grad = b.walkLaunchInfo(), b.gradientStats()
-    return {"rootFusedCount": b.rootFusedCount(), "sitePrefetchCount": b.sitePrefetchCount(), "ticket_walks": info["ticket_walks"],
-            "slice_accumulations": info["slice_accumulations"], "held_answered": grad["fused"] + grad["walked"], "late": grad["late"],
-            "walks": b.walkStats()["walks"], "eigen_calls": b.eigenStats()["calls"], "demotions": b.tipEmissionStats()["demotions"]}
+    out = {"rootFusedCount": b.rootFusedCount(), "sitePrefetchCount": b.sitePrefetchCount(), "ticket_walks": info["ticket_walks"],
+           "slice_accumulations": info["slice_accumulations"], "held_answered": grad["fused"] + grad["walked"], "late": grad["late"],
+           "walks": b.walkStats()["walks"], "eigen_calls": b.eigenStats()["calls"], "demotions": b.tipEmissionStats()["demotions"]}
+    if queries:
+        out.update({"generator_calls": b.generatorStats()["calls"], "epoch_calls": b.epochStats()["calls"],
+                    "posteriors_materialised": b.nodePosteriorStats()["materialised"], "placement_materialised": b.placementStats()["materialised"],
+                    "nodepattern_materialised": b.nodePatternStats()["materialised"]})
+    return out
 
 
 def lockstep(shape, seed, oracle_lib, tmp_path, sharded=False, profile="base"):
     """-> the default engine's counters at the end of the sequence"""
     recs = records(shape, seed, profile)
     instances = []
+    started = time.perf_counter()
     try:
         if sharded:
             g = len(bm.beagle.engine().resource_list()) - 2
@@ -135,13 +159,13 @@ def lockstep(shape, seed, oracle_lib, tmp_path, sharded=False, profile="base"):
                 worst[kind] = max(worst[kind], d) if d == d else d
                 if not d <= cs.BOUND:
                     fail("read %d (%s): engine against oracle %.3e, bound %.0e" % (k, kind, d, cs.BOUND), shape, seed, step, recs, tmp_path, profile)
-        print("shape %s seed %d%s%s: largest deviation from the oracle by kind of read: %s%s"
-              % (shape, seed, ", sharded" if sharded else "", "" if profile == "base" else ", " + profile,
-                 ", ".join("%s %.1e" % kv for kv in sorted(worst.items())),
+        print("shape %s seed %d%s%s: %d calls in %.2f s; largest deviation from the oracle by kind of read: %s%s"
+              % (shape, seed, ", sharded" if sharded else "", "" if profile == "base" else ", " + profile, len(recs),
+                 time.perf_counter() - started, ", ".join("%s %.1e" % kv for kv in sorted(worst.items())),
                  "; %d of %d (sampler call, pattern) pairs undecided" % (undecided, pairs) if pairs else ""))
         if undecided > cs.UNDECIDED_CAP * pairs:
             fail("%d of %d (sampler call, pattern) pairs undecided" % (undecided, pairs), shape, seed, len(recs) - 1, recs, tmp_path, profile)
-        return counters(eng)
+        return counters(eng, queries=(profile == "queries" and not sharded))
     finally:
         for b in instances:
             b.finalize()
@@ -207,3 +231,36 @@ def test_the_extension_sequences_reach_the_deferral_decisions(shape, oracle_lib,
 @pytest.mark.parametrize("seed", [1, 2])
 def test_extension_calls_sharded_handle_and_oracle_in_lockstep(seed, oracle_lib, tmp_path):
     lockstep((4, 4, 12, 130), seed, oracle_lib, tmp_path, sharded=True, profile="extensions")
+
+
+# ---- profile "queries": the five entry points merged after the extension profile, in the generated orders -------------------------
+_counters_q = {}
+
+
+@pytest.mark.parametrize("case", CASES_Q, ids=case_id)
+def test_query_calls_engine_twin_and_oracle_in_lockstep(case, oracle_lib, tmp_path):
+    shape, seed = case
+    _counters_q[case] = None
+    _counters_q[case] = lockstep(shape, seed, oracle_lib, tmp_path, profile="queries")
+
+
+@pytest.mark.parametrize("shape", [s for s in SHAPES_EXT if s[0] == 4], ids=lambda s: "S%d-C%d-T%d-P%d" % s)
+def test_the_query_sequences_reach_the_deferral_decisions(shape, oracle_lib, tmp_path):
+    """Summed over a 4-state shape's seeds: a held pre-order list was both run by a later call and answered while held around the
+    new calls; nodePosteriors, placementScores and nodePatternLikelihoods each materialised buffers that the walk had left unstored;
+    the generator call and the epoch call ran; a folded tip was demoted; models were decomposed on the device."""
+    total = collections.Counter()
+    for seed in SEEDS_EXT[shape]:
+        if (shape, seed) not in _counters_q:
+            _counters_q[(shape, seed)] = lockstep(shape, seed, oracle_lib, tmp_path, profile="queries")
+        total.update(_counters_q[(shape, seed)] or {})
+    print("shape %s, queries: %s" % (shape, dict(total)))
+    for key in ("late", "held_answered", "posteriors_materialised", "placement_materialised", "nodepattern_materialised", "generator_calls",
+                "epoch_calls", "demotions", "eigen_calls"):
+        assert total[key] > 0, (key, dict(total))
+
+
+@pytest.mark.parametrize("seed", [1, 2])
+def test_query_calls_sharded_handle_and_oracle_in_lockstep(seed, oracle_lib, tmp_path):
+    """placementScores answers NO_IMPLEMENTATION on the sharded handle before it changes anything and is left out; the four others run."""
+    lockstep((4, 4, 12, 130), seed, oracle_lib, tmp_path, sharded=True, profile="queries")
