@@ -349,11 +349,8 @@ int beagleBastaUpdatePartials(int instance, const int* operations, int operation
         HIP_TRY(hipEventRecord(b->sent, s));
         HIP_TRY(hipMemsetAsync(b->dTickets.p, 0, (size_t)n * sizeof(unsigned), s));
     }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (timeThisCall(in)) {
-        { int rce = nextTimerEvents(in, &e0, &e1); if (rce) return rce; }
-        HIP_TRY(hipEventRecord(e0, s));
-    }
+    CallTimer timer(in);
+    rc = timer.start(); if (rc) return rc;
     int launches = 0;
     if (forest) {
         mi355::launchBastaChains(s, b->dOps.as<int>(), b->dLink.as<int>(), b->dLink.as<int>() + (size_t)2 * n, nLeaves, b->dTickets.as<unsigned>(), in->matrices, b->vectors, sizes, coalescent, in->S);
@@ -368,8 +365,7 @@ int beagleBastaUpdatePartials(int instance, const int* operations, int operation
         }
         if (n > 0) b->statIntervalCalls++;
     }
-    if (e1 && launches > 0) { HIP_TRY(hipEventRecord(e1, s)); in->pendingLaunches += launches; }
-    else if (e1) { in->eventsUsed--; in->timedCalls--; }
+    rc = timer.stop(launches); if (rc) return rc;
     HIP_TRY(hipGetLastError());
     return BEAGLE_SUCCESS;
 }
@@ -481,18 +477,14 @@ int beagleBastaSampleStates(int instance, const int* operations, int operationCo
     uint8_t* dStage = L.stage.at(base);
     HIP_TRY(hipMemsetAsync(base + L.occupancy.offset, 0, L.bytes() - L.occupancy.offset, s));      // counters and the error word
     long chunks = 0;
-    const bool timed = timeThisCall(in);
+    CallTimer timer(in);
     for (size_t r0 = 0; r0 < R; r0 += chunk, chunks++) {
         a.r0 = (int)r0; a.count = (int)std::min(chunk, R - r0);
         HIP_TRY(hipMemsetAsync(a.states, 0xFF, L.states.bytes(), s));
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (timed) {                                         // (a timed call: every chunk's launches, not its copy-out)
-            { int rce = nextTimerEvents(in, &e0, &e1); if (rce) return rce; }
-            HIP_TRY(hipEventRecord(e0, s));
-        }
+        rc = timer.start(); if (rc) return rc;               // (a timed call: a pair around every chunk's launches, not its copy-out)
         for (int lv = 0; lv < levels; lv++)
             mi355::launchBastaStates(s, a, b->levelStart[lv], b->levelStart[lv + 1] - b->levelStart[lv]);
-        if (e1) { HIP_TRY(hipEventRecord(e1, s)); in->pendingLaunches += levels; }
+        rc = timer.stop(levels); if (rc) return rc;
         HIP_TRY(hipGetLastError());
         if (outStates) {
             mi355::launchBastaStatesTranspose(s, a.states, (int)V, (int)chunk, a.count, dStage);
@@ -570,18 +562,15 @@ int beagleBastaGradient(int instance, const int* operations, int operationCount,
     a.adjoints = L.adjoints.at(base); a.w = L.w.at(base); a.parts = L.parts.at(base); a.out = L.out.at(base);
     a.S = S;
     const int levels = (int)b->levelStart.size() - 1;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (timeThisCall(in)) {
-        { int rce = nextTimerEvents(in, &e0, &e1); if (rce) return rce; }
-        HIP_TRY(hipEventRecord(e0, s));
-    }
+    CallTimer timer(in);
+    rc = timer.start(); if (rc) return rc;
     mi355::launchBastaReduce(s, a.ops, a.intervals, nIntervals, a.lengths, b->vectors, a.sizes, a.coalescent, efgh[0], efgh[1], efgh[2], efgh[3],
                              b->intervalLogL, b->intervalLogL + b->maxIntervals, S);
     HIP_TRY(hipMemsetAsync(a.adjoints, 0, L.adjoints.bytes(), s));           // (a vector the list does not touch, a root coalescence's dest)
     for (int lv = 0; lv < levels; lv++) mi355::launchBastaGradientSweep(s, a, b->levelStart[lv], b->levelStart[lv + 1] - b->levelStart[lv]);
     mi355::launchBastaGradientReduce(s, a, nIntervals);
     const int launches = levels + 4;                         // the levels, the two launches behind e, f, g, h and the two reductions
-    if (e1) { HIP_TRY(hipEventRecord(e1, s)); in->pendingLaunches += launches; }
+    rc = timer.stop(launches); if (rc) return rc;
     HIP_TRY(hipGetLastError());
     b->statGradientCalls++; b->statGradientLaunches = launches; b->statGradientLevels = levels;
     std::vector<double> out(entries), adjoints(outAdjoints ? V * S : 0);

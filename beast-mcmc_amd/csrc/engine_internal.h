@@ -452,7 +452,6 @@ struct Resources {
 extern const long GPU_FLAGS;
 Resources* resources();
 void setPairLayout(Instance* in);
-int executeHeldPre(Instance* in);
 int holdPreList(Instance* in, const int* ops, int count);
 bool supersedesHeld(Instance* in, const int* ops, int count);
 int ensureWalkDummies(Instance* in);
@@ -534,25 +533,51 @@ int demoteFoldedTips(Instance* in);                      // ... every folded tip
 void dropTipEmission(Instance* in, int tip);             // setTipStates / setTipPartials: the tip is the caller's again
 void freeTipEmissions(Instance* in);
 #define DEMOTE_FOLDED_TIPS(in) do { if ((in)->emis) { const int rcDemote__ = demoteFoldedTips(in); if (rcDemote__) return rcDemote__; } } while (0)
-// is this updatePartials call one the kernel timer brackets with an event pair?  (an event costs a barrier packet on the stream:
-// 6 us of an evaluation each — a sampled timer keeps that out of most of a timed region)
-inline bool timeThisCall(Instance* in) {
-    if (!in->timing) return false;
-    if (++in->timingTick < in->timingEvery) return false;
-    in->timingTick = 0;
-    in->timedCalls++;
-    return true;
-}
-// the next HIP-event pair of the kernel timer for a call timeThisCall said yes to (one is created when none is left)
-inline int nextTimerEvents(Instance* in, hipEvent_t* first, hipEvent_t* second) {
-    if (in->eventsUsed == in->events.size()) {
-        hipEvent_t a = nullptr, b = nullptr;
-        HIP_TRY(hipEventCreate(&a)); HIP_TRY(hipEventCreate(&b));
-        in->events.emplace_back(a, b);
+// The kernel timer's bracket around the launches of ONE call (beagleMi355KernelTimer): begin() in front of them, the first event in
+// front of the first launch (start(), or a callee that is handed first()), stop() behind the last one.  Whichever way the call ends,
+// error returns included, Instance::eventsUsed counts exactly the pairs with both events recorded and Instance::timedCalls the
+// calls that contributed one: a pair stopped without a launch, or never stopped, goes back.  live(in) is taken only when there is an
+// event to record (on an untimed call it would launch a walk that is being held back for the root call: PendingWalk).
+struct CallTimer {
+    explicit CallTimer(Instance* i) : in(i) {}
+    CallTimer(const CallTimer&) = delete; CallTimer& operator=(const CallTimer&) = delete;
+    ~CallTimer() { stop(0); if (counted && !pairs) in->timedCalls--; }
+    // Is this call one the timer brackets (an event costs a barrier packet on the stream: 6 us of an evaluation each — a sampled timer
+    // keeps that out of most of a timed region)?  Decided at the call's first begin(); if so, the next HIP-event pair of the instance
+    // (one is created when none is left).  A call that brackets its chunks one by one begins again per chunk: one counted call, a pair each.
+    int begin() {
+        if (!decided && in->timing && ++in->timingTick >= in->timingEvery) { in->timingTick = 0; in->timedCalls++; counted = true; }
+        decided = true;
+        if (!counted || e1) return 0;
+        if (in->eventsUsed == in->events.size()) {
+            hipEvent_t a = nullptr, b = nullptr;
+            HIP_TRY(hipEventCreate(&a)); HIP_TRY(hipEventCreate(&b));
+            in->events.emplace_back(a, b);
+        }
+        e0 = in->events[in->eventsUsed].first; e1 = in->events[in->eventsUsed].second; in->eventsUsed++;
+        return 0;
     }
-    *first = in->events[in->eventsUsed].first; *second = in->events[in->eventsUsed].second; in->eventsUsed++;
-    return 0;
-}
+    // the first event, once: handed to a callee that records it itself right in front of its launch (runPlan's recordBeforeWalk), or
+    // recorded here — what a loop over chunks calls in front of every chunk's first launch (it begins, where the caller has not)
+    hipEvent_t first() { hipEvent_t e = e0; e0 = nullptr; return e; }
+    int start() {
+        const int rc = begin(); if (rc) return rc;
+        if (hipEvent_t e = first()) HIP_TRY(hipEventRecord(e, live(in)));
+        return 0;
+    }
+    // behind the last launch: the second event and the launches the pair stands for; nothing was launched: the pair goes back
+    int stop(int launches) {
+        if (!e1) return 0;
+        if (launches > 0) { HIP_TRY(hipEventRecord(e1, live(in))); in->pendingLaunches += launches; pairs++; }
+        else in->eventsUsed--;
+        e0 = e1 = nullptr;
+        return 0;
+    }
+private:
+    Instance* const in;
+    hipEvent_t e0 = nullptr, e1 = nullptr;               // the pair in hand (e0: until it is handed out)
+    bool decided = false, counted = false; int pairs = 0;      // (pairs: of this call, with both events recorded)
+};
 
 // ---- the pattern walk (4 states) ------------------------------------------------------------------------------------
 // A partials buffer is "virtual" when its content is DEFINED instead of stored (planner.h VirtDef): a few steps over
@@ -608,6 +633,58 @@ int executeHeldPre(Instance* in);
 int edgeDifferentials(Instance* in, const int* postIdx, const int* preIdx, const int* dIdx, int wIdx, int count,
                       double* outDerivatives, double* outSum, double* outSumSquared);
 int crossProducts(Instance* in, const int* postIdx, const int* preIdx, int rateIdx, int wIdx, const double* lengths, int count, double* outSum);
+// ---- what a call reads as data must BE data: the partials buffers (valid indices) a call is about to read.  A buffer is stored;
+// unstored (defined by the 4-state walk: its definition keys are noted, in order of first appearance, each once); a compact tip, read
+// as states; a folded emission tip, which the caller demotes or does not read as data; or never written to: BEAGLE_ERROR_OUT_OF_RANGE.
+// materialize() gives the noted definitions real data in one materializeList.  Nothing changes before it: a list that fails leaves
+// the instance as it was.
+struct ReadSet {
+    explicit ReadSet(Instance* i) : in(i) {}
+    int post(int b) { return isCompactTip(in, b) || foldedTip(in, b) ? 0 : pre(b); }       // a post-order operand
+    // a pre-order operand: compact states are no partials (nor is a pre-order buffer ever a destination the walk leaves unstored: a
+    // caller that names an unstored post-order buffer here still reads real data)
+    int pre(int b) { return note(b) || (!isCompactTip(in, b) && in->partials[b]) ? 0 : (int)BEAGLE_ERROR_OUT_OF_RANGE; }
+    // b's definition keys if it is unstored (-> true): all that a caller needs that has classified b itself (an operand that an
+    // earlier operation of its own list writes is no error)
+    bool note(int b) {
+        if (!isVirt(in, b)) return false;
+        ofOne.clear(); in->planner.keysOf(b, ofOne);
+        for (int key : ofOne) noteKey(key);
+        return true;
+    }
+    // ... and a definition key the caller has from elsewhere (the planner's lists of who reads a tip or a scale buffer)
+    void noteKey(int key) {
+        if ((size_t)key >= noted.size()) noted.resize(std::max((size_t)key + 1, (size_t)in->partialsCount * in->planner.partitionCount()), 0);
+        if (!noted[(size_t)key]) { noted[(size_t)key] = 1; need.push_back(key); }
+    }
+    size_t keys() const { return need.size(); }            // distinct definitions noted so far
+    int materialize() { return materializeList(in, need); }
+private:
+    Instance* const in;
+    std::vector<int> need, ofOne; std::vector<char> noted;
+};
+// ... and where a descriptor finds such an operand once the read set is materialised: a post-order operand's partials or (*states)
+// compact states, a pre-order operand's partials.  Null: nothing there, the fill's BEAGLE_ERROR_OUT_OF_RANGE.
+inline const void* postOperand(const Instance* in, int b, int* states) {
+    *states = isCompactTip(in, b);
+    return *states ? (const void*)in->tipStates[b] : (const void*)in->partials[b];
+}
+inline const double* preOperand(const Instance* in, int b) { return isCompactTip(in, b) ? nullptr : in->partials[b]; }
+// What an entry point that reads pre- and post-order partials where they are calls once, behind its own checks and under
+// GET_INSTANCE_KEEP_PENDING; collect(ReadSet&) checks the call's indices and feeds the read set.  The whole list BEFORE anything changes
+// (a list that fails leaves the instance, and a held-back pre-order list, as they were); then the held list, which writes the pre-order
+// partials the call reads and gives its own unstored operands — the call's among them — real data; folded tips demoted (their partials
+// are read as data: engine_tipemission.cpp); the list again, for what is STILL unstored (*unstoredAtEntry: the first pass's distinct
+// definitions, what the ...Materialised statistics count); one materializeList.
+template <class Collect> int makeResident(Instance* in, Collect&& collect, long* unstoredAtEntry) {
+    ReadSet atEntry(in), reads(in);
+    int rc = collect(atEntry); if (rc) return rc;
+    *unstoredAtEntry = (long)atEntry.keys();
+    if (in->heldPre.held) { rc = executeHeldPre(in); if (rc) return rc; }
+    DEMOTE_FOLDED_TIPS(in);
+    rc = collect(reads); if (rc) return rc;
+    return reads.materialize();
+}
 
 // ---- engine_sampling.cpp
 // Where a device-side draw left its results (in->ancestralDev, scratch_layout.h ancestralLayout)

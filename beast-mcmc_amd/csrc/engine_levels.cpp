@@ -61,7 +61,7 @@ int runOperationsLevels(Instance* in, const int* ops, int count, int tuple, int 
         }
         std::vector<int> need;
         in->planner.mustMaterializeBefore(ops, count, tuple, need);
-        if (!need.empty()) { int rc = materializeList(in, need); if (rc) return rc; }
+        { int rc = materializeList(in, need); if (rc) return rc; }
     }
     auto cherryChild = [&](int c) -> size_t {                         // descriptor index of a virtual child
         const mi355::VirtStep& st = in->planner.definition(c).steps[0];
@@ -233,15 +233,15 @@ int runOperationsLevels(Instance* in, const int* ops, int count, int tuple, int 
     // launch per dependency level reading its slice.  With the kernel timer on, ONE HIP-event pair brackets
     // all level launches of the call (gaps between levels included — they are part of what the path costs).
     const size_t maxChunkOps = (RING_BYTES / 4) / sizeof(OpDesc);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (timeThisCall(in)) { int rce = nextTimerEvents(in, &e0, &e1); if (rce) return rce; }
+    CallTimer timer(in);
+    { int rce = timer.begin(); if (rce) return rce; }
     int launches = 0;
     for (int chunkBegin = 0; chunkBegin < launchCount;) {
         const int chunkEnd = (int)std::min<size_t>((size_t)launchCount, (size_t)chunkBegin + maxChunkOps);
         void* dChunk = nullptr;
         int rc = uploadTransient(in, &sorted[chunkBegin], (size_t)(chunkEnd - chunkBegin) * sizeof(OpDesc), &dChunk);
         if (rc) return rc;
-        if (e0 && chunkBegin == 0) HIP_TRY(hipEventRecord(e0, live(in)));
+        rc = timer.start(); if (rc) return rc;
         for (int l = 0; l <= maxLevel; l++) {
             const int begin = std::max(start[l], chunkBegin), end = std::min(start[l + 1], chunkEnd);
             if (begin >= end) continue;
@@ -261,8 +261,7 @@ int runOperationsLevels(Instance* in, const int* ops, int count, int tuple, int 
         }
         chunkBegin = chunkEnd;
     }
-    if (e1 && launches > 0) { HIP_TRY(hipEventRecord(e1, live(in))); in->pendingLaunches += launches; }
-    else if (e1) { in->eventsUsed--; in->timedCalls--; }       // nothing was launched: give the (unrecorded) event pair back
+    { int rce = timer.stop(launches); if (rce) return rce; }
     HIP_TRY(hipGetLastError());
     return foldCumulative(in, ops, count, tuple, globalCum);
 }
@@ -312,17 +311,16 @@ int runOperations(Instance* in, const int* ops, int count, int tuple, int global
         bool writes = false;
         for (int k = 0; k < count && !writes; k++) writes = ops[(size_t)k * tuple + 1] != BEAGLE_OP_NONE;
         if (!writes || in->walkTWrite) return runOperationsWalk(in, ops, count, tuple, globalCum);
-        std::vector<int> need;
+        ReadSet reads(in);                                   // (the level path checks the operands themselves: a child may be an earlier operation's destination)
         for (int k = 0; k < count; k++) {
             const int* op = ops + (size_t)k * tuple;
             if (badIndex(op[0], in->partialsCount) || badIndex(op[3], in->partialsCount) || badIndex(op[5], in->partialsCount)) return BEAGLE_ERROR_OUT_OF_RANGE;
-            if (isVirt(in, op[3])) in->planner.keysOf(op[3], need);
-            if (isVirt(in, op[5])) in->planner.keysOf(op[5], need);
+            reads.note(op[3]); reads.note(op[5]);
             // (the level path forgets a destination's definitions for ALL partitions; what another partition still defines there
             // has to exist before that)
-            if (in->partitionCount > 1 && isVirt(in, op[0])) in->planner.keysOf(op[0], need);
+            if (in->partitionCount > 1) reads.note(op[0]);
         }
-        if (!need.empty()) { int rc = materializeList(in, need); if (rc) return rc; }
+        { int rc = reads.materialize(); if (rc) return rc; }
     }
     return runOperationsLevels(in, ops, count, tuple, globalCum);
 }

@@ -10,22 +10,19 @@ using namespace mi355::eng;
 static int nodeHeightDerivatives(Instance* in, const int* nodes, const double* rates, int nodeCount, int wIdx, double* outFirst, double* outSecond) {
     if (in->partitionCount > 1 || in->S > 64 || in->basta) return BEAGLE_ERROR_NO_IMPLEMENTATION;
     if (badIndex(wIdx, in->eigenCount)) return BEAGLE_ERROR_OUT_OF_RANGE;
-    std::vector<int> need;
+    ReadSet reads(in);
     for (int r = 0; r < nodeCount; r++) {
         const int* nd = nodes + (size_t)8 * r;
         const int pre = nd[0], dI = nd[7];
-        if (badIndex(pre, in->partialsCount) || isCompactTip(in, pre) || (dI != -1 && badIndex(dI, in->matrixCount))) return BEAGLE_ERROR_OUT_OF_RANGE;
-        if (!in->partials[pre] && !isVirt(in, pre)) return BEAGLE_ERROR_OUT_OF_RANGE;              // a buffer nothing was ever written to
-        if (isVirt(in, pre)) in->planner.keysOf(pre, need);
+        if (badIndex(pre, in->partialsCount) || (dI != -1 && badIndex(dI, in->matrixCount))) return BEAGLE_ERROR_OUT_OF_RANGE;
+        if (int bad = reads.pre(pre)) return bad;
         for (int w = 0; w < 2; w++) {
             const int post = nd[1 + 3 * w], mat = nd[2 + 3 * w], dmat = nd[3 + 3 * w];
             if (badIndex(post, in->partialsCount) || badIndex(mat, in->matrixCount) || badIndex(dmat, in->matrixCount)) return BEAGLE_ERROR_OUT_OF_RANGE;
-            if (isCompactTip(in, post)) continue;
-            if (isVirt(in, post)) in->planner.keysOf(post, need);
-            else if (!in->partials[post]) return BEAGLE_ERROR_OUT_OF_RANGE;
+            if (int bad = reads.post(post)) return bad;
         }
     }
-    if (!need.empty()) { int rc = materializeList(in, need); if (rc) return rc; }
+    int rc = reads.materialize(); if (rc) return rc;
     const bool second = outSecond != nullptr, general = !(in->S == 4 && !in->tiled);
     const int nb = mi355::edgeBlocks(in->P);
     // nodes per chunk: the descriptors fit a quarter of the staging ring, the block sums 256 MiB, the general kernel's products 128 MiB
@@ -33,13 +30,12 @@ static int nodeHeightDerivatives(Instance* in, const int* nodes, const double* r
     chunk = std::min(chunk, std::max<size_t>(1, ((size_t)256 << 20) / ((size_t)(nb + 1) * 2 * sizeof(double))));
     const size_t productDoubles = general ? mi355::nodeHeightProductDoubles(1, in->S, in->C) : 0;
     if (general) chunk = std::min(chunk, std::max<size_t>(1, ((size_t)128 << 20) / (productDoubles * sizeof(double))));
-    int rc = ensureEdgeScratch(in, chunk * (size_t)(nb + 1) * 2 * sizeof(double)); if (rc) return rc;
+    rc = ensureEdgeScratch(in, chunk * (size_t)(nb + 1) * 2 * sizeof(double)); if (rc) return rc;
     double *dBlock = in->edgeScratch.as<double>(), *dSums = dBlock + chunk * nb * 2;
     ScopedDevice products(in);                                      // (the general kernel's; freed, behind a drained stream, wherever the call ends)
     if (general) { rc = products.alloc(chunk * productDoubles * sizeof(double)); if (rc) return rc; }
     double* const dProducts = products.as<double>();
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (timeThisCall(in)) { int rce = nextTimerEvents(in, &e0, &e1); if (rce) return rce; }
+    CallTimer timer(in);
     std::vector<mi355::NodeHeightJob> jobs;
     std::vector<double> sums;
     bool finite = true;
@@ -52,12 +48,9 @@ static int nodeHeightDerivatives(Instance* in, const int* nodes, const double* r
             const double* rt = rates + 3 * (b + e);
             mi355::NodeHeightJob& jb = jobs[e];
             memset(&jb, 0, sizeof(jb));
-            jb.pre = in->partials[nd[0]];
-            const bool stJ = isCompactTip(in, nd[1]), stK = isCompactTip(in, nd[4]);
-            jb.postJ = stJ ? (const void*)in->tipStates[nd[1]] : (const void*)in->partials[nd[1]];
-            jb.postK = stK ? (const void*)in->tipStates[nd[4]] : (const void*)in->partials[nd[4]];
+            jb.pre = preOperand(in, nd[0]);
+            jb.postJ = postOperand(in, nd[1], &jb.statesJ); jb.postK = postOperand(in, nd[4], &jb.statesK);
             if (!jb.pre || !jb.postJ || !jb.postK) { rc = BEAGLE_ERROR_OUT_OF_RANGE; break; }
-            jb.statesJ = stJ; jb.statesK = stK;
             jb.matJ = nd[2]; jb.dJ = nd[3]; jb.matK = nd[5]; jb.dK = nd[6]; jb.dI = nd[7];
             jb.slot = (int)e;
             jb.rJ = rt[0]; jb.rK = rt[1]; jb.rI = nd[7] < 0 ? 0.0 : rt[2];
@@ -65,7 +58,7 @@ static int nodeHeightDerivatives(Instance* in, const int* nodes, const double* r
         if (rc) break;
         void* dJobs = nullptr;
         rc = uploadTransient(in, jobs.data(), m * sizeof(mi355::NodeHeightJob), &dJobs); if (rc) break;
-        if (e0 && b == 0 && hipEventRecord(e0, live(in)) != hipSuccess) { rc = BEAGLE_ERROR_GENERAL; break; }
+        rc = timer.start(); if (rc) break;
         const double* weights = in->weights + (size_t)wIdx * in->C;
         if (!general)
             mi355::launchNodeHeight4(live(in), (const mi355::NodeHeightJob*)dJobs, (int)m, in->matrices, weights, in->patternWeights, dBlock, in->P, in->C, second);
@@ -73,10 +66,7 @@ static int nodeHeightDerivatives(Instance* in, const int* nodes, const double* r
                                           in->P, in->S, in->C, in->tiled, second)) { rc = BEAGLE_ERROR_GENERAL; break; }
         mi355::launchEdgeFinal(live(in), dBlock, (int)m, in->P, dSums);
         launches += general ? (second ? 4 : 3) : 2;
-        if (e1 && b + m >= (size_t)nodeCount) {
-            if (hipEventRecord(e1, live(in)) != hipSuccess) { rc = BEAGLE_ERROR_GENERAL; break; }
-            in->pendingLaunches += launches; e1 = nullptr;
-        }
+        if (b + m >= (size_t)nodeCount) { rc = timer.stop(launches); if (rc) break; }
         sums.resize(m * 2);
         rc = download(in, sums.data(), dSums, sums.size() * sizeof(double)); if (rc) break;
         for (size_t e = 0; e < m; e++) {
@@ -84,7 +74,6 @@ static int nodeHeightDerivatives(Instance* in, const int* nodes, const double* r
             if (outSecond) { outSecond[b + e] = sums[2 * e + 1]; finite = finite && std::isfinite(sums[2 * e + 1]); }
         }
     }
-    if (e1) { in->eventsUsed--; in->timedCalls--; }                 // the call failed before its last launch: give the event pair back
     products.reset();
     if (rc) return rc;
     if (hipGetLastError() != hipSuccess) return BEAGLE_ERROR_GENERAL;

@@ -30,7 +30,7 @@ int nodePattern(Instance* in, const int* nodes, const double* logWeights, int no
     if (in->partitionCount > 1 || in->basta || in->S > 255) return BEAGLE_ERROR_NO_IMPLEMENTATION;
     if (badIndex(wIdx, in->eigenCount) || badIndex(fIdx, in->eigenCount) || badIndex(deathState, in->S)) return BEAGLE_ERROR_OUT_OF_RANGE;
     if (!postOrder(nodes, nodeCount) || !in->patternWeights) return BEAGLE_ERROR_OUT_OF_RANGE;
-    std::vector<int> need;
+    ReadSet reads(in);
     bool heldWritesOne = false;
     for (int r = 0; r < nodeCount; r++) {
         const int b = nodes[4 * r], sc = nodes[4 * r + 1];
@@ -38,14 +38,13 @@ int nodePattern(Instance* in, const int* nodes, const double* logWeights, int no
         if (badIndex(b, in->partialsCount)) return BEAGLE_ERROR_OUT_OF_RANGE;
         if (sc != -1 && badIndex(sc, in->scaleCount)) return BEAGLE_ERROR_OUT_OF_RANGE;
         if (!tip && isCompactTip(in, b)) return BEAGLE_ERROR_OUT_OF_RANGE;
-        if (isVirt(in, b)) in->planner.keysOf(b, need);
-        else if (!isCompactTip(in, b) && !in->partials[b] && !foldedTip(in, b)) return BEAGLE_ERROR_OUT_OF_RANGE;      // a buffer nothing was ever written to
+        if (int bad = reads.post(b)) return bad;
         heldWritesOne = heldWritesOne || heldWrites(in, b);
     }
     // a held-back pre-order list stays held unless it writes what this call reads (materialising runs programs of its own: it goes first)
-    if (in->heldPre.held && (heldWritesOne || !need.empty())) { int rc = executeHeldPre(in); if (rc) return rc; }
+    if (in->heldPre.held && (heldWritesOne || reads.keys())) { int rc = executeHeldPre(in); if (rc) return rc; }
     DEMOTE_FOLDED_TIPS(in);
-    if (!need.empty()) { int rc = materializeList(in, need); if (rc) return rc; }
+    { int rc = reads.materialize(); if (rc) return rc; }
 
     // scratch slots: a row's is free again once its parent has read it (the parent may take it over: it reads before it writes)
     std::vector<mi355::NodePatternRow> rows(nodeCount);
@@ -103,7 +102,7 @@ int nodePattern(Instance* in, const int* nodes, const double* logWeights, int no
     long empty = 0;
     for (size_t p = 0; p < P; p++) if (back[p] == -INFINITY) empty++;
     in->statNodePatternCalls++; in->statNodePatternRows += nodeCount; in->statNodePatternEmpty += empty;
-    in->statNodePatternMaterialised += (long)need.size();
+    in->statNodePatternMaterialised += (long)reads.keys();
     return BEAGLE_SUCCESS;
 }
 

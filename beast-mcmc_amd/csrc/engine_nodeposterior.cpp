@@ -20,28 +20,17 @@ int nodePosteriors(Instance* in, const int* nodes, int nodeCount, int wIdx, size
                    double* totals, bool* fpError) {
     if (in->partitionCount > 1 || in->basta || in->S > 255) return BEAGLE_ERROR_NO_IMPLEMENTATION;
     if (badIndex(wIdx, in->eigenCount) || (totals && !in->patternWeights)) return BEAGLE_ERROR_OUT_OF_RANGE;
-    // the whole list before anything changes: every index, and the operands the 4-state walk left unstored
-    auto unstored = [&](std::vector<int>& need) -> int {
+    long unstoredAtEntry = 0;
+    int rc = makeResident(in, [&](ReadSet& reads) -> int {
         for (int r = 0; r < nodeCount; r++) {
             const int post = nodes[2 * r], pre = nodes[2 * r + 1];
-            if (badIndex(post, in->partialsCount) || badIndex(pre, in->partialsCount) || isCompactTip(in, pre)) return BEAGLE_ERROR_OUT_OF_RANGE;
-            if (isVirt(in, pre)) in->planner.keysOf(pre, need);                                    // (no pre-order destination is: a caller that names an unstored post-order buffer here still reads real data)
-            else if (!in->partials[pre]) return BEAGLE_ERROR_OUT_OF_RANGE;                          // a buffer nothing was ever written to
-            if (foldedTip(in, post) || isCompactTip(in, post)) continue;
-            if (isVirt(in, post)) in->planner.keysOf(post, need);
-            else if (!in->partials[post]) return BEAGLE_ERROR_OUT_OF_RANGE;
+            if (badIndex(post, in->partialsCount) || badIndex(pre, in->partialsCount)) return BEAGLE_ERROR_OUT_OF_RANGE;
+            if (int bad = reads.pre(pre)) return bad;
+            if (int bad = reads.post(post)) return bad;
         }
-        std::sort(need.begin(), need.end());                                                        // (a node listed twice counts once)
-        need.erase(std::unique(need.begin(), need.end()), need.end());
         return 0;
-    };
-    std::vector<int> atEntry, need;
-    int rc = unstored(atEntry); if (rc) return rc;
-    // a held-back pre-order list writes the pre(i): it runs now, and gives its own unstored operands — ours among them — real data
-    if (in->heldPre.held) { rc = executeHeldPre(in); if (rc) return rc; }
-    DEMOTE_FOLDED_TIPS(in);                     // (tips' partials are read as data: engine_tipemission.cpp)
-    rc = unstored(need); if (rc) return rc;
-    if (!need.empty()) { rc = materializeList(in, need); if (rc) return rc; }
+    }, &unstoredAtEntry);
+    if (rc) return rc;
 
     const size_t R = (size_t)nodeCount, P = (size_t)in->P, S = (size_t)in->S, C = (size_t)in->C, blocks = (size_t)mi355::edgeBlocks(in->P);
     const bool full = out.posteriors != nullptr, map = out.mapStates || out.mapProbabilities, wantTotals = totals != nullptr;
@@ -58,8 +47,7 @@ int nodePosteriors(Instance* in, const int* nodes, int nodeCount, int wIdx, size
     uint8_t* dStates = L.mapStates.at(base);
     unsigned* dError = L.error.at(base);
     HIP_TRY(hipMemsetAsync(dError, 0, sizeof(unsigned), live(in)));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (timeThisCall(in)) { int rce = nextTimerEvents(in, &e0, &e1); if (rce) return rce; }
+    CallTimer timer(in);
     const double* weights = in->weights + (size_t)wIdx * in->C;
     std::vector<mi355::NodePosteriorRow> rows;
     int launches = 0;
@@ -67,18 +55,16 @@ int nodePosteriors(Instance* in, const int* nodes, int nodeCount, int wIdx, size
         const size_t m = std::min(chunk, R - b);
         rows.assign(m, mi355::NodePosteriorRow{});
         for (size_t e = 0; e < m; e++) {
-            const int post = nodes[2 * (b + e)], pre = nodes[2 * (b + e) + 1];
             mi355::NodePosteriorRow& row = rows[e];
-            row.statesPost = isCompactTip(in, post);
-            row.post = row.statesPost ? (const void*)in->tipStates[post] : (const void*)in->partials[post];
-            row.pre = in->partials[pre];
+            row.post = postOperand(in, nodes[2 * (b + e)], &row.statesPost);
+            row.pre = preOperand(in, nodes[2 * (b + e) + 1]);
             row.slot = (int)e;
             if (!row.post || !row.pre) { rc = BEAGLE_ERROR_OUT_OF_RANGE; break; }
         }
         if (rc) break;
         void* dRows = nullptr;
         rc = uploadTransient(in, rows.data(), m * sizeof(mi355::NodePosteriorRow), &dRows); if (rc) break;
-        if (e0 && b == 0 && hipEventRecord(e0, live(in)) != hipSuccess) { rc = BEAGLE_ERROR_GENERAL; break; }
+        rc = timer.start(); if (rc) break;
         if (full || map || wantTotals) {
             if (!mi355::launchNodePosteriors(live(in), (const mi355::NodePosteriorRow*)dRows, (int)m, weights, in->patternWeights, in->P, in->S,
                                              in->C, in->tiled, dPost, out.mapStates ? dStates : nullptr, out.mapProbabilities ? dProb : nullptr,
@@ -91,10 +77,7 @@ int nodePosteriors(Instance* in, const int* nodes, int nodeCount, int wIdx, size
             launches++;
         }
         if (hipGetLastError() != hipSuccess) { rc = BEAGLE_ERROR_GENERAL; break; }
-        if (e1 && b + m >= R) {
-            if (hipEventRecord(e1, live(in)) != hipSuccess) { rc = BEAGLE_ERROR_GENERAL; break; }
-            in->pendingLaunches += launches; e1 = nullptr;
-        }
+        if (b + m >= R) { rc = timer.stop(launches); if (rc) break; }
         // this launch's rows to theirs of the outputs; the next launch overwrites the scratch, so the last copy is waited for
         // (the states: linear where the instance has every column, as copyStagedRows does — a strided copy goes row by row)
         if (out.mapStates && (globalP == P ? hipMemcpyAsync(out.mapStates + b * P, dStates, m * P, hipMemcpyDeviceToHost, live(in))
@@ -107,12 +90,11 @@ int nodePosteriors(Instance* in, const int* nodes, int nodeCount, int wIdx, size
         if (full) { rc = copyStagedRows(in, dPost, m, b, b + m, 1, R, P * S, globalP * S, pOffset * S, out.posteriors); if (rc) break; }
         if (hipStreamSynchronize(live(in)) != hipSuccess) { rc = BEAGLE_ERROR_GENERAL; break; }
     }
-    if (e1) { in->eventsUsed--; in->timedCalls--; }                 // the call failed before its last launch: give the event pair back
     if (rc) return rc;
     unsigned err = 0;
     rc = download(in, &err, dError, sizeof(err)); if (rc) return rc;
     if (err) *fpError = true;
-    in->statNodePosteriorCalls++; in->statNodePosteriorRows += nodeCount; in->statNodePosteriorMaterialised += (long)atEntry.size();
+    in->statNodePosteriorCalls++; in->statNodePosteriorRows += nodeCount; in->statNodePosteriorMaterialised += unstoredAtEntry;
     in->statNodePosteriorLaunches += launches;
     return BEAGLE_SUCCESS;
 }

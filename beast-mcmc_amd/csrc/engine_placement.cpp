@@ -24,35 +24,23 @@ int placementScores(Instance* in, const int* cands, int candidateCount, int wIdx
     for (int i = 0; i < siteCount; i++) if (sitePatterns[i] < -1 || sitePatterns[i] >= in->P) return BEAGLE_ERROR_OUT_OF_RANGE;
     for (size_t i = 0, n = (size_t)queryCount * siteCount; i < n; i++)
         if (queryCodes[i] >= codeCount && queryCodes[i] != 255) return BEAGLE_ERROR_OUT_OF_RANGE;
-    // the whole list before anything changes: every index, and the operands the 4-state walk left unstored
-    auto unstored = [&](std::vector<int>& need) -> int {
+    long unstoredAtEntry = 0;
+    int rc = makeResident(in, [&](ReadSet& reads) -> int {
         for (int k = 0; k < candidateCount; k++) {
             const int* c = cands + FIELDS * k;
             const int pre = c[PARENT_PRE], sib = c[SIBLING_POST], mSib = c[SIBLING_MATRIX], child = c[CHILD_POST];
-            if (badIndex(pre, in->partialsCount) || isCompactTip(in, pre) || badIndex(child, in->partialsCount)) return BEAGLE_ERROR_OUT_OF_RANGE;
+            if (badIndex(pre, in->partialsCount) || badIndex(child, in->partialsCount)) return BEAGLE_ERROR_OUT_OF_RANGE;
             if ((sib == BEAGLE_OP_NONE) != (mSib == BEAGLE_OP_NONE)) return BEAGLE_ERROR_OUT_OF_RANGE;
             if (sib != BEAGLE_OP_NONE && (badIndex(sib, in->partialsCount) || badIndex(mSib, in->matrixCount))) return BEAGLE_ERROR_OUT_OF_RANGE;
             if (c[UPPER_MATRIX] != BEAGLE_OP_NONE && badIndex(c[UPPER_MATRIX], in->matrixCount)) return BEAGLE_ERROR_OUT_OF_RANGE;
             if (badIndex(c[LOWER_MATRIX], in->matrixCount) || badIndex(c[PENDANT_MATRIX], in->matrixCount)) return BEAGLE_ERROR_OUT_OF_RANGE;
-            if (isVirt(in, pre)) in->planner.keysOf(pre, need);
-            else if (!in->partials[pre]) return BEAGLE_ERROR_OUT_OF_RANGE;                          // a buffer nothing was ever written to
-            for (int post : {sib, child}) {
-                if (post == BEAGLE_OP_NONE || foldedTip(in, post) || isCompactTip(in, post)) continue;
-                if (isVirt(in, post)) in->planner.keysOf(post, need);
-                else if (!in->partials[post]) return BEAGLE_ERROR_OUT_OF_RANGE;
-            }
+            if (int bad = reads.pre(pre)) return bad;
+            if (sib != BEAGLE_OP_NONE) if (int bad = reads.post(sib)) return bad;
+            if (int bad = reads.post(child)) return bad;
         }
-        std::sort(need.begin(), need.end());                                                        // (a buffer listed twice counts once)
-        need.erase(std::unique(need.begin(), need.end()), need.end());
         return 0;
-    };
-    std::vector<int> atEntry, need;
-    int rc = unstored(atEntry); if (rc) return rc;
-    // a held-back pre-order list writes the parents' pre-order partials: it runs now
-    if (in->heldPre.held) { rc = executeHeldPre(in); if (rc) return rc; }
-    DEMOTE_FOLDED_TIPS(in);                     // (tips' partials are read as data: engine_tipemission.cpp)
-    rc = unstored(need); if (rc) return rc;
-    if (!need.empty()) { rc = materializeList(in, need); if (rc) return rc; }
+    }, &unstoredAtEntry);
+    if (rc) return rc;
 
     const size_t K = (size_t)candidateCount, Q = (size_t)queryCount, P = (size_t)in->P, S = (size_t)in->S, C = (size_t)in->C, X = (size_t)codeCount;
     const size_t sites = (size_t)siteCount, segments = (size_t)mi355::placementSegments(in->P, codeCount);
@@ -83,9 +71,8 @@ int placementScores(Instance* in, const int* cands, int candidateCount, int wIdx
     rc = upload(in, dSitePatterns, sitePatterns, sites * sizeof(int)); if (rc) return rc;
     rc = upload(in, dSlots, slots.data(), slots.size() * sizeof(int)); if (rc) return rc;
     HIP_TRY(hipMemsetAsync(dError, 0, sizeof(unsigned), live(in)));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (timeThisCall(in)) { int rce = nextTimerEvents(in, &e0, &e1); if (rce) return rce; }
-    if (e0 && hipEventRecord(e0, live(in)) != hipSuccess) rc = BEAGLE_ERROR_GENERAL;
+    CallTimer timer(in);
+    rc = timer.start();
     const double* weights = in->weights + (size_t)wIdx * in->C;
     const size_t SS = C * S * S;
     int launches = 0;
@@ -109,15 +96,13 @@ int placementScores(Instance* in, const int* cands, int candidateCount, int wIdx
         for (size_t e = 0; e < m; e++) {
             const int* c = cands + FIELDS * (b + e);
             mi355::PlacementCandidate& row = rows[e];
-            row.pre = in->partials[c[PARENT_PRE]];
+            row.pre = preOperand(in, c[PARENT_PRE]);
             if (c[SIBLING_POST] != BEAGLE_OP_NONE) {
-                row.sibStates = isCompactTip(in, c[SIBLING_POST]);
-                row.sib = row.sibStates ? (const void*)in->tipStates[c[SIBLING_POST]] : (const void*)in->partials[c[SIBLING_POST]];
+                row.sib = postOperand(in, c[SIBLING_POST], &row.sibStates);
                 row.mSib = in->matrices + SS * c[SIBLING_MATRIX];
                 if (!row.sib) rc = BEAGLE_ERROR_OUT_OF_RANGE;
             }
-            row.childStates = isCompactTip(in, c[CHILD_POST]);
-            row.child = row.childStates ? (const void*)in->tipStates[c[CHILD_POST]] : (const void*)in->partials[c[CHILD_POST]];
+            row.child = postOperand(in, c[CHILD_POST], &row.childStates);
             row.mUp = c[UPPER_MATRIX] == BEAGLE_OP_NONE ? nullptr : in->matrices + SS * c[UPPER_MATRIX];
             row.mLow = in->matrices + SS * c[LOWER_MATRIX];
             row.pendant = pendantOf[c[PENDANT_MATRIX]];
@@ -139,22 +124,18 @@ int placementScores(Instance* in, const int* cands, int candidateCount, int wIdx
             mi355::launchPlacementScores(live(in), dCounts, dTable, (int)n, (int)m, in->P, codeCount, dPartial, dScores);
             launches += 2;
             if (hipGetLastError() != hipSuccess) { rc = BEAGLE_ERROR_GENERAL; break; }
-            if (e1 && b + m >= K && q0 + n >= Q) {
-                if (hipEventRecord(e1, live(in)) != hipSuccess) { rc = BEAGLE_ERROR_GENERAL; break; }
-                in->pendingLaunches += launches; e1 = nullptr;
-            }
+            if (b + m >= K && q0 + n >= Q) { rc = timer.stop(launches); if (rc) break; }
             // this launch's block of the scores; the next launch overwrites the scratch, so the copy is waited for
             if (hipMemcpy2DAsync(outScores + q0 * K + b, K * sizeof(double), dScores, m * sizeof(double), m * sizeof(double), n,
                                  hipMemcpyDeviceToHost, live(in)) != hipSuccess) { rc = BEAGLE_ERROR_GENERAL; break; }
             if (hipStreamSynchronize(live(in)) != hipSuccess) { rc = BEAGLE_ERROR_GENERAL; break; }
         }
     }
-    if (e1) { in->eventsUsed--; in->timedCalls--; }                 // the call failed before its last launch: give the event pair back
     if (rc) return rc;
     unsigned err = 0;
     rc = download(in, &err, dError, sizeof(err)); if (rc) return rc;
     if (err) *fpError = true;
-    in->statPlacementCalls++; in->statPlacementCandidates += candidateCount; in->statPlacementMaterialised += (long)atEntry.size();
+    in->statPlacementCalls++; in->statPlacementCandidates += candidateCount; in->statPlacementMaterialised += unstoredAtEntry;
     in->statPlacementLaunches += launches;
     return BEAGLE_SUCCESS;
 }

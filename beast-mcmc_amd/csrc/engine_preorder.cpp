@@ -82,13 +82,9 @@ static bool walkableDefinition(const Instance* in, int buf) {
 }
 // the held list is about to run on kernels that read real partials: its unstored operands get theirs
 static int materializeHeldOperands(Instance* in) {
-    if (!in->virt) return 0;
-    std::vector<int> need;
-    for (const Instance::HeldPreNode& nd : in->heldPre.nodes) {
-        if (isVirt(in, nd.postA)) in->planner.keysOf(nd.postA, need);
-        if (isVirt(in, nd.postB)) in->planner.keysOf(nd.postB, need);
-    }
-    return need.empty() ? 0 : materializeList(in, need);
+    ReadSet reads(in);
+    for (const Instance::HeldPreNode& nd : in->heldPre.nodes) { reads.note(nd.postA); reads.note(nd.postB); }
+    return reads.materialize();
 }
 
 // Enqueue a pre-order op list (7-int tuples {pre(child), writeScale, readScale, pre(parent), matrix(child), post(sibling),
@@ -127,7 +123,8 @@ int runPreOperations(Instance* in, const int* ops, int count, int globalCum, boo
     // everything these ops read must be real data — except, for a list that is going to be held back and walked, the short
     // definitions the walk re-evaluates itself —, and nothing they overwrite may still define a virtual buffer
     const bool mayWalk = mayHold && in->fuseGradient && in->S == 4 && !in->tiled && globalCum == BEAGLE_OP_NONE && in->gradientVirtual && in->preWalk;
-    std::vector<int> need, deferred;
+    ReadSet reads(in);
+    std::vector<int> deferred;
     long unstoredOperands = 0;
     for (int k = 0; k < count; k++) {
         const int* op = ops + (size_t)k * tuple;
@@ -137,12 +134,12 @@ int runPreOperations(Instance* in, const int* ops, int count, int globalCum, boo
         if (isVirt(in, sib)) {
             unstoredOperands++;
             if (mayWalk && wS == BEAGLE_OP_NONE && op[2] == BEAGLE_OP_NONE && walkableDefinition(in, sib)) deferred.push_back(sib);
-            else in->planner.keysOf(sib, need);
+            else reads.note(sib);
         }
-        if (isVirt(in, par)) in->planner.keysOf(par, need);
+        reads.note(par);
         if (in->virt) {
-            need.insert(need.end(), in->planner.tipUsers(dest).begin(), in->planner.tipUsers(dest).end());
-            if (wS != BEAGLE_OP_NONE) need.insert(need.end(), in->planner.scaleUsers(wS).begin(), in->planner.scaleUsers(wS).end());
+            for (int key : in->planner.tipUsers(dest)) reads.noteKey(key);
+            if (wS != BEAGLE_OP_NONE) for (int key : in->planner.scaleUsers(wS)) reads.noteKey(key);
         }
     }
     // a list still held back: the new one replaces it unexecuted when it rewrites everything the old one would have written
@@ -157,7 +154,7 @@ int runPreOperations(Instance* in, const int* ops, int count, int globalCum, boo
     // away instead of leaving it to a second walk (runOperationsWalk; 1000 x 20 000: 1.86 -> 0.9 ms for the post-order half).
     // The hint is renewed by every pre-order list and runs out 16 post-order evaluations after the last one.
     if ((int)unstoredOperands >= std::max(4, count / 4) || in->storeAllEvaluations > 0) in->storeAllEvaluations = 16;
-    if (!need.empty()) { int rc = materializeList(in, need); if (rc) return rc; }
+    { int rc = reads.materialize(); if (rc) return rc; }
     std::vector<OpDesc> descs(count);
     std::vector<int> level(count), wLevel(n, -1), rLevel(n, -1), opWrite(count, BEAGLE_OP_NONE);
     int maxLevel = 0;
@@ -198,9 +195,9 @@ int runPreOperations(Instance* in, const int* ops, int count, int globalCum, boo
         if (rc <= 0) return rc;                                    // held (0) or failed (< 0); 1 = not the shape: run it now
     }
     if (!deferred.empty()) {                                       // it runs now, on kernels that read real partials
-        std::vector<int> keys;
-        for (int b : deferred) if (isVirt(in, b)) in->planner.keysOf(b, keys);
-        if (!keys.empty()) { int rc = materializeList(in, keys); if (rc) return rc; }
+        ReadSet late(in);
+        for (int b : deferred) late.note(b);
+        { int rc = late.materialize(); if (rc) return rc; }
         for (int k = 0; k < count; k++) {
             const int sib = ops[(size_t)k * tuple + 5];
             if (!descs[k].child2) { if (!in->partials[sib]) return BEAGLE_ERROR_OUT_OF_RANGE; descs[k].child2 = in->partials[sib]; }
@@ -519,10 +516,9 @@ static int walkedGradient(Instance* in, const std::vector<int>& edgeOf, const in
     // the list's root is what the likelihood is formed from, straight from its operands' partials: those two are real
     {
         const Instance::HeldPreNode& rt = h.nodes[h.segRoot[0]];
-        std::vector<int> keys;
-        if (isVirt(in, rt.postA)) in->planner.keysOf(rt.postA, keys);
-        if (isVirt(in, rt.postB)) in->planner.keysOf(rt.postB, keys);
-        if (!keys.empty()) { int rcm = materializeList(in, keys); if (rcm) return rcm; }
+        ReadSet reads(in);
+        reads.note(rt.postA); reads.note(rt.postB);
+        const int rcm = reads.materialize(); if (rcm) return rcm;
     }
     if (!in->preDummyStates) {
         void* q = nullptr; int rc = devAlloc(in, &q, ((size_t)in->P + 255) & ~(size_t)255); if (rc) return rc;
@@ -685,6 +681,18 @@ static int walkedGradient(Instance* in, const std::vector<int>& edgeOf, const in
     return 0;
 }
 
+// the edges' indices (dIdx: nullptr when the call has none), then their post- and pre-order operands as real data
+static int edgeOperandsResident(Instance* in, const int* postIdx, const int* preIdx, const int* dIdx, int count) {
+    ReadSet reads(in);
+    for (int e = 0; e < count; e++) {
+        if (badIndex(postIdx[e], in->partialsCount) || badIndex(preIdx[e], in->partialsCount) || (dIdx && badIndex(dIdx[e], in->matrixCount)))
+            return BEAGLE_ERROR_OUT_OF_RANGE;
+        if (int bad = reads.post(postIdx[e])) return bad;
+        if (int bad = reads.pre(preIdx[e])) return bad;
+    }
+    return reads.materialize();
+}
+
 int edgeDifferentials(Instance* in, const int* postIdx, const int* preIdx, const int* dIdx, int wIdx, int count,
                       double* outDerivatives, double* outSum, double* outSumSquared) {
     if (count <= 0) return 0;
@@ -698,19 +706,12 @@ int edgeDifferentials(Instance* in, const int* postIdx, const int* preIdx, const
         if (rc == 0) { rc = fusedGradient(in, edgeOf, dIdx, wIdx, count, outSum, outSumSquared); if (rc <= 0) return rc; }
         rc = executeHeldPre(in); if (rc) return rc;
     }
-    std::vector<int> need;
-    for (int e = 0; e < count; e++) {
-        if (badIndex(postIdx[e], in->partialsCount) || badIndex(preIdx[e], in->partialsCount) || badIndex(dIdx[e], in->matrixCount))
-            return BEAGLE_ERROR_OUT_OF_RANGE;
-        if (isVirt(in, postIdx[e])) in->planner.keysOf(postIdx[e], need);
-        if (isVirt(in, preIdx[e])) in->planner.keysOf(preIdx[e], need);
-    }
-    if (!need.empty()) { int rc = materializeList(in, need); if (rc) return rc; }
+    int rc = edgeOperandsResident(in, postIdx, preIdx, dIdx, count); if (rc) return rc;
     const int nb = mi355::edgeBlocks(in->P);
     const size_t perEdgeBytes = (size_t)nb * 2 * sizeof(double) + 2 * sizeof(double) + (outDerivatives ? (size_t)in->P * sizeof(double) : 0);
     int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)count, ((size_t)256 << 20) / perEdgeBytes));
     chunk = std::min(chunk, 32768);
-    int rc = ensureEdgeScratch(in, (size_t)chunk * (nb + 1) * 2 * sizeof(double)); if (rc) return rc;
+    rc = ensureEdgeScratch(in, (size_t)chunk * (nb + 1) * 2 * sizeof(double)); if (rc) return rc;
     double *dBlock = in->edgeScratch.as<double>(), *dSums = dBlock + (size_t)chunk * nb * 2;
     ScopedDevice per(in);                                  // the per-pattern derivatives of a chunk
     if (outDerivatives) rc = per.alloc((size_t)chunk * in->P * sizeof(double));
@@ -724,13 +725,10 @@ int edgeDifferentials(Instance* in, const int* postIdx, const int* preIdx, const
         const int m = std::min(chunk, count - b);
         descs.assign(m, mi355::EdgeDesc());
         for (int e = 0; e < m && !rc; e++) {
-            const int po = postIdx[b + e], pr = preIdx[b + e];
             mi355::EdgeDesc& d = descs[e];
-            if (in->tipStates[po] && po < in->tipCount) { d.post = in->tipStates[po]; d.postIsStates = 1; }
-            else if (in->partials[po]) { d.post = in->partials[po]; d.postIsStates = 0; }
-            else rc = BEAGLE_ERROR_OUT_OF_RANGE;
-            if (!in->partials[pr] || (in->tipStates[pr] && pr < in->tipCount)) rc = BEAGLE_ERROR_OUT_OF_RANGE;
-            d.pre = in->partials[pr];
+            d.post = postOperand(in, postIdx[b + e], &d.postIsStates);
+            d.pre = preOperand(in, preIdx[b + e]);
+            if (!d.post || !d.pre) rc = BEAGLE_ERROR_OUT_OF_RANGE;
             d.dmat = dIdx[b + e];
         }
         if (rc) break;
@@ -798,27 +796,18 @@ int edgeDifferentials(Instance* in, const int* postIdx, const int* preIdx, const
 // calculateCrossProductDifferentials (semantics: include/beagle_mi355.h)
 int crossProducts(Instance* in, const int* postIdx, const int* preIdx, int rateIdx, int wIdx, const double* lengths, int count, double* outSum) {
     if (count <= 0) return 0;
-    std::vector<int> need;
-    for (int e = 0; e < count; e++) {
-        if (badIndex(postIdx[e], in->partialsCount) || badIndex(preIdx[e], in->partialsCount)) return BEAGLE_ERROR_OUT_OF_RANGE;
-        if (isVirt(in, postIdx[e])) in->planner.keysOf(postIdx[e], need);
-        if (isVirt(in, preIdx[e])) in->planner.keysOf(preIdx[e], need);
-    }
-    if (!need.empty()) { int rc = materializeList(in, need); if (rc) return rc; }
+    int rc = edgeOperandsResident(in, postIdx, preIdx, nullptr, count); if (rc) return rc;
     std::vector<mi355::EdgeDesc> descs(count);
     for (int e = 0; e < count; e++) {
-        const int po = postIdx[e], pr = preIdx[e];
         mi355::EdgeDesc& d = descs[e];
-        if (in->tipStates[po] && po < in->tipCount) { d.post = in->tipStates[po]; d.postIsStates = 1; }
-        else if (in->partials[po]) { d.post = in->partials[po]; d.postIsStates = 0; }
-        else return BEAGLE_ERROR_OUT_OF_RANGE;
-        if (!in->partials[pr] || (in->tipStates[pr] && pr < in->tipCount)) return BEAGLE_ERROR_OUT_OF_RANGE;
-        d.pre = in->partials[pr];
+        d.post = postOperand(in, postIdx[e], &d.postIsStates);
+        d.pre = preOperand(in, preIdx[e]);
+        if (!d.post || !d.pre) return BEAGLE_ERROR_OUT_OF_RANGE;
     }
     const size_t nOut = (size_t)in->S * in->S;
     const int nb = mi355::edgeBlocks(in->P);
     ScopedDevice partial(in), out(in);
-    int rc = partial.alloc((size_t)nb * nOut * sizeof(double)); if (rc) return rc;
+    rc = partial.alloc((size_t)nb * nOut * sizeof(double)); if (rc) return rc;
     rc = out.alloc(nOut * sizeof(double)); if (rc) return rc;
     double *dPartial = partial.as<double>(), *dOut = out.as<double>();
     std::vector<double> sums(nOut);

@@ -28,15 +28,15 @@ struct HostCopy {
 
 // out == nullptr (count must fit one chunk): the data is left in the pinned buffer exportHost[0] (beagleMi355GetPartialsPinned)
 static int exportPartials(Instance* in, const int* bufferIndices, const int* scaleIndices, int count, double* out) {
-    std::vector<int> need;
+    ReadSet reads(in);
     for (int k = 0; k < count; k++) {
         const int b = bufferIndices[k];
         if (badIndex(b, in->partialsCount)) return BEAGLE_ERROR_OUT_OF_RANGE;
         if (scaleIndices && scaleIndices[k] != BEAGLE_OP_NONE && badIndex(scaleIndices[k], in->scaleCount)) return BEAGLE_ERROR_OUT_OF_RANGE;
-        if (isVirt(in, b)) in->planner.keysOf(b, need);
         if (foldedTip(in, b)) { const int rcd = demoteFoldedTip(in, b); if (rcd) return rcd; }      // (a tip with an emission table gets its partials: engine_tipemission.cpp)
+        if (int bad = reads.pre(b)) return bad;              // (compact states are no partials to read back)
     }
-    if (!need.empty()) { int rc = materializeList(in, need); if (rc) return rc; }
+    { int rc = reads.materialize(); if (rc) return rc; }
     const size_t elems = (size_t)in->C * in->P * in->S, bytes = elems * sizeof(double);
     // chunks of about 32 MiB, two in flight: while the device converts and copies chunk k + 1, the host empties chunk k
     const size_t chunk = std::max<size_t>(1, std::min<size_t>((size_t)count, ((size_t)32 << 20) / bytes));
@@ -65,7 +65,7 @@ static int exportPartials(Instance* in, const int* bufferIndices, const int* sca
         const size_t n = chunkCount(c);
         for (size_t k = 0; k < n; k++) {
             const int b = bufferIndices[c * chunk + k];
-            if (!in->partials[b] || isCompactTip(in, b)) return BEAGLE_ERROR_OUT_OF_RANGE;
+            if (!preOperand(in, b)) return BEAGLE_ERROR_OUT_OF_RANGE;
             const double* sc = nullptr; int raw = 0;
             if (scaleIndices && scaleIndices[c * chunk + k] != BEAGLE_OP_NONE) {
                 int rc = ensureScale(in, scaleIndices[c * chunk + k]); if (rc) return rc;

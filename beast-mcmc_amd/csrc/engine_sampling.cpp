@@ -62,15 +62,15 @@ int mi355::eng::drawAncestral(Instance* in, const int* nodes, int nodeCount, int
                               int globalP, int pOffset, AncestralDraw* d) {
     if (in->partitionCount > 1) return BEAGLE_ERROR_NO_IMPLEMENTATION;
     if (badIndex(wIdx, in->eigenCount) || badIndex(fIdx, in->eigenCount)) return BEAGLE_ERROR_OUT_OF_RANGE;
-    std::vector<int> need;
+    ReadSet reads(in);
     for (int r = 0; r < nodeCount; r++) {
         const int b = nodes[3 * r], m = nodes[3 * r + 1], parent = nodes[3 * r + 2];
         if (badIndex(b, in->partialsCount)) return BEAGLE_ERROR_OUT_OF_RANGE;
         if (r == 0 && isCompactTip(in, b)) return BEAGLE_ERROR_OUT_OF_RANGE;
         if (r > 0 && (badIndex(m, in->matrixCount) || parent < 0 || parent >= r)) return BEAGLE_ERROR_OUT_OF_RANGE;
-        if (isVirt(in, b)) in->planner.keysOf(b, need);
+        if (int bad = reads.post(b)) return bad;
     }
-    if (!need.empty()) { int rc = materializeList(in, need); if (rc) return rc; }
+    int rc = reads.materialize(); if (rc) return rc;
     const size_t n = (size_t)in->C * in->S * in->S;
     std::vector<mi355::AncestralRow> rows(nodeCount);
     for (int r = 0; r < nodeCount; r++) {
@@ -84,7 +84,7 @@ int mi355::eng::drawAncestral(Instance* in, const int* nodes, int nodeCount, int
         row.parent = r == 0 ? -1 : nodes[3 * r + 2];
     }
     const scratch::AncestralLayout L(nodeCount, in->P);
-    int rc = growScratch(in, in->ancestralDev, L.bytes()); if (rc) return rc;
+    rc = growScratch(in, in->ancestralDev, L.bytes()); if (rc) return rc;
     d->states = L.states.at(in->ancestralDev.p);
     d->cats = L.cats.at(in->ancestralDev.p);
     d->error = L.error.at(in->ancestralDev.p);                 // (right behind the categories: copyAncestral takes both in one copy)

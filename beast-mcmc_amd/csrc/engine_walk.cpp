@@ -965,10 +965,8 @@ int materializeList(Instance* in, const std::vector<int>& xs) {
     return runPlan(in, mp);
 }
 int materializeVirtual(Instance* in, int X) {         // every partition of buffer X
-    if (!isVirt(in, X)) return 0;
-    std::vector<int> keys;
-    in->planner.keysOf(X, keys);
-    return materializeList(in, keys);
+    ReadSet reads(in);
+    return reads.note(X) ? reads.materialize() : 0;
 }
 int materializeScaleUsers(Instance* in, int scaleIdx) {
     if (!in->virt || in->planner.scaleUsers(scaleIdx).empty()) return 0;
@@ -1072,11 +1070,10 @@ int runOperationsWalk(Instance* in, const int* ops, int count, int tuple, int gl
             const double usPlan = usSince(t0);
             in->hostPlanUs += usPlan; in->hostPlanHitUs += usPlan; in->hostHits++;
             const Clock::time_point t1 = Clock::now();
-            hipEvent_t a = nullptr, b = nullptr;
-            const bool launches = !in->planner.planned->prog.empty();
-            if (launches && timeThisCall(in)) { int rce = nextTimerEvents(in, &a, &b); if (rce) return rce; }
-            int rc = runPlan(in, *in->planner.planned, in->planner.plannedTag, a); if (rc) return rc;
-            if (b) { HIP_TRY(hipEventRecord(b, live(in))); in->pendingLaunches += in->lowerLaunched ? 2 : 1; }
+            CallTimer timer(in);
+            if (!in->planner.planned->prog.empty()) { int rce = timer.begin(); if (rce) return rce; }
+            int rc = runPlan(in, *in->planner.planned, in->planner.plannedTag, timer.first()); if (rc) return rc;
+            rc = timer.stop(in->lowerLaunched ? 2 : 1); if (rc) return rc;
             const double usRun = usSince(t1);
             in->hostRunUs += usRun; in->hostRunHitUs += usRun;
             if (in->hostTrace && usPlan + usRun > 40.0)
@@ -1096,8 +1093,8 @@ int runOperationsWalk(Instance* in, const int* ops, int count, int tuple, int gl
             (cum != BEAGLE_OP_NONE && badIndex(cum, in->scaleCount)))
             return BEAGLE_ERROR_OUT_OF_RANGE;
     }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (timeThisCall(in)) { int rce = nextTimerEvents(in, &e0, &e1); if (rce) return rce; }
+    CallTimer timer(in);
+    { int rce = timer.begin(); if (rce) return rce; }
     int launches = 0;
     in->hostPrepUs += usSince(t0);
     for (int begin = 0; begin < count;) {
@@ -1112,7 +1109,7 @@ int runOperationsWalk(Instance* in, const int* ops, int count, int tuple, int gl
         in->planner.mustMaterializeBefore(sub, n, tuple, need);
         // (long memory definitions the list only reads — a branch move's siblings — are stored once, not walked by every move that passes them)
         if (allowVirtual && in->planner.stepLimit == 0) in->planner.longMemoryOperands(sub, n, tuple, in->memDefInlineSteps, need);
-        if (!need.empty()) { int rc = materializeList(in, need); if (rc) return rc; }
+        { int rc = materializeList(in, need); if (rc) return rc; }
         in->hostPrepUs += usSince(t1); t1 = Clock::now();
         const long hitsBefore = in->planner.cacheHits;
         int rc = in->planner.plan(sub, n, tuple, parts, allowVirtual, in->plan, walkChunkOps(in, n));
@@ -1124,18 +1121,16 @@ int runOperationsWalk(Instance* in, const int* ops, int count, int tuple, int gl
         t1 = Clock::now();
         // with the kernel timer on, ONE HIP-event pair brackets the walk launches of the call (the program upload and the
         // snapshot copies are outside: the events time the pruning kernel, which is what the roofline is about)
-        if (!in->planner.planned->prog.empty()) {
-            rc = runPlan(in, *in->planner.planned, in->planner.plannedTag, launches == 0 ? e0 : nullptr); if (rc) return rc;
-            launches += in->lowerLaunched ? 2 : 1;
-        } else { rc = runPlan(in, *in->planner.planned, in->planner.plannedTag); if (rc) return rc; }
+        const bool walks = !in->planner.planned->prog.empty();
+        rc = runPlan(in, *in->planner.planned, in->planner.plannedTag, walks ? timer.first() : nullptr); if (rc) return rc;
+        if (walks) launches += in->lowerLaunched ? 2 : 1;
         { const double us = usSince(t1); in->hostRunUs += us; if (hit) in->hostRunHitUs += us;
           if (in->hostTrace && usPlanThis + us > 40.0)
               fprintf(stderr, "[mi355] call %ld (%d ops from %d, cache %s, tag %ld): planner %.1f us, run %.1f us (resolved again: %d, folds rebuilt so far %ld)\n", in->hostCalls, n, begin,
                       hit ? "hit" : "miss", in->planner.plannedTag, usPlanThis, us, (int)in->lastResolveMiss, in->statFoldBuilds); }
         begin += n;
     }
-    if (e1 && launches > 0) { HIP_TRY(hipEventRecord(e1, live(in))); in->pendingLaunches += launches; }
-    else if (e1) { in->eventsUsed--; in->timedCalls--; }       // nothing was launched: give the (unrecorded) event pair back
+    { int rce = timer.stop(launches); if (rce) return rce; }
     return foldCumulative(in, ops, count, tuple, globalCum);
 }
 
