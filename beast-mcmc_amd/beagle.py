@@ -126,7 +126,7 @@ ABI_SYMBOLS = ["beagleGetVersion", "beagleGetCitation", "beagleGetResourceList",
                "beagleMi355KernelTimer", "beagleMi355DeviceBytes", "beagleMi355WalkStats", "beagleMi355GradientStats", "beagleMi355GetPartialsBatch", "beagleMi355SampleAncestralStates", "beagleMi355SampleMarkovJumps", "beagleMi355SampleMarkovJumpsUniformized",
                "beagleMi355SimulateSequences", "beagleMi355SimulateCompleteHistories", "beagleMi355RobustCounts", "beagleMi355SimulateUnconditionedCounts", "beagleMi355NodeHeightDerivatives", "beagleMi355UpdateDifferentialMatrices", "beagleMi355SetReversibleModels", "beagleMi355GetEigenDecomposition", "beagleMi355EigenStats", "beagleMi355UpdateTransitionMatricesFromGenerators", "beagleMi355GeneratorStats", "beagleMi355UpdateTransitionMatricesWithEpochs", "beagleMi355EpochStats", "beagleMi355NodePatternLikelihoods", "beagleMi355NodePatternStats", "beagleMi355NodePosteriors", "beagleMi355NodePosteriorStats", "beagleMi355PlacementScores", "beagleMi355PlacementStats", "beagleMi355SetTipEmission", "beagleMi355TipEmissionStats",
                "beagleMi355GetPartialsPinned", "beagleMi355GetSiteLogLikelihoodsPinned",
-               "beagleMi355KernelTimerCalls", "beagleMi355WalkHealth", "beagleMi355RepeatStats", "beagleMi355TableOperandStats", "beagleMi355WalkLaunchInfo", "beagleMi355RootFusedCount", "beagleMi355SitePrefetchCount", "beagleMi355KernelTimerRestart", "beagleMi355GetDimensions", "beagleMi355GetCommUniqueId", "beagleMi355CommInit", "beagleMi355CommInfo", "beagleMi355CalculateRootLogLikelihoodsAllReduce"] + \
+               "beagleMi355KernelTimerCalls", "beagleMi355WalkHealth", "beagleMi355RepeatStats", "beagleMi355RepeatSubRunStats", "beagleMi355TableOperandStats", "beagleMi355WalkLaunchInfo", "beagleMi355RootFusedCount", "beagleMi355SitePrefetchCount", "beagleMi355KernelTimerRestart", "beagleMi355GetDimensions", "beagleMi355GetCommUniqueId", "beagleMi355CommInit", "beagleMi355CommInfo", "beagleMi355CalculateRootLogLikelihoodsAllReduce"] + \
               ["beagleBasta" + k for k in ("AllocateCoalescentBuffers", "UpdatePartials", "AccumulatePartials", "GetBuffer", "GetBufferLength", "Stats", "SampleStates", "StatesStats",
                                            "Gradient", "GradientStats", "UpdatePartialsGrad", "UpdateTransitionMatricesGrad", "AccumulatePartialsGrad")]
 BASTA_OPERATION_SIZE = 8
@@ -1167,6 +1167,13 @@ class Beagle:
         keys = ("table_rows", "table_reads", "repeat_clades", "table_bytes", "clades_indexed", "index_host_us", "two_table_nodes",
                 "tables_under_definitions", "index_host_bytes", "index_resets")
         return {k: int(out[i]) for i, k in enumerate(keys)}
+
+    def repeatSubRunStats(self):
+        """Plain clades taken from class tables inside definitions that are not taken whole, since the last kernelTimer call
+        (include/beagle_mi355.h beagleMi355RepeatSubRunStats)."""
+        out = (C.c_long * 2)()
+        self._check("repeatSubRunStats", self._ext("beagleMi355RepeatSubRunStats", [C.c_int, C.POINTER(C.c_long)])(self.instance, out))
+        return {"sub_runs": int(out[0]), "sub_run_micro_ops": int(out[1])}
 
     def tableOperandStats(self):
         """Class-table operands in the assembly loop's programs since the last kernelTimer call (include/beagle_mi355.h beagleMi355TableOperandStats)."""

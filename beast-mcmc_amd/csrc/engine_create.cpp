@@ -253,6 +253,8 @@ int beagleCreateInstance(int tipCount, int partialsBufferCount, int compactBuffe
         // default 8 per tip + 1024) — small values make a short chain cross the reset a long one reaches (tests)
         if (in->repeatsOn && getenv("BEAGLE_MI355_REPEAT_CAPACITY")) in->repeatIndex.setCapacity((size_t)std::max(1, atoi(getenv("BEAGLE_MI355_REPEAT_CAPACITY"))));
     }
+    // class tables for the plain clades inside memory definitions, and slices weighed by what that leaves (planner.h memDefTables)
+    in->planner.memDefTables = !switchOn("BEAGLE_MI355_NO_MEMDEF_TABLES");
     in->planner.cacheEnabled = !switchOn("BEAGLE_MI355_NO_PLAN_CACHE");
     in->fastWalk = !switchOn("BEAGLE_MI355_NO_FAST_WALK");
     in->strictWaits = !(getenv("BEAGLE_MI355_STRICT_WAITS") && atoi(getenv("BEAGLE_MI355_STRICT_WAITS")) == 0);

@@ -121,6 +121,7 @@ struct Instance {
         long memReads = 0, tipReads = 0, scaleReads = 0, scaleWrites = 0, stored = 0, fused = 0;      // (fused: cherries, kernels.h WK_CHERRY)
         long microOps = 0;                               // of the walk proper (class-table programs: tableRows)
         long tableRows = 0, tableReads = 0, repeatClades = 0, twoTables = 0, unstoredConsumers = 0;   // repeated sub-patterns (below)
+        long subRuns = 0, subRunOps = 0;                  // ... of them the plain clades inside runs not taken whole (planner.h RepeatRun::sub), their micro-operations
         // ... as the device program has them (ProgramResolver::microOp; beagleMi355TableOperandStats): first children read from tables, those
         // directly behind a micro-operation whose first child comes from memory / that has a fused cherry, the most classes of a table read
         long tabFirst = 0, tabFirstBehindMem = 0, tabFirstBehindCherry = 0, tabMaxClasses = 0;
@@ -199,6 +200,7 @@ struct Instance {
     double* repeatArena = nullptr; int repeatArenas = 0; mi355::RepeatRows repeatRows;      // [arenas][C][P][4]; who has which rows
     std::vector<int> repeatQueue;                        // clades waiting for their index (built where the host waits for a result)
     long statTableRows = 0, statTableReads = 0, statRepeatClades = 0, statTwoTables = 0, statUnstoredConsumers = 0;      // since the last timer reset
+    long statSubRuns = 0, statSubRunOps = 0;                                                                             // (the same; beagleMi355RepeatSubRunStats)
     long statTabFirst = 0, statTabFirstBehindMem = 0, statTabFirstBehindCherry = 0, statTabMaxClasses = 0;               // (the same)
     size_t repeatTableCap = 0;                           // most tables kept (three times what the last compressed plan took): past it, as when the arena is full
     bool lastPlanCached = false;                         // the last runPlan ran a cached full-evaluation plan (the result wait behind it is long enough for index work)

@@ -11,6 +11,7 @@ static void resetWalkCounters(Instance* in) {
     in->statMicroOps = in->statStored = in->statMemReads = in->statTipReads = in->statScaleReads = in->statWalks = in->statScaleWrites = 0;
     in->statFastWalks = in->statFused = 0;
     in->statTableRows = in->statTableReads = in->statRepeatClades = in->statTwoTables = in->statUnstoredConsumers = 0;
+    in->statSubRuns = in->statSubRunOps = 0;
     in->statTabFirst = in->statTabFirstBehindMem = in->statTabFirstBehindCherry = in->statTabMaxClasses = 0;
 }
 
@@ -158,6 +159,16 @@ int beagleMi355RepeatStats(int instance, long* out10) {
     for (const auto& b : in->repeatPool) bytes += b.size;
     out6[0] = in->statTableRows; out6[1] = in->statTableReads; out6[2] = in->statRepeatClades;
     out6[3] = (long)bytes; out6[4] = in->repeatIndex.builds; out6[5] = in->statRepeatBuildUs;
+    return BEAGLE_SUCCESS;
+}
+
+int beagleMi355RepeatSubRunStats(int instance, long* out2) {
+    if (mi355::isShardedHandle(instance)) {             // shard 0's
+        return mi355::shardedFirst(instance, [&](int h) { return beagleMi355RepeatSubRunStats(h, out2); });
+    }
+    Instance* in = lookup(instance);
+    if (!in || !out2) return BEAGLE_ERROR_UNINITIALIZED_INSTANCE;
+    out2[0] = in->statSubRuns; out2[1] = in->statSubRunOps;
     return BEAGLE_SUCCESS;
 }
 

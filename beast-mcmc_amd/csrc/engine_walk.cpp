@@ -185,14 +185,14 @@ static int prepareRepeats(Instance* in, const mi355::Plan& plan, const mi355::Fo
                    ~Spent() { in->statRepeatBuildUs += (long)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(); } } spent{in, std::chrono::steady_clock::now()};
     slot->compressed = false; slot->repeatsMissing = false; slot->lowerRange = 0;
     Instance::WalkTraffic& t = slot->traffic;
-    t.tableRows = t.tableReads = t.repeatClades = t.twoTables = t.unstoredConsumers = 0;
+    t.tableRows = t.tableReads = t.repeatClades = t.twoTables = t.unstoredConsumers = t.subRuns = t.subRunOps = 0;
     // the index forgets nothing clade by clade: at its capacity everything goes (tables and kept programs with it) and this list's clades
     // are indexed afresh, here — once in thousands of topology moves
     if (in->repeatIndex.overCapacity()) { dropRepeatTables(in, true); in->statRepeatResets++; }
     std::vector<mi355::RepeatRun> cand, take;
     std::vector<int> missing;
     const bool buildNow = in->repeatTables.empty() && in->repeatQueue.empty();
-    mi355::findRepeatRuns(plan, fold, in->repeatIndex, buildNow, cand, &missing);
+    mi355::findRepeatRuns(plan, fold, in->repeatIndex, buildNow, cand, &missing, in->planner.memDefTables);
     if (!missing.empty()) {
         slot->repeatsMissing = true;
         for (int c : missing) if (std::find(in->repeatQueue.begin(), in->repeatQueue.end(), c) == in->repeatQueue.end()) in->repeatQueue.push_back(c);
@@ -229,6 +229,7 @@ static int prepareRepeats(Instance* in, const mi355::Plan& plan, const mi355::Fo
     slot->compressed = true;
     t.tableReads = slot->repeats.tableReads; t.repeatClades = (long)slot->repeats.lower.size();
     t.twoTables = slot->repeats.twoTables; t.unstoredConsumers = slot->repeats.unstoredConsumers;
+    t.subRuns = slot->repeats.subRuns; t.subRunOps = slot->repeats.subRunOps;
     for (const mi355::PlanSeg& sg : slot->repeats.lower) {
         const Instance::RepeatTable& tab = in->repeatTables[sg.partition];
         t.tableRows += (long)tab.D * sg.progCount;
@@ -607,6 +608,7 @@ static void accountTraffic(Instance* in, const Instance::Resolved& r) {
     in->statScaleWrites += t.scaleWrites; in->statStored += t.stored; in->statFused += t.fused; in->statMicroOps += t.microOps;
     in->statTableRows += t.tableRows; in->statTableReads += t.tableReads; in->statRepeatClades += t.repeatClades;
     in->statTwoTables += t.twoTables; in->statUnstoredConsumers += t.unstoredConsumers;
+    in->statSubRuns += t.subRuns; in->statSubRunOps += t.subRunOps;
     in->statTabFirst += t.tabFirst; in->statTabFirstBehindMem += t.tabFirstBehindMem; in->statTabFirstBehindCherry += t.tabFirstBehindCherry;
     in->statTabMaxClasses = std::max(in->statTabMaxClasses, t.tabMaxClasses);
 }

@@ -530,7 +530,7 @@ int WalkPlanner::plan(const int* ops, int count, int tuple, int parts, bool allo
             const int way = promoteWay >= 0 ? promoteWay : cacheNext_;
             if (promoteWay < 0) cacheNext_ = (cacheNext_ + 1) % CACHE_WAYS;
             fill = &cache_[way];
-            fill->valid = false; fill->cleanAtEpoch = -1; fill->tag = ++wayGen_[way] * CACHE_WAYS + way + 1; fill->count = count; fill->tuple = tuple; fill->parts = parts; fill->chunkOps = chunkOps; fill->repeatWeights = repeatWeights;
+            fill->valid = false; fill->cleanAtEpoch = -1; fill->tag = ++wayGen_[way] * CACHE_WAYS + way + 1; fill->count = count; fill->tuple = tuple; fill->parts = parts; fill->chunkOps = chunkOps; fill->repeatWeights = repeatWeights; fill->memDefTables = memDefTables;
             fill->allowVirtual = allowVirtual; fill->stepLimit = allowVirtual ? stepLimit : 0; fill->memStepCap = allowVirtual ? memCapNow_ : 0; fill->tipEpoch = compactEpoch; fill->simple = simple;
             fill->ops.assign(ops, ops + (size_t)count * tuple);
         }
@@ -683,7 +683,8 @@ int WalkPlanner::plan(const int* ops, int count, int tuple, int parts, bool allo
                         if (prod >= 0 && !info_[prod].virtDest) { if (!info_[prod].emitted) w += weight[prod]; }
                         else if (virt_[key(buf, o.part)].on) {
                             if (repeatW && plainDefinition(virt_[key(buf, o.part)])) { w += 1; continue; }      // (a table row gathered by this op)
-                            w += virt_[key(buf, o.part)].nSteps;
+                            // (a memory definition under memDefTables: its path, and a gather per plain clade off it)
+                            w += repeatW && memDefTables && virt_[key(buf, o.part)].memKey >= 0 ? memDefWeight(virt_[key(buf, o.part)]) : virt_[key(buf, o.part)].nSteps;
                             const int a = anyMem ? operandOp(key(buf, o.part)) : -1;      // (a memory definition: its operand's program comes with it)
                             if (a >= 0 && !info_[a].emitted) w += weight[a];
                         }
@@ -752,7 +753,7 @@ int WalkPlanner::plan(const int* ops, int count, int tuple, int parts, bool allo
     }
     // launches run wave by wave: order the slices that way (stable: partitions keep their order inside a wave)
     std::stable_sort(out.segs.begin(), out.segs.end(), [](const PlanSeg& a, const PlanSeg& b) { return a.wave < b.wave; });
-    linkSlices(out, repeatW);
+    linkSlices(out, repeatW ? (memDefTables ? 2 : 1) : 0);
     if (fill) {
         // (the entry TAKES the program — `out` is left with whatever the entry held — and `planned` names the entry's copy, as on
         // a hit; the definitions of unstored destinations are copied, steps in use only, over whatever the way held before)
@@ -779,7 +780,64 @@ bool WalkPlanner::plainDefinition(const VirtDef& v) const {
     return v.nSteps > 0;
 }
 
-void WalkPlanner::linkSlices(Plan& out, bool repeatDurations) {
+// (planner.h memDefTables) what compression leaves of a memory definition: the steps from memStep up to the last one, and off that path a
+// clade of compact tips as the one gather it becomes, anything else — a clade over uploaded tip partials — as its steps
+int WalkPlanner::memDefWeight(const VirtDef& v) const {
+    int size[PLAN_MAX_STEPS]; bool plain[PLAN_MAX_STEPS];       // per step: its subtree (operands are earlier steps)
+    for (int t = 0; t < v.nSteps; t++) {
+        const VirtStep& s = v.steps[t];
+        if (s.type == VT_CHERRY) { size[t] = 1; plain[t] = !s.memA && !s.memB; }
+        else if (s.type == VT_EXTEND) { size[t] = 1 + size[s.subA]; plain[t] = plain[s.subA] && !s.memB; }
+        else { size[t] = 1 + size[s.subA] + size[s.subB]; plain[t] = plain[s.subA] && plain[s.subB]; }
+    }
+    auto off = [&](int sub) { return plain[sub] ? 1 : size[sub]; };
+    int p = v.memStep, w = 1;
+    if (v.steps[p].type == VT_EXTEND) w += off(v.steps[p].subA);
+    for (int t = p + 1; t < v.nSteps; t++) {
+        const VirtStep& s = v.steps[t];
+        if (s.subA != p && s.subB != p) continue;
+        w++;
+        if (s.type == VT_JOIN) w += off(s.subA == p ? s.subB : s.subA);
+        p = t;
+    }
+    return w;
+}
+
+namespace {
+// The maximal plain sub-clades of micro-operations [start, start + count) of one run (planner.h RepeatRun): ranges [first, root] in which
+// every micro-operation stores nothing, pays nothing (`pays`) and reads tips, the ACC of its predecessor in the range or a hold slot parked
+// in the range, and whose result is read by a micro-operation of the run that is not such a one itself.  In program order.
+template <class Pays> void plainSubRanges(const std::vector<MicroOp>& prog, int start, int count, Pays pays, std::vector<PlanRun>& out) {
+    std::vector<int> first((size_t)count, -1);            // per micro-operation: where its plain sub-clade begins, -1: it heads none
+    int parked[3] = {-1, -1, -1};
+    auto at = [&](int i) -> int& { return first[(size_t)(i - start)]; };
+    for (int i = start; i < start + count; i++) {
+        const MicroOp& m = prog[(size_t)i];
+        bool ok = m.storeBuf < 0 && !pays(i);
+        int f = i, h = -1;
+        if (isHoldKind(m.k1)) { h = parked[m.k1 - PK_H0]; parked[m.k1 - PK_H0] = -1; if (h < 0 || at(h) < 0) ok = false; }
+        else if (m.k1 != PK_TIPS) ok = false;
+        if (m.k2 == PK_ACC) {
+            // (post-order: the operand in ACC ends right before this one, a parked operand right before that one's range)
+            if (i == start || at(i - 1) < 0 || prog[(size_t)i - 1].hold) ok = false;
+            else if (h >= 0 && ok && at(i - 1) != h + 1) ok = false;
+            else f = h >= 0 && ok ? at(h) : at(i - 1);
+        } else if (m.k2 != PK_TIPS || h >= 0) ok = false;
+        at(i) = ok ? f : -1;
+        if (m.hold) parked[m.hold - 1] = i;
+    }
+    for (int i = start; i < start + count; i++) {
+        if (at(i) < 0) continue;
+        const MicroOp& m = prog[(size_t)i];
+        int j = -1;
+        if (m.hold) { for (int q = i + 1; q < start + count; q++) if (prog[(size_t)q].k1 == PK_H0 + m.hold - 1) { j = q; break; } }
+        else if (i + 1 < start + count && prog[(size_t)i + 1].k2 == PK_ACC) j = i + 1;
+        if (j >= 0 && at(j) < 0) out.push_back(PlanRun{at(i), i - at(i) + 1});
+    }
+}
+}  // namespace
+
+void WalkPlanner::linkSlices(Plan& out, int repeatDurations) {
     const size_t nKeys = (size_t)partialsCount_ * keyParts_;
     if (storedBy_.size() < nKeys) { storedBy_.assign(nKeys, -1); storedStamp_.assign(nKeys, 0); }
     linkStamp_++;
@@ -838,20 +896,28 @@ void WalkPlanner::linkSlices(Plan& out, bool repeatDurations) {
     std::stable_sort(out.launchOrder.begin(), out.launchOrder.end(), [&](int a, int b) { return out.segs[a].tail > out.segs[b].tail; });
     if (launchMachines <= 0.0 || n < 3) return;
     // how long a slice runs: its micro-operations — under planner.h repeatWeights with every run that reads tips only counted as the one
-    // gather it becomes
+    // gather it becomes, and (2: planner.h memDefTables) inside any other run every plain sub-clade the same way
     std::vector<int> duration(n);
     for (int s = 0; s < n; s++) duration[s] = out.segs[s].progCount;
-    if (repeatDurations)
+    if (repeatDurations) {
+        std::vector<PlanRun> sub;
         for (const PlanRun& run : out.runs) {
             bool plain = run.count > 1;
             for (int i = run.start; plain && i < run.start + run.count; i++) {
                 const MicroOp& m = out.prog[(size_t)i];
                 plain = m.storeBuf < 0 && m.k1 != PK_MEM && m.k2 != PK_MEM;
             }
-            if (!plain) continue;
+            int saved = plain ? run.count - 1 : 0;
+            if (!plain && repeatDurations > 1 && run.count > 1) {
+                sub.clear();
+                plainSubRanges(out.prog, run.start, run.count, [](int) { return false; }, sub);
+                for (const PlanRun& q : sub) saved += q.count - 1;
+            }
+            if (saved <= 0) continue;
             for (int s = 0; s < n; s++)
-                if (run.start >= out.segs[s].progStart && run.start < out.segs[s].progStart + out.segs[s].progCount) { duration[s] -= run.count - 1; break; }
+                if (run.start >= out.segs[s].progStart && run.start < out.segs[s].progStart + out.segs[s].progCount) { duration[s] -= saved; break; }
         }
+    }
     // List scheduling on `machines` identical machines, a slice taking its length: whenever a machine is free, the ready slice
     // (all of its dependencies finished) with the longest tail starts; the order of the starts is the launch order.
     const int machines = std::max(1, (int)(launchMachines + 0.5));
@@ -905,7 +971,7 @@ bool WalkPlanner::promotable(const CacheEntry& e, bool allowVirtual) const {
 
 WalkPlanner::CacheEntry* WalkPlanner::findCached(const int* ops, int count, int tuple, int parts, bool allowVirtual, int chunkOps) {
     for (CacheEntry& e : cache_)
-        if (e.valid && e.count == count && e.tuple == tuple && e.parts == parts && e.chunkOps == chunkOps && e.allowVirtual == allowVirtual && e.repeatWeights == repeatWeights &&
+        if (e.valid && e.count == count && e.tuple == tuple && e.parts == parts && e.chunkOps == chunkOps && e.allowVirtual == allowVirtual && e.repeatWeights == repeatWeights && e.memDefTables == memDefTables &&
             e.stepLimit == (allowVirtual ? stepLimit : 0) && (e.memStepCap == (allowVirtual ? memStepCap : 0) || e.memStepCap == (allowVirtual ? memCapSeen() : 0)) &&
             e.tipEpoch == compactEpoch && memcmp(e.ops.data(), ops, (size_t)count * tuple * sizeof(int)) == 0)
             return &e;
@@ -1126,20 +1192,19 @@ bool RepeatIndex::build(int id, int* budget) {
     return c.built && !c.over;
 }
 
-void findRepeatRuns(const Plan& plan, const FoldMap* fold, RepeatIndex& idx, bool build, std::vector<RepeatRun>& out, std::vector<int>* missing) {
+void findRepeatRuns(const Plan& plan, const FoldMap* fold, RepeatIndex& idx, bool build, std::vector<RepeatRun>& out, std::vector<int>* missing, bool subRuns) {
     out.clear();
     if (plan.runs.empty()) return;
     for (const MicroOp& m : plan.prog) if (m.smode == PS_WRITE) return;
     auto pays = [&](int i) { return fold ? fold->payStart[(size_t)i + 1] > fold->payStart[(size_t)i] : plan.prog[(size_t)i].smode == PS_READ; };
     // the slice of every run (runs are in program order, slices tile the program in any order)
     auto sliceEnd = [&](int at) { for (const PlanSeg& sg : plan.segs) if (at >= sg.progStart && at < sg.progStart + sg.progCount) return sg.progStart + sg.progCount; return -1; };
-    for (size_t r = 0; r < plan.runs.size(); r++) {
-        const PlanRun& run = plan.runs[r];
-        const int last = run.start + run.count - 1, end = sliceEnd(run.start);
-        if (run.count <= 0 || end < 0 || last >= end) continue;
+    // micro-operations [start, last], whose slice ends at `end`, as a candidate (a whole run, or a sub-run of one).  false: the range itself
+    // does not qualify — it stores, pays or reads something else than tips and its own results
+    auto candidate = [&](int start, int last, int end, bool sub) {
         bool ok = true;
         int acc = -1, hold[3] = {-1, -1, -1};
-        for (int i = run.start; i <= last && ok; i++) {
+        for (int i = start; i <= last && ok; i++) {
             const MicroOp& m = plan.prog[(size_t)i];
             if (m.storeBuf >= 0 || pays(i)) ok = false;
             int a, b;
@@ -1149,32 +1214,46 @@ void findRepeatRuns(const Plan& plan, const FoldMap* fold, RepeatIndex& idx, boo
             acc = idx.intern(a, b);
             if (m.hold && i < last) hold[m.hold - 1] = acc;
         }
-        if (!ok) continue;
-        RepeatRun rr; rr.run = (int)r; rr.clade = acc; rr.viaHold = plan.prog[(size_t)last].hold != 0; rr.consumer = -1;
+        if (!ok) return false;
+        RepeatRun rr; rr.start = start; rr.count = last - start + 1; rr.clade = acc; rr.viaHold = plan.prog[(size_t)last].hold != 0; rr.consumer = -1; rr.sub = sub;
         if (rr.viaHold) {
             const int k = PK_H0 + plan.prog[(size_t)last].hold - 1;
             for (int j = last + 1; j < end; j++) if (plan.prog[(size_t)j].k1 == k) { rr.consumer = j; break; }
         } else if (last + 1 < end && plan.prog[(size_t)last + 1].k2 == PK_ACC) rr.consumer = last + 1;
-        if (rr.consumer < 0) continue;
+        if (rr.consumer < 0) return true;
         const RepeatIndex::Clade& c = idx.clade(rr.clade);
         if (!c.built) {
             if (build) idx.build(rr.clade);
-            else { if (missing) missing->push_back(rr.clade); continue; }
+            else { if (missing) missing->push_back(rr.clade); return true; }
         }
-        if (idx.clade(rr.clade).over) continue;
+        if (idx.clade(rr.clade).over) return true;
         out.push_back(rr);
+        return true;
+    };
+    std::vector<PlanRun> sub;
+    for (size_t r = 0; r < plan.runs.size(); r++) {
+        const PlanRun& run = plan.runs[r];
+        const int last = run.start + run.count - 1, end = sliceEnd(run.start);
+        if (run.count <= 0 || end < 0 || last >= end) continue;
+        if (candidate(run.start, last, end, false) || !subRuns) continue;
+        // not as a whole — a memory definition evaluated from memory, mostly: the plain clades inside it (planner.h RepeatRun), their
+        // consumers inside the run
+        sub.clear();
+        plainSubRanges(plan.prog, run.start, run.count, pays, sub);
+        for (const PlanRun& q : sub) candidate(q.start, q.start + q.count - 1, last + 1, true);
     }
 }
 
 void emitRepeatPlan(const Plan& plan, const std::vector<RepeatRun>& take, RepeatPlan& out) {
-    out.plan.clear(); out.lower.clear(); out.origin.clear(); out.tableReads = 0; out.twoTables = 0; out.unstoredConsumers = 0;
+    out.plan.clear(); out.lower.clear(); out.origin.clear(); out.tableReads = 0; out.twoTables = 0; out.unstoredConsumers = 0; out.subRuns = 0; out.subRunOps = 0;
     const size_t n = plan.prog.size();
     std::vector<MicroOp> mod(plan.prog);
     std::vector<char> gone(n, 0);
     auto sliceStart = [&](int at) { for (const PlanSeg& sg : plan.segs) if (at >= sg.progStart && at < sg.progStart + sg.progCount) return sg.progStart; return 0; };
     for (const RepeatRun& rr : take) {                   // (in program order: a consumer's first operand is settled before its second)
-        const PlanRun& run = plan.runs[(size_t)rr.run];
+        const PlanRun run{rr.start, rr.count};
         for (int i = run.start; i < run.start + run.count; i++) gone[(size_t)i] = 1;
+        if (rr.sub) { out.subRuns++; out.subRunOps += run.count; }
         MicroOp& c = mod[(size_t)rr.consumer];
         out.tableReads++;
         if (rr.viaHold) { c.k1 = PK_TAB; c.a1 = rr.clade; continue; }
@@ -1209,7 +1288,7 @@ void emitRepeatPlan(const Plan& plan, const std::vector<RepeatRun>& take, Repeat
         sg.progCount = (int)out.plan.prog.size() - sg.progStart;
     }
     for (const RepeatRun& rr : take) {
-        const PlanRun& run = plan.runs[(size_t)rr.run];
+        const PlanRun run{rr.start, rr.count};
         PlanSeg sg; sg.progStart = (int)out.plan.prog.size(); sg.progCount = run.count; sg.partition = rr.clade; sg.wave = 0;
         sg.depStart = 0; sg.depCount = 0; sg.tail = run.count; sg.next = -1;
         for (int i = run.start; i < run.start + run.count; i++) {

@@ -149,16 +149,25 @@ struct RepeatRows {
 // A run of Plan::runs that can be taken from a class table: every leaf a compact tip, nothing stored, nothing rescaled in write mode, no
 // micro-operation of it pays reciprocals (`fold`: the plan's own FoldMap — its memberships are kept, the consumer pays what it paid; without
 // one every read-mode micro-operation pays for itself and such a run stays), its consumer in the same slice.
-struct RepeatRun { int run, clade, consumer; bool viaHold; };
-// the candidates of `plan`; a clade whose index is missing is built (`build`) or listed in `missing` and left out
-void findRepeatRuns(const Plan& plan, const FoldMap* fold, RepeatIndex& idx, bool build, std::vector<RepeatRun>& out, std::vector<int>* missing = nullptr);
+// What is taken is a RANGE of the program, [start, start + count): a whole run, or — `sub` — a SUB-RUN, a maximal plain sub-clade inside a run
+// that cannot be taken whole.  A memory definition evaluated from memory (a slice above the one that stored its operand, WalkPlanner::memStepCap)
+// is ONE run with a PK_MEM leaf, yet most of its steps are the plain clades hanging off the path from that leaf to its last step: each of
+// them is a contiguous post-order range that reads tips, ACC and hold slots written inside the range, stores nothing, pays nothing, and
+// hands its result to a micro-operation of the same run — the next one through ACC, or a later one through the hold slot it is parked in —
+// which is all a whole run is asked for.  Interned and limited by the class count as a whole run is.
+struct RepeatRun { int start, count, clade, consumer; bool viaHold, sub; };
+// the candidates of `plan`, in program order; a clade whose index is missing is built (`build`) or listed in `missing` and left out.
+// subRuns false: whole runs only (WalkPlanner::memDefTables)
+void findRepeatRuns(const Plan& plan, const FoldMap* fold, RepeatIndex& idx, bool build, std::vector<RepeatRun>& out, std::vector<int>* missing = nullptr,
+                    bool subRuns = true);
 // The plan with the runs of `take` evaluated once per class.  out.plan: the UPPER program — the source's slices in the source's order, with its
 // dependencies, launch order and leaves, the runs gone and their consumers reading PK_TAB operands — and behind it in out.plan.prog the
 // LOWER programs, one slice per run (out.lower; PlanSeg::partition = the clade): the run's own micro-operations, paying nothing, the last
 // one's result to be stored as the clade's table.  origin[i]: the micro-operation of the source that out.plan.prog[i] came from.
 // twoTables: consumers with both children from tables;  unstoredConsumers: consumers that are not stored themselves — steps of a memory
-// definition evaluated behind its operand's program (planner.h memStepCap), the only unstored micro-operations with a definition as a child
-struct RepeatPlan { Plan plan; std::vector<PlanSeg> lower; std::vector<int> origin; int tableReads = 0, twoTables = 0, unstoredConsumers = 0; };
+// definition evaluated behind its operand's program (planner.h memStepCap) or, with sub-runs, from memory: the only unstored micro-operations
+// with a table as a child;  subRuns / subRunOps: the sub-runs among `take`, and the micro-operations they took out of the walk
+struct RepeatPlan { Plan plan; std::vector<PlanSeg> lower; std::vector<int> origin; int tableReads = 0, twoTables = 0, unstoredConsumers = 0, subRuns = 0, subRunOps = 0; };
 void emitRepeatPlan(const Plan& plan, const std::vector<RepeatRun>& take, RepeatPlan& out);
 
 // Definition of a virtual buffer: one step per internal node of a small all-compact-tip subtree, in post-order (a step's
@@ -322,6 +331,13 @@ public:
     // Part of a cached plan's identity.  lastWeighed: such a plan's weight in all, 0: the last plan() was not weighed this way.
     bool repeatWeights = false;
     long lastWeighed = 0;
+    // memDefTables: ... and the plain clades INSIDE its memory definitions too (planner.h RepeatRun: sub-runs), so under repeatWeights a memory
+    // definition weighs what it leaves in the walk as well: the steps on the path from its stored operand to its last step plus ONE per plain
+    // clade hanging off that path — whether it is evaluated from memory or behind its operand's program, where those clades are runs of their
+    // own.  With all of its steps counted, a list planned under the longer cap was peeled into two to three times the slices and waves of the
+    // same list under the shorter one (profiles/memdef_tables.txt).  Part of a cached plan's identity.  false: whole runs only, a memory
+    // definition weighs its steps.
+    bool memDefTables = true;
     // ... and the slice sizes of such a plan, chosen from its weight once pass 2 knows it (the engine's rule, engine_walk.cpp
     // walkRepeatChunkOps): chunk and top arrive as plan()'s chunkOps and chunkTopOps and leave as what the plan is cut with.  None: as they are.
     std::function<void(long weight, int& chunk, int& top)> repeatChunkRule;
@@ -354,8 +370,9 @@ private:
     bool onPath(const VirtDef& v, int idx) const;                    // is step memStep in the subtree of step idx
     void realInfo(int k);                // OpInfo::need / size of the (real) op k
     int virtNeed(int buf) const { return virt_[buf].nSteps ? virt_[buf].steps[virt_[buf].nSteps - 1].need : 0; }
-    void linkSlices(Plan& out, bool repeatDurations = false);      // PlanSeg::dep*, tail and Plan::launchOrder
+    void linkSlices(Plan& out, int repeatDurations = 0);           // PlanSeg::dep*, tail and Plan::launchOrder (1: whole plain runs count as one gather, 2: sub-runs too)
     bool plainDefinition(const VirtDef& v) const;                  // every leaf a compact tip: what a class table can stand for (repeatWeights)
+    int memDefWeight(const VirtDef& v) const;                      // a memory definition's path steps + one per plain clade off the path (memDefTables)
     std::vector<int> storedBy_, storedStamp_;          // per (buffer, partition): the slice of the current plan that stores it
     int linkStamp_ = 0;
     int memCapNow_ = 0;                                // the cap of the list being planned (memStepCap, or memCapSeen())
@@ -388,7 +405,7 @@ private:
         bool valid = false;
         long tag = 0;
         int count = 0, tuple = 0, parts = 0, chunkOps = 0, stepLimit = 0, memStepCap = 0;
-        bool allowVirtual = false, repeatWeights = false;
+        bool allowVirtual = false, repeatWeights = false, memDefTables = true;
         std::vector<int> ops;
         long tipEpoch = -1;                            // compactEpoch the plan was made under
         bool simple = false;                           // see replayCached

@@ -981,6 +981,12 @@ int beagleMi355WalkHealth(int instance, long* out4);
  * of host memory the class indices take, out[9]: times they were dropped at their capacity (a chain of topology moves).  All zero where
  * the feature is off (BEAGLE_MI355_NO_REPEATS=1, small buffers, write-mode evaluations). */
 int beagleMi355RepeatStats(int instance, long* out10);
+/* ... and of those class-table programs the SUB-RUNS: plain clades inside a definition that cannot be taken from a table as a whole — the
+ * clades hanging off the path of a memory definition that is evaluated from memory (DESIGN.md 4.1 "Tables inside memory definitions").
+ * Since the last beagleMi355KernelTimer / KernelTimerRestart call — out[0]: sub-runs taken, counted per evaluation (they are among
+ * beagleMi355RepeatStats' out[2]), out[1]: the full-width micro-operations they took out of the walk.  Both zero with
+ * BEAGLE_MI355_NO_MEMDEF_TABLES=1 and wherever beagleMi355RepeatStats reports zeros. */
+int beagleMi355RepeatSubRunStats(int instance, long* out2);
 /* Class-table operands as the device programs of the assembly loop read them (4 states), since the last beagleMi355KernelTimer /
  * KernelTimerRestart call — out[0]: micro-operations whose FIRST child is read from a class table, out[1]: those that come directly
  * behind a micro-operation whose own first child is read from memory, out[2]: those directly behind a micro-operation with a fused
