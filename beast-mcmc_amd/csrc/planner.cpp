@@ -11,6 +11,31 @@ constexpr int OP_NONE = -1;                 // BEAGLE_OP_NONE
 enum { CL_TIPS = 0, CL_MEM = 1, CL_VIRT = 2, CL_REAL = 3, CL_PATH = 4 };      // (CL_PATH: planner.h memStepCap, emitReal)
 inline int popcount2(unsigned m) { return (int)(m & 1u) + (int)((m >> 1) & 1u) + (int)((m >> 2) & 1u); }      // free hold slots (up to 3)
 inline int lowestSlot(unsigned m) { return (m & 1u) ? 0 : (m & 2u) ? 1 : 2; }
+
+// The path of a memory definition (planner.h memStepCap): the steps from memStep — the one that reads the stored operand — up to step
+// `upTo`, each of them the step that has the one before it as an operand (steps are in post-order: it comes later).  visit(t, off) is
+// called for every step t on the path, bottom up; `off` is the operand of t that is NOT on the path when that is an earlier step of the
+// definition — the other side of a VT_JOIN, subA of a VT_EXTEND that reads the stored operand as its leaf — and -1 when it is a tip.
+// Returns the last step reached: `upTo` exactly when that step is on the path.
+template <class Visit> int walkMemPath(const VirtDef& v, int upTo, Visit visit) {
+    int p = v.memStep;
+    visit(p, v.steps[p].type == VT_EXTEND ? v.steps[p].subA : -1);
+    for (int t = p + 1; t <= upTo && p != upTo; t++) {
+        const VirtStep& s = v.steps[t];
+        if (s.subA != p && s.subB != p) continue;
+        visit(t, s.type == VT_JOIN ? (s.subA == p ? s.subB : s.subA) : -1);
+        p = t;
+    }
+    return p;
+}
+
+// The slice (index into plan.segs) that holds micro-operation `at` of plan.prog, -1: none.  Slices tile the program in any order and a
+// plan has a handful of them, so this is a scan.
+inline int sliceHolding(const Plan& plan, int at) {
+    for (size_t s = 0; s < plan.segs.size(); s++)
+        if (at >= plan.segs[s].progStart && at < plan.segs[s].progStart + plan.segs[s].progCount) return (int)s;
+    return -1;
+}
 }  // namespace
 
 void WalkPlanner::init(int partialsCount, int tipCount, int matrixCount, int scaleCount, int maxVirtSteps, bool virtualEnabled, int holdSlots) {
@@ -160,14 +185,16 @@ int WalkPlanner::hazardFreePrefix(const int* ops, int begin, int count, int tupl
     for (; k < count; k++) {
         const int* op = ops + (size_t)k * tuple;
         const int part = tuple > 7 ? op[7] : 0;
-        const size_t kd = (size_t)op[0] * parts + part, k1 = (size_t)op[3] * parts + part, k2 = (size_t)op[5] * parts + part;
+        // (the CALLER's partition count, which sized the marks above — plan() is what checks it against the planner's: not key())
+        auto at = [&](int idx) { return (size_t)idx * parts + part; };
+        const size_t kd = at(op[0]), k1 = at(op[3]), k2 = at(op[5]);
         bool hazard = wStamp_[kd] == stamp_ || rStamp_[kd] == stamp_;
-        if (op[1] != OP_NONE) { const size_t s = (size_t)op[1] * parts + part; hazard = hazard || sWStamp_[s] == stamp_ || sRStamp_[s] == stamp_; }
-        if (op[2] != OP_NONE && op[1] == OP_NONE) { const size_t s = (size_t)op[2] * parts + part; hazard = hazard || sWStamp_[s] == stamp_; }
+        if (op[1] != OP_NONE) { const size_t s = at(op[1]); hazard = hazard || sWStamp_[s] == stamp_ || sRStamp_[s] == stamp_; }
+        if (op[2] != OP_NONE && op[1] == OP_NONE) hazard = hazard || sWStamp_[at(op[2])] == stamp_;
         if (hazard && k > begin) break;
         rStamp_[k1] = stamp_; rStamp_[k2] = stamp_; wStamp_[kd] = stamp_;
-        if (op[1] != OP_NONE) sWStamp_[(size_t)op[1] * parts + part] = stamp_;
-        else if (op[2] != OP_NONE) sRStamp_[(size_t)op[2] * parts + part] = stamp_;
+        if (op[1] != OP_NONE) sWStamp_[at(op[1])] = stamp_;
+        else if (op[2] != OP_NONE) sRStamp_[at(op[2])] = stamp_;
     }
     return k - begin;
 }
@@ -177,11 +204,11 @@ void WalkPlanner::mustMaterializeBefore(const int* ops, int count, int tuple, st
     stamp_++;
     const size_t nKeys = (size_t)partialsCount_ * keyParts_;
     if (wStamp_.size() < nKeys) { wStamp_.assign(nKeys, 0); rStamp_.assign(nKeys, 0); wOp_.assign(nKeys, 0); }
-    auto keyOf = [&](const int* op) { return (size_t)op[0] * keyParts_ + (tuple > 7 ? op[7] : 0); };
+    auto keyOf = [&](const int* op) { return key(op[0], tuple > 7 ? op[7] : 0); };
     for (int k = 0; k < count; k++) wStamp_[keyOf(ops + (size_t)k * tuple)] = stamp_;
     for (int k = 0; k < count; k++) {
         const int* op = ops + (size_t)k * tuple;
-        if ((op[3] == op[0] || op[5] == op[0]) && virt_[keyOf(op)].on) out.push_back((int)keyOf(op));     // in-place update of a virtual buffer
+        if ((op[3] == op[0] || op[5] == op[0]) && virt_[keyOf(op)].on) out.push_back(keyOf(op));     // in-place update of a virtual buffer
         const int wS = op[1];
         if (wS == OP_NONE || wS < 0 || wS >= scaleCount_) continue;
         for (int u : scaleUsers_[wS])
@@ -222,24 +249,16 @@ int WalkPlanner::operandOp(int vkey) const {
 }
 
 bool WalkPlanner::onPath(const VirtDef& v, int idx) const {
-    int p = v.memStep;
-    for (int t = p + 1; t <= idx && p != idx; t++)
-        if (v.steps[t].subA == p || v.steps[t].subB == p) p = t;
-    return p == idx;
+    return walkMemPath(v, idx, [](int, int) {}) == idx;
 }
 
 // Steps memStep .. upTo of a memory definition evaluated where the program has just produced the stored operand (needA: the hold
 // slots the operand's own evaluation takes): at every step of the path the costlier side first, parked while the other is evaluated.
 int WalkPlanner::pathNeed(const VirtDef& v, int upTo, int needA) const {
-    auto both = [](int a, int b) { return std::min(std::max(a, 1 + b), std::max(b, 1 + a)); };
-    int p = v.memStep, n = needA;
-    if (v.steps[p].type == VT_EXTEND) n = both(needA, v.steps[v.steps[p].subA].need);
-    for (int t = p + 1; t <= upTo && p != upTo; t++) {
-        const VirtStep& s = v.steps[t];
-        if (s.subA != p && s.subB != p) continue;
-        if (s.type == VT_JOIN) n = both(n, v.steps[s.subA == p ? s.subB : s.subA].need);
-        p = t;
-    }
+    int n = needA;
+    walkMemPath(v, upTo, [&](int, int off) {
+        if (off >= 0) { const int b = v.steps[off].need; n = std::min(std::max(n, 1 + b), std::max(b, 1 + n)); }
+    });
     return n;
 }
 
@@ -248,9 +267,8 @@ void WalkPlanner::realInfo(int k) {
     OpInfo& o = info_[k];
     int need[2] = {0, 0}, size[2] = {0, 0}; bool eval[2] = {false, false}, real[2] = {false, false};
     for (int w = 0; w < 2; w++) {
-        const bool tip = w ? o.tip2 : o.tip1;
-        const int c = w ? o.c2 : o.c1, prod = w ? prod2_[k] : prod1_[k];
-        if (tip) continue;
+        const int c = o.ch[w].buf, prod = o.ch[w].prod;
+        if (o.ch[w].tip) continue;
         if (prod >= 0 && !info_[prod].virtDest) { eval[w] = real[w] = true; need[w] = info_[prod].need; size[w] = info_[prod].size; }
         else if (virt_[key(c, o.part)].on) {
             const VirtDef& v = virt_[key(c, o.part)];
@@ -315,7 +333,7 @@ void WalkPlanner::emitVirtualStep(int buf, int idx, unsigned freeMask, bool writ
     }
     if (st.scaleIdx >= 0) {
         m.scaleIdx = st.scaleIdx;
-        const size_t sk = (size_t)st.scaleIdx * parts_ + partitionOf(buf);      // scale-buffer use is tracked per partition
+        const size_t sk = scaleKey(st.scaleIdx, partitionOf(buf));      // scale-buffer use is tracked per partition
         const bool w = writeMode && sWStamp_[sk] == stamp_;
         m.smode = w ? PS_WRITE : PS_READ;
         if (w) sDone_[sk] = stamp_;
@@ -354,11 +372,10 @@ void WalkPlanner::emitReal(int root, unsigned rootMask, Plan& out) {
                 const OpInfo& o = info_[f.j];
                 for (int w = 0; w < 2; w++) {
                     Child& c = f.ch[w];
-                    c.buf = w ? o.c2 : o.c1; c.mat = w ? o.m2 : o.m1;
-                    const bool tip = w ? o.tip2 : o.tip1;
+                    c.buf = o.ch[w].buf; c.mat = o.ch[w].mat;
                     c.prod = -1; c.need = 0; c.size = 0; c.vkey = key(c.buf, o.part); c.vstep = -1;
-                    if (tip) { c.cls = CL_TIPS; continue; }
-                    const int prod = w ? prod2_[f.j] : prod1_[f.j];
+                    if (o.ch[w].tip) { c.cls = CL_TIPS; continue; }
+                    const int prod = o.ch[w].prod;
                     bool virt = false;
                     if (prod >= 0) {
                         const OpInfo& p = info_[prod];
@@ -460,7 +477,7 @@ void WalkPlanner::emitReal(int root, unsigned rootMask, Plan& out) {
             if (f.j >= 0) {
                 OpInfo& o = info_[f.j];
                 m.storeBuf = o.dest;
-                if (o.wS != OP_NONE) { m.scaleIdx = o.wS; m.smode = PS_WRITE; sDone_[(size_t)o.wS * parts_ + o.part] = stamp_; }
+                if (o.wS != OP_NONE) { m.scaleIdx = o.wS; m.smode = PS_WRITE; sDone_[scaleKey(o.wS, o.part)] = stamp_; }
                 else if (o.rS != OP_NONE) { m.scaleIdx = o.rS; m.smode = PS_READ; }
                 o.emitted = true;
                 lastStored++;
@@ -468,7 +485,7 @@ void WalkPlanner::emitReal(int root, unsigned rootMask, Plan& out) {
                 const VirtStep& s = virt_[f.pkey].steps[f.pidx];
                 if (s.scaleIdx >= 0) {                    // (as emitVirtualStep)
                     m.scaleIdx = s.scaleIdx;
-                    const size_t sk = (size_t)s.scaleIdx * parts_ + partitionOf(f.pkey);
+                    const size_t sk = scaleKey(s.scaleIdx, partitionOf(f.pkey));
                     const bool w = sWStamp_[sk] == stamp_;
                     m.smode = w ? PS_WRITE : PS_READ;
                     if (w) sDone_[sk] = stamp_;
@@ -480,6 +497,9 @@ void WalkPlanner::emitReal(int root, unsigned rootMask, Plan& out) {
     }
 }
 
+// ---- plan(): the steps ---------------------------------------------------------------------------------------------
+// What they hand each other is in ListState (planner.h) and in info_; the marks per buffer and scale buffer (wStamp_ / wOp_, sWStamp_,
+// sDone_) are valid for the current stamp_ only.
 int WalkPlanner::plan(const int* ops, int count, int tuple, int parts, bool allowVirtual, Plan& out, int chunkOps) {
     out.clear();
     planned = &out; plannedTag = 0;
@@ -492,288 +512,368 @@ int WalkPlanner::plan(const int* ops, int count, int tuple, int parts, bool allo
     if (sWStamp_.size() < nS) { sWStamp_.assign(nS, 0); sRStamp_.assign(nS, 0); sDone_.assign(nS, 0); }
     stamp_++;
     if (parts != keyParts_) return -1;                 // (BEAGLE_ERROR_GENERAL) the engine sets the partition count first
-    allowVirtual = allowVirtual && enabled_;
-
-    // ---- closed list?  then the plan may be in the cache (planner.h)
-    CacheEntry* fill = nullptr;
-    bool anyRescale = false;
+    ListState& L = list_;
+    L.ops = ops; L.count = count; L.tuple = tuple; L.parts = parts; L.chunkOps = chunkOps; L.out = &out;
+    L.allowVirtual = allowVirtual && enabled_;
     lastWeighed = 0;
-    int promoteWay = -1;
-    if (cacheEnabled && count >= 16) {
-        if (CacheEntry* hit = findCached(ops, count, tuple, parts, allowVirtual, chunkOps)) {
-            if (!promotable(*hit, allowVirtual)) {
-                stamp_++;
-                replay(*hit, ops);
-                cacheHits++;
-                return 0;                              // (replay() has set lastWeighed)
-            }
-            hit->valid = false;                        // the list's second coming: planned again under the longer cap (planner.h memStepCapSeen),
-            memCapNow_ = memCapSeen();                 // into the way it had: no other kept plan is evicted for it
-            promoteWay = (int)(hit - cache_);
-        }
-        bool closed = true, simple = true;
-        for (int k = 0; k < count && closed; k++) {
-            const int* op = ops + (size_t)k * tuple;
-            const int part = tuple > 7 ? op[7] : 0;
-            if (op[1] != OP_NONE) anyRescale = true;
-            if (!compactTip[op[3]] && wStamp_[(size_t)op[3] * parts + part] != stamp_) closed = false;
-            if (!compactTip[op[5]] && wStamp_[(size_t)op[5] * parts + part] != stamp_) closed = false;
-            wStamp_[(size_t)op[0] * parts + part] = stamp_;
-            if (op[1] != OP_NONE || op[0] == op[3] || op[0] == op[5] || (compactTip[op[0]] || leafPartials[op[0]]) ||
-                (tuple > 7 && op[8] != OP_NONE)) simple = false;
-        }
-        stamp_++;                                      // the marks above must not look like producers to pass 1
-        if (closed) {
-            if (preferSeenCap) memCapNow_ = memCapSeen();
-            // (a way's tags are 8 g + way + 1, g counted per way: unique, and the tags of the eight ways differ in their low three bits,
-            // which is how the engine finds the program it keeps for a plan — engine_walk.cpp runPlan)
-            const int way = promoteWay >= 0 ? promoteWay : cacheNext_;
-            if (promoteWay < 0) cacheNext_ = (cacheNext_ + 1) % CACHE_WAYS;
-            fill = &cache_[way];
-            fill->valid = false; fill->cleanAtEpoch = -1; fill->tag = ++wayGen_[way] * CACHE_WAYS + way + 1; fill->count = count; fill->tuple = tuple; fill->parts = parts; fill->chunkOps = chunkOps; fill->repeatWeights = repeatWeights; fill->memDefTables = memDefTables;
-            fill->allowVirtual = allowVirtual; fill->stepLimit = allowVirtual ? stepLimit : 0; fill->memStepCap = allowVirtual ? memCapNow_ : 0; fill->tipEpoch = compactEpoch; fill->simple = simple;
-            fill->ops.assign(ops, ops + (size_t)count * tuple);
-        }
-    }
-    info_.assign(count, OpInfo());
-    prod1_.assign(count, -1); prod2_.assign(count, -1);
-    std::vector<char> consumed(count, 0);
-    const bool memDefs = allowVirtual && memDefsOn(parts);
-    bool anyMem = false;
-
-    // ---- pass 1, list order: virtual definitions, producers, hold needs
-    for (int k = 0; k < count; k++) {
-        const int* op = ops + (size_t)k * tuple;
-        if (k + 6 < count) {                               // (a definition is 1.5 KB: the destination's two lines that matter, a few operations ahead)
-            const int* ahead = op + (size_t)6 * tuple;
-            const char* a = reinterpret_cast<const char*>(&virt_[(size_t)ahead[0] * parts + (tuple > 7 ? ahead[7] : 0)]);
-            __builtin_prefetch(a, 1); __builtin_prefetch(a + 64, 1);
-        }
-        OpInfo& o = info_[k];
-        o.dest = op[0]; o.wS = op[1]; o.rS = op[2]; o.c1 = op[3]; o.m1 = op[4]; o.c2 = op[5]; o.m2 = op[6];
-        o.part = tuple > 7 ? op[7] : 0;
-        o.tip1 = compactTip[o.c1] != 0; o.tip2 = compactTip[o.c2] != 0;
-        o.leaf1 = o.tip1 || leafPartials[o.c1] != 0; o.leaf2 = o.tip2 || leafPartials[o.c2] != 0;
-        o.virtDest = false; o.emitted = false; o.need = 0; o.size = 1;
-        const size_t kd = (size_t)o.dest * parts + o.part, kc1 = (size_t)o.c1 * parts + o.part, kc2 = (size_t)o.c2 * parts + o.part;
-        if (!o.tip1 && wStamp_[kc1] == stamp_) { prod1_[k] = wOp_[kc1]; consumed[prod1_[k]] = 1; }
-        if (!o.tip2 && wStamp_[kc2] == stamp_) { prod2_[k] = wOp_[kc2]; consumed[prod2_[k]] = 1; }
-        if (o.wS != OP_NONE) sWStamp_[(size_t)o.wS * parts + o.part] = stamp_;
-
-        const bool v1 = !o.leaf1 && virt_[kc1].on, v2 = !o.leaf2 && virt_[kc2].on;
-        const int ownScale = o.wS != OP_NONE ? o.wS : o.rS;
-        bool makeVirtual = false;
-        // (memory definitions: ONE child may be a stored internal node, or a definition that reads one — planner.h memStepCap)
-        const bool st1 = memDefs && !o.leaf1 && !v1, st2 = memDefs && !o.leaf2 && !v2;
-        if (allowVirtual && (o.leaf1 || v1 || st1) && (o.leaf2 || v2 || st2) && !(st1 && st2) && o.c1 != o.dest && o.c2 != o.dest) {
-            VirtDef& ev = virt_[kd];
-            // Steady state: the same op on the same buffers as when `dest` was last defined, its virtual children unchanged
-            // (same definition version) and re-confirmed in this list exactly as they were fresh then -> the definition
-            // stands; only its matrix snapshots are refreshed.  Anything else rebuilds it.
-            auto childSame = [&](size_t c, bool tip, bool sigTip, int ver, bool fresh) {      // c: the child's key
-                if (tip != sigTip) return false;
-                if (tip) return true;
-                const VirtDef& cv = virt_[c];
-                return fresh && cv.stamp == stamp_ && cv.version == ver;
-            };
-            if (ev.on && ev.memKey < 0 && !st1 && !st2 && ev.nSteps <= stepCap() && ev.sigC1 == o.c1 && ev.sigM1 == o.m1 && ev.sigC2 == o.c2 && ev.sigM2 == o.m2 && ev.sigScale == ownScale &&
-                ev.sigMem1 == (o.leaf1 && !o.tip1) && ev.sigMem2 == (o.leaf2 && !o.tip2) &&
-                childSame(kc1, o.leaf1, ev.sigTip1, ev.childVer1, ev.fresh1) && childSame(kc2, o.leaf2, ev.sigTip2, ev.childVer2, ev.fresh2)) {
-                for (int st = 0; st < ev.nSteps; st++) {
-                    out.snapPairs.push_back(ev.steps[st].originA); out.snapPairs.push_back(snapSlot((int)kd, st, 0));
-                    out.snapPairs.push_back(ev.steps[st].originB); out.snapPairs.push_back(snapSlot((int)kd, st, 1));
-                }
-                ev.stamp = stamp_;
-                makeVirtual = true;
-            } else {
-                VirtDef saved = ev;
-                if (saved.on) clearVirtualKey((int)kd);
-                makeVirtual = buildVirtual((int)kd, o.leaf1 || st1 ? o.c1 : (int)kc1, o.leaf1 || st1, (o.leaf1 && !o.tip1) || st1, o.m1,
-                                           o.leaf2 || st2 ? o.c2 : (int)kc2, o.leaf2 || st2, (o.leaf2 && !o.tip2) || st2, o.m2, ownScale, out.snapPairs, st1, st2);
-                if (!makeVirtual && saved.on) { virt_[kd] = saved; tagOf_[kd] = saved.cacheTag; tagEpoch_++; registerVirtual((int)kd); }
-                if (makeVirtual) {
-                    VirtDef& nv = virt_[kd];
-                    nv.version = ++virtVersion_;
-                    nv.sigC1 = o.c1; nv.sigM1 = o.m1; nv.sigC2 = o.c2; nv.sigM2 = o.m2; nv.sigScale = ownScale;
-                    nv.sigTip1 = o.leaf1 || st1; nv.sigTip2 = o.leaf2 || st2; nv.sigMem1 = (o.leaf1 && !o.tip1) || st1; nv.sigMem2 = (o.leaf2 && !o.tip2) || st2;
-                    nv.fresh1 = !nv.sigTip1 && virt_[kc1].stamp == stamp_; nv.fresh2 = !nv.sigTip2 && virt_[kc2].stamp == stamp_;
-                    nv.childVer1 = nv.sigTip1 ? -1 : virt_[kc1].version; nv.childVer2 = nv.sigTip2 ? -1 : virt_[kc2].version;
-                }
-            }
-        }
-        if (!makeVirtual && virt_[kd].on) clearVirtualKey((int)kd);      // whatever it was, this op replaces it
-        o.virtDest = makeVirtual;
-        wStamp_[kd] = stamp_; wOp_[kd] = k;
-
-        if (makeVirtual && virt_[kd].memKey >= 0) anyMem = true;
-        if (!makeVirtual) {
-            realInfo(k);
-            // two memory definitions, each behind its own operand's program, can take a hold slot more than the walk has: store them
-            if (memDefs && o.need > popcount2(allSlots_)) {
-                for (int w = 0; w < 2; w++) {
-                    const int ck = key(w ? o.c2 : o.c1, o.part);
-                    if ((w ? o.tip2 : o.tip1) || operandOp(ck) < 0 || wStamp_[ck] != stamp_) continue;
-                    const int x = wOp_[ck];
-                    clearVirtualKey(ck);
-                    info_[x].virtDest = false;
-                    realInfo(x);
-                }
-                realInfo(k);
-            }
-        }
-    }
-    // Memory definitions: who consumes whom is settled backwards — a definition nothing in this list evaluates is stored after all (the
-    // root of a tree: whoever reads it would otherwise evaluate it from memory in a launch of its own), and a stored operand is
-    // consumed by a definition only where that definition is evaluated
-    if (anyMem) {
-        std::fill(consumed.begin(), consumed.end(), 0);
-        std::vector<char> live(count, 0), absorbed(count, 0);      // evaluated by a real op of the list; its steps stand in a longer definition
-        for (int k = count - 1; k >= 0; k--) {
-            OpInfo& o = info_[k];
-            const int kd = key(o.dest, o.part);
-            if (o.virtDest && virt_[kd].memKey >= 0 && !live[k] && !absorbed[k]) { clearVirtualKey(kd); o.virtDest = false; realInfo(k); }
-            if (o.virtDest) {
-                const int a = live[k] ? operandOp(kd) : -1;
-                if (a >= 0) consumed[a] = 1;
-                for (int w = 0; w < 2; w++) {
-                    const int prod = w ? prod2_[k] : prod1_[k];
-                    if (prod >= 0 && info_[prod].virtDest) absorbed[prod] = 1;
-                }
-                continue;
-            }
-            for (int w = 0; w < 2; w++) {
-                const int prod = w ? prod2_[k] : prod1_[k];
-                if (prod < 0) continue;
-                if (info_[prod].virtDest) live[prod] = 1; else consumed[prod] = 1;
-            }
-        }
-    }
-
+    if (cacheStep(L)) return 0;                        // (replay() has set lastWeighed)
+    definePass(L);
+    if (L.anyMem) settleMemoryConsumers(L);
     // ---- pass 2: walk order.  One slice per partition; inside it, every unconsumed real op is a root of the forest.
     // With chunkOps > 0 the forest is peeled in waves: a wave = the maximal subtrees of at most chunkOps micro-operations
     // among what is left, one slice each; what is above them reads their (stored) roots in a later wave.
-    std::vector<int> partsSeen;
-    {
-        std::vector<char> seen(parts, 0);
-        for (int k = 0; k < count; k++) if (!seen[info_[k].part]) { seen[info_[k].part] = 1; partsSeen.push_back(info_[k].part); }
-    }
-    lastWaves = 0;
+    listPartitions(L);
     // (planner.h repeatWeights: a closed list — one that is cached — of one partition in which nothing rescales)
-    const bool repeatW = repeatWeights && fill && parts == 1 && !anyRescale && allowVirtual;
-    int cutOps = chunkOps, cutTop = chunkTopOps;
-    bool ruled = !repeatW;
-    std::vector<int> weight, chunkRoots, stack;
-    for (int part : partsSeen) {
-        int wave = 0;
-        for (;;) {
-            bool chunked = false;
-            int chunk = (wave == 0 || cutTop <= 0) ? cutOps : std::min(cutOps, cutTop);
-            if (chunk > 0 || !ruled) {
-                // micro-operations below every op that is still to be emitted (children precede parents in the list)
-                weight.assign(count, 0);
-                long total = 0;
-                for (int k = 0; k < count; k++) {
-                    const OpInfo& o = info_[k];
-                    if (o.part != part || o.virtDest || o.emitted) continue;
-                    int w = 1;
-                    for (int c = 0; c < 2; c++) {
-                        const bool tip = c ? o.tip2 : o.tip1;
-                        const int buf = c ? o.c2 : o.c1, prod = c ? prod2_[k] : prod1_[k];
-                        if (tip) continue;
-                        if (prod >= 0 && !info_[prod].virtDest) { if (!info_[prod].emitted) w += weight[prod]; }
-                        else if (virt_[key(buf, o.part)].on) {
-                            if (repeatW && plainDefinition(virt_[key(buf, o.part)])) { w += 1; continue; }      // (a table row gathered by this op)
-                            // (a memory definition under memDefTables: its path, and a gather per plain clade off it)
-                            w += repeatW && memDefTables && virt_[key(buf, o.part)].memKey >= 0 ? memDefWeight(virt_[key(buf, o.part)]) : virt_[key(buf, o.part)].nSteps;
-                            const int a = anyMem ? operandOp(key(buf, o.part)) : -1;      // (a memory definition: its operand's program comes with it)
-                            if (a >= 0 && !info_[a].emitted) w += weight[a];
-                        }
-                    }
-                    weight[k] = w;
-                    if (!consumed[k]) total += w;
-                }
-                if (!ruled) {                              // the whole plan's weight is known: the slice sizes that go with it
-                    ruled = true;
-                    lastWeighed = total;
-                    if (repeatChunkRule) repeatChunkRule(total, cutOps, cutTop);
-                    chunk = cutOps;
-                }
-                if (chunk > 0 && total > chunk + chunk / 2) {
-                    chunkRoots.clear(); stack.clear();
-                    for (int k = count - 1; k >= 0; k--) {
-                        const OpInfo& o = info_[k];
-                        if (o.part == part && !o.virtDest && !o.emitted && !consumed[k]) stack.push_back(k);
-                    }
-                    while (!stack.empty()) {
-                        const int k = stack.back(); stack.pop_back();
-                        if (weight[k] <= chunk) { chunkRoots.push_back(k); continue; }
-                        bool descended = false;
-                        for (int c = 1; c >= 0; c--) {
-                            int prod = c ? prod2_[k] : prod1_[k];
-                            if (anyMem && !(c ? info_[k].tip2 : info_[k].tip1) && (prod < 0 || info_[prod].virtDest)) prod = operandOp(key(c ? info_[k].c2 : info_[k].c1, part));
-                            if (prod >= 0 && !info_[prod].virtDest && !info_[prod].emitted) { stack.push_back(prod); descended = true; }
-                        }
-                        if (!descended) chunkRoots.push_back(k);      // heavier than a chunk but nothing below is left to peel
-                    }
-                    // a DAG may reach the same op twice: emit once
-                    std::sort(chunkRoots.begin(), chunkRoots.end());
-                    chunkRoots.erase(std::unique(chunkRoots.begin(), chunkRoots.end()), chunkRoots.end());
-                    // only worth a wave of its own when it really runs side by side
-                    if (chunkRoots.size() >= 2) {
-                        for (int k : chunkRoots) {
-                            if (info_[k].emitted) continue;
-                            PlanSeg seg; seg.progStart = (int)out.prog.size(); seg.partition = part; seg.wave = wave;
-                            emitReal(k, allSlots_, out);
-                            seg.progCount = (int)out.prog.size() - seg.progStart;
-                            out.segs.push_back(seg);
-                        }
-                        chunked = true;
-                        wave++;
-                    }
-                }
-            }
-            if (chunked) continue;
-            PlanSeg seg; seg.progStart = (int)out.prog.size(); seg.partition = part; seg.wave = wave;
-            for (int k = 0; k < count; k++) {
-                OpInfo& o = info_[k];
-                if (o.part != part || o.virtDest || o.emitted) continue;
-                if (!consumed[k]) emitReal(k, allSlots_, out);
-            }
-            // virtual nodes of a rescaling evaluation still owe their scale factors if nothing above evaluated them
-            for (int k = 0; k < count; k++) {
-                const OpInfo& o = info_[k];
-                if (o.part != part || !o.virtDest || o.wS == OP_NONE) continue;
-                if (sDone_[(size_t)o.wS * parts + o.part] != stamp_) emitVirtual(key(o.dest, o.part), allSlots_, true, out);
-            }
-            seg.progCount = (int)out.prog.size() - seg.progStart;
-            if (seg.progCount > 0) { out.segs.push_back(seg); wave++; }
-            break;
-        }
-        lastWaves = std::max(lastWaves, wave);
-    }
+    L.repeatW = repeatWeights && L.fill && parts == 1 && !L.anyRescale && L.allowVirtual;
+    L.cutOps = chunkOps; L.cutTop = chunkTopOps; L.ruled = !L.repeatW;
+    lastWaves = 0;
+    for (int part : L.partsSeen) lastWaves = std::max(lastWaves, emitPartition(L, part));
     // launches run wave by wave: order the slices that way (stable: partitions keep their order inside a wave)
     std::stable_sort(out.segs.begin(), out.segs.end(), [](const PlanSeg& a, const PlanSeg& b) { return a.wave < b.wave; });
-    linkSlices(out, repeatW ? (memDefTables ? 2 : 1) : 0);
-    if (fill) {
-        // (the entry TAKES the program — `out` is left with whatever the entry held — and `planned` names the entry's copy, as on
-        // a hit; the definitions of unstored destinations are copied, steps in use only, over whatever the way held before)
-        fill->plan.clear();
-        fill->plan.prog.swap(out.prog); fill->plan.segs.swap(out.segs); fill->plan.deps.swap(out.deps);
-        fill->plan.launchOrder.swap(out.launchOrder); fill->plan.snapPairs.swap(out.snapPairs); fill->plan.runs.swap(out.runs); fill->plan.leaves = out.leaves;
-        planned = &fill->plan;
-        if ((int)fill->defs.size() < count) fill->defs.resize(count);
-        fill->defOn.assign(count, 0);
-        for (int k = 0; k < count; k++)
-            if (info_[k].virtDest) { const int kk = key(info_[k].dest, info_[k].part); virt_[kk].cacheTag = fill->tag; tagOf_[kk] = fill->tag; tagEpoch_++; fill->defs[k] = virt_[kk]; fill->defOn[k] = 1; }
-        plannedTag = fill->tag;
-        fill->stored = lastStored; fill->memReads = lastMemReads; fill->holds = lastHolds; fill->waves = lastWaves; fill->weighed = lastWeighed;
-        fill->valid = true;
-    }
+    linkSlices(out, L.repeatW ? (memDefTables ? 2 : 1) : 0);
+    if (L.fill) fillCache(L);
     return 0;
 }
 
-// Which slices read what other slices of the same plan store (planner.h PlanSeg): a slice reads a stored result only as a
-// PK_MEM operand, and only of a slice of an EARLIER wave of the same partition (tests/native/plan_check.cpp checks both).
+// Cache step: closed list?  then the plan may be in the cache (planner.h CacheEntry).  Reads the list, the cache and the tips' flags.
+// true: the plan was kept and has been replayed (planned, plannedTag and the statistics are the entry's) — plan() is done.  false: the
+// list is to be planned, under memCapNow_ — raised to the longer cap here for a kept list's second coming (its entry is dropped) and
+// for a new closed list under preferSeenCap; L.fill is the entry to put the plan into, its identity written, when the list is closed,
+// L.anyRescale says whether it has a write-mode operation and L.simple is replayCached's `simple`.  Leaves no mark behind: stamp_ is
+// moved past the ones its scan made.
+bool WalkPlanner::cacheStep(ListState& L) {
+    const int* ops = L.ops;
+    const int count = L.count, tuple = L.tuple;
+    L.fill = nullptr; L.anyRescale = false; L.simple = false;
+    if (!cacheEnabled || count < 16) return false;
+    int promoteWay = -1;
+    if (CacheEntry* hit = findCached(ops, count, tuple, L.parts, L.allowVirtual, L.chunkOps)) {
+        if (!promotable(*hit, L.allowVirtual)) {
+            stamp_++;
+            replay(*hit, ops);
+            cacheHits++;
+            return true;
+        }
+        hit->valid = false;                        // the list's second coming: planned again under the longer cap (planner.h memStepCapSeen),
+        memCapNow_ = memCapSeen();                 // into the way it had: no other kept plan is evicted for it
+        promoteWay = (int)(hit - cache_);
+    }
+    bool closed = true, simple = true;
+    for (int k = 0; k < count && closed; k++) {
+        const int* op = ops + (size_t)k * tuple;
+        const int part = tuple > 7 ? op[7] : 0;
+        if (op[1] != OP_NONE) L.anyRescale = true;
+        if (!compactTip[op[3]] && wStamp_[key(op[3], part)] != stamp_) closed = false;
+        if (!compactTip[op[5]] && wStamp_[key(op[5], part)] != stamp_) closed = false;
+        wStamp_[key(op[0], part)] = stamp_;
+        if (op[1] != OP_NONE || op[0] == op[3] || op[0] == op[5] || (compactTip[op[0]] || leafPartials[op[0]]) ||
+            (tuple > 7 && op[8] != OP_NONE)) simple = false;
+    }
+    stamp_++;                                      // the marks above must not look like producers to pass 1
+    if (!closed) return false;
+    if (preferSeenCap) memCapNow_ = memCapSeen();
+    // (a way's tags are 8 g + way + 1, g counted per way: unique, and the tags of the eight ways differ in their low three bits,
+    // which is how the engine finds the program it keeps for a plan — engine_walk.cpp runPlan)
+    const int way = promoteWay >= 0 ? promoteWay : cacheNext_;
+    if (promoteWay < 0) cacheNext_ = (cacheNext_ + 1) % CACHE_WAYS;
+    CacheEntry* fill = &cache_[way];
+    fill->valid = false; fill->cleanAtEpoch = -1; fill->tag = ++wayGen_[way] * CACHE_WAYS + way + 1; fill->count = count; fill->tuple = tuple; fill->parts = L.parts; fill->chunkOps = L.chunkOps; fill->repeatWeights = repeatWeights; fill->memDefTables = memDefTables;
+    fill->allowVirtual = L.allowVirtual; fill->stepLimit = L.allowVirtual ? stepLimit : 0; fill->memStepCap = L.allowVirtual ? memCapNow_ : 0; fill->tipEpoch = compactEpoch; fill->simple = simple;
+    fill->ops.assign(ops, ops + (size_t)count * tuple);
+    L.fill = fill; L.simple = simple;
+    return false;
+}
+
+// Pass 1, list order: virtual definitions, producers, hold needs.  Reads the list and the definitions the planner holds; leaves info_
+// complete for every op (Operand::prod, virtDest, and need / size of the real ones), the definitions of this list's destinations made,
+// re-confirmed or dropped (their snapshot copies in out.snapPairs), wStamp_ / wOp_ naming the op that writes each key and sWStamp_
+// the scale buffers written, L.consumed and L.anyMem.
+void WalkPlanner::definePass(ListState& L) {
+    info_.assign(L.count, OpInfo());
+    L.consumed.assign(L.count, 0);
+    L.memDefs = L.allowVirtual && memDefsOn(L.parts);
+    L.anyMem = false;
+    for (int k = 0; k < L.count; k++) {
+        if (k + 6 < L.count) {                             // (a definition is 1.5 KB: the destination's two lines that matter, a few operations ahead)
+            const int* ahead = L.ops + (size_t)(k + 6) * L.tuple;
+            const char* a = reinterpret_cast<const char*>(&virt_[key(ahead[0], L.tuple > 7 ? ahead[7] : 0)]);
+            __builtin_prefetch(a, 1); __builtin_prefetch(a + 64, 1);
+        }
+        defineOp(L, k);
+    }
+}
+
+// The signature of a definition — the op that made it, as far as it decides what the definition is: children, matrices, scale buffer,
+// which children are leaves and which of those are read from memory, and the version of a child that is a definition itself.
+// definitionStands reads what signDefinition wrote: the steady state — the same op on the same buffers as when `dest` was last defined,
+// its virtual children unchanged (same definition version) and re-confirmed in this list exactly as they were fresh then -> the
+// definition stands; only its matrix snapshots are refreshed.  Anything else rebuilds it.  (stored: the child is a stored internal node
+// read as a leaf — a memory definition, which is rebuilt every time.)
+bool WalkPlanner::definitionStands(const VirtDef& ev, const OpInfo& o, int ownScale, const bool stored[2]) const {
+    const Operand &a = o.ch[0], &b = o.ch[1];
+    auto childSame = [&](const Operand& c, bool sigTip, int ver, bool fresh) {
+        if (c.leaf != sigTip) return false;
+        if (c.leaf) return true;
+        const VirtDef& cv = virt_[key(c.buf, o.part)];
+        return fresh && cv.stamp == stamp_ && cv.version == ver;
+    };
+    return ev.on && ev.memKey < 0 && !stored[0] && !stored[1] && ev.nSteps <= stepCap() &&
+           ev.sigC1 == a.buf && ev.sigM1 == a.mat && ev.sigC2 == b.buf && ev.sigM2 == b.mat && ev.sigScale == ownScale &&
+           ev.sigMem1 == (a.leaf && !a.tip) && ev.sigMem2 == (b.leaf && !b.tip) &&
+           childSame(a, ev.sigTip1, ev.childVer1, ev.fresh1) && childSame(b, ev.sigTip2, ev.childVer2, ev.fresh2);
+}
+
+void WalkPlanner::signDefinition(VirtDef& nv, const OpInfo& o, int ownScale, const bool stored[2]) {
+    const Operand &a = o.ch[0], &b = o.ch[1];
+    const VirtDef &va = virt_[key(a.buf, o.part)], &vb = virt_[key(b.buf, o.part)];
+    nv.version = ++virtVersion_;
+    nv.sigC1 = a.buf; nv.sigM1 = a.mat; nv.sigC2 = b.buf; nv.sigM2 = b.mat; nv.sigScale = ownScale;
+    nv.sigTip1 = a.leaf || stored[0]; nv.sigTip2 = b.leaf || stored[1];
+    nv.sigMem1 = (a.leaf && !a.tip) || stored[0]; nv.sigMem2 = (b.leaf && !b.tip) || stored[1];
+    nv.fresh1 = !nv.sigTip1 && va.stamp == stamp_; nv.fresh2 = !nv.sigTip2 && vb.stamp == stamp_;
+    nv.childVer1 = nv.sigTip1 ? -1 : va.version; nv.childVer2 = nv.sigTip2 ? -1 : vb.version;
+}
+
+// Pass 1 for op k (its children are earlier ops of the list, or come from outside it): fills info_[k], marks the ops that produce its
+// children as consumed, and decides whether its destination is a definition (re-confirmed, or built) or real data; a real one gets its
+// hold need and size.
+void WalkPlanner::defineOp(ListState& L, int k) {
+    const int* op = L.ops + (size_t)k * L.tuple;
+    Plan& out = *L.out;
+    OpInfo& o = info_[k];
+    o.dest = op[0]; o.wS = op[1]; o.rS = op[2];
+    o.part = L.tuple > 7 ? op[7] : 0;
+    o.virtDest = false; o.emitted = false; o.need = 0; o.size = 1;
+    const int kd = key(o.dest, o.part);
+    int kc[2];
+    for (int w = 0; w < 2; w++) {
+        Operand& c = o.ch[w];
+        c.buf = op[3 + 2 * w]; c.mat = op[4 + 2 * w];
+        c.tip = compactTip[c.buf] != 0; c.leaf = c.tip || leafPartials[c.buf] != 0;
+        kc[w] = key(c.buf, o.part);
+        c.prod = -1;
+        if (!c.tip && wStamp_[kc[w]] == stamp_) { c.prod = wOp_[kc[w]]; L.consumed[c.prod] = 1; }
+    }
+    if (o.wS != OP_NONE) sWStamp_[scaleKey(o.wS, o.part)] = stamp_;
+
+    const int ownScale = o.wS != OP_NONE ? o.wS : o.rS;
+    bool makeVirtual = false;
+    // (memory definitions: ONE child may be a stored internal node, or a definition that reads one — planner.h memStepCap)
+    bool virt[2], stored[2], asLeaf[2];
+    for (int w = 0; w < 2; w++) {
+        virt[w] = !o.ch[w].leaf && virt_[kc[w]].on;
+        stored[w] = L.memDefs && !o.ch[w].leaf && !virt[w];
+        asLeaf[w] = o.ch[w].leaf || stored[w];
+    }
+    if (L.allowVirtual && (asLeaf[0] || virt[0]) && (asLeaf[1] || virt[1]) && !(stored[0] && stored[1]) && o.ch[0].buf != o.dest && o.ch[1].buf != o.dest) {
+        VirtDef& ev = virt_[kd];
+        if (definitionStands(ev, o, ownScale, stored)) {
+            for (int st = 0; st < ev.nSteps; st++) {
+                out.snapPairs.push_back(ev.steps[st].originA); out.snapPairs.push_back(snapSlot(kd, st, 0));
+                out.snapPairs.push_back(ev.steps[st].originB); out.snapPairs.push_back(snapSlot(kd, st, 1));
+            }
+            ev.stamp = stamp_;
+            makeVirtual = true;
+        } else {
+            VirtDef saved = ev;
+            if (saved.on) clearVirtualKey(kd);
+            const Operand &a = o.ch[0], &b = o.ch[1];
+            makeVirtual = buildVirtual(kd, asLeaf[0] ? a.buf : kc[0], asLeaf[0], (a.leaf && !a.tip) || stored[0], a.mat,
+                                       asLeaf[1] ? b.buf : kc[1], asLeaf[1], (b.leaf && !b.tip) || stored[1], b.mat, ownScale, out.snapPairs, stored[0], stored[1]);
+            if (!makeVirtual && saved.on) { virt_[kd] = saved; tagOf_[kd] = saved.cacheTag; tagEpoch_++; registerVirtual(kd); }
+            if (makeVirtual) signDefinition(virt_[kd], o, ownScale, stored);
+        }
+    }
+    if (!makeVirtual && virt_[kd].on) clearVirtualKey(kd);      // whatever it was, this op replaces it
+    o.virtDest = makeVirtual;
+    wStamp_[kd] = stamp_; wOp_[kd] = k;
+
+    if (makeVirtual && virt_[kd].memKey >= 0) L.anyMem = true;
+    if (!makeVirtual) {
+        realInfo(k);
+        // two memory definitions, each behind its own operand's program, can take a hold slot more than the walk has: store them
+        if (L.memDefs && o.need > popcount2(allSlots_)) {
+            for (int w = 0; w < 2; w++) {
+                if (o.ch[w].tip || operandOp(kc[w]) < 0 || wStamp_[kc[w]] != stamp_) continue;
+                const int x = wOp_[kc[w]];
+                clearVirtualKey(kc[w]);
+                info_[x].virtDest = false;
+                realInfo(x);
+            }
+            realInfo(k);
+        }
+    }
+}
+
+// Backward settlement of who consumes a memory definition (only when pass 1 made one).
+// Memory definitions: who consumes whom is settled backwards — a definition nothing in this list evaluates is stored after all (the
+// root of a tree: whoever reads it would otherwise evaluate it from memory in a launch of its own), and a stored operand is
+// consumed by a definition only where that definition is evaluated.  Reads info_ and the definitions; leaves L.consumed rebuilt,
+// and the unevaluated memory definitions dropped, their ops real (need / size set).
+void WalkPlanner::settleMemoryConsumers(ListState& L) {
+    const int count = L.count;
+    std::vector<char>& consumed = L.consumed;
+    std::fill(consumed.begin(), consumed.end(), 0);
+    std::vector<char> live(count, 0), absorbed(count, 0);      // evaluated by a real op of the list; its steps stand in a longer definition
+    for (int k = count - 1; k >= 0; k--) {
+        OpInfo& o = info_[k];
+        const int kd = key(o.dest, o.part);
+        if (o.virtDest && virt_[kd].memKey >= 0 && !live[k] && !absorbed[k]) { clearVirtualKey(kd); o.virtDest = false; realInfo(k); }
+        if (o.virtDest) {
+            const int a = live[k] ? operandOp(kd) : -1;
+            if (a >= 0) consumed[a] = 1;
+            for (int w = 0; w < 2; w++) {
+                const int prod = o.ch[w].prod;
+                if (prod >= 0 && info_[prod].virtDest) absorbed[prod] = 1;
+            }
+            continue;
+        }
+        for (int w = 0; w < 2; w++) {
+            const int prod = o.ch[w].prod;
+            if (prod < 0) continue;
+            if (info_[prod].virtDest) live[prod] = 1; else consumed[prod] = 1;
+        }
+    }
+}
+
+// The partitions the list names, in the order of their first operation: L.partsSeen.
+void WalkPlanner::listPartitions(ListState& L) {
+    L.partsSeen.clear();
+    std::vector<char> seen(L.parts, 0);
+    for (int k = 0; k < L.count; k++) if (!seen[info_[k].part]) { seen[info_[k].part] = 1; L.partsSeen.push_back(info_[k].part); }
+}
+
+// Pass 2 for one partition: wave after wave peeled off while what is left weighs more than a chunk and a half, then the remainder as
+// one slice.  Reads info_, L.consumed and the cut (L.cutOps / cutTop / ruled); appends the partition's slices (progStart, progCount,
+// partition, wave) and their micro-operations to the plan, marks the ops emitted, and returns the number of waves.  The first weighing
+// of a list that is weighed for compression settles lastWeighed and the cut (planner.h repeatChunkRule).
+int WalkPlanner::emitPartition(ListState& L, int part) {
+    int wave = 0;
+    for (;;) {
+        int chunk = (wave == 0 || L.cutTop <= 0) ? L.cutOps : std::min(L.cutOps, L.cutTop);
+        if (chunk > 0 || !L.ruled) {
+            const long total = weighPartition(L, part);
+            if (!L.ruled) {                              // the whole plan's weight is known: the slice sizes that go with it
+                L.ruled = true;
+                lastWeighed = total;
+                if (repeatChunkRule) repeatChunkRule(total, L.cutOps, L.cutTop);
+                chunk = L.cutOps;
+            }
+            if (chunk > 0 && total > chunk + chunk / 2 && peelWave(L, part, chunk, wave)) { wave++; continue; }
+        }
+        if (emitRemainder(L, part, wave)) wave++;
+        return wave;
+    }
+}
+
+// Weighs what is left of a partition: L.weight[k] = micro-operations below every op that is still to be emitted (children precede
+// parents in the list; 0 for the others), under L.repeatW with definitions counted as what compression leaves of them.  Returns the sum
+// over the roots (the ops nothing consumes).  Reads info_, L.consumed, the definitions.
+long WalkPlanner::weighPartition(ListState& L, int part) {
+    std::vector<int>& weight = L.weight;
+    weight.assign(L.count, 0);
+    long total = 0;
+    for (int k = 0; k < L.count; k++) {
+        const OpInfo& o = info_[k];
+        if (o.part != part || o.virtDest || o.emitted) continue;
+        int w = 1;
+        for (int c = 0; c < 2; c++) {
+            const int prod = o.ch[c].prod;
+            if (o.ch[c].tip) continue;
+            if (prod >= 0 && !info_[prod].virtDest) { if (!info_[prod].emitted) w += weight[prod]; continue; }
+            const int ck = key(o.ch[c].buf, o.part);
+            const VirtDef& v = virt_[ck];
+            if (!v.on) continue;
+            if (L.repeatW && plainDefinition(v)) { w += 1; continue; }      // (a table row gathered by this op)
+            // (a memory definition under memDefTables: its path, and a gather per plain clade off it)
+            w += L.repeatW && memDefTables && v.memKey >= 0 ? memDefWeight(v) : v.nSteps;
+            const int a = L.anyMem ? operandOp(ck) : -1;      // (a memory definition: its operand's program comes with it)
+            if (a >= 0 && !info_[a].emitted) w += weight[a];
+        }
+        weight[k] = w;
+        if (!L.consumed[k]) total += w;
+    }
+    return total;
+}
+
+// Peels one wave: the maximal subtrees of at most `chunk` micro-operations (L.weight) among what is left of the partition, one slice
+// each.  false, and nothing emitted: fewer than two such subtrees.  Reads info_, L.weight, L.consumed.
+bool WalkPlanner::peelWave(ListState& L, int part, int chunk, int wave) {
+    Plan& out = *L.out;
+    std::vector<int>&chunkRoots = L.chunkRoots, &stack = L.stack;
+    chunkRoots.clear(); stack.clear();
+    for (int k = L.count - 1; k >= 0; k--) {
+        const OpInfo& o = info_[k];
+        if (o.part == part && !o.virtDest && !o.emitted && !L.consumed[k]) stack.push_back(k);
+    }
+    while (!stack.empty()) {
+        const int k = stack.back(); stack.pop_back();
+        if (L.weight[k] <= chunk) { chunkRoots.push_back(k); continue; }
+        bool descended = false;
+        for (int c = 1; c >= 0; c--) {
+            const Operand& ch = info_[k].ch[c];
+            int prod = ch.prod;
+            if (L.anyMem && !ch.tip && (prod < 0 || info_[prod].virtDest)) prod = operandOp(key(ch.buf, part));
+            if (prod >= 0 && !info_[prod].virtDest && !info_[prod].emitted) { stack.push_back(prod); descended = true; }
+        }
+        if (!descended) chunkRoots.push_back(k);      // heavier than a chunk but nothing below is left to peel
+    }
+    // a DAG may reach the same op twice: emit once
+    std::sort(chunkRoots.begin(), chunkRoots.end());
+    chunkRoots.erase(std::unique(chunkRoots.begin(), chunkRoots.end()), chunkRoots.end());
+    // only worth a wave of its own when it really runs side by side
+    if (chunkRoots.size() < 2) return false;
+    for (int k : chunkRoots) {
+        if (info_[k].emitted) continue;
+        PlanSeg seg; seg.progStart = (int)out.prog.size(); seg.partition = part; seg.wave = wave;
+        emitReal(k, allSlots_, out);
+        seg.progCount = (int)out.prog.size() - seg.progStart;
+        out.segs.push_back(seg);
+    }
+    return true;
+}
+
+// Emits what is left of the partition as one slice of wave `wave`: every root, and the write-mode leftovers.  false: nothing was left
+// (no slice is added).  Reads info_, L.consumed, sDone_.
+bool WalkPlanner::emitRemainder(ListState& L, int part, int wave) {
+    Plan& out = *L.out;
+    PlanSeg seg; seg.progStart = (int)out.prog.size(); seg.partition = part; seg.wave = wave;
+    for (int k = 0; k < L.count; k++) {
+        const OpInfo& o = info_[k];
+        if (o.part != part || o.virtDest || o.emitted) continue;
+        if (!L.consumed[k]) emitReal(k, allSlots_, out);
+    }
+    // virtual nodes of a rescaling evaluation still owe their scale factors if nothing above evaluated them
+    for (int k = 0; k < L.count; k++) {
+        const OpInfo& o = info_[k];
+        if (o.part != part || !o.virtDest || o.wS == OP_NONE) continue;
+        if (sDone_[scaleKey(o.wS, o.part)] != stamp_) emitVirtual(key(o.dest, o.part), allSlots_, true, out);
+    }
+    seg.progCount = (int)out.prog.size() - seg.progStart;
+    if (seg.progCount > 0) out.segs.push_back(seg);
+    return seg.progCount > 0;
+}
+
+// The cache fill: the finished plan goes into L.fill.
+// (the entry TAKES the program — `out` is left with whatever the entry held — and `planned` names the entry's copy, as on
+// a hit; the definitions of unstored destinations are copied, steps in use only, over whatever the way held before)
+void WalkPlanner::fillCache(ListState& L) {
+    CacheEntry* fill = L.fill;
+    Plan& out = *L.out;
+    const int count = L.count;
+    fill->plan.clear();
+    fill->plan.prog.swap(out.prog); fill->plan.segs.swap(out.segs); fill->plan.deps.swap(out.deps);
+    fill->plan.launchOrder.swap(out.launchOrder); fill->plan.snapPairs.swap(out.snapPairs); fill->plan.runs.swap(out.runs); fill->plan.leaves = out.leaves;
+    planned = &fill->plan;
+    if ((int)fill->defs.size() < count) fill->defs.resize(count);
+    fill->defOn.assign(count, 0);
+    for (int k = 0; k < count; k++)
+        if (info_[k].virtDest) { const int kk = key(info_[k].dest, info_[k].part); virt_[kk].cacheTag = fill->tag; tagOf_[kk] = fill->tag; tagEpoch_++; fill->defs[k] = virt_[kk]; fill->defOn[k] = 1; }
+    plannedTag = fill->tag;
+    fill->stored = lastStored; fill->memReads = lastMemReads; fill->holds = lastHolds; fill->waves = lastWaves; fill->weighed = lastWeighed;
+    fill->valid = true;
+}
+
 bool WalkPlanner::plainDefinition(const VirtDef& v) const {
     if (v.memKey >= 0) return false;
     for (int s = 0; s < v.nSteps; s++) if (v.steps[s].memA || v.steps[s].memB) return false;
@@ -791,15 +891,8 @@ int WalkPlanner::memDefWeight(const VirtDef& v) const {
         else { size[t] = 1 + size[s.subA] + size[s.subB]; plain[t] = plain[s.subA] && plain[s.subB]; }
     }
     auto off = [&](int sub) { return plain[sub] ? 1 : size[sub]; };
-    int p = v.memStep, w = 1;
-    if (v.steps[p].type == VT_EXTEND) w += off(v.steps[p].subA);
-    for (int t = p + 1; t < v.nSteps; t++) {
-        const VirtStep& s = v.steps[t];
-        if (s.subA != p && s.subB != p) continue;
-        w++;
-        if (s.type == VT_JOIN) w += off(s.subA == p ? s.subB : s.subA);
-        p = t;
-    }
+    int w = 0;
+    walkMemPath(v, v.nSteps - 1, [&](int, int sub) { w += 1 + (sub >= 0 ? off(sub) : 0); });
     return w;
 }
 
@@ -837,7 +930,10 @@ template <class Pays> void plainSubRanges(const std::vector<MicroOp>& prog, int 
 }
 }  // namespace
 
-void WalkPlanner::linkSlices(Plan& out, int repeatDurations) {
+// Which slices read what other slices of the same plan store (planner.h PlanSeg): a slice reads a stored result only as a
+// PK_MEM operand, and only of a slice of an EARLIER wave of the same partition (tests/native/plan_check.cpp checks both).
+// Reads prog and the slices' ranges; leaves every slice's depStart / depCount and Plan::deps.
+void WalkPlanner::linkDependencies(Plan& out) {
     const size_t nKeys = (size_t)partialsCount_ * keyParts_;
     if (storedBy_.size() < nKeys) { storedBy_.assign(nKeys, -1); storedStamp_.assign(nKeys, 0); }
     linkStamp_++;
@@ -846,7 +942,7 @@ void WalkPlanner::linkSlices(Plan& out, int repeatDurations) {
         const PlanSeg& sg = out.segs[s];
         for (int k = sg.progStart; k < sg.progStart + sg.progCount; k++) {
             const int st = out.prog[k].storeBuf;
-            if (st >= 0) { const size_t kk = (size_t)st * keyParts_ + sg.partition; storedBy_[kk] = s; storedStamp_[kk] = linkStamp_; }
+            if (st >= 0) { const size_t kk = (size_t)key(st, sg.partition); storedBy_[kk] = s; storedStamp_[kk] = linkStamp_; }
         }
     }
     out.deps.clear();
@@ -856,7 +952,7 @@ void WalkPlanner::linkSlices(Plan& out, int repeatDurations) {
         sg.depStart = (int)out.deps.size();
         auto reads = [&](int kind, int buf) {
             if (kind != PK_MEM) return;
-            const size_t kk = (size_t)buf * keyParts_ + sg.partition;
+            const size_t kk = (size_t)key(buf, sg.partition);
             if (kk >= nKeys || storedStamp_[kk] != linkStamp_) return;
             const int by = storedBy_[kk];
             if (by == s || mark[by] == s) return;
@@ -865,24 +961,33 @@ void WalkPlanner::linkSlices(Plan& out, int repeatDurations) {
         };
         for (int k = sg.progStart; k < sg.progStart + sg.progCount; k++) { reads(out.prog[k].k1, out.prog[k].a1); reads(out.prog[k].k2, out.prog[k].a2); }
         sg.depCount = (int)out.deps.size() - sg.depStart;
-        sg.tail = 0;
     }
-    // tickets (planner.h PlanSeg::next): does every slice have at most one dependant?
-    {
-        std::vector<int> dependants(n, 0);
-        for (int s = 0; s < n; s++) out.segs[s].next = -1;
-        for (int s = 0; s < n; s++)
-            for (int d = out.segs[s].depStart; d < out.segs[s].depStart + out.segs[s].depCount; d++) { dependants[out.deps[d]]++; out.segs[out.deps[d]].next = s; }
-        bool forest = n > 0;
-        int leaves = 0;
-        for (int s = 0; s < n; s++) {
-            if (dependants[s] > 1 || out.segs[s].progCount <= 0) forest = false;
-            if (out.segs[s].depCount == 0) leaves++;
-        }
-        out.leaves = forest ? leaves : 0;
+}
+
+namespace {
+// tickets (planner.h PlanSeg::next): does every slice have at most one dependant?  Reads the dependencies; leaves every slice's
+// `next` and Plan::leaves (0: no forest, or an empty slice).
+void ticketForest(Plan& out) {
+    const int n = (int)out.segs.size();
+    std::vector<int> dependants(n, 0);
+    for (int s = 0; s < n; s++) out.segs[s].next = -1;
+    for (int s = 0; s < n; s++)
+        for (int d = out.segs[s].depStart; d < out.segs[s].depStart + out.segs[s].depCount; d++) { dependants[out.deps[d]]++; out.segs[out.deps[d]].next = s; }
+    bool forest = n > 0;
+    int leaves = 0;
+    for (int s = 0; s < n; s++) {
+        if (dependants[s] > 1 || out.segs[s].progCount <= 0) forest = false;
+        if (out.segs[s].depCount == 0) leaves++;
     }
-    // tail: own length + the longest tail among the slices that wait for this one.  Slices are sorted by wave and read only
-    // earlier waves, so one backward sweep settles every slice before the ones it reads.
+    out.leaves = forest ? leaves : 0;
+}
+
+// tail: own length + the longest tail among the slices that wait for this one.  Slices are sorted by wave and read only
+// earlier waves, so one backward sweep settles every slice before the ones it reads.  Leaves every slice's tail and the plain launch
+// order: descending tail.
+void sliceTails(Plan& out) {
+    const int n = (int)out.segs.size();
+    for (int s = 0; s < n; s++) out.segs[s].tail = 0;
     for (int s = n - 1; s >= 0; s--) {
         PlanSeg& sg = out.segs[s];
         sg.tail += sg.progCount;
@@ -894,33 +999,51 @@ void WalkPlanner::linkSlices(Plan& out, int repeatDurations) {
     out.launchOrder.resize(n);
     for (int s = 0; s < n; s++) out.launchOrder[s] = s;
     std::stable_sort(out.launchOrder.begin(), out.launchOrder.end(), [&](int a, int b) { return out.segs[a].tail > out.segs[b].tail; });
-    if (launchMachines <= 0.0 || n < 3) return;
-    // how long a slice runs: its micro-operations — under planner.h repeatWeights with every run that reads tips only counted as the one
-    // gather it becomes, and (2: planner.h memDefTables) inside any other run every plain sub-clade the same way
+}
+
+// A run that the slice DURATIONS count as one gather: more than one micro-operation, none of which stores or reads memory.  Not
+// tableCandidate of findRepeatRuns, which decides what the engine really takes from a class table: that one also asks that no
+// micro-operation of the range PAYS reciprocals, that every tip is a compact one the index knows, that the result has a consumer in the
+// slice and that the clade is within the class limit.  Who pays is known only once the engine has folded the plan (foldScaleFactors runs
+// on the finished plan, engine_walk.cpp), the index only with the alignment — the schedule is simulated before either, so the
+// durations ignore them: an estimate that can count a run the engine then leaves in the walk.  Do not merge the two.
+bool gatherRun(const std::vector<MicroOp>& prog, const PlanRun& run) {
+    bool plain = run.count > 1;
+    for (int i = run.start; plain && i < run.start + run.count; i++) {
+        const MicroOp& m = prog[(size_t)i];
+        plain = m.storeBuf < 0 && m.k1 != PK_MEM && m.k2 != PK_MEM;
+    }
+    return plain;
+}
+
+// how long a slice runs: its micro-operations — under planner.h repeatWeights with every run that reads tips only counted as the one
+// gather it becomes, and (2: planner.h memDefTables) inside any other run every plain sub-clade the same way
+std::vector<int> sliceDurations(const Plan& out, int repeatDurations) {
+    const int n = (int)out.segs.size();
     std::vector<int> duration(n);
     for (int s = 0; s < n; s++) duration[s] = out.segs[s].progCount;
-    if (repeatDurations) {
-        std::vector<PlanRun> sub;
-        for (const PlanRun& run : out.runs) {
-            bool plain = run.count > 1;
-            for (int i = run.start; plain && i < run.start + run.count; i++) {
-                const MicroOp& m = out.prog[(size_t)i];
-                plain = m.storeBuf < 0 && m.k1 != PK_MEM && m.k2 != PK_MEM;
-            }
-            int saved = plain ? run.count - 1 : 0;
-            if (!plain && repeatDurations > 1 && run.count > 1) {
-                sub.clear();
-                plainSubRanges(out.prog, run.start, run.count, [](int) { return false; }, sub);
-                for (const PlanRun& q : sub) saved += q.count - 1;
-            }
-            if (saved <= 0) continue;
-            for (int s = 0; s < n; s++)
-                if (run.start >= out.segs[s].progStart && run.start < out.segs[s].progStart + out.segs[s].progCount) { duration[s] -= saved; break; }
+    if (!repeatDurations) return duration;
+    std::vector<PlanRun> sub;
+    for (const PlanRun& run : out.runs) {
+        const bool plain = gatherRun(out.prog, run);
+        int saved = plain ? run.count - 1 : 0;
+        if (!plain && repeatDurations > 1 && run.count > 1) {
+            sub.clear();
+            plainSubRanges(out.prog, run.start, run.count, [](int) { return false; }, sub);
+            for (const PlanRun& q : sub) saved += q.count - 1;
         }
+        if (saved <= 0) continue;
+        const int s = sliceHolding(out, run.start);
+        if (s >= 0) duration[s] -= saved;
     }
-    // List scheduling on `machines` identical machines, a slice taking its length: whenever a machine is free, the ready slice
-    // (all of its dependencies finished) with the longest tail starts; the order of the starts is the launch order.
-    const int machines = std::max(1, (int)(launchMachines + 0.5));
+    return duration;
+}
+
+// List scheduling on `machines` identical machines, a slice taking its duration: whenever a machine is free, the ready slice
+// (all of its dependencies finished) with the longest tail starts; the order of the starts is the launch order.  Reads the
+// dependencies, tails and the descending-tail order; replaces Plan::launchOrder.
+void scheduleLaunchOrder(Plan& out, const std::vector<int>& duration, int machines) {
+    const int n = (int)out.segs.size();
     std::vector<int> waiting(n, 0);                       // unfinished dependencies
     std::vector<std::vector<int>> dependants(n);
     for (int s = 0; s < n; s++) {
@@ -962,6 +1085,15 @@ void WalkPlanner::linkSlices(Plan& out, int repeatDurations) {
         running.emplace_back(freeAt[m], s);
     }
     if ((int)order.size() == n) out.launchOrder = order;
+}
+}  // namespace
+
+void WalkPlanner::linkSlices(Plan& out, int repeatDurations) {
+    linkDependencies(out);
+    ticketForest(out);
+    sliceTails(out);
+    if (launchMachines <= 0.0 || out.segs.size() < 3) return;
+    scheduleLaunchOrder(out, sliceDurations(out, repeatDurations), std::max(1, (int)(launchMachines + 0.5)));
 }
 
 // a kept plan made under the first-sight cap while lists that come again have a longer one
@@ -1197,11 +1329,10 @@ void findRepeatRuns(const Plan& plan, const FoldMap* fold, RepeatIndex& idx, boo
     if (plan.runs.empty()) return;
     for (const MicroOp& m : plan.prog) if (m.smode == PS_WRITE) return;
     auto pays = [&](int i) { return fold ? fold->payStart[(size_t)i + 1] > fold->payStart[(size_t)i] : plan.prog[(size_t)i].smode == PS_READ; };
-    // the slice of every run (runs are in program order, slices tile the program in any order)
-    auto sliceEnd = [&](int at) { for (const PlanSeg& sg : plan.segs) if (at >= sg.progStart && at < sg.progStart + sg.progCount) return sg.progStart + sg.progCount; return -1; };
     // micro-operations [start, last], whose slice ends at `end`, as a candidate (a whole run, or a sub-run of one).  false: the range itself
-    // does not qualify — it stores, pays or reads something else than tips and its own results
-    auto candidate = [&](int start, int last, int end, bool sub) {
+    // does not qualify — it stores, pays or reads something else than tips and its own results.  (Stricter than gatherRun of the slice
+    // durations, which cannot know who pays: see there.)
+    auto tableCandidate = [&](int start, int last, int end, bool sub) {
         bool ok = true;
         int acc = -1, hold[3] = {-1, -1, -1};
         for (int i = start; i <= last && ok; i++) {
@@ -1233,14 +1364,16 @@ void findRepeatRuns(const Plan& plan, const FoldMap* fold, RepeatIndex& idx, boo
     std::vector<PlanRun> sub;
     for (size_t r = 0; r < plan.runs.size(); r++) {
         const PlanRun& run = plan.runs[r];
-        const int last = run.start + run.count - 1, end = sliceEnd(run.start);
+        // the slice of every run (runs are in program order, slices tile the program in any order)
+        const int s = sliceHolding(plan, run.start);
+        const int last = run.start + run.count - 1, end = s < 0 ? -1 : plan.segs[(size_t)s].progStart + plan.segs[(size_t)s].progCount;
         if (run.count <= 0 || end < 0 || last >= end) continue;
-        if (candidate(run.start, last, end, false) || !subRuns) continue;
+        if (tableCandidate(run.start, last, end, false) || !subRuns) continue;
         // not as a whole — a memory definition evaluated from memory, mostly: the plain clades inside it (planner.h RepeatRun), their
         // consumers inside the run
         sub.clear();
         plainSubRanges(plan.prog, run.start, run.count, pays, sub);
-        for (const PlanRun& q : sub) candidate(q.start, q.start + q.count - 1, last + 1, true);
+        for (const PlanRun& q : sub) tableCandidate(q.start, q.start + q.count - 1, last + 1, true);
     }
 }
 
@@ -1249,7 +1382,7 @@ void emitRepeatPlan(const Plan& plan, const std::vector<RepeatRun>& take, Repeat
     const size_t n = plan.prog.size();
     std::vector<MicroOp> mod(plan.prog);
     std::vector<char> gone(n, 0);
-    auto sliceStart = [&](int at) { for (const PlanSeg& sg : plan.segs) if (at >= sg.progStart && at < sg.progStart + sg.progCount) return sg.progStart; return 0; };
+    auto sliceStart = [&](int at) { const int s = sliceHolding(plan, at); return s < 0 ? 0 : plan.segs[(size_t)s].progStart; };
     for (const RepeatRun& rr : take) {                   // (in program order: a consumer's first operand is settled before its second)
         const PlanRun run{rr.start, rr.count};
         for (int i = run.start; i < run.start + run.count; i++) gone[(size_t)i] = 1;

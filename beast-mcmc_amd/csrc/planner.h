@@ -243,8 +243,8 @@ public:
     int bufferOf(int key) const { return key / keyParts_; }
     int partitionOf(int key) const { return key % keyParts_; }
     bool isVirtualKey(int key) const { return virt_[key].on; }
-    bool isVirtual(int buf) const { for (int k = 0; k < keyParts_; k++) if (virt_[(std::size_t)buf * keyParts_ + k].on) return true; return false; }
-    void keysOf(int buf, std::vector<int>& out) const { for (int k = 0; k < keyParts_; k++) if (virt_[(std::size_t)buf * keyParts_ + k].on) out.push_back(buf * keyParts_ + k); }
+    bool isVirtual(int buf) const { for (int k = 0; k < keyParts_; k++) if (virt_[key(buf, k)].on) return true; return false; }
+    void keysOf(int buf, std::vector<int>& out) const { for (int k = 0; k < keyParts_; k++) if (virt_[key(buf, k)].on) out.push_back(key(buf, k)); }
     const VirtDef& definition(int key) const { return virt_[key]; }
     bool virtualEnabled() const { return enabled_; }
     int snapSlot(int key, int step, int which) const { return matrixCount_ + key * 2 * maxSteps_ + 2 * step + which; }
@@ -253,7 +253,7 @@ public:
     const std::vector<int>& tipUsers(int tip) const { return tipUsers_[tip]; }       // KEYS of the definitions that read this tip
     const std::vector<int>& scaleUsers(int idx) const { return scaleUsers_[idx]; }   // ... this scale buffer
     void clearVirtualKey(int key);       // forget the definition (that range of the buffer is about to get real data)
-    void clearVirtual(int buf) { for (int k = 0; k < keyParts_; k++) clearVirtualKey(buf * keyParts_ + k); }
+    void clearVirtual(int buf) { for (int k = 0; k < keyParts_; k++) clearVirtualKey(key(buf, k)); }
     // Define `buf` as the cherry node(tipA over matrix mA, tipB over matrix mB) [read-mode scale buffer scaleIdx or PLAN_NONE]
     // (the level-scheduled T32 path, engine_levels.cpp runOperationsLevels: one partition); appends the matrix snapshot copies to snapPairs.
     bool defineCherry(int buf, int tipA, int mA, int tipB, int mB, int scaleIdx, std::vector<int>& snapPairs);
@@ -350,9 +350,13 @@ public:
     long plannedTag = 0;
 
 private:
+    // a child of an operation: its buffer and branch matrix, the op of this list that produced it (or -1);  tip: compact states;
+    // leaf: that, or uploaded tip partials
+    struct Operand { int buf, mat, prod; bool tip, leaf; };
     struct OpInfo {
-        int dest, wS, rS, c1, m1, c2, m2, part;
-        bool tip1, tip2, leaf1, leaf2, virtDest;     // tip: compact states;  leaf: that, or uploaded tip partials
+        int dest, wS, rS, part;
+        Operand ch[2];
+        bool virtDest;
         int need;           // hold slots the evaluation needs (-1: not computed yet)
         int size;           // real micro-ops below (ordering heuristic)
         bool emitted;
@@ -371,8 +375,10 @@ private:
     void realInfo(int k);                // OpInfo::need / size of the (real) op k
     int virtNeed(int buf) const { return virt_[buf].nSteps ? virt_[buf].steps[virt_[buf].nSteps - 1].need : 0; }
     void linkSlices(Plan& out, int repeatDurations = 0);           // PlanSeg::dep*, tail and Plan::launchOrder (1: whole plain runs count as one gather, 2: sub-runs too)
+    void linkDependencies(Plan& out);                              // ... its first step: PlanSeg::depStart / depCount and Plan::deps
     bool plainDefinition(const VirtDef& v) const;                  // every leaf a compact tip: what a class table can stand for (repeatWeights)
     int memDefWeight(const VirtDef& v) const;                      // a memory definition's path steps + one per plain clade off the path (memDefTables)
+    std::size_t scaleKey(int idx, int part) const { return (std::size_t)idx * parts_ + part; }      // key()'s counterpart for the per-partition marks of a scale buffer
     std::vector<int> storedBy_, storedStamp_;          // per (buffer, partition): the slice of the current plan that stores it
     int linkStamp_ = 0;
     int memCapNow_ = 0;                                // the cap of the list being planned (memStepCap, or memCapSeen())
@@ -393,7 +399,6 @@ private:
     std::vector<int> wStamp_, rStamp_, wOp_;          // per (buffer, partition)
     std::vector<int> sWStamp_, sRStamp_, sDone_;      // per scale buffer: written / read in this list, write emitted
     std::vector<OpInfo> info_;
-    std::vector<int> prod1_, prod2_;                   // op of this list that produced each child (or -1)
     unsigned allSlots_ = 3u;                           // mask of the hold slots
     int parts_ = 1;
 
@@ -426,6 +431,36 @@ private:
     void replay(const CacheEntry& e, const int* ops);
     bool promotable(const CacheEntry& e, bool allowVirtual) const;
     CacheEntry* findCached(const int* ops, int count, int tuple, int parts, bool allowVirtual, int chunkOps);
+
+    // What the steps of one plan() call hand each other (planner.cpp: "plan(): the steps"; each step's contract says which of these it
+    // reads and leaves behind).  A member for the vectors' capacity only: nothing in it outlives the call.
+    struct ListState {
+        const int* ops = nullptr;                      // plan()'s arguments
+        int count = 0, tuple = 0, parts = 1, chunkOps = 0;
+        bool allowVirtual = false;
+        Plan* out = nullptr;
+        CacheEntry* fill = nullptr;                    // cache step: the entry a closed list's plan goes into (nullptr: not kept)
+        bool anyRescale = false, simple = false;       // cache step: the list has a write-mode operation;  CacheEntry::simple
+        bool memDefs = false, anyMem = false;          // pass 1: memory definitions may be made;  one was made
+        std::vector<char> consumed;                    // pass 1, settlement: per op, its result is evaluated inside another op's program
+        std::vector<int> partsSeen;                    // the partitions the list names, in the order it names them
+        bool repeatW = false, ruled = true;            // pass 2: weigh for compression (planner.h repeatWeights);  the slice sizes are final
+        int cutOps = 0, cutTop = 0;                    // pass 2: what the plan is cut with (chunkOps / chunkTopOps, or repeatChunkRule's)
+        std::vector<int> weight, chunkRoots, stack;    // pass 2: per op, the micro-operations below it that are still to be emitted;  scratch
+    };
+    ListState list_;
+    bool cacheStep(ListState& L);
+    void definePass(ListState& L);
+    void defineOp(ListState& L, int k);
+    bool definitionStands(const VirtDef& ev, const OpInfo& o, int ownScale, const bool stored[2]) const;
+    void signDefinition(VirtDef& nv, const OpInfo& o, int ownScale, const bool stored[2]);
+    void settleMemoryConsumers(ListState& L);
+    void listPartitions(ListState& L);
+    int emitPartition(ListState& L, int part);
+    long weighPartition(ListState& L, int part);
+    bool peelWave(ListState& L, int part, int chunk, int wave);
+    bool emitRemainder(ListState& L, int part, int wave);
+    void fillCache(ListState& L);
 };
 
 }  // namespace mi355

@@ -1,7 +1,7 @@
 // plan_check_first_read.cpp — long memory definitions stored when a list first reads them (beast-mcmc_amd/csrc/planner.h
 // longMemoryOperands; the engine's use of it: engine_walk.cpp runOperationsWalk), on the CPU.  TEST INFRASTRUCTURE, not product.
 //
-// The worlds, the interpreter, the tree and the buffer-index protocol are plan_check.cpp's (included below, its main() renamed).  Chains of
+// The worlds, the interpreter, the tree and the buffer-index protocol are plan_harness.h's.  Chains of
 // full evaluations and branch moves — half of them rejected — are driven as the engine drives them: before a list that is not a full
 // evaluation is planned, the planner names the memory definitions of more than `minSteps` steps that the list reads as a child without
 // writing them or their stored operand, and they are materialised.  Asserted:
@@ -13,9 +13,7 @@
 //     cap, when it comes the second time — fewer stored nodes —, and from the third time on it is replayed from the plan cache; a move's
 //     list never makes a memory definition longer than memStepCap; with preferSeenCap set a new closed list stores no more nodes than
 //     the lists that had come again.
-#define main plan_check_main
-#include "plan_check.cpp"
-#undef main
+#include "plan_harness.h"
 
 static long g_named = 0, g_namedAgain = 0;
 
@@ -174,6 +172,7 @@ int main() {
     printf("chains whose lists stored fewer nodes when they came the second time: %ld\n", g_promoted);
     printf("new lists planned under the long cap at once that stored fewer nodes than a first sight: %ld\n", g_atOnce);
     if (g_named < 100 || g_namedAgain != 0 || g_promoted < 10 || g_atOnce < 10) { fprintf(stderr, "first-read storing or the second-sight cap was hardly exercised, or a stored definition was named again\n"); return 1; }
+    printDigest();
     printf("plan_check_first_read: OK\n");
     return 0;
 }

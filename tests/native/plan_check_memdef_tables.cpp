@@ -1,8 +1,7 @@
 // plan_check_memdef_tables.cpp — class tables for the plain clades inside memory definitions (beast-mcmc_amd/csrc/planner.h RepeatRun: sub-runs,
 // WalkPlanner::memDefTables) on the CPU.  TEST INFRASTRUCTURE, not product.
 //
-// On plan_check.cpp's harness (its worlds, tree, buffer protocol and index-level interpreter, included below with its main() renamed); the
-// compressed-plan interpreter restates the one of plan_check_slicing.cpp.  Random and caterpillar trees of 24, 48 and 200 tips and two seeded
+// On plan_harness.h's harness (its worlds, tree, buffer protocol and index-level interpreters).  Random and caterpillar trees of 24, 48 and 200 tips and two seeded
 // random trees of 1 000, definition caps 8 and 24, memory-definition caps 8 and 24 — for every list, and as the engine has them: 8 when a closed
 // list is first seen, 24 when it comes again.  Every list is planned by two planners fed the same calls, one with the feature and one with the
 // switch set (memDefTables = false), both weighing for compression.  Asserted:
@@ -14,79 +13,7 @@
 //     and the feature is part of a cached plan's identity; a plan without memory definitions is the same bytes on both sides;
 //   * the 1 000-tip trees planned under the longer cap leave no more micro-operations in the walk than under cap 8 plus their path steps,
 //     and are cut into no more slices and waves than under cap 8 plus one each.
-#define main plan_check_main
-#include "plan_check.cpp"
-#undef main
-#include <map>
-
-#define REQUIRE(cond, ...) do { if (!(cond)) { fprintf(stderr, "FAILED %s (%s:%d) [%s, list %ld]: ", #cond, __FILE__, __LINE__, g_where, g_list); fprintf(stderr, __VA_ARGS__); fprintf(stderr, "\n"); exit(1); } } while (0)
-
-// alignments that repeat: five prototype columns, 2 % of the states redrawn, ~1 % missing under two codes
-static std::vector<std::vector<uint8_t>> repeatingTips(int T, int patterns, std::mt19937& rng) {
-    std::vector<std::vector<uint8_t>> tips((size_t)T, std::vector<uint8_t>((size_t)patterns));
-    const int protos = 5;
-    std::vector<std::vector<uint8_t>> proto((size_t)protos, std::vector<uint8_t>((size_t)T));
-    for (auto& pr : proto) for (auto& s : pr) s = (uint8_t)(rng() % 4);
-    for (int p = 0; p < patterns; p++) {
-        const std::vector<uint8_t>& pr = proto[rng() % protos];
-        for (int t = 0; t < T; t++) {
-            uint8_t s = rng() % 50 == 0 ? (uint8_t)(rng() % 4) : pr[(size_t)t];
-            if (rng() % 100 == 0) s = (uint8_t)(4 + rng() % 2);
-            tips[(size_t)t][(size_t)p] = s;
-        }
-    }
-    return tips;
-}
-
-// the compressed plan on the walk kernel's register model: class-table programs first (one row per class, at the class's representative
-// pattern), then the slices of the walk in launch order, a PK_TAB operand = the pattern's class row of that clade's table
-static void runCompressed(World& w, const RepeatPlan& rp, const FoldMap& fold, const RepeatIndex& idx) {
-    const Plan& plan = rp.plan;
-    std::vector<std::vector<double>> src;
-    for (size_t i = 0; i + 1 < plan.snapPairs.size(); i += 2) src.push_back(w.mats[plan.snapPairs[i]]);
-    for (size_t i = 0; i + 1 < plan.snapPairs.size(); i += 2) w.mats[plan.snapPairs[i + 1]] = src[i / 2];
-    std::map<int, std::vector<V4>> table;
-    auto runSlice = [&](const PlanSeg& sg, bool lower) {
-        const RepeatIndex::Clade* cl = lower ? &idx.clade(sg.partition) : nullptr;
-        const int n1 = lower ? cl->D : P;
-        if (lower) table[sg.partition].assign((size_t)cl->D * C, V4());
-        for (int q = 0; q < n1; q++) {
-            const int p = lower ? cl->rep[(size_t)q] : q;
-            V4 ACC[8], H[3][8];
-            for (int k = sg.progStart; k < sg.progStart + sg.progCount; k++) {
-                const MicroOp& m = plan.prog[(size_t)k];
-                V4 r[8];
-                auto operand = [&](int kind, int a, int mat, int c, bool first) {
-                    const double* M = &w.mats[(size_t)mat][(size_t)c * 16];
-                    if (kind == PK_TIPS) return column(M, w.tips[(size_t)a][(size_t)p]);
-                    if (kind == PK_MEM) { CHECK(!lower && !w.partials[(size_t)a].empty(), m, k); V4 x; memcpy(x.v, &w.partials[(size_t)a][((size_t)c * P + p) * 4], 32); return matvec(M, x); }
-                    if (kind == PK_TAB) { CHECK(!lower && table.count(a), m, k); return matvec(M, table[a][(size_t)idx.clade(a).cls[(size_t)p] * C + c]); }
-                    if (first) { CHECK(isHoldKind(kind), m, k); return matvec(M, H[kind - PK_H0][c]); }
-                    CHECK(kind == PK_ACC, m, k);
-                    return matvec(M, ACC[c]);
-                };
-                for (int c = 0; c < C; c++) {
-                    const V4 f1 = operand(m.k1, m.a1, m.mat1, c, true), f2 = operand(m.k2, m.a2, m.mat2, c, false);
-                    for (int i = 0; i < 4; i++) r[c].v[i] = f1.v[i] * f2.v[i];
-                }
-                CHECK(m.smode != PS_WRITE, m, k);
-                const int o = rp.origin[(size_t)k];
-                double im = 1.0;
-                for (int f = fold.payStart[(size_t)o]; f < fold.payStart[(size_t)o + 1]; f++) im *= 1.0 / w.scale[(size_t)fold.members[(size_t)f]][(size_t)p];
-                if (fold.payStart[(size_t)o + 1] > fold.payStart[(size_t)o]) { CHECK(!lower, m, k); for (int c = 0; c < C; c++) for (int i = 0; i < 4; i++) r[c].v[i] *= im; }
-                if (m.storeBuf >= 0) {
-                    CHECK(!lower, m, k);
-                    if (w.partials[(size_t)m.storeBuf].empty()) w.partials[(size_t)m.storeBuf].assign((size_t)C * P * 4, 0.0);
-                    for (int c = 0; c < C; c++) memcpy(&w.partials[(size_t)m.storeBuf][((size_t)c * P + p) * 4], r[c].v, 32);
-                }
-                if (lower && k == sg.progStart + sg.progCount - 1) for (int c = 0; c < C; c++) table[sg.partition][(size_t)q * C + c] = r[c];
-                for (int c = 0; c < C; c++) { ACC[c] = r[c]; if (m.hold) H[m.hold - 1][c] = r[c]; }
-            }
-        }
-    };
-    for (const PlanSeg& sg : rp.lower) runSlice(sg, true);
-    for (int si : plan.launchOrder) runSlice(plan.segs[(size_t)si], false);
-}
+#include "plan_harness.h"
 
 // micro-operations of the upper program that head a sub-tree over tips only which a class table could have stood for: within the slice it
 // reads tips, the ACC or a hold slot of such sub-trees only, stores and pays nothing, and a micro-operation of the slice reads its result
@@ -157,7 +84,7 @@ static Compressed checkCompression(Harness& h, int foldCap) {
     REQUIRE(paid == fm.members.size(), "%zu of %zu fold members are paid by the walk", paid, fm.members.size());
     World a = h.plan, b = h.plan;
     runPlan(a, plan, h.partStart, h.partEnd, &fm);
-    runCompressed(b, rp, fm, idx);
+    runCompressed(b, rp, &fm, idx, h.partStart, h.partEnd);
     for (int buf = 0; buf < h.nBuf; buf++) {
         REQUIRE(a.partials[(size_t)buf].size() == b.partials[(size_t)buf].size(), "buffer %d", buf);
         if (!a.partials[(size_t)buf].empty()) REQUIRE(memcmp(a.partials[(size_t)buf].data(), b.partials[(size_t)buf].data(), a.partials[(size_t)buf].size() * 8) == 0, "buffer %d differs from the uncompressed plan", buf);
@@ -174,14 +101,6 @@ static Compressed checkCompression(Harness& h, int foldCap) {
     return out;
 }
 
-// (plan_check_slicing.cpp) a run every micro-operation of which reads tips, ACC or hold slots and stores nothing: one gather under the whole-run rule
-static bool plainRun(const Plan& plan, const PlanRun& run) {
-    for (int i = run.start; i < run.start + run.count; i++) {
-        const MicroOp& m = plan.prog[(size_t)i];
-        if (m.storeBuf >= 0 || m.k1 == PK_MEM || m.k2 == PK_MEM) return false;
-    }
-    return run.count > 0;
-}
 // ... and its check of a peeled slice's weight: with the switch set that rule is the planner's
 static long g_peeled = 0;
 static void checkWholeRunWeights(const Plan& plan, int chunk, int top) {
@@ -323,6 +242,7 @@ int main() {
         REQUIRE(c24.on.upper <= c8.on.upper + c24.on.unstored, "%d micro-operations left at cap 24, %d at cap 8 plus %d path steps", c24.on.upper, c8.on.upper, c24.on.unstored);
         REQUIRE(c24.slices <= c8.slices + 1 && c24.waves <= c8.waves + 1, "%d slices in %d waves at cap 24, %d in %d at cap 8", c24.slices, c24.waves, c8.slices, c8.waves);
     }
+    printDigest();
     printf("plan_check_memdef_tables: OK\n");
     return 0;
 }

@@ -2,7 +2,7 @@
 // evaluation, on the CPU.  TEST INFRASTRUCTURE, not product.
 //
 // The two worlds, the index-level interpreter of the walk kernel's register model, the tree and BEAST's buffer-index protocol are
-// plan_check.cpp's (included below, its main() renamed); what is new here is the planner setting — WalkPlanner::memStepCap > 0, which
+// plan_harness.h's; what is new here is the planner setting — WalkPlanner::memStepCap > 0, which
 // plan_check.cpp leaves at 0 — and what is asserted on top of bitwise equality with list-order evaluation:
 //   * no definition reads more than one stored internal node, and one that reads one has at most memStepCap steps;
 //   * a program never reads back a buffer its own slice stores, except as the first child of a micro-operation that stores itself (the
@@ -11,9 +11,7 @@
 //   * fewer nodes are stored than with memStepCap = 0;
 //   * a list that overwrites a stored operand without redefining the definition that reads it finds that definition in the
 //     materialise-before set, and the definition keeps the value from before the overwrite.
-#define main plan_check_main
-#include "plan_check.cpp"
-#undef main
+#include "plan_harness.h"
 
 static long g_memDefs = 0, g_inlineEvaluations = 0, g_memoryEvaluations = 0, g_forcedBefore = 0;
 
@@ -210,6 +208,7 @@ int main() {
     printf("memory definitions seen: %ld; micro-operations behind their operand's own program: %ld, reading a stored node from memory: %ld; forced before an overwrite: %ld\n",
            g_memDefs, g_inlineEvaluations, g_memoryEvaluations, g_forcedBefore);
     if (g_memDefs < 1000 || g_inlineEvaluations < 1000 || g_memoryEvaluations < 100 || g_forcedBefore < 6) { fprintf(stderr, "memory definitions were hardly exercised\n"); return 1; }
+    printDigest();
     printf("plan_check_memdefs: OK\n");
     return 0;
 }

@@ -6,37 +6,15 @@
 //    clade, D is the number of distinct sub-patterns, the representative of a class is its smallest pattern, a second index over the same
 //    data is the same index, a clade over the limit has no index and one exactly at it has, and after a subtree swap only the clades on
 //    the two paths to the root are indexed again (RepeatIndex::builds).
-// 2. The emitted plan, on plan_check.cpp's harness (its worlds, tree, buffer protocol and index-level interpreter, included below with its
-//    main() renamed): every PK_TAB operand names a clade that has a class-table program in the same plan, class-table programs pay no
-//    factors and store nothing but their table, the payments of the whole plan are those of the uncompressed plan (FoldMap through
+// 2. The emitted plan, on plan_harness.h's worlds, tree, buffer protocol and index-level interpreters: every PK_TAB operand names a
+//    clade that has a class-table program in the same plan, class-table programs pay no factors and store nothing but their table, the payments of the whole plan are those of the uncompressed plan (FoldMap through
 //    RepeatPlan::origin), and the compressed plan — tables evaluated at the representatives, consumers reading a pattern's class row —
 //    leaves every stored buffer with the bits the uncompressed plan leaves, with folding at two caps and without folding.
 // 3. RepeatRows: tables start at multiples of 128 rows and stay inside one arena.
-#define main plan_check_main
-#include "plan_check.cpp"
-#undef main
-#include <map>
+#include "plan_harness.h"
 #include <string>
 
-#define REQUIRE(cond, ...) do { if (!(cond)) { fprintf(stderr, "FAILED %s (%s:%d): ", #cond, __FILE__, __LINE__); fprintf(stderr, __VA_ARGS__); fprintf(stderr, "\n"); exit(1); } } while (0)
-
 // ---- 1. the index ------------------------------------------------------------------------------------------------------------
-static std::vector<std::vector<uint8_t>> randomTips(int T, int patterns, bool divergent, std::mt19937& rng) {
-    std::vector<std::vector<uint8_t>> tips((size_t)T, std::vector<uint8_t>((size_t)patterns));
-    const int protos = 5;
-    std::vector<std::vector<uint8_t>> proto((size_t)protos, std::vector<uint8_t>((size_t)T));
-    for (auto& pr : proto) for (auto& s : pr) s = (uint8_t)(rng() % 4);
-    for (int p = 0; p < patterns; p++) {
-        const std::vector<uint8_t>& pr = proto[rng() % protos];
-        for (int t = 0; t < T; t++) {
-            uint8_t s = divergent ? (uint8_t)(rng() % 4) : (rng() % 50 == 0 ? (uint8_t)(rng() % 4) : pr[(size_t)t]);
-            if (rng() % 100 == 0) s = (uint8_t)(4 + rng() % 2);          // ~1 % missing, under two codes
-            tips[(size_t)t][(size_t)p] = s;
-        }
-    }
-    return tips;
-}
-
 struct CladeIds { std::vector<int> id; };       // RepeatIndex id of every node of a tree
 static CladeIds internTree(const Tree& tree, RepeatIndex& idx) {
     const int N = 2 * tree.T - 1;
@@ -157,62 +135,6 @@ static void checkIndex(int T, int patterns, bool divergent, unsigned seed) {
 }
 
 // ---- 2. the emitted plan -----------------------------------------------------------------------------------------------------
-// the compressed plan on the walk kernel's register model: class-table programs first (one row per class, evaluated on the class's
-// representative pattern), then the slices of the walk, a PK_TAB operand = the pattern's class row of that clade's table
-static void runRepeatPlan(World& w, const RepeatPlan& rp, const FoldMap* fold, const RepeatIndex& idx, const std::vector<int>& partStart, const std::vector<int>& partEnd) {
-    const Plan& plan = rp.plan;
-    std::vector<std::vector<double>> src;
-    for (size_t i = 0; i + 1 < plan.snapPairs.size(); i += 2) src.push_back(w.mats[plan.snapPairs[i]]);
-    for (size_t i = 0; i + 1 < plan.snapPairs.size(); i += 2) w.mats[plan.snapPairs[i + 1]] = src[i / 2];
-    std::map<int, std::vector<V4>> table;                 // clade -> [class][category]
-    auto runSlice = [&](const PlanSeg& sg, bool lower) {
-        const RepeatIndex::Clade* cl = lower ? &idx.clade(sg.partition) : nullptr;
-        const int n0 = lower ? 0 : partStart[sg.partition], n1 = lower ? cl->D : partEnd[sg.partition];
-        if (lower) table[sg.partition].assign((size_t)cl->D * C, V4());
-        for (int q = n0; q < n1; q++) {
-            const int p = lower ? cl->rep[(size_t)q] : q;
-            V4 ACC[8], H[3][8];
-            for (int k = sg.progStart; k < sg.progStart + sg.progCount; k++) {
-                const MicroOp& m = plan.prog[(size_t)k];
-                V4 r[8];
-                auto operand = [&](int kind, int a, int mat, int c, bool first) {
-                    const double* M = &w.mats[(size_t)mat][(size_t)c * 16];
-                    if (kind == PK_TIPS) return column(M, w.tips[(size_t)a][(size_t)p]);
-                    if (kind == PK_MEM) { CHECK(!lower && !w.partials[(size_t)a].empty(), m, k); V4 x; memcpy(x.v, &w.partials[(size_t)a][((size_t)c * P + p) * 4], 32); return matvec(M, x); }
-                    if (kind == PK_TAB) { CHECK(!lower && table.count(a), m, k); return matvec(M, table[a][(size_t)idx.clade(a).cls[(size_t)p] * C + c]); }
-                    if (first) { CHECK(isHoldKind(kind), m, k); return matvec(M, H[kind - PK_H0][c]); }
-                    CHECK(kind == PK_ACC, m, k);
-                    return matvec(M, ACC[c]);
-                };
-                for (int c = 0; c < C; c++) {
-                    const V4 f1 = operand(m.k1, m.a1, m.mat1, c, true), f2 = operand(m.k2, m.a2, m.mat2, c, false);
-                    for (int i = 0; i < 4; i++) r[c].v[i] = f1.v[i] * f2.v[i];
-                }
-                CHECK(m.smode != PS_WRITE, m, k);
-                const int o = rp.origin[(size_t)k];
-                if (fold) {
-                    double im = 1.0;
-                    for (int f = fold->payStart[(size_t)o]; f < fold->payStart[(size_t)o + 1]; f++) im *= 1.0 / w.scale[(size_t)fold->members[(size_t)f]][(size_t)p];
-                    if (fold->payStart[(size_t)o + 1] > fold->payStart[(size_t)o]) { CHECK(!lower, m, k); for (int c = 0; c < C; c++) for (int i = 0; i < 4; i++) r[c].v[i] *= im; }
-                } else if (m.smode == PS_READ) {
-                    CHECK(!lower, m, k);
-                    const double im = 1.0 / w.scale[(size_t)m.scaleIdx][(size_t)p];
-                    for (int c = 0; c < C; c++) for (int i = 0; i < 4; i++) r[c].v[i] *= im;
-                }
-                if (m.storeBuf >= 0) {
-                    CHECK(!lower, m, k);
-                    if (w.partials[(size_t)m.storeBuf].empty()) w.partials[(size_t)m.storeBuf].assign((size_t)C * P * 4, 0.0);
-                    for (int c = 0; c < C; c++) memcpy(&w.partials[(size_t)m.storeBuf][((size_t)c * P + p) * 4], r[c].v, 32);
-                }
-                if (lower && k == sg.progStart + sg.progCount - 1) { CHECK(m.hold == 0, m, k); for (int c = 0; c < C; c++) table[sg.partition][(size_t)q * C + c] = r[c]; }
-                for (int c = 0; c < C; c++) { ACC[c] = r[c]; if (m.hold) H[m.hold - 1][c] = r[c]; }
-            }
-        }
-    };
-    for (const PlanSeg& sg : rp.lower) runSlice(sg, true);
-    for (int si : plan.launchOrder) runSlice(plan.segs[(size_t)si], false);
-}
-
 static long g_unstoredConsumers = 0;
 static long g_plans = 0, g_runsTaken = 0, g_runsSeen = 0, g_twoTables = 0, g_tabFirst = 0, g_tabSecond = 0, g_memWithTable = 0, g_unparked = 0, g_noFoldTaken = 0;
 static void checkCompressed(Harness& h, int limit) {
@@ -294,7 +216,7 @@ static void checkCompressed(Harness& h, int limit) {
         // snapshot copies are idempotent)
         World a = h.plan, b = h.plan;
         runPlan(a, plan, h.partStart, h.partEnd, folded ? &fm : nullptr);
-        runRepeatPlan(b, rp, folded ? &fm : nullptr, idx, h.partStart, h.partEnd);
+        runCompressed(b, rp, folded ? &fm : nullptr, idx, h.partStart, h.partEnd);
         for (int buf = 0; buf < h.nBuf; buf++) {
             REQUIRE(a.partials[(size_t)buf].size() == b.partials[(size_t)buf].size(), "buffer %d", buf);
             if (!a.partials[(size_t)buf].empty()) REQUIRE(memcmp(a.partials[(size_t)buf].data(), b.partials[(size_t)buf].data(), a.partials[(size_t)buf].size() * 8) == 0, "buffer %d differs from the uncompressed plan (fold cap %d) [%s]", buf, cap, g_where);
@@ -403,6 +325,7 @@ int main() {
     REQUIRE(g_tabFirst > 0 && g_tabSecond > 0 && g_twoTables > 0, "no node with two table children was seen");
     REQUIRE(g_unstoredConsumers > 0, "no memory definition with a table clade as its other child was seen");
     printf("  memory definitions over a table clade: %ld\n", g_unstoredConsumers);
+    printDigest();
     printf("plan_check_repeats: OK\n");
     return 0;
 }

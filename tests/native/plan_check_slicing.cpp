@@ -1,7 +1,7 @@
 // plan_check_slicing.cpp — slices cut by what compression leaves of a list (beast-mcmc_amd/csrc/planner.h WalkPlanner::repeatWeights) on the
 // CPU.  TEST INFRASTRUCTURE, not product.
 //
-// On plan_check.cpp's harness (its worlds, tree, buffer protocol and index-level interpreter, included below with its main() renamed):
+// On plan_harness.h's harness (its worlds, tree, buffer protocol and index-level interpreters):
 // random and caterpillar trees of 24, 48 and 200 tips and one seeded random tree of 1 000, definition caps 8 and 24, memory-definition
 // caps 0 and 8, every list planned twice — by two planners fed the same calls, one weighing a plain definition as its steps (the cut of
 // the uncompressed list), one as the single gather it becomes.  Under the compressed weighting
@@ -14,80 +14,8 @@
 //   * no peeled slice weighs more than its chunk unless it holds one stored node only (nothing below it was left to peel);
 //   * the 1 000-tip tree is cut into strictly fewer slices than by its list length, at the same chunk;
 //   * the same list under the other weighting is a cache miss, and a hit again under the first.
-#define main plan_check_main
-#include "plan_check.cpp"
-#undef main
-#include <map>
+#include "plan_harness.h"
 #include <set>
-
-#define REQUIRE(cond, ...) do { if (!(cond)) { fprintf(stderr, "FAILED %s (%s:%d) [%s, list %ld]: ", #cond, __FILE__, __LINE__, g_where, g_list); fprintf(stderr, __VA_ARGS__); fprintf(stderr, "\n"); exit(1); } } while (0)
-
-// alignments that repeat: five prototype columns, 2 % of the states redrawn, ~1 % missing under two codes
-static std::vector<std::vector<uint8_t>> repeatingTips(int T, int patterns, std::mt19937& rng) {
-    std::vector<std::vector<uint8_t>> tips((size_t)T, std::vector<uint8_t>((size_t)patterns));
-    const int protos = 5;
-    std::vector<std::vector<uint8_t>> proto((size_t)protos, std::vector<uint8_t>((size_t)T));
-    for (auto& pr : proto) for (auto& s : pr) s = (uint8_t)(rng() % 4);
-    for (int p = 0; p < patterns; p++) {
-        const std::vector<uint8_t>& pr = proto[rng() % protos];
-        for (int t = 0; t < T; t++) {
-            uint8_t s = rng() % 50 == 0 ? (uint8_t)(rng() % 4) : pr[(size_t)t];
-            if (rng() % 100 == 0) s = (uint8_t)(4 + rng() % 2);
-            tips[(size_t)t][(size_t)p] = s;
-        }
-    }
-    return tips;
-}
-
-// the compressed plan on the walk kernel's register model: class-table programs first (one row per class, at the class's representative
-// pattern), then the slices of the walk in launch order, a PK_TAB operand = the pattern's class row of that clade's table
-static void runCompressed(World& w, const RepeatPlan& rp, const FoldMap& fold, const RepeatIndex& idx) {
-    const Plan& plan = rp.plan;
-    std::vector<std::vector<double>> src;
-    for (size_t i = 0; i + 1 < plan.snapPairs.size(); i += 2) src.push_back(w.mats[plan.snapPairs[i]]);
-    for (size_t i = 0; i + 1 < plan.snapPairs.size(); i += 2) w.mats[plan.snapPairs[i + 1]] = src[i / 2];
-    std::map<int, std::vector<V4>> table;
-    auto runSlice = [&](const PlanSeg& sg, bool lower) {
-        const RepeatIndex::Clade* cl = lower ? &idx.clade(sg.partition) : nullptr;
-        const int n1 = lower ? cl->D : P;
-        if (lower) table[sg.partition].assign((size_t)cl->D * C, V4());
-        for (int q = 0; q < n1; q++) {
-            const int p = lower ? cl->rep[(size_t)q] : q;
-            V4 ACC[8], H[3][8];
-            for (int k = sg.progStart; k < sg.progStart + sg.progCount; k++) {
-                const MicroOp& m = plan.prog[(size_t)k];
-                V4 r[8];
-                auto operand = [&](int kind, int a, int mat, int c, bool first) {
-                    const double* M = &w.mats[(size_t)mat][(size_t)c * 16];
-                    if (kind == PK_TIPS) return column(M, w.tips[(size_t)a][(size_t)p]);
-                    if (kind == PK_MEM) { CHECK(!lower && !w.partials[(size_t)a].empty(), m, k); V4 x; memcpy(x.v, &w.partials[(size_t)a][((size_t)c * P + p) * 4], 32); return matvec(M, x); }
-                    if (kind == PK_TAB) { CHECK(!lower && table.count(a), m, k); return matvec(M, table[a][(size_t)idx.clade(a).cls[(size_t)p] * C + c]); }
-                    if (first) { CHECK(isHoldKind(kind), m, k); return matvec(M, H[kind - PK_H0][c]); }
-                    CHECK(kind == PK_ACC, m, k);
-                    return matvec(M, ACC[c]);
-                };
-                for (int c = 0; c < C; c++) {
-                    const V4 f1 = operand(m.k1, m.a1, m.mat1, c, true), f2 = operand(m.k2, m.a2, m.mat2, c, false);
-                    for (int i = 0; i < 4; i++) r[c].v[i] = f1.v[i] * f2.v[i];
-                }
-                CHECK(m.smode != PS_WRITE, m, k);
-                const int o = rp.origin[(size_t)k];
-                double im = 1.0;
-                for (int f = fold.payStart[(size_t)o]; f < fold.payStart[(size_t)o + 1]; f++) im *= 1.0 / w.scale[(size_t)fold.members[(size_t)f]][(size_t)p];
-                if (fold.payStart[(size_t)o + 1] > fold.payStart[(size_t)o]) { CHECK(!lower, m, k); for (int c = 0; c < C; c++) for (int i = 0; i < 4; i++) r[c].v[i] *= im; }
-                if (m.storeBuf >= 0) {
-                    CHECK(!lower, m, k);
-                    if (w.partials[(size_t)m.storeBuf].empty()) w.partials[(size_t)m.storeBuf].assign((size_t)C * P * 4, 0.0);
-                    for (int c = 0; c < C; c++) memcpy(&w.partials[(size_t)m.storeBuf][((size_t)c * P + p) * 4], r[c].v, 32);
-                }
-                if (lower && k == sg.progStart + sg.progCount - 1) for (int c = 0; c < C; c++) table[sg.partition][(size_t)q * C + c] = r[c];
-                for (int c = 0; c < C; c++) { ACC[c] = r[c]; if (m.hold) H[m.hold - 1][c] = r[c]; }
-            }
-        }
-    };
-    for (const PlanSeg& sg : rp.lower) runSlice(sg, true);
-    for (int si : plan.launchOrder) runSlice(plan.segs[(size_t)si], false);
-}
 
 static long g_compressedPlans = 0, g_runsTaken = 0;
 // the plan the harness has just run (h.plan holds its results; the snapshot copies are idempotent), compressed
@@ -110,20 +38,11 @@ static void checkCompression(Harness& h) {
     REQUIRE(paid == fm.members.size(), "%zu of %zu fold members are paid by the walk", paid, fm.members.size());
     World a = h.plan, b = h.plan;
     runPlan(a, plan, h.partStart, h.partEnd, &fm);
-    runCompressed(b, rp, fm, idx);
+    runCompressed(b, rp, &fm, idx, h.partStart, h.partEnd);
     for (int buf = 0; buf < h.nBuf; buf++) {
         REQUIRE(a.partials[(size_t)buf].size() == b.partials[(size_t)buf].size(), "buffer %d", buf);
         if (!a.partials[(size_t)buf].empty()) REQUIRE(memcmp(a.partials[(size_t)buf].data(), b.partials[(size_t)buf].data(), a.partials[(size_t)buf].size() * 8) == 0, "buffer %d differs from the uncompressed plan", buf);
     }
-}
-
-// a run every micro-operation of which reads tips, ACC or hold slots and stores nothing: what the weighting counts as one gather
-static bool plainRun(const Plan& plan, const PlanRun& run) {
-    for (int i = run.start; i < run.start + run.count; i++) {
-        const MicroOp& m = plan.prog[(size_t)i];
-        if (m.storeBuf >= 0 || m.k1 == PK_MEM || m.k2 == PK_MEM) return false;
-    }
-    return run.count > 0;
 }
 
 static long g_peeled = 0, g_heavy = 0;
@@ -268,6 +187,7 @@ int main() {
     const std::pair<int, int> big = scenario(1000, false, 16, 1, 10, 8, 150, 8, 3);
     printf("  1000 tips, chunk 150: %d slices by the list's length, %d by what compression leaves\n", big.first, big.second);
     REQUIRE(big.second < big.first, "%d slices against %d", big.second, big.first);
+    printDigest();
     printf("plan_check_slicing: OK\n");
     return 0;
 }
