@@ -27,6 +27,20 @@ def position_models(seed):
     return eigs, pis, rates
 
 
+def near_tie_position_models():
+    """HKY kappa = 1 + 1e-6 and kappa = 1 + 8e-8, both with pi = (.1, .2, .3, .4), and one GTR model of position_models(0), at
+    position_models' site rates -> (eigs, frequencies, site rates).  The product chain's eigenvalue gaps lie on both sides of
+    populateAuxInt's 1e-7 threshold and inside the band position_models keeps out of; tests that use this chain measure against
+    an exact yardstick (tests/markov_jumps_exact.py), not against a floor."""
+    pi = np.array([0.1, 0.2, 0.3, 0.4])
+    eigs, pis, rates = position_models(0)
+    eigs = [substmodel.hky(1.0 + 1e-6, pi), substmodel.hky(1.0 + 8e-8, pi), eigs[2]]
+    lam = rr.product_chain(eigs, rates)[2]
+    gap = np.abs(lam[:, None] - lam[None, :])
+    assert ((gap > 1e-7) & (gap < 1e-4)).any() and ((gap > 1e-9) & (gap < 1e-7)).any()
+    return eigs, [pi, pi, pis[2]], rates
+
+
 def three_registers(seed=5):
     """syn, non-syn and a general-valued register with a non-zero diagonal (which must be ignored)."""
     syn, non = rr.codon_registers(helpers.golden("robust_counting.json")["universal_code"]["table"])

@@ -3,8 +3,9 @@ beast-mcmc_amd/robustcounting.py) against the host restatement (tests/robust_cou
 ancestral sampler's byte for byte; values and totals equal by the criterion of tests/test_gpu_markov_jumps.py,
 |a - b| <= 1e-12 |b| + floor with floor = 1e-15 x (magJ / P + |J| magP / P^2) gathered the same way (the kernels and the
 restatement form every product and sum alike; the device's exp() and the host's differ in the last bit, which the difference
-quotient of populateAuxInt amplifies by 1 / |la - lb| — the case builder keeps eigenvalue gaps out of (1e-7, 1e-4)).  The
-unconditioned histories must equal the restatement exactly.
+quotient of populateAuxInt amplifies by 1 / |la - lb| — the case builder keeps eigenvalue gaps out of (1e-7, 1e-4); chains with
+gaps inside that band and under the tie threshold, and a branch of 1e-6, are in tests/test_gpu_markov_jumps_exact.py, which measures
+the whole tables against an exact yardstick instead of a floor).  The unconditioned histories must equal the restatement exactly.
 """
 import ctypes as C
 
