@@ -545,18 +545,27 @@ bool WalkPlanner::cacheStep(ListState& L) {
     const int* ops = L.ops;
     const int count = L.count, tuple = L.tuple;
     L.fill = nullptr; L.anyRescale = false; L.simple = false;
-    if (!cacheEnabled || count < 16) return false;
+    if (count < 16) return false;
     int promoteWay = -1;
     if (CacheEntry* hit = findCached(ops, count, tuple, L.parts, L.allowVirtual, L.chunkOps)) {
         if (!promotable(*hit, L.allowVirtual)) {
-            stamp_++;
-            replay(*hit, ops);
-            cacheHits++;
-            return true;
+            if (cacheEnabled) {
+                stamp_++;
+                replay(*hit, ops);
+                cacheHits++;
+                return true;
+            }
+            // cacheEnabled off: nothing is replayed — the list is planned from scratch under the cap its entry was planned under, into the
+            // way it had.  It stays a KEPT plan (a tag): what the engine does to kept plans only (folded reciprocals, class tables) does
+            // not depend on the switch, and neither does a bit of the results
+            hit->valid = false;
+            if (L.allowVirtual && hit->memStepCap > 0) memCapNow_ = hit->memStepCap;
+            promoteWay = (int)(hit - cache_);
+        } else {
+            hit->valid = false;                    // the list's second coming: planned again under the longer cap (planner.h memStepCapSeen),
+            memCapNow_ = memCapSeen();             // into the way it had: no other kept plan is evicted for it
+            promoteWay = (int)(hit - cache_);
         }
-        hit->valid = false;                        // the list's second coming: planned again under the longer cap (planner.h memStepCapSeen),
-        memCapNow_ = memCapSeen();                 // into the way it had: no other kept plan is evicted for it
-        promoteWay = (int)(hit - cache_);
     }
     bool closed = true, simple = true;
     for (int k = 0; k < count && closed; k++) {

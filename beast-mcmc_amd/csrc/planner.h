@@ -343,7 +343,7 @@ public:
     std::function<void(long weight, int& chunk, int& top)> repeatChunkRule;
     long cacheHits = 0;                  // plans served from the cache below
     long replayInPlace = 0;              // definitions a replay took over from another entry with their leaves unchanged (user lists edited in place)
-    bool cacheEnabled = true;
+    bool cacheEnabled = true;            // false: no plan is replayed — a closed list is planned from scratch every time, under the cap its kept plan had, and is kept (a tag) all the same
     // what the last plan() produced: `out`, or the cache's copy (no copy is made on a hit).  plannedTag identifies the
     // cache entry (0: not cached) so that the engine can keep what it derives from the plan.
     const Plan* planned = nullptr;

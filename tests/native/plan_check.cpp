@@ -320,6 +320,7 @@ int main(int argc, char** argv) {
     if (argc > 1 && !strcmp(argv[1], "bench")) { benchPlanner(); return 0; }
     if (argc > 1 && !strcmp(argv[1], "bench-replay")) { benchReplay(); return 0; }
     const int reps = argc > 1 ? atoi(argv[1]) : 3;
+    TopologyStats topology;
     for (int r = 0; r < reps; r++) {
         for (int T : {2, 3, 5, 8, 13, 40, 150}) {
             scenarioMcmc(T, true, false, 1000 * r + T, 60, false);
@@ -330,7 +331,22 @@ int main(int argc, char** argv) {
         for (int T : {9, 40, 150, 600}) { scenarioSteady(T, false, 6000 * r + T); scenarioSteady(T, true, 7000 * r + T); }
         scenarioPartitions(77 + r, 9); scenarioPartitions(177 + r, 40);
         scenarioHazards(5 + r);
+        // chains that change the topology (plan_harness.h scenarioTopology): plain virtual buffers and real ones, random chunk sizes and
+        // the engine's fixed ones (the plan cache's fast replay), a caterpillar, the step limit of a gradient chain mixed in
+        for (int T : {9, 40, 150}) {
+            TopologyOptions o;
+            topology.add(scenarioTopology(T, true, 8000 * r + T, 60, o));
+            o.fixedChunk = T == 9 ? 0 : T == 40 ? 8 : 20;
+            topology.add(scenarioTopology(T, true, 8100 * r + T, 60, o));
+            o.mixStepLimit = true;
+            topology.add(scenarioTopology(T, true, 8200 * r + T, 45, o));
+            topology.add(scenarioTopology(T, false, 8300 * r + T, 30, TopologyOptions()));
+        }
+        { TopologyOptions o; o.caterpillar = true; o.fixedChunk = 8; topology.add(scenarioTopology(60, true, 8400 * r + 60, 60, o)); o.mixStepLimit = true; topology.add(scenarioTopology(17, true, 8500 * r + 17, 60, o)); }
     }
+    for (int T : {40, 150}) { TopologyOptions o; o.fixedChunk = 8; topologyWithoutPlanCache(T, 8600u + (unsigned)T, 60, o); }
+    topology.print("plan_check");
+    if (topology.rejectedTopology < 10 || topology.rootRestored < 1 || topology.closedAgain < 10 || topology.cacheHits < 10 || topology.writeCycles < 10) { fprintf(stderr, "the topology chains hardly exercised rejections, repeated closed lists or rescaling\n"); return 1; }
     P = 2; C = 1;
     scenarioMcmc(5000, true, true, 9, 3, false);     // 4999 dependency levels
     scenarioMcmc(5000, false, true, 11, 2, false);

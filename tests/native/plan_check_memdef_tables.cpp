@@ -242,6 +242,23 @@ int main() {
         REQUIRE(c24.on.upper <= c8.on.upper + c24.on.unstored, "%d micro-operations left at cap 24, %d at cap 8 plus %d path steps", c24.on.upper, c8.on.upper, c24.on.unstored);
         REQUIRE(c24.slices <= c8.slices + 1 && c24.waves <= c8.waves + 1, "%d slices in %d waves at cap 24, %d in %d at cap 8", c24.slices, c24.waves, c8.slices, c8.waves);
     }
+    // chains that change the topology (plan_harness.h scenarioTopology) in this program's configuration: weighing for compression, caps 8 at first
+    // sight and 24 from the second coming, sub-runs taken from the chain's one index — with the feature and with the switch set
+    {
+        TopologyStats topology;
+        C = 2;
+        for (int on = 1; on >= 0; on--)
+            for (int T : {24, 48, 96}) {
+                P = T == 96 ? 40 : 129;
+                TopologyOptions o; o.repeats = true; o.classLimit = 65535; o.memStepCap = 8; o.memStepCapSeen = 24; o.initSeed = T == 24 ? 7 : 10; o.fixedChunk = 8; o.weights = true; o.memDefTables = on != 0;
+                o.caterpillar = T == 48;
+                const TopologyStats st = scenarioTopology(T, true, 40u + (unsigned)T, 60, o);
+                if (!on) REQUIRE(st.subRuns == 0, "%ld sub-runs with the switch set", st.subRuns);
+                topology.add(st);
+            }
+        topology.print("plan_check_memdef_tables");
+        REQUIRE(topology.compressed > 50 && topology.subRuns > 0 && topology.cladesAcrossMoves > 0 && topology.resets == 0, "%ld plans compressed, %ld sub-runs, %ld clades behind topology moves, %ld resets", topology.compressed, topology.subRuns, topology.cladesAcrossMoves, topology.resets);
+    }
     printDigest();
     printf("plan_check_memdef_tables: OK\n");
     return 0;

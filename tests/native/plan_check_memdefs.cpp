@@ -26,13 +26,14 @@ static int storedOperands(const WalkPlanner& pl, const VirtDef& v) {
     return n;
 }
 
-static void checkDefinitions(const Harness& h) {
+static void checkDefinitions(const Harness& h, int memCap = -1) {      // memCap: the cap in force (default: memStepCap)
+    if (memCap < 0) memCap = h.pl.memStepCap;
     for (int b = 0; b < h.nBuf; b++) {
         if (!h.pl.isVirtualKey(b)) continue;
         const VirtDef& v = h.pl.definition(b);
         const int n = storedOperands(h.pl, v);
-        if (n > 1 || (n == 1) != (v.memKey >= 0) || (n == 1 && v.nSteps > h.pl.memStepCap)) {
-            fprintf(stderr, "definition of buffer %d: %d stored operands, memKey %d, %d steps under a cap of %d [%s, list %ld]\n", b, n, v.memKey, v.nSteps, h.pl.memStepCap, g_where, g_list);
+        if (n > 1 || (n == 1) != (v.memKey >= 0) || (n == 1 && v.nSteps > memCap)) {
+            fprintf(stderr, "definition of buffer %d: %d stored operands, memKey %d, %d steps under a cap of %d [%s, list %ld]\n", b, n, v.memKey, v.nSteps, memCap, g_where, g_list);
             exit(1);
         }
         if (n == 1) {
@@ -180,7 +181,33 @@ static void scenarioOverwrite(int T, bool caterpillar, unsigned seed) {
     c.finish();
 }
 
+// what update() above asserts, behind every list of a topology chain (a closed list that has come twice is planned under memStepCapSeen)
+static void afterTopologyList(Harness& h) {
+    checkDefinitions(h, h.pl.memCapSeen());
+    if (h.pl.plannedTag == 0) return;
+    checkNoReadBack(*h.pl.planned);
+    countEvaluations(h, *h.pl.planned);
+}
+
 int main() {
+    // chains that change the topology (plan_harness.h scenarioTopology) with memory definitions as the engine sets them: 8 steps when a
+    // closed list is first seen, 24 when it comes again; definition caps 8 and 24, two and three hold slots, in slices and in one piece
+    {
+        TopologyStats topology;
+        const long seenBefore = g_memDefs;
+        for (unsigned seed : {1u, 2u})
+            for (int T : {9, 40, 150})
+                for (int initSeed : {7, 10, 1}) {                // (Harness::init: definition cap 8 / 24 with three hold slots, 8 with two)
+                    TopologyOptions o; o.memStepCap = 8; o.memStepCapSeen = 24; o.initSeed = initSeed; o.fixedChunk = (seed + (unsigned)T) % 2 ? 8 : 0; o.afterList = afterTopologyList;
+                    topology.add(scenarioTopology(T, true, 500 * seed + (unsigned)T + (unsigned)initSeed, 60, o));
+                }
+        { TopologyOptions o; o.memStepCap = 8; o.memStepCapSeen = 24; o.initSeed = 10; o.fixedChunk = 20; o.caterpillar = true; o.afterList = afterTopologyList; topology.add(scenarioTopology(80, true, 91, 60, o)); }
+        { TopologyOptions o; o.memStepCap = 8; o.memStepCapSeen = 24; o.initSeed = 10; o.fixedChunk = 8; o.mixStepLimit = true; o.afterList = afterTopologyList; topology.add(scenarioTopology(40, true, 92, 60, o)); }
+        for (int T : {40, 150}) { TopologyOptions o; o.memStepCap = 8; o.memStepCapSeen = 24; o.initSeed = 10; o.fixedChunk = 8; o.afterList = afterTopologyList; topologyWithoutPlanCache(T, 93u + (unsigned)T, 60, o); }
+        topology.print("plan_check_memdefs");
+        printf("  memory definitions seen in topology chains: %ld\n", g_memDefs - seenBefore);
+        if (g_memDefs - seenBefore < 1000 || topology.closedAgain < 10 || topology.rejectedTopology < 10) { fprintf(stderr, "the topology chains hardly met memory definitions\n"); return 1; }
+    }
     // (T, caterpillar): stored nodes of a full evaluation with and without memory definitions, same tree, same settings
     for (unsigned seed : {1u, 2u, 3u}) {
         for (int T : {3, 5, 8, 13, 40, 150, 400}) {

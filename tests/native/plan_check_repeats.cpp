@@ -319,6 +319,24 @@ int main() {
     for (int T : {24, 48})
         for (int chunk : {0, 8}) { scenarioRepeats(T, 300, seed, chunk, -1, true); seed++; }
     scenarioRepeats(24, 300, 77, 0, 5);
+    // chains that change the topology (plan_harness.h scenarioTopology): ONE index through the chain, every cached read-mode plan run compressed,
+    // a capacity small enough that the index is dropped in the middle of the chain — and one chain under the default capacity, which never is
+    {
+        TopologyStats topology;
+        C = 2;
+        for (unsigned s : {1u, 2u})
+            for (int T : {24, 48}) {
+                P = T == 24 ? 129 : 300;
+                TopologyOptions o; o.repeats = true; o.classLimit = std::max(1, P / 2); o.capacity = (size_t)T; o.memStepCap = 8; o.memStepCapSeen = s == 1 ? 24 : 0;
+                o.initSeed = s == 1 && T == 48 ? 10 : 7; o.fixedChunk = s == 1 ? 8 : 0; o.weights = true;      // (definition cap 24 on 48 tips, else 8: under 24, a 24-tip tree stores nothing)
+                topology.add(scenarioTopology(T, true, 700 * s + (unsigned)T, 60, o));
+            }
+        P = 129;
+        { TopologyOptions o; o.repeats = true; o.classLimit = 64; o.memStepCap = 8; o.memStepCapSeen = 24; o.initSeed = 7; o.fixedChunk = 8; o.weights = true;
+          const TopologyStats st = scenarioTopology(24, true, 33, 60, o); REQUIRE(st.resets == 0, "%ld resets under the default capacity", st.resets); topology.add(st); }
+        topology.print("plan_check_repeats");
+        REQUIRE(topology.compressed > 50 && topology.cladesAcrossMoves > 0 && topology.resets >= 4, "%ld plans compressed, %ld clades behind topology moves, %ld resets", topology.compressed, topology.cladesAcrossMoves, topology.resets);
+    }
     printf("  plans: %ld compressed, %ld of %ld definition runs taken (%ld without folding); table operands first %ld / second %ld, two-table nodes %ld, "
            "stored sibling of a table %ld, parked siblings freed %ld\n", g_plans, g_runsTaken, g_runsSeen, g_noFoldTaken, g_tabFirst, g_tabSecond, g_twoTables, g_memWithTable, g_unparked);
     REQUIRE(g_plans > 0 && g_runsTaken > 0 && g_noFoldTaken > 0, "nothing was compressed");

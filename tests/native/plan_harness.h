@@ -2,8 +2,8 @@
 //
 // The two worlds and list-order evaluation (truthOp), the index-level interpreters of the walk kernel's register model — runPlan for a
 // plan, runCompressed for a plan with class tables (planner.h RepeatPlan) —, checkUserLists, the Harness that drives a planner the way
-// the engine does, a tree with BEAST's buffer-index protocol, the alignments that repeat, and a digest of every plan the interpreters
-// execute (printDigest).  Included by exactly one source file per program: everything here has internal linkage.
+// the engine does, a tree with BEAST's buffer-index protocol and the two topology moves, the alignments that repeat, chains that change
+// the topology (scenarioTopology, topologyWithoutPlanCache), and a digest of every plan the interpreters execute (printDigest).  Included by exactly one source file per program: everything here has internal linkage.
 #pragma once
 #include <algorithm>
 #include <cassert>
@@ -459,9 +459,10 @@ struct Harness {
 
 // ---- a tree and BEAST's buffer-index protocol -------------------------------------------------------------------
 struct Tree {
-    int T; std::vector<int> left, right, parent;   // internal nodes T..2T-2; root = 2T-2
+    int T; std::vector<int> left, right, parent;   // internal nodes T..2T-2
+    int root = -1;                                 // 2T-2 as random() builds it; a topology move can make another node the root
     void random(int tips, std::mt19937& rng, bool caterpillar) {
-        T = tips; const int N = 2 * T - 1;
+        T = tips; const int N = 2 * T - 1; root = N - 1;
         left.assign(N, -1); right.assign(N, -1); parent.assign(N, -1);
         std::vector<int> roots;
         for (int i = 0; i < T; i++) roots.push_back(i);
@@ -489,13 +490,37 @@ struct Tree {
         const int N = 2 * T - 1;
         std::vector<int> depth(N, 0), order;
         for (int n = N - 2; n >= 0; n--) {}
-        std::vector<int> stack{N - 1};
+        std::vector<int> stack{root};
         std::vector<std::pair<int, int>> byDepth;
         while (!stack.empty()) { int n = stack.back(); stack.pop_back(); if (n < T) continue; byDepth.push_back({depth[n], n});
             depth[left[n]] = depth[right[n]] = depth[n] + 1; stack.push_back(left[n]); stack.push_back(right[n]); }
         std::stable_sort(byDepth.begin(), byDepth.end(), [](auto& a, auto& b) { return a.first > b.first; });
         for (auto& d : byDepth) order.push_back(d.second);
         return order;
+    }
+    // ---- topology moves (node numbers follow BEAST: a pruned node's parent travels with it) ----
+    int sibling(int n) const { const int p = parent[n]; return left[p] == n ? right[p] : left[p]; }
+    void replaceChild(int p, int from, int to) { (left[p] == from ? left[p] : right[p]) = to; parent[to] = p; }
+    bool below(int n, int top) const { for (int a = n; a >= 0; a = parent[a]) if (a == top) return true; return false; }
+    // narrow exchange: i and its uncle swap places (i's parent is not the root).  parentChanged / childrenChanged: the nodes a
+    // TreeChangedEvent names
+    void narrowExchange(int i, std::vector<int>& parentChanged, std::vector<int>& childrenChanged) {
+        const int p = parent[i], g = parent[p], u = sibling(p);
+        replaceChild(p, i, u); replaceChild(g, u, i);
+        parentChanged = {i, u}; childrenChanged = {p, g};
+    }
+    // prune and regraft: i's sibling takes the place of i's parent p (or becomes the root), p goes onto the branch above j (or
+    // becomes the root when j is).  j is outside what is pruned — the subtree of i and p itself — and is not the sibling, above which
+    // p already sits
+    void pruneRegraft(int i, int j, std::vector<int>& parentChanged, std::vector<int>& childrenChanged) {
+        const int p = parent[i], s = sibling(i), g = parent[p];
+        assert(!below(j, i) && j != p && j != s);
+        parentChanged = {s, p, j}; childrenChanged = {p};
+        if (g >= 0) { replaceChild(g, p, s); childrenChanged.push_back(g); } else { root = s; parent[s] = -1; }
+        const int jp = parent[j];
+        (left[p] == s ? left[p] : right[p]) = j;
+        if (jp >= 0) { replaceChild(jp, j, p); if (jp != g) childrenChanged.push_back(jp); } else { root = p; parent[p] = -1; }
+        parent[j] = p;
     }
 };
 
@@ -602,4 +627,204 @@ static inline bool plainRun(const Plan& plan, const PlanRun& run) {
         if (m.storeBuf >= 0 || m.k1 == PK_MEM || m.k2 == PK_MEM) return false;
     }
     return run.count > 0;
+}
+
+// ---- chains that change the topology ---------------------------------------------------------------------------------------
+// What a BEAST chain spends half of its tree proposals on: narrow exchange and prune-and-regraft (subtree slide, wide exchange and
+// Wilson-Balding are one of the two as far as the buffer protocol goes), with height moves, rejections, rescaling cycles, closed full
+// lists that come again, and random materialisations in between.  The truth world against the planned world, bitwise after every list.
+// The dirty set is the caller stand-in's (tools/host/tree_likelihood.cpp runTraversal): a node named by a tree-changed event is dirty
+// with both of its children, a dirty node that has a parent gets a new branch matrix in the other flip, and a node gets an operation
+// when the subtree of one of its children was updated.
+struct TopologyOptions {
+    bool virt = true, caterpillar = false, mixStepLimit = false;
+    int memStepCap = 0, memStepCapSeen = 0;
+    int fixedChunk = -1;                   // >= 0: as the engine plans (Harness::fixedChunk: the fast replay of a closed list needs it)
+    int initSeed = -1;                     // >= 0: Harness::init's seed (definition cap, hold slots, machines, top slices)
+    bool repeats = false;                  // tips from repeatingTips; every cached read-mode plan also runs compressed (runCompressed) over ONE
+    int classLimit = 0; size_t capacity = 0;   //   index kept through the chain, dropped at `capacity` as the engine drops it (prepareRepeats)
+    bool weights = false, memDefTables = true; // WalkPlanner::repeatWeights / memDefTables
+    void (*afterList)(Harness&) = nullptr; // a program's own assertions on the list the harness has just run
+    bool noPlanCache = false;              // WalkPlanner::cacheEnabled off: every list planned from scratch (topologyWithoutPlanCache)
+};
+struct TopologyStats {
+    long steps = 0, heightMoves = 0, narrow = 0, prune = 0, rejectedTopology = 0, rootToParent = 0, rootToSibling = 0, rootRestored = 0;
+    long closedLists = 0, closedAgain = 0, writeCycles = 0, lists = 0, cacheHits = 0;
+    long compressed = 0, subRuns = 0, resets = 0, cladesAcrossMoves = 0;      // (repeats) cladesAcrossMoves: clades the index took in behind accepted topology moves
+    void add(const TopologyStats& o) {
+        steps += o.steps; heightMoves += o.heightMoves; narrow += o.narrow; prune += o.prune; rejectedTopology += o.rejectedTopology;
+        rootToParent += o.rootToParent; rootToSibling += o.rootToSibling; rootRestored += o.rootRestored; closedLists += o.closedLists; closedAgain += o.closedAgain;
+        writeCycles += o.writeCycles; lists += o.lists; cacheHits += o.cacheHits; compressed += o.compressed; subRuns += o.subRuns; resets += o.resets; cladesAcrossMoves += o.cladesAcrossMoves;
+    }
+    void print(const char* program) const {
+        printf("%s topology chains: %ld steps (%ld lists): %ld height moves, %ld narrow exchanges, %ld prune-and-regrafts, %ld topology moves rejected; root changes: %ld to the pruned node's parent, "
+               "%ld to its sibling, %ld put back by a rejection; %ld closed full lists, %ld of them a second time, %ld write-mode cycles, %ld plan-cache hits; "
+               "%ld plans compressed (%ld sub-runs), %ld clades indexed behind topology moves, %ld index resets\n",
+               program, steps, lists, heightMoves, narrow, prune, rejectedTopology, rootToParent, rootToSibling, rootRestored, closedLists, closedAgain, writeCycles, cacheHits,
+               compressed, subRuns, cladesAcrossMoves, resets);
+    }
+};
+
+static inline TopologyStats scenarioTopology(int T, bool virt, unsigned seed, int steps, TopologyOptions o = TopologyOptions()) {
+    std::mt19937 rng(seed);
+    static char where[200];
+    snprintf(where, sizeof where, "topology T=%d virt=%d cat=%d seed=%u memcaps %d/%d chunk %d repeats=%d", T, (int)virt, (int)o.caterpillar, seed, o.memStepCap, o.memStepCapSeen, o.fixedChunk, (int)o.repeats);
+    g_where = where; g_list = 0;
+    REQUIRE(T >= 5, "a topology chain needs five tips");
+    TopologyStats st;
+    Tree tree; tree.random(T, rng, o.caterpillar);
+    const int N = 2 * T - 1;
+    Harness h; h.init(T, T + 2 * (T - 1), 2 * N, 2 * (T - 1), virt, o.initSeed >= 0 ? (unsigned)o.initSeed : seed + 1);
+    h.mixStepLimit = o.mixStepLimit; h.fixedChunk = o.fixedChunk;
+    h.pl.memStepCap = o.memStepCap; h.pl.memStepCapSeen = o.memStepCapSeen; h.pl.repeatWeights = o.weights; h.pl.memDefTables = o.memDefTables;
+    h.pl.cacheEnabled = !o.noPlanCache;
+    RepeatIndex idx;
+    if (o.repeats) {
+        const auto tips = repeatingTips(T, P, rng);
+        for (int t = 0; t < T; t++) {
+            h.truth.tips[(size_t)t] = tips[(size_t)t]; h.plan.tips[(size_t)t] = tips[(size_t)t];
+            h.compact[(size_t)t] = 1; h.pl.setCompactTip(t, true); h.pl.setLeafPartials(t, false);
+        }
+        idx.init(T, P, o.classLimit);
+        if (o.capacity) idx.setCapacity(o.capacity);
+        for (int t = 0; t < T; t++) idx.setTip(t, h.plan.tips[(size_t)t].data());
+    } else
+        for (int i = 0; i < T; i++) h.setTipStates(i);
+    for (int s = 0; s < 2 * N; s++) h.setMatrix(s);
+    Protocol pr(tree);
+    bool topologyPending = false;                      // an accepted topology move since the index last saw a list
+    // one list through the harness, the program's own checks, and — repeats — the compressed plan over the chain's index
+    auto run = [&](const std::vector<int>& ops) {
+        const long hits = h.pl.cacheHits + h.fastReplays;
+        h.update(ops, 7);
+        st.lists++; st.cacheHits += h.pl.cacheHits + h.fastReplays - hits;
+        if (o.afterList) o.afterList(h);
+        if (!o.repeats || h.pl.plannedTag == 0) return;
+        const Plan& plan = *h.pl.planned;
+        FoldMap fm;
+        if (!foldScaleFactors(plan, st.lists % 2 ? 32 : 4, fm)) return;       // (a list that rescales in write mode is left alone)
+        if (idx.overCapacity()) { idx.clear(); st.resets++; }
+        const size_t before = idx.size();
+        std::vector<RepeatRun> cand;
+        findRepeatRuns(plan, &fm, idx, true, cand, nullptr, h.pl.memDefTables);
+        if (topologyPending) { st.cladesAcrossMoves += (long)(idx.size() - before); topologyPending = false; }
+        if (cand.empty()) return;
+        RepeatPlan rp;
+        emitRepeatPlan(plan, cand, rp);
+        World a = h.plan, b = h.plan;                  // (the list has just run: its snapshot copies are idempotent)
+        runPlan(a, plan, h.partStart, h.partEnd, &fm);
+        runCompressed(b, rp, &fm, idx, h.partStart, h.partEnd);
+        for (int buf = 0; buf < h.nBuf; buf++) {
+            REQUIRE(a.partials[(size_t)buf].size() == b.partials[(size_t)buf].size(), "buffer %d", buf);
+            if (!a.partials[(size_t)buf].empty()) REQUIRE(memcmp(a.partials[(size_t)buf].data(), b.partials[(size_t)buf].data(), a.partials[(size_t)buf].size() * 8) == 0, "buffer %d differs from the uncompressed plan", buf);
+        }
+        st.compressed++; st.subRuns += rp.subRuns;
+    };
+    // the stand-in's traversal over the CURRENT tree: new matrices for the dirty nodes, operations up to the root
+    auto traverse = [&](std::vector<char> updateNode, int mode, bool level) {
+        for (int n = 0; n < N; n++)
+            if (updateNode[(size_t)n] && tree.parent[n] >= 0) { pr.mFlip[n] ^= 1; h.setMatrix(pr.mBuf(n)); }
+        std::vector<int> post; tree.postOrder(tree.root, post);
+        for (int n : post) if (updateNode[(size_t)tree.left[n]] || updateNode[(size_t)tree.right[n]]) updateNode[(size_t)n] = 2;      // (2: has an operation)
+        std::vector<int> nodes;
+        for (int n : (level ? tree.levelOrder() : post)) if (updateNode[(size_t)n] == 2) nodes.push_back(n);
+        for (int n : nodes) pr.pFlip[n] ^= 1;
+        std::vector<int> ops; pr.emit(nodes, mode, ops);
+        return ops;
+    };
+    auto dirtyWithChildren = [&](std::vector<char>& updateNode, int n) {
+        updateNode[(size_t)n] = 1;
+        if (n >= T) { updateNode[(size_t)tree.left[n]] = 1; updateNode[(size_t)tree.right[n]] = 1; }
+    };
+    // as scenarioMcmc begins: no scaling, then write mode, then read mode
+    for (int mode : {0, 1, 2}) run(traverse(std::vector<char>((size_t)N, 1), mode, mode != 0));
+    for (int step = 0; step < steps; step++) {
+        pr.store();
+        const Tree saved = tree;
+        std::vector<char> updateNode((size_t)N, 0);
+        // both directions of root change are part of every scenario, accepted: p onto the branch above the root, and a child of the root pruned
+        const bool forceUp = step == steps / 3, forceDown = step == (2 * steps) / 3;
+        const unsigned kind = forceUp || forceDown ? 2u : rng() % 4;      // 0, 1: heights;  2: prune and regraft;  3: narrow exchange
+        bool topology = false;
+        if (kind == 3) {
+            int i = -1;
+            for (int tries = 0; tries < 100 && i < 0; tries++) { const int x = (int)(rng() % (unsigned)N); if (x != tree.root && tree.parent[x] != tree.root) i = x; }
+            if (i >= 0) {
+                std::vector<int> pc, cc; tree.narrowExchange(i, pc, cc);
+                for (int n : pc) updateNode[(size_t)n] = 1;
+                for (int n : cc) dirtyWithChildren(updateNode, n);
+                st.narrow++; topology = true;
+            }
+        } else if (kind == 2) {
+            int i = -1, j = -1;
+            if (forceDown) { const int s = tree.left[tree.root] >= T ? tree.left[tree.root] : tree.right[tree.root]; i = tree.sibling(s); j = rng() % 2 ? tree.left[s] : tree.right[s]; }
+            for (int tries = 0; tries < 200 && j < 0; tries++) {
+                const int x = (int)(rng() % (unsigned)N), y = forceUp ? tree.root : (int)(rng() % (unsigned)N);
+                if (x == tree.root || (forceUp && tree.parent[x] == tree.root)) continue;
+                if (tree.below(y, x) || y == tree.parent[x] || y == tree.sibling(x)) continue;
+                i = x; j = y;
+            }
+            REQUIRE(j >= 0 || !(forceUp || forceDown), "no prune-and-regraft found");
+            if (j >= 0) {
+                const int before = tree.root, p = tree.parent[i];
+                std::vector<int> pc, cc; tree.pruneRegraft(i, j, pc, cc);
+                for (int n : pc) updateNode[(size_t)n] = 1;
+                for (int n : cc) dirtyWithChildren(updateNode, n);
+                st.prune++; topology = true;
+                if (tree.root != before) { if (tree.root == p) st.rootToParent++; else st.rootToSibling++; }
+            }
+        }
+        if (!topology) {
+            const int nChanges = 1 + (int)(rng() % 2);
+            for (int q = 0; q < nChanges; q++) dirtyWithChildren(updateNode, (int)(rng() % (unsigned)N));
+            st.heightMoves++;
+        }
+        const bool level = rng() % 2;
+        const int mode = step % 9 == 4 ? 1 : 2;          // every ninth proposal is a rescaling evaluation: everything, in write mode
+        if (mode == 1) { updateNode.assign((size_t)N, 1); st.writeCycles++; }
+        run(traverse(updateNode, mode, level));
+        const bool rejected = !(forceUp || forceDown) && rng() % 3 == 0;
+        if (rejected) {
+            if (tree.root != saved.root) st.rootRestored++;
+            pr.restore(); tree = saved;
+            if (topology) st.rejectedTopology++;
+        } else if (topology) topologyPending = true;
+        if (rng() % 4 == 0) { std::vector<int> xs; for (int q = 0; q < 3; q++) xs.push_back(T + (int)(rng() % (unsigned)(2 * (T - 1)))); h.materialise(xs); }
+        if (step % 4 == 2) {                             // a model move: every node dirty, a closed list on the current topology
+            pr.store();
+            const std::vector<int> ops = traverse(std::vector<char>((size_t)N, 1), 2, level);
+            run(ops); st.closedLists++;
+            if (rng() % 2) {                             // ... and the same list again (new values in the same matrix slots)
+                for (int n = 0; n < N; n++) if (tree.parent[n] >= 0 && rng() % 2) h.setMatrix(pr.mBuf(n));
+                run(ops); st.closedAgain++;
+                if (rng() % 2) run(ops);                 // (a third time: planned again at its second coming under memStepCapSeen, out of the cache now)
+            }
+        }
+        st.steps++;
+    }
+    std::vector<int> every; for (int b = T; b < h.nBuf; b++) every.push_back(b);
+    h.materialise(every);
+    h.compareAll();
+    REQUIRE(st.rootToParent > 0 && st.rootToSibling > 0, "root changes: %ld to the parent, %ld to the sibling", st.rootToParent, st.rootToSibling);
+    REQUIRE(st.narrow > 0 && st.prune >= 2 && st.closedLists > 0, "%ld narrow exchanges, %ld prune-and-regrafts, %ld closed lists", st.narrow, st.prune, st.closedLists);
+    if (o.repeats && o.capacity) REQUIRE(st.resets > 0, "the index never reached its capacity of %zu (%zu clades at the end)", o.capacity, idx.size());
+    return st;
+}
+
+// The same chain with the plan cache and with WalkPlanner::cacheEnabled off (the engine's BEAGLE_MI355_NO_PLAN_CACHE=1): no plan is replayed,
+// and yet every plan the interpreters execute is the same, byte for byte and in the same order (the digest), and a closed list is a kept
+// plan either way — what the engine does to kept plans only (folded reciprocals, class tables) must not depend on the switch.
+static inline void topologyWithoutPlanCache(int T, unsigned seed, int steps, TopologyOptions o) {
+    REQUIRE(o.fixedChunk >= 0, "random chunk sizes are drawn per plan() call");
+    const unsigned long long digest = g_digest; const long plans = g_digestPlans;
+    unsigned long long got[2]; long count[2], hits[2];
+    for (int off = 0; off < 2; off++) {
+        g_digest = 14695981039346656037ull; g_digestPlans = 0;
+        o.noPlanCache = off != 0;
+        hits[off] = scenarioTopology(T, true, seed, steps, o).cacheHits;
+        got[off] = g_digest; count[off] = g_digestPlans;
+    }
+    g_digest = digest; g_digestPlans = plans;
+    REQUIRE(hits[0] > 0 && hits[1] == 0, "%ld plan-cache hits, %ld with the cache off", hits[0], hits[1]);
+    REQUIRE(got[0] == got[1] && count[0] == count[1], "the plans differ without the plan cache: digest %016llx over %ld plans, %016llx over %ld with it", got[1], count[1], got[0], count[0]);
 }
