@@ -14,6 +14,7 @@ Layout (only what the hot path needs — SURVEY.md §8):
   nodeheight.py       node-height gradients and diagonal Hessians in one call (DiscreteTraitNodeHeightDelegate's caller side)
   nodeposteriors.py   marginal node state posteriors on the device in one call (NodePosteriorTreeLikelihood's caller side)
   placement.py        scores of attaching new sequences on every branch in one call (CheckPointTreeModifier's caller side)
+  regraft.py          scores of every regraft point of a pruned subtree in one call (GibbsPruneAndRegraft's caller side)
   substgradient.py    substitution-parameter gradients through differential matrices formed on the device (BranchSubstitutionParameterDelegate's caller side)
   eigensystems.py     eigen systems of a set of reversible models decomposed on the device in one call (SubstitutionModelDelegate's caller side)
   generators.py       branch matrices straight from generators, no eigen system, in one call (SubstitutionModelDelegate's caller side for models without one)
@@ -27,5 +28,5 @@ Layout (only what the hot path needs — SURVEY.md §8):
 
 The directory name contains a hyphen, so import it through the root-level shim: ``import beast_mcmc_amd``.
 """
-from . import ancestral, basta, beagle, completehistory, eigensystems, epochs, generators, markovjumps, mds, multipartition, nodeheight, nodeposteriors, placement, robustcounting, simulate, stochasticdollo, substgradient, tipmodels, treelikelihood     # noqa: F401
+from . import ancestral, basta, beagle, completehistory, eigensystems, epochs, generators, markovjumps, mds, multipartition, nodeheight, nodeposteriors, placement, regraft, robustcounting, simulate, stochasticdollo, substgradient, tipmodels, treelikelihood     # noqa: F401
 from .inputs import patterns, siterates, substmodel, synth, trees   # noqa: F401

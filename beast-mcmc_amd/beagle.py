@@ -124,7 +124,7 @@ ABI_SYMBOLS = ["beagleGetVersion", "beagleGetCitation", "beagleGetResourceList",
               ["beagle" + k for k in _PROTOS] + \
               ["beagleMi355SetStream", "beagleMi355CalculateRootLogLikelihoodsDevice", "beagleMi355Synchronize",
                "beagleMi355KernelTimer", "beagleMi355DeviceBytes", "beagleMi355WalkStats", "beagleMi355GradientStats", "beagleMi355GetPartialsBatch", "beagleMi355SampleAncestralStates", "beagleMi355SampleMarkovJumps", "beagleMi355SampleMarkovJumpsUniformized",
-               "beagleMi355SimulateSequences", "beagleMi355SimulateCompleteHistories", "beagleMi355RobustCounts", "beagleMi355SimulateUnconditionedCounts", "beagleMi355NodeHeightDerivatives", "beagleMi355UpdateDifferentialMatrices", "beagleMi355SetReversibleModels", "beagleMi355GetEigenDecomposition", "beagleMi355EigenStats", "beagleMi355UpdateTransitionMatricesFromGenerators", "beagleMi355GeneratorStats", "beagleMi355UpdateTransitionMatricesWithEpochs", "beagleMi355EpochStats", "beagleMi355NodePatternLikelihoods", "beagleMi355NodePatternStats", "beagleMi355NodePosteriors", "beagleMi355NodePosteriorStats", "beagleMi355PlacementScores", "beagleMi355PlacementStats", "beagleMi355SetTipEmission", "beagleMi355TipEmissionStats",
+               "beagleMi355SimulateSequences", "beagleMi355SimulateCompleteHistories", "beagleMi355RobustCounts", "beagleMi355SimulateUnconditionedCounts", "beagleMi355NodeHeightDerivatives", "beagleMi355UpdateDifferentialMatrices", "beagleMi355SetReversibleModels", "beagleMi355GetEigenDecomposition", "beagleMi355EigenStats", "beagleMi355UpdateTransitionMatricesFromGenerators", "beagleMi355GeneratorStats", "beagleMi355UpdateTransitionMatricesWithEpochs", "beagleMi355EpochStats", "beagleMi355NodePatternLikelihoods", "beagleMi355NodePatternStats", "beagleMi355NodePosteriors", "beagleMi355NodePosteriorStats", "beagleMi355PlacementScores", "beagleMi355PlacementStats", "beagleMi355RegraftScores", "beagleMi355RegraftStats", "beagleMi355SetTipEmission", "beagleMi355TipEmissionStats",
                "beagleMi355GetPartialsPinned", "beagleMi355GetSiteLogLikelihoodsPinned",
                "beagleMi355KernelTimerCalls", "beagleMi355WalkHealth", "beagleMi355RepeatStats", "beagleMi355RepeatSubRunStats", "beagleMi355TableOperandStats", "beagleMi355WalkLaunchInfo", "beagleMi355RootFusedCount", "beagleMi355SitePrefetchCount", "beagleMi355KernelTimerRestart", "beagleMi355GetDimensions", "beagleMi355GetCommUniqueId", "beagleMi355CommInit", "beagleMi355CommInfo", "beagleMi355CalculateRootLogLikelihoodsAllReduce"] + \
               ["beagleBasta" + k for k in ("AllocateCoalescentBuffers", "UpdatePartials", "AccumulatePartials", "GetBuffer", "GetBufferLength", "Stats", "SampleStates", "StatesStats",
@@ -859,6 +859,28 @@ class Beagle:
         """What placementScores has done (include/beagle_mi355.h beagleMi355PlacementStats)."""
         out = (C.c_long * 4)()
         self._check("placementStats", self._ext("beagleMi355PlacementStats", [C.c_int, C.POINTER(C.c_long)])(self.instance, out))
+        return {"calls": int(out[0]), "candidates": int(out[1]), "materialised": int(out[2]), "launches": int(out[3])}
+
+    def regraftScores(self, candidates, subtree, subtree_scale=NONE, categoryWeightsIndex=0, flags=0, pattern_log_ratios=False):
+        """Scores of hanging a pruned subtree at every candidate in one call (include/beagle_mi355.h beagleMi355RegraftScores).
+        ``candidates``: [candidateCount][7] rows as for placementScores; ``subtree``: the post-order buffer of the subtree's root;
+        ``subtree_scale``: the scale buffer with its accumulated factors, or NONE.  -> (scores [candidateCount], R [candidateCount, P]
+        or None, return code): the code is 0, or -8 (FLOATING_POINT) when some pattern's likelihood was 0 or not finite — the arrays
+        are written either way, NaN there; every other code raises BeagleException."""
+        rows = _i(candidates).reshape(-1, 7)
+        K = rows.shape[0]
+        scores = np.empty(K, dtype=np.float64)
+        ratios = np.empty((K, self.patternCount), dtype=np.float64) if pattern_log_ratios else None
+        f = self._ext("beagleMi355RegraftScores", [C.c_int, _IP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _DP, _DP])
+        rc = f(self.instance, _ip(rows), K, int(subtree), int(subtree_scale), int(categoryWeightsIndex), int(flags), _dp(scores), _dp(ratios))
+        if rc != 0 and rc != -8:
+            raise BeagleException("regraftScores", rc)
+        return scores, ratios, rc
+
+    def regraftStats(self):
+        """What regraftScores has done (include/beagle_mi355.h beagleMi355RegraftStats)."""
+        out = (C.c_long * 4)()
+        self._check("regraftStats", self._ext("beagleMi355RegraftStats", [C.c_int, C.POINTER(C.c_long)])(self.instance, out))
         return {"calls": int(out[0]), "candidates": int(out[1]), "materialised": int(out[2]), "launches": int(out[3])}
 
     def sampleMarkovJumps(self, nodes, branchTimes, branchRates, eigenIndex, categoryRatesIndex, categoryWeightsIndex,

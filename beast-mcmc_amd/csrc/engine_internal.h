@@ -19,6 +19,7 @@
 //   engine_nodepattern.cpp  the stochastic Dollo node-pattern likelihood over a post-order node list in one call
 //   engine_nodeposterior.cpp  marginal node state posteriors from resident pre- and post-order partials in one call
 //   engine_placement.cpp  scores of attaching new sequences at candidate points of the tree in one call
+//   engine_regraft.cpp    scores of hanging a pruned subtree at candidate points of the tree it was cut from in one call
 //   engine_stats.cpp     stream, synchronisation, kernel timer, counters
 // each of them argument checks, buffer bookkeeping and one call into the files above.
 // All arithmetic is in the .hip files; these files validate indices, resolve buffer indices to device pointers and enqueue
@@ -421,6 +422,8 @@ struct Instance {
     long statNodePosteriorCalls = 0, statNodePosteriorRows = 0, statNodePosteriorMaterialised = 0, statNodePosteriorLaunches = 0;   // (beagleMi355NodePosteriorStats)
     DevBuf placementDev;                                 // placement scores (engine_placement.cpp): placementLayout
     long statPlacementCalls = 0, statPlacementCandidates = 0, statPlacementMaterialised = 0, statPlacementLaunches = 0;   // (beagleMi355PlacementStats)
+    DevBuf regraftDev;                                   // regraft scores (engine_regraft.cpp): regraftLayout
+    long statRegraftCalls = 0, statRegraftCandidates = 0, statRegraftMaterialised = 0, statRegraftLaunches = 0;           // (beagleMi355RegraftStats)
 };
 
 extern std::mutex g_mutex;
@@ -686,6 +689,40 @@ template <class Collect> int makeResident(Instance* in, Collect&& collect, long*
     DEMOTE_FOLDED_TIPS(in);
     rc = collect(reads); if (rc) return rc;
     return reads.materialize();
+}
+// One candidate attachment of beagleMi355PlacementScores / beagleMi355RegraftScores, {parentPre, siblingPost, siblingMatrix, childPost,
+// upperMatrix, lowerMatrix, pendantMatrix}: its indices checked (only the sibling pair, together, and the upper matrix may be
+// BEAGLE_OP_NONE) and its three buffers fed to the read set — what both entry points call per row inside their makeResident collect.
+constexpr int ATTACH_FIELDS = 7;
+enum { ATTACH_PARENT_PRE, ATTACH_SIBLING_POST, ATTACH_SIBLING_MATRIX, ATTACH_CHILD_POST, ATTACH_UPPER_MATRIX, ATTACH_LOWER_MATRIX, ATTACH_PENDANT_MATRIX };
+inline int checkAttachment(const Instance* in, const int* c, ReadSet& reads) {
+    const int pre = c[ATTACH_PARENT_PRE], sib = c[ATTACH_SIBLING_POST], mSib = c[ATTACH_SIBLING_MATRIX], child = c[ATTACH_CHILD_POST];
+    if (badIndex(pre, in->partialsCount) || badIndex(child, in->partialsCount)) return BEAGLE_ERROR_OUT_OF_RANGE;
+    if ((sib == BEAGLE_OP_NONE) != (mSib == BEAGLE_OP_NONE)) return BEAGLE_ERROR_OUT_OF_RANGE;
+    if (sib != BEAGLE_OP_NONE && (badIndex(sib, in->partialsCount) || badIndex(mSib, in->matrixCount))) return BEAGLE_ERROR_OUT_OF_RANGE;
+    if (c[ATTACH_UPPER_MATRIX] != BEAGLE_OP_NONE && badIndex(c[ATTACH_UPPER_MATRIX], in->matrixCount)) return BEAGLE_ERROR_OUT_OF_RANGE;
+    if (badIndex(c[ATTACH_LOWER_MATRIX], in->matrixCount) || badIndex(c[ATTACH_PENDANT_MATRIX], in->matrixCount)) return BEAGLE_ERROR_OUT_OF_RANGE;
+    if (int bad = reads.pre(pre)) return bad;
+    if (sib != BEAGLE_OP_NONE) if (int bad = reads.post(sib)) return bad;
+    return reads.post(child);
+}
+// ... and its descriptor once the read set is resident (pendant: which of the call's distinct pendant matrices; slot: its row of
+// the launch).  BEAGLE_ERROR_OUT_OF_RANGE: a buffer that holds nothing.
+inline int fillAttachment(const Instance* in, const int* c, int pendant, int slot, mi355::PlacementCandidate* row) {
+    const size_t SS = (size_t)in->C * in->S * in->S;
+    *row = mi355::PlacementCandidate{};
+    row->pre = preOperand(in, c[ATTACH_PARENT_PRE]);
+    if (c[ATTACH_SIBLING_POST] != BEAGLE_OP_NONE) {
+        row->sib = postOperand(in, c[ATTACH_SIBLING_POST], &row->sibStates);
+        row->mSib = in->matrices + SS * c[ATTACH_SIBLING_MATRIX];
+        if (!row->sib) return BEAGLE_ERROR_OUT_OF_RANGE;
+    }
+    row->child = postOperand(in, c[ATTACH_CHILD_POST], &row->childStates);
+    row->mUp = c[ATTACH_UPPER_MATRIX] == BEAGLE_OP_NONE ? nullptr : in->matrices + SS * c[ATTACH_UPPER_MATRIX];
+    row->mLow = in->matrices + SS * c[ATTACH_LOWER_MATRIX];
+    row->pendant = pendant;
+    row->slot = slot;
+    return row->pre && row->child ? 0 : (int)BEAGLE_ERROR_OUT_OF_RANGE;
 }
 
 // ---- engine_sampling.cpp

@@ -13,8 +13,6 @@ namespace {
 
 constexpr size_t TABLE_SCRATCH_BYTES = 256ull << 20;       // most log-table scratch of one launch
 constexpr size_t COUNT_SCRATCH_BYTES = 256ull << 20;       // most count-table and query-code scratch of one launch
-constexpr int FIELDS = 7;                                  // ints per candidate
-enum { PARENT_PRE, SIBLING_POST, SIBLING_MATRIX, CHILD_POST, UPPER_MATRIX, LOWER_MATRIX, PENDANT_MATRIX };
 
 int placementScores(Instance* in, const int* cands, int candidateCount, int wIdx, const int* sitePatterns, int siteCount,
                     const unsigned char* queryCodes, int queryCount, const double* codeTable, int codeCount, double* outScores,
@@ -27,16 +25,7 @@ int placementScores(Instance* in, const int* cands, int candidateCount, int wIdx
     long unstoredAtEntry = 0;
     int rc = makeResident(in, [&](ReadSet& reads) -> int {
         for (int k = 0; k < candidateCount; k++) {
-            const int* c = cands + FIELDS * k;
-            const int pre = c[PARENT_PRE], sib = c[SIBLING_POST], mSib = c[SIBLING_MATRIX], child = c[CHILD_POST];
-            if (badIndex(pre, in->partialsCount) || badIndex(child, in->partialsCount)) return BEAGLE_ERROR_OUT_OF_RANGE;
-            if ((sib == BEAGLE_OP_NONE) != (mSib == BEAGLE_OP_NONE)) return BEAGLE_ERROR_OUT_OF_RANGE;
-            if (sib != BEAGLE_OP_NONE && (badIndex(sib, in->partialsCount) || badIndex(mSib, in->matrixCount))) return BEAGLE_ERROR_OUT_OF_RANGE;
-            if (c[UPPER_MATRIX] != BEAGLE_OP_NONE && badIndex(c[UPPER_MATRIX], in->matrixCount)) return BEAGLE_ERROR_OUT_OF_RANGE;
-            if (badIndex(c[LOWER_MATRIX], in->matrixCount) || badIndex(c[PENDANT_MATRIX], in->matrixCount)) return BEAGLE_ERROR_OUT_OF_RANGE;
-            if (int bad = reads.pre(pre)) return bad;
-            if (sib != BEAGLE_OP_NONE) if (int bad = reads.post(sib)) return bad;
-            if (int bad = reads.post(child)) return bad;
+            if (int bad = checkAttachment(in, cands + ATTACH_FIELDS * k, reads)) return bad;
         }
         return 0;
     }, &unstoredAtEntry);
@@ -49,7 +38,7 @@ int placementScores(Instance* in, const int* cands, int candidateCount, int wIdx
     std::map<int, int> pendantOf;
     std::vector<int> slots;
     for (size_t k = 0; k < K; k++) {
-        const int m = cands[FIELDS * k + PENDANT_MATRIX];
+        const int m = cands[ATTACH_FIELDS * k + ATTACH_PENDANT_MATRIX];
         if (pendantOf.emplace(m, (int)slots.size()).second) slots.push_back(m);
     }
     // candidates per launch: the descriptors fit a quarter of the staging ring, the log table its budget, the grid its second
@@ -74,7 +63,6 @@ int placementScores(Instance* in, const int* cands, int candidateCount, int wIdx
     CallTimer timer(in);
     rc = timer.start();
     const double* weights = in->weights + (size_t)wIdx * in->C;
-    const size_t SS = C * S * S;
     int launches = 0;
     if (!rc) { mi355::launchPendantTables(live(in), in->matrices, dSlots, (int)slots.size(), dCodeTable, in->S, in->C, codeCount, dPendant); launches++; }
 
@@ -94,20 +82,9 @@ int placementScores(Instance* in, const int* cands, int candidateCount, int wIdx
         const size_t m = std::min(kChunk, K - b);
         rows.assign(m, mi355::PlacementCandidate{});
         for (size_t e = 0; e < m; e++) {
-            const int* c = cands + FIELDS * (b + e);
-            mi355::PlacementCandidate& row = rows[e];
-            row.pre = preOperand(in, c[PARENT_PRE]);
-            if (c[SIBLING_POST] != BEAGLE_OP_NONE) {
-                row.sib = postOperand(in, c[SIBLING_POST], &row.sibStates);
-                row.mSib = in->matrices + SS * c[SIBLING_MATRIX];
-                if (!row.sib) rc = BEAGLE_ERROR_OUT_OF_RANGE;
-            }
-            row.child = postOperand(in, c[CHILD_POST], &row.childStates);
-            row.mUp = c[UPPER_MATRIX] == BEAGLE_OP_NONE ? nullptr : in->matrices + SS * c[UPPER_MATRIX];
-            row.mLow = in->matrices + SS * c[LOWER_MATRIX];
-            row.pendant = pendantOf[c[PENDANT_MATRIX]];
-            row.slot = (int)e;
-            if (!row.pre || !row.child) rc = BEAGLE_ERROR_OUT_OF_RANGE;
+            const int* c = cands + ATTACH_FIELDS * (b + e);
+            rc = fillAttachment(in, c, pendantOf[c[ATTACH_PENDANT_MATRIX]], (int)e, &rows[e]);
+            if (rc) break;
         }
         if (rc) break;
         void* dRows = nullptr;

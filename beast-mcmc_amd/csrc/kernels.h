@@ -730,6 +730,32 @@ void launchPlacementCounts(hipStream_t stream, const int* sitePatterns, const ui
 int  placementSegments(int P, int X);
 void launchPlacementScores(hipStream_t stream, const int* counts, const double* table, int nQueries, int nCands, int P, int X, double* partial,
                            double* scores);
+// ---- regraft scores (kernels_regraft.hip; beagleMi355RegraftScores) -------------------------------------------------------
+// The candidates are PlacementCandidate rows (pendant: which pendant vector of the call, launchRegraftPendants); what is attached is a
+// pruned subtree's post-order partials, so there is no code table: one number per (candidate, pattern).
+constexpr int REGRAFT_MAX_CANDIDATES = 65535;        // candidates of one launch (the grid's second dimension)
+constexpr int REGRAFT_SEGMENT = 64;                 // patterns one accumulator of the weighted pattern sum runs over
+// doubles of one pendant vector q [C][P][S] in the instance's partials layout (T32: whole tiles of 32 patterns)
+inline size_t regraftPendantDoubles(int P, int S, int C, bool tiled) { return (size_t)C * S * (tiled ? (size_t)((P + 31) >> 5) * 32 : (size_t)P); }
+// out [nSlots] vectors of regraftPendantDoubles: q[m][c][p][a] = sum_b M_{slots[m]},c[a][b] * subtree_c,p(b), b ascending from 0.0, in
+// the layout of the instance's partials, so that the main stage streams it as a fourth partials buffer.  subtree: partials, or
+// (subtreeStates) compact states — 1.0 at the state, all ones when it is >= S.
+void launchRegraftPendants(hipStream_t stream, const double* matrices, const int* dSlots, int nSlots, const void* subtree, bool subtreeStates,
+                           int P, int S, int C, bool tiled, double* out);
+// Per candidate k, pattern p and category c, with u, t, e as for launchPlacementTable and q the candidate's pendant vector (every sum
+// ascending from 0.0):   D += w_c * sum_a e(a),   N += w_c * sum_a e(a) q_c(a);
+// ratios [slot][P] = log(N / D) + logscale[p] — NaN where D is 0 or not finite (and *fpError = 1 unless patternWeights[p] is 0: no score
+// uses it); -inf where N is 0.  scale (nullptr: no term): P log factors, or (scaleRaw) P factors whose logarithm is taken.
+// false: too many candidates, or the state count needs more LDS than a workgroup can have.
+bool launchRegraftRatios(hipStream_t stream, const PlacementCandidate* dCands, int nCands, const double* catWeights, const double* pendants,
+                         const double* scale, bool scaleRaw, const double* patternWeights, int P, int S, int C, bool tiled, double* ratios,
+                         unsigned* fpError);
+int  regraftPatternBlock(int S);                     // patterns a workgroup of launchRegraftRatios takes (0: none fit)
+// scores [nCands] = sum_p patternWeights[p] * ratios[k][p], patterns of weight 0 left out: per segment of REGRAFT_SEGMENT patterns
+// ascending from 0.0 into partial [regraftSegments][nCands], then the segments ascending from 0.0 (two launches)
+inline int regraftSegments(int P) { return (P + REGRAFT_SEGMENT - 1) / REGRAFT_SEGMENT; }
+void launchRegraftScores(hipStream_t stream, const double* ratios, const double* patternWeights, int nCands, int P, double* partial,
+                         double* scores);
 // ---- sequence simulation (kernels_simulate.hip; beagleMi355SimulateSequences) -------------------------------------------
 // One row of the pre-order node list, resolved on the host: its branch matrix [C][S][S] (nullptr at the root), the scratch row
 // ("slot") its states go to and the slot of its parent (-1 at the root); parentIsPrev: the parent is the row right before it, whose

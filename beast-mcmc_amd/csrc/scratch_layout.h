@@ -1,5 +1,5 @@
 // scratch_layout.h — what is inside the samplers' grow-on-demand device buffers (engine_internal.h Instance::ancestralDev, jumpDev,
-// uniformDev, nodePatternDev, nodePosteriorDev, placementDev, eventDev, simulateDev, robustDev, historyDev): a carver that lays sections out one after another, and per
+// uniformDev, nodePatternDev, nodePosteriorDev, placementDev, regraftDev, eventDev, simulateDev, robustDev, historyDev): a carver that lays sections out one after another, and per
 // buffer a layout that names its sections from plain integers.  Host only, plain C++17, no HIP: tests/native/scratch_layout_check.cpp
 // (NodePatternLayout: node_pattern_layout_check.cpp) compiles it alone and checks every layout's offsets, order and alignment.  The .cpp files resolve sections to pointers (at / as) and grow the
 // buffer to bytes(); they keep no offset arithmetic.
@@ -105,6 +105,19 @@ struct PlacementLayout : Carver {
         counts = take<int>(queries * P * X); align(256);
         sitePatterns = take<int>(sites); slots = take<int>(pendants); align(256);
         codes = take<uint8_t>(queries * sites); align(256);
+        error = take<unsigned>(1);
+    }
+};
+
+// regraftDev: pendant vectors [pendants][perVector] | log ratios [candidates][P] (outPatternLogRatios) | segment sums
+//             [segments][candidates] | scores [candidates] | (256) pendant matrix slots [pendants] | (256) error word
+//             — candidates: those of one launch; perVector: kernels.h regraftPendantDoubles, a multiple of 4 doubles
+struct RegraftLayout : Carver {
+    Doubles pendants, ratios, partial, scores; Ints slots; Section<unsigned> error;
+    RegraftLayout(size_t candidates, size_t pendantCount, size_t perVector, size_t segments, size_t P) {
+        pendants = take<double>(pendantCount * perVector); align(256);
+        ratios = take<double>(candidates * P); partial = take<double>(segments * candidates); scores = take<double>(candidates); align(256);
+        slots = take<int>(pendantCount); align(256);
         error = take<unsigned>(1);
     }
 };

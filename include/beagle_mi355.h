@@ -671,6 +671,49 @@ int beagleMi355PlacementScores(int instance, const int* candidates, int candidat
 /* out4 = {beagleMi355PlacementScores calls since creation, candidates they covered, operands materialised for them, kernel launches}.
  * Operands materialised: the distinct unstored buffers among a call's listed ones when it arrived. */
 int beagleMi355PlacementStats(int instance, long* out4);
+/* Regraft scores: for every candidate attachment k, lnL(T' with a pruned subtree hung at k) - lnL(T'), in ONE call behind a pruning pass
+ * and a pre-order pass over T', the tree without the subtree.  The reference's Gibbs tree operator (src/dr/evomodel/operators/
+ * GibbsPruneAndRegraft.java: gibbsProposal :89-160, prunedGibbsProposal :162-269) edits the tree twice and evaluates the whole
+ * likelihood once per candidate; everything those likelihoods are made of is resident after one gradient pass over T'.
+ *   candidates [candidateCount][7] = {parentPre, siblingPost, siblingMatrix, childPost, upperMatrix, lowerMatrix, pendantMatrix}: the
+ *          rows of beagleMi355PlacementScores, with the same rules — siblingPost and siblingMatrix may both be BEAGLE_OP_NONE,
+ *          upperMatrix may be BEAGLE_OP_NONE, {pre(root), NONE, NONE, post(root), NONE, P(x), pendant} is an attachment above the root;
+ *          siblingPost and childPost: compact tip states, a tip's partials, a tip behind an emission table, an internal node's
+ *          partials, stored or left unstored by the 4-state walk.  pendantMatrix: P(attachment point -> the subtree's root); the Gibbs
+ *          operator keeps the height of the subtree's parent, so its list names one.
+ *   subtreeBuffer: the post-order buffer of the pruned subtree's root, of any of those kinds (a pruned tip: its compact states, a
+ *          state >= stateCount counting as all ones).
+ *   subtreeCumulativeScaleIndex: a scale buffer that holds the subtree's accumulated scale factors, or BEAGLE_OP_NONE.
+ *   flags: none is defined; it must be 0.
+ * With s, u, t, l and e as for beagleMi355PlacementScores and w the weights of categoryWeightsIndex, per candidate k, pattern p,
+ * category c:
+ *   q_c(a) = sum_b Mpend_c[a][b] post_sub,c,p(b);   D_p = sum_c w_c sum_a e_c(a);   N_p = sum_c w_c sum_a e_c(a) q_c(a);
+ *   R_k[p] = log(N_p / D_p) + logscale_sub[p];      score[k] = sum_p patternWeight_p R_k[p].
+ * logscale_sub is there only when a scale buffer is named: the value beagleGetLogScaleFactors returns for it, whichever form the
+ * instance keeps.  lnL(T' with the subtree at k) = lnL(T') + score[k].  Every per-pattern scale factor of the three partials of T'
+ * cancels in N / D, so rescaled instances work as they are.  The pattern weights are the instance's own (beagleSetPatternWeights).
+ * The score is summed over segments of 64 patterns, each ascending from 0.0, then the segments ascending from 0.0; a pattern of
+ * weight 0 is left out, so its -inf or NaN never reaches the score.  The order depends on patternCount alone: two calls, a permuted
+ * or split candidate list and any chunk size give the same bits.
+ *   outScores [candidateCount];  outPatternLogRatios (may be NULL) [candidateCount][patternCount] = R.
+ * N = 0 gives -inf (an impossible attachment, no error).  A pattern of a candidate whose D is 0 or not finite makes the call return
+ * BEAGLE_ERROR_FLOATING_POINT after everything is written: that R is NaN, and so is every score that uses it (at a pattern of weight 0
+ * no score does: that R is NaN and the call succeeds).
+ * Nothing of the instance changes (buffers that the 4-state walk left unstored are materialised, as for beagleGetPartials; tips with a
+ * folded emission table get their partials; a held-back pre-order list runs first).  Candidates are cut into launches whose log ratios
+ * stay within 256 MiB (BEAGLE_MI355_REGRAFT_CHUNK=<candidates> in the environment, read at every call: tests).  2..255 states, any
+ * category count.
+ * BEAGLE_ERROR_OUT_OF_RANGE, before anything runs, for a bad buffer, matrix, weights or scale index, a buffer never written (the
+ * subtree's included), a sibling named without its matrix, flags != 0, a NULL input, a count < 1, or an instance without pattern
+ * weights.  BEAGLE_ERROR_NO_IMPLEMENTATION — deliberately out of scope — on an instance with pattern partitions, on an instance with
+ * BASTA buffers, on a sharded handle, and with more than 255 states.  BEAGLE_ERROR_OUT_OF_MEMORY when the scratch cannot be had (a
+ * pendant vector of the subtree's size per DISTINCT pendant matrix).  An extension: no BEAST class calls it today. */
+int beagleMi355RegraftScores(int instance, const int* candidates, int candidateCount, int subtreeBuffer,
+                             int subtreeCumulativeScaleIndex, int categoryWeightsIndex, int flags, double* outScores,
+                             double* outPatternLogRatios);
+/* out4 = {beagleMi355RegraftScores calls since creation, candidates they covered, operands materialised for them, kernel launches}.
+ * Operands materialised: the distinct unstored buffers among a call's listed ones (the subtree's included) when it arrived. */
+int beagleMi355RegraftStats(int instance, long* out4);
 /* Markov jumps: ONE call that draws the ancestral states as beagleMi355SampleAncestralStates does and, for every register k, row
  * r >= 1 and pattern p, forms the expected number of registered substitutions (a count register) or the expected reward (a reward
  * register) on row r's branch, conditioned on the drawn parent and child states — what MarkovJumpsBeagleTreeLikelihood.hookCalculation
